@@ -80,7 +80,16 @@ def parse():
                     help="drop the per-iteration statistics (Result.Statistics) in the timed region; by default they are "
                          "delivered, as the reference's callers read them (keyframe_tracker.cpp:167, "
                          "constraint_proposal_voter.cpp:128)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last one -- what a caller of the timed path receives, "
+                         "per-iteration statistics included -- as DIR/<name>.npy (float64, rank 0; a fixed seeded sample of the "
+                         "pairs when all of them would exceed 64 MB): the inputs are seeded, so two builds run with the same "
+                         "arguments can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.plumbing_only or args.tile_shard):
+        ap.error("--dump-outputs writes the results of the default workload's timed steps: not with --plumbing-only or --tile-shard")
     if args.counter_leg:
         args.no_extras = args.no_cpu_baseline = True
     if args.no_extras:
@@ -390,6 +399,8 @@ def main():
     elapsed = time.perf_counter() - t0
     if T == 1:
         trk.marker(2)
+    if args.dump_outputs and rank == 0:  # (before anything else reuses the result structs the last step was collected into)
+        dump_outputs(args.dump_outputs, kept, B)
     region_check = None if args.counter_leg else check_timed_region(capi, synth, cfg, device, kept, refs, curb)
     alg_bytes = sum(c[0] for c in col)
     discarded_bytes = sum(c[4] for c in col)
@@ -693,6 +704,73 @@ def check_timed_region(capi, synth, cfg, device, kept, refs, curb, n_samples=48)
     if n == 0 or identical != n:
         raise SystemExit("bench.py: a result of the timed region differs from the same pair's single match(): " + json.dumps(out))
     return out
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+DUMP_SAMPLE_SEED = 20131103
+
+
+def dump_outputs(out_dir, kept, n_pairs, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the results of the LAST timed step as its host threads collected them (the result structs
+    dvo_amd_match_wait filled), as out_dir/<name>.npy in float64, matrices oriented as capi.Result gives them.  Per pair:
+    transformation, information, log_likelihood and the level statistics; per delivered iteration the iteration_* rows, those
+    of dumped pair n at iteration_offset[n] : iteration_offset[n + 1].  Run-time bookkeeping (ticks, passes, bytes) is not an
+    output and is left out.  pair[n] is the dumped pair's position in the step: all of them in order when they fit in `limit`
+    bytes, otherwise the longest prefix of a seeded permutation of the step that fits, in step order."""
+    from dvo_slam_amd import capi
+
+    by_pair = [None] * n_pairs
+    for entry in kept:
+        if entry is not None:
+            ix, raw = entry
+            for k, i in enumerate(ix):
+                by_pair[i] = raw[k]
+    if any(r is None for r in by_pair):
+        raise SystemExit("bench.py --dump-outputs: the last timed step did not return every pair")
+    empty = np.zeros(0, dtype=np.dtype(capi.CIterationStats))
+    its = []
+    for r in by_pair:
+        if not r.iterations or r.n_iterations == 0:  # per-iteration statistics dropped (--no-stats)
+            its.append(empty)
+            continue
+        a = np.ctypeslib.as_array(r.iterations, shape=(r.n_iterations,))
+        order = [L.first_iteration + k for L in r.levels[:r.n_levels] for k in range(L.n_iterations)]
+        its.append(a[np.array(order, dtype=np.int64)])
+    n_levels = by_pair[0].n_levels
+    # float64 values written per iteration row, and per pair (pair, offset, transformation, information, likelihood, levels)
+    it_fields = 1 + 1 + 1 + 2 + 4 + 1 + 1 + 6 + 36 + 16 + 16
+    pair_bytes = 8 * np.array([2 + 16 + 36 + 1 + 5 * n_levels + it_fields * len(a) for a in its])
+    budget = limit - 2**16  # (the .npy headers)
+    if pair_bytes.sum() <= budget:
+        take = np.arange(n_pairs)
+    else:
+        perm = np.random.default_rng(DUMP_SAMPLE_SEED).permutation(n_pairs)
+        take = np.sort(perm[:int(np.searchsorted(np.cumsum(pair_bytes[perm]), budget, side="right"))])
+    sel = [by_pair[i] for i in take]
+    rows = np.concatenate([its[i] for i in take]) if len(take) else empty
+    out = {
+        "pair": take,
+        "transformation": [np.array(r.transformation[:]).reshape(4, 4).T for r in sel],
+        "information": [np.array(r.information[:]).reshape(6, 6).T for r in sel],
+        "log_likelihood": [r.loglik for r in sel],
+        "iteration_offset": np.concatenate([[0], np.cumsum([len(its[i]) for i in take])]),
+        "iteration_id": rows["id"],
+        "iteration_valid_constraints": rows["valid_constraints"],
+        "iteration_tdist_loglik": rows["tdist_loglik"],
+        "iteration_tdist_mean": rows["tdist_mean"],
+        "iteration_tdist_precision": rows["tdist_precision"].reshape(-1, 2, 2).transpose(0, 2, 1),
+        "iteration_prior_loglik": rows["prior_loglik"],
+        "iteration_has_increment": rows["has_increment"],
+        "iteration_increment": rows["increment"],
+        "iteration_information": rows["information"].reshape(-1, 6, 6).transpose(0, 2, 1),
+        "iteration_estimate": rows["estimate"].reshape(-1, 4, 4).transpose(0, 2, 1),
+        "iteration_initial": rows["initial"].reshape(-1, 4, 4).transpose(0, 2, 1),
+    }
+    for field in ("id", "max_valid_pixels", "valid_pixels", "termination", "n_iterations"):
+        out["level_" + field] = [[getattr(L, field) for L in r.levels[:n_levels]] for r in sel]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, value in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(value, dtype=np.float64))
 
 
 def stats_variant(run_steps, B, args, with_stats):

@@ -42,17 +42,37 @@ def _host_tag() -> str:
     return hashlib.sha1(model.encode()).hexdigest()[:10]
 
 
+_native_elsewhere = {}  # host tag -> a timing build this process compiled outside the tree
+
+
 def build_native() -> str:
     """The TIMING build of the same source with the reference's own flags, `-O3 -march=native` + SSE
-    (dvo_core/CMakeLists.txt:35-40), compiled on the host that runs it.  Only bench.py's cpu_baseline legs use it; the
-    parity checker is always the `build()` flavour (-mno-fma -ffp-contract=off -frounding-math: portable bits)."""
-    path = os.path.join(_HERE, "_build", f"libdvo_oracle_native_{_host_tag()}.so")
+    (dvo_core/CMakeLists.txt:35-40), compiled on the host that runs it.  Only bench.py's cpu_baseline legs (and one test) use it;
+    the parity checker is always the `build()` flavour (-mno-fma -ffp-contract=off -frounding-math: portable bits).
+    __graft_entry__.build() makes it in oracle/_build/ for the host the build runs on, so that a run there writes nothing into the
+    tree.  Where that copy is missing or stale and oracle/_build/ cannot be written (a read-only checkout on another CPU model),
+    it is compiled into a private temporary directory instead."""
+    tag = _host_tag()
+    path = os.path.join(_HERE, "_build", f"libdvo_oracle_native_{tag}.so")
     src = [os.path.join(_HERE, f) for f in ("dvo_oracle.c", "dvo_oracle.h")]
-    if not os.path.exists(path) or any(os.path.getmtime(s) > os.path.getmtime(path) for s in src):
+    if os.path.exists(path) and all(os.path.getmtime(s) <= os.path.getmtime(path) for s in src):
+        return path
+    if tag in _native_elsewhere:
+        return _native_elsewhere[tag]
+    try:
         os.makedirs(os.path.dirname(path), exist_ok=True)
-        subprocess.run([os.environ.get("CC", "gcc"), "-O3", "-march=native", "-msse3", "-fPIC", "-std=gnu11", "-shared", "-o",
-                        path + ".tmp", src[0], "-lm", "-lpthread"], check=True)
-        os.replace(path + ".tmp", path)
+        writable = os.access(os.path.dirname(path), os.W_OK)
+    except OSError:
+        writable = False
+    if not writable:
+        import tempfile
+
+        path = os.path.join(tempfile.mkdtemp(prefix="dvo_oracle_native_"), os.path.basename(path))
+    subprocess.run([os.environ.get("CC", "gcc"), "-O3", "-march=native", "-msse3", "-fPIC", "-std=gnu11", "-shared", "-o",
+                    path + ".tmp", src[0], "-lm", "-lpthread"], check=True)
+    os.replace(path + ".tmp", path)
+    if not writable:
+        _native_elsewhere[tag] = path
     return path
 
 

@@ -244,18 +244,30 @@ def test_the_segment_tables_are_the_documented_ones(capi, synth, frames):
 
 
 def test_trackers_created_back_to_back_are_spread_over_the_hardware_queues(capi, capsys):
-    """The runtime maps streams onto its four hardware queues and a hardware queue runs one kernel at a time: how the trackers of a
-    GPU are spread over them decides up to a third of a batch's throughput (profiles/r05_stream_queue_assignment_ab.txt: 55-56 k
-    pairs/s for six trackers two to a queue with neighbours together, 47 k on two queues, 39 k on one).  The library takes the stream
-    the runtime deals it (a context that chose among probed candidates made the common case worse); this is the diagnostic that shows
-    the outcome -- the hardware queue of a tracker's stream, asked of the GPU -- on six trackers created back to back, as
-    INTEGRATION.md advises: no queue may carry more than two of them."""
+    """The runtime maps streams onto its hardware queues (GPU_MAX_HW_QUEUES, four by default) and a hardware queue runs one kernel at
+    a time: how the trackers of a GPU are spread over them decides up to a third of a batch's throughput
+    (profiles/r05_stream_queue_assignment_ab.txt: 55-56 k pairs/s for six trackers two to a queue with neighbours together, 47 k on
+    two queues, 39 k on one).  The library takes the stream the runtime deals it (a context that chose among probed candidates made
+    the common case worse); this is the diagnostic that shows the outcome -- the hardware queue of a tracker's stream, asked of the
+    GPU -- on six trackers created back to back, as INTEGRATION.md advises: no queue may carry more of them than an even spread puts
+    on it (two of six on the default four queues).  They are created in a fresh process: the streams this session's other tests
+    still hold would shift where the runtime puts the next ones, as streams created between the trackers would."""
+    import json
+    import os
+    import subprocess
+    import sys
     from collections import Counter
 
-    cfg = capi.Config(FirstLevel=3, LastLevel=0)
-    trackers = [capi.DenseTracker(cfg) for _ in range(6)]
-    queues = [t.hw_queue() for t in trackers]
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import json\nfrom dvo_slam_amd import capi\n"
+            "trackers = [capi.DenseTracker(capi.Config(FirstLevel=3, LastLevel=0)) for _ in range(6)]\n"
+            "print(json.dumps([t.hw_queue() for t in trackers]))\n")
+    out = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code], cwd=root,
+                         capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-3000:]
+    queues = json.loads(out.stdout.strip().splitlines()[-1])
+    n_hw_queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
     with capsys.disabled():
-        print(f"\n[hardware queues] six trackers created back to back: pipe << 3 | queue = {queues}")
-    assert all(0 <= q < 64 for q in queues)
-    assert max(Counter(queues).values()) <= 2
+        print(f"\n[hardware queues] six trackers created back to back on {n_hw_queues} hardware queues: pipe << 3 | queue = {queues}")
+    assert len(queues) == 6 and all(0 <= q < 64 for q in queues)
+    assert max(Counter(queues).values()) <= -(-6 // n_hw_queues)

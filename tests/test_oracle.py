@@ -15,6 +15,22 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def test_native_timing_build_needs_no_write_access_to_the_tree(orc, monkeypatch):
+    """bench.py's CPU baseline runs the -march=native build of the oracle.  A checkout it cannot write to, on a CPU model no build
+    ran on, must still get one: compiled outside the tree, once per process, and loadable."""
+    oracle_dir = os.path.dirname(os.path.abspath(orc.__file__))
+    real_access = os.access
+    monkeypatch.setattr(orc, "_host_tag", lambda: "host-without-a-build")
+    monkeypatch.setattr(orc, "_native_elsewhere", {})
+    monkeypatch.setattr(os, "access", lambda p, mode, **kw: False if os.path.abspath(p).startswith(oracle_dir) else
+                        real_access(p, mode, **kw))
+    path = orc.build_native()
+    assert not os.path.abspath(path).startswith(os.path.dirname(oracle_dir) + os.sep), path
+    assert os.path.exists(path) and orc.build_native() == path
+    assert not os.path.exists(os.path.join(oracle_dir, "_build", os.path.basename(path)))
+    assert hasattr(C.CDLL(path), "orc_default_config")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # SE(3): Sophus SE3d closed forms (dense_tracking.cpp:147,238,259-263,371)
 # ---------------------------------------------------------------------------------------------------------------------
