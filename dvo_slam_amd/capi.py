@@ -36,7 +36,8 @@ EXPORTS = [
     "dvo_amd_match_submit", "dvo_amd_match_wait", "dvo_amd_match_poll", "dvo_amd_debug_next_seq",
     "dvo_amd_set_reciprocal_mode", "dvo_amd_get_reciprocal_mode", "dvo_amd_debug_rcp", "dvo_amd_debug_block_trace",
     "dvo_amd_debug_ll_overflow", "dvo_amd_debug_marker", "dvo_amd_debug_rcp_form", "dvo_amd_debug_weights", "dvo_amd_debug_hw_queue",
-    "dvo_amd_debug_level_geometry",
+    "dvo_amd_debug_level_geometry", "dvo_amd_point_cloud", "dvo_amd_map_cloud", "dvo_amd_voxel_downsample", "dvo_amd_write_pcd",
+    "dvo_amd_debug_map_timing",
 ]
 
 
@@ -88,6 +89,10 @@ class CQ7Probe(C.Structure):
     _fields_ = [("n_tail", C.c_int), ("valid_constraints", C.c_int), ("valid_counted", C.c_int), ("recomputed_equal", C.c_int),
                 ("pixel", C.c_int * 3), ("weight_table", C.c_float * 3), ("weight_exact", C.c_float * 3),
                 ("scale_sums_delta", C.c_double * 3), ("moments_delta", C.c_double * 87)]
+
+
+class CCloudStats(C.Structure):
+    _fields_ = [("points_in", C.c_longlong), ("finite", C.c_longlong), ("out_of_range", C.c_longlong), ("voxels", C.c_longlong)]
 
 
 class DvoAmdError(RuntimeError):
@@ -206,6 +211,12 @@ def lib():
     L.dvo_amd_debug_take_wire.argtypes = [C.POINTER(C.c_uint), C.c_uint, C.c_int, C.POINTER(C.c_uint)]
     L.dvo_amd_debug_next_seq.argtypes = [C.c_uint]
     L.dvo_amd_debug_next_seq.restype = C.c_uint
+    L.dvo_amd_point_cloud.argtypes = [vp, vp, C.c_int, dp, vp, C.c_int, vp]
+    L.dvo_amd_map_cloud.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(vp), C.POINTER(C.c_int), C.c_float, vp,
+                                    C.c_longlong, C.POINTER(CCloudStats)]
+    L.dvo_amd_voxel_downsample.argtypes = [vp, C.c_longlong, vp, C.c_float, vp, C.c_longlong, C.POINTER(CCloudStats)]
+    L.dvo_amd_write_pcd.argtypes = [C.c_char_p, vp, C.c_longlong, C.c_int, C.c_int]
+    L.dvo_amd_debug_map_timing.argtypes = [vp, dp, dp, C.POINTER(C.c_longlong)]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -228,6 +239,38 @@ def _check(status: int, where: str):
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _pose_cm(pose):
+    """a 4x4 pose (row-major numpy, as everywhere in this binding) as the column-major doubles of the C ABI"""
+    return np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(4, 4).T)
+
+
+def _split_points(points):
+    """dvo_amd_point records (n x 4 words) -> (xyz float32 [n, 3], rgb uint32 [n])"""
+    return points[:, :3].copy(), points[:, 3].view(np.uint32).copy()
+
+
+def _pack_points(xyz, rgb):
+    xyz = np.asarray(xyz, dtype=np.float32).reshape(-1, 3)
+    rgb = np.asarray(rgb, dtype=np.uint32).reshape(-1)
+    if len(rgb) != len(xyz):
+        raise ValueError("xyz and rgb must hold the same number of points")
+    pts = np.empty((len(xyz), 4), np.float32)
+    pts[:, :3] = xyz
+    pts[:, 3] = rgb.view(np.float32)
+    return pts
+
+
+_cloud_trackers = {}
+
+
+def _cloud_tracker(device: int):
+    """the context RgbdImagePyramid.point_cloud runs in when no tracker is passed: one DenseTracker per device, created on first
+    use and kept (with its point-cloud buffers) for the life of the process"""
+    if device not in _cloud_trackers:
+        _cloud_trackers[device] = DenseTracker(device=device)
+    return _cloud_trackers[device]
 
 
 class Config:
@@ -362,6 +405,30 @@ class RgbdImagePyramid:
         return cnt.value, mask
 
 
+    def point_cloud(self, pose=None, bgr=None, level: int = 0, tracker: "DenseTracker | None" = None):
+        """RgbdCamera::buildPointCloud of a level transformed by `pose` (4x4, None = identity) and coloured from `bgr` (uint8
+        HxWx3 of the level, None = grey from the intensity plane): (xyz float32 [h, w, 3], rgb uint32 [h, w]) in scan order,
+        NaN points included (dvo_amd_point_cloud).  The entry runs in a tracker's context: `tracker` when one is given,
+        otherwise a shared DenseTracker of the pyramid's device that this module creates on the first such call and keeps for
+        the life of the process (with the buffers of the largest cloud it built; nothing is allocated per call once warm).
+        Pass `tracker=` to choose the context -- and with it where the buffers live and when they are freed."""
+        w, h, _ = self.level_info(level)
+        out = np.empty((h * w, 4), np.float32)
+        T = None if pose is None else _pose_cm(pose)
+        bgr_ptr, stride = None, 0
+        if bgr is not None:
+            bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
+            if bgr.shape != (h, w, 3):
+                raise ValueError(f"bgr must be ({h}, {w}, 3) uint8 for level {level}")
+            bgr_ptr, stride = bgr.ctypes.data, w * 3
+        trk = tracker or _cloud_tracker(self.device)
+        _check(lib().dvo_amd_point_cloud(trk._h, self._h, level,
+                                         None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)),
+                                         bgr_ptr, stride, out.ctypes.data), "dvo_amd_point_cloud")
+        xyz, rgb = _split_points(out)
+        return xyz.reshape(h, w, 3), rgb.reshape(h, w)
+
+
 class Result:
     """DenseTracker::Result: Transformation (4x4), Information (6x6), LogLikelihood, Statistics.Levels."""
 
@@ -457,6 +524,66 @@ class DenseTracker:
         out = np.empty_like(a)
         _check(lib().dvo_amd_debug_rcp(self._h, a.size, _fp(a), _fp(out)), "dvo_amd_debug_rcp")
         return out.reshape(np.shape(x))
+
+    def _voxels(self, call, where, capacity):
+        """runs call(out, capacity, stats) and grows the output once on DVO_AMD_ERR_CAPACITY"""
+        stats = CCloudStats()
+        out = np.empty((max(1, capacity), 4), np.float32)
+        rc = call(out.ctypes.data, capacity, C.byref(stats))
+        if rc == 7:  # DVO_AMD_ERR_CAPACITY: stats.voxels is the size needed
+            capacity = int(stats.voxels)
+            out = np.empty((max(1, capacity), 4), np.float32)
+            rc = call(out.ctypes.data, capacity, C.byref(stats))
+        _check(rc, where)
+        xyz, rgb = _split_points(out[:stats.voxels])
+        return xyz, rgb, {"points_in": stats.points_in, "finite": stats.finite, "out_of_range": stats.out_of_range,
+                          "voxels": stats.voxels}
+
+    def map_cloud(self, pyramids, poses, bgrs=None, leaf: float = 0.01, capacity: int | None = None):
+        """The voxel aggregate of level 0 of every pyramid at its pose (4x4 each), coloured from bgrs (None, or one uint8 HxWx3
+        or None per pyramid): (xyz float32 [V, 3], rgb uint32 [V], stats dict) in voxel-key order (dvo_amd_map_cloud)."""
+        n = len(pyramids)
+        if len(poses) != n or (bgrs is not None and len(bgrs) != n):
+            raise ValueError("one pose (and one bgr entry) per pyramid")
+        hs = (C.c_void_p * max(1, n))(*[p._h for p in pyramids])
+        T = np.ascontiguousarray(np.stack([_pose_cm(P) for P in poses])) if n else np.zeros((1, 4, 4))
+        keep, bp, st = [], None, None
+        if bgrs is not None:
+            bp = (C.c_void_p * max(1, n))()
+            st = (C.c_int * max(1, n))()
+            for k, (p, b) in enumerate(zip(pyramids, bgrs)):
+                if b is None:
+                    continue
+                w, h, _ = p.level_info(0)
+                b = np.ascontiguousarray(b, dtype=np.uint8)
+                if b.shape != (h, w, 3):
+                    raise ValueError(f"bgrs[{k}] must be ({h}, {w}, 3) uint8")
+                keep.append(b)
+                bp[k], st[k] = b.ctypes.data, w * 3
+        if capacity is None:
+            capacity = max(1, sum(p.level_info(0)[0] * p.level_info(0)[1] for p in pyramids) // 8)
+
+        def call(out, cap, stats):
+            return lib().dvo_amd_map_cloud(self._h, n, hs, T.ctypes.data_as(C.POINTER(C.c_double)), bp, st, leaf, out, cap,
+                                           stats)
+        return self._voxels(call, "dvo_amd_map_cloud", capacity)
+
+    def voxel_downsample(self, xyz, rgb, leaf: float, capacity: int | None = None):
+        """The voxel aggregate of given points (xyz [n, 3], rgb uint32 [n]): as map_cloud (dvo_amd_voxel_downsample)."""
+        pts = _pack_points(xyz, rgb)
+        n = len(pts)
+        if capacity is None:
+            capacity = max(1, n // 8)
+
+        def call(out, cap, stats):
+            return lib().dvo_amd_voxel_downsample(self._h, n, pts.ctypes.data, leaf, out, cap, stats)
+        return self._voxels(call, "dvo_amd_voxel_downsample", capacity)
+
+    def map_timing(self):
+        """(diagnostic) the last map_cloud / voxel_downsample: (device ms of its kernels, ms of the output copy, points)"""
+        d, c, n = C.c_double(), C.c_double(), C.c_longlong()
+        _check(lib().dvo_amd_debug_map_timing(self._h, C.byref(d), C.byref(c), C.byref(n)), "dvo_amd_debug_map_timing")
+        return d.value, c.value, n.value
 
     def configure(self, config: Config):
         c = config._c()

@@ -4,6 +4,7 @@
 //   dvo_sharded.cpp   one pair tile-sharded into bands / over several GPUs: band pipeline, record exchange, RCCL fallback
 //   dvo_probes.cpp    entries that work in slot 0 outside the match driver: residuals / error image, the stage probe, the kernel
 //                     micro-benchmarks and the diagnostics of include/dvo_amd_debug.h
+//   dvo_map.cpp       the keyframe map's point cloud: organized clouds at a pose, the deterministic voxel aggregate
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -108,6 +109,11 @@ struct dvo_amd_pyramid {
 // ------------------------------------------------------------------------------------------------------------------
 
 struct Runner;  // the resident pairs of a context and the queue behind them (defined with the driver below)
+namespace dvo_amd {
+namespace host {
+struct MapWorkspace;  // the buffers of the map entries (dvo_map.cpp)
+}  // namespace host
+}  // namespace dvo_amd
 
 struct JobSlot {
   float2 *res[2] = {nullptr, nullptr};
@@ -218,6 +224,7 @@ struct dvo_amd_context {
   std::vector<double> tick_log_pending;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
+  host::MapWorkspace *map_ws = nullptr;  // dvo_amd_point_cloud / _map_cloud / _voxel_downsample: grown to the largest call
 };
 
 namespace dvo_amd {
@@ -376,6 +383,7 @@ int runner_fail(dvo_amd_context *ctx, int code);
 int runner_fail_told(dvo_amd_context *ctx, int code);
 int runner_reported_status(Runner &R, unsigned long long ticket);
 int queue_must_be_idle(dvo_amd_context *ctx, const char *what);
+void map_workspace_release(dvo_amd_context *ctx);  // dvo_map.cpp
 int runner_step(dvo_amd_context *ctx, size_t g);
 int runner_drain(dvo_amd_context *ctx);
 int runner_configure(dvo_amd_context *ctx, int in_flight, int n_pad);

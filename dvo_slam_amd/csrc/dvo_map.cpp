@@ -1,0 +1,748 @@
+// The keyframe map's point cloud (dvo_amd.h: dvo_amd_point_cloud, dvo_amd_map_cloud, dvo_amd_voxel_downsample):
+//   k_cloud        one pass over a level's depth / intensity planes and rays: the organized cloud at a pose, 16-B stores
+//   k_map_keys     the same points (one shared device function) straight into the aggregate: finite and in-range points are
+//                  compacted with their 63-bit voxel key; counts and the min / max voxel index per thread, one integer atomic
+//                  per wave at the end
+//   k_rekey        63-bit key -> the dense key of the bits actually present (order preserving)
+//   k_radix_*      stable LSD radix sort of (key, point index), 8-bit digits: per-block digit histograms, an exclusive scan of
+//                  the [digit][block] table, a stable scatter (ranks within a wave by ballots, across waves through LDS)
+//   k_heads        first position of every run of equal keys -> (scan) the voxel index of every sorted position
+//   k_accum        runs of a sorted chunk summed in registers, flushed into the voxel's integer sums with u64 atomics
+//   k_voxel_out    centroid and colour of every voxel from its integer sums
+// Every sum is an integer sum: the result does not depend on the order points arrive in, on the compaction order or on the
+// launch geometry -- bit for bit.
+#include <climits>
+#include <cmath>
+#include <cstring>
+
+#include "dvo_internal.h"
+
+namespace dvo_amd {
+namespace map {
+
+constexpr int kBlock = 256;
+constexpr int kRadixBits = 8;
+constexpr int kRadix = 1 << kRadixBits;
+constexpr int kSortItems = 16;                    // items per thread of a radix tile
+constexpr int kSortTile = kBlock * kSortItems;    // 4096 items per radix block
+constexpr int kScanTile = kBlock * 16;            // items per block of the generic exclusive scan
+constexpr int kAccumChunk = 16;                   // sorted positions one k_accum thread sums before it flushes
+constexpr int kIndexBias = 1 << 20;               // voxel index range [-2^20, 2^20)
+constexpr double kFix = 16777216.0;               // 2^24: the fixed point of the centroid sums
+// At most 2^31 points per call: every position the kernels form in 32 bits (a radix tile's t0 + c * 256 + tid, a k_accum
+// chunk's start) then stays below 2^31 + 2^16 and cannot wrap.
+
+// one image of a map call, as the kernels read it
+struct MapImage {
+  const float *z, *i, *tx, *ty;
+  const unsigned char *bgr;  // device, tight (w * 3 bytes per row); null: grey from the intensity plane
+  int w, h;
+  float T[12];               // rows 0..2 of (float)pose, row-major
+};
+
+struct MapCtrl {
+  unsigned long long kept, finite, out_of_range;
+  int mn[3], mx[3];
+  unsigned voxels, pad;
+};
+
+struct VoxelAcc {
+  unsigned long long count, s[3], c[3], pad;
+};
+
+__device__ __forceinline__ unsigned grey8(float v) {
+  if (!(v == v)) return 0u;
+  return (unsigned)fminf(fmaxf(v, 0.0f), 255.0f);
+}
+
+// the point of pixel (u, v): camera point (tx[u] z, ty[v] z, z), transformed in the order the header pins, coloured
+__device__ __forceinline__ float4 image_point(const MapImage &im, int u, int v) {
+  const size_t p = (size_t)v * im.w + u;
+  const float z = im.z[p];
+  const float x = im.tx[u] * z, y = im.ty[v] * z;
+  const float *T = im.T;
+  const float wx = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+  const float wy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+  const float wz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+  unsigned rgb;
+  if (im.bgr) {
+    const unsigned char *c = im.bgr + p * 3;
+    rgb = ((unsigned)c[2] << 16) | ((unsigned)c[1] << 8) | (unsigned)c[0];
+  } else {
+    const unsigned g = grey8(im.i[p]);
+    rgb = (g << 16) | (g << 8) | g;
+  }
+  return make_float4(wx, wy, wz, __uint_as_float(rgb));
+}
+
+__global__ void __launch_bounds__(kBlock) k_cloud(MapImage im, float4 *out) {
+  const long long n = (long long)im.w * im.h;
+  for (long long p = (long long)blockIdx.x * kBlock + threadIdx.x; p < n; p += (long long)gridDim.x * kBlock) {
+    const int v = (int)(p / im.w), u = (int)(p - (long long)v * im.w);
+    out[p] = image_point(im, u, v);
+  }
+}
+
+__device__ __forceinline__ unsigned long long lanemask_lt() { return (1ull << (threadIdx.x & 63)) - 1ull; }
+
+__device__ __forceinline__ int wave_min(int v) {
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// what a thread of an input stage has counted over its points; flushed once per wave at the end of the kernel
+struct Counts {
+  unsigned long long finite = 0, out_of_range = 0;
+  int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+};
+
+// voxel of one point: kept (finite and in range) with its 63-bit key
+__device__ __forceinline__ void key_and_count(const float4 pt, float inv, bool active, Counts &cnt, bool &keep,
+                                              unsigned long long &key) {
+  const bool finite = active && isfinite(pt.x) && isfinite(pt.y) && isfinite(pt.z);
+  float f[3] = {floorf(pt.x * inv), floorf(pt.y * inv), floorf(pt.z * inv)};
+  bool in = finite;
+  int idx[3] = {0, 0, 0};
+  for (int a = 0; a < 3; ++a) {
+    in = in && f[a] >= -(float)kIndexBias && f[a] < (float)kIndexBias;
+    idx[a] = in ? (int)f[a] : 0;
+  }
+  keep = in;
+  key = ((unsigned long long)(idx[0] + kIndexBias) << 42) | ((unsigned long long)(idx[1] + kIndexBias) << 21) |
+        (unsigned long long)(idx[2] + kIndexBias);
+  cnt.finite += finite ? 1 : 0;
+  cnt.out_of_range += (finite && !in) ? 1 : 0;
+  if (in)
+    for (int a = 0; a < 3; ++a) cnt.mn[a] = min(cnt.mn[a], idx[a]), cnt.mx[a] = max(cnt.mx[a], idx[a]);
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// every lane of the wave must call it
+__device__ __forceinline__ void flush_counts(Counts &cnt, MapCtrl *ctrl) {
+  const unsigned long long fin = wave_sum(cnt.finite), oor = wave_sum(cnt.out_of_range);
+  int mn[3], mx[3];
+  for (int a = 0; a < 3; ++a) mn[a] = wave_min(cnt.mn[a]), mx[a] = wave_max(cnt.mx[a]);
+  if ((threadIdx.x & 63) == 0) {
+    if (fin) atomicAdd(&ctrl->finite, fin);
+    if (oor) atomicAdd(&ctrl->out_of_range, oor);
+    if (fin != oor)
+      for (int a = 0; a < 3; ++a) atomicMin(&ctrl->mn[a], mn[a]), atomicMax(&ctrl->mx[a], mx[a]);
+  }
+}
+
+// compaction slot of a kept point (wave-aggregated atomic: the order of the compacted points is not deterministic, nothing
+// downstream depends on it)
+__device__ __forceinline__ unsigned long long compact_slot(bool keep, MapCtrl *ctrl) {
+  const unsigned long long bk = __ballot(keep);
+  unsigned long long base = 0;
+  if ((threadIdx.x & 63) == 0 && bk) base = atomicAdd(&ctrl->kept, (unsigned long long)__popcll(bk));
+  base = __shfl(base, 0, 64);
+  return base + __popcll(bk & lanemask_lt());
+}
+
+// aggregate input from images: grid (blocks over the largest image, images)
+__global__ void __launch_bounds__(kBlock) k_map_keys(const MapImage *images, int image0, float inv, float4 *pts,
+                                                     unsigned long long *keys, unsigned *vals, MapCtrl *ctrl) {
+  const MapImage im = images[image0 + blockIdx.y];
+  const long long n = (long long)im.w * im.h;
+  Counts cnt;
+  for (long long p0 = (long long)blockIdx.x * kBlock; p0 < n; p0 += (long long)gridDim.x * kBlock) {
+    const long long p = p0 + threadIdx.x;
+    const bool active = p < n;
+    float4 pt = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (active) {
+      const int v = (int)(p / im.w), u = (int)(p - (long long)v * im.w);
+      pt = image_point(im, u, v);
+    }
+    bool keep;
+    unsigned long long key;
+    key_and_count(pt, inv, active, cnt, keep, key);
+    const unsigned long long slot = compact_slot(keep, ctrl);
+    if (keep) pts[slot] = pt, keys[slot] = key, vals[slot] = (unsigned)slot;
+  }
+  flush_counts(cnt, ctrl);
+}
+
+// aggregate input from a point array (already on the device); vals index the array itself
+__global__ void __launch_bounds__(kBlock) k_points_keys(const float4 *in, unsigned long long n, float inv,
+                                                        unsigned long long *keys, unsigned *vals, MapCtrl *ctrl) {
+  Counts cnt;
+  for (unsigned long long p0 = (unsigned long long)blockIdx.x * kBlock; p0 < n; p0 += (unsigned long long)gridDim.x * kBlock) {
+    const unsigned long long p = p0 + threadIdx.x;
+    const bool active = p < n;
+    const float4 pt = active ? in[p] : make_float4(0.f, 0.f, 0.f, 0.f);
+    bool keep;
+    unsigned long long key;
+    key_and_count(pt, inv, active, cnt, keep, key);
+    const unsigned long long slot = compact_slot(keep, ctrl);
+    if (keep) keys[slot] = key, vals[slot] = (unsigned)p;
+  }
+  flush_counts(cnt, ctrl);
+}
+
+struct Rekey {
+  int mn[3];
+  int sh_i, sh_j;  // bits of the j and k fields, of the k field
+};
+
+__global__ void __launch_bounds__(kBlock) k_rekey(unsigned long long *keys, unsigned long long n, Rekey r) {
+  for (unsigned long long p = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; p < n; p += (unsigned long long)gridDim.x * kBlock) {
+    const unsigned long long k = keys[p];
+    const unsigned long long i = ((k >> 42) & 0x1FFFFF) - (unsigned long long)(r.mn[0] + kIndexBias);
+    const unsigned long long j = ((k >> 21) & 0x1FFFFF) - (unsigned long long)(r.mn[1] + kIndexBias);
+    const unsigned long long kk = (k & 0x1FFFFF) - (unsigned long long)(r.mn[2] + kIndexBias);
+    keys[p] = (i << r.sh_i) | (j << r.sh_j) | kk;
+  }
+}
+
+// per-block digit histogram of a radix tile -> counts[digit * n_blocks + block]
+__global__ void __launch_bounds__(kBlock) k_radix_hist(const unsigned long long *keys, unsigned n, int shift, unsigned *counts) {
+  __shared__ unsigned hist[kRadix];
+  hist[threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned t0 = blockIdx.x * kSortTile;
+  for (int c = 0; c < kSortItems; ++c) {
+    const unsigned p = t0 + c * kBlock + threadIdx.x;
+    if (p < n) atomicAdd(&hist[(unsigned)(keys[p] >> shift) & (kRadix - 1)], 1u);
+  }
+  __syncthreads();
+  counts[(size_t)threadIdx.x * gridDim.x + blockIdx.x] = hist[threadIdx.x];
+}
+
+// stable scatter of a radix tile: items in tile order (chunk, wave, lane); offsets = the scanned counts
+__global__ void __launch_bounds__(kBlock) k_radix_scatter(const unsigned long long *keys_in, const unsigned *vals_in,
+                                                          unsigned long long *keys_out, unsigned *vals_out, unsigned n,
+                                                          int shift, const unsigned *offsets) {
+  __shared__ unsigned base[kRadix];
+  __shared__ unsigned wcnt[kBlock / 64][kRadix];
+  const int wave = threadIdx.x >> 6;
+  base[threadIdx.x] = offsets[(size_t)threadIdx.x * gridDim.x + blockIdx.x];
+  const unsigned t0 = blockIdx.x * kSortTile;
+  for (int c = 0; c < kSortItems; ++c) {
+    for (int w = 0; w < kBlock / 64; ++w) wcnt[w][threadIdx.x] = 0;
+    __syncthreads();
+    const unsigned p = t0 + c * kBlock + threadIdx.x;
+    const bool active = p < n;
+    const unsigned long long k = active ? keys_in[p] : 0ull;
+    const unsigned v = active ? vals_in[p] : 0u;
+    const unsigned d = (unsigned)(k >> shift) & (kRadix - 1);
+    unsigned long long peers = __ballot(active);
+    for (int b = 0; b < kRadixBits; ++b) {
+      const unsigned long long bal = __ballot((d >> b) & 1u);
+      peers &= ((d >> b) & 1u) ? bal : ~bal;
+    }
+    const unsigned rank = __popcll(peers & lanemask_lt());
+    if (active && rank == 0) wcnt[wave][d] = __popcll(peers);  // the first lane of each digit group writes its count
+    __syncthreads();
+    if (active) {
+      unsigned off = base[d] + rank;
+      for (int w = 0; w < wave; ++w) off += wcnt[w][d];
+      if (off < n) keys_out[off] = k, vals_out[off] = v;  // (always: the offsets are a permutation of [0, n))
+    }
+    __syncthreads();
+    unsigned add = 0;
+    for (int w = 0; w < kBlock / 64; ++w) add += wcnt[w][threadIdx.x];
+    base[threadIdx.x] += add;
+    __syncthreads();
+  }
+}
+
+// exclusive scan of one value per thread over the block (256 threads); *total = the block's sum
+__device__ unsigned block_exclusive_scan(unsigned v, unsigned *total) {
+  __shared__ unsigned wsum[kBlock / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned incl = v;
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned t = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += t;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  unsigned before = 0, all = 0;
+  for (int w = 0; w < kBlock / 64; ++w) {
+    before += w < wave ? wsum[w] : 0u;
+    all += wsum[w];
+  }
+  __syncthreads();
+  *total = all;
+  return before + incl - v;
+}
+
+__global__ void __launch_bounds__(kBlock) k_scan_reduce(const unsigned *a, unsigned n, unsigned *bsum) {
+  const unsigned t0 = blockIdx.x * kScanTile;
+  unsigned s = 0;
+  for (int c = 0; c < kScanTile / kBlock; ++c) {
+    const unsigned p = t0 + c * kBlock + threadIdx.x;
+    if (p < n) s += a[p];
+  }
+  unsigned total;
+  (void)block_exclusive_scan(s, &total);
+  if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+
+// one block: exclusive scan of the block sums in place; *grand = the sum of all
+__global__ void __launch_bounds__(kBlock) k_scan_blocks(unsigned *bsum, unsigned nb, unsigned *grand) {
+  unsigned carry = 0;
+  for (unsigned c0 = 0; c0 < nb; c0 += kBlock) {
+    const unsigned p = c0 + threadIdx.x;
+    const unsigned v = p < nb ? bsum[p] : 0u;
+    unsigned total;
+    const unsigned ex = block_exclusive_scan(v, &total);
+    if (p < nb) bsum[p] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0 && grand) *grand = carry;
+}
+
+__global__ void __launch_bounds__(kBlock) k_scan_apply(unsigned *a, unsigned n, const unsigned *bsum) {
+  const unsigned t0 = blockIdx.x * kScanTile;
+  unsigned carry = bsum[blockIdx.x];
+  for (int c = 0; c < kScanTile / kBlock; ++c) {
+    const unsigned p = t0 + c * kBlock + threadIdx.x;
+    const unsigned v = p < n ? a[p] : 0u;
+    unsigned total;
+    const unsigned ex = block_exclusive_scan(v, &total);
+    if (p < n) a[p] = carry + ex;
+    carry += total;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_heads(const unsigned long long *keys, unsigned n, unsigned *flags) {
+  for (unsigned p = blockIdx.x * kBlock + threadIdx.x; p < n; p += gridDim.x * kBlock)
+    flags[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1u : 0u;
+}
+
+__device__ __forceinline__ void flush(VoxelAcc *acc, unsigned n_vox, unsigned v, unsigned long long cnt, const long long s[3],
+                                      const unsigned long long c[3]) {
+  if (v >= n_vox) return;  // (never: v < the number of heads)
+  VoxelAcc *a = acc + v;
+  atomicAdd(&a->count, cnt);
+  for (int q = 0; q < 3; ++q) atomicAdd(&a->s[q], (unsigned long long)s[q]), atomicAdd(&a->c[q], c[q]);
+}
+
+// vidx = the exclusive scan of the head flags: the voxel of sorted position p is vidx[p] + flag(p) - 1; sums wrap modulo 2^64
+__global__ void __launch_bounds__(kBlock) k_accum(const unsigned long long *keys, const unsigned *vals, const unsigned *vidx,
+                                                  unsigned n, const float4 *pts, VoxelAcc *acc, unsigned n_vox) {
+  const unsigned p0 = (blockIdx.x * kBlock + threadIdx.x) * kAccumChunk;
+  if (p0 >= n) return;
+  const unsigned p1 = min(n, p0 + kAccumChunk);
+  unsigned long long key = keys[p0];
+  unsigned vox = vidx[p0] + ((p0 == 0 || keys[p0 - 1] != key) ? 1u : 0u) - 1u;
+  unsigned long long cnt = 0, c[3] = {0, 0, 0};
+  long long s[3] = {0, 0, 0};
+  for (unsigned p = p0; p < p1; ++p) {
+    const unsigned long long k = keys[p];
+    if (k != key) {
+      flush(acc, n_vox, vox, cnt, s, c);
+      key = k, ++vox, cnt = 0;
+      for (int q = 0; q < 3; ++q) s[q] = 0, c[q] = 0;
+    }
+    const float4 pt = pts[vals[p]];
+    const unsigned rgb = __float_as_uint(pt.w);
+    s[0] += llrint((double)pt.x * kFix), s[1] += llrint((double)pt.y * kFix), s[2] += llrint((double)pt.z * kFix);
+    c[0] += (rgb >> 16) & 0xFF, c[1] += (rgb >> 8) & 0xFF, c[2] += rgb & 0xFF;
+    ++cnt;
+  }
+  flush(acc, n_vox, vox, cnt, s, c);
+}
+
+__global__ void __launch_bounds__(kBlock) k_voxel_out(const VoxelAcc *acc, unsigned n_vox, float4 *out) {
+  for (unsigned v = blockIdx.x * kBlock + threadIdx.x; v < n_vox; v += gridDim.x * kBlock) {
+    const VoxelAcc a = acc[v];
+    const double den = (double)a.count * kFix;
+    float xyz[3];
+    unsigned ch[3];
+    for (int q = 0; q < 3; ++q) {
+      xyz[q] = (float)((double)(long long)a.s[q] / den);
+      ch[q] = (unsigned)((a.c[q] + a.count / 2) / a.count);
+    }
+    out[v] = make_float4(xyz[0], xyz[1], xyz[2], __uint_as_float((ch[0] << 16) | (ch[1] << 8) | ch[2]));
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------------------------
+
+unsigned grid_for(unsigned long long n, unsigned per_block, unsigned cap = 4096) {
+  const unsigned long long b = (n + per_block - 1) / per_block;
+  return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(b, cap));
+}
+
+}  // namespace map
+
+namespace host {
+
+// device buffers of the map entries: grown to the largest call, kept by the context (nothing is allocated once warm)
+struct MapWorkspace {
+  struct Buf {
+    void *p = nullptr;
+    size_t bytes = 0;
+  };
+  Buf pts, keys[2], vals[2], flags, counts, bsum, acc, out, bgr, images, ctrl;
+  hipEvent_t ev[8] = {};  // input stage, sort, reduction, output copy: begin / end each
+  double device_ms = 0.0, copy_ms = 0.0;  // the last map call: kernels (three timed segments), the output copy
+  long long points = 0;
+};
+
+namespace {
+
+int grow(MapWorkspace::Buf &b, size_t bytes) {
+  if (bytes <= b.bytes) return DVO_AMD_OK;
+  if (b.p) (void)hipFree(b.p), b.p = nullptr, b.bytes = 0;
+  bytes = align_up(std::max<size_t>(bytes, 256), 1 << 16);
+  const hipError_t e = hipMalloc(&b.p, bytes);
+  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
+  if (e != hipSuccess) return fail_hip("hipMalloc (map workspace)", e);
+  b.bytes = bytes;
+  return DVO_AMD_OK;
+}
+
+int workspace(dvo_amd_context *ctx, MapWorkspace **out) {
+  if (!ctx->map_ws) {
+    MapWorkspace *w = new MapWorkspace();
+    for (hipEvent_t &e : w->ev) {
+      const hipError_t he = hipEventCreate(&e);
+      if (he != hipSuccess) {
+        ctx->map_ws = w;
+        return fail_hip("hipEventCreate (map workspace)", he);
+      }
+    }
+    ctx->map_ws = w;
+  }
+  *out = ctx->map_ws;
+  return DVO_AMD_OK;
+}
+
+int have_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
+  return DVO_AMD_OK;
+}
+
+bool valid_leaf(float leaf) { return std::isfinite(leaf) && leaf > 0.0f && leaf <= 65536.0f; }
+
+void float_pose(const double *pose, float T[12]) {
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) T[r * 4 + c] = pose ? (float)pose[c * 4 + r] : (r == c ? 1.0f : 0.0f);
+}
+
+int bits_for(int span) {
+  int b = 0;
+  while (b < 31 && (1u << b) <= (unsigned)span) ++b;
+  return b;
+}
+
+// exclusive scan of a[0..n) in place on the stream; grand (device, may be null) = the total
+int scan(MapWorkspace &W, unsigned *a, unsigned n, unsigned *grand, hipStream_t st) {
+  const unsigned nb = std::max(1u, (n + map::kScanTile - 1) / map::kScanTile);
+  int rc = grow(W.bsum, sizeof(unsigned) * nb);
+  if (rc) return rc;
+  unsigned *bsum = (unsigned *)W.bsum.p;
+  hipLaunchKernelGGL(map::k_scan_reduce, dim3(nb), dim3(map::kBlock), 0, st, a, n, bsum);
+  hipLaunchKernelGGL(map::k_scan_blocks, dim3(1), dim3(map::kBlock), 0, st, bsum, nb, grand);
+  hipLaunchKernelGGL(map::k_scan_apply, dim3(nb), dim3(map::kBlock), 0, st, a, n, bsum);
+  HIP_TRY(hipGetLastError());
+  return DVO_AMD_OK;
+}
+
+// The aggregate of the m points the input stage left in keys[0] / vals[0] (c: the control block it filled, read back): sorts,
+// finds the voxels, checks the capacity, reduces and copies the voxels to `out`.  Events 2..5 time the two kernel segments.
+int reduce_voxels(MapWorkspace &W, const map::MapCtrl &c, const float4 *pts, dvo_amd_point *out, long long capacity,
+                  dvo_amd_cloud_stats *stats, hipStream_t st) {
+  const unsigned m = (unsigned)c.kept;
+  unsigned n_vox = 0;
+  if (m > 0) {
+    // the bits present: fields i | j | k of (index - min), packed densely -- order preserving
+    const int bi = bits_for(c.mx[0] - c.mn[0]), bj = bits_for(c.mx[1] - c.mn[1]), bk = bits_for(c.mx[2] - c.mn[2]);
+    map::Rekey r = {{c.mn[0], c.mn[1], c.mn[2]}, bj + bk, bk};
+    const int passes = (bi + bj + bk + map::kRadixBits - 1) / map::kRadixBits;
+    const unsigned nb = (m + map::kSortTile - 1) / map::kSortTile;
+    int rc = grow(W.counts, sizeof(unsigned) * map::kRadix * (size_t)nb);
+    // the scan scratch for the larger of the two scans (the digit table, the head flags), before anything is enqueued
+    if (!rc) rc = grow(W.bsum, sizeof(unsigned) * (std::max<size_t>((size_t)map::kRadix * nb, m) / map::kScanTile + 1));
+    if (rc) return rc;
+    unsigned long long *keys[2] = {(unsigned long long *)W.keys[0].p, (unsigned long long *)W.keys[1].p};
+    unsigned *vals[2] = {(unsigned *)W.vals[0].p, (unsigned *)W.vals[1].p};
+    unsigned *counts = (unsigned *)W.counts.p;
+    map::MapCtrl *dctrl = (map::MapCtrl *)W.ctrl.p;
+    HIP_TRY(hipEventRecord(W.ev[2], st));
+    hipLaunchKernelGGL(map::k_rekey, dim3(map::grid_for(m, map::kBlock)), dim3(map::kBlock), 0, st, keys[0], (unsigned long long)m, r);
+    int cur = 0;
+    for (int pass = 0; pass < passes; ++pass) {
+      const int shift = pass * map::kRadixBits;
+      hipLaunchKernelGGL(map::k_radix_hist, dim3(nb), dim3(map::kBlock), 0, st, keys[cur], m, shift, counts);
+      rc = scan(W, counts, map::kRadix * nb, nullptr, st);
+      if (rc) return rc;
+      hipLaunchKernelGGL(map::k_radix_scatter, dim3(nb), dim3(map::kBlock), 0, st, keys[cur], vals[cur], keys[cur ^ 1],
+                         vals[cur ^ 1], m, shift, (const unsigned *)counts);
+      cur ^= 1;
+    }
+    unsigned *flags = (unsigned *)W.flags.p;
+    hipLaunchKernelGGL(map::k_heads, dim3(map::grid_for(m, map::kBlock)), dim3(map::kBlock), 0, st, keys[cur], m, flags);
+    rc = scan(W, flags, m, &dctrl->voxels, st);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(W.ev[3], st));
+    HIP_TRY(hipMemcpyAsync(&n_vox, &dctrl->voxels, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((long long)n_vox <= capacity && out) {
+      rc = grow(W.acc, sizeof(map::VoxelAcc) * (size_t)n_vox);
+      if (!rc) rc = grow(W.out, sizeof(float4) * (size_t)n_vox);
+      if (rc) return rc;
+      map::VoxelAcc *acc = (map::VoxelAcc *)W.acc.p;
+      HIP_TRY(hipEventRecord(W.ev[4], st));
+      HIP_TRY(hipMemsetAsync(acc, 0, sizeof(map::VoxelAcc) * (size_t)n_vox, st));
+      const unsigned long long threads = ((unsigned long long)m + map::kAccumChunk - 1) / map::kAccumChunk;
+      hipLaunchKernelGGL(map::k_accum, dim3((unsigned)((threads + map::kBlock - 1) / map::kBlock)), dim3(map::kBlock), 0, st,
+                         keys[cur], vals[cur], flags, m, pts, acc, n_vox);
+      hipLaunchKernelGGL(map::k_voxel_out, dim3(map::grid_for(n_vox, map::kBlock)), dim3(map::kBlock), 0, st, acc, n_vox,
+                         (float4 *)W.out.p);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(W.ev[5], st));
+    }
+  }
+  if (stats) stats->voxels = n_vox;
+  if ((long long)n_vox > capacity) {
+    g_last_error = "voxel aggregate: " + std::to_string(n_vox) + " voxels, capacity " + std::to_string(capacity);
+    return DVO_AMD_ERR_CAPACITY;
+  }
+  if (n_vox > 0) {
+    HIP_TRY(hipEventRecord(W.ev[6], st));
+    HIP_TRY(hipMemcpyAsync(out, W.out.p, sizeof(float4) * (size_t)n_vox, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipEventRecord(W.ev[7], st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float a = 0.f, b = 0.f, d = 0.f;
+    HIP_TRY(hipEventElapsedTime(&a, W.ev[2], W.ev[3]));
+    HIP_TRY(hipEventElapsedTime(&b, W.ev[4], W.ev[5]));
+    HIP_TRY(hipEventElapsedTime(&d, W.ev[6], W.ev[7]));
+    W.device_ms += a + b;
+    W.copy_ms = d;
+  }
+  return DVO_AMD_OK;
+}
+
+// the control block before an input stage, and its read-back into the stats
+int start_ctrl(MapWorkspace &W, hipStream_t st) {
+  int rc = grow(W.ctrl, sizeof(map::MapCtrl));
+  if (rc) return rc;
+  map::MapCtrl c;
+  std::memset(&c, 0, sizeof(c));
+  for (int a = 0; a < 3; ++a) c.mn[a] = INT_MAX, c.mx[a] = INT_MIN;
+  HIP_TRY(hipMemcpyAsync(W.ctrl.p, &c, sizeof(c), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(W.ev[0], st));
+  return DVO_AMD_OK;
+}
+
+int read_ctrl(MapWorkspace &W, map::MapCtrl *c, long long points_in, dvo_amd_cloud_stats *stats, hipStream_t st) {
+  HIP_TRY(hipEventRecord(W.ev[1], st));
+  HIP_TRY(hipMemcpyAsync(c, W.ctrl.p, sizeof(*c), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.f;
+  HIP_TRY(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+  W.device_ms = ms, W.copy_ms = 0.0, W.points = points_in;
+  if (stats) {
+    stats->points_in = points_in;
+    stats->finite = (long long)c->finite;
+    stats->out_of_range = (long long)c->out_of_range;
+    stats->voxels = 0;
+  }
+  return DVO_AMD_OK;
+}
+
+// the per-point buffers of the sort for n points
+int grow_points(MapWorkspace &W, size_t n, bool pts) {
+  int rc = DVO_AMD_OK;
+  for (int b = 0; b < 2 && !rc; ++b) rc = grow(W.keys[b], 8 * n), rc = rc ? rc : grow(W.vals[b], 4 * n);
+  if (!rc) rc = grow(W.flags, 4 * n);
+  if (!rc && pts) rc = grow(W.pts, 16 * n);
+  return rc;
+}
+
+// the image descriptors of a call (and its BGR planes, packed to w * 3 bytes per row) on the device
+int upload_images(MapWorkspace &W, int n, dvo_amd_pyramid *const *images, int level, const double *poses, int pose_stride,
+                  const unsigned char *const *bgrs, const int *bgr_strides, std::vector<map::MapImage> &host, hipStream_t st) {
+  host.resize((size_t)n);
+  size_t bgr_bytes = 0;
+  for (int k = 0; k < n; ++k) {
+    const LevelData &L = images[k]->lv[level];
+    map::MapImage &im = host[(size_t)k];
+    im.z = L.z_plane, im.i = L.i_plane, im.tx = L.tx, im.ty = L.ty, im.bgr = nullptr, im.w = L.w, im.h = L.h;
+    float_pose(poses ? poses + (size_t)pose_stride * k : nullptr, im.T);
+    if (bgrs && bgrs[k]) bgr_bytes += (size_t)L.w * L.h * 3;
+  }
+  int rc = grow(W.images, sizeof(map::MapImage) * std::max(1, n));
+  if (!rc && bgr_bytes) rc = grow(W.bgr, bgr_bytes);
+  if (rc) return rc;
+  size_t at = 0;
+  for (int k = 0; k < n; ++k) {
+    if (!bgrs || !bgrs[k]) continue;
+    map::MapImage &im = host[(size_t)k];
+    unsigned char *dst = (unsigned char *)W.bgr.p + at;
+    const int stride = bgr_strides ? bgr_strides[k] : im.w * 3;
+    if (stride < im.w * 3) return DVO_AMD_ERR_INVALID_ARGUMENT;
+    HIP_TRY(hipMemcpy2DAsync(dst, (size_t)im.w * 3, bgrs[k], (size_t)stride, (size_t)im.w * 3, im.h, hipMemcpyHostToDevice, st));
+    im.bgr = dst;
+    at += (size_t)im.w * im.h * 3;
+  }
+  if (n > 0)
+    HIP_TRY(hipMemcpyAsync(W.images.p, host.data(), sizeof(map::MapImage) * n, hipMemcpyHostToDevice, st));
+  return DVO_AMD_OK;
+}
+
+int check_images(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *images, int level) {
+  for (int k = 0; k < n; ++k) {
+    if (!images[k]) return DVO_AMD_ERR_INVALID_ARGUMENT;
+    if (level >= images[k]->n_levels) return DVO_AMD_ERR_TOO_FEW_LEVELS;
+    if (images[k]->device != ctx->device) return DVO_AMD_ERR_DEVICE_MISMATCH;
+  }
+  return DVO_AMD_OK;
+}
+
+}  // namespace
+
+void map_workspace_release(dvo_amd_context *ctx) {
+  MapWorkspace *w = ctx->map_ws;
+  if (!w) return;
+  for (MapWorkspace::Buf *b : {&w->pts, &w->keys[0], &w->keys[1], &w->vals[0], &w->vals[1], &w->flags, &w->counts, &w->bsum,
+                               &w->acc, &w->out, &w->bgr, &w->images, &w->ctrl})
+    if (b->p) (void)hipFree(b->p);
+  for (hipEvent_t e : w->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete w;
+  ctx->map_ws = nullptr;
+}
+
+}  // namespace host
+}  // namespace dvo_amd
+
+extern "C" {
+
+int dvo_amd_point_cloud(dvo_amd_context *ctx, dvo_amd_pyramid *image, int level, const double *pose, const unsigned char *bgr,
+                        int bgr_stride_bytes, dvo_amd_point *out) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx || !image || !out || level < 0) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = host::check_images(ctx, 1, &image, level);
+  if (rc) return rc;
+  rc = queue_must_be_idle(ctx, "dvo_amd_point_cloud");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  host::MapWorkspace *W = nullptr;
+  rc = host::workspace(ctx, &W);
+  if (rc) return rc;
+  const hipStream_t st = ctx->stream;
+  std::vector<map::MapImage> im;
+  const unsigned char *const bgrs[1] = {bgr};
+  const int strides[1] = {bgr_stride_bytes};
+  rc = host::upload_images(*W, 1, &image, level, pose, 16, bgr ? bgrs : nullptr, strides, im, st);
+  if (rc) return rc;
+  const size_t n = (size_t)im[0].w * im[0].h;
+  rc = host::grow(W->out, 16 * n);
+  if (rc) return rc;
+  hipLaunchKernelGGL(map::k_cloud, dim3(map::grid_for(n, map::kBlock)), dim3(map::kBlock), 0, st, im[0], (float4 *)W->out.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, W->out.p, 16 * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_map_cloud(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *images, const double *poses,
+                      const unsigned char *const *bgrs, const int *bgr_strides, float leaf_size, dvo_amd_point *out,
+                      long long capacity, dvo_amd_cloud_stats *stats) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!ctx || n < 0 || (n > 0 && (!images || !poses)) || capacity < 0 || (capacity > 0 && !out) || !host::valid_leaf(leaf_size))
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = host::check_images(ctx, n, images, 0);
+  if (rc) return rc;
+  rc = queue_must_be_idle(ctx, "dvo_amd_map_cloud");
+  if (rc) return rc;
+  unsigned long long total = 0;
+  int max_px = 1;
+  for (int k = 0; k < n; ++k) {
+    total += (unsigned long long)images[k]->lv[0].n;
+    max_px = std::max(max_px, images[k]->lv[0].n);
+  }
+  if (total > (1ull << 31)) {
+    g_last_error = "dvo_amd_map_cloud: more than 2^31 points in one call";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  host::MapWorkspace *W = nullptr;
+  rc = host::workspace(ctx, &W);
+  if (!rc) rc = host::grow_points(*W, std::max<size_t>(1, total), true);
+  if (rc) return rc;
+  const hipStream_t st = ctx->stream;
+  std::vector<map::MapImage> im;
+  rc = host::upload_images(*W, n, images, 0, poses, 16, bgrs, bgr_strides, im, st);
+  if (!rc) rc = host::start_ctrl(*W, st);
+  if (rc) return rc;
+  const float inv = 1.0f / leaf_size;
+  for (int k0 = 0; k0 < n; k0 += 65535) {
+    const int nk = std::min(65535, n - k0);
+    hipLaunchKernelGGL(map::k_map_keys, dim3(map::grid_for(max_px, map::kBlock, 64), nk), dim3(map::kBlock), 0, st,
+                       (const map::MapImage *)W->images.p, k0, inv, (float4 *)W->pts.p, (unsigned long long *)W->keys[0].p,
+                       (unsigned *)W->vals[0].p, (map::MapCtrl *)W->ctrl.p);
+  }
+  HIP_TRY(hipGetLastError());
+  map::MapCtrl c;
+  rc = host::read_ctrl(*W, &c, (long long)total, stats, st);
+  if (rc) return rc;
+  return host::reduce_voxels(*W, c, (const float4 *)W->pts.p, out, capacity, stats, st);
+}
+
+int dvo_amd_voxel_downsample(dvo_amd_context *ctx, long long n, const dvo_amd_point *in, float leaf_size, dvo_amd_point *out,
+                             long long capacity, dvo_amd_cloud_stats *stats) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!ctx || n < 0 || (n > 0 && !in) || capacity < 0 || (capacity > 0 && !out) || !host::valid_leaf(leaf_size))
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  if ((unsigned long long)n > (1ull << 31)) {
+    g_last_error = "dvo_amd_voxel_downsample: more than 2^31 points in one call";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  rc = queue_must_be_idle(ctx, "dvo_amd_voxel_downsample");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  host::MapWorkspace *W = nullptr;
+  rc = host::workspace(ctx, &W);
+  if (!rc) rc = host::grow_points(*W, std::max<long long>(1, n), true);
+  if (rc) return rc;
+  const hipStream_t st = ctx->stream;
+  if (n > 0) HIP_TRY(hipMemcpyAsync(W->pts.p, in, 16 * (size_t)n, hipMemcpyHostToDevice, st));
+  rc = host::start_ctrl(*W, st);
+  if (rc) return rc;
+  if (n > 0)
+    hipLaunchKernelGGL(map::k_points_keys, dim3(map::grid_for(n, map::kBlock, 2048)), dim3(map::kBlock), 0, st,
+                       (const float4 *)W->pts.p, (unsigned long long)n, 1.0f / leaf_size, (unsigned long long *)W->keys[0].p,
+                       (unsigned *)W->vals[0].p, (map::MapCtrl *)W->ctrl.p);
+  HIP_TRY(hipGetLastError());
+  map::MapCtrl c;
+  rc = host::read_ctrl(*W, &c, n, stats, st);
+  if (rc) return rc;
+  return host::reduce_voxels(*W, c, (const float4 *)W->pts.p, out, capacity, stats, st);
+}
+
+int dvo_amd_debug_map_timing(dvo_amd_context *ctx, double *device_ms, double *copy_ms, long long *points) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  const host::MapWorkspace *W = ctx->map_ws;
+  if (device_ms) *device_ms = W ? W->device_ms : 0.0;
+  if (copy_ms) *copy_ms = W ? W->copy_ms : 0.0;
+  if (points) *points = W ? W->points : 0;
+  return DVO_AMD_OK;
+}
+
+}  // extern "C"

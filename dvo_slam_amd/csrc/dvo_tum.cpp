@@ -1,5 +1,6 @@
 // TUM RGB-D benchmark file formats: a PNG reader standing in for cv::imread
-// (benchmark_slam.cpp:50-51) and the trajectory line of benchmark_slam.cpp:490-504.  Host code only, zlib for inflate.
+// (benchmark_slam.cpp:50-51), the trajectory line of benchmark_slam.cpp:490-504 and the binary PCD file of a coloured point
+// cloud (pcl::io::savePCDFileBinary).  Host code only, zlib for inflate.
 #include <zlib.h>
 
 #include <cmath>
@@ -246,6 +247,24 @@ int dvo_amd_format_trajectory_line(double timestamp, const double *T, char *buf,
   const int n = std::snprintf(buf, (size_t)capacity, "%lld.%09lld %g %g %g %g %g %g %g \n", sec, nsec, T[12], T[13], T[14],
                               q[0], q[1], q[2], q[3]);
   return (n < 0 || n >= capacity) ? -1 : n;
+}
+
+int dvo_amd_write_pcd(const char *path, const dvo_amd_point *points, long long n, int width, int height) {
+  if (!path || n < 0 || (n > 0 && !points) || width < 0 || height < 0 || (long long)width * height != n)
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  std::FILE *f = std::fopen(path, "wb");
+  if (!f) return DVO_AMD_ERR_IO;
+  // pcl::PCDWriter::generateHeader for PointXYZRGB; the binary block holds the four fields packed, 16 bytes per point
+  const int h = std::fprintf(f,
+                             "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\n"
+                             "TYPE F F F F\nCOUNT 1 1 1 1\nWIDTH %d\nHEIGHT %d\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %lld\n"
+                             "DATA binary\n",
+                             width, height, n);
+  bool ok = h > 0;
+  static_assert(sizeof(dvo_amd_point) == 16, "dvo_amd_point is 16 bytes");
+  if (ok && n > 0) ok = std::fwrite(points, sizeof(dvo_amd_point), (size_t)n, f) == (size_t)n;
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? DVO_AMD_OK : DVO_AMD_ERR_IO;
 }
 
 }  // extern "C"

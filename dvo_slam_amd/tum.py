@@ -160,3 +160,16 @@ def replay(assoc_path: str, trajectory_path: str | None = None, K=TUM_FR1_INTRIN
         if fh:
             fh.close()
     return out
+
+
+def write_pcd(path: str, xyz, rgb):
+    """Binary PCD v0.7 of a coloured cloud as pcl::io::savePCDFileBinary writes PointXYZRGB (dvo_amd_write_pcd).  xyz [h, w, 3]
+    with rgb [h, w] is written organized (WIDTH w, HEIGHT h); xyz [n, 3] with rgb [n] as n x 1."""
+    xyz = np.asarray(xyz, dtype=np.float32)
+    rgb = np.asarray(rgb, dtype=np.uint32)
+    if xyz.ndim == 3:
+        height, width = xyz.shape[:2]
+    else:
+        height, width = 1, len(xyz)
+    pts = capi._pack_points(xyz, rgb)
+    capi._check(_lib().dvo_amd_write_pcd(os.fsencode(path), pts.ctypes.data, len(pts), width, height), "dvo_amd_write_pcd")

@@ -423,6 +423,71 @@ int dvo_amd_png_read_gray16(const char *path, unsigned short *dst, int width, in
  * T: column-major 4x4.  Returns the number of characters written (excluding the terminator), or -1 if capacity is too small. */
 int dvo_amd_format_trajectory_line(double timestamp, const double *T, char *buf, int capacity);
 
+/*
+ * The keyframe map's point cloud (AsyncPointCloudBuilder::BuildJob::build, async_point_cloud_builder.cpp:61-110, over
+ * RgbdCamera::buildPointCloud, rgbd_image.cpp:245-262; PointCloudAggregator::build, point_cloud_aggregator.cpp:74-109).
+ *
+ * Point record: 16 bytes, rgb packed 0x00RRGGBB the way PCL packs PointXYZRGB.
+ *
+ * Organized cloud of one image (dvo_amd_point_cloud): w*h points of the requested level in scan order, NaN points included
+ * (the reference pushes them).  Camera point (tx[u]*z, ty[v]*z, z) in fp32, z the level's depth plane (NaN where invalid),
+ * tx[u] = (u - ox) / fx and ty[v] = (v - oy) / fy the level's rays.  World point: T = (float)pose element by element, then
+ * x' = ((T00*x + T01*y) + T02*z) + T03 and the same order for y' and z', every product and sum rounded on its own (no
+ * contraction).  The reference computes the transform with Eigen's 4x4 product, whose summation order is Eigen's and is not
+ * pinned here (like Q7 / Q8): the two agree to fp32 rounding, not bit for bit.  Colour: from the caller's 8-bit BGR image of
+ * the level (w*h*3, stride in bytes) when one is given; otherwise grey from the intensity plane, r = g = b = the value clamped
+ * to [0, 255] and truncated, NaN -> 0 (the reference's implicit float -> uint8 conversion is undefined out of range).
+ *
+ * Voxel aggregate (dvo_amd_map_cloud over level 0 of every image, dvo_amd_voxel_downsample over given points):
+ *  - non-finite points are dropped;
+ *  - voxel index i = (int)floorf(x * inv) with inv = 1.0f / leaf_size in fp32, the same for j and k (pcl::VoxelGrid's rule);
+ *    a point with an index outside [-2^20, 2^20) is dropped and counted in out_of_range;
+ *  - one point per occupied voxel, in ascending order of the 63-bit key ((i+2^20)<<42) | ((j+2^20)<<21) | (k+2^20);
+ *  - centroid in fixed point: every coordinate becomes q = llrint((double)x * 2^24), summed in int64 per voxel; the output is
+ *    (float)((double)sum / ((double)count * 2^24)).  The sums are exact while the |q| of a voxel add up to less than 2^63
+ *    (2^31 points within 256 m of the origin); beyond that they wrap modulo 2^64 -- still the same bits in every run;
+ *  - colour: every channel is (sum + count/2) / count in integers.
+ * Integer sums make the result independent of the order the points arrive in: bit-identical from run to run, for any keyframe
+ * order and any launch geometry (as for match(), tests/test_determinism.py).
+ * Departure from the reference: PCL's ApproximateVoxelGrid (setDownsampleAllData(true), leaf 1 cm) keeps a 512-entry hash and
+ * flushes a voxel whenever another voxel lands on its slot, so it may emit one voxel several times and its output depends on
+ * the point order -- a sequential artefact.  This follows pcl::VoxelGrid's one point per voxel instead.
+ * leaf_size must be finite and in (0, 65536] m (DVO_AMD_ERR_INVALID_ARGUMENT otherwise: a larger leaf would let llrint leave
+ * the int64 range); at most 2^31 points per call (DVO_AMD_ERR_INVALID_ARGUMENT beyond).  When `capacity` is smaller than the number of voxels the call returns
+ * DVO_AMD_ERR_CAPACITY with stats->voxels set to the size needed (out untouched).  stats may be NULL.
+ * Like every compute entry: DVO_AMD_ERR_NO_DEVICE without a GPU, DVO_AMD_ERR_DEVICE_MISMATCH for a pyramid of another device,
+ * DVO_AMD_ERR_INVALID_ARGUMENT while pairs are queued on the context (dvo_amd_match_submit).  Buffers are the context's, grown to
+ * the largest call and kept: nothing is allocated per call once warm.
+ */
+typedef struct {
+  float x, y, z;
+  unsigned int rgb;
+} dvo_amd_point;
+
+typedef struct {
+  long long points_in;     /* points handed to the call (NaN ones included) */
+  long long finite;        /* ... of them with three finite coordinates */
+  long long out_of_range;  /* finite points dropped for a voxel index outside [-2^20, 2^20) */
+  long long voxels;        /* occupied voxels: points written, or the capacity needed */
+} dvo_amd_cloud_stats;
+
+/* pose: column-major 4x4, NULL = identity; bgr: NULL = grey from the intensity plane; out: w*h points of the level */
+int dvo_amd_point_cloud(dvo_amd_context *ctx, dvo_amd_pyramid *image, int level, const double *pose,
+                        const unsigned char *bgr, int bgr_stride_bytes, dvo_amd_point *out);
+/* the organized clouds of level 0 of n images at their poses (n x 16 doubles, column-major each), aggregated in one call.
+ * bgrs: NULL or n entries, each NULL (grey) or the image's level-0 BGR (w*h*3, bgr_strides[k] bytes per row; bgr_strides NULL:
+ * tight rows) */
+int dvo_amd_map_cloud(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *images, const double *poses,
+                      const unsigned char *const *bgrs, const int *bgr_strides, float leaf_size, dvo_amd_point *out,
+                      long long capacity, dvo_amd_cloud_stats *stats);
+int dvo_amd_voxel_downsample(dvo_amd_context *ctx, long long n, const dvo_amd_point *in, float leaf_size,
+                             dvo_amd_point *out, long long capacity, dvo_amd_cloud_stats *stats);
+
+/* Binary PCD v0.7 as pcl::io::savePCDFileBinary writes a PointXYZRGB cloud: FIELDS x y z rgb, SIZE 4 4 4 4, TYPE F F F F
+ * (rgb holds the packed bits), COUNT 1 1 1 1, WIDTH / HEIGHT as given (organized, or n x 1), VIEWPOINT 0 0 0 1 0 0 0,
+ * POINTS width*height (= n), then the records.  Host code only. */
+int dvo_amd_write_pcd(const char *path, const dvo_amd_point *points, long long n, int width, int height);
+
 /* dvo::core::computeResidualsAndValidFlagsSse (dense_tracking_impl.cpp:400-403) for one level and one float transform
  * (column-major 4x4, reference -> current).  residuals: width*height x 2 floats in pixel order, NaN where the pixel is not
  * selected or its warp is invalid.  Used by the parity tests and by dvo_amd_error_image. */

@@ -26,12 +26,15 @@
 #include <iostream>
 #include <limits>
 #include <memory>
+#include <mutex>
 #include <ostream>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../dvo_amd.h"
+
+#define DVO_AMD_MAX_DEVICES_FOR_CLOUDS 16
 
 #if !defined(DVO_AMD_NO_EIGEN) && defined(__has_include)
 #if __has_include(<Eigen/Geometry>)
@@ -209,19 +212,50 @@ class RgbdImagePyramid;
 // rgbd_image.h:146-240, as far as callers of the hot path use it: LocalTracker::update pre-builds the point cloud and the
 // 8-channel acceleration structure of every level (local_tracker.cpp:163-169).  Here every level, its derivative planes,
 // rays and gather layout are built on the GPU by RgbdImagePyramid::build, so these members have nothing left to do.
+// RgbdImage::pointcloud (rgbd_image.h: Eigen::Matrix<float, 4, Dynamic>): the level's points (x, y, z, 1) at the identity pose,
+// column-major 4 x (width * height), NaN points included.  Filled by dvo_amd_point_cloud on the first access and kept: a
+// caller that never reads it costs nothing.  The accessors the reference's readers use; no Eigen expression support.
+class PointCloudMatrix {
+ public:
+  PointCloudMatrix() : owner_(nullptr), level_(0), filled_(false) {}
+  long rows() const { return 4; }
+  inline long cols() const;
+  inline const float *data() const;
+  float operator()(long r, long c) const { return data()[c * 4 + r]; }
+
+ private:
+  friend class RgbdImagePyramid;
+  inline void fill() const;
+  const RgbdImagePyramid *owner_;
+  int level_;
+  mutable bool filled_;
+  mutable std::vector<float> xyzw_;
+};
+
 class RgbdImage {
  public:
   RgbdImage() : width(0), height(0), owner_(nullptr), level_(0) {}
   size_t width, height;
   IntrinsicMatrix intrinsics;  // of this level (RgbdCamera::intrinsics())
+  // the colour image callers attach (camera_keyframe_tracking.cpp:252): float B, G, R in 0..255, width * height pixels.  Read
+  // by AsyncPointCloudBuilder::BuildJob (include/dvo_amd/point_cloud.hpp), converted to 8 bits by the rule of dvo_amd.h
+  // (clamped to [0, 255], truncated, NaN -> 0); empty: grey from the intensity plane.
+#ifdef DVO_AMD_HAVE_OPENCV
+  cv::Mat rgb;  // CV_32FC3
+#else
+  std::vector<float> rgb;  // interleaved B, G, R
+#endif
+  PointCloudMatrix pointcloud;
   void initialize() {}
   void calculateDerivatives() {}
   bool calculateIntensityDerivatives() { return false; }
   void calculateDepthDerivatives() {}
-  void buildPointCloud() {}
+  void buildPointCloud() {}  // no-op: `pointcloud` fills itself on first access
   void buildAccelerationStructure() {}
   // host copy of one plane of this level: 0 intensity, 1 depth, 2 intensity_dx, 3 intensity_dy, 4 depth_dx, 5 depth_dy
   inline std::vector<float> plane(int which) const;
+  const RgbdImagePyramid *pyramid() const { return owner_; }  // (not in the reference) the pyramid this level belongs to
+  int level() const { return level_; }                        // ... and its index there
 
  private:
   friend class RgbdImagePyramid;
@@ -275,11 +309,13 @@ class RgbdImagePyramid {
       img.width = (size_t)w, img.height = (size_t)h;
       img.intrinsics = IntrinsicMatrix::create(k[0], k[1], k[2], k[3]);
       img.owner_ = this, img.level_ = (int)idx;
+      img.pointcloud.owner_ = this, img.pointcloud.level_ = (int)idx, img.pointcloud.filled_ = false;
     }
     return img;
   }
 
   double timestamp() const { return timestamp_; }
+  int device() const { return device_; }
   int width() const { return width_; }
   int height() const { return height_; }
   dvo_amd_pyramid *handle() const { return handle_; }
@@ -301,6 +337,45 @@ inline std::vector<float> RgbdImage::plane(int which) const {
   std::vector<float> out(width * height);
   detail::check(dvo_amd_pyramid_download_plane(owner_->handle(), level_, which, out.data()), "RgbdImage::plane");
   return out;
+}
+
+namespace cloud {
+// The context the adaptor's point-cloud calls run in when the caller has no DenseTracker to hand (RgbdImage::pointcloud, the
+// map builder of point_cloud.hpp): one per device, created on first use and kept for the life of the process with the buffers
+// of the largest cloud it built.  A context is not thread-safe: callers hold the returned lock for the duration of the call.
+inline dvo_amd_context *context(int device, std::unique_lock<std::mutex> &lock) {
+  static std::mutex mu;
+  static dvo_amd_context *ctx[DVO_AMD_MAX_DEVICES_FOR_CLOUDS] = {};
+  if (device < 0 || device >= DVO_AMD_MAX_DEVICES_FOR_CLOUDS) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "cloud_context");
+  lock = std::unique_lock<std::mutex>(mu);
+  if (!ctx[device]) ::dvo::detail::check(dvo_amd_context_create(device, nullptr, &ctx[device]), "cloud_context");
+  return ctx[device];
+}
+}  // namespace cloud
+
+inline long PointCloudMatrix::cols() const {
+  fill();
+  return (long)(xyzw_.size() / 4);
+}
+inline const float *PointCloudMatrix::data() const {
+  fill();
+  return xyzw_.data();
+}
+inline void PointCloudMatrix::fill() const {
+  if (filled_) return;
+  if (!owner_) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "RgbdImage::pointcloud");
+  int w = 0, h = 0;
+  ::dvo::detail::check(dvo_amd_pyramid_level_info(owner_->handle(), level_, &w, &h, nullptr), "RgbdImage::pointcloud");
+  std::vector<dvo_amd_point> pts((size_t)w * h);
+  {
+    std::unique_lock<std::mutex> lock;
+    dvo_amd_context *ctx = cloud::context(owner_->device(), lock);
+    ::dvo::detail::check(dvo_amd_point_cloud(ctx, owner_->handle(), level_, nullptr, nullptr, 0, pts.data()), "RgbdImage::pointcloud");
+  }
+  xyzw_.resize(pts.size() * 4);
+  for (size_t p = 0; p < pts.size(); ++p)
+    xyzw_[4 * p] = pts[p].x, xyzw_[4 * p + 1] = pts[p].y, xyzw_[4 * p + 2] = pts[p].z, xyzw_[4 * p + 3] = 1.0f;
+  filled_ = true;
 }
 
 // rgbd_image.h:39-89: the 48-byte record PointSelection::select hands out ({x, y, z, 1; I, Z, Ix, Iy, Zx, Zy, 0, 0})

@@ -1,0 +1,242 @@
+// point_cloud.hpp -- header-only C++ adaptor of the keyframe map's point cloud over the C ABI (include/dvo_amd.h):
+//   dvo::visualization::AsyncPointCloudBuilder::{PointCloud, BuildJob}   dvo_core/include/dvo/visualization/async_point_cloud_builder.h
+//   dvo::visualization::PointCloudAggregator                             dvo_core/include/dvo/visualization/point_cloud_aggregator.h
+// PCL-free: PointCloud holds PointXYZRGB records with the members callers read (points, width, height, push_back, size,
+// reserve).  A BuildJob's cloud is dvo_amd_point_cloud at the job's pose; PointCloudAggregator::build keeps the reference's
+// std::map name order and its max(n / 50, 1) step and aggregates the clouds it picks in ONE call on the GPU: dvo_amd_map_cloud
+// when every picked entry is a job on a level-0 image, dvo_amd_voxel_downsample of all of them otherwise (the same result: the
+// aggregate of the concatenated clouds).  The aggregate is dvo_amd.h's one-point-per-voxel grid, not ApproximateVoxelGrid's
+// order-dependent hash.
+#ifndef DVO_AMD_POINT_CLOUD_HPP_
+#define DVO_AMD_POINT_CLOUD_HPP_
+
+#include <cmath>
+#include <cstdint>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+#include "dense_tracking.hpp"
+
+namespace dvo {
+namespace visualization {
+
+// pcl::PointXYZRGB as far as the map's readers use it (default: the origin, black -- what PCL's constructor gives)
+struct PointXYZRGB {
+  float x, y, z;
+  std::uint8_t r, g, b;
+  PointXYZRGB() : x(0.0f), y(0.0f), z(0.0f), r(0), g(0), b(0) {}
+};
+
+namespace detail {
+inline PointXYZRGB from_record(const dvo_amd_point &p) {
+  PointXYZRGB q;
+  q.x = p.x, q.y = p.y, q.z = p.z;
+  q.r = (std::uint8_t)((p.rgb >> 16) & 0xFF), q.g = (std::uint8_t)((p.rgb >> 8) & 0xFF), q.b = (std::uint8_t)(p.rgb & 0xFF);
+  return q;
+}
+inline dvo_amd_point to_record(const PointXYZRGB &q) {
+  dvo_amd_point p;
+  p.x = q.x, p.y = q.y, p.z = q.z;
+  p.rgb = ((unsigned)q.r << 16) | ((unsigned)q.g << 8) | (unsigned)q.b;
+  return p;
+}
+// dvo_amd.h's colour rule: clamped to [0, 255], truncated, NaN -> 0
+inline unsigned char to8(float v) {
+  if (!(v == v)) return 0;
+  return (unsigned char)(v < 0.0f ? 0.0f : (v > 255.0f ? 255.0f : v));
+}
+// the image's float BGR as the 8-bit BGR the C ABI takes (empty: no colour image, grey from the intensity plane)
+inline std::vector<unsigned char> bgr8(const core::RgbdImage &image) {
+  std::vector<unsigned char> out;
+  const size_t w = image.width, h = image.height;
+#ifdef DVO_AMD_HAVE_OPENCV
+  if (image.rgb.empty()) return out;
+  if (image.rgb.type() != CV_MAKETYPE(CV_32F, 3) || (size_t)image.rgb.cols != w || (size_t)image.rgb.rows != h)
+    throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "RgbdImage::rgb (CV_32FC3 of the image's size)");
+  out.resize(w * h * 3);
+  for (size_t y = 0; y < h; ++y) {
+    const float *row = image.rgb.ptr<float>((int)y);
+    for (size_t x = 0; x < w * 3; ++x) out[y * w * 3 + x] = to8(row[x]);
+  }
+#else
+  if (image.rgb.empty()) return out;
+  if (image.rgb.size() != w * h * 3) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "RgbdImage::rgb (width * height * 3)");
+  out.resize(w * h * 3);
+  for (size_t i = 0; i < out.size(); ++i) out[i] = to8(image.rgb[i]);
+#endif
+  return out;
+}
+}  // namespace detail
+
+class AsyncPointCloudBuilder {
+ public:
+  struct PointCloud {
+    typedef PointXYZRGB PointType;
+    typedef std::shared_ptr<PointCloud> Ptr;
+    std::vector<PointXYZRGB> points;
+    std::uint32_t width, height;
+    PointCloud() : width(0), height(1) {}
+    void push_back(const PointXYZRGB &p) {
+      points.push_back(p);
+      width = (std::uint32_t)points.size(), height = 1;
+    }
+    size_t size() const { return points.size(); }
+    void reserve(size_t n) { points.reserve(n); }
+  };
+
+  // async_point_cloud_builder.h:43-54: the cloud of one image at a pose (RgbdCamera::buildPointCloud, transformed and coloured)
+  struct BuildJob {
+    typedef std::shared_ptr<BuildJob> Ptr;
+    const core::RgbdImage &image;
+    core::AffineTransformd pose;
+
+    BuildJob(const core::RgbdImage &image, const core::AffineTransformd pose = core::AffineTransformd()) : image(image), pose(pose) {}
+
+    // the organized cloud: width x height points in scan order, NaN points included (async_point_cloud_builder.cpp:61-110)
+    PointCloud::Ptr build() const {
+      std::vector<dvo_amd_point> pts;
+      records(pts);
+      PointCloud::Ptr cloud(new PointCloud);
+      cloud->points.reserve(pts.size());
+      for (size_t i = 0; i < pts.size(); ++i) cloud->points.push_back(detail::from_record(pts[i]));
+      cloud->width = (std::uint32_t)image.width, cloud->height = (std::uint32_t)image.height;
+      return cloud;
+    }
+
+    // the same cloud as the C ABI's records
+    void records(std::vector<dvo_amd_point> &out) const {
+      const core::RgbdImagePyramid *pyr = owner();
+      const std::vector<unsigned char> bgr = detail::bgr8(image);
+      out.resize(image.width * image.height);
+      std::unique_lock<std::mutex> lock;
+      dvo_amd_context *ctx = core::cloud::context(pyr->device(), lock);
+      ::dvo::detail::check(dvo_amd_point_cloud(ctx, pyr->handle(), level(), core::data(pose), bgr.empty() ? nullptr : bgr.data(),
+                                               (int)image.width * 3, out.data()),
+                           "AsyncPointCloudBuilder::BuildJob::build");
+    }
+
+    const core::RgbdImagePyramid *owner() const {
+      if (!image.pyramid()) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "BuildJob: an image that is not a pyramid level");
+      return image.pyramid();
+    }
+    int level() const { return image.level(); }
+  };
+};
+
+// point_cloud_aggregator.h:36-55 / point_cloud_aggregator.cpp:74-109
+class PointCloudAggregator {
+ public:
+  typedef AsyncPointCloudBuilder::PointCloud PointCloud;
+  typedef AsyncPointCloudBuilder::BuildJob BuildJob;
+
+  explicit PointCloudAggregator(float leaf_size = 0.01f) : leaf_(leaf_size) {}
+
+  void add(const std::string &name, const BuildJob &job) {
+    std::lock_guard<std::mutex> g(mu_);
+    entries_[name] = Entry(std::make_shared<BuildJob>(job), PointCloud::Ptr());
+  }
+  void add(const std::string &name, const PointCloud::Ptr &cloud) {
+    std::lock_guard<std::mutex> g(mu_);
+    entries_[name] = Entry(BuildJob::Ptr(), cloud);
+  }
+  void remove(const std::string &name) {
+    std::lock_guard<std::mutex> g(mu_);
+    entries_.erase(name);
+  }
+
+  PointCloud::Ptr build() {
+    std::map<std::string, Entry> local;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      local = entries_;
+    }
+    PointCloud::Ptr out(new PointCloud);
+    if (local.empty()) {  // the reference's single default point
+      out->push_back(PointXYZRGB());
+      return out;
+    }
+    const size_t step = std::max(local.size() / size_t(50), size_t(1));
+    std::vector<const Entry *> picked;
+    bool all_jobs = true;
+    size_t k = 0;
+    for (std::map<std::string, Entry>::const_iterator it = local.begin(); it != local.end(); ++it, ++k)
+      if (k % step == 0) {
+        picked.push_back(&it->second);
+        all_jobs = all_jobs && it->second.first && it->second.first->level() == 0;
+      }
+    int device = 0;
+    for (size_t i = 0; i < picked.size(); ++i)
+      if (picked[i]->first) device = picked[i]->first->owner()->device();
+    std::vector<dvo_amd_point> voxels;
+    dvo_amd_cloud_stats stats;
+    if (all_jobs) {
+      std::vector<dvo_amd_pyramid *> pyrs;
+      std::vector<double> poses;
+      std::vector<std::vector<unsigned char> > bgr(picked.size());
+      std::vector<const unsigned char *> bgr_ptr;
+      std::vector<int> strides;
+      for (size_t i = 0; i < picked.size(); ++i) {
+        const BuildJob &j = *picked[i]->first;
+        pyrs.push_back(j.owner()->handle());
+        poses.insert(poses.end(), core::data(j.pose), core::data(j.pose) + 16);
+        bgr[i] = detail::bgr8(j.image);
+        bgr_ptr.push_back(bgr[i].empty() ? nullptr : bgr[i].data());
+        strides.push_back((int)j.image.width * 3);
+      }
+      aggregate(device, "PointCloudAggregator::build", voxels, stats, [&](dvo_amd_context *ctx, dvo_amd_point *o, long long cap,
+                                                                          dvo_amd_cloud_stats *st) {
+        return dvo_amd_map_cloud(ctx, (int)pyrs.size(), pyrs.data(), poses.data(), bgr_ptr.data(), strides.data(), leaf_, o, cap,
+                                 st);
+      });
+    } else {
+      std::vector<dvo_amd_point> all, one;
+      for (size_t i = 0; i < picked.size(); ++i) {
+        if (picked[i]->first) {
+          picked[i]->first->records(one);
+          all.insert(all.end(), one.begin(), one.end());
+        } else if (picked[i]->second) {
+          const std::vector<PointXYZRGB> &p = picked[i]->second->points;
+          for (size_t q = 0; q < p.size(); ++q) all.push_back(detail::to_record(p[q]));
+        }
+      }
+      aggregate(device, "PointCloudAggregator::build", voxels, stats, [&](dvo_amd_context *ctx, dvo_amd_point *o, long long cap,
+                                                                          dvo_amd_cloud_stats *st) {
+        return dvo_amd_voxel_downsample(ctx, (long long)all.size(), all.data(), leaf_, o, cap, st);
+      });
+    }
+    out->reserve(voxels.size());
+    for (size_t i = 0; i < voxels.size(); ++i) out->points.push_back(detail::from_record(voxels[i]));
+    out->width = (std::uint32_t)voxels.size(), out->height = 1;
+    return out;
+  }
+
+ private:
+  typedef std::pair<BuildJob::Ptr, PointCloud::Ptr> Entry;
+
+  // one aggregate call, the output grown once on DVO_AMD_ERR_CAPACITY
+  template <typename Call>
+  static void aggregate(int device, const char *where, std::vector<dvo_amd_point> &out, dvo_amd_cloud_stats &stats, Call call) {
+    std::unique_lock<std::mutex> lock;
+    dvo_amd_context *ctx = core::cloud::context(device, lock);
+    out.resize(1 << 16);
+    int rc = call(ctx, out.data(), (long long)out.size(), &stats);
+    if (rc == DVO_AMD_ERR_CAPACITY) {
+      out.resize((size_t)stats.voxels);
+      rc = call(ctx, out.data(), (long long)out.size(), &stats);
+    }
+    ::dvo::detail::check(rc, where);
+    out.resize((size_t)stats.voxels);
+  }
+
+  float leaf_;
+  std::mutex mu_;
+  std::map<std::string, Entry> entries_;
+};
+
+}  // namespace visualization
+}  // namespace dvo
+
+#endif  // DVO_AMD_POINT_CLOUD_HPP_

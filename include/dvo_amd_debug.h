@@ -145,6 +145,11 @@ int dvo_amd_debug_marker(dvo_amd_context *ctx, unsigned tag);
 int dvo_amd_debug_ll_overflow(dvo_amd_context *ctx, const float *residuals, int n_blocks, int steps, int seg_first, int n_segs,
                               int rank_offset, int rank_end, int cut_rank, const float *precision, int *overflowed);
 
+/* the last dvo_amd_map_cloud / dvo_amd_voxel_downsample of the context: device time of its kernels from hipEvents inside the
+ * call (input stage, sort, reduction; host gaps between them excluded), the time of the copy of the voxels to the host, and
+ * the points it was handed.  scripts/map_cloud_timing.py */
+int dvo_amd_debug_map_timing(dvo_amd_context *ctx, double *device_ms, double *copy_ms, long long *points);
+
 #ifdef __cplusplus
 }
 #endif
