@@ -1,0 +1,1190 @@
+// The pose-graph optimizer (dvo_amd.h: dvo_amd_optimize_graph), fp64 throughout:
+//   k_linearise    one thread per edge: error, chi2, the Cauchy weights, both analytic Jacobians, the edge's three 6x6 products
+//                  and two 6-vectors into an edge-indexed record
+//   k_objective    one thread per edge: chi2, rho0, rho1 at the current estimate (F = the fixed-shape sum of rho0)
+//   k_assemble_H   one 64-lane group per 6x6 block of H (both mirror images are assembled, so H is stored full): 36 lanes own
+//                  one entry each and sum its contributors in edge order from the host's CSR list
+//   k_assemble_b   one thread per entry of b, contributors in edge order
+//   k_damp_copy    working copy of H with lambda on the diagonal (H itself stays undamped)
+//   k_potrf_panel  blocked right-looking Cholesky, 64 x 64 tiles: the diagonal tile in one workgroup (LDS); the first pivot
+//                  <= 0 is written to one device word and every later kernel of the factorization and solve returns at once
+//   k_trsm         the tiles below the diagonal tile: X L^T = A
+//   k_syrk         the trailing update A_ij -= A_ik A_jk^T with v_mfma_f64_16x16x4_f64
+//   k_trsv         forward and back substitution in one workgroup (the right-hand side in LDS)
+//   k_matvec       y = H v, one wave per row, a fixed butterfly across the wave
+//   k_dots         fixed-shape dot products (one workgroup each)
+//   k_update       X <- X * inc(x) for every free vertex
+// Every sum has one fixed order and there are no floating-point atomics: the result is bit-identical from run to run.
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <map>
+
+#include "dvo_internal.h"
+
+namespace dvo_amd {
+namespace graph {
+
+constexpr int kTile = 64;         // Cholesky tile
+constexpr int kLds = kTile + 1;   // LDS row stride of a tile (odd in doubles)
+constexpr int kBlock = 256;
+constexpr int kRecord = 132;      // doubles per edge record (k_linearise)
+constexpr int kMaxN = 6 * DVO_AMD_GRAPH_MAX_FREE_VERTICES;
+constexpr int kDotThreads = 256;
+constexpr int kMaxDots = 8;
+
+// edge record layout
+constexpr int kE = 0, kChi2 = 6, kRho0 = 7, kRho1 = 8, kAff = 9, kAtt = 45, kAft = 81, kGf = 117, kGt = 123;
+
+struct Pose {  // rotation row-major, translation
+  double R[9], t[3];
+};
+
+__device__ __host__ inline Pose load_pose(const double *T) {  // column-major 4x4
+  Pose p;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) p.R[r * 3 + c] = T[c * 4 + r];
+    p.t[r] = T[12 + r];
+  }
+  return p;
+}
+
+__device__ inline Pose inverse(const Pose &a) {
+  Pose o;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) o.R[r * 3 + c] = a.R[c * 3 + r];
+  for (int r = 0; r < 3; ++r) o.t[r] = -((o.R[r * 3 + 0] * a.t[0] + o.R[r * 3 + 1] * a.t[1]) + o.R[r * 3 + 2] * a.t[2]);
+  return o;
+}
+
+__device__ inline Pose compose(const Pose &a, const Pose &b) {
+  Pose o;
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c)
+      o.R[r * 3 + c] = (a.R[r * 3 + 0] * b.R[0 * 3 + c] + a.R[r * 3 + 1] * b.R[1 * 3 + c]) + a.R[r * 3 + 2] * b.R[2 * 3 + c];
+    o.t[r] = ((a.R[r * 3 + 0] * b.t[0] + a.R[r * 3 + 1] * b.t[1]) + a.R[r * 3 + 2] * b.t[2]) + a.t[r];
+  }
+  return o;
+}
+
+// Eigen's Quaternion(Matrix3) (Shepperd), normalised, sign with w >= 0: q = (w, x, y, z)
+__device__ inline void quaternion(const double *m, double q[4]) {
+  const double tr = (m[0] + m[4]) + m[8];
+  double w, v[3];
+  if (tr > 0.0) {
+    double t = sqrt(tr + 1.0);
+    w = 0.5 * t;
+    t = 0.5 / t;
+    v[0] = (m[7] - m[5]) * t;
+    v[1] = (m[2] - m[6]) * t;
+    v[2] = (m[3] - m[1]) * t;
+  } else {
+    int i = 0;
+    if (m[4] > m[0]) i = 1;
+    if (m[8] > m[i * 3 + i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    double t = sqrt(((m[i * 3 + i] - m[j * 3 + j]) - m[k * 3 + k]) + 1.0);
+    v[i] = 0.5 * t;
+    t = 0.5 / t;
+    w = (m[k * 3 + j] - m[j * 3 + k]) * t;
+    v[j] = (m[j * 3 + i] + m[i * 3 + j]) * t;
+    v[k] = (m[k * 3 + i] + m[i * 3 + k]) * t;
+  }
+  const double nrm = sqrt(((w * w + v[0] * v[0]) + v[1] * v[1]) + v[2] * v[2]);
+  double s = 1.0 / nrm;
+  if (w < 0.0) s = -s;
+  q[0] = w * s;
+  q[1] = v[0] * s;
+  q[2] = v[1] * s;
+  q[3] = v[2] * s;
+}
+
+// inc(d): translation d[0..2], rotation of (sqrt(1 - |d[3..5]|^2), d[3..5]) (identity when 1 - |q|^2 < 0)
+__device__ inline Pose increment(const double *d) {
+  Pose p;
+  const double x = d[3], y = d[4], z = d[5];
+  const double w2 = 1.0 - ((x * x + y * y) + z * z);
+  if (w2 < 0.0) {
+    for (int i = 0; i < 9; ++i) p.R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  } else {
+    const double w = sqrt(w2);
+    p.R[0] = 1.0 - 2.0 * (y * y + z * z);
+    p.R[1] = 2.0 * (x * y - z * w);
+    p.R[2] = 2.0 * (x * z + y * w);
+    p.R[3] = 2.0 * (x * y + z * w);
+    p.R[4] = 1.0 - 2.0 * (x * x + z * z);
+    p.R[5] = 2.0 * (y * z - x * w);
+    p.R[6] = 2.0 * (x * z - y * w);
+    p.R[7] = 2.0 * (y * z + x * w);
+    p.R[8] = 1.0 - 2.0 * (x * x + y * y);
+  }
+  p.t[0] = d[0];
+  p.t[1] = d[1];
+  p.t[2] = d[2];
+  return p;
+}
+
+// Delta = Z^-1 * (X_from^-1 * X_to), e = (t, q_xyz), chi2 = e^T O e
+struct EdgeEval {
+  Pose Zi, D;
+  double q[4], e[6], chi2;
+};
+
+__device__ inline void eval_edge(const dvo_amd_graph_edge &E, const double *poses, EdgeEval &v) {
+  const Pose Xf = load_pose(poses + 16 * (size_t)E.from), Xt = load_pose(poses + 16 * (size_t)E.to);
+  v.Zi = inverse(load_pose(E.measurement));
+  v.D = compose(v.Zi, compose(inverse(Xf), Xt));
+  quaternion(v.D.R, v.q);
+  for (int i = 0; i < 3; ++i) {
+    v.e[i] = v.D.t[i];
+    v.e[3 + i] = v.q[1 + i];
+  }
+  double chi2 = 0.0;
+  for (int i = 0; i < 6; ++i) {
+    double oe = 0.0;
+    for (int j = 0; j < 6; ++j) oe += E.information[j * 6 + i] * v.e[j];
+    chi2 += v.e[i] * oe;
+  }
+  v.chi2 = chi2;
+}
+
+__device__ inline void robust(double chi2, double delta, double *rho0, double *rho1) {
+  if (delta > 0.0) {
+    const double dsqr = delta * delta;
+    const double aux = (1.0 / dsqr) * chi2 + 1.0;
+    *rho0 = dsqr * log(aux);
+    *rho1 = 1.0 / aux;
+  } else {
+    *rho0 = chi2;
+    *rho1 = 1.0;
+  }
+}
+
+__global__ void k_objective(int n_edges, const dvo_amd_graph_edge *__restrict__ edges, const double *__restrict__ poses,
+                            double delta, double *__restrict__ rho0, double *__restrict__ chi2, double *__restrict__ rho1) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_edges) return;
+  EdgeEval v;
+  eval_edge(edges[k], poses, v);
+  double r0, r1;
+  robust(v.chi2, delta, &r0, &r1);
+  rho0[k] = r0;
+  chi2[k] = v.chi2;
+  rho1[k] = r1;
+}
+
+__global__ void __launch_bounds__(64) k_linearise(int n_edges, const dvo_amd_graph_edge *__restrict__ edges,
+                                                  const double *__restrict__ poses, double delta, double *__restrict__ rec) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_edges) return;
+  const dvo_amd_graph_edge &E = edges[k];
+  EdgeEval v;
+  eval_edge(E, poses, v);
+  double r0, r1;
+  robust(v.chi2, delta, &r0, &r1);
+  double *o = rec + (size_t)k * kRecord;
+  for (int i = 0; i < 6; ++i) o[kE + i] = v.e[i];
+  o[kChi2] = v.chi2;
+  o[kRho0] = r0;
+  o[kRho1] = r1;
+
+  // Jacobians, row-major 6x6 (rows t, q_xyz; columns translation, quaternion part of the increment)
+  double Jf[36], Jt[36];
+  const double w = v.q[0], qv[3] = {v.q[1], v.q[2], v.q[3]};
+  const double *R = v.D.R, *t = v.D.t;
+  const double *RzT = v.Zi.R;  // rotation of Z^-1 = Rz^T
+  const Pose Z = load_pose(E.measurement);
+  const double *tz = Z.t;
+  for (int i = 0; i < 36; ++i) Jf[i] = Jt[i] = 0.0;
+  // J_to = [R 0; 0 wI + [v]x]
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Jt[r * 6 + c] = R[r * 3 + c];
+  const double vx[9] = {0.0, -qv[2], qv[1], qv[2], 0.0, -qv[0], -qv[1], qv[0], 0.0};
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) Jt[(3 + r) * 6 + 3 + c] = (r == c ? w : 0.0) + vx[r * 3 + c];
+  // J_from = [-Rz^T  2([t]x Rz^T + Rz^T [tz]x); 0  -(wI - [v]x) Rz^T]
+  const double txm[9] = {0.0, -t[2], t[1], t[2], 0.0, -t[0], -t[1], t[0], 0.0};
+  const double tzm[9] = {0.0, -tz[2], tz[1], tz[2], 0.0, -tz[0], -tz[1], tz[0], 0.0};
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      Jf[r * 6 + c] = -RzT[r * 3 + c];
+      double a = 0.0, b = 0.0, m = 0.0;
+      for (int p = 0; p < 3; ++p) {
+        a += txm[r * 3 + p] * RzT[p * 3 + c];
+        b += RzT[r * 3 + p] * tzm[p * 3 + c];
+        m += ((r == p ? w : 0.0) - vx[r * 3 + p]) * RzT[p * 3 + c];
+      }
+      Jf[r * 6 + 3 + c] = 2.0 * (a + b);
+      Jf[(3 + r) * 6 + 3 + c] = -m;
+    }
+  // W = rho1 Omega (Omega column-major, symmetric); WJ = W J; products J_a^T W J_b; g = -J^T W e
+  double W[36], We[6];
+  for (int r = 0; r < 6; ++r)
+    for (int c = 0; c < 6; ++c) W[r * 6 + c] = r1 * E.information[c * 6 + r];
+  for (int r = 0; r < 6; ++r) {
+    double s = 0.0;
+    for (int c = 0; c < 6; ++c) s += W[r * 6 + c] * v.e[c];
+    We[r] = s;
+  }
+  double WJ[36];
+  for (int which = 0; which < 2; ++which) {
+    const double *J = which ? Jt : Jf;
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) {
+        double s = 0.0;
+        for (int p = 0; p < 6; ++p) s += W[r * 6 + p] * J[p * 6 + c];
+        WJ[r * 6 + c] = s;
+      }
+    // which = 0: Aff = Jf^T W Jf; which = 1: Att = Jt^T W Jt and Aft = Jf^T W Jt
+    for (int r = 0; r < 6; ++r)
+      for (int c = 0; c < 6; ++c) {
+        double s = 0.0;
+        for (int p = 0; p < 6; ++p) s += J[p * 6 + r] * WJ[p * 6 + c];
+        o[(which ? kAtt : kAff) + r * 6 + c] = s;
+        if (which) {
+          double u = 0.0;
+          for (int p = 0; p < 6; ++p) u += Jf[p * 6 + r] * WJ[p * 6 + c];
+          o[kAft + r * 6 + c] = u;
+        }
+      }
+    for (int r = 0; r < 6; ++r) {
+      double s = 0.0;
+      for (int p = 0; p < 6; ++p) s += J[p * 6 + r] * We[p];
+      o[(which ? kGt : kGf) + r] = -s;
+    }
+  }
+}
+
+// contributor codes: edge * 4 + kind; kind 0 Aff, 1 Att, 2 Aft, 3 Aft^T
+__global__ void __launch_bounds__(64) k_assemble_H(const int2 *__restrict__ block_rc, const int *__restrict__ ptr,
+                                                   const int *__restrict__ contrib, const double *__restrict__ rec,
+                                                   double *__restrict__ H, int N) {
+  const int blk = blockIdx.x, lane = threadIdx.x;
+  if (lane >= 36) return;
+  const int r = lane / 6, c = lane % 6;
+  double s = 0.0;
+  for (int p = ptr[blk]; p < ptr[blk + 1]; ++p) {
+    const int code = contrib[p], kind = code & 3;
+    const double *o = rec + (size_t)(code >> 2) * kRecord;
+    const double v = kind == 0 ? o[kAff + r * 6 + c] : kind == 1 ? o[kAtt + r * 6 + c] : kind == 2 ? o[kAft + r * 6 + c]
+                                                                                                   : o[kAft + c * 6 + r];
+    s += v;
+  }
+  const int2 rc = block_rc[blk];
+  H[(size_t)(6 * rc.x + r) * N + 6 * rc.y + c] = s;
+}
+
+// contributor codes: edge * 2 + (0 from, 1 to)
+__global__ void k_assemble_b(int n, const int *__restrict__ ptr, const int *__restrict__ contrib,
+                             const double *__restrict__ rec, double *__restrict__ b) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int slot = i / 6, r = i % 6;
+  double s = 0.0;
+  for (int p = ptr[slot]; p < ptr[slot + 1]; ++p) {
+    const int code = contrib[p];
+    s += rec[(size_t)(code >> 1) * kRecord + ((code & 1) ? kGt : kGf) + r];
+  }
+  b[i] = s;
+}
+
+__global__ void k_pad_diag(double *H, int N, int n) {
+  const int i = n + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < N) H[(size_t)i * N + i] = 1.0;
+}
+
+__global__ void k_damp_copy(const double *__restrict__ H, double *__restrict__ L, int N, int n, double lambda, int damp) {
+  const size_t total = (size_t)N * N;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    double v = H[i];
+    const size_t r = i / N, c = i % N;
+    if (damp && r == c && r < (size_t)n) v = v + lambda;
+    L[i] = v;
+  }
+}
+
+__global__ void k_max_diag(const double *__restrict__ H, int N, int n, double *out) {
+  __shared__ double red[kBlock];
+  double m = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) m = fmax(m, fabs(H[(size_t)i * N + i]));
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = kBlock / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = red[0];
+}
+
+// diagonal tile k: unblocked right-looking Cholesky in LDS
+__global__ void __launch_bounds__(kBlock) k_potrf_panel(double *L, int N, int k, int *flag) {
+  if (*(volatile int *)flag >= 0) return;
+  __shared__ double A[kTile * kLds];
+  __shared__ int bad;
+  const int tid = threadIdx.x, base = k * kTile;
+  for (int e = tid; e < kTile * kTile; e += kBlock) {
+    const int r = e / kTile, c = e % kTile;
+    A[r * kLds + c] = L[(size_t)(base + r) * N + base + c];
+  }
+  if (tid == 0) bad = -1;
+  __syncthreads();
+  for (int j = 0; j < kTile; ++j) {
+    const double piv = A[j * kLds + j];
+    if (!(piv > 0.0)) {  // uniform: every thread read the same LDS word
+      if (tid == 0) *flag = base + j;
+      return;
+    }
+    const double d = sqrt(piv);
+    __syncthreads();  // everyone has read the pivot before it is overwritten
+    if (tid == 0) A[j * kLds + j] = d;
+    if (tid > j && tid < kTile) A[tid * kLds + j] = A[tid * kLds + j] / d;
+    __syncthreads();
+    const int rem = kTile - 1 - j;
+    for (int e = tid; e < rem * rem; e += kBlock) {
+      const int r = j + 1 + e / rem, c = j + 1 + e % rem;
+      if (c <= r) A[r * kLds + c] = A[r * kLds + c] - A[r * kLds + j] * A[c * kLds + j];
+    }
+    __syncthreads();
+  }
+  (void)bad;
+  for (int e = tid; e < kTile * kTile; e += kBlock) {
+    const int r = e / kTile, c = e % kTile;
+    if (c <= r) L[(size_t)(base + r) * N + base + c] = A[r * kLds + c];
+  }
+}
+
+// tiles (i, k), i > k: X L_kk^T = A_ik
+__global__ void __launch_bounds__(kBlock) k_trsm(double *L, int N, int k, const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  __shared__ double D[kTile * kLds];
+  __shared__ double A[kTile * kLds];
+  const int tid = threadIdx.x, kb = k * kTile, ib = (k + 1 + blockIdx.x) * kTile;
+  for (int e = tid; e < kTile * kTile; e += kBlock) {
+    const int r = e / kTile, c = e % kTile;
+    D[r * kLds + c] = L[(size_t)(kb + r) * N + kb + c];
+    A[r * kLds + c] = L[(size_t)(ib + r) * N + kb + c];
+  }
+  __syncthreads();
+  for (int j = 0; j < kTile; ++j) {
+    if (tid < kTile) A[tid * kLds + j] = A[tid * kLds + j] / D[j * kLds + j];
+    __syncthreads();
+    const int rem = kTile - 1 - j;
+    for (int e = tid; e < kTile * rem; e += kBlock) {
+      const int r = e / rem, c = j + 1 + e % rem;
+      A[r * kLds + c] = A[r * kLds + c] - A[r * kLds + j] * D[c * kLds + j];
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < kTile * kTile; e += kBlock) {
+    const int r = e / kTile, c = e % kTile;
+    L[(size_t)(ib + r) * N + kb + c] = A[r * kLds + c];
+  }
+}
+
+typedef double double4_t __attribute__((ext_vector_type(4)));
+
+// tiles (i, j), k < j <= i: A_ij -= A_ik A_jk^T.  4 waves, each a 32 x 32 quarter = 2 x 2 MFMA 16x16 tiles; K in two halves.
+// v_mfma_f64_16x16x4_f64: lane l gives A[row l&15][k l>>4] and B[k l>>4][col l&15]; D[row (l>>4) + 4 reg][col l&15].
+__global__ void __launch_bounds__(kBlock) k_syrk(double *L, int N, int k, const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  const int j = k + 1 + blockIdx.x, i = k + 1 + blockIdx.y;
+  if (j > i) return;
+  constexpr int kHalf = kTile / 2, kS = kHalf + 1;
+  __shared__ double Ai[kTile * kS];
+  __shared__ double Aj[kTile * kS];
+  const int tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
+  const int kb = k * kTile, ib = i * kTile, jb = j * kTile;
+  const int r0 = 32 * (wave >> 1), c0 = 32 * (wave & 1);
+  double4_t acc[2][2];
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  for (int h = 0; h < 2; ++h) {
+    __syncthreads();
+    for (int e = tid; e < kTile * kHalf; e += kBlock) {
+      const int r = e / kHalf, c = e % kHalf;
+      Ai[r * kS + c] = L[(size_t)(ib + r) * N + kb + h * kHalf + c];
+      Aj[r * kS + c] = L[(size_t)(jb + r) * N + kb + h * kHalf + c];
+    }
+    __syncthreads();
+    for (int kk = 0; kk < kHalf; kk += 4) {
+      const int kl = kk + (lane >> 4);
+      for (int a = 0; a < 2; ++a) {
+        const double av = Ai[(r0 + 16 * a + (lane & 15)) * kS + kl];
+        for (int b = 0; b < 2; ++b) {
+          const double bv = Aj[(c0 + 16 * b + (lane & 15)) * kS + kl];
+          acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[a][b], 0, 0, 0);
+        }
+      }
+    }
+  }
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b)
+      for (int reg = 0; reg < 4; ++reg) {
+        const int r = r0 + 16 * a + (lane >> 4) + 4 * reg, c = c0 + 16 * b + (lane & 15);
+        double *p = L + (size_t)(ib + r) * N + jb + c;
+        *p = *p - acc[a][b][reg];
+      }
+}
+
+// L y = b, L^T x = y in one workgroup; x may alias nothing else.  The right-hand side lives in LDS.
+constexpr int kSolveThreads = 1024;
+__global__ void __launch_bounds__(kSolveThreads) k_trsv(const double *__restrict__ L, int N, const double *__restrict__ b,
+                                                        double *__restrict__ x, const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  __shared__ double r[kMaxN + kTile];
+  const int tid = threadIdx.x, lane = tid % 64, T = N / kTile;
+  for (int i = tid; i < N; i += kSolveThreads) r[i] = b[i];
+  __syncthreads();
+  for (int k = 0; k < T; ++k) {  // forward
+    const int kb = k * kTile;
+    if (tid < 64) {
+      double ri = r[kb + lane];
+      for (int j = 0; j < kTile; ++j) {
+        if (lane == j) ri = ri / L[(size_t)(kb + j) * N + kb + j];
+        const double yj = __shfl(ri, j);
+        if (lane > j) ri = ri - L[(size_t)(kb + lane) * N + kb + j] * yj;
+      }
+      r[kb + lane] = ri;
+    }
+    __syncthreads();
+    for (int i = kb + kTile + tid; i < N; i += kSolveThreads) {
+      double s = r[i];
+      const double *row = L + (size_t)i * N + kb;
+      for (int p = 0; p < kTile; ++p) s = s - row[p] * r[kb + p];
+      r[i] = s;
+    }
+    __syncthreads();
+  }
+  for (int k = T - 1; k >= 0; --k) {  // backward
+    const int kb = k * kTile;
+    if (tid < 64) {
+      double ri = r[kb + lane];
+      for (int j = kTile - 1; j >= 0; --j) {
+        if (lane == j) ri = ri / L[(size_t)(kb + j) * N + kb + j];
+        const double yj = __shfl(ri, j);
+        if (lane < j) ri = ri - L[(size_t)(kb + j) * N + kb + lane] * yj;
+      }
+      r[kb + lane] = ri;
+    }
+    __syncthreads();
+    for (int i = tid; i < kb; i += kSolveThreads) {
+      double s = r[i];
+      for (int p = 0; p < kTile; ++p) s = s - L[(size_t)(kb + p) * N + i] * r[kb + p];
+      r[i] = s;
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < N; i += kSolveThreads) x[i] = r[i];
+}
+
+// y = H v over the n real rows (H stored full); one wave per row, lanes stride the columns, then a fixed butterfly
+__global__ void __launch_bounds__(kBlock) k_matvec(const double *__restrict__ H, int N, int n, const double *__restrict__ v,
+                                                   double *__restrict__ y) {
+  const int row = blockIdx.x * (kBlock / 64) + threadIdx.x / 64, lane = threadIdx.x % 64;
+  if (row >= n) return;
+  const double *h = H + (size_t)row * N;
+  double s = 0.0;
+  for (int c = lane; c < n; c += 64) s += h[c] * v[c];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) y[row] = s;
+}
+
+struct DotArgs {
+  const double *a[kMaxDots], *b[kMaxDots];  // b null: sum of a; b == a: squared norm
+  double lambda[kMaxDots];                  // mode 1 entries: sum a (lambda a + b)
+  int mode[kMaxDots];
+  int n[kMaxDots];
+};
+
+__global__ void __launch_bounds__(kDotThreads) k_dots(DotArgs args, double *out) {
+  __shared__ double red[kDotThreads];
+  const int d = blockIdx.x, tid = threadIdx.x, n = args.n[d];
+  const double *a = args.a[d], *b = args.b[d];
+  double s = 0.0;
+  for (int i = tid; i < n; i += kDotThreads) {
+    if (args.mode[d] == 1)
+      s += a[i] * (args.lambda[d] * a[i] + b[i]);
+    else
+      s += b ? a[i] * b[i] : a[i];
+  }
+  red[tid] = s;
+  __syncthreads();
+  for (int h = kDotThreads / 2; h > 0; h >>= 1) {
+    if (tid < h) red[tid] = red[tid] + red[tid + h];
+    __syncthreads();
+  }
+  if (tid == 0) out[d] = red[0];
+}
+
+// out = alpha x (mode 0), x + beta (y - x) (mode 1), x - y (mode 2)
+__global__ void k_vec(int n, int mode, double alpha, const double *__restrict__ x, const double *__restrict__ y,
+                      double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = mode == 0 ? alpha * x[i] : mode == 1 ? x[i] + alpha * (y[i] - x[i]) : x[i] - y[i];
+}
+
+// X <- X * inc(x) for every free vertex (skipped when the solve behind x failed)
+__global__ void k_update(int m, const int *__restrict__ vertex_of, const double *__restrict__ x, double *__restrict__ poses,
+                         const int *flag) {
+  if (flag && *(volatile const int *)flag >= 0) return;
+  const int s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= m) return;
+  double *T = poses + 16 * (size_t)vertex_of[s];
+  const Pose X = load_pose(T), D = increment(x + 6 * s);
+  const Pose Y = compose(X, D);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) T[c * 4 + r] = Y.R[r * 3 + c];
+    T[12 + r] = Y.t[r];
+  }
+}
+
+inline int grid_for(size_t n, int block) { return (int)std::max<size_t>(1, (n + block - 1) / block); }
+
+}  // namespace graph
+
+namespace host {
+
+struct GraphWorkspace {
+  struct Buf {
+    void *p = nullptr;
+    size_t bytes = 0;
+  };
+  Buf poses, saved, edges, rec, rho0, chi2, rho1, H, L, b, x, hsd, hdl, aux, block_rc, block_ptr, block_c, b_ptr, b_c,
+      vertex_of, scalars, flag;
+  hipEvent_t ev[4] = {};
+  double lin_ms = 0.0, fac_ms = 0.0;
+  int n_padded = 0, factorizations = 0;
+};
+
+namespace {
+
+int grow(GraphWorkspace::Buf &b, size_t bytes) {
+  if (bytes <= b.bytes) return DVO_AMD_OK;
+  if (b.p) (void)hipFree(b.p), b.p = nullptr, b.bytes = 0;
+  bytes = align_up(std::max<size_t>(bytes, 256), 1 << 12);
+  const hipError_t e = hipMalloc(&b.p, bytes);
+  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
+  if (e != hipSuccess) return fail_hip("hipMalloc (graph workspace)", e);
+  b.bytes = bytes;
+  return DVO_AMD_OK;
+}
+
+int workspace(dvo_amd_context *ctx, GraphWorkspace **out) {
+  if (!ctx->graph_ws) {
+    GraphWorkspace *w = new GraphWorkspace();
+    ctx->graph_ws = w;
+    for (hipEvent_t &e : w->ev) HIP_TRY(hipEventCreate(&e));
+  }
+  *out = ctx->graph_ws;
+  return DVO_AMD_OK;
+}
+
+bool finite_all(const double *p, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(p[i])) return false;
+  return true;
+}
+
+int check_arguments(int n_vertices, const double *poses, int n_edges, const dvo_amd_graph_edge *edges,
+                    const dvo_amd_graph_options *opt) {
+  auto bad = [](const std::string &why) {
+    g_last_error = "dvo_amd_optimize_graph: " + why;
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  };
+  if (n_vertices < 0 || n_edges < 0 || !opt || (n_vertices > 0 && !poses) || (n_edges > 0 && !edges))
+    return bad("null pointer or negative count");
+  if (opt->algorithm != DVO_AMD_GRAPH_LEVENBERG && opt->algorithm != DVO_AMD_GRAPH_DOGLEG) return bad("unknown algorithm");
+  if (opt->max_iterations < 0 || opt->max_trials < 1) return bad("max_iterations < 0 or max_trials < 1");
+  if (!std::isfinite(opt->robust_delta) || !std::isfinite(opt->initial_lambda) || !std::isfinite(opt->initial_delta))
+    return bad("non-finite option");
+  for (int v = 0; v < n_vertices; ++v)
+    if (!finite_all(poses + 16 * (size_t)v, 16)) return bad("non-finite pose of vertex " + std::to_string(v));
+  for (int k = 0; k < n_edges; ++k) {
+    const dvo_amd_graph_edge &E = edges[k];
+    const std::string id = " (edge " + std::to_string(k) + ")";
+    if (E.from < 0 || E.from >= n_vertices || E.to < 0 || E.to >= n_vertices) return bad("vertex index out of range" + id);
+    if (E.from == E.to) return bad("from == to" + id);
+    if (!finite_all(E.measurement, 16) || !finite_all(E.information, 36)) return bad("non-finite measurement or information" + id);
+    for (int r = 0; r < 6; ++r)
+      for (int c = r + 1; c < 6; ++c) {
+        const double a = E.information[c * 6 + r], b = E.information[r * 6 + c];
+        if (std::fabs(a - b) > 1e-9 * std::max(std::max(std::fabs(a), std::fabs(b)), 1e-300))
+          return bad("information matrix not symmetric" + id);
+      }
+  }
+  return DVO_AMD_OK;
+}
+
+// one call: the device state and the host's view of the scalars
+struct Solver {
+  GraphWorkspace &W;
+  hipStream_t st;
+  int n_vertices, n_edges, m, n, N, nblocks;
+  double delta;
+  int cholesky_failures = 0;
+  bool timed_lin = false, timed_fac = false;
+
+  double *poses() { return (double *)W.poses.p; }
+  double *H() { return (double *)W.H.p; }
+  double *L() { return (double *)W.L.p; }
+  double *b() { return (double *)W.b.p; }
+  double *x() { return (double *)W.x.p; }
+  double *hsd() { return (double *)W.hsd.p; }
+  double *hdl() { return (double *)W.hdl.p; }
+  double *aux() { return (double *)W.aux.p; }
+  int *flag() { return (int *)W.flag.p; }
+  double *scalars() { return (double *)W.scalars.p; }
+
+  int objective_enqueue() {
+    if (n_edges > 0)
+      hipLaunchKernelGGL(graph::k_objective, dim3(graph::grid_for(n_edges, 64)), dim3(64), 0, st, n_edges,
+                         (const dvo_amd_graph_edge *)W.edges.p, poses(), delta, (double *)W.rho0.p, (double *)W.chi2.p,
+                         (double *)W.rho1.p);
+    HIP_TRY(hipGetLastError());
+    return DVO_AMD_OK;
+  }
+
+  // up to kMaxDots reductions into scalars[slot..]; {a, b, mode, lambda}
+  struct Dot {
+    const double *a, *b;
+    int mode;
+    double lambda;
+    int n;
+  };
+  int dots_enqueue(std::initializer_list<Dot> list, int first_slot) {
+    graph::DotArgs args;
+    std::memset(&args, 0, sizeof(args));
+    int d = 0;
+    for (const Dot &x : list) {
+      args.a[d] = x.a;
+      args.b[d] = x.b;
+      args.mode[d] = x.mode;
+      args.lambda[d] = x.lambda;
+      args.n[d] = x.n;
+      ++d;
+    }
+    hipLaunchKernelGGL(graph::k_dots, dim3(d), dim3(graph::kDotThreads), 0, st, args, scalars() + first_slot);
+    HIP_TRY(hipGetLastError());
+    return DVO_AMD_OK;
+  }
+
+  // reads scalars[0..count) and the factorization flag
+  int read(double *s, int count, int *flag_out) {
+    if (count > 0) HIP_TRY(hipMemcpyAsync(s, scalars(), sizeof(double) * count, hipMemcpyDeviceToHost, st));
+    int f = -1;
+    if (flag_out) HIP_TRY(hipMemcpyAsync(&f, flag(), sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (flag_out) *flag_out = f;
+    return DVO_AMD_OK;
+  }
+
+  // F at the current estimate
+  int objective(double *F) {
+    int rc = objective_enqueue();
+    if (!rc) rc = dots_enqueue({{(const double *)W.rho0.p, nullptr, 0, 0.0, n_edges}}, 0);
+    if (!rc) rc = read(F, 1, nullptr);
+    return rc;
+  }
+
+  int linearise() {
+    if (!timed_lin) HIP_TRY(hipEventRecord(W.ev[0], st));
+    hipLaunchKernelGGL(graph::k_linearise, dim3(graph::grid_for(n_edges, 64)), dim3(64), 0, st, n_edges,
+                       (const dvo_amd_graph_edge *)W.edges.p, poses(), delta, (double *)W.rec.p);
+    hipLaunchKernelGGL(graph::k_assemble_H, dim3(nblocks), dim3(64), 0, st, (const int2 *)W.block_rc.p,
+                       (const int *)W.block_ptr.p, (const int *)W.block_c.p, (const double *)W.rec.p, H(), N);
+    hipLaunchKernelGGL(graph::k_assemble_b, dim3(graph::grid_for(n, 256)), dim3(256), 0, st, n, (const int *)W.b_ptr.p,
+                       (const int *)W.b_c.p, (const double *)W.rec.p, b());
+    HIP_TRY(hipGetLastError());
+    if (!timed_lin) HIP_TRY(hipEventRecord(W.ev[1], st));
+    return DVO_AMD_OK;
+  }
+
+  // (H + lambda I) x = b (damp) or H x = b into `out`; the flag word says whether a pivot failed (read by the caller)
+  int factor_solve_enqueue(bool damp, double lambda, double *out) {
+    if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[2], st));
+    HIP_TRY(hipMemsetAsync(flag(), 0xff, sizeof(int), st));
+    hipLaunchKernelGGL(graph::k_damp_copy, dim3(std::min(4096, graph::grid_for((size_t)N * N, 256))), dim3(256), 0, st,
+                       (const double *)H(), L(), N, n, lambda, damp ? 1 : 0);
+    const int T = N / graph::kTile;
+    for (int k = 0; k < T; ++k) {
+      hipLaunchKernelGGL(graph::k_potrf_panel, dim3(1), dim3(graph::kBlock), 0, st, L(), N, k, flag());
+      if (k + 1 < T) {
+        hipLaunchKernelGGL(graph::k_trsm, dim3(T - k - 1), dim3(graph::kBlock), 0, st, L(), N, k, (const int *)flag());
+        hipLaunchKernelGGL(graph::k_syrk, dim3(T - k - 1, T - k - 1), dim3(graph::kBlock), 0, st, L(), N, k,
+                           (const int *)flag());
+      }
+    }
+    HIP_TRY(hipGetLastError());
+    if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[3], st));
+    hipLaunchKernelGGL(graph::k_trsv, dim3(1), dim3(graph::kSolveThreads), 0, st, (const double *)L(), N,
+                       (const double *)b(), out, (const int *)flag());
+    HIP_TRY(hipGetLastError());
+    ++W.factorizations;
+    return DVO_AMD_OK;
+  }
+
+  void note_failure(int f) {
+    if (f >= 0) ++cholesky_failures;
+  }
+
+  int push() {
+    HIP_TRY(hipMemcpyAsync(W.saved.p, W.poses.p, 16 * sizeof(double) * (size_t)n_vertices, hipMemcpyDeviceToDevice, st));
+    return DVO_AMD_OK;
+  }
+  int pop() {
+    HIP_TRY(hipMemcpyAsync(W.poses.p, W.saved.p, 16 * sizeof(double) * (size_t)n_vertices, hipMemcpyDeviceToDevice, st));
+    return DVO_AMD_OK;
+  }
+  int update_enqueue(const double *step, bool guarded) {
+    hipLaunchKernelGGL(graph::k_update, dim3(graph::grid_for(m, 64)), dim3(64), 0, st, m, (const int *)W.vertex_of.p, step,
+                       poses(), guarded ? (const int *)flag() : nullptr);
+    HIP_TRY(hipGetLastError());
+    return DVO_AMD_OK;
+  }
+  int vec(int mode, double alpha, const double *x_, const double *y_, double *out) {
+    hipLaunchKernelGGL(graph::k_vec, dim3(graph::grid_for(n, 256)), dim3(256), 0, st, n, mode, alpha, x_, y_, out);
+    HIP_TRY(hipGetLastError());
+    return DVO_AMD_OK;
+  }
+  int matvec(const double *v, double *y) {
+    hipLaunchKernelGGL(graph::k_matvec, dim3(graph::grid_for(n, graph::kBlock / 64)), dim3(graph::kBlock), 0, st,
+                       (const double *)H(), N, n, v, y);
+    HIP_TRY(hipGetLastError());
+    return DVO_AMD_OK;
+  }
+};
+
+void record(dvo_amd_graph_iteration *iterations, int capacity, int it, double F, double step, double lambda, double delta,
+            int trials, int accepted) {
+  if (!iterations || it >= capacity) return;
+  dvo_amd_graph_iteration &r = iterations[it];
+  r.objective = F;
+  r.step_norm = step;
+  r.lambda = lambda;
+  r.delta = delta;
+  r.trials = trials;
+  r.accepted = accepted;
+}
+
+#define GRAPH_TRY(expr)       \
+  do {                        \
+    const int rc_ = (expr);   \
+    if (rc_) return rc_;      \
+  } while (0)
+
+// OptimizationAlgorithmLevenberg::solve, max_iterations times
+int run_levenberg(Solver &S, const dvo_amd_graph_options &opt, double *F, dvo_amd_graph_iteration *iterations, int capacity,
+                  dvo_amd_graph_stats &stats) {
+  double lambda = 0.0, nu = 2.0;
+  for (int it = 0; it < opt.max_iterations; ++it) {
+    GRAPH_TRY(S.linearise());
+    if (it == 0) {
+      if (opt.initial_lambda > 0.0) {
+        lambda = opt.initial_lambda;
+      } else {
+        hipLaunchKernelGGL(graph::k_max_diag, dim3(1), dim3(graph::kBlock), 0, S.st, (const double *)S.H(), S.N, S.n,
+                           S.scalars());
+        HIP_TRY(hipGetLastError());
+        double md = 0.0;
+        GRAPH_TRY(S.read(&md, 1, nullptr));
+        lambda = 1e-5 * md;
+      }
+      nu = 2.0;
+    }
+    int trials = 0;
+    double rho = 0.0, step = 0.0;
+    int accepted = 0;
+    do {
+      GRAPH_TRY(S.push());
+      GRAPH_TRY(S.factor_solve_enqueue(true, lambda, S.x()));
+      GRAPH_TRY(S.update_enqueue(S.x(), true));
+      GRAPH_TRY(S.objective_enqueue());
+      GRAPH_TRY(S.dots_enqueue({{(const double *)S.W.rho0.p, nullptr, 0, 0.0, S.n_edges},
+                                {S.x(), S.b(), 1, lambda, S.n},
+                                {S.x(), S.x(), 0, 0.0, S.n}},
+                               0));
+      double s[3];
+      int f = -1;
+      GRAPH_TRY(S.read(s, 3, &f));
+      S.timed_lin = S.timed_fac = true;
+      S.note_failure(f);
+      const bool ok = f < 0;
+      const double Fp = ok ? s[0] : std::numeric_limits<double>::infinity();
+      rho = ok ? (*F - Fp) / (s[1] + 1e-3) : -std::numeric_limits<double>::infinity();
+      if (rho > 0.0 && std::isfinite(Fp)) {
+        const double alpha = std::min(1.0 - std::pow(2.0 * rho - 1.0, 3), 2.0 / 3.0);
+        lambda *= std::max(1.0 / 3.0, alpha);
+        nu = 2.0;
+        *F = Fp;
+        step = std::sqrt(s[2]);
+        accepted = 1;
+      } else {
+        lambda *= nu;
+        nu *= 2.0;
+        if (ok) GRAPH_TRY(S.pop());
+        if (!std::isfinite(lambda)) break;  // before the attempt is counted, as g2o does
+      }
+      ++trials;
+    } while (rho < 0.0 && trials < opt.max_trials);
+    record(iterations, capacity, it, *F, step, lambda, 0.0, trials, accepted);
+    stats.iterations = it + 1;
+    if (trials == opt.max_trials || rho == 0.0 || !std::isfinite(lambda)) {
+      stats.termination = DVO_AMD_GRAPH_TERMINATE;
+      break;
+    }
+  }
+  stats.lambda = lambda;
+  return DVO_AMD_OK;
+}
+
+// OptimizationAlgorithmDogleg::solve, max_iterations times
+int run_dogleg(Solver &S, const dvo_amd_graph_options &opt, double *F, dvo_amd_graph_iteration *iterations, int capacity,
+               dvo_amd_graph_stats &stats) {
+  double Delta = opt.initial_delta, lambda = opt.initial_lambda;
+  bool was_pd = true;
+  const int n = S.n;
+  for (int it = 0; it < opt.max_iterations; ++it) {
+    GRAPH_TRY(S.linearise());
+    // alpha = |b|^2 / b^T H b, h_sd = alpha b
+    GRAPH_TRY(S.matvec(S.b(), S.aux()));
+    GRAPH_TRY(S.dots_enqueue({{S.b(), S.b(), 0, 0.0, n}, {S.aux(), S.b(), 0, 0.0, n}}, 0));
+    double s[4];
+    GRAPH_TRY(S.read(s, 2, nullptr));
+    const double alpha = s[0] / s[1];
+    GRAPH_TRY(S.vec(0, alpha, S.b(), nullptr, S.hsd()));
+    GRAPH_TRY(S.dots_enqueue({{S.hsd(), S.hsd(), 0, 0.0, n}}, 0));
+    GRAPH_TRY(S.read(s, 1, nullptr));
+    const double hsd_sq = s[0], hsd_norm = std::sqrt(hsd_sq);
+    double hgn_norm = -1.0, step = 0.0;
+    bool solved_gn = false, good = false;
+    int trials = 0;
+    do {
+      ++trials;
+      if (!solved_gn) {
+        solved_gn = true;
+        bool ok = false;
+        while (!ok) {
+          GRAPH_TRY(S.factor_solve_enqueue(!was_pd, lambda, S.x()));
+          GRAPH_TRY(S.dots_enqueue({{S.x(), S.x(), 0, 0.0, n}}, 0));
+          int f = -1;
+          GRAPH_TRY(S.read(s, 1, &f));
+          S.timed_lin = S.timed_fac = true;
+          S.note_failure(f);
+          ok = f < 0;
+          was_pd = was_pd && ok;
+          if (!was_pd) {
+            if (ok) {
+              lambda = std::max(1e-12, lambda / (0.5 * 10.0));
+            } else {
+              lambda *= 10.0;
+              if (lambda > 1e3) {
+                lambda = 1e3;
+                record(iterations, capacity, it, *F, 0.0, lambda, Delta, trials, 0);
+                stats.iterations = it + 1;
+                stats.termination = DVO_AMD_GRAPH_FAIL;
+                stats.lambda = lambda;
+                stats.delta = Delta;
+                return DVO_AMD_OK;
+              }
+            }
+          }
+        }
+        hgn_norm = std::sqrt(s[0]);
+      }
+      if (hgn_norm < Delta) {
+        HIP_TRY(hipMemcpyAsync(S.hdl(), S.x(), sizeof(double) * n, hipMemcpyDeviceToDevice, S.st));
+      } else if (hsd_norm > Delta) {
+        GRAPH_TRY(S.vec(0, Delta / hsd_norm, S.hsd(), nullptr, S.hdl()));
+      } else {
+        GRAPH_TRY(S.vec(2, 0.0, S.x(), S.hsd(), S.aux()));  // aux = h_gn - h_sd
+        GRAPH_TRY(S.dots_enqueue({{S.hsd(), S.aux(), 0, 0.0, n}, {S.aux(), S.aux(), 0, 0.0, n}}, 0));
+        GRAPH_TRY(S.read(s, 2, nullptr));
+        const double c = s[0], bma = s[1];
+        double beta;
+        if (c <= 0.0)
+          beta = (-c + std::sqrt(c * c + bma * (Delta * Delta - hsd_sq))) / bma;
+        else
+          beta = (Delta * Delta - hsd_sq) / (c + std::sqrt(c * c + bma * (Delta * Delta - hsd_sq)));
+        GRAPH_TRY(S.vec(1, beta, S.hsd(), S.x(), S.hdl()));
+      }
+      // linear gain 2 b^T h - h^T H h; then the trial
+      GRAPH_TRY(S.matvec(S.hdl(), S.aux()));
+      GRAPH_TRY(S.push());
+      GRAPH_TRY(S.update_enqueue(S.hdl(), false));
+      GRAPH_TRY(S.objective_enqueue());
+      GRAPH_TRY(S.dots_enqueue({{S.aux(), S.hdl(), 0, 0.0, n},
+                                {S.b(), S.hdl(), 0, 0.0, n},
+                                {S.hdl(), S.hdl(), 0, 0.0, n},
+                                {(const double *)S.W.rho0.p, nullptr, 0, 0.0, S.n_edges}},
+                               0));
+      GRAPH_TRY(S.read(s, 4, nullptr));
+      double gain = -1.0 * s[0] + 2.0 * s[1];
+      const double Fp = s[3], hdl_norm = std::sqrt(s[2]);
+      if (std::fabs(gain) < 1e-12) gain = 1e-12;
+      const double rho = (*F - Fp) / gain;
+      if (rho > 0.0) {
+        good = true;
+        *F = Fp;
+        step = hdl_norm;
+      } else {
+        GRAPH_TRY(S.pop());
+      }
+      if (rho > 0.75)
+        Delta = std::max(Delta, 3.0 * hdl_norm);
+      else if (rho < 0.25)
+        Delta *= 0.5;
+    } while (!good && trials < opt.max_trials);
+    record(iterations, capacity, it, *F, step, lambda, Delta, trials, good ? 1 : 0);
+    stats.iterations = it + 1;
+    if (trials == opt.max_trials || !good) {
+      stats.termination = DVO_AMD_GRAPH_TERMINATE;
+      break;
+    }
+  }
+  stats.lambda = lambda;
+  stats.delta = Delta;
+  return DVO_AMD_OK;
+}
+
+// dvo_amd_debug_graph_system: the first linear system and its undamped solve instead of an optimization
+struct Probe {
+  double *H, *b, *x, *F;
+  int *failed_pivot;
+};
+
+int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fixed, int n_edges,
+             const dvo_amd_graph_edge *edges, const dvo_amd_graph_options &opt, double *edge_chi2, double *edge_weight,
+             int capacity, dvo_amd_graph_iteration *iterations, dvo_amd_graph_stats &stats, const Probe *probe = nullptr) {
+  // the unknowns: free active vertices in increasing index
+  std::vector<char> active(n_vertices, 0);
+  for (int k = 0; k < n_edges; ++k) active[edges[k].from] = active[edges[k].to] = 1;
+  std::vector<int> slot(n_vertices, -1), vertex_of;
+  for (int v = 0; v < n_vertices; ++v)
+    if (active[v] && !(fixed && fixed[v])) {
+      slot[v] = (int)vertex_of.size();
+      vertex_of.push_back(v);
+    }
+  const int m = (int)vertex_of.size();
+  stats.n_free = m;
+  if (m > DVO_AMD_GRAPH_MAX_FREE_VERTICES) {
+    g_last_error = "dvo_amd_optimize_graph: " + std::to_string(m) + " free active vertices (the dense solver takes at most " +
+                   std::to_string(DVO_AMD_GRAPH_MAX_FREE_VERTICES) + ")";
+    return DVO_AMD_ERR_CAPACITY;
+  }
+  const int n = 6 * m, N = std::max(graph::kTile, (int)align_up((size_t)n, graph::kTile));
+  // contributor lists (CSR by target block / by vertex slot), contributors in edge order
+  std::map<long long, std::vector<int>> blocks;
+  std::vector<std::vector<int>> bl(std::max(m, 1));
+  for (int k = 0; k < n_edges; ++k) {
+    const int f = slot[edges[k].from], t = slot[edges[k].to];
+    if (f >= 0) blocks[(long long)f * m + f].push_back(4 * k + 0), bl[f].push_back(2 * k + 0);
+    if (t >= 0) blocks[(long long)t * m + t].push_back(4 * k + 1), bl[t].push_back(2 * k + 1);
+    if (f >= 0 && t >= 0) {
+      blocks[(long long)f * m + t].push_back(4 * k + 2);
+      blocks[(long long)t * m + f].push_back(4 * k + 3);
+    }
+  }
+  std::vector<int2> block_rc;
+  std::vector<int> block_ptr(1, 0), block_c, b_ptr(1, 0), b_c;
+  for (const auto &kv : blocks) {
+    block_rc.push_back(make_int2((int)(kv.first / std::max(m, 1)), (int)(kv.first % std::max(m, 1))));
+    block_c.insert(block_c.end(), kv.second.begin(), kv.second.end());
+    block_ptr.push_back((int)block_c.size());
+  }
+  for (int s = 0; s < m; ++s) {
+    b_c.insert(b_c.end(), bl[s].begin(), bl[s].end());
+    b_ptr.push_back((int)b_c.size());
+  }
+
+  HIP_TRY(hipSetDevice(ctx->device));
+  GraphWorkspace *Wp = nullptr;
+  GRAPH_TRY(workspace(ctx, &Wp));
+  GraphWorkspace &W = *Wp;
+  const size_t E = std::max(n_edges, 1), V = std::max(n_vertices, 1);
+  GRAPH_TRY(grow(W.poses, 16 * sizeof(double) * V));
+  GRAPH_TRY(grow(W.saved, 16 * sizeof(double) * V));
+  GRAPH_TRY(grow(W.edges, sizeof(dvo_amd_graph_edge) * E));
+  GRAPH_TRY(grow(W.rec, sizeof(double) * graph::kRecord * E));
+  GRAPH_TRY(grow(W.rho0, sizeof(double) * E));
+  GRAPH_TRY(grow(W.chi2, sizeof(double) * E));
+  GRAPH_TRY(grow(W.rho1, sizeof(double) * E));
+  GRAPH_TRY(grow(W.H, sizeof(double) * (size_t)N * N));
+  GRAPH_TRY(grow(W.L, sizeof(double) * (size_t)N * N));
+  for (GraphWorkspace::Buf *b : {&W.b, &W.x, &W.hsd, &W.hdl, &W.aux}) GRAPH_TRY(grow(*b, sizeof(double) * N));
+  GRAPH_TRY(grow(W.block_rc, sizeof(int2) * std::max<size_t>(1, block_rc.size())));
+  GRAPH_TRY(grow(W.block_ptr, sizeof(int) * block_ptr.size()));
+  GRAPH_TRY(grow(W.block_c, sizeof(int) * std::max<size_t>(1, block_c.size())));
+  GRAPH_TRY(grow(W.b_ptr, sizeof(int) * b_ptr.size()));
+  GRAPH_TRY(grow(W.b_c, sizeof(int) * std::max<size_t>(1, b_c.size())));
+  GRAPH_TRY(grow(W.vertex_of, sizeof(int) * std::max<size_t>(1, vertex_of.size())));
+  GRAPH_TRY(grow(W.scalars, sizeof(double) * graph::kMaxDots));
+  GRAPH_TRY(grow(W.flag, sizeof(int)));
+  W.n_padded = N;
+  W.factorizations = 0;
+  W.lin_ms = W.fac_ms = 0.0;
+  const hipStream_t st = ctx->stream;
+  auto up = [&](GraphWorkspace::Buf &b, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
+  };
+  HIP_TRY(up(W.poses, poses, 16 * sizeof(double) * n_vertices));
+  HIP_TRY(up(W.edges, edges, sizeof(dvo_amd_graph_edge) * n_edges));
+  HIP_TRY(up(W.block_rc, block_rc.data(), sizeof(int2) * block_rc.size()));
+  HIP_TRY(up(W.block_ptr, block_ptr.data(), sizeof(int) * block_ptr.size()));
+  HIP_TRY(up(W.block_c, block_c.data(), sizeof(int) * block_c.size()));
+  HIP_TRY(up(W.b_ptr, b_ptr.data(), sizeof(int) * b_ptr.size()));
+  HIP_TRY(up(W.b_c, b_c.data(), sizeof(int) * b_c.size()));
+  HIP_TRY(up(W.vertex_of, vertex_of.data(), sizeof(int) * vertex_of.size()));
+  // blocks no edge touches stay zero; the padding is the identity (its unknowns solve to 0)
+  HIP_TRY(hipMemsetAsync(W.H.p, 0, sizeof(double) * (size_t)N * N, st));
+  HIP_TRY(hipMemsetAsync(W.b.p, 0, sizeof(double) * N, st));
+  if (N > n) hipLaunchKernelGGL(graph::k_pad_diag, dim3(graph::grid_for(N - n, 64)), dim3(64), 0, st, (double *)W.H.p, N, n);
+  HIP_TRY(hipGetLastError());
+
+  Solver S{W, st, n_vertices, n_edges, m, n, N, (int)block_rc.size(), opt.robust_delta};
+  double F = 0.0;
+  GRAPH_TRY(S.objective(&F));
+  stats.initial_objective = F;
+  if (probe) {
+    if (probe->F) *probe->F = F;
+    if (m == 0) return DVO_AMD_OK;
+    GRAPH_TRY(S.linearise());
+    GRAPH_TRY(S.factor_solve_enqueue(false, 0.0, S.x()));
+    int f = -1;
+    GRAPH_TRY(S.read(nullptr, 0, &f));
+    if (probe->failed_pivot) *probe->failed_pivot = f;
+    if (probe->H) HIP_TRY(hipMemcpy2DAsync(probe->H, sizeof(double) * n, W.H.p, sizeof(double) * N, sizeof(double) * n, n,
+                                           hipMemcpyDeviceToHost, st));
+    if (probe->b) HIP_TRY(hipMemcpyAsync(probe->b, W.b.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (probe->x) HIP_TRY(hipMemcpyAsync(probe->x, W.x.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return DVO_AMD_OK;
+  }
+  stats.termination = DVO_AMD_GRAPH_ITERATIONS_EXHAUSTED;
+  stats.delta = opt.algorithm == DVO_AMD_GRAPH_DOGLEG ? opt.initial_delta : 0.0;
+  stats.lambda = opt.algorithm == DVO_AMD_GRAPH_DOGLEG ? opt.initial_lambda : 0.0;
+  if (m > 0) {
+    if (opt.algorithm == DVO_AMD_GRAPH_LEVENBERG)
+      GRAPH_TRY(run_levenberg(S, opt, &F, iterations, capacity, stats));
+    else
+      GRAPH_TRY(run_dogleg(S, opt, &F, iterations, capacity, stats));
+  }
+  stats.cholesky_failures = S.cholesky_failures;
+  // the final estimate's per-edge chi2 / rho1, and F from the same evaluation
+  double Ff = 0.0;
+  GRAPH_TRY(S.objective(&Ff));
+  stats.final_objective = Ff;
+  if (edge_chi2 && n_edges) HIP_TRY(hipMemcpyAsync(edge_chi2, W.chi2.p, sizeof(double) * n_edges, hipMemcpyDeviceToHost, st));
+  if (edge_weight && n_edges)
+    HIP_TRY(hipMemcpyAsync(edge_weight, W.rho1.p, sizeof(double) * n_edges, hipMemcpyDeviceToHost, st));
+  // only the free active vertices change: copy those back, the others stay the caller's bits
+  std::vector<double> out(16 * (size_t)std::max(n_vertices, 1));
+  if (n_vertices) HIP_TRY(hipMemcpyAsync(out.data(), W.poses.p, 16 * sizeof(double) * n_vertices, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  for (int v : vertex_of) std::memcpy(poses + 16 * (size_t)v, out.data() + 16 * (size_t)v, 16 * sizeof(double));
+  if (S.timed_lin) {
+    float ms = 0.0f;
+    if (hipEventElapsedTime(&ms, W.ev[0], W.ev[1]) == hipSuccess) W.lin_ms = ms;
+    if (hipEventElapsedTime(&ms, W.ev[2], W.ev[3]) == hipSuccess) W.fac_ms = ms;
+  }
+  return DVO_AMD_OK;
+}
+
+int have_device() {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
+  return DVO_AMD_OK;
+}
+
+}  // namespace
+
+void graph_workspace_release(dvo_amd_context *ctx) {
+  GraphWorkspace *w = ctx->graph_ws;
+  if (!w) return;
+  for (GraphWorkspace::Buf *b : {&w->poses, &w->saved, &w->edges, &w->rec, &w->rho0, &w->chi2, &w->rho1, &w->H, &w->L, &w->b,
+                                 &w->x, &w->hsd, &w->hdl, &w->aux, &w->block_rc, &w->block_ptr, &w->block_c, &w->b_ptr,
+                                 &w->b_c, &w->vertex_of, &w->scalars, &w->flag})
+    if (b->p) (void)hipFree(b->p);
+  for (hipEvent_t e : w->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete w;
+  ctx->graph_ws = nullptr;
+}
+
+}  // namespace host
+}  // namespace dvo_amd
+
+extern "C" {
+
+void dvo_amd_default_graph_options(int algorithm, dvo_amd_graph_options *opt) {
+  if (!opt) return;
+  std::memset(opt, 0, sizeof(*opt));
+  opt->algorithm = algorithm;
+  opt->robust_delta = 5.0;  // createRobustKernel: RobustKernelCauchy, delta 5 (keyframe_graph.cpp:840-852)
+  if (algorithm == DVO_AMD_GRAPH_DOGLEG) {
+    opt->max_iterations = 100;
+    opt->max_trials = 100;
+    opt->initial_lambda = 1e-7;
+    opt->initial_delta = 1e4;
+  } else {
+    opt->max_iterations = 50;  // LocalMap::optimize (local_map.cpp:205-210)
+    opt->max_trials = 10;
+    opt->initial_lambda = 0.0;
+    opt->initial_delta = 0.0;
+  }
+}
+
+int dvo_amd_optimize_graph(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fixed, int n_edges,
+                           const dvo_amd_graph_edge *edges, const dvo_amd_graph_options *opt, double *edge_chi2,
+                           double *edge_weight, int iteration_capacity, dvo_amd_graph_iteration *iterations,
+                           dvo_amd_graph_stats *stats) {
+  dvo_amd_graph_stats local;
+  dvo_amd_graph_stats &s = stats ? *stats : local;
+  std::memset(&s, 0, sizeof(s));
+  int rc = host::check_arguments(n_vertices, poses, n_edges, edges, opt);
+  if (rc) return rc;
+  rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx || iteration_capacity < 0 || (iteration_capacity > 0 && !iterations)) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = queue_must_be_idle(ctx, "dvo_amd_optimize_graph");
+  if (rc) return rc;
+  return host::optimize(ctx, n_vertices, poses, fixed, n_edges, edges, *opt, edge_chi2, edge_weight, iteration_capacity,
+                        iterations, s);
+}
+
+int dvo_amd_debug_graph_system(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,
+                               const dvo_amd_graph_edge *edges, double robust_delta, double *H, double *b, double *x,
+                               double *F, int *n_free, int *failed_pivot) {
+  dvo_amd_graph_options opt;
+  dvo_amd_default_graph_options(DVO_AMD_GRAPH_DOGLEG, &opt);
+  opt.robust_delta = robust_delta;
+  int rc = host::check_arguments(n_vertices, poses, n_edges, edges, &opt);
+  if (rc) return rc;
+  rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = queue_must_be_idle(ctx, "dvo_amd_debug_graph_system");
+  if (rc) return rc;
+  std::vector<double> copy(poses, poses + 16 * (size_t)n_vertices);  // the entry does not move any pose
+  dvo_amd_graph_stats st;
+  std::memset(&st, 0, sizeof(st));
+  const host::Probe probe{H, b, x, F, failed_pivot};
+  rc = host::optimize(ctx, n_vertices, copy.data(), fixed, n_edges, edges, opt, nullptr, nullptr, 0, nullptr, st, &probe);
+  if (n_free) *n_free = st.n_free;
+  return rc;
+}
+
+int dvo_amd_debug_graph_timing(dvo_amd_context *ctx, double *linearise_ms, double *factorize_ms, int *n_padded,
+                               int *factorizations) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  const host::GraphWorkspace *W = ctx->graph_ws;
+  if (linearise_ms) *linearise_ms = W ? W->lin_ms : 0.0;
+  if (factorize_ms) *factorize_ms = W ? W->fac_ms : 0.0;
+  if (n_padded) *n_padded = W ? W->n_padded : 0;
+  if (factorizations) *factorizations = W ? W->factorizations : 0;
+  return DVO_AMD_OK;
+}
+
+}  // extern "C"

@@ -5,6 +5,7 @@
 //   dvo_probes.cpp    entries that work in slot 0 outside the match driver: residuals / error image, the stage probe, the kernel
 //                     micro-benchmarks and the diagnostics of include/dvo_amd_debug.h
 //   dvo_map.cpp       the keyframe map's point cloud: organized clouds at a pose, the deterministic voxel aggregate
+//   dvo_graph.cpp     the pose-graph optimizer: edge linearisation, dense fp64 Cholesky, Levenberg-Marquardt and dogleg
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -112,6 +113,7 @@ struct Runner;  // the resident pairs of a context and the queue behind them (de
 namespace dvo_amd {
 namespace host {
 struct MapWorkspace;  // the buffers of the map entries (dvo_map.cpp)
+struct GraphWorkspace;  // the buffers of dvo_amd_optimize_graph (dvo_graph.cpp)
 }  // namespace host
 }  // namespace dvo_amd
 
@@ -225,6 +227,7 @@ struct dvo_amd_context {
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   size_t events_used = 0;
   host::MapWorkspace *map_ws = nullptr;  // dvo_amd_point_cloud / _map_cloud / _voxel_downsample: grown to the largest call
+  host::GraphWorkspace *graph_ws = nullptr;  // dvo_amd_optimize_graph: grown to the largest call
 };
 
 namespace dvo_amd {
@@ -384,6 +387,7 @@ int runner_fail_told(dvo_amd_context *ctx, int code);
 int runner_reported_status(Runner &R, unsigned long long ticket);
 int queue_must_be_idle(dvo_amd_context *ctx, const char *what);
 void map_workspace_release(dvo_amd_context *ctx);  // dvo_map.cpp
+void graph_workspace_release(dvo_amd_context *ctx);  // dvo_graph.cpp
 int runner_step(dvo_amd_context *ctx, size_t g);
 int runner_drain(dvo_amd_context *ctx);
 int runner_configure(dvo_amd_context *ctx, int in_flight, int n_pad);

@@ -1,0 +1,221 @@
+"""Pose-graph optimization over the C ABI (dvo_amd_optimize_graph): the keyframe graph's g2o::SparseOptimizer with VertexSE3 /
+EdgeSE3, Levenberg-Marquardt (LocalMap::optimize) or dogleg (KeyframeGraph), with RobustKernelCauchy.  The semantics are pinned
+in include/dvo_amd.h.  Poses are row-major 4x4 numpy arrays, as everywhere in this binding.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+
+LEVENBERG, DOGLEG = 0, 1
+ALGORITHMS = {"levenberg": LEVENBERG, "dogleg": DOGLEG}
+TERMINATION = {0: "iterations exhausted", 1: "terminate", 2: "fail"}
+MAX_FREE_VERTICES = 1024
+
+
+class CGraphEdge(C.Structure):
+    _fields_ = [("from_", C.c_int), ("to", C.c_int), ("measurement", C.c_double * 16), ("information", C.c_double * 36)]
+
+
+class CGraphOptions(C.Structure):
+    _fields_ = [("algorithm", C.c_int), ("max_iterations", C.c_int), ("max_trials", C.c_int), ("reserved", C.c_int),
+                ("robust_delta", C.c_double), ("initial_lambda", C.c_double), ("initial_delta", C.c_double)]
+
+
+class CGraphIteration(C.Structure):
+    _fields_ = [("objective", C.c_double), ("step_norm", C.c_double), ("lambda_", C.c_double), ("delta", C.c_double),
+                ("trials", C.c_int), ("accepted", C.c_int)]
+
+
+class CGraphStats(C.Structure):
+    _fields_ = [("iterations", C.c_int), ("termination", C.c_int), ("n_free", C.c_int), ("cholesky_failures", C.c_int),
+                ("initial_objective", C.c_double), ("final_objective", C.c_double), ("lambda_", C.c_double),
+                ("delta", C.c_double)]
+
+
+_bound = False
+
+
+def _lib():
+    global _bound
+    L = capi.lib()
+    if not _bound:
+        dp = C.POINTER(C.c_double)
+        L.dvo_amd_default_graph_options.restype = None
+        L.dvo_amd_default_graph_options.argtypes = [C.c_int, C.POINTER(CGraphOptions)]
+        L.dvo_amd_optimize_graph.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_int), C.c_int, C.POINTER(CGraphEdge),
+                                             C.POINTER(CGraphOptions), dp, dp, C.c_int, C.POINTER(CGraphIteration),
+                                             C.POINTER(CGraphStats)]
+        L.dvo_amd_debug_graph_timing.argtypes = [C.c_void_p, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.dvo_amd_debug_graph_system.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_int), C.c_int, C.POINTER(CGraphEdge),
+                                                 C.c_double, dp, dp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _bound = True
+    return L
+
+
+def default_options(algorithm: str = "dogleg") -> CGraphOptions:
+    o = CGraphOptions()
+    _lib().dvo_amd_default_graph_options(ALGORITHMS[algorithm], C.byref(o))
+    return o
+
+
+class Result:
+    """What optimize() returns: poses (list of 4x4), per-edge chi2 and weight (rho1), per-iteration records and the stats."""
+
+    def __init__(self, poses, chi2, weight, iterations, stats: CGraphStats):
+        self.poses = poses
+        self.chi2 = chi2
+        self.weight = weight
+        self.iterations = iterations   # dict of arrays: objective, step_norm, lambda, delta, trials, accepted
+        self.n_iterations = stats.iterations
+        self.termination = TERMINATION.get(stats.termination, str(stats.termination))
+        self.n_free = stats.n_free
+        self.cholesky_failures = stats.cholesky_failures
+        self.initial_objective = stats.initial_objective
+        self.final_objective = stats.final_objective
+        self.lambda_ = stats.lambda_
+        self.delta = stats.delta
+
+
+class PoseGraph:
+    """g2o::SparseOptimizer with VertexSE3 / EdgeSE3: add_vertex, add_edge, optimize.  Edge ids are their order of insertion;
+    removed edges keep their id (None in `edges`) and are left out of the next optimize()."""
+
+    def __init__(self):
+        self.poses = []
+        self.fixed = []
+        self.edges = []     # (from, to, Z 4x4, information 6x6) or None once removed
+        self.last = None    # the last Result
+
+    def add_vertex(self, pose=None, fixed: bool = False) -> int:
+        self.poses.append(np.array(np.eye(4) if pose is None else pose, dtype=np.float64).reshape(4, 4))
+        self.fixed.append(bool(fixed))
+        return len(self.poses) - 1
+
+    def set_fixed(self, vertex: int, fixed: bool = True):
+        self.fixed[vertex] = bool(fixed)
+
+    def add_edge(self, from_: int, to: int, measurement, information) -> int:
+        Z = np.array(measurement, dtype=np.float64).reshape(4, 4)
+        O = np.array(information, dtype=np.float64).reshape(6, 6)
+        self.edges.append((int(from_), int(to), Z, O))
+        return len(self.edges) - 1
+
+    def live_edges(self):
+        return [k for k, e in enumerate(self.edges) if e is not None]
+
+    def add_constraints(self, proposals, vertex_of) -> list:
+        """Add the surviving proposals of constraints.ConstraintProposalValidator.validate() as edges, the way
+        KeyframeGraph::insertConstraint does (keyframe_graph.cpp:619-633): vertex 0 = the proposal's Reference keyframe, vertex 1
+        = its Current one, measurement p.TrackingResult.Transformation, information p.TrackingResult.Information.
+        vertex_of: keyframe -> vertex id (a dict keyed by keyframe id, or a callable).  Returns the new edge ids."""
+        look = vertex_of if callable(vertex_of) else (lambda kf: vertex_of[kf.id])
+        ids = []
+        for p in proposals:
+            r = p.TrackingResult
+            ids.append(self.add_edge(look(p.Reference), look(p.Current), r.Transformation, r.Information))
+        return ids
+
+    def optimize(self, tracker: "capi.DenseTracker", algorithm: str = "dogleg", iterations: int | None = None,
+                 robust_delta: float = 5.0, max_trials: int | None = None, initial_lambda: float | None = None,
+                 initial_delta: float | None = None, update: bool = True) -> Result:
+        """Optimize in the tracker's context (dvo_amd_optimize_graph).  Defaults are the reference's (dvo_amd.h); update=True
+        writes the optimized poses back into the graph."""
+        L = _lib()
+        o = default_options(algorithm)
+        if iterations is not None:
+            o.max_iterations = int(iterations)
+        if max_trials is not None:
+            o.max_trials = int(max_trials)
+        if initial_lambda is not None:
+            o.initial_lambda = float(initial_lambda)
+        if initial_delta is not None:
+            o.initial_delta = float(initial_delta)
+        o.robust_delta = float(robust_delta)
+        live, nv, ne, P, fixed, ce = self._pack()
+        chi2 = np.zeros(max(ne, 1))
+        weight = np.zeros(max(ne, 1))
+        cap = max(o.max_iterations, 1)
+        its = (CGraphIteration * cap)()
+        st = CGraphStats()
+        dp = C.POINTER(C.c_double)
+        rc = L.dvo_amd_optimize_graph(tracker._h, nv, P.ctypes.data_as(dp), fixed.ctypes.data_as(C.POINTER(C.c_int)), ne, ce,
+                                      C.byref(o), chi2.ctypes.data_as(dp), weight.ctypes.data_as(dp), cap, its, C.byref(st))
+        capi._check(rc, "dvo_amd_optimize_graph")
+        poses = [P[v].T.copy() for v in range(nv)]
+        n_it = min(st.iterations, cap)
+        rec = {"objective": np.array([its[i].objective for i in range(n_it)]),
+               "step_norm": np.array([its[i].step_norm for i in range(n_it)]),
+               "lambda": np.array([its[i].lambda_ for i in range(n_it)]),
+               "delta": np.array([its[i].delta for i in range(n_it)]),
+               "trials": np.array([its[i].trials for i in range(n_it)], dtype=np.int64),
+               "accepted": np.array([its[i].accepted for i in range(n_it)], dtype=np.int64)}
+        w_full = np.full(len(self.edges), np.nan)
+        c_full = np.full(len(self.edges), np.nan)
+        w_full[live] = weight[:ne]
+        c_full[live] = chi2[:ne]
+        res = Result(poses, c_full, w_full, rec, st)
+        res.robust_delta = o.robust_delta
+        if update:
+            self.poses = [T.copy() for T in poses]
+        self.last = res
+        return res
+
+    def _pack(self):
+        live = self.live_edges()
+        nv, ne = len(self.poses), len(live)
+        P = np.ascontiguousarray(np.stack([T.T for T in self.poses]) if nv else np.zeros((1, 4, 4)))
+        fixed = np.ascontiguousarray(np.asarray(self.fixed, dtype=np.int32)) if nv else np.zeros(1, np.int32)
+        ce = (CGraphEdge * max(ne, 1))()
+        for i, k in enumerate(live):
+            f, t, Z, O = self.edges[k]
+            ce[i].from_, ce[i].to = f, t
+            ce[i].measurement[:] = list(Z.T.reshape(-1))
+            ce[i].information[:] = list(O.T.reshape(-1))
+        return live, nv, ne, P, fixed, ce
+
+    def debug_system(self, tracker: "capi.DenseTracker", robust_delta: float = 5.0):
+        """(diagnostic) the first linear system of optimize() on the current poses (dvo_amd_debug_graph_system):
+        (H n x n, b, x of the undamped solve or None when a pivot failed, F, index of the failed pivot or -1)"""
+        L = _lib()
+        live, nv, ne, P, fixed, ce = self._pack()
+        active = {v for k in live for v in self.edges[k][:2]}
+        n = 6 * sum(1 for v in range(nv) if v in active and not self.fixed[v])
+        H, b, x = np.zeros((max(n, 1), max(n, 1))), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        F, nf, fp = C.c_double(), C.c_int(), C.c_int()
+        dp = C.POINTER(C.c_double)
+        capi._check(L.dvo_amd_debug_graph_system(tracker._h, nv, P.ctypes.data_as(dp), fixed.ctypes.data_as(C.POINTER(C.c_int)),
+                                                 ne, ce, float(robust_delta), H.ctypes.data_as(dp), b.ctypes.data_as(dp),
+                                                 x.ctypes.data_as(dp), C.byref(F), C.byref(nf), C.byref(fp)),
+                    "dvo_amd_debug_graph_system")
+        assert 6 * nf.value == n
+        return H[:n, :n], b[:n], (x[:n] if fp.value < 0 else None), F.value, fp.value
+
+    def remove_outlier_edges(self, weight_threshold: float, n_max: int = -1) -> list:
+        """KeyframeGraph::removeOutlierConstraints (keyframe_graph.cpp:643-675) on the weights (rho1) of the last optimize():
+        edges with a robust kernel (every edge when that optimize() had robust_delta > 0, none otherwise) whose weight is below the threshold are
+        removed lowest weight first, at most n_max of them (n_max < 0: all).  Equal weights go by edge id (the reference keys a
+        std::map by the weight and so keeps only one edge per weight value).  Returns the removed edge ids in removal order."""
+        if self.last is None:
+            raise RuntimeError("remove_outlier_edges needs the weights of an optimize() first")
+        if not self.last.robust_delta > 0:
+            return []
+        w = self.last.weight
+        cand = [k for k in self.live_edges() if k < len(w) and np.isfinite(w[k]) and w[k] < weight_threshold]
+        cand.sort(key=lambda k: (w[k], k))
+        if n_max >= 0:
+            cand = cand[:n_max]
+        for k in cand:
+            self.edges[k] = None
+        return cand
+
+
+def debug_timing(tracker: "capi.DenseTracker"):
+    """(diagnostic) the last optimize() on the tracker: (first linearise ms, first factorization ms, padded n, factorizations)"""
+    a, b, n, f = C.c_double(), C.c_double(), C.c_int(), C.c_int()
+    capi._check(_lib().dvo_amd_debug_graph_timing(tracker._h, C.byref(a), C.byref(b), C.byref(n), C.byref(f)),
+                "dvo_amd_debug_graph_timing")
+    return a.value, b.value, n.value, f.value

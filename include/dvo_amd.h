@@ -498,6 +498,114 @@ int dvo_amd_error_image(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_am
                         int level, float *image);
 
 
+/*
+ * Pose-graph optimization (KeyframeGraph's g2o::SparseOptimizer with OptimizationAlgorithmDogleg, keyframe_graph.cpp:137-144,
+ * and LocalMap::optimize's OptimizationAlgorithmLevenberg, local_map.cpp:205-210; both over VertexSE3 / EdgeSE3 with an
+ * optional RobustKernelCauchy).  The semantics are pinned here, not by g2o's source; tests/pose_graph_restatement.py restates
+ * them in float64 numpy.
+ *
+ * Vertices: SE3 poses, column-major double[16].  A vertex is free unless fixed[i] != 0 (fixed may be NULL: all free).  A vertex
+ * touched by no edge is inactive and returned unchanged (g2o's initializeOptimization leaves it out).  The unknowns are the free
+ * active vertices in increasing vertex index, m of them, n = 6m unknowns.
+ * Increment (VertexSE3::oplusImpl, fromVectorMQT): X <- X * inc(d), d = (tx, ty, tz, qx, qy, qz); inc(d) has translation t and
+ * the rotation of the quaternion (w, qx, qy, qz), w = sqrt(1 - |q|^2); when 1 - |q|^2 < 0 the rotation is the identity.  g2o
+ * re-normalises a vertex's rotation every 1000 updates; this entry does not.
+ * Edge error (EdgeSE3::computeError, toVectorMQT): edge (from, to, Z, Omega), Delta = Z^-1 * (X_from^-1 * X_to) (inverses of
+ * isometries: (R^T, -R^T t)), e = (t(Delta), q_xyz(Delta)) with q the unit quaternion of R(Delta) (Eigen's Quaternion(R),
+ * normalised) with its sign chosen so that w >= 0; chi2 = e^T Omega e.
+ * Jacobians: analytic, of e with respect to d_from and d_to at d = 0, in fp64.  With R, t the rotation and translation of Delta,
+ * (w, v) its quaternion, Rz, tz those of Z and [a]x the cross-product matrix:
+ *   J_to   = [ R      0                         ]      J_from = [ -Rz^T   2 ([t]x Rz^T + Rz^T [tz]x) ]
+ *            [ 0      w I + [v]x                ]               [ 0       -(w I - [v]x) Rz^T          ]
+ * (rows: t, q_xyz; columns: translation, quaternion part of d).  inc(d) rotates by I + 2[dq]x to first order; J_to is
+ * Delta*inc(d), J_from is Z^-1 inc(d)^-1 Z Delta.
+ * Robust kernel (RobustKernelCauchy): delta > 0 and a = chi2 / delta^2 + 1 (computed as (1/delta^2) * chi2 + 1):
+ * rho0 = delta^2 log a, rho1 = 1 / a; delta <= 0: rho0 = chi2, rho1 = 1.  The objective is F = sum over edges of rho0.
+ * Normal equations (BaseBinaryEdge::constructQuadraticForm with robustInformation = rho1 Omega, no second-order term):
+ * H += J_i^T (rho1 Omega) J_j and b -= J_i^T (rho1 Omega) e over the edge's free blocks; H x = b; x is applied vertex by vertex
+ * with inc.  A Cholesky pivot <= 0 (or NaN) is a failed solve.
+ * Levenberg-Marquardt (OptimizationAlgorithmLevenberg::solve): at the first iteration of a call lambda = 1e-5 * max diag(H), or
+ * initial_lambda when > 0, and nu = 2.  Every iteration linearises once and makes up to max_trials attempts: solve
+ * (H + lambda I) x = b, apply x, evaluate F' (+inf for a failed solve, whose x is not applied), rho = (F - F') /
+ * (1e-3 + sum x_i (lambda x_i + b_i)) (rho = -inf for a failed solve).  rho > 0 and F' finite: lambda *= max(1/3, min(2/3,
+ * 1 - (2 rho - 1)^3)), nu = 2, the step is kept and the iteration ends.  Otherwise lambda *= nu, nu *= 2, the estimate is
+ * restored, and the attempts go on while rho < 0.  The call terminates (DVO_AMD_GRAPH_TERMINATE) when an iteration used all
+ * max_trials attempts, ended with rho == 0, or left lambda non-finite.
+ * Dogleg (OptimizationAlgorithmDogleg::solve): per call Delta = initial_delta (1e4), lambda = initial_lambda (1e-7), and
+ * "positive definite so far".  Per iteration: h_sd = alpha b with alpha = |b|^2 / (b^T H b); h_gn solves H x = b undamped while
+ * every solve so far succeeded; from the first failed Cholesky on it solves (H + lambda I) x = b, a failure multiplies lambda
+ * by 10 (the call fails, DVO_AMD_GRAPH_FAIL, when lambda would exceed 1e3), a success sets lambda = max(1e-12, lambda / 5).
+ * h_gn is solved once per iteration.  The step h: h_gn if |h_gn| < Delta; else (Delta / |h_sd|) h_sd if |h_sd| > Delta; else
+ * h_sd + beta (h_gn - h_sd) with c = h_sd . (h_gn - h_sd), s = |h_gn - h_sd|^2 and beta = (-c + sqrt(c^2 + s (Delta^2 -
+ * |h_sd|^2))) / s when c <= 0, (Delta^2 - |h_sd|^2) / (c + sqrt(c^2 + s (Delta^2 - |h_sd|^2))) otherwise.  Linear gain
+ * g = 2 b^T h - h^T H h, replaced by 1e-12 when |g| < 1e-12; rho = (F - F') / g; the step is kept if rho > 0; then Delta =
+ * max(Delta, 3 |h|) if rho > 0.75, Delta /= 2 if rho < 0.25.  Up to max_trials (100) attempts per iteration without
+ * re-linearising; the call terminates when an iteration used all max_trials attempts or kept no step.
+ * Outputs: the optimized poses of all vertices (fixed and inactive ones bit for bit as given); per edge chi2 and rho1 at the
+ * final estimate (what removeOutlierConstraints, keyframe_graph.cpp:643-675, thresholds); per iteration F after it, the norm of
+ * the kept step (0 when none), lambda and Delta after it, the attempts made and whether a step was kept.  An iteration that
+ * ends the call, a failing dogleg one included, is counted and recorded.
+ * Determinism: every sum has a fixed order (by edge index within a block, a fixed tile order in the factorization, fixed-shape
+ * reductions); no floating-point atomics: the result is a function of the inputs in their order and of the options alone,
+ * bit-identical between runs and contexts on one device.
+ * Limits: the system is solved densely (O(n^3) per factorization, fp64; H is n x n on the device).  That fits a keyframe-only
+ * graph and the dense final graph of a sequence of some hundred frames (fr1/desk: 573 frames, n = 3438); more than 1024 free
+ * active vertices return DVO_AMD_ERR_CAPACITY with poses untouched.  A sparse factorization is not implemented.
+ * Argument checks come first and need no device: DVO_AMD_ERR_INVALID_ARGUMENT for an out-of-range vertex index, from == to, a
+ * non-finite measurement, information or pose, an information matrix not symmetric to 1e-9 relative (|O_ij - O_ji| >
+ * 1e-9 max(|O_ij|, |O_ji|, 1e-300)), bad options (algorithm, max_iterations < 0, max_trials < 1, non-finite values).  Then
+ * DVO_AMD_ERR_NO_DEVICE without a GPU and DVO_AMD_ERR_INVALID_ARGUMENT for a NULL ctx or a context with queued pairs.
+ */
+#define DVO_AMD_GRAPH_LEVENBERG 0
+#define DVO_AMD_GRAPH_DOGLEG 1
+#define DVO_AMD_GRAPH_MAX_FREE_VERTICES 1024
+/* termination */
+#define DVO_AMD_GRAPH_ITERATIONS_EXHAUSTED 0
+#define DVO_AMD_GRAPH_TERMINATE 1
+#define DVO_AMD_GRAPH_FAIL 2
+
+typedef struct {
+  int from, to;              /* vertex indices: edge vertex 0 and vertex 1 */
+  double measurement[16];    /* Z, column-major */
+  double information[36];    /* Omega, column-major, symmetric */
+} dvo_amd_graph_edge;
+
+typedef struct {
+  int algorithm;             /* DVO_AMD_GRAPH_LEVENBERG / _DOGLEG */
+  int max_iterations;
+  int max_trials;            /* attempts per iteration: 10 (Levenberg), 100 (dogleg) */
+  int reserved;
+  double robust_delta;       /* Cauchy kernel delta on every edge; <= 0: no kernel */
+  double initial_lambda;     /* Levenberg: <= 0 = 1e-5 max diag(H); dogleg: 1e-7 */
+  double initial_delta;      /* dogleg trust region: 1e4 (unused by Levenberg) */
+} dvo_amd_graph_options;
+
+typedef struct {
+  double objective;          /* F after the iteration */
+  double step_norm;          /* |x| of the kept step, 0 if none */
+  double lambda, delta;      /* after the iteration (delta: 0 for Levenberg) */
+  int trials;
+  int accepted;
+} dvo_amd_graph_iteration;
+
+typedef struct {
+  int iterations;            /* iterations done */
+  int termination;           /* DVO_AMD_GRAPH_ITERATIONS_EXHAUSTED / _TERMINATE / _FAIL */
+  int n_free;                /* m: free active vertices */
+  int cholesky_failures;     /* factorizations that met a pivot <= 0 */
+  double initial_objective, final_objective, lambda, delta;
+} dvo_amd_graph_stats;
+
+/* the reference's values above for the algorithm: Levenberg max_iterations 50, max_trials 10, initial_lambda 0 (= tau max
+ * diag); dogleg max_iterations 100, max_trials 100, initial_lambda 1e-7, initial_delta 1e4; robust_delta 5 for both */
+void dvo_amd_default_graph_options(int algorithm, dvo_amd_graph_options *opt);
+/* poses: n_vertices x 16 doubles, optimized in place.  edge_chi2 / edge_weight (n_edges each), iterations (iteration_capacity
+ * records; later iterations are counted in stats but not recorded) and stats may be NULL. */
+int dvo_amd_optimize_graph(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fixed, int n_edges,
+                           const dvo_amd_graph_edge *edges, const dvo_amd_graph_options *opt, double *edge_chi2,
+                           double *edge_weight, int iteration_capacity, dvo_amd_graph_iteration *iterations,
+                           dvo_amd_graph_stats *stats);
+
 /* Host-side helpers (no GPU needed): the SE(3) exponential / logarithm with Sophus' tangent order (upsilon, omega) and the
  * pivoted LDL^T 6x6 solve the driver uses in place of Sophus::SE3d::exp/log and Eigen::LDLT (dense_tracking.cpp:238,259,347).
  * Exported so that bindings do not need Sophus to build a T_init or to compare poses. */

@@ -149,6 +149,16 @@ int dvo_amd_debug_ll_overflow(dvo_amd_context *ctx, const float *residuals, int 
  * call (input stage, sort, reduction; host gaps between them excluded), the time of the copy of the voxels to the host, and
  * the points it was handed.  scripts/map_cloud_timing.py */
 int dvo_amd_debug_map_timing(dvo_amd_context *ctx, double *device_ms, double *copy_ms, long long *points);
+/* the last dvo_amd_optimize_graph on the context: device ms of its first linearisation (linearise + assemble) and of its first
+ * factorization (damped copy + blocked Cholesky), the padded system size, and the factorizations done */
+int dvo_amd_debug_graph_timing(dvo_amd_context *ctx, double *linearise_ms, double *factorize_ms, int *n_padded,
+                               int *factorizations);
+/* the first linear system of dvo_amd_optimize_graph on these inputs, before any step: H (n x n, row-major, full), b (n) and
+ * F; x (n) = the undamped solve H x = b, valid when *failed_pivot < 0 (else the index of the first pivot <= 0).  Any of the
+ * outputs may be NULL; H / b / x need 6 * (free active vertices) entries per side, *n_free says how many.  Poses are not moved. */
+int dvo_amd_debug_graph_system(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,
+                               const dvo_amd_graph_edge *edges, double robust_delta, double *H, double *b, double *x,
+                               double *F, int *n_free, int *failed_pivot);
 
 #ifdef __cplusplus
 }
