@@ -15,6 +15,8 @@
 //   k_dots         fixed-shape dot products (one workgroup each)
 //   k_update       X <- X * inc(x) for every free vertex
 // Every sum has one fixed order and there are no floating-point atomics: the result is bit-identical from run to run.
+#include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstring>
 #include <limits>
@@ -541,6 +543,222 @@ __global__ void k_update(int m, const int *__restrict__ vertex_of, const double 
 
 inline int grid_for(size_t n, int block) { return (int)std::max<size_t>(1, (n + block - 1) / block); }
 
+// ---- the sparse solver (DVO_AMD_GRAPH_SOLVER_SPARSE): multifrontal Cholesky over the nested-dissection assembly tree -------
+//   H is stored as its nonzero 6x6 blocks (row-major 36 doubles each, both mirror images), sorted by (row, col) slot: the same
+//   contributor lists and k_assemble_H as the dense path, pointed at block k with block_rc = (k, 0) and N = 6.
+//   A front is dense, row-major, lower triangle used: local blocks are its pivots (p, in elimination order) then its update set
+//   (u, in elimination order).  Pivot block i sits at scalar 6i, update block j at ppad + 6j.  Small fronts have ppad = 6p and
+//   ld = 6(p + u); wide fronts pad ppad and ld to kTile (pad pivots are the identity) and go through the dense path's
+//   k_potrf_panel / k_trsm / k_syrk with the front as the matrix, over the pivot tiles only.  After the factorization the
+//   trailing ld - ppad rows and columns of a front hold its update matrix C - L21 L21^T, which the parent gathers.
+//   Per level (leaves first): k_front_assemble (H blocks + lambda + the children's update matrices, children in a fixed order),
+//   then k_front_factor (one workgroup per small front) and the tiled kernels per wide front.  Forward substitution bottom-up
+//   (each front's update vector sits behind its pivots in its vector slot), backward top-down (a gather of the ancestors'
+//   solved entries).  Dependencies between fronts are kernel boundaries; the failure word stops every later kernel.
+constexpr int kFrontThreads = 256;
+constexpr int kSmallMaxLd = 1024;   // a small front's column lives in LDS
+constexpr int kWidePivots = 192;    // 6p above this (32 vertices): the tiled path
+
+struct Front {
+  long long a_off, hmap_off;  // front matrix (ld x ld doubles); (p + u) x p H-block indices (-1: none)
+  int v_off, ld, p, u, ppad;  // vector slot (ld doubles)
+  int loc_off;                // slots of the p + u local blocks
+  int inv_off;                // this front as a child: parent-local block -> index in this front's update set, or -1
+  int ch_begin, ch_end;       // children (front ids) in child_list
+};
+
+// scalar index i of a front -> local block (or -1 for padding) and the entry within it
+__device__ inline int local_block(const Front &F, int i, int *w) {
+  *w = i % 6;
+  if (i < 6 * F.p) return i / 6;
+  if (i >= F.ppad && i < F.ppad + 6 * F.u) {
+    *w = (i - F.ppad) % 6;
+    return F.p + (i - F.ppad) / 6;
+  }
+  return -1;
+}
+
+// the lower triangle of each front of the level: H blocks + lambda on the diagonal, then the children's update matrices in order
+__global__ void __launch_bounds__(kBlock) k_front_assemble(const Front *__restrict__ fronts, const int *__restrict__ ids,
+                                                           const double *__restrict__ Hs, const int *__restrict__ hmap,
+                                                           const int *__restrict__ inv, const int *__restrict__ child_list,
+                                                           double *__restrict__ A, double lambda, int damp, const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  const Front F = fronts[ids[blockIdx.y]];
+  const long long total = (long long)F.ld * F.ld;
+  double *a = A + F.a_off;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+    const int r = (int)(e / F.ld), c = (int)(e % F.ld);
+    if (c > r) continue;
+    int wr, wc;
+    const int br = local_block(F, r, &wr), bc = local_block(F, c, &wc);
+    double v = 0.0;
+    if (br < 0 || bc < 0) {
+      v = (r == c && r < F.ppad) ? 1.0 : 0.0;  // pad pivots: the identity
+    } else {
+      if (bc < F.p) {
+        const int hb = hmap[F.hmap_off + (long long)br * F.p + bc];
+        if (hb >= 0) v = Hs[36 * (size_t)hb + 6 * wr + wc];
+        if (damp && r == c) v = v + lambda;
+      }
+      for (int q = F.ch_begin; q < F.ch_end; ++q) {
+        const Front C = fronts[child_list[q]];
+        const int jr = inv[C.inv_off + br], jc = inv[C.inv_off + bc];
+        if (jr >= 0 && jc >= 0)
+          v = v + A[C.a_off + (long long)(C.ppad + 6 * jr + wr) * C.ld + C.ppad + 6 * jc + wc];
+      }
+    }
+    a[(long long)r * F.ld + c] = v;
+  }
+}
+
+// partial Cholesky of a small front (its first 6p columns) in one workgroup, right-looking, one vertex (6 columns) at a time:
+// the panel's columns are factorized one by one (each kept in LDS), then the lower triangle behind the panel gets the rank-6
+// update in one pass, one wave per row.  Every entry subtracts the six products in column order, as six rank-1 steps would.
+__global__ void __launch_bounds__(kFrontThreads) k_front_factor(const Front *__restrict__ fronts, const int *__restrict__ ids,
+                                                                double *__restrict__ A, int *flag) {
+  if (*(volatile int *)flag >= 0) return;
+  __shared__ double col[6][kSmallMaxLd];
+  const Front F = fronts[ids[blockIdx.x]];
+  double *a = A + F.a_off;
+  const int ld = F.ld, np = 6 * F.p, tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
+  for (int j0 = 0; j0 < np; j0 += 6) {
+    for (int q = 0; q < 6; ++q) {
+      const int j = j0 + q;
+      const double piv = a[(long long)j * ld + j];
+      if (!(piv > 0.0)) {  // uniform: every thread read the same word after the last barrier
+        if (tid == 0) atomicMax(flag, j);
+        return;
+      }
+      const double d = sqrt(piv);
+      for (int i = j + 1 + tid; i < ld; i += kFrontThreads) {
+        const double v = a[(long long)i * ld + j] / d;
+        a[(long long)i * ld + j] = v;
+        col[q][i] = v;
+      }
+      __syncthreads();  // everyone has read the pivot, and the column is in LDS
+      if (tid == 0) a[(long long)j * ld + j] = d;
+      const int w = 5 - q;  // the panel's columns behind j
+      if (w > 0) {
+        for (int e = tid; e < (ld - j - 1) * w; e += kFrontThreads) {
+          const int r = j + 1 + e / w, c = j + 1 + e % w;
+          if (c <= r) a[(long long)r * ld + c] = a[(long long)r * ld + c] - col[q][r] * col[q][c];
+        }
+        __syncthreads();
+      }
+    }
+    const int j1 = j0 + 6;
+    for (int r = j1 + wave; r < ld; r += kFrontThreads / 64) {
+      double lr[6];
+      for (int q = 0; q < 6; ++q) lr[q] = col[q][r];
+      double *row = a + (long long)r * ld;
+      for (int c = j1 + lane; c <= r; c += 64) {
+        double v = row[c];
+        for (int q = 0; q < 6; ++q) v = v - lr[q] * col[q][c];
+        row[c] = v;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// forward substitution of the level's fronts: the right-hand side (b on the pivots, the children's update vectors added in
+// order), L11 y = r1 in place, then r2 -= L21 y: the front's update vector
+__global__ void __launch_bounds__(kFrontThreads) k_front_forward(const Front *__restrict__ fronts, const int *__restrict__ ids,
+                                                                 const double *__restrict__ A, const int *__restrict__ loc,
+                                                                 const int *__restrict__ inv,
+                                                                 const int *__restrict__ child_list,
+                                                                 const double *__restrict__ b, double *__restrict__ V,
+                                                                 const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  const Front F = fronts[ids[blockIdx.x]];
+  const double *a = A + F.a_off;
+  double *r = V + F.v_off;
+  const int ld = F.ld, np = 6 * F.p, nu = 6 * F.u, tid = threadIdx.x;
+  for (int i = tid; i < ld; i += kFrontThreads) {
+    int w;
+    const int blk = local_block(F, i, &w);
+    double v = 0.0;
+    if (blk >= 0) {
+      if (blk < F.p) v = b[6 * (size_t)loc[F.loc_off + blk] + w];
+      for (int q = F.ch_begin; q < F.ch_end; ++q) {
+        const Front C = fronts[child_list[q]];
+        const int j = inv[C.inv_off + blk];
+        if (j >= 0) v = v + V[C.v_off + C.ppad + 6 * j + w];
+      }
+    }
+    r[i] = v;
+  }
+  __syncthreads();
+  for (int j = 0; j < np; ++j) {
+    const double y = r[j] / a[(long long)j * ld + j];
+    __syncthreads();
+    if (tid == 0) r[j] = y;
+    const int below = np - j - 1;
+    for (int t = tid; t < below + nu; t += kFrontThreads) {
+      const int i = t < below ? j + 1 + t : F.ppad + (t - below);
+      r[i] = r[i] - a[(long long)i * ld + j] * y;
+    }
+    __syncthreads();
+  }
+}
+
+// backward substitution of the level's fronts: z = y - L21^T x2 (x2 = the ancestors' solved entries), L11^T x1 = z
+__global__ void __launch_bounds__(kFrontThreads) k_front_backward(const Front *__restrict__ fronts, const int *__restrict__ ids,
+                                                                  const double *__restrict__ A, const int *__restrict__ loc,
+                                                                  double *__restrict__ V, double *__restrict__ x,
+                                                                  const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  const Front F = fronts[ids[blockIdx.x]];
+  const double *a = A + F.a_off;
+  double *r = V + F.v_off;
+  const int ld = F.ld, np = 6 * F.p, nu = 6 * F.u, tid = threadIdx.x;
+  for (int j = tid; j < np; j += kFrontThreads) {
+    double s = r[j];
+    for (int t = 0; t < nu; ++t)
+      s = s - a[(long long)(F.ppad + t) * ld + j] * x[6 * (size_t)loc[F.loc_off + F.p + t / 6] + t % 6];
+    r[j] = s;
+  }
+  __syncthreads();
+  for (int j = np - 1; j >= 0; --j) {
+    const double xj = r[j] / a[(long long)j * ld + j];
+    __syncthreads();
+    if (tid == 0) r[j] = xj;
+    for (int i = tid; i < j; i += kFrontThreads) r[i] = r[i] - a[(long long)j * ld + i] * xj;
+    __syncthreads();
+  }
+  for (int i = tid; i < np; i += kFrontThreads) x[6 * (size_t)loc[F.loc_off + i / 6] + i % 6] = r[i];
+}
+
+// y = H v over the stored blocks: one thread per row, blocks of the block row in column order, entries in column order
+__global__ void k_bsr_matvec(int n, const int *__restrict__ row_ptr, const int2 *__restrict__ rc,
+                             const double *__restrict__ Hs, const double *__restrict__ v, double *__restrict__ y) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = i / 6, w = i % 6;
+  double acc = 0.0;
+  for (int k = row_ptr[s]; k < row_ptr[s + 1]; ++k) {
+    const double *h = Hs + 36 * (size_t)k + 6 * w;
+    const double *x = v + 6 * (size_t)rc[k].y;
+    for (int c = 0; c < 6; ++c) acc += h[c] * x[c];
+  }
+  y[i] = acc;
+}
+
+// max |diag(H)| over the diagonal blocks (fmax is exact: any order gives the same value)
+__global__ void k_max_diag_blocks(int n, const int *__restrict__ diag_block, const double *__restrict__ Hs, double *out) {
+  __shared__ double red[kBlock];
+  double m = 0.0;
+  for (int i = threadIdx.x; i < n; i += kBlock) m = fmax(m, fabs(Hs[36 * (size_t)diag_block[i / 6] + 7 * (i % 6)]));
+  red[threadIdx.x] = m;
+  __syncthreads();
+  for (int s = kBlock / 2; s > 0; s >>= 1) {
+    if (threadIdx.x < s) red[threadIdx.x] = fmax(red[threadIdx.x], red[threadIdx.x + s]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *out = red[0];
+}
+
 }  // namespace graph
 
 namespace host {
@@ -552,9 +770,15 @@ struct GraphWorkspace {
   };
   Buf poses, saved, edges, rec, rho0, chi2, rho1, H, L, b, x, hsd, hdl, aux, block_rc, block_ptr, block_c, b_ptr, b_c,
       vertex_of, scalars, flag;
-  hipEvent_t ev[4] = {};
+  // the sparse solver: H blocks, their row pointers and (row, col) slots, the diagonal block of each slot, the fronts and their
+  // maps, the level lists, the front matrices and vectors
+  Buf Hs, bsr_ptr, bsr_rc, diag_block, fronts, hmap, inv, child_list, loc, level_ids, small_ids, A, V;
+  hipEvent_t ev[6] = {};
   double lin_ms = 0.0, fac_ms = 0.0;
   int n_padded = 0, factorizations = 0;
+  // the last sparse call
+  double sp_symbolic_ms = 0.0, sp_lin_ms = 0.0, sp_fac_ms = 0.0, sp_solve_ms = 0.0, sp_factor_doubles = 0.0, sp_flops = 0.0;
+  int sp_fronts = 0, sp_levels = 0, sp_widest = 0;
 };
 
 namespace {
@@ -595,6 +819,7 @@ int check_arguments(int n_vertices, const double *poses, int n_edges, const dvo_
   if (n_vertices < 0 || n_edges < 0 || !opt || (n_vertices > 0 && !poses) || (n_edges > 0 && !edges))
     return bad("null pointer or negative count");
   if (opt->algorithm != DVO_AMD_GRAPH_LEVENBERG && opt->algorithm != DVO_AMD_GRAPH_DOGLEG) return bad("unknown algorithm");
+  if (opt->solver != DVO_AMD_GRAPH_SOLVER_DENSE && opt->solver != DVO_AMD_GRAPH_SOLVER_SPARSE) return bad("unknown solver");
   if (opt->max_iterations < 0 || opt->max_trials < 1) return bad("max_iterations < 0 or max_trials < 1");
   if (!std::isfinite(opt->robust_delta) || !std::isfinite(opt->initial_lambda) || !std::isfinite(opt->initial_delta))
     return bad("non-finite option");
@@ -616,6 +841,259 @@ int check_arguments(int n_vertices, const double *poses, int n_edges, const dvo_
   return DVO_AMD_OK;
 }
 
+// ---- the sparse solver's symbolic phase (host, once per call): nested dissection on the m x m block pattern ---------------
+constexpr int kLeafVertices = 16;
+
+struct Symbolic {
+  int m = 0, n_fronts = 0, n_levels = 0, widest = 0;
+  std::vector<int> perm, pos;                    // perm[k] = the slot eliminated k-th; pos = its inverse
+  std::vector<int> parent, level;                // per front (postorder: children before parents); level 0 = leaves
+  std::vector<int> piv_ptr, piv, upd_ptr, upd;   // CSR: pivot slots, update slots (both in elimination order)
+  std::vector<int> child_ptr, child;             // CSR: children in a fixed order
+  double factor_doubles = 0.0, flops = 0.0, front_doubles = 0.0;
+  double vector_doubles = 0.0, map_ints = 0.0;  // the fronts' vectors; hmap + inv + loc entries
+  std::vector<int> ld, ppad;                     // the device layout of each front
+};
+
+// adjacency of the free active slots (sorted, without repeats)
+std::vector<std::vector<int>> block_adjacency(int m, const std::vector<int> &slot, int n_edges, const dvo_amd_graph_edge *edges) {
+  std::vector<std::vector<int>> adj(m);
+  for (int k = 0; k < n_edges; ++k) {
+    const int f = slot[edges[k].from], t = slot[edges[k].to];
+    if (f >= 0 && t >= 0) adj[f].push_back(t), adj[t].push_back(f);
+  }
+  for (auto &a : adj) {
+    std::sort(a.begin(), a.end());
+    a.erase(std::unique(a.begin(), a.end()), a.end());
+  }
+  return adj;
+}
+
+struct Dissection {
+  const std::vector<std::vector<int>> &adj;
+  std::vector<int> owner, seen, dist;  // owner: the set a slot belongs to now; seen: BFS stamps
+  int sets = 0, stamp = 0;
+  std::vector<std::vector<int>> piv, children;  // per front, in creation order (= postorder)
+
+  explicit Dissection(const std::vector<std::vector<int>> &a)
+      : adj(a), owner(a.size(), -1), seen(a.size(), -1), dist(a.size(), 0) {}
+
+  int front(std::vector<int> p, std::vector<int> ch) {
+    piv.push_back(std::move(p));
+    children.push_back(std::move(ch));
+    return (int)piv.size() - 1;
+  }
+
+  // BFS inside set `id` from r: the vertices in BFS order (neighbours in slot order), dist[] their levels
+  void bfs(int r, int id, std::vector<int> &order) {
+    ++stamp;
+    order.clear();
+    order.push_back(r);
+    seen[r] = stamp;
+    dist[r] = 0;
+    for (size_t h = 0; h < order.size(); ++h) {
+      const int v = order[h];
+      for (int w : adj[v])
+        if (owner[w] == id && seen[w] != stamp) {
+          seen[w] = stamp;
+          dist[w] = dist[v] + 1;
+          order.push_back(w);
+        }
+    }
+  }
+
+  int degree_in(int v, int id) const {
+    int d = 0;
+    for (int w : adj[v]) d += owner[w] == id;
+    return d;
+  }
+
+  // the roots of the fronts made for `verts` (sorted slots)
+  std::vector<int> run(std::vector<int> verts) {
+    if ((int)verts.size() <= kLeafVertices) return {front(std::move(verts), {})};
+    const int id = sets++;
+    for (int v : verts) owner[v] = id;
+    // components, by their smallest slot
+    std::vector<std::vector<int>> comps;
+    std::vector<int> order;
+    {
+      const int cstamp = ++stamp;
+      std::vector<int> queue;
+      for (int v : verts) {
+        if (seen[v] == cstamp) continue;
+        queue.assign(1, v);
+        seen[v] = cstamp;
+        for (size_t h = 0; h < queue.size(); ++h)
+          for (int w : adj[queue[h]])
+            if (owner[w] == id && seen[w] != cstamp) seen[w] = cstamp, queue.push_back(w);
+        std::sort(queue.begin(), queue.end());
+        comps.push_back(queue);
+      }
+    }
+    if (comps.size() > 1) {  // a forest: small components share a leaf front, large ones are dissected on their own
+      std::vector<int> roots, bin;
+      for (auto &c : comps) {
+        if ((int)c.size() > kLeafVertices) {
+          for (int r : run(std::move(c))) roots.push_back(r);
+          continue;
+        }
+        if ((int)(bin.size() + c.size()) > kLeafVertices) {
+          std::sort(bin.begin(), bin.end());
+          roots.push_back(front(std::move(bin), {}));
+          bin.clear();
+        }
+        bin.insert(bin.end(), c.begin(), c.end());
+      }
+      if (!bin.empty()) {
+        std::sort(bin.begin(), bin.end());
+        roots.push_back(front(std::move(bin), {}));
+      }
+      return roots;
+    }
+    // a pseudo-peripheral vertex: from the smallest slot, move to a vertex of the last level of least degree while the
+    // eccentricity grows
+    int r = verts[0];
+    bfs(r, id, order);
+    for (int round = 0; round < 8; ++round) {
+      const int ecc = dist[order.back()];
+      int best = -1;
+      for (int i = (int)order.size() - 1; i >= 0 && dist[order[i]] == ecc; --i) {
+        const int v = order[i];
+        if (best < 0 || degree_in(v, id) < degree_in(best, id) || (degree_in(v, id) == degree_in(best, id) && v < best))
+          best = v;
+      }
+      std::vector<int> o2;
+      bfs(best, id, o2);
+      if (dist[o2.back()] <= ecc) {
+        bfs(r, id, order);  // restore r's levels
+        break;
+      }
+      r = best;
+      order.swap(o2);
+    }
+    const int depth = dist[order.back()];
+    if (depth < 2) return {front(std::move(verts), {})};  // no level separates anything: one dense front
+    std::vector<int> count(depth + 1, 0), sep_count(depth + 1, 0);
+    for (int v : order) {
+      ++count[dist[v]];
+      for (int w : adj[v])
+        if (owner[w] == id && dist[w] == dist[v] + 1) {
+          ++sep_count[dist[v]];
+          break;
+        }
+    }
+    // the separator: the vertices of one level with a neighbour in the next.  Among levels that leave both sides at least a
+    // quarter of the set, the smallest separator, then the better balance, then the lower level; without such a level the
+    // least |separator| x larger side
+    const long long total = (long long)verts.size();
+    int pick = -1;
+    long long best_key[3] = {0, 0, 0};
+    bool balanced_found = false;
+    long long below_prefix = 0;
+    for (int i = 1; i < depth; ++i) {
+      below_prefix += count[i - 1];
+      const long long sep = sep_count[i], below = below_prefix + count[i] - sep, above = total - below_prefix - count[i];
+      const bool balanced = 4 * std::min(below, above) >= total;
+      const long long key[3] = {balanced ? sep : sep * std::max(below, above), std::max(below, above), i};
+      if (balanced && !balanced_found) balanced_found = true, pick = -1;
+      if (balanced_found && !balanced) continue;
+      if (pick < 0 || std::lexicographical_compare(key, key + 3, best_key, best_key + 3)) {
+        pick = i;
+        std::copy(key, key + 3, best_key);
+      }
+    }
+    std::vector<int> sep, below, above;
+    for (int v : verts) {
+      if (dist[v] > pick) {
+        above.push_back(v);
+      } else if (dist[v] < pick) {
+        below.push_back(v);
+      } else {
+        bool cut = false;
+        for (int w : adj[v]) cut = cut || (owner[w] == id && dist[w] == pick + 1);
+        (cut ? sep : below).push_back(v);
+      }
+    }
+    std::vector<int> roots = run(std::move(below));
+    for (int x : run(std::move(above))) roots.push_back(x);
+    return {front(std::move(sep), std::move(roots))};
+  }
+};
+
+// ordering, assembly tree, update sets, levels, the device layout and the predicted storage and flops
+Symbolic symbolic(const std::vector<std::vector<int>> &adj) {
+  Symbolic S;
+  const int m = (int)adj.size();
+  S.m = m;
+  if (m == 0) {
+    S.piv_ptr = S.upd_ptr = S.child_ptr = {0};
+    return S;
+  }
+  Dissection D(adj);
+  std::vector<int> all(m);
+  for (int s = 0; s < m; ++s) all[s] = s;
+  D.run(std::move(all));
+  const int nf = (int)D.piv.size();
+  S.n_fronts = nf;
+  S.pos.assign(m, -1);
+  S.piv_ptr.assign(1, 0);
+  for (int k = 0; k < nf; ++k) {
+    for (int v : D.piv[k]) S.pos[v] = (int)S.perm.size(), S.perm.push_back(v);
+    S.piv.insert(S.piv.end(), D.piv[k].begin(), D.piv[k].end());
+    S.piv_ptr.push_back((int)S.piv.size());
+  }
+  S.parent.assign(nf, -1);
+  S.level.assign(nf, 0);
+  S.child_ptr.assign(1, 0);
+  for (int k = 0; k < nf; ++k) {
+    for (int c : D.children[k]) {
+      S.parent[c] = k;
+      S.level[k] = std::max(S.level[k], S.level[c] + 1);
+    }
+    S.child.insert(S.child.end(), D.children[k].begin(), D.children[k].end());
+    S.child_ptr.push_back((int)S.child.size());
+  }
+  // update set: the later-eliminated neighbours of the pivots, and the children's update sets without this front's pivots
+  std::vector<int> tag(m, -1);
+  std::vector<std::vector<int>> upd(nf);
+  for (int k = 0; k < nf; ++k) {
+    const int end = S.pos[S.piv[S.piv_ptr[k + 1] - 1]] + 1;
+    auto add = [&](int w) {
+      if (S.pos[w] >= end && tag[w] != k) tag[w] = k, upd[k].push_back(w);
+    };
+    for (int q = S.piv_ptr[k]; q < S.piv_ptr[k + 1]; ++q)
+      for (int w : adj[S.piv[q]]) add(w);
+    for (int c : D.children[k])
+      for (int w : upd[c]) add(w);
+    std::sort(upd[k].begin(), upd[k].end(), [&](int a, int b) { return S.pos[a] < S.pos[b]; });
+  }
+  S.upd_ptr.assign(1, 0);
+  for (int k = 0; k < nf; ++k) {
+    S.upd.insert(S.upd.end(), upd[k].begin(), upd[k].end());
+    S.upd_ptr.push_back((int)S.upd.size());
+    const double p = 6.0 * (S.piv_ptr[k + 1] - S.piv_ptr[k]), u = 6.0 * upd[k].size();
+    S.factor_doubles += p * (p + 1) / 2 + u * p;
+    S.flops += p * p * p / 3.0 + u * p * p + u * u * p;  // potrf, trsm, the update matrix
+    S.n_levels = std::max(S.n_levels, S.level[k] + 1);
+    S.widest = std::max(S.widest, (int)(p + u));
+    const int np = (int)p, nu = (int)u;
+    const bool wide = np > graph::kWidePivots || np + nu > graph::kSmallMaxLd;
+    const int pp = wide ? (int)align_up(np, graph::kTile) : np;
+    const int ld = wide ? (int)align_up(pp + nu, graph::kTile) : np + nu;
+    S.ppad.push_back(pp);
+    S.ld.push_back(ld);
+    S.front_doubles += (double)ld * ld;
+    S.vector_doubles += ld;
+    S.map_ints += (double)(np + nu) / 6 * (np / 6) + (np + nu) / 6;  // hmap, loc
+  }
+  for (int k = 0; k < nf; ++k)
+    if (S.parent[k] >= 0) {
+      const int q = S.parent[k];
+      S.map_ints += (S.piv_ptr[q + 1] - S.piv_ptr[q]) + (S.upd_ptr[q + 1] - S.upd_ptr[q]);  // inv
+    }
+  return S;
+}
+
 // one call: the device state and the host's view of the scalars
 struct Solver {
   GraphWorkspace &W;
@@ -624,6 +1102,14 @@ struct Solver {
   double delta;
   int cholesky_failures = 0;
   bool timed_lin = false, timed_fac = false;
+  // the sparse solver's schedule (null: the dense path)
+  struct Sparse {
+    std::vector<int> level_begin, small_begin, small_count;  // per level: its fronts in level_ids, its small fronts in small_ids
+    std::vector<std::vector<int>> wide;                      // per level: the wide fronts' ids
+    std::vector<int> max_ld;                                 // per level
+    std::vector<graph::Front> fronts;                        // host copy (wide fronts' offsets)
+  };
+  const Sparse *sp = nullptr;
 
   double *poses() { return (double *)W.poses.p; }
   double *H() { return (double *)W.H.p; }
@@ -691,8 +1177,10 @@ struct Solver {
     if (!timed_lin) HIP_TRY(hipEventRecord(W.ev[0], st));
     hipLaunchKernelGGL(graph::k_linearise, dim3(graph::grid_for(n_edges, 64)), dim3(64), 0, st, n_edges,
                        (const dvo_amd_graph_edge *)W.edges.p, poses(), delta, (double *)W.rec.p);
+    // the sparse path stores block k at Hs + 36 k: block_rc holds (k, 0) and the row stride is 6
     hipLaunchKernelGGL(graph::k_assemble_H, dim3(nblocks), dim3(64), 0, st, (const int2 *)W.block_rc.p,
-                       (const int *)W.block_ptr.p, (const int *)W.block_c.p, (const double *)W.rec.p, H(), N);
+                       (const int *)W.block_ptr.p, (const int *)W.block_c.p, (const double *)W.rec.p,
+                       sp ? (double *)W.Hs.p : H(), sp ? 6 : N);
     hipLaunchKernelGGL(graph::k_assemble_b, dim3(graph::grid_for(n, 256)), dim3(256), 0, st, n, (const int *)W.b_ptr.p,
                        (const int *)W.b_c.p, (const double *)W.rec.p, b());
     HIP_TRY(hipGetLastError());
@@ -700,8 +1188,66 @@ struct Solver {
     return DVO_AMD_OK;
   }
 
+  // max |diag(H)| into scalars[0]
+  int max_diag_enqueue() {
+    if (sp)
+      hipLaunchKernelGGL(graph::k_max_diag_blocks, dim3(1), dim3(graph::kBlock), 0, st, n, (const int *)W.diag_block.p,
+                         (const double *)W.Hs.p, scalars());
+    else
+      hipLaunchKernelGGL(graph::k_max_diag, dim3(1), dim3(graph::kBlock), 0, st, (const double *)H(), N, n, scalars());
+    HIP_TRY(hipGetLastError());
+    return DVO_AMD_OK;
+  }
+
+  int sparse_factor_solve_enqueue(bool damp, double lambda, double *out) {
+    const graph::Front *fr = (const graph::Front *)W.fronts.p;
+    const int *ids = (const int *)W.level_ids.p, *small = (const int *)W.small_ids.p;
+    double *A = (double *)W.A.p, *V = (double *)W.V.p;
+    if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[2], st));
+    HIP_TRY(hipMemsetAsync(flag(), 0xff, sizeof(int), st));
+    const int levels = (int)sp->level_begin.size() - 1;
+    for (int l = 0; l < levels; ++l) {
+      const int count = sp->level_begin[l + 1] - sp->level_begin[l];
+      const int gx = std::min(64, graph::grid_for((size_t)sp->max_ld[l] * sp->max_ld[l], graph::kBlock));
+      hipLaunchKernelGGL(graph::k_front_assemble, dim3(gx, count), dim3(graph::kBlock), 0, st, fr, ids + sp->level_begin[l],
+                         (const double *)W.Hs.p, (const int *)W.hmap.p, (const int *)W.inv.p, (const int *)W.child_list.p,
+                         A, lambda, damp ? 1 : 0, (const int *)flag());
+      if (sp->small_count[l])
+        hipLaunchKernelGGL(graph::k_front_factor, dim3(sp->small_count[l]), dim3(graph::kFrontThreads), 0, st, fr,
+                           small + sp->small_begin[l], A, flag());
+      for (int k : sp->wide[l]) {  // the dense path's tiled kernels on the front, over its pivot tiles
+        const graph::Front &F = sp->fronts[k];
+        double *a = A + F.a_off;
+        const int T = F.ld / graph::kTile, P = F.ppad / graph::kTile;
+        for (int t = 0; t < P; ++t) {
+          hipLaunchKernelGGL(graph::k_potrf_panel, dim3(1), dim3(graph::kBlock), 0, st, a, F.ld, t, flag());
+          if (t + 1 < T) {
+            hipLaunchKernelGGL(graph::k_trsm, dim3(T - t - 1), dim3(graph::kBlock), 0, st, a, F.ld, t, (const int *)flag());
+            hipLaunchKernelGGL(graph::k_syrk, dim3(T - t - 1, T - t - 1), dim3(graph::kBlock), 0, st, a, F.ld, t,
+                               (const int *)flag());
+          }
+        }
+      }
+    }
+    HIP_TRY(hipGetLastError());
+    if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[3], st));
+    for (int l = 0; l < levels; ++l)
+      hipLaunchKernelGGL(graph::k_front_forward, dim3(sp->level_begin[l + 1] - sp->level_begin[l]), dim3(graph::kFrontThreads),
+                         0, st, fr, ids + sp->level_begin[l], (const double *)A, (const int *)W.loc.p, (const int *)W.inv.p,
+                         (const int *)W.child_list.p, (const double *)b(), V, (const int *)flag());
+    for (int l = levels - 1; l >= 0; --l)
+      hipLaunchKernelGGL(graph::k_front_backward, dim3(sp->level_begin[l + 1] - sp->level_begin[l]),
+                         dim3(graph::kFrontThreads), 0, st, fr, ids + sp->level_begin[l], (const double *)A,
+                         (const int *)W.loc.p, V, out, (const int *)flag());
+    HIP_TRY(hipGetLastError());
+    if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[4], st));
+    ++W.factorizations;
+    return DVO_AMD_OK;
+  }
+
   // (H + lambda I) x = b (damp) or H x = b into `out`; the flag word says whether a pivot failed (read by the caller)
   int factor_solve_enqueue(bool damp, double lambda, double *out) {
+    if (sp) return sparse_factor_solve_enqueue(damp, lambda, out);
     if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[2], st));
     HIP_TRY(hipMemsetAsync(flag(), 0xff, sizeof(int), st));
     hipLaunchKernelGGL(graph::k_damp_copy, dim3(std::min(4096, graph::grid_for((size_t)N * N, 256))), dim3(256), 0, st,
@@ -748,6 +1294,12 @@ struct Solver {
     return DVO_AMD_OK;
   }
   int matvec(const double *v, double *y) {
+    if (sp) {
+      hipLaunchKernelGGL(graph::k_bsr_matvec, dim3(graph::grid_for(n, 256)), dim3(256), 0, st, n, (const int *)W.bsr_ptr.p,
+                         (const int2 *)W.bsr_rc.p, (const double *)W.Hs.p, v, y);
+      HIP_TRY(hipGetLastError());
+      return DVO_AMD_OK;
+    }
     hipLaunchKernelGGL(graph::k_matvec, dim3(graph::grid_for(n, graph::kBlock / 64)), dim3(graph::kBlock), 0, st,
                        (const double *)H(), N, n, v, y);
     HIP_TRY(hipGetLastError());
@@ -783,9 +1335,7 @@ int run_levenberg(Solver &S, const dvo_amd_graph_options &opt, double *F, dvo_am
       if (opt.initial_lambda > 0.0) {
         lambda = opt.initial_lambda;
       } else {
-        hipLaunchKernelGGL(graph::k_max_diag, dim3(1), dim3(graph::kBlock), 0, S.st, (const double *)S.H(), S.N, S.n,
-                           S.scalars());
-        HIP_TRY(hipGetLastError());
+        GRAPH_TRY(S.max_diag_enqueue());
         double md = 0.0;
         GRAPH_TRY(S.read(&md, 1, nullptr));
         lambda = 1e-5 * md;
@@ -951,6 +1501,11 @@ int run_dogleg(Solver &S, const dvo_amd_graph_options &opt, double *F, dvo_amd_g
 struct Probe {
   double *H, *b, *x, *F;
   int *failed_pivot;
+  // the sparse probe: the stored blocks (row, col slots; 36 doubles each, row-major), capacity in / count out
+  int *block_rc = nullptr;
+  double *blocks = nullptr;
+  int block_capacity = 0;
+  int *n_blocks = nullptr;
 };
 
 int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fixed, int n_edges,
@@ -967,12 +1522,14 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
     }
   const int m = (int)vertex_of.size();
   stats.n_free = m;
-  if (m > DVO_AMD_GRAPH_MAX_FREE_VERTICES) {
-    g_last_error = "dvo_amd_optimize_graph: " + std::to_string(m) + " free active vertices (the dense solver takes at most " +
-                   std::to_string(DVO_AMD_GRAPH_MAX_FREE_VERTICES) + ")";
+  const bool sparse = opt.solver == DVO_AMD_GRAPH_SOLVER_SPARSE;
+  const int cap = sparse ? DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE : DVO_AMD_GRAPH_MAX_FREE_VERTICES;
+  if (m > cap) {
+    g_last_error = "dvo_amd_optimize_graph: " + std::to_string(m) + " free active vertices (the " +
+                   (sparse ? "sparse" : "dense") + " solver takes at most " + std::to_string(cap) + ")";
     return DVO_AMD_ERR_CAPACITY;
   }
-  const int n = 6 * m, N = std::max(graph::kTile, (int)align_up((size_t)n, graph::kTile));
+  const int n = 6 * m, N = sparse ? n : std::max(graph::kTile, (int)align_up((size_t)n, graph::kTile));
   // contributor lists (CSR by target block / by vertex slot), contributors in edge order
   std::map<long long, std::vector<int>> blocks;
   std::vector<std::vector<int>> bl(std::max(m, 1));
@@ -997,6 +1554,113 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
     b_ptr.push_back((int)b_c.size());
   }
 
+  // the sparse solver: symbolic phase, then the fronts' maps and the level schedule
+  Solver::Sparse sched;
+  Symbolic sym;
+  std::vector<int2> slot_rc;  // (row, col) slots of the stored blocks
+  std::vector<int> bsr_ptr, diag_block, hmap, inv, child_list, loc, level_ids, small_ids;
+  double symbolic_ms = 0.0;
+  if (sparse) {
+    const auto t0 = std::chrono::steady_clock::now();
+    sym = symbolic(block_adjacency(m, slot, n_edges, edges));
+    symbolic_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    // everything the sparse path grows: fronts, vectors, H blocks, the maps and the front records (the other buffers are the
+    // dense path's O(m + edges) ones); against 90 % of the free memory plus what the context already holds of these
+    double held = 0.0;
+    if (ctx->graph_ws)
+      for (const GraphWorkspace::Buf *b : {&ctx->graph_ws->A, &ctx->graph_ws->V, &ctx->graph_ws->Hs, &ctx->graph_ws->hmap,
+                                           &ctx->graph_ws->inv, &ctx->graph_ws->loc, &ctx->graph_ws->fronts})
+        held += (double)b->bytes;
+    const double need = sizeof(double) * (sym.front_doubles + sym.vector_doubles + 36.0 * block_rc.size()) +
+                        sizeof(int) * sym.map_ints + sizeof(graph::Front) * (double)sym.n_fronts;
+    if (need > ((double)free_b + held) * 0.9) {
+      g_last_error = "dvo_amd_optimize_graph: the sparse factorization needs " +
+                     std::to_string((long long)(need / 1048576.0)) + " MiB of device storage";
+      return DVO_AMD_ERR_OUT_OF_MEMORY;
+    }
+    slot_rc = block_rc;
+    bsr_ptr.assign(m + 1, 0);
+    diag_block.assign(m, -1);
+    std::map<long long, int> block_index;
+    for (int k = 0; k < (int)block_rc.size(); ++k) {
+      ++bsr_ptr[block_rc[k].x + 1];
+      if (block_rc[k].x == block_rc[k].y) diag_block[block_rc[k].x] = k;
+      block_index[(long long)block_rc[k].x * m + block_rc[k].y] = k;
+      block_rc[k] = make_int2(k, 0);
+    }
+    for (int s = 0; s < m; ++s) bsr_ptr[s + 1] += bsr_ptr[s];
+    const int nf = sym.n_fronts;
+    sched.fronts.resize(nf);
+    long long a_off = 0, h_off = 0;
+    int v_off = 0;
+    for (int k = 0; k < nf; ++k) {
+      graph::Front &F = sched.fronts[k];
+      F.p = sym.piv_ptr[k + 1] - sym.piv_ptr[k];
+      F.u = sym.upd_ptr[k + 1] - sym.upd_ptr[k];
+      F.ld = sym.ld[k];
+      F.ppad = sym.ppad[k];
+      F.a_off = a_off;
+      F.v_off = v_off;
+      F.hmap_off = h_off;
+      F.loc_off = (int)loc.size();
+      a_off += (long long)F.ld * F.ld;
+      v_off += F.ld;
+      loc.insert(loc.end(), sym.piv.begin() + sym.piv_ptr[k], sym.piv.begin() + sym.piv_ptr[k + 1]);
+      loc.insert(loc.end(), sym.upd.begin() + sym.upd_ptr[k], sym.upd.begin() + sym.upd_ptr[k + 1]);
+      const int f = F.p + F.u;
+      hmap.resize(h_off + (long long)f * F.p, -1);
+      for (int r = 0; r < f; ++r)
+        for (int c = 0; c < F.p && c <= r; ++c) {
+          const auto it = block_index.find((long long)loc[F.loc_off + r] * m + loc[F.loc_off + c]);
+          if (it != block_index.end()) hmap[h_off + (long long)r * F.p + c] = it->second;
+        }
+      h_off += (long long)f * F.p;
+      F.ch_begin = (int)child_list.size();
+      child_list.insert(child_list.end(), sym.child.begin() + sym.child_ptr[k], sym.child.begin() + sym.child_ptr[k + 1]);
+      F.ch_end = (int)child_list.size();
+    }
+    // each child's map from its parent's local blocks into its own update set
+    std::vector<int> where(m, -1);
+    for (int k = 0; k < nf; ++k) {
+      const graph::Front &P = sched.fronts[k];
+      for (int q = sym.child_ptr[k]; q < sym.child_ptr[k + 1]; ++q) {
+        graph::Front &C = sched.fronts[sym.child[q]];
+        for (int j = 0; j < C.u; ++j) where[loc[C.loc_off + C.p + j]] = j;
+        C.inv_off = (int)inv.size();
+        for (int b = 0; b < P.p + P.u; ++b) inv.push_back(where[loc[P.loc_off + b]]);
+        for (int j = 0; j < C.u; ++j) where[loc[C.loc_off + C.p + j]] = -1;
+      }
+    }
+    for (int k = 0; k < nf; ++k)
+      if (sym.parent[k] < 0) sched.fronts[k].inv_off = 0;  // roots have no parent and an empty update set
+    if (inv.empty()) inv.push_back(-1);
+    // the level schedule: fronts by level (leaves first), in front order within a level
+    const int L = sym.n_levels;
+    sched.level_begin.assign(1, 0);
+    sched.small_begin.assign(1, 0);
+    sched.small_count.assign(L, 0);
+    sched.wide.assign(L, {});
+    sched.max_ld.assign(L, 0);
+    for (int l = 0; l < L; ++l) {
+      for (int k = 0; k < nf; ++k) {
+        if (sym.level[k] != l) continue;
+        level_ids.push_back(k);
+        sched.max_ld[l] = std::max(sched.max_ld[l], sched.fronts[k].ld);
+        const bool wide = sched.fronts[k].ppad != 6 * sched.fronts[k].p || sched.fronts[k].ld > graph::kSmallMaxLd ||
+                          6 * sched.fronts[k].p > graph::kWidePivots;
+        if (wide)
+          sched.wide[l].push_back(k);
+        else
+          small_ids.push_back(k), ++sched.small_count[l];
+      }
+      sched.level_begin.push_back((int)level_ids.size());
+      sched.small_begin.push_back((int)small_ids.size());
+    }
+  }
+
   HIP_TRY(hipSetDevice(ctx->device));
   GraphWorkspace *Wp = nullptr;
   GRAPH_TRY(workspace(ctx, &Wp));
@@ -1009,9 +1673,12 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
   GRAPH_TRY(grow(W.rho0, sizeof(double) * E));
   GRAPH_TRY(grow(W.chi2, sizeof(double) * E));
   GRAPH_TRY(grow(W.rho1, sizeof(double) * E));
-  GRAPH_TRY(grow(W.H, sizeof(double) * (size_t)N * N));
-  GRAPH_TRY(grow(W.L, sizeof(double) * (size_t)N * N));
-  for (GraphWorkspace::Buf *b : {&W.b, &W.x, &W.hsd, &W.hdl, &W.aux}) GRAPH_TRY(grow(*b, sizeof(double) * N));
+  if (!sparse) {
+    GRAPH_TRY(grow(W.H, sizeof(double) * (size_t)N * N));
+    GRAPH_TRY(grow(W.L, sizeof(double) * (size_t)N * N));
+  }
+  // at least one double: a sparse call with no free active vertex has N = 0 and still clears b
+  for (GraphWorkspace::Buf *b : {&W.b, &W.x, &W.hsd, &W.hdl, &W.aux}) GRAPH_TRY(grow(*b, sizeof(double) * std::max(N, 1)));
   GRAPH_TRY(grow(W.block_rc, sizeof(int2) * std::max<size_t>(1, block_rc.size())));
   GRAPH_TRY(grow(W.block_ptr, sizeof(int) * block_ptr.size()));
   GRAPH_TRY(grow(W.block_c, sizeof(int) * std::max<size_t>(1, block_c.size())));
@@ -1027,6 +1694,34 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
   auto up = [&](GraphWorkspace::Buf &b, const void *src, size_t bytes) {
     return bytes ? hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
   };
+  if (sparse) {
+    auto grow_up = [&](GraphWorkspace::Buf &b, const void *src, size_t bytes) {
+      const int rc = grow(b, std::max<size_t>(bytes, 1));
+      return rc ? rc : (up(b, src, bytes) == hipSuccess ? DVO_AMD_OK : fail_hip("hipMemcpyAsync (sparse maps)", hipGetLastError()));
+    };
+    GRAPH_TRY(grow(W.Hs, sizeof(double) * 36 * std::max<size_t>(1, block_rc.size())));
+    GRAPH_TRY(grow_up(W.bsr_ptr, bsr_ptr.data(), sizeof(int) * bsr_ptr.size()));
+    GRAPH_TRY(grow_up(W.bsr_rc, slot_rc.data(), sizeof(int2) * slot_rc.size()));
+    GRAPH_TRY(grow_up(W.diag_block, diag_block.data(), sizeof(int) * diag_block.size()));
+    GRAPH_TRY(grow_up(W.fronts, sched.fronts.data(), sizeof(graph::Front) * sched.fronts.size()));
+    GRAPH_TRY(grow_up(W.hmap, hmap.data(), sizeof(int) * hmap.size()));
+    GRAPH_TRY(grow_up(W.inv, inv.data(), sizeof(int) * inv.size()));
+    GRAPH_TRY(grow_up(W.child_list, child_list.data(), sizeof(int) * child_list.size()));
+    GRAPH_TRY(grow_up(W.loc, loc.data(), sizeof(int) * loc.size()));
+    GRAPH_TRY(grow_up(W.level_ids, level_ids.data(), sizeof(int) * level_ids.size()));
+    GRAPH_TRY(grow_up(W.small_ids, small_ids.data(), sizeof(int) * small_ids.size()));
+    GRAPH_TRY(grow(W.A, sizeof(double) * (size_t)sym.front_doubles));
+    size_t v_total = 0;
+    for (const graph::Front &F : sched.fronts) v_total += F.ld;
+    GRAPH_TRY(grow(W.V, sizeof(double) * v_total));
+    W.sp_symbolic_ms = symbolic_ms;
+    W.sp_lin_ms = W.sp_fac_ms = W.sp_solve_ms = 0.0;
+    W.sp_fronts = sym.n_fronts;
+    W.sp_levels = sym.n_levels;
+    W.sp_widest = sym.widest;
+    W.sp_factor_doubles = sym.factor_doubles;
+    W.sp_flops = sym.flops;
+  }
   HIP_TRY(up(W.poses, poses, 16 * sizeof(double) * n_vertices));
   HIP_TRY(up(W.edges, edges, sizeof(dvo_amd_graph_edge) * n_edges));
   HIP_TRY(up(W.block_rc, block_rc.data(), sizeof(int2) * block_rc.size()));
@@ -1036,12 +1731,13 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
   HIP_TRY(up(W.b_c, b_c.data(), sizeof(int) * b_c.size()));
   HIP_TRY(up(W.vertex_of, vertex_of.data(), sizeof(int) * vertex_of.size()));
   // blocks no edge touches stay zero; the padding is the identity (its unknowns solve to 0)
-  HIP_TRY(hipMemsetAsync(W.H.p, 0, sizeof(double) * (size_t)N * N, st));
-  HIP_TRY(hipMemsetAsync(W.b.p, 0, sizeof(double) * N, st));
+  if (!sparse) HIP_TRY(hipMemsetAsync(W.H.p, 0, sizeof(double) * (size_t)N * N, st));
+  HIP_TRY(hipMemsetAsync(W.b.p, 0, sizeof(double) * std::max(N, 1), st));
   if (N > n) hipLaunchKernelGGL(graph::k_pad_diag, dim3(graph::grid_for(N - n, 64)), dim3(64), 0, st, (double *)W.H.p, N, n);
   HIP_TRY(hipGetLastError());
 
   Solver S{W, st, n_vertices, n_edges, m, n, N, (int)block_rc.size(), opt.robust_delta};
+  if (sparse) S.sp = &sched;
   double F = 0.0;
   GRAPH_TRY(S.objective(&F));
   stats.initial_objective = F;
@@ -1053,7 +1749,14 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
     int f = -1;
     GRAPH_TRY(S.read(nullptr, 0, &f));
     if (probe->failed_pivot) *probe->failed_pivot = f;
-    if (probe->H) HIP_TRY(hipMemcpy2DAsync(probe->H, sizeof(double) * n, W.H.p, sizeof(double) * N, sizeof(double) * n, n,
+    if (sparse) {
+      const int nb = (int)slot_rc.size();
+      if (probe->n_blocks) *probe->n_blocks = nb;
+      if (probe->block_rc && nb <= probe->block_capacity)
+        for (int k = 0; k < nb; ++k) probe->block_rc[2 * k] = slot_rc[k].x, probe->block_rc[2 * k + 1] = slot_rc[k].y;
+      if (probe->blocks && nb <= probe->block_capacity)
+        HIP_TRY(hipMemcpyAsync(probe->blocks, W.Hs.p, sizeof(double) * 36 * nb, hipMemcpyDeviceToHost, st));
+    } else if (probe->H) HIP_TRY(hipMemcpy2DAsync(probe->H, sizeof(double) * n, W.H.p, sizeof(double) * N, sizeof(double) * n, n,
                                            hipMemcpyDeviceToHost, st));
     if (probe->b) HIP_TRY(hipMemcpyAsync(probe->b, W.b.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
     if (probe->x) HIP_TRY(hipMemcpyAsync(probe->x, W.x.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
@@ -1086,6 +1789,11 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, W.ev[0], W.ev[1]) == hipSuccess) W.lin_ms = ms;
     if (hipEventElapsedTime(&ms, W.ev[2], W.ev[3]) == hipSuccess) W.fac_ms = ms;
+    if (sparse) {
+      W.sp_lin_ms = W.lin_ms;
+      W.sp_fac_ms = W.fac_ms;
+      if (hipEventElapsedTime(&ms, W.ev[3], W.ev[4]) == hipSuccess) W.sp_solve_ms = ms;
+    }
   }
   return DVO_AMD_OK;
 }
@@ -1103,7 +1811,9 @@ void graph_workspace_release(dvo_amd_context *ctx) {
   if (!w) return;
   for (GraphWorkspace::Buf *b : {&w->poses, &w->saved, &w->edges, &w->rec, &w->rho0, &w->chi2, &w->rho1, &w->H, &w->L, &w->b,
                                  &w->x, &w->hsd, &w->hdl, &w->aux, &w->block_rc, &w->block_ptr, &w->block_c, &w->b_ptr,
-                                 &w->b_c, &w->vertex_of, &w->scalars, &w->flag})
+                                 &w->b_c, &w->vertex_of, &w->scalars, &w->flag, &w->Hs, &w->bsr_ptr, &w->bsr_rc,
+                                 &w->diag_block, &w->fronts, &w->hmap, &w->inv, &w->child_list, &w->loc, &w->level_ids,
+                                 &w->small_ids, &w->A, &w->V})
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : w->ev)
     if (e) (void)hipEventDestroy(e);
@@ -1172,6 +1882,96 @@ int dvo_amd_debug_graph_system(dvo_amd_context *ctx, int n_vertices, const doubl
   rc = host::optimize(ctx, n_vertices, copy.data(), fixed, n_edges, edges, opt, nullptr, nullptr, 0, nullptr, st, &probe);
   if (n_free) *n_free = st.n_free;
   return rc;
+}
+
+int dvo_amd_debug_graph_system_sparse(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed,
+                                      int n_edges, const dvo_amd_graph_edge *edges, double robust_delta, int block_capacity,
+                                      int *n_blocks, int *block_rc, double *blocks, double *b, double *x, double *F,
+                                      int *n_free, int *failed_pivot) {
+  dvo_amd_graph_options opt;
+  dvo_amd_default_graph_options(DVO_AMD_GRAPH_DOGLEG, &opt);
+  opt.robust_delta = robust_delta;
+  opt.solver = DVO_AMD_GRAPH_SOLVER_SPARSE;
+  int rc = host::check_arguments(n_vertices, poses, n_edges, edges, &opt);
+  if (rc) return rc;
+  if (block_capacity < 0) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = queue_must_be_idle(ctx, "dvo_amd_debug_graph_system_sparse");
+  if (rc) return rc;
+  std::vector<double> copy(poses, poses + 16 * (size_t)n_vertices);
+  dvo_amd_graph_stats st;
+  std::memset(&st, 0, sizeof(st));
+  int nb = 0;
+  host::Probe probe{nullptr, b, x, F, failed_pivot};
+  probe.block_rc = block_rc;
+  probe.blocks = blocks;
+  probe.block_capacity = block_capacity;
+  probe.n_blocks = &nb;
+  rc = host::optimize(ctx, n_vertices, copy.data(), fixed, n_edges, edges, opt, nullptr, nullptr, 0, nullptr, st, &probe);
+  if (n_free) *n_free = st.n_free;
+  if (n_blocks) *n_blocks = nb;
+  if (!rc && nb > block_capacity && (block_rc || blocks)) return DVO_AMD_ERR_CAPACITY;
+  return rc;
+}
+
+int dvo_amd_debug_graph_symbolic(int n_vertices, const int *fixed, int n_edges, const dvo_amd_graph_edge *edges,
+                                 int capacity, int *n_free, int *n_fronts, int *n_update, int *n_levels, int *widest,
+                                 int *perm, int *parent, int *level, int *pivot_ptr, int *pivot, int *update_ptr, int *update,
+                                 double *factor_doubles, double *flops) {
+  if (n_vertices < 0 || n_edges < 0 || capacity < 0 || (n_edges > 0 && !edges)) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  for (int k = 0; k < n_edges; ++k)
+    if (edges[k].from < 0 || edges[k].from >= n_vertices || edges[k].to < 0 || edges[k].to >= n_vertices ||
+        edges[k].from == edges[k].to)
+      return DVO_AMD_ERR_INVALID_ARGUMENT;
+  std::vector<char> active(n_vertices, 0);
+  for (int k = 0; k < n_edges; ++k) active[edges[k].from] = active[edges[k].to] = 1;
+  std::vector<int> slot(n_vertices, -1);
+  int m = 0;
+  for (int v = 0; v < n_vertices; ++v)
+    if (active[v] && !(fixed && fixed[v])) slot[v] = m++;
+  if (n_free) *n_free = m;
+  if (m > DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE) return DVO_AMD_ERR_CAPACITY;
+  const host::Symbolic S = host::symbolic(host::block_adjacency(m, slot, n_edges, edges));
+  const int nf = S.n_fronts, nu = (int)S.upd.size();
+  if (n_fronts) *n_fronts = nf;
+  if (n_update) *n_update = nu;
+  if (n_levels) *n_levels = S.n_levels;
+  if (widest) *widest = S.widest;
+  if (factor_doubles) *factor_doubles = S.factor_doubles;
+  if (flops) *flops = S.flops;
+  if (std::max(std::max(m, nf + 1), nu) > capacity) return DVO_AMD_ERR_CAPACITY;
+  auto put = [](int *dst, const std::vector<int> &src) {
+    if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(int) * src.size());
+  };
+  put(perm, S.perm);
+  put(parent, S.parent);
+  put(level, S.level);
+  put(pivot_ptr, S.piv_ptr);
+  put(pivot, S.piv);
+  put(update_ptr, S.upd_ptr);
+  put(update, S.upd);
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_debug_graph_sparse_timing(dvo_amd_context *ctx, double *symbolic_ms, double *linearise_ms, double *factorize_ms,
+                                      double *solve_ms, int *fronts, int *levels, int *widest, double *factor_doubles,
+                                      double *flops) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  const host::GraphWorkspace *W = ctx->graph_ws;
+  if (symbolic_ms) *symbolic_ms = W ? W->sp_symbolic_ms : 0.0;
+  if (linearise_ms) *linearise_ms = W ? W->sp_lin_ms : 0.0;
+  if (factorize_ms) *factorize_ms = W ? W->sp_fac_ms : 0.0;
+  if (solve_ms) *solve_ms = W ? W->sp_solve_ms : 0.0;
+  if (fronts) *fronts = W ? W->sp_fronts : 0;
+  if (levels) *levels = W ? W->sp_levels : 0;
+  if (widest) *widest = W ? W->sp_widest : 0;
+  if (factor_doubles) *factor_doubles = W ? W->sp_factor_doubles : 0.0;
+  if (flops) *flops = W ? W->sp_flops : 0.0;
+  return DVO_AMD_OK;
 }
 
 int dvo_amd_debug_graph_timing(dvo_amd_context *ctx, double *linearise_ms, double *factorize_ms, int *n_padded,

@@ -12,8 +12,11 @@ from . import capi
 
 LEVENBERG, DOGLEG = 0, 1
 ALGORITHMS = {"levenberg": LEVENBERG, "dogleg": DOGLEG}
+DENSE, SPARSE = 0, 1
+SOLVERS = {"dense": DENSE, "sparse": SPARSE}
 TERMINATION = {0: "iterations exhausted", 1: "terminate", 2: "fail"}
 MAX_FREE_VERTICES = 1024
+MAX_FREE_VERTICES_SPARSE = 65536
 
 
 class CGraphEdge(C.Structure):
@@ -21,7 +24,7 @@ class CGraphEdge(C.Structure):
 
 
 class CGraphOptions(C.Structure):
-    _fields_ = [("algorithm", C.c_int), ("max_iterations", C.c_int), ("max_trials", C.c_int), ("reserved", C.c_int),
+    _fields_ = [("algorithm", C.c_int), ("max_iterations", C.c_int), ("max_trials", C.c_int), ("solver", C.c_int),
                 ("robust_delta", C.c_double), ("initial_lambda", C.c_double), ("initial_delta", C.c_double)]
 
 
@@ -52,6 +55,12 @@ def _lib():
         L.dvo_amd_debug_graph_timing.argtypes = [C.c_void_p, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dvo_amd_debug_graph_system.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_int), C.c_int, C.POINTER(CGraphEdge),
                                                  C.c_double, dp, dp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        ip = C.POINTER(C.c_int)
+        L.dvo_amd_debug_graph_system_sparse.argtypes = [C.c_void_p, C.c_int, dp, ip, C.c_int, C.POINTER(CGraphEdge), C.c_double,
+                                                        C.c_int, ip, ip, dp, dp, dp, dp, ip, ip]
+        L.dvo_amd_debug_graph_symbolic.argtypes = [C.c_int, ip, C.c_int, C.POINTER(CGraphEdge), C.c_int, ip, ip, ip, ip, ip,
+                                                   ip, ip, ip, ip, ip, ip, ip, dp, dp]
+        L.dvo_amd_debug_graph_sparse_timing.argtypes = [C.c_void_p, dp, dp, dp, dp, ip, ip, ip, dp, dp]
         _bound = True
     return L
 
@@ -121,11 +130,13 @@ class PoseGraph:
 
     def optimize(self, tracker: "capi.DenseTracker", algorithm: str = "dogleg", iterations: int | None = None,
                  robust_delta: float = 5.0, max_trials: int | None = None, initial_lambda: float | None = None,
-                 initial_delta: float | None = None, update: bool = True) -> Result:
+                 initial_delta: float | None = None, update: bool = True, solver: str = "dense") -> Result:
         """Optimize in the tracker's context (dvo_amd_optimize_graph).  Defaults are the reference's (dvo_amd.h); update=True
-        writes the optimized poses back into the graph."""
+        writes the optimized poses back into the graph.  solver: "dense" (at most MAX_FREE_VERTICES free vertices) or "sparse"
+        (the multifrontal sparse Cholesky, at most MAX_FREE_VERTICES_SPARSE)."""
         L = _lib()
         o = default_options(algorithm)
+        o.solver = SOLVERS[solver]
         if iterations is not None:
             o.max_iterations = int(iterations)
         if max_trials is not None:
@@ -194,6 +205,33 @@ class PoseGraph:
         assert 6 * nf.value == n
         return H[:n, :n], b[:n], (x[:n] if fp.value < 0 else None), F.value, fp.value
 
+    def debug_system_sparse(self, tracker: "capi.DenseTracker", robust_delta: float = 5.0):
+        """(diagnostic) the first linear system of optimize(solver="sparse") (dvo_amd_debug_graph_system_sparse):
+        (block (row, col) slots k x 2, blocks k x 6 x 6, b, x of the undamped sparse solve or None when a pivot failed, F,
+        the failed pivot or -1)"""
+        L = _lib()
+        live, nv, ne, P, fixed, ce = self._pack()
+        active = {v for k in live for v in self.edges[k][:2]}
+        m = sum(1 for v in range(nv) if v in active and not self.fixed[v])
+        cap = m + 2 * ne
+        rc, blocks = np.zeros((max(cap, 1), 2), np.int32), np.zeros((max(cap, 1), 6, 6))
+        b, x = np.zeros(max(6 * m, 1)), np.zeros(max(6 * m, 1))
+        F, nf, fp, nb = C.c_double(), C.c_int(), C.c_int(), C.c_int()
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        capi._check(L.dvo_amd_debug_graph_system_sparse(tracker._h, nv, P.ctypes.data_as(dp), fixed.ctypes.data_as(ip), ne, ce,
+                                                        float(robust_delta), cap, C.byref(nb), rc.ctypes.data_as(ip),
+                                                        blocks.ctypes.data_as(dp), b.ctypes.data_as(dp), x.ctypes.data_as(dp),
+                                                        C.byref(F), C.byref(nf), C.byref(fp)),
+                    "dvo_amd_debug_graph_system_sparse")
+        assert nf.value == m
+        k, n = nb.value, 6 * m
+        return rc[:k].copy(), blocks[:k].copy(), b[:n], (x[:n] if fp.value < 0 else None), F.value, fp.value
+
+    def debug_symbolic(self):
+        """(diagnostic) the sparse solver's symbolic phase on this graph's structure; see symbolic()"""
+        live = self.live_edges()
+        return symbolic(len(self.poses), [self.edges[k][:2] for k in live], self.fixed)
+
     def remove_outlier_edges(self, weight_threshold: float, n_max: int = -1) -> list:
         """KeyframeGraph::removeOutlierConstraints (keyframe_graph.cpp:643-675) on the weights (rho1) of the last optimize():
         edges with a robust kernel (every edge when that optimize() had robust_delta > 0, none otherwise) whose weight is below the threshold are
@@ -219,3 +257,45 @@ def debug_timing(tracker: "capi.DenseTracker"):
     capi._check(_lib().dvo_amd_debug_graph_timing(tracker._h, C.byref(a), C.byref(b), C.byref(n), C.byref(f)),
                 "dvo_amd_debug_graph_timing")
     return a.value, b.value, n.value, f.value
+
+
+def symbolic(n_vertices: int, pairs, fixed=None) -> dict:
+    """(diagnostic, no GPU) the sparse solver's symbolic phase (dvo_amd_debug_graph_symbolic) for n_vertices vertices, the edges'
+    (from, to) pairs in edge order and the fixed flags: dict(n_free, perm, parent, level, pivots, updates (lists of slot
+    arrays per front, in elimination order), n_levels, widest, factor_doubles, flops)"""
+    L = _lib()
+    ce = (CGraphEdge * max(len(pairs), 1))()
+    for i, (f, t) in enumerate(pairs):
+        ce[i].from_, ce[i].to = int(f), int(t)
+    fx = None if fixed is None else np.ascontiguousarray(np.asarray(fixed, dtype=np.int32))
+    ip = C.POINTER(C.c_int)
+    counts = [C.c_int() for _ in range(5)]
+    fd, fl = C.c_double(), C.c_double()
+    cap = max(n_vertices + 1, 16)
+    while True:
+        arrs = [np.zeros(cap, np.int32) for _ in range(7)]
+        rc = L.dvo_amd_debug_graph_symbolic(n_vertices, None if fx is None else fx.ctypes.data_as(ip), len(pairs), ce, cap,
+                                            *[C.byref(c) for c in counts], *[a.ctypes.data_as(ip) for a in arrs],
+                                            C.byref(fd), C.byref(fl))
+        if rc == 7 and counts[0].value <= MAX_FREE_VERTICES_SPARSE:
+            cap = max(counts[0].value, counts[1].value + 1, counts[2].value)
+            continue
+        capi._check(rc, "dvo_amd_debug_graph_symbolic")
+        break
+    m, nf = counts[0].value, counts[1].value
+    perm, parent, level, pptr, piv, uptr, upd = arrs
+    return {"n_free": m, "perm": perm[:m].copy(), "parent": parent[:nf].copy(), "level": level[:nf].copy(),
+            "pivots": [piv[pptr[k]:pptr[k + 1]].copy() for k in range(nf)],
+            "updates": [upd[uptr[k]:uptr[k + 1]].copy() for k in range(nf)],
+            "n_levels": counts[3].value, "widest": counts[4].value, "factor_doubles": fd.value, "flops": fl.value}
+
+
+def debug_sparse_timing(tracker: "capi.DenseTracker") -> dict:
+    """(diagnostic) the last sparse optimize() on the tracker (dvo_amd_debug_graph_sparse_timing)"""
+    d = [C.c_double() for _ in range(4)]
+    i = [C.c_int() for _ in range(3)]
+    fd, fl = C.c_double(), C.c_double()
+    capi._check(_lib().dvo_amd_debug_graph_sparse_timing(tracker._h, *[C.byref(x) for x in d], *[C.byref(x) for x in i],
+                                                         C.byref(fd), C.byref(fl)), "dvo_amd_debug_graph_sparse_timing")
+    return {"symbolic_ms": d[0].value, "linearise_ms": d[1].value, "factorize_ms": d[2].value, "solve_ms": d[3].value,
+            "fronts": i[0].value, "levels": i[1].value, "widest": i[2].value, "factor_doubles": fd.value, "flops": fl.value}

@@ -548,17 +548,45 @@ int dvo_amd_error_image(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_am
  * Determinism: every sum has a fixed order (by edge index within a block, a fixed tile order in the factorization, fixed-shape
  * reductions); no floating-point atomics: the result is a function of the inputs in their order and of the options alone,
  * bit-identical between runs and contexts on one device.
- * Limits: the system is solved densely (O(n^3) per factorization, fp64; H is n x n on the device).  That fits a keyframe-only
- * graph and the dense final graph of a sequence of some hundred frames (fr1/desk: 573 frames, n = 3438); more than 1024 free
- * active vertices return DVO_AMD_ERR_CAPACITY with poses untouched.  A sparse factorization is not implemented.
+ * Limits and solvers (options.solver):
+ * DVO_AMD_GRAPH_SOLVER_DENSE (0, the default): H is solved densely (O(n^3) per factorization, fp64; H is n x n on the
+ * device).  That fits a keyframe-only graph and the dense final graph of a sequence of some hundred frames (fr1/desk: 573
+ * frames, n = 3438); more than DVO_AMD_GRAPH_MAX_FREE_VERTICES (1024) free active vertices return DVO_AMD_ERR_CAPACITY with
+ * poses untouched.
+ * DVO_AMD_GRAPH_SOLVER_SPARSE (1): a multifrontal sparse Cholesky on the 6 x 6 block pattern of H (g2o's LinearSolverCSparse
+ * role), for the one-vertex-per-frame final graph of sequences of thousands of frames.  Once per call the host orders the free
+ * active vertices by nested dissection (recursive bisection with BFS level-structure vertex separators, down to parts of at
+ * most 16 vertices or parts no BFS level separates; components as a forest).  The order and the assembly tree are a function
+ * of the graph's structure alone (the free active vertices, the edges and their order; ties go by vertex slot).  H is stored
+ * as its nonzero 6 x 6 blocks, each bit-identical to the same block of the dense path's H; the factorization runs level by
+ * level up the assembly tree, and a call with no free active vertex returns DVO_AMD_OK with poses untouched, as the dense
+ * path does.
+ *   - Same iteration semantics: every rule above (increment, error, Jacobians, Cauchy kernel, Levenberg and dogleg drivers,
+ *     failure rules) applies unchanged.
+ *   - A different elimination order and summation order: solves, b^T H b and h^T H h agree with the dense path to rounding,
+ *     not bit for bit, and so may the iterations built on them.
+ *   - Deterministic: no floating-point atomics; results are bit-identical between runs and contexts on one device.
+ *   - A pivot <= 0 or NaN in any front is a failed solve, counted in cholesky_failures, and the step is not applied.
+ *   - A zero row or column of H fails on both paths.  A numerically singular system (a component with no fixed vertex) or a
+ *     near-singular one may fail on one path and not on the other: the two orders round differently.
+ *   - More than DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE (65536) free active vertices return DVO_AMD_ERR_CAPACITY with poses
+ *     untouched (slots and block indices are 32-bit; 6 x 65536 unknowns index every front and vector in int).  When the
+ *     storage the symbolic phase predicts for the sparse solver (front matrices and vectors, H blocks, index maps) exceeds
+ *     90 % of the device's free memory plus what the context already holds of it, the call returns
+ *     DVO_AMD_ERR_OUT_OF_MEMORY with poses untouched, as does a device allocation that fails later; there is no fall-back to
+ *     another path.
  * Argument checks come first and need no device: DVO_AMD_ERR_INVALID_ARGUMENT for an out-of-range vertex index, from == to, a
  * non-finite measurement, information or pose, an information matrix not symmetric to 1e-9 relative (|O_ij - O_ji| >
- * 1e-9 max(|O_ij|, |O_ji|, 1e-300)), bad options (algorithm, max_iterations < 0, max_trials < 1, non-finite values).  Then
- * DVO_AMD_ERR_NO_DEVICE without a GPU and DVO_AMD_ERR_INVALID_ARGUMENT for a NULL ctx or a context with queued pairs.
+ * 1e-9 max(|O_ij|, |O_ji|, 1e-300)), bad options (algorithm, solver, max_iterations < 0, max_trials < 1, non-finite values).
+ * Then DVO_AMD_ERR_NO_DEVICE without a GPU and DVO_AMD_ERR_INVALID_ARGUMENT for a NULL ctx or a context with queued pairs.
  */
 #define DVO_AMD_GRAPH_LEVENBERG 0
 #define DVO_AMD_GRAPH_DOGLEG 1
 #define DVO_AMD_GRAPH_MAX_FREE_VERTICES 1024
+#define DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE 65536
+/* options.solver */
+#define DVO_AMD_GRAPH_SOLVER_DENSE 0
+#define DVO_AMD_GRAPH_SOLVER_SPARSE 1
 /* termination */
 #define DVO_AMD_GRAPH_ITERATIONS_EXHAUSTED 0
 #define DVO_AMD_GRAPH_TERMINATE 1
@@ -574,7 +602,7 @@ typedef struct {
   int algorithm;             /* DVO_AMD_GRAPH_LEVENBERG / _DOGLEG */
   int max_iterations;
   int max_trials;            /* attempts per iteration: 10 (Levenberg), 100 (dogleg) */
-  int reserved;
+  int solver;                /* DVO_AMD_GRAPH_SOLVER_DENSE (0, default) / _SPARSE */
   double robust_delta;       /* Cauchy kernel delta on every edge; <= 0: no kernel */
   double initial_lambda;     /* Levenberg: <= 0 = 1e-5 max diag(H); dogleg: 1e-7 */
   double initial_delta;      /* dogleg trust region: 1e4 (unused by Levenberg) */

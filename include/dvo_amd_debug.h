@@ -159,6 +159,33 @@ int dvo_amd_debug_graph_timing(dvo_amd_context *ctx, double *linearise_ms, doubl
 int dvo_amd_debug_graph_system(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,
                                const dvo_amd_graph_edge *edges, double robust_delta, double *H, double *b, double *x,
                                double *F, int *n_free, int *failed_pivot);
+/* the sparse counterpart of dvo_amd_debug_graph_system (options.solver = DVO_AMD_GRAPH_SOLVER_SPARSE): the stored 6 x 6 blocks
+ * of H (*n_blocks of them, both mirror images, sorted by (row, col) slot; block_rc: row, col per block; blocks: 36 doubles
+ * each, row-major), b and x (6 * n_free each, slot order; x = the undamped sparse solve, valid when *failed_pivot < 0, else
+ * *failed_pivot >= 0 is an index within the failing front) and F.  More than block_capacity blocks: DVO_AMD_ERR_CAPACITY
+ * with *n_blocks set.  Poses are not moved. */
+int dvo_amd_debug_graph_system_sparse(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed,
+                                      int n_edges, const dvo_amd_graph_edge *edges, double robust_delta, int block_capacity,
+                                      int *n_blocks, int *block_rc, double *blocks, double *b, double *x, double *F,
+                                      int *n_free, int *failed_pivot);
+/* the sparse solver's symbolic phase on these vertices and edges (only from / to of an edge are read); needs no GPU.  Slots
+ * are the free active vertices in increasing index.  perm (n_free): the slot eliminated k-th; per front (postorder, children
+ * before parents): parent (-1 for a root), level (0 = leaves; a parent's level exceeds its children's), pivot slots and
+ * update slots as CSR (pivot_ptr / update_ptr: n_fronts + 1 entries), both in elimination order; the predicted factor doubles
+ * (nonzeros of L) and flops of one numeric factorization; the level count and the widest front (scalar dimension).  Every
+ * array holds `capacity` ints; when n_free, n_fronts + 1 or n_update exceeds it the call returns DVO_AMD_ERR_CAPACITY with
+ * the counts set.  Any output may be NULL. */
+int dvo_amd_debug_graph_symbolic(int n_vertices, const int *fixed, int n_edges, const dvo_amd_graph_edge *edges,
+                                 int capacity, int *n_free, int *n_fronts, int *n_update, int *n_levels, int *widest,
+                                 int *perm, int *parent, int *level, int *pivot_ptr, int *pivot, int *update_ptr, int *update,
+                                 double *factor_doubles, double *flops);
+/* the last sparse dvo_amd_optimize_graph on the context: host ms of its symbolic phase; device ms (hipEvents) of its first
+ * linearisation, of its first numeric factorization (assembly + partial factorization of every front) and of the
+ * substitutions that follow it; the front count, level count, widest front (scalar dimension), predicted factor doubles and
+ * flops */
+int dvo_amd_debug_graph_sparse_timing(dvo_amd_context *ctx, double *symbolic_ms, double *linearise_ms, double *factorize_ms,
+                                      double *solve_ms, int *fronts, int *levels, int *widest, double *factor_doubles,
+                                      double *flops);
 
 #ifdef __cplusplus
 }
