@@ -11,7 +11,9 @@ LocalTracker::update pre-builds them (dvo_slam/src/local_tracker.cpp:163-169), s
 DenseTracker::match only.  With N GPUs every rank aligns its own B pairs (independent units, no data-path
 collective): weak scaling, value = N * B * K / max-over-ranks(time).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline figure needs: set-up, warm-up, the timed
+steps, --dump-outputs and the line.  Everything else it can measure or check (single-pair latency, the timed-region check,
+the roofline and its counter passes, CPU baselines, side workloads, the tile-shard side measurement) runs with --full.
 """
 import argparse
 import json
@@ -43,8 +45,14 @@ def parse():
                     help="distinct keyframes.  Pair i of a step = (keyframe i %% R, frame (i // R) %% C): with the defaults "
                          "(96 x 12 = 1152) every pair of a step is a different combination and the 108 pyramids (2.1 GB) "
                          "are far beyond the 256 MiB Infinity Cache")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample (rank 0, N=1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the single-pair latency probe, the check of the timed "
+                         "region against single match() calls, the per-launch kernel timing pass and the roofline (with its "
+                         "rocprofv3 counter passes), the CPU baselines, the side workloads and, with N > 1 GPUs, the tile-shard "
+                         "side measurement.  Without it a run sets up, warms up, times the steps, writes --dump-outputs and "
+                         "prints the line")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline sample (--full, rank 0, N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) no CPU baselines")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="multi-rank rehearsal on a one-GPU box: every rank uses GPU 0 and the ranks synchronise over gloo "
                          "(exercises the N > 1 code path; the figure is meaningless)")
@@ -52,15 +60,16 @@ def parse():
                     help="no GPU work at all: ranks rendezvous over gloo, 'align' their share with a stand-in sleep and print "
                          "the line (tests/test_distributed.py checks the spawn / aggregate / one-line plumbing on the CPU)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the informational side measurements (cache-resident variant, STREAM copy, frame ingest, "
+                    help="(--full) skip the informational side measurements (cache-resident variant, STREAM copy, frame ingest, "
                          "loop-closure validator, all-core CPU baseline); rank 0 at N=1 only")
     ap.add_argument("--counter-leg", action="store_true",
-                    help="the short run a rocprofv3 counter pass profiles (bench.py starts two of them itself, see "
-                         "--no-live-counters): like --no-extras --no-cpu-baseline, and without the single-pair latency probe and the "
-                         "timed-region check")
+                    help="the short run a rocprofv3 counter pass profiles (bench.py --full starts them itself, see "
+                         "--no-live-counters): like --full --no-extras --no-cpu-baseline, and without the single-pair latency probe "
+                         "and the timed-region check")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="do not run the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) as child processes of this run; "
-                         "roofline.traffic then comes from the committed profile of the same command (traffic_source says which)")
+                    help="(--full) do not run the rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ_INSTS_VALU + SQ_INSTS_MFMA) "
+                         "as child processes of this run; roofline.traffic then comes from the committed profile of the same "
+                         "command (traffic_source says which)")
     ap.add_argument("--tile-shard", action="store_true",
                     help="BASELINE config 4 instead of the default: ONE pair at a time, every level tile-sharded over the "
                          "N GPUs with a per-iteration exchange of the band records (strong scaling, expected to be "
@@ -90,8 +99,8 @@ def parse():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and (args.plumbing_only or args.tile_shard):
         ap.error("--dump-outputs writes the results of the default workload's timed steps: not with --plumbing-only or --tile-shard")
-    if args.counter_leg:
-        args.no_extras = args.no_cpu_baseline = True
+    if args.counter_leg:  # (the counter summaries select the launches the line's roofline section counts)
+        args.full = args.no_extras = args.no_cpu_baseline = True
     if args.no_extras:
         args.no_live_counters = True  # (the counter passes are a side measurement of the full line)
     if args.threads is None:
@@ -259,11 +268,13 @@ def main():
     ref = capi.RgbdImagePyramid(ref_frame[0], ref_frame[1], K, levels, device=device)
     curs = [capi.RgbdImagePyramid(f[0], f[1], K, levels, device=device) for f in cur_frames]
     prep_first_ms = (time.perf_counter() - t0) * 1e3 / (1 + len(curs))  # includes the one-off slab allocations
-    # steady state (slabs come from the pool): build some of the same frames again and drop them
-    t0 = time.perf_counter()
-    for f in cur_frames[:8]:
-        capi.RgbdImagePyramid(f[0], f[1], K, levels, device=device)
-    prep_ms = (time.perf_counter() - t0) * 1e3 / len(cur_frames[:8])
+    prep_ms = None
+    if args.full and not args.tile_shard:
+        # steady state (slabs come from the pool): build some of the same frames again and drop them
+        t0 = time.perf_counter()
+        for f in cur_frames[:8]:
+            capi.RgbdImagePyramid(f[0], f[1], K, levels, device=device)
+        prep_ms = (time.perf_counter() - t0) * 1e3 / len(cur_frames[:8])
     if args.tile_shard:
         return tile_shard_bench(args, capi, synth, sharding, dist, rank, world, device, ref_frame, cur_frames, K, levels,
                                 first_level)
@@ -362,31 +373,34 @@ def main():
         # every library of the run is mapped by now: raw-address stacks (glog under rocprofv3) can be attributed afterwards
         with open(os.environ["DVO_BENCH_MAPS"], "w") as fh:
             fh.write(open("/proc/self/maps").read())
-    # single-pair latency (informational)
-    # One match() per frame is the reference's default deployment (dvo_ros/src/camera_dense_tracking.cpp:269): a tracker configured
-    # for it (dvo_amd_config::segment_geometry = DVO_AMD_GEOMETRY_LATENCY, round 5) next to the batch's own configuration.
-    n_lat = 10
+    # single-pair latency (informational, --full)
+    single_ms = single_ms_batch_geometry = None
+    if args.full:
+        # One match() per frame is the reference's default deployment (dvo_ros/src/camera_dense_tracking.cpp:269): a tracker configured
+        # for it (dvo_amd_config::segment_geometry = DVO_AMD_GEOMETRY_LATENCY, round 5) next to the batch's own configuration.
+        n_lat = 10
 
-    def latency_of(tracker):
-        rounds = []
-        for _ in range(0 if args.counter_leg else 3):  # the median of three rounds of ten: one round is at the mercy of whatever the box does in those 7 ms
-            t0 = time.perf_counter()
-            for i in range(n_lat):
-                tracker.match(ref, curs[i % len(curs)])
-            rounds.append((time.perf_counter() - t0) * 1e3 / n_lat)
-        return sorted(rounds)[1] if rounds else None
-    trk_latency = capi.DenseTracker(capi.Config(FirstLevel=first_level, LastLevel=0, SegmentGeometry=capi.GEOMETRY_LATENCY), device=device)
-    if not args.counter_leg:
-        trk_latency.match(ref, curs[0])  # (its scratch and streams exist before the clock starts)
-    single_ms = latency_of(trk_latency)
-    single_ms_batch_geometry = latency_of(trk)
-    del trk_latency
+        def latency_of(tracker):
+            rounds = []
+            for _ in range(0 if args.counter_leg else 3):  # the median of three rounds of ten: one round is at the mercy of whatever the box does in those 7 ms
+                t0 = time.perf_counter()
+                for i in range(n_lat):
+                    tracker.match(ref, curs[i % len(curs)])
+                rounds.append((time.perf_counter() - t0) * 1e3 / n_lat)
+            return sorted(rounds)[1] if rounds else None
+        trk_latency = capi.DenseTracker(capi.Config(FirstLevel=first_level, LastLevel=0, SegmentGeometry=capi.GEOMETRY_LATENCY), device=device)
+        if not args.counter_leg:
+            trk_latency.match(ref, curs[0])  # (its scratch and streams exist before the clock starts)
+        single_ms = latency_of(trk_latency)
+        single_ms_batch_geometry = latency_of(trk)
+        del trk_latency
 
     # With one host thread the HIP events around every k_tick launch are taken inside the timed region.  With several
     # threads kernels of different streams overlap on the GPU, so the per-launch durations are measured in a second,
     # single-stream pass of the same batch right after the timed region.
     # The launches the per-launch roofline figures describe are bracketed by two no-op dispatches named k_marker, so that a
-    # profiler's summary can pick exactly them (dvo_slam_amd/pmc.py).
+    # profiler's summary can pick exactly them (dvo_slam_amd/pmc.py).  A plain run takes the events too (and does not report
+    # them): the timed region is then the same with and without --full.
     if T == 1:
         trk.marker(1)
         trk.kernel_timing(True, reset=True)
@@ -401,17 +415,19 @@ def main():
         trk.marker(2)
     if args.dump_outputs and rank == 0:  # (before anything else reuses the result structs the last step was collected into)
         dump_outputs(args.dump_outputs, kept, B)
-    region_check = None if args.counter_leg else check_timed_region(capi, synth, cfg, device, kept, refs, curb)
+    region_check = None
+    if args.full and not args.counter_leg:
+        region_check = check_timed_region(capi, synth, cfg, device, kept, refs, curb)
     alg_bytes = sum(c[0] for c in col)
     discarded_bytes = sum(c[4] for c in col)
     passes = sum(c[1] for c in col)
     iterations_delivered = sum(c[3] for c in col)
     if sum(c[2] for c in col):
         raise SystemExit("bench.py: a pair of the timed region came back NaN")
-    if T == 1:
+    if args.full and T == 1:
         k_ms, k_launches = trk.kernel_timing(False)
         log = trk.tick_log()
-    else:
+    elif args.full:
         # one host thread's share of the batch, same residency as in the timed region, on one stream
         trk.marker(1)
         trk.kernel_timing(True, reset=True)
@@ -430,7 +446,7 @@ def main():
 
     tile_shard = None
     side_hung = False
-    if world > 1 and (not args.rehearse_on_one_gpu or os.environ.get("DVO_AMD_EXCHANGE") == "peer"):
+    if args.full and world > 1 and (not args.rehearse_on_one_gpu or os.environ.get("DVO_AMD_EXCHANGE") == "peer"):
         # (a one-GPU rehearsal can only exercise the peer exchange: RCCL refuses two ranks on one device)
         # BASELINE config 4 from the driver's own multi-GPU command: every rank takes part (the exchange is collective).
         # The headline figure above is complete at this point.  The side measurement runs under a deadline on its own thread:
@@ -460,12 +476,6 @@ def main():
                                                   "tile-shard side measurement on rank %d" % rank)
 
     if rank == 0:
-        if T == 1:
-            alg_bytes_k, discarded_k = alg_bytes, discarded_bytes
-        # USEFUL algorithmic bytes: speculative residual passes whose iteration was rolled back are not counted
-        useful_k = alg_bytes_k - discarded_k
-        achieved = useful_k / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
-        useful = alg_bytes - discarded_bytes
         line = {
             "metric": "frame-pairs/s (640x480, 4-level GN align)" if W == 640 else f"frame-pairs/s ({W}x{H}, {levels}-level GN align)",
             "value": value,
@@ -505,166 +515,176 @@ def main():
             },
             "build_id": capi.build_id(),
             "iterations_per_pair": iterations_delivered / max(1, B * args.steps),
-            "timed_region_check": region_check,
-            "max_deviation_from_single_match": region_check["max_deviation_from_single_match"] if region_check else None,
-            "single_pair_latency_ms": single_ms,
-            "single_pair_latency": {
-                "ms": single_ms, "configuration": "segment_geometry = DVO_AMD_GEOMETRY_LATENCY (levels 3..0 in 1/2/2/4 steps per wave)",
-                "ms_with_the_batch_configuration": single_ms_batch_geometry,
-                "batch_configuration": "segment_geometry = DVO_AMD_GEOMETRY_THROUGHPUT (4/4/10/10: row-aligned segments on the fine levels), what the timed region runs",
-                "what": "one dvo_amd_match() at a time through the Python binding, median of three rounds of ten pairs; the geometry "
-                        "is a field of the tracker's configuration and part of what a result is a function of"},
-            "prep_ms_per_frame": prep_ms,
-            "prep_ms_per_frame_first_use": prep_first_ms,
-            # build the new frame's pyramid from host planes + one match()
-            "end_to_end_ms_per_frame_one_stream": None if single_ms is None else prep_ms + single_ms,
-            "roofline": {
-                "bound": "hbm",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "achieved_is": "USEFUL algorithmic bytes (56 B per selected reference pixel per residual pass, SURVEY.md 8d, without "
-                               "the speculative passes that were rolled back: `speculation_waste`) / k_tick launch duration; an "
-                               "upper-level view, not the bytes HBM actually moved: see `traffic` and `issue`",
-                "speculation_waste": {"discarded_fraction_of_submitted_bytes": (discarded_k / alg_bytes_k) if alg_bytes_k else None,
-                                      "achieved_counting_discarded_passes": alg_bytes_k / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0},
-                "traffic": None,          # filled in below: roofline_traffic()
-                "traffic_source": None,
-                "kernel": "k_tick (fused warp+residual+weights+normal equations, with the log-likelihood items of the tick)",
-                "launches": int(k_launches),
-                "avg_launch_us": (k_ms * 1e3 / k_launches) if k_launches else None,
-                "alg_bytes_per_launch": (useful_k / k_launches) if k_launches else None,
-                "measured": "HIP events stamped by the dispatch itself (hipExtLaunchKernel start / stop) on the launching "
-                            "stream, every launch alone on the GPU, " + ("inside the timed region" if T == 1 else
-                            "in a single-stream pass over one host thread's share of the batch, same pairs in flight, right after "
-                            "the timed region (which ran %d streams at once: its launches overlap, so the per-launch figure "
-                            "here is not the concurrent rate)" % T),
-                "residual_passes": int(passes),
-                "concurrent": {
-                    "achieved": useful / elapsed_local / 1e9, "unit": "GB/s", "frac": useful / elapsed_local / 1e9 / HBM_PEAK_GBS,
-                    "discarded_fraction_of_submitted_bytes": (discarded_bytes / alg_bytes) if alg_bytes else None,
-                    "what": "all launches of the timed region of this GPU together: their USEFUL algorithmic bytes / the wall time of "
-                            "the region (%d host threads, k_finalize and the host turn-around included)" % T},
-                "issue": issue_roofline(log, k_ms),
-            },
+            "full": args.full,
         }
-        line["roofline"]["traffic"], line["roofline"]["traffic_source"] = roofline_traffic(args, world, line)
-        try:
-            if args.no_extras:  # (a counter / trace pass must not find batch-form k_tick launches behind the timing pass)
-                raise RuntimeError("skipped under --no-extras")
-            # (the level's own geometry -- ten steps of 64 pixels per wave, one image row, for a 640x480 level 0 since the end of round 5
-            # -- and, beside it, 8 steps)
-            ms_i, ab_i, nl_i = trk.bench_residual_pass(ref, curs[0], 0, cur_pose(0), 36, 0, reps=20)
-            ms_8, ab_8, nl_8 = trk.bench_residual_pass(ref, curs[0], 0, cur_pose(0), 36, 2, reps=20)
-            line["roofline_isolated_kernel"] = {
-                "what": "the residual pass alone: level 0, 36 pairs in one launch (one launch's worth of resident pairs), the wave "
-                        "segments match() gives this level (segment_geometry = DVO_AMD_GEOMETRY_THROUGHPUT)",
-                "achieved": ab_i / ms_i / 1e6, "unit": "GB/s", "frac": ab_i / ms_i / 1e6 / HBM_PEAK_GBS,
-                "launch_us": ms_i * 1e3 / nl_i, "alg_bytes_per_launch": ab_i / nl_i,
-                "with_8_steps_per_wave": {"frac": ab_8 / ms_8 / 1e6 / HBM_PEAK_GBS, "launch_us": ms_8 * 1e3 / nl_8}}
-            # the timed region against what the kernel body reaches on its best case in this very run (the level-0 pass alone on
-            # the GPU sits on the kernel's practical issue ceiling): how much of that the whole job keeps
-            line["roofline"]["concurrent"]["fraction_of_the_isolated_kernel"] = (
-                line["roofline"]["concurrent"]["frac"] / line["roofline_isolated_kernel"]["frac"])
-        except Exception as exc:  # pragma: no cover
-            line["roofline_isolated_kernel"] = {"error": str(exc)}
-        if tile_shard is not None:
-            line["tile_shard"] = tile_shard
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline(args, ref_frame, cur_frames[:8], K, levels, first_level)
-        if world == 1 and not args.no_extras:
-            def cache_resident():
-                # round 1's workload for comparison: 8 distinct frames against ONE keyframe (9 pyramids, 180 MB: inside the
-                # Infinity Cache, each distinct pair ~4x in every launch, identical reads that L2 dedups)
-                r_l, c_l = [ref] * B, [curs[i % 8] for i in range(B)]
-                run_steps(1, [], r_l, c_l)
-                t0 = time.perf_counter()
-                n = max(2, args.steps // 2)
-                run_steps(n, [], r_l, c_l)
-                dt = time.perf_counter() - t0
-                return {"value": B * n / dt, "unit": "frame-pairs/s", "steps": n,
-                        "what": "the same batch size with 8 distinct frames against 1 keyframe (9 pyramids inside the "
-                                "Infinity Cache, pairs repeated 144x per step): round 1's default workload"}
-            def sensor_noise():
-                # The regime the reference actually runs in (benchmark_slam.cpp:56-80): the SAME views and the same pair list as
-                # the timed region, delivered as a sensor delivers them -- 8-bit grey, uint16 depth at 1/5000 m, depth noise of
-                # the sigma the reference models itself (dense_tracking_impl.cpp:122-128) -- and ingested on the device
-                # (dvo_amd_pyramid_create_raw).  Not the headline: BASELINE.json's metric is quoted on the noise-free pair.
-                t_ingest = [0.0]
-
-                def raw_pyr(frame, fid):
-                    g, z = synth.sensor_from_analytic(frame[0], frame[1], frame_id=fid)
+        if args.full:
+            if T == 1:
+                alg_bytes_k, discarded_k = alg_bytes, discarded_bytes
+            # USEFUL algorithmic bytes: speculative residual passes whose iteration was rolled back are not counted
+            useful_k = alg_bytes_k - discarded_k
+            achieved = useful_k / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0
+            useful = alg_bytes - discarded_bytes
+            line.update({
+                "timed_region_check": region_check,
+                "max_deviation_from_single_match": region_check["max_deviation_from_single_match"] if region_check else None,
+                "single_pair_latency_ms": single_ms,
+                "single_pair_latency": {
+                    "ms": single_ms, "configuration": "segment_geometry = DVO_AMD_GEOMETRY_LATENCY (levels 3..0 in 1/2/2/4 steps per wave)",
+                    "ms_with_the_batch_configuration": single_ms_batch_geometry,
+                    "batch_configuration": "segment_geometry = DVO_AMD_GEOMETRY_THROUGHPUT (4/4/10/10: row-aligned segments on the fine levels), what the timed region runs",
+                    "what": "one dvo_amd_match() at a time through the Python binding, median of three rounds of ten pairs; the geometry "
+                            "is a field of the tracker's configuration and part of what a result is a function of"},
+                "prep_ms_per_frame": prep_ms,
+                "prep_ms_per_frame_first_use": prep_first_ms,
+                # build the new frame's pyramid from host planes + one match()
+                "end_to_end_ms_per_frame_one_stream": None if single_ms is None else prep_ms + single_ms,
+                "roofline": {
+                    "bound": "hbm",
+                    "achieved": achieved,
+                    "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS,
+                    "achieved_is": "USEFUL algorithmic bytes (56 B per selected reference pixel per residual pass, SURVEY.md 8d, without "
+                                   "the speculative passes that were rolled back: `speculation_waste`) / k_tick launch duration; an "
+                                   "upper-level view, not the bytes HBM actually moved: see `traffic` and `issue`",
+                    "speculation_waste": {"discarded_fraction_of_submitted_bytes": (discarded_k / alg_bytes_k) if alg_bytes_k else None,
+                                          "achieved_counting_discarded_passes": alg_bytes_k / (k_ms * 1e-3) / 1e9 if k_ms > 0 else 0.0},
+                    "traffic": None,          # filled in below: roofline_traffic()
+                    "traffic_source": None,
+                    "kernel": "k_tick (fused warp+residual+weights+normal equations, with the log-likelihood items of the tick)",
+                    "launches": int(k_launches),
+                    "avg_launch_us": (k_ms * 1e3 / k_launches) if k_launches else None,
+                    "alg_bytes_per_launch": (useful_k / k_launches) if k_launches else None,
+                    "measured": "HIP events stamped by the dispatch itself (hipExtLaunchKernel start / stop) on the launching "
+                                "stream, every launch alone on the GPU, " + ("inside the timed region" if T == 1 else
+                                "in a single-stream pass over one host thread's share of the batch, same pairs in flight, right after "
+                                "the timed region (which ran %d streams at once: its launches overlap, so the per-launch figure "
+                                "here is not the concurrent rate)" % T),
+                    "residual_passes": int(passes),
+                    "concurrent": {
+                        "achieved": useful / elapsed_local / 1e9, "unit": "GB/s", "frac": useful / elapsed_local / 1e9 / HBM_PEAK_GBS,
+                        "discarded_fraction_of_submitted_bytes": (discarded_bytes / alg_bytes) if alg_bytes else None,
+                        "what": "all launches of the timed region of this GPU together: their USEFUL algorithmic bytes / the wall time of "
+                                "the region (%d host threads, k_finalize and the host turn-around included)" % T},
+                    "issue": issue_roofline(log, k_ms),
+                },
+            })
+            line["roofline"]["traffic"], line["roofline"]["traffic_source"] = roofline_traffic(args, world, line)
+            try:
+                if args.no_extras:  # (a counter / trace pass must not find batch-form k_tick launches behind the timing pass)
+                    raise RuntimeError("skipped under --no-extras")
+                # (the level's own geometry -- ten steps of 64 pixels per wave, one image row, for a 640x480 level 0 since the end of round 5
+                # -- and, beside it, 8 steps)
+                ms_i, ab_i, nl_i = trk.bench_residual_pass(ref, curs[0], 0, cur_pose(0), 36, 0, reps=20)
+                ms_8, ab_8, nl_8 = trk.bench_residual_pass(ref, curs[0], 0, cur_pose(0), 36, 2, reps=20)
+                line["roofline_isolated_kernel"] = {
+                    "what": "the residual pass alone: level 0, 36 pairs in one launch (one launch's worth of resident pairs), the wave "
+                            "segments match() gives this level (segment_geometry = DVO_AMD_GEOMETRY_THROUGHPUT)",
+                    "achieved": ab_i / ms_i / 1e6, "unit": "GB/s", "frac": ab_i / ms_i / 1e6 / HBM_PEAK_GBS,
+                    "launch_us": ms_i * 1e3 / nl_i, "alg_bytes_per_launch": ab_i / nl_i,
+                    "with_8_steps_per_wave": {"frac": ab_8 / ms_8 / 1e6 / HBM_PEAK_GBS, "launch_us": ms_8 * 1e3 / nl_8}}
+                # the timed region against what the kernel body reaches on its best case in this very run (the level-0 pass alone on
+                # the GPU sits on the kernel's practical issue ceiling): how much of that the whole job keeps
+                line["roofline"]["concurrent"]["fraction_of_the_isolated_kernel"] = (
+                    line["roofline"]["concurrent"]["frac"] / line["roofline_isolated_kernel"]["frac"])
+            except Exception as exc:  # pragma: no cover
+                line["roofline_isolated_kernel"] = {"error": str(exc)}
+            if tile_shard is not None:
+                line["tile_shard"] = tile_shard
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline(args, ref_frame, cur_frames[:8], K, levels, first_level)
+            if world == 1 and not args.no_extras:
+                def cache_resident():
+                    # round 1's workload for comparison: 8 distinct frames against ONE keyframe (9 pyramids, 180 MB: inside the
+                    # Infinity Cache, each distinct pair ~4x in every launch, identical reads that L2 dedups)
+                    r_l, c_l = [ref] * B, [curs[i % 8] for i in range(B)]
+                    run_steps(1, [], r_l, c_l)
                     t0 = time.perf_counter()
-                    p = capi.RgbdImagePyramid.from_raw(g, z, K, levels, device=device)
-                    t_ingest[0] += time.perf_counter() - t0
-                    return p
-                s_refs = [raw_pyr(ref_frame, 5000)] + [raw_pyr(ref_frames_extra[i - 1], 5000 + i) for i in range(1, n_refs)]
-                s_curs = [raw_pyr(f, 6000 + i) for i, f in enumerate(cur_frames)]
-                t_build = t_ingest[0]
-                r_l, c_l = [s_refs[r] for r, _ in idx], [s_curs[c] for _, c in idx]
-                run_steps(1, [], r_l, c_l)
-                n = max(2, args.steps // 2)
-                tally = []
-                t0 = time.perf_counter()
-                run_steps(n, tally, r_l, c_l)
-                dt = time.perf_counter() - t0
-                if sum(c[2] for c in tally):
-                    raise RuntimeError("a pair of the sensor-noise workload came back NaN")
-                return {"value": B * n / dt, "unit": "frame-pairs/s", "steps": n,
-                        "iterations_per_pair": sum(c[3] for c in tally) / (B * n),
-                        "residual_passes_per_pair": sum(c[1] for c in tally) / (B * n),
-                        "useful_algorithmic_mb_per_pair": sum(c[0] - c[4] for c in tally) / (B * n) / 1e6,
-                        "concurrent_frac_of_hbm_peak": sum(c[0] - c[4] for c in tally) / dt / 1e9 / HBM_PEAK_GBS,
-                        "frames_ingested_from_raw_ms_each": t_build * 1e3 / (len(s_refs) + len(s_curs)),
-                        "what": "the timed region's pair list on sensor-realistic input: the same views as 8-bit grey + uint16 "
-                                "depth at 1/5000 m with hashed Gaussian depth noise sigma_z(z) = 0.0012 + 0.0019 (z - 0.4)^2 and "
-                                "1.5 grey levels of intensity noise, ingested on the device; same trackers, same residency"}
-            def host_rcpps():
-                # the opt-in reciprocal mode that reproduces the host's _mm_rcp_ps bit for bit (dense_tracking_impl.cpp:192,700)
-                # from a table: the timed region's workload once more with it switched on, and what it costs
-                for t_ in trackers:
-                    t_.set_reciprocal_mode("host_sse")
-                try:
-                    run_steps(1, [])
+                    n = max(2, args.steps // 2)
+                    run_steps(n, [], r_l, c_l)
+                    dt = time.perf_counter() - t0
+                    return {"value": B * n / dt, "unit": "frame-pairs/s", "steps": n,
+                            "what": "the same batch size with 8 distinct frames against 1 keyframe (9 pyramids inside the "
+                                    "Infinity Cache, pairs repeated 144x per step): round 1's default workload"}
+                def sensor_noise():
+                    # The regime the reference actually runs in (benchmark_slam.cpp:56-80): the SAME views and the same pair list as
+                    # the timed region, delivered as a sensor delivers them -- 8-bit grey, uint16 depth at 1/5000 m, depth noise of
+                    # the sigma the reference models itself (dense_tracking_impl.cpp:122-128) -- and ingested on the device
+                    # (dvo_amd_pyramid_create_raw).  Not the headline: BASELINE.json's metric is quoted on the noise-free pair.
+                    t_ingest = [0.0]
+
+                    def raw_pyr(frame, fid):
+                        g, z = synth.sensor_from_analytic(frame[0], frame[1], frame_id=fid)
+                        t0 = time.perf_counter()
+                        p = capi.RgbdImagePyramid.from_raw(g, z, K, levels, device=device)
+                        t_ingest[0] += time.perf_counter() - t0
+                        return p
+                    s_refs = [raw_pyr(ref_frame, 5000)] + [raw_pyr(ref_frames_extra[i - 1], 5000 + i) for i in range(1, n_refs)]
+                    s_curs = [raw_pyr(f, 6000 + i) for i, f in enumerate(cur_frames)]
+                    t_build = t_ingest[0]
+                    r_l, c_l = [s_refs[r] for r, _ in idx], [s_curs[c] for _, c in idx]
+                    run_steps(1, [], r_l, c_l)
                     n = max(2, args.steps // 2)
                     tally = []
                     t0 = time.perf_counter()
-                    run_steps(n, tally)
+                    run_steps(n, tally, r_l, c_l)
                     dt = time.perf_counter() - t0
-                    mb_pair = sum(c[0] - c[4] for c in tally) / (B * n) / 1e6
-                    conc = sum(c[0] - c[4] for c in tally) / dt / 1e9 / HBM_PEAK_GBS
+                    if sum(c[2] for c in tally):
+                        raise RuntimeError("a pair of the sensor-noise workload came back NaN")
                     return {"value": B * n / dt, "unit": "frame-pairs/s", "steps": n,
-                            "relative_to_the_default_mode": (B * n / dt) / value,
                             "iterations_per_pair": sum(c[3] for c in tally) / (B * n),
-                            "useful_algorithmic_mb_per_pair": mb_pair,
-                            "concurrent_frac_of_hbm_peak": conc,
-                            # the same work per second?  rcpps arithmetic converges differently (more iterations, more of them on
-                            # the fine levels): pairs/s compares two different amounts of work, bytes/s does not
-                            "relative_to_the_default_mode_at_equal_work": conc / (useful / elapsed_local / 1e9 / HBM_PEAK_GBS),
-                            "form": trackers[0].reciprocal_form()[0],
-                            "table_mantissa_bits": trackers[0].reciprocal_mode()[1],
-                            "what": "dvo_amd_set_reciprocal_mode(DVO_AMD_RCP_HOST_SSE): 1 / z of the projection and the reciprocal of "
-                                    "the t-distribution weights are this host's _mm_rcp_ps (the device's own reciprocal plus 4-bit "
-                                    "corrections in LDS, or a device-resident table: `form`); every weight of a pass is computeWeightsSse's, "
-                                    "its exact-division tail included (k_q7_tail: one more small dispatch per tick)"}
-                finally:
+                            "residual_passes_per_pair": sum(c[1] for c in tally) / (B * n),
+                            "useful_algorithmic_mb_per_pair": sum(c[0] - c[4] for c in tally) / (B * n) / 1e6,
+                            "concurrent_frac_of_hbm_peak": sum(c[0] - c[4] for c in tally) / dt / 1e9 / HBM_PEAK_GBS,
+                            "frames_ingested_from_raw_ms_each": t_build * 1e3 / (len(s_refs) + len(s_curs)),
+                            "what": "the timed region's pair list on sensor-realistic input: the same views as 8-bit grey + uint16 "
+                                    "depth at 1/5000 m with hashed Gaussian depth noise sigma_z(z) = 0.0012 + 0.0019 (z - 0.4)^2 and "
+                                    "1.5 grey levels of intensity noise, ingested on the device; same trackers, same residency"}
+                def host_rcpps():
+                    # the opt-in reciprocal mode that reproduces the host's _mm_rcp_ps bit for bit (dense_tracking_impl.cpp:192,700)
+                    # from a table: the timed region's workload once more with it switched on, and what it costs
                     for t_ in trackers:
-                        t_.set_reciprocal_mode("exact")
-            for name, fn in (("sensor_noise_workload", sensor_noise),
-                             ("host_rcpps_mode", host_rcpps),
-                             ("cache_resident_workload", cache_resident),
-                             ("no_stats_variant", lambda: stats_variant(run_steps, B, args, with_stats)),
-                             ("stream_copy", lambda: stream_copy(device)),
-                             ("ingest", lambda: ingest_timing(capi, synth, cur_frames, K, levels, device)),
-                             ("loop_closure_validator", lambda: validator_timing(capi, synth, W, H, device)),
-                             ("dual_match_front_end", lambda: dual_match_timing(capi, ref, curs, levels, first_level, device)),
-                             ("cpu_baseline_many_threads", lambda: None if args.no_cpu_baseline else
-                              cpu_baseline_threads(args, ref_frame, cur_frames[:8], K, levels, first_level))):
-                try:
-                    line[name] = fn()
-                except Exception as exc:  # pragma: no cover - side measurements never fail the bench line
-                    line[name] = {"error": repr(exc)}
+                        t_.set_reciprocal_mode("host_sse")
+                    try:
+                        run_steps(1, [])
+                        n = max(2, args.steps // 2)
+                        tally = []
+                        t0 = time.perf_counter()
+                        run_steps(n, tally)
+                        dt = time.perf_counter() - t0
+                        mb_pair = sum(c[0] - c[4] for c in tally) / (B * n) / 1e6
+                        conc = sum(c[0] - c[4] for c in tally) / dt / 1e9 / HBM_PEAK_GBS
+                        return {"value": B * n / dt, "unit": "frame-pairs/s", "steps": n,
+                                "relative_to_the_default_mode": (B * n / dt) / value,
+                                "iterations_per_pair": sum(c[3] for c in tally) / (B * n),
+                                "useful_algorithmic_mb_per_pair": mb_pair,
+                                "concurrent_frac_of_hbm_peak": conc,
+                                # the same work per second?  rcpps arithmetic converges differently (more iterations, more of them on
+                                # the fine levels): pairs/s compares two different amounts of work, bytes/s does not
+                                "relative_to_the_default_mode_at_equal_work": conc / (useful / elapsed_local / 1e9 / HBM_PEAK_GBS),
+                                "form": trackers[0].reciprocal_form()[0],
+                                "table_mantissa_bits": trackers[0].reciprocal_mode()[1],
+                                "what": "dvo_amd_set_reciprocal_mode(DVO_AMD_RCP_HOST_SSE): 1 / z of the projection and the reciprocal of "
+                                        "the t-distribution weights are this host's _mm_rcp_ps (the device's own reciprocal plus 4-bit "
+                                        "corrections in LDS, or a device-resident table: `form`); every weight of a pass is computeWeightsSse's, "
+                                        "its exact-division tail included (k_q7_tail: one more small dispatch per tick)"}
+                    finally:
+                        for t_ in trackers:
+                            t_.set_reciprocal_mode("exact")
+                for name, fn in (("sensor_noise_workload", sensor_noise),
+                                 ("host_rcpps_mode", host_rcpps),
+                                 ("cache_resident_workload", cache_resident),
+                                 ("no_stats_variant", lambda: stats_variant(run_steps, B, args, with_stats)),
+                                 ("stream_copy", lambda: stream_copy(device)),
+                                 ("ingest", lambda: ingest_timing(capi, synth, cur_frames, K, levels, device)),
+                                 ("loop_closure_validator", lambda: validator_timing(capi, synth, W, H, device)),
+                                 ("dual_match_front_end", lambda: dual_match_timing(capi, ref, curs, levels, first_level, device)),
+                                 ("cpu_baseline_many_threads", lambda: None if args.no_cpu_baseline else
+                                  cpu_baseline_threads(args, ref_frame, cur_frames[:8], K, levels, first_level))):
+                    try:
+                        line[name] = fn()
+                    except Exception as exc:  # pragma: no cover - side measurements never fail the bench line
+                        line[name] = {"error": repr(exc)}
         print(json.dumps(line), file=OUT, flush=True)
     if side_hung:  # a thread of this process is stuck inside a collective: no orderly teardown is possible
         sys.stdout.flush()

@@ -37,7 +37,7 @@ def main():
         bench = json.loads(open(sys.argv[4]).read().strip().splitlines()[-1])
         bench_w = json.loads(open(sys.argv[5]).read().strip().splitlines()[-1]) if len(sys.argv) > 5 else None
         out = pmc.traffic_summary(sys.argv[2], sys.argv[3], bench, bench_line_write=bench_w,
-                                  command="python bench.py --steps 2 --warmup 1 --prime 1 --no-extras --no-cpu-baseline --no-live-counters "
+                                  command="python bench.py --full --steps 2 --warmup 1 --prime 1 --no-extras --no-cpu-baseline --no-live-counters "
                                           "under rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (one pass each)")
         print(json.dumps(out, indent=1))
 

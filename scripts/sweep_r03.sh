@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 mkdir -p "$R/$out"
 for c in "$@"; do
   name=${c%%|*}; rest=${c#*|}; envs=${rest%%|*}; args=${rest#*|}
-  env $envs python3 "$R/bench.py" --steps 12 --warmup 3 --no-extras --no-cpu-baseline $args > "$R/$out/$name.json" 2> "$R/$out/$name.err" || { echo "$name failed"; tail -3 "$R/$out/$name.err"; exit 1; }
+  env $envs python3 "$R/bench.py" --full --steps 12 --warmup 3 --no-extras --no-cpu-baseline $args > "$R/$out/$name.json" 2> "$R/$out/$name.err" || { echo "$name failed"; tail -3 "$R/$out/$name.err"; exit 1; }
   python3 - "$R/$out/$name.json" "$name" <<'PY'
 import json,sys
 d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1])
