@@ -246,6 +246,22 @@ __device__ __forceinline__ Gathered gather_pixel(const LevelPairDesc &d, int bas
   return g;
 }
 
+// Cache policy of k_tick's streams, chosen here and nowhere else:
+//  - the current pyramid's gather planes (gather_pixel above) and the reference pyramid's compacted arrays (the six prefetched
+//    dword loads of a step) are shared by every resident pair of that frame: default policy, they are what should stay cached;
+//  - the residual spill, its one re-read by the likelihood pass of a later tick and the per-block records are private to a pair
+//    and touched exactly once per direction: non-temporal (the `nt` bit of global_store / global_load), so that a sixth of the
+//    tick's traffic does not age the shared lines out of L2 and the Infinity Cache.  An nt store is an ordinary write-back store
+//    as far as visibility goes (the consumer is a later launch), an nt load bypasses only L1, where a streamed line has no reuse.
+template <class T>
+__device__ __forceinline__ void st_once(DVO_GLOBAL T *p, const T v) {
+  __builtin_nontemporal_store(v, p);
+}
+template <class T>
+__device__ __forceinline__ T ld_once(const DVO_GLOBAL T *p) {
+  return __builtin_nontemporal_load(p);
+}
+
 // ZERO_E: also zero the gradient terms of an invalid pixel (the register-accumulator form needs that; the staged forms scale
 // them by a zero weight with a multiply whose 0 * anything is 0, so the four selects are saved)
 template <bool ZERO_E>
@@ -497,7 +513,7 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
         DVO_KEEP(sv.x);
         DVO_KEEP(sv.y);
       } else {
-        *reinterpret_cast<DVO_GLOBAL v2f *>(p_res + 8u * cur_idx) = sv;
+        st_once(reinterpret_cast<DVO_GLOBAL v2f *>(p_res + 8u * cur_idx), sv);
       }
     }
 
@@ -748,12 +764,12 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
 
   DVO_GLOBAL float *rec = (DVO_GLOBAL float *)d.records + (size_t)lb * kRecStride;
   if ((DVO_ABLATE & 128) && tid < kNumAcc) {
-    rec[kRecAcc + tid] = stage[tid];
+    st_once(rec + kRecAcc + tid, stage[tid]);
   } else if ((DVO_ABLATE & 256) && tid == 128) {
-    rec[kRecCount] = sm[0][kRecCount];
+    st_once(rec + kRecCount, sm[0][kRecCount]);
   } else if (tid < kNumAcc) {
     if (ACC == 0) {
-      rec[kRecAcc + tid] = (sm[0][kRecAcc + tid] + sm[1][kRecAcc + tid]) + (sm[2][kRecAcc + tid] + sm[3][kRecAcc + tid]);
+      st_once(rec + kRecAcc + tid, (sm[0][kRecAcc + tid] + sm[1][kRecAcc + tid]) + (sm[2][kRecAcc + tid] + sm[3][kRecAcc + tid]));
     } else {
       constexpr int kW = kBufs * kWave * 16;  // floats between the staging areas of two waves
       float v;
@@ -766,7 +782,7 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
         v = (stage[e0] + stage[kW + e0]) + (stage[2 * kW + e0] + stage[3 * kW + e0]);
         if (e1 >= 0) v += (stage[e1] + stage[kW + e1]) + (stage[2 * kW + e1] + stage[3 * kW + e1]);
       }
-      rec[kRecAcc + tid] = v;
+      st_once(rec + kRecAcc + tid, v);
     }
   } else if (tid == 128) {
     // ordered combine of the four wave segments (see combine rule in k_finalize).  Everything is read first and the fold is
@@ -785,7 +801,7 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
     float s0[3] = {0.0f, 0.0f, 0.0f}, s1[3] = {0.0f, 0.0f, 0.0f};
 #pragma unroll
     for (int wv = 0; wv < kWavesPerBlock; ++wv) {
-      rec[kRecWaveCnt + wv] = u2f(CB[wv]);
+      st_once(rec + kRecWaveCnt + wv, u2f(CB[wv]));
       const bool ne = CB[wv] != 0;           // an empty segment is skipped
       const bool first = c == 0;             // nothing before it: its first weight is the combined segment's
       const bool flip = (c & 1u) != 0;       // b starts on the opposite parity of a
@@ -806,12 +822,12 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
       l0 = ne ? L0[wv] : l0, l1 = ne ? L1[wv] : l1;
       c += CB[wv];
     }
-    rec[kRecCount] = u2f(c);
-    rec[kRecFirstW] = fw;
-    rec[kRecLastR] = l0;
-    rec[kRecLastR + 1] = l1;
-    for (int i = 0; i < 3; ++i) rec[kRecS0 + i] = s0[i], rec[kRecS1 + i] = s1[i];
-    rec[14] = 0.0f, rec[15] = 0.0f;
+    st_once(rec + kRecCount, u2f(c));
+    st_once(rec + kRecFirstW, fw);
+    st_once(rec + kRecLastR, l0);
+    st_once(rec + kRecLastR + 1, l1);
+    for (int i = 0; i < 3; ++i) st_once(rec + kRecS0 + i, s0[i]), st_once(rec + kRecS1 + i, s1[i]);
+    st_once(rec + 14, 0.0f), st_once(rec + 15, 0.0f);
 #if defined(DVO_TRACE_BLOCKS) && defined(DVO_TRACE_TAIL)
     __hip_atomic_store(&trace_tail, trace_clock(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 #endif
@@ -856,7 +872,7 @@ __device__ void loglik_pass(const TickItem &it, const LevelPairDesc &d, const in
   auto load_chunk = [&](v2f(&dst)[kLlChunk], const int first) __attribute__((always_inline)) {
 #pragma unroll
     for (int k = 0; k < kLlChunk; ++k)
-      if (first + k < steps) dst[k] = src[(first + k) * kWave];
+      if (first + k < steps) dst[k] = ld_once(src + (first + k) * kWave);
   };
   load_chunk(cur, 0);
   // valid pixels of this band that precede the segment (written by k_finalize of the residual pass that filled the buffer)
