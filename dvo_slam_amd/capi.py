@@ -39,7 +39,7 @@ EXPORTS = [
     "dvo_amd_debug_level_geometry", "dvo_amd_point_cloud", "dvo_amd_map_cloud", "dvo_amd_voxel_downsample", "dvo_amd_write_pcd",
     "dvo_amd_debug_map_timing", "dvo_amd_default_graph_options", "dvo_amd_optimize_graph", "dvo_amd_debug_graph_timing",
     "dvo_amd_debug_graph_system", "dvo_amd_debug_graph_system_sparse", "dvo_amd_debug_graph_symbolic",
-    "dvo_amd_debug_graph_sparse_timing",
+    "dvo_amd_debug_graph_sparse_timing", "dvo_amd_optimize_graphs_batch", "dvo_amd_debug_graph_batch_records",
 ]
 
 

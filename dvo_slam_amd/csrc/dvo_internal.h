@@ -6,6 +6,7 @@
 //                     micro-benchmarks and the diagnostics of include/dvo_amd_debug.h
 //   dvo_map.cpp       the keyframe map's point cloud: organized clouds at a pose, the deterministic voxel aggregate
 //   dvo_graph.cpp     the pose-graph optimizer: edge linearisation, dense fp64 Cholesky, Levenberg-Marquardt and dogleg
+//   dvo_graph_batch.cpp  many small pose graphs in one launch: one workgroup per graph, the whole optimization on the device
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -114,6 +115,7 @@ namespace dvo_amd {
 namespace host {
 struct MapWorkspace;  // the buffers of the map entries (dvo_map.cpp)
 struct GraphWorkspace;  // the buffers of dvo_amd_optimize_graph (dvo_graph.cpp)
+struct GraphBatchWorkspace;  // the buffers of dvo_amd_optimize_graphs_batch (dvo_graph_batch.cpp)
 }  // namespace host
 }  // namespace dvo_amd
 
@@ -228,6 +230,7 @@ struct dvo_amd_context {
   size_t events_used = 0;
   host::MapWorkspace *map_ws = nullptr;  // dvo_amd_point_cloud / _map_cloud / _voxel_downsample: grown to the largest call
   host::GraphWorkspace *graph_ws = nullptr;  // dvo_amd_optimize_graph: grown to the largest call
+  host::GraphBatchWorkspace *graph_batch_ws = nullptr;  // dvo_amd_optimize_graphs_batch: grown to the largest call
 };
 
 namespace dvo_amd {
@@ -388,6 +391,10 @@ int runner_reported_status(Runner &R, unsigned long long ticket);
 int queue_must_be_idle(dvo_amd_context *ctx, const char *what);
 void map_workspace_release(dvo_amd_context *ctx);  // dvo_map.cpp
 void graph_workspace_release(dvo_amd_context *ctx);  // dvo_graph.cpp
+void graph_batch_workspace_release(dvo_amd_context *ctx);  // dvo_graph_batch.cpp
+// the argument checks of the pose-graph entries (dvo_graph.cpp); `entry` prefixes dvo_amd_last_error()
+int graph_check_arguments(const char *entry, int n_vertices, const double *poses, int n_edges, const dvo_amd_graph_edge *edges,
+                          const dvo_amd_graph_options *opt);
 int runner_step(dvo_amd_context *ctx, size_t g);
 int runner_drain(dvo_amd_context *ctx);
 int runner_configure(dvo_amd_context *ctx, int in_flight, int n_pad);

@@ -17,6 +17,7 @@ SOLVERS = {"dense": DENSE, "sparse": SPARSE}
 TERMINATION = {0: "iterations exhausted", 1: "terminate", 2: "fail"}
 MAX_FREE_VERTICES = 1024
 MAX_FREE_VERTICES_SPARSE = 65536
+BATCH_MAX_FREE_VERTICES = 32
 
 
 class CGraphEdge(C.Structure):
@@ -37,6 +38,12 @@ class CGraphStats(C.Structure):
     _fields_ = [("iterations", C.c_int), ("termination", C.c_int), ("n_free", C.c_int), ("cholesky_failures", C.c_int),
                 ("initial_objective", C.c_double), ("final_objective", C.c_double), ("lambda_", C.c_double),
                 ("delta", C.c_double)]
+
+
+class CGraphBatchItem(C.Structure):
+    _fields_ = [("n_vertices", C.c_int), ("poses", C.POINTER(C.c_double)), ("fixed", C.POINTER(C.c_int)),
+                ("n_edges", C.c_int), ("edges", C.POINTER(CGraphEdge)), ("edge_chi2", C.POINTER(C.c_double)),
+                ("edge_weight", C.POINTER(C.c_double)), ("stats", CGraphStats)]
 
 
 _bound = False
@@ -61,6 +68,8 @@ def _lib():
         L.dvo_amd_debug_graph_symbolic.argtypes = [C.c_int, ip, C.c_int, C.POINTER(CGraphEdge), C.c_int, ip, ip, ip, ip, ip,
                                                    ip, ip, ip, ip, ip, ip, ip, dp, dp]
         L.dvo_amd_debug_graph_sparse_timing.argtypes = [C.c_void_p, dp, dp, dp, dp, ip, ip, ip, dp, dp]
+        L.dvo_amd_optimize_graphs_batch.argtypes = [C.c_void_p, C.c_int, C.POINTER(CGraphBatchItem), C.POINTER(CGraphOptions)]
+        L.dvo_amd_debug_graph_batch_records.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(CGraphIteration), ip]
         _bound = True
     return L
 
@@ -249,6 +258,73 @@ class PoseGraph:
         for k in cand:
             self.edges[k] = None
         return cand
+
+
+def _records(its, n):
+    return {"objective": np.array([its[i].objective for i in range(n)]),
+            "step_norm": np.array([its[i].step_norm for i in range(n)]),
+            "lambda": np.array([its[i].lambda_ for i in range(n)]),
+            "delta": np.array([its[i].delta for i in range(n)]),
+            "trials": np.array([its[i].trials for i in range(n)], dtype=np.int64),
+            "accepted": np.array([its[i].accepted for i in range(n)], dtype=np.int64)}
+
+
+def optimize_batch(tracker: "capi.DenseTracker", graphs, algorithm: str = "levenberg", iterations: int | None = None,
+                   robust_delta: float = 5.0, max_trials: int | None = None, initial_lambda: float | None = None,
+                   initial_delta: float | None = None, update: bool = True) -> list:
+    """Optimize many small, independent PoseGraphs in one call (dvo_amd_optimize_graphs_batch): one workgroup per graph, one
+    kernel launch for the whole batch, at most BATCH_MAX_FREE_VERTICES free vertices per graph.  One set of options for all of
+    them, with the defaults of PoseGraph.optimize for the algorithm.  Returns one Result per graph, in order (their
+    `iterations` is empty: the entry returns no per-iteration records); update=True writes the poses back into the graphs.
+    Raises what PoseGraph.optimize raises when the call fails (capi.DvoAmdError with the status)."""
+    L = _lib()
+    o = default_options(algorithm)
+    if iterations is not None:
+        o.max_iterations = int(iterations)
+    if max_trials is not None:
+        o.max_trials = int(max_trials)
+    if initial_lambda is not None:
+        o.initial_lambda = float(initial_lambda)
+    if initial_delta is not None:
+        o.initial_delta = float(initial_delta)
+    o.robust_delta = float(robust_delta)
+    graphs = list(graphs)
+    items = (CGraphBatchItem * max(len(graphs), 1))()
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    keep = []
+    for i, pg in enumerate(graphs):
+        live, nv, ne, P, fixed, ce = pg._pack()
+        chi2, weight = np.zeros(max(ne, 1)), np.zeros(max(ne, 1))
+        keep.append((live, nv, ne, P, fixed, ce, chi2, weight))
+        items[i].n_vertices, items[i].n_edges = nv, ne
+        items[i].poses, items[i].fixed, items[i].edges = P.ctypes.data_as(dp), fixed.ctypes.data_as(ip), ce
+        items[i].edge_chi2, items[i].edge_weight = chi2.ctypes.data_as(dp), weight.ctypes.data_as(dp)
+    capi._check(L.dvo_amd_optimize_graphs_batch(tracker._h, len(graphs), items, C.byref(o)), "dvo_amd_optimize_graphs_batch")
+    out = []
+    for i, pg in enumerate(graphs):
+        live, nv, ne, P, fixed, ce, chi2, weight = keep[i]
+        poses = [P[v].T.copy() for v in range(nv)]
+        w_full, c_full = np.full(len(pg.edges), np.nan), np.full(len(pg.edges), np.nan)
+        w_full[live] = weight[:ne]
+        c_full[live] = chi2[:ne]
+        st = CGraphStats.from_buffer_copy(items[i].stats)
+        res = Result(poses, c_full, w_full, _records(None, 0), st)
+        res.robust_delta = o.robust_delta
+        if update:
+            pg.poses = [T.copy() for T in poses]
+        pg.last = res
+        out.append(res)
+    return out
+
+
+def debug_batch_records(tracker: "capi.DenseTracker", graph: int, capacity: int = 256) -> dict:
+    """(diagnostic) the per-iteration records of graph `graph` of the tracker's last optimize_batch(), in the layout of
+    Result.iterations (dvo_amd_debug_graph_batch_records)"""
+    its = (CGraphIteration * max(capacity, 1))()
+    n = C.c_int()
+    capi._check(_lib().dvo_amd_debug_graph_batch_records(tracker._h, int(graph), int(capacity), its, C.byref(n)),
+                "dvo_amd_debug_graph_batch_records")
+    return _records(its, min(n.value, capacity))
 
 
 def debug_timing(tracker: "capi.DenseTracker"):

@@ -634,6 +634,55 @@ int dvo_amd_optimize_graph(dvo_amd_context *ctx, int n_vertices, double *poses, 
                            double *edge_weight, int iteration_capacity, dvo_amd_graph_iteration *iterations,
                            dvo_amd_graph_stats *stats);
 
+/*
+ * Many small, independent pose graphs in one call: the local maps of a sequence (LocalMap::optimize, local_map.cpp:197-213: a
+ * fixed keyframe, one vertex per frame, an odometry and a keyframe edge per frame, Levenberg) or the frames between two fixed
+ * keyframes (KeyframeGraph::optimizeInterKeyframePoses, keyframe_graph.cpp:294-332).  One workgroup optimizes one graph and the
+ * whole optimization of every graph runs in one kernel launch.
+ * Per graph the semantics are those pinned above for dvo_amd_optimize_graph -- increment, edge error, Jacobians, Cauchy kernel,
+ * normal equations, the Levenberg and the dogleg driver with their failure rules, fixed and inactive vertices returned bit for
+ * bit, termination codes, cholesky_failures -- with one set of options for the whole batch.  What differs:
+ *  - opt->solver must be DVO_AMD_GRAPH_SOLVER_DENSE (DVO_AMD_ERR_INVALID_ARGUMENT otherwise).
+ *  - The order of the floating-point sums inside a graph is this entry's own, and fixed.  H and b: contributors in edge order
+ *    (the same bits as the dense path's).  Cholesky: right-looking over the packed lower triangle, one vertex (6 columns) at a
+ *    time -- the 6 x 6 diagonal block column by column, then every row below against it (columns 0 to 5), then every trailing
+ *    entry minus its 6 products in column order.  Substitution: forward by vertex (the block's 6 unknowns in order, then every
+ *    later row minus its 6 products in order), backward its mirror image.  F and the dot products: 256 strided partial sums,
+ *    an xor butterfly (32, 16, 8, 4, 2, 1) over each group of 64 and ((s0 + s1) + s2) + s3 over the four groups.  H v: per
+ *    row 64 strided partial sums and the same butterfly.  Levenberg's (2 rho - 1)^3 is t * t * t.  Results agree with
+ *    dvo_amd_optimize_graph(DVO_AMD_GRAPH_SOLVER_DENSE) on the same graph to rounding, not bit for bit -- the relationship the
+ *    sparse solver has to the dense one.
+ *  - A graph's result (poses, edge_chi2, edge_weight, stats) is a function of that graph and the options alone: bit-identical
+ *    whatever else is in the batch, at whatever index it stands, for any n_graphs, between runs and between contexts on one
+ *    device.  No floating-point atomics; workgroups do not communicate.
+ *  - Per-iteration records are not returned, only stats.
+ *  - Capacity: a graph with more than DVO_AMD_GRAPH_BATCH_MAX_FREE_VERTICES free active vertices makes the whole call return
+ *    DVO_AMD_ERR_CAPACITY with every pose of every item untouched; this is checked on the host, after the argument checks and
+ *    before the device is looked for.  Vertices (fixed ones) and edges per graph are not limited.
+ *  - Argument checks are those of dvo_amd_optimize_graph, in its order: the options first, then item by item in index order.
+ *    A bad item makes the whole call return DVO_AMD_ERR_INVALID_ARGUMENT, dvo_amd_last_error() names the item ("item 3: ..."),
+ *    and nothing is touched.  Then the capacity check, DVO_AMD_ERR_NO_DEVICE without a GPU, DVO_AMD_ERR_INVALID_ARGUMENT for a
+ *    NULL ctx or a context with queued pairs.  n_graphs == 0 is DVO_AMD_OK.  A graph with no free active vertex or no edge
+ *    keeps its poses and reports zero iterations (its objective and edge outputs are still evaluated), as on the single path.
+ *  - What happens inside a graph (a failing dogleg: DVO_AMD_GRAPH_FAIL; Levenberg's terminate) is reported in that item's
+ *    stats and does not touch the other graphs: the call returns DVO_AMD_OK.
+ * Buffers are the context's, grown to the largest call and kept.
+ */
+#define DVO_AMD_GRAPH_BATCH_MAX_FREE_VERTICES 32   /* per graph: 192 unknowns, the packed factor (145 KB) fits one workgroup's LDS */
+
+typedef struct {
+  int n_vertices;
+  double *poses;                     /* n_vertices x 16, column-major, optimized in place */
+  const int *fixed;                  /* may be NULL: all free */
+  int n_edges;
+  const dvo_amd_graph_edge *edges;
+  double *edge_chi2, *edge_weight;   /* n_edges each, may be NULL */
+  dvo_amd_graph_stats stats;         /* out */
+} dvo_amd_graph_batch_item;
+
+int dvo_amd_optimize_graphs_batch(dvo_amd_context *ctx, int n_graphs, dvo_amd_graph_batch_item *items,
+                                  const dvo_amd_graph_options *opt);
+
 /* Host-side helpers (no GPU needed): the SE(3) exponential / logarithm with Sophus' tangent order (upsilon, omega) and the
  * pivoted LDL^T 6x6 solve the driver uses in place of Sophus::SE3d::exp/log and Eigen::LDLT (dense_tracking.cpp:238,259,347).
  * Exported so that bindings do not need Sophus to build a T_init or to compare poses. */

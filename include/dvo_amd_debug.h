@@ -153,6 +153,10 @@ int dvo_amd_debug_map_timing(dvo_amd_context *ctx, double *device_ms, double *co
  * factorization (damped copy + blocked Cholesky), the padded system size, and the factorizations done */
 int dvo_amd_debug_graph_timing(dvo_amd_context *ctx, double *linearise_ms, double *factorize_ms, int *n_padded,
                                int *factorizations);
+/* the per-iteration records of graph `graph` of the last dvo_amd_optimize_graphs_batch on the context (the entry itself returns
+ * only stats): at most `capacity` of them into `records`, *n_recorded = how many the call kept (the first 256 iterations) */
+int dvo_amd_debug_graph_batch_records(dvo_amd_context *ctx, int graph, int capacity, dvo_amd_graph_iteration *records,
+                                      int *n_recorded);
 /* the first linear system of dvo_amd_optimize_graph on these inputs, before any step: H (n x n, row-major, full), b (n) and
  * F; x (n) = the undamped solve H x = b, valid when *failed_pivot < 0 (else the index of the first pivot <= 0).  Any of the
  * outputs may be NULL; H / b / x need 6 * (free active vertices) entries per side, *n_free says how many.  Poses are not moved. */
