@@ -37,7 +37,7 @@ EXPORTS = [
     "dvo_amd_set_reciprocal_mode", "dvo_amd_get_reciprocal_mode", "dvo_amd_debug_rcp", "dvo_amd_debug_block_trace",
     "dvo_amd_debug_ll_overflow", "dvo_amd_debug_marker", "dvo_amd_debug_rcp_form", "dvo_amd_debug_weights", "dvo_amd_debug_hw_queue",
     "dvo_amd_debug_level_geometry", "dvo_amd_point_cloud", "dvo_amd_map_cloud", "dvo_amd_voxel_downsample", "dvo_amd_write_pcd",
-    "dvo_amd_debug_map_timing", "dvo_amd_default_graph_options", "dvo_amd_optimize_graph", "dvo_amd_debug_graph_timing",
+    "dvo_amd_debug_map_timing", "dvo_amd_default_graph_options", "dvo_amd_optimize_graph", "dvo_amd_graph_marginals", "dvo_amd_debug_graph_timing",
     "dvo_amd_debug_graph_system", "dvo_amd_debug_graph_system_sparse", "dvo_amd_debug_graph_symbolic",
     "dvo_amd_debug_graph_sparse_timing", "dvo_amd_optimize_graphs_batch", "dvo_amd_debug_graph_batch_records",
 ]

@@ -557,6 +557,242 @@ __global__ void k_max_diag_blocks(int n, const int *__restrict__ diag_block, con
   if (threadIdx.x == 0) *out = red[0];
 }
 
+// ---- marginal covariances (dvo_amd_graph_marginals): entries of Z = H^-1 by selected inversion -----------------------------
+//   With H = L L^T, Z L = L^-T gives, for a pivot (block) column t and the rows R behind it, Z_Rt = -Z_RR Y and
+//   Z_tt = L_tt^-T L_tt^-1 - Y^T Z_Rt with Y = L_Rt L_tt^-1: column t needs only entries of Z inside the column's own row
+//   structure, so the recurrence runs front by front down the assembly tree (root first).  A front's Z lives in a second arena
+//   with the factor's layout; its trailing part (Z22, the inverse over the update set) is a gather from the parent's finished Z.
+//   Small fronts: one workgroup, one scalar column at a time, Z kept full (both mirror images are the same bits).  Wide fronts
+//   and the dense solver (one front holding everything, so Z is the whole inverse): 64 x 64 tiles, lower triangle only, with
+//   v_mfma_f64_16x16x4_f64; every reader takes entry (max, min), which is what makes Z exactly symmetric.
+constexpr int kSelThreads = 512;
+enum { kLoadPlain = 0, kLoadTrans = 1, kLoadSym = 2 };  // kLoadSym: a diagonal tile of which the lower triangle is stored
+
+struct SelInfo {
+  long long parent_a_off;  // the parent's front (-1: a root)
+  int parent_ld, up_off;   // up[up_off + j]: the parent's scalar index of update block j
+};
+
+struct MargReq {
+  long long base;  // the front's offset in Z
+  int ld, r0, c0, out;
+};
+
+struct ColReq {
+  int row, out, transposed;  // the other vertex's first unknown, the output block, 1: the solved vertex is the block's row
+};
+
+__device__ inline double tile_at(const double *X, int ld, int mode, int r, int k) {
+  if (mode == kLoadTrans || (mode == kLoadSym && k > r)) return X[(size_t)k * ld + r];
+  return X[(size_t)r * ld + k];
+}
+
+// acc[r][c] += sum over k of X(r, k) Y(c, k) for two 64 x 64 tiles, K in two halves through LDS, k ascending; the waves'
+// quarters and the MFMA operand layout are k_syrk's
+__device__ inline void tile_mac(double4_t (&acc)[2][2], const double *X, int ldx, int xm, const double *Y, int ldy, int ym,
+                                double *Xs, double *Ys) {
+  constexpr int kHalf = kTile / 2, kS = kHalf + 1;
+  const int tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
+  const int r0 = 32 * (wave >> 1), c0 = 32 * (wave & 1);
+  for (int h = 0; h < 2; ++h) {
+    __syncthreads();
+    for (int e = tid; e < kTile * kHalf; e += kBlock) {
+      int r = e / kHalf, c = e % kHalf;
+      if (xm == kLoadTrans) c = e / kTile, r = e % kTile;  // along the stored rows
+      Xs[r * kS + c] = tile_at(X, ldx, xm, r, h * kHalf + c);
+      r = e / kHalf, c = e % kHalf;
+      if (ym == kLoadTrans) c = e / kTile, r = e % kTile;
+      Ys[r * kS + c] = tile_at(Y, ldy, ym, r, h * kHalf + c);
+    }
+    __syncthreads();
+    for (int kk = 0; kk < kHalf; kk += 4) {
+      const int kl = kk + (lane >> 4);
+      for (int a = 0; a < 2; ++a) {
+        const double av = Xs[(r0 + 16 * a + (lane & 15)) * kS + kl];
+        for (int b = 0; b < 2; ++b) {
+          const double bv = Ys[(c0 + 16 * b + (lane & 15)) * kS + kl];
+          acc[a][b] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc[a][b], 0, 0, 0);
+        }
+      }
+    }
+  }
+}
+
+// f(row, column, value) for the entries of the tile this lane holds (k_syrk's layout of the accumulators)
+template <class F>
+__device__ inline void tile_each(const double4_t (&acc)[2][2], F f) {
+  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b)
+      for (int g = 0; g < 4; ++g)
+        f(32 * (wave >> 1) + 16 * a + (lane >> 4) + 4 * g, 32 * (wave & 1) + 16 * b + (lane & 15), acc[a][b][g]);
+}
+
+// W = L_tt^-1 (lower triangular, the upper triangle written as zeros): one thread per column, forward substitution in LDS.
+// Column c of W is thread c's own: it keeps W[r][c], r > c, in the tile's unused upper triangle at [c][r].
+__global__ void __launch_bounds__(kBlock) k_tile_inverse(const double *__restrict__ L, int ld, int t, double *__restrict__ Wt,
+                                                         const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  __shared__ double A[kTile * kLds];
+  const int tid = threadIdx.x, base = t * kTile;
+  for (int e = tid; e < kTile * kTile; e += kBlock) {
+    const int r = e / kTile, c = e % kTile;
+    if (c <= r) A[r * kLds + c] = L[(size_t)(base + r) * ld + base + c];
+  }
+  __syncthreads();
+  if (tid < kTile) {
+    const int c = tid;
+    const double wcc = 1.0 / A[c * kLds + c];
+    for (int r = c + 1; r < kTile; ++r) {
+      double s = A[r * kLds + c] * wcc;
+      for (int k = c + 1; k < r; ++k) s += A[r * kLds + k] * A[c * kLds + k];
+      A[c * kLds + r] = -(s / A[r * kLds + r]);
+    }
+  }
+  __syncthreads();
+  for (int e = tid; e < kTile * kTile; e += kBlock) {
+    const int r = e / kTile, c = e % kTile;
+    Wt[e] = r > c ? A[c * kLds + r] : r == c ? 1.0 / A[r * kLds + r] : 0.0;
+  }
+}
+
+// Y_i = L_it W for the tile rows i behind t (Y: consecutive 64 x 64 tiles, row-major)
+__global__ void __launch_bounds__(kBlock) k_tile_y(const double *__restrict__ L, int ld, int t, const double *__restrict__ Wt,
+                                                   double *__restrict__ Y, const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  __shared__ double Xs[kTile * (kTile / 2 + 1)];
+  __shared__ double Ys[kTile * (kTile / 2 + 1)];
+  const int i = t + 1 + blockIdx.x;
+  double4_t acc[2][2];
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  tile_mac(acc, L + (size_t)i * kTile * ld + (size_t)t * kTile, ld, kLoadPlain, Wt, kTile, kLoadTrans, Xs, Ys);
+  double *y = Y + (size_t)blockIdx.x * kTile * kTile;
+  tile_each(acc, [&](int r, int c, double v) { y[r * kTile + c] = v; });
+}
+
+// Z_it = -sum over the tile rows k behind t (ascending) of Z_ik Y_k, Z_ik read from the stored lower triangle
+__global__ void __launch_bounds__(kBlock) k_tile_zcol(double *Z, int ld, int t, int T, const double *__restrict__ Y,
+                                                      const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  __shared__ double Xs[kTile * (kTile / 2 + 1)];
+  __shared__ double Ys[kTile * (kTile / 2 + 1)];
+  const int i = t + 1 + blockIdx.x;
+  double4_t acc[2][2];
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) acc[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  for (int k = t + 1; k < T; ++k) {
+    const double *z = k <= i ? Z + (size_t)i * kTile * ld + (size_t)k * kTile : Z + (size_t)k * kTile * ld + (size_t)i * kTile;
+    tile_mac(acc, z, ld, k < i ? kLoadPlain : k == i ? kLoadSym : kLoadTrans, Y + (size_t)(k - t - 1) * kTile * kTile, kTile,
+             kLoadTrans, Xs, Ys);
+  }
+  double *out = Z + (size_t)i * kTile * ld + (size_t)t * kTile;
+  tile_each(acc, [&](int r, int c, double v) { out[(size_t)r * ld + c] = -v; });
+}
+
+// Z_tt = W^T W - sum over k (ascending) of Z_kt^T Y_k; the lower triangle is stored
+__global__ void __launch_bounds__(kBlock) k_tile_zdiag(double *Z, int ld, int t, int T, const double *__restrict__ Wt,
+                                                       const double *__restrict__ Y, const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  __shared__ double Xs[kTile * (kTile / 2 + 1)];
+  __shared__ double Ys[kTile * (kTile / 2 + 1)];
+  double4_t ww[2][2], zy[2][2];
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) ww[a][b] = zy[a][b] = (double4_t){0.0, 0.0, 0.0, 0.0};
+  tile_mac(ww, Wt, kTile, kLoadTrans, Wt, kTile, kLoadTrans, Xs, Ys);
+  for (int k = t + 1; k < T; ++k)
+    tile_mac(zy, Z + (size_t)k * kTile * ld + (size_t)t * kTile, ld, kLoadTrans, Y + (size_t)(k - t - 1) * kTile * kTile, kTile,
+             kLoadTrans, Xs, Ys);
+  double *out = Z + (size_t)t * kTile * ld + (size_t)t * kTile;
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) ww[a][b] = ww[a][b] - zy[a][b];
+  tile_each(ww, [&](int r, int c, double v) {
+    if (c <= r) out[(size_t)r * ld + c] = v;
+  });
+}
+
+// the trailing part of each front of the level: Z over its update set, from the parent's Z (padding: zeros)
+__global__ void __launch_bounds__(kBlock) k_front_gather_z22(const Front *__restrict__ fronts, const int *__restrict__ ids,
+                                                             const SelInfo *__restrict__ info, const int *__restrict__ up,
+                                                             double *Z, const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  const int id = ids[blockIdx.y];
+  const Front F = fronts[id];
+  const SelInfo I = info[id];
+  const int w = F.ld - F.ppad;
+  const long long total = (long long)w * w;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+    const int r = (int)(e / w), c = (int)(e % w);
+    double v = 0.0;
+    if (r < 6 * F.u && c < 6 * F.u && I.parent_a_off >= 0) {
+      const int pr = up[I.up_off + r / 6] + r % 6, pc = up[I.up_off + c / 6] + c % 6;
+      v = Z[I.parent_a_off + (long long)max(pr, pc) * I.parent_ld + min(pr, pc)];
+    }
+    Z[F.a_off + (long long)(F.ppad + r) * F.ld + F.ppad + c] = v;
+  }
+}
+
+// a small front in one workgroup, pivot columns last to first: z_Rj = -(Z_RR l_Rj) / l_jj (one wave per row, a fixed butterfly),
+// z_jj = (1 / l_jj - l_Rj . z_Rj) / l_jj; both mirror images of the column are written
+__global__ void __launch_bounds__(kSelThreads) k_front_selinv(const Front *__restrict__ fronts, const int *__restrict__ ids,
+                                                              const double *__restrict__ A, double *Z, const int *flag) {
+  if (*(volatile const int *)flag >= 0) return;
+  __shared__ double col[kSmallMaxLd];
+  __shared__ double zc[kSmallMaxLd];
+  const Front F = fronts[ids[blockIdx.x]];
+  const double *a = A + F.a_off;
+  double *z = Z + F.a_off;
+  const int ld = F.ld, np = 6 * F.p, tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
+  for (int j = np - 1; j >= 0; --j) {
+    const double d = a[(long long)j * ld + j];
+    for (int i = j + 1 + tid; i < ld; i += kSelThreads) col[i] = a[(long long)i * ld + j];
+    __syncthreads();
+    for (int i = j + 1 + wave; i < ld; i += kSelThreads / 64) {
+      const double *zr = z + (long long)i * ld;
+      double s = 0.0;
+      for (int k = j + 1 + lane; k < ld; k += 64) s += zr[k] * col[k];
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+      if (lane == 0) zc[i] = -(s / d);
+    }
+    __syncthreads();
+    if (wave == 0) {
+      double s = 0.0;
+      for (int k = j + 1 + lane; k < ld; k += 64) s += zc[k] * col[k];
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+      if (lane == 0) z[(long long)j * ld + j] = (1.0 / d - s) / d;
+    }
+    for (int i = j + 1 + tid; i < ld; i += kSelThreads) {
+      z[(long long)i * ld + j] = zc[i];
+      z[(long long)j * ld + i] = zc[i];
+    }
+    __syncthreads();
+  }
+}
+
+// requested blocks whose two vertices meet in one front (the dense solver: always), column-major, from entry (max, min)
+__global__ void k_marg_gather(int n, const MargReq *__restrict__ req, const double *__restrict__ Z, double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 36 * n) return;
+  const MargReq q = req[i / 36];
+  const int e = i % 36, r = q.r0 + e % 6, c = q.c0 + e / 6;
+  out[36 * (size_t)q.out + e] = Z[q.base + (long long)max(r, c) * q.ld + min(r, c)];
+}
+
+// requested blocks read from the six solved columns of one vertex (cols: 6 x n)
+__global__ void k_marg_columns(int n_req, const ColReq *__restrict__ req, const double *__restrict__ cols, int n,
+                               double *__restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 36 * n_req) return;
+  const ColReq q = req[i / 36];
+  const int e = i % 36, r = e % 6, c = e / 6;
+  out[36 * (size_t)q.out + e] = q.transposed ? cols[(size_t)r * n + q.row + c] : cols[(size_t)c * n + q.row + r];
+}
+
+__global__ void k_unit_vector(double *b, int n, int at) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) b[i] = i == at ? 1.0 : 0.0;
+}
+
 }  // namespace graph
 
 namespace host {
@@ -571,6 +807,9 @@ struct GraphWorkspace {
   // the sparse solver: H blocks, their row pointers and (row, col) slots, the diagonal block of each slot, the fronts and their
   // maps, the level lists, the front matrices and vectors
   Buf Hs, bsr_ptr, bsr_rc, diag_block, fronts, hmap, inv, child_list, loc, level_ids, small_ids, A, V;
+  // marginals: the fronts' Z (the factor's layout), the fronts' parents and child -> parent maps, one tile column of Y and the
+  // inverse of a diagonal tile, the requests, the six solved columns of a vertex, the output blocks
+  Buf Zinv, sel_info, up, ytiles, wtile, mreq, creq, cols, mout;
   hipEvent_t ev[6] = {};
   double lin_ms = 0.0, fac_ms = 0.0;
   int n_padded = 0, factorizations = 0;
@@ -1114,6 +1353,171 @@ struct Solver {
   }
 };
 
+// dvo_amd_graph_marginals: the requests between free active vertices, and what the device stage reports
+struct MargJob {
+  int n = 0;
+  const int *a = nullptr, *b = nullptr;  // vertex indices
+  double *out = nullptr;                 // 36 n: block k column-major at out + 36 k
+  int failed_pivot = -1, solved_columns = 0;
+};
+
+#define GRAPH_TRY(expr)       \
+  do {                        \
+    const int rc_ = (expr);   \
+    if (rc_) return rc_;      \
+  } while (0)
+
+// one front's tile columns, last pivot tile first (the dense solver: the whole matrix, P = T)
+int tiled_selinv_enqueue(Solver &S, const double *L, double *Z, int ld, int P) {
+  GraphWorkspace &W = S.W;
+  const int T = ld / graph::kTile;
+  double *Wt = (double *)W.wtile.p, *Y = (double *)W.ytiles.p;
+  for (int t = P - 1; t >= 0; --t) {
+    hipLaunchKernelGGL(graph::k_tile_inverse, dim3(1), dim3(graph::kBlock), 0, S.st, L, ld, t, Wt, (const int *)S.flag());
+    if (t + 1 < T) {
+      hipLaunchKernelGGL(graph::k_tile_y, dim3(T - t - 1), dim3(graph::kBlock), 0, S.st, L, ld, t, (const double *)Wt, Y,
+                         (const int *)S.flag());
+      hipLaunchKernelGGL(graph::k_tile_zcol, dim3(T - t - 1), dim3(graph::kBlock), 0, S.st, Z, ld, t, T, (const double *)Y,
+                         (const int *)S.flag());
+    }
+    hipLaunchKernelGGL(graph::k_tile_zdiag, dim3(1), dim3(graph::kBlock), 0, S.st, Z, ld, t, T, (const double *)Wt,
+                       (const double *)Y, (const int *)S.flag());
+  }
+  HIP_TRY(hipGetLastError());
+  return DVO_AMD_OK;
+}
+
+// after a successful undamped factorization: Z by selected inversion, then the requested blocks
+int marginals_stage(Solver &S, MargJob &J, const std::vector<int> &slot, const Symbolic *sym, const std::vector<int> &loc) {
+  GraphWorkspace &W = S.W;
+  const hipStream_t st = S.st;
+  const int n = S.n, N = S.N, m = S.m;
+  auto upload = [&](GraphWorkspace::Buf &b, const void *src, size_t bytes) {
+    const int rc = grow(b, std::max<size_t>(bytes, 1));
+    if (rc) return rc;
+    if (bytes && hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
+      return fail_hip("hipMemcpyAsync (marginals)", hipGetLastError());
+    return (int)DVO_AMD_OK;
+  };
+  GRAPH_TRY(grow(W.wtile, sizeof(double) * graph::kTile * graph::kTile));
+  GRAPH_TRY(grow(W.mout, sizeof(double) * 36 * std::max(J.n, 1)));
+  std::vector<graph::MargReq> zreq;
+  struct Column {
+    int slot;
+    std::vector<graph::ColReq> req;
+  };
+  std::map<int, Column> columns;  // by solved slot
+  const double *Z = nullptr;
+  // host-side index vectors must outlive the asynchronous uploads: they live until the final synchronize below
+  std::vector<graph::SelInfo> info;
+  std::vector<int> up;
+  std::vector<graph::ColReq> all;
+  if (!S.sp) {
+    GRAPH_TRY(grow(W.ytiles, sizeof(double) * (size_t)N * graph::kTile));
+    GRAPH_TRY(tiled_selinv_enqueue(S, S.L(), S.H(), N, N / graph::kTile));
+    Z = S.H();
+    for (int k = 0; k < J.n; ++k) zreq.push_back({0, N, 6 * slot[J.a[k]], 6 * slot[J.b[k]], k});
+  } else {
+    const std::vector<graph::Front> &fr = S.sp->fronts;
+    const int nf = (int)fr.size();
+    auto scalar_of = [](const graph::Front &F, int local) { return local < F.p ? 6 * local : F.ppad + 6 * (local - F.p); };
+    info.assign(nf, graph::SelInfo{-1, 0, 0});
+    std::vector<int> where(m, -1), front_of(m, -1);
+    int widest = graph::kTile;
+    for (int k = 0; k < nf; ++k) {
+      const graph::Front &P = fr[k];
+      widest = std::max(widest, P.ld);
+      for (int b = 0; b < P.p; ++b) front_of[loc[P.loc_off + b]] = k;
+      for (int b = 0; b < P.p + P.u; ++b) where[loc[P.loc_off + b]] = scalar_of(P, b);
+      for (int q = sym->child_ptr[k]; q < sym->child_ptr[k + 1]; ++q) {
+        const int c = sym->child[q];
+        info[c] = graph::SelInfo{P.a_off, P.ld, (int)up.size()};
+        for (int j = 0; j < fr[c].u; ++j) up.push_back(where[loc[fr[c].loc_off + fr[c].p + j]]);
+      }
+      for (int b = 0; b < P.p + P.u; ++b) where[loc[P.loc_off + b]] = -1;
+    }
+    if (up.empty()) up.push_back(0);
+    GRAPH_TRY(grow(W.Zinv, sizeof(double) * (size_t)sym->front_doubles));
+    GRAPH_TRY(grow(W.ytiles, sizeof(double) * (size_t)widest * graph::kTile));
+    GRAPH_TRY(upload(W.sel_info, info.data(), sizeof(graph::SelInfo) * info.size()));
+    GRAPH_TRY(upload(W.up, up.data(), sizeof(int) * up.size()));
+    const graph::Front *dfr = (const graph::Front *)W.fronts.p;
+    const int *ids = (const int *)W.level_ids.p, *small = (const int *)W.small_ids.p;
+    double *Zd = (double *)W.Zinv.p;
+    const int levels = (int)S.sp->level_begin.size() - 1;
+    for (int l = levels - 1; l >= 0; --l) {
+      const int count = S.sp->level_begin[l + 1] - S.sp->level_begin[l];
+      const int gx = std::min(64, graph::grid_for((size_t)S.sp->max_ld[l] * S.sp->max_ld[l], graph::kBlock));
+      hipLaunchKernelGGL(graph::k_front_gather_z22, dim3(gx, count), dim3(graph::kBlock), 0, st, dfr,
+                         ids + S.sp->level_begin[l], (const graph::SelInfo *)W.sel_info.p, (const int *)W.up.p, Zd,
+                         (const int *)S.flag());
+      if (S.sp->small_count[l])
+        hipLaunchKernelGGL(graph::k_front_selinv, dim3(S.sp->small_count[l]), dim3(graph::kSelThreads), 0, st, dfr,
+                           small + S.sp->small_begin[l], (const double *)W.A.p, Zd, (const int *)S.flag());
+      HIP_TRY(hipGetLastError());
+      for (int k : S.sp->wide[l])
+        GRAPH_TRY(tiled_selinv_enqueue(S, (const double *)W.A.p + fr[k].a_off, Zd + fr[k].a_off, fr[k].ld,
+                                       fr[k].ppad / graph::kTile));
+    }
+    Z = Zd;
+    // a pair meets in the front of whichever of the two is eliminated first, if it meets anywhere
+    for (int k = 0; k < J.n; ++k) {
+      const int sa = slot[J.a[k]], sb = slot[J.b[k]];
+      const graph::Front &F = fr[front_of[sym->pos[sa] <= sym->pos[sb] ? sa : sb]];
+      int la = -1, lb = -1;
+      for (int b = 0; b < F.p + F.u; ++b) {
+        if (loc[F.loc_off + b] == sa) la = b;
+        if (loc[F.loc_off + b] == sb) lb = b;
+      }
+      if (la >= 0 && lb >= 0) {
+        zreq.push_back({F.a_off, F.ld, scalar_of(F, la), scalar_of(F, lb), k});
+      } else {  // the slow path: the block column of the lower slot, whichever order the pair was asked in
+        Column &C = columns[std::min(sa, sb)];
+        C.slot = std::min(sa, sb);
+        C.req.push_back({6 * std::max(sa, sb), k, sa < sb ? 1 : 0});
+      }
+    }
+  }
+  if (!zreq.empty()) {
+    GRAPH_TRY(upload(W.mreq, zreq.data(), sizeof(graph::MargReq) * zreq.size()));
+    hipLaunchKernelGGL(graph::k_marg_gather, dim3(graph::grid_for(36 * zreq.size(), 256)), dim3(256), 0, st, (int)zreq.size(),
+                       (const graph::MargReq *)W.mreq.p, Z, (double *)W.mout.p);
+    HIP_TRY(hipGetLastError());
+  }
+  if (!columns.empty()) {
+    GRAPH_TRY(grow(W.cols, sizeof(double) * 6 * (size_t)n));
+    for (const auto &kv : columns) all.insert(all.end(), kv.second.req.begin(), kv.second.req.end());
+    GRAPH_TRY(upload(W.creq, all.data(), sizeof(graph::ColReq) * all.size()));
+    const graph::Front *dfr = (const graph::Front *)W.fronts.p;
+    const int *ids = (const int *)W.level_ids.p;
+    const int levels = (int)S.sp->level_begin.size() - 1;
+    size_t first = 0;
+    for (const auto &kv : columns) {
+      for (int q = 0; q < 6; ++q) {
+        hipLaunchKernelGGL(graph::k_unit_vector, dim3(graph::grid_for(n, 256)), dim3(256), 0, st, S.b(), n, 6 * kv.first + q);
+        for (int l = 0; l < levels; ++l)
+          hipLaunchKernelGGL(graph::k_front_forward, dim3(S.sp->level_begin[l + 1] - S.sp->level_begin[l]),
+                             dim3(graph::kFrontThreads), 0, st, dfr, ids + S.sp->level_begin[l], (const double *)W.A.p,
+                             (const int *)W.loc.p, (const int *)W.inv.p, (const int *)W.child_list.p, (const double *)S.b(),
+                             (double *)W.V.p, (const int *)S.flag());
+        for (int l = levels - 1; l >= 0; --l)
+          hipLaunchKernelGGL(graph::k_front_backward, dim3(S.sp->level_begin[l + 1] - S.sp->level_begin[l]),
+                             dim3(graph::kFrontThreads), 0, st, dfr, ids + S.sp->level_begin[l], (const double *)W.A.p,
+                             (const int *)W.loc.p, (double *)W.V.p, (double *)W.cols.p + (size_t)q * n, (const int *)S.flag());
+      }
+      const int cnt = (int)kv.second.req.size();
+      hipLaunchKernelGGL(graph::k_marg_columns, dim3(graph::grid_for(36 * (size_t)cnt, 256)), dim3(256), 0, st, cnt,
+                         (const graph::ColReq *)W.creq.p + first, (const double *)W.cols.p, n, (double *)W.mout.p);
+      HIP_TRY(hipGetLastError());
+      first += cnt;
+    }
+    J.solved_columns = (int)columns.size();
+  }
+  if (J.n) HIP_TRY(hipMemcpyAsync(J.out, W.mout.p, sizeof(double) * 36 * (size_t)J.n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return DVO_AMD_OK;
+}
+
 void record(dvo_amd_graph_iteration *iterations, int capacity, int it, double F, double step, double lambda, double delta,
             int trials, int accepted) {
   if (!iterations || it >= capacity) return;
@@ -1125,12 +1529,6 @@ void record(dvo_amd_graph_iteration *iterations, int capacity, int it, double F,
   r.trials = trials;
   r.accepted = accepted;
 }
-
-#define GRAPH_TRY(expr)       \
-  do {                        \
-    const int rc_ = (expr);   \
-    if (rc_) return rc_;      \
-  } while (0)
 
 // OptimizationAlgorithmLevenberg::solve, max_iterations times
 int run_levenberg(Solver &S, const dvo_amd_graph_options &opt, double *F, dvo_amd_graph_iteration *iterations, int capacity,
@@ -1313,6 +1711,7 @@ struct Probe {
   double *blocks = nullptr;
   int block_capacity = 0;
   int *n_blocks = nullptr;
+  MargJob *marg = nullptr;  // dvo_amd_graph_marginals: blocks of H^-1 instead of the probe's outputs
 };
 
 int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fixed, int n_edges,
@@ -1331,8 +1730,9 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
   stats.n_free = m;
   const bool sparse = opt.solver == DVO_AMD_GRAPH_SOLVER_SPARSE;
   const int cap = sparse ? DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE : DVO_AMD_GRAPH_MAX_FREE_VERTICES;
+  const std::string entry = probe && probe->marg ? "dvo_amd_graph_marginals" : "dvo_amd_optimize_graph";
   if (m > cap) {
-    g_last_error = "dvo_amd_optimize_graph: " + std::to_string(m) + " free active vertices (the " +
+    g_last_error = entry + ": " + std::to_string(m) + " free active vertices (the " +
                    (sparse ? "sparse" : "dense") + " solver takes at most " + std::to_string(cap) + ")";
     return DVO_AMD_ERR_CAPACITY;
   }
@@ -1381,10 +1781,18 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
       for (const GraphWorkspace::Buf *b : {&ctx->graph_ws->A, &ctx->graph_ws->V, &ctx->graph_ws->Hs, &ctx->graph_ws->hmap,
                                            &ctx->graph_ws->inv, &ctx->graph_ws->loc, &ctx->graph_ws->fronts})
         held += (double)b->bytes;
-    const double need = sizeof(double) * (sym.front_doubles + sym.vector_doubles + 36.0 * block_rc.size()) +
-                        sizeof(int) * sym.map_ints + sizeof(graph::Front) * (double)sym.n_fronts;
+    double need = sizeof(double) * (sym.front_doubles + sym.vector_doubles + 36.0 * block_rc.size()) +
+                  sizeof(int) * sym.map_ints + sizeof(graph::Front) * (double)sym.n_fronts;
+    if (probe && probe->marg) {  // the inverse: a second arena of fronts, a tile column, six solved columns, maps, the blocks
+      if (ctx->graph_ws) held += (double)ctx->graph_ws->Zinv.bytes;
+      const int widest_ld = sym.ld.empty() ? 0 : *std::max_element(sym.ld.begin(), sym.ld.end());
+      need += sizeof(double) * (sym.front_doubles + (double)graph::kTile * (widest_ld + graph::kTile) + 36.0 * m +
+                                36.0 * probe->marg->n) +
+              (sizeof(graph::SelInfo) + sizeof(int)) * (double)sym.n_fronts + sizeof(int) * (double)sym.upd.size() +
+              sizeof(graph::MargReq) * (double)probe->marg->n;
+    }
     if (need > ((double)free_b + held) * 0.9) {
-      g_last_error = "dvo_amd_optimize_graph: the sparse factorization needs " +
+      g_last_error = entry + ": the sparse factorization needs " +
                      std::to_string((long long)(need / 1048576.0)) + " MiB of device storage";
       return DVO_AMD_ERR_OUT_OF_MEMORY;
     }
@@ -1556,6 +1964,11 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
     int f = -1;
     GRAPH_TRY(S.read(nullptr, 0, &f));
     if (probe->failed_pivot) *probe->failed_pivot = f;
+    if (probe->marg) {
+      probe->marg->failed_pivot = f;
+      if (f >= 0) return DVO_AMD_OK;
+      return marginals_stage(S, *probe->marg, slot, sparse ? &sym : nullptr, loc);
+    }
     if (sparse) {
       const int nb = (int)slot_rc.size();
       if (probe->n_blocks) *probe->n_blocks = nb;
@@ -1620,7 +2033,8 @@ void graph_workspace_release(dvo_amd_context *ctx) {
                                  &w->x, &w->hsd, &w->hdl, &w->aux, &w->block_rc, &w->block_ptr, &w->block_c, &w->b_ptr,
                                  &w->b_c, &w->vertex_of, &w->scalars, &w->flag, &w->Hs, &w->bsr_ptr, &w->bsr_rc,
                                  &w->diag_block, &w->fronts, &w->hmap, &w->inv, &w->child_list, &w->loc, &w->level_ids,
-                                 &w->small_ids, &w->A, &w->V})
+                                 &w->small_ids, &w->A, &w->V, &w->Zinv, &w->sel_info, &w->up, &w->ytiles, &w->wtile,
+                                 &w->mreq, &w->creq, &w->cols, &w->mout})
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : w->ev)
     if (e) (void)hipEventDestroy(e);
@@ -1667,6 +2081,79 @@ int dvo_amd_optimize_graph(dvo_amd_context *ctx, int n_vertices, double *poses, 
   if (rc) return rc;
   return host::optimize(ctx, n_vertices, poses, fixed, n_edges, edges, *opt, edge_chi2, edge_weight, iteration_capacity,
                         iterations, s);
+}
+
+int dvo_amd_graph_marginals(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,
+                            const dvo_amd_graph_edge *edges, const dvo_amd_graph_options *opt, int n_blocks, const int *block_a,
+                            const int *block_b, double *blocks, dvo_amd_graph_marginal_stats *stats) {
+  dvo_amd_graph_marginal_stats local;
+  dvo_amd_graph_marginal_stats &s = stats ? *stats : local;
+  std::memset(&s, 0, sizeof(s));
+  int rc = host::graph_check_arguments("dvo_amd_graph_marginals", n_vertices, poses, n_edges, edges, opt);
+  if (rc) return rc;
+  auto bad = [](const std::string &why) {
+    g_last_error = "dvo_amd_graph_marginals: " + why;
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  };
+  if (n_blocks < 0) return bad("n_blocks < 0");
+  if (n_blocks > 0 && (!block_a || !block_b || !blocks)) return bad("null block_a, block_b or blocks");
+  for (int k = 0; k < n_blocks; ++k)
+    if (block_a[k] < 0 || block_a[k] >= n_vertices || block_b[k] < 0 || block_b[k] >= n_vertices)
+      return bad("vertex index out of range (block " + std::to_string(k) + ")");
+  std::vector<char> active(std::max(n_vertices, 1), 0);
+  for (int k = 0; k < n_edges; ++k) active[edges[k].from] = active[edges[k].to] = 1;
+  int m = 0;
+  for (int v = 0; v < n_vertices; ++v) m += active[v] && !(fixed && fixed[v]);
+  const bool sparse = opt->solver == DVO_AMD_GRAPH_SOLVER_SPARSE;
+  const int cap = sparse ? DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE : DVO_AMD_GRAPH_MAX_FREE_VERTICES;
+  if (m > cap) {
+    g_last_error = "dvo_amd_graph_marginals: " + std::to_string(m) + " free active vertices (the " +
+                   (sparse ? "sparse" : "dense") + " solver takes at most " + std::to_string(cap) + ")";
+    return DVO_AMD_ERR_CAPACITY;
+  }
+  rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = queue_must_be_idle(ctx, "dvo_amd_graph_marginals");
+  if (rc) return rc;
+  // blocks that touch a fixed vertex are zeros, else those that touch an inactive one NaN; the others go to the device
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  std::vector<int> kind(std::max(n_blocks, 1), 0), qa, qb, at;
+  int n_fixed = 0, n_inactive = 0;
+  for (int k = 0; k < n_blocks; ++k) {
+    const int a = block_a[k], b = block_b[k];
+    if (fixed && (fixed[a] || fixed[b])) {
+      kind[k] = 1, ++n_fixed;
+    } else if (!active[a] || !active[b]) {
+      kind[k] = 2, ++n_inactive;
+    } else {
+      qa.push_back(a), qb.push_back(b), at.push_back(k);
+    }
+  }
+  std::vector<double> out(36 * std::max<size_t>(qa.size(), 1), nan);
+  host::MargJob job;
+  job.n = (int)qa.size();
+  job.a = qa.data();
+  job.b = qb.data();
+  job.out = out.data();
+  std::vector<double> copy(poses, poses + 16 * (size_t)n_vertices);  // the entry does not move any pose
+  dvo_amd_graph_stats st;
+  std::memset(&st, 0, sizeof(st));
+  host::Probe probe{nullptr, nullptr, nullptr, nullptr, nullptr};
+  probe.marg = &job;
+  rc = host::optimize(ctx, n_vertices, copy.data(), fixed, n_edges, edges, *opt, nullptr, nullptr, 0, nullptr, st, &probe);
+  if (rc) return rc;
+  const bool ok = job.failed_pivot < 0;
+  for (int k = 0; k < n_blocks; ++k)
+    for (int e = 0; e < 36; ++e) blocks[36 * (size_t)k + e] = kind[k] == 1 ? 0.0 : nan;
+  if (ok)
+    for (size_t i = 0; i < at.size(); ++i) std::memcpy(blocks + 36 * (size_t)at[i], out.data() + 36 * i, 36 * sizeof(double));
+  s.n_free = st.n_free;
+  s.factorized = ok ? 1 : 0;
+  s.fixed_blocks = n_fixed;
+  s.inactive_blocks = n_inactive;
+  s.solved_columns = ok ? job.solved_columns : 0;
+  return DVO_AMD_OK;
 }
 
 int dvo_amd_debug_graph_system(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,

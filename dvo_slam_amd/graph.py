@@ -18,6 +18,7 @@ TERMINATION = {0: "iterations exhausted", 1: "terminate", 2: "fail"}
 MAX_FREE_VERTICES = 1024
 MAX_FREE_VERTICES_SPARSE = 65536
 BATCH_MAX_FREE_VERTICES = 32
+ROTATION_VECTOR_SCALE = np.array([1.0, 1.0, 1.0, 2.0, 2.0, 2.0])  # S: quaternion-vector units -> rotation-vector units
 
 
 class CGraphEdge(C.Structure):
@@ -40,6 +41,11 @@ class CGraphStats(C.Structure):
                 ("delta", C.c_double)]
 
 
+class CGraphMarginalStats(C.Structure):
+    _fields_ = [("n_free", C.c_int), ("factorized", C.c_int), ("fixed_blocks", C.c_int), ("inactive_blocks", C.c_int),
+                ("solved_columns", C.c_int), ("reserved", C.c_int)]
+
+
 class CGraphBatchItem(C.Structure):
     _fields_ = [("n_vertices", C.c_int), ("poses", C.POINTER(C.c_double)), ("fixed", C.POINTER(C.c_int)),
                 ("n_edges", C.c_int), ("edges", C.POINTER(CGraphEdge)), ("edge_chi2", C.POINTER(C.c_double)),
@@ -59,6 +65,9 @@ def _lib():
         L.dvo_amd_optimize_graph.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_int), C.c_int, C.POINTER(CGraphEdge),
                                              C.POINTER(CGraphOptions), dp, dp, C.c_int, C.POINTER(CGraphIteration),
                                              C.POINTER(CGraphStats)]
+        L.dvo_amd_graph_marginals.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_int), C.c_int, C.POINTER(CGraphEdge),
+                                              C.POINTER(CGraphOptions), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), dp,
+                                              C.POINTER(CGraphMarginalStats)]
         L.dvo_amd_debug_graph_timing.argtypes = [C.c_void_p, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.dvo_amd_debug_graph_system.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_int), C.c_int, C.POINTER(CGraphEdge),
                                                  C.c_double, dp, dp, dp, dp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -184,6 +193,38 @@ class PoseGraph:
         self.last = res
         return res
 
+    def marginals(self, tracker: "capi.DenseTracker", pairs=None, solver: str = "dense", robust_delta: float = 5.0,
+                  rotation: str = "quaternion"):
+        """Blocks of Sigma = H^-1 at the current poses (dvo_amd_graph_marginals; the semantics are pinned in dvo_amd.h):
+        (blocks (k, 6, 6) float64 row-major, stats).  pairs: (a, b) vertex pairs, block k = rows of a, columns of b; None means
+        every vertex's diagonal block, in vertex order.  A block that touches a fixed vertex is zeros, one that touches an
+        inactive vertex NaN; when stats.factorized == 0 every other block is NaN.  rotation="quaternion": the increment's own
+        coordinates (tx, ty, tz, qx, qy, qz); "vector": S Sigma S with S = diag(1, 1, 1, 2, 2, 2), rotation-vector units
+        (radians).  With solver="sparse" pairs that share no edge take the slow path (stats.solved_columns)."""
+        if rotation not in ("quaternion", "vector"):
+            raise ValueError("rotation must be 'quaternion' or 'vector'")
+        L = _lib()
+        o = default_options("dogleg")
+        o.solver = SOLVERS[solver]
+        o.robust_delta = float(robust_delta)
+        live, nv, ne, P, fixed, ce = self._pack()
+        if pairs is None:
+            pairs = [(v, v) for v in range(nv)]
+        pr = np.asarray(list(pairs), dtype=np.int32).reshape(-1, 2)
+        k = len(pr)
+        a, b = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        out = np.zeros((max(k, 1), 36))
+        st = CGraphMarginalStats()
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        rc = L.dvo_amd_graph_marginals(tracker._h, nv, P.ctypes.data_as(dp), fixed.ctypes.data_as(ip), ne, ce, C.byref(o), k,
+                                       a.ctypes.data_as(ip) if k else None, b.ctypes.data_as(ip) if k else None,
+                                       out.ctypes.data_as(dp) if k else None, C.byref(st))
+        capi._check(rc, "dvo_amd_graph_marginals")
+        blocks = np.ascontiguousarray(out[:k].reshape(k, 6, 6).transpose(0, 2, 1))  # column-major -> row-major
+        if rotation == "vector":
+            blocks = blocks * np.outer(ROTATION_VECTOR_SCALE, ROTATION_VECTOR_SCALE)
+        return blocks, st
+
     def _pack(self):
         live = self.live_edges()
         nv, ne = len(self.poses), len(live)
@@ -258,6 +299,54 @@ class PoseGraph:
         for k in cand:
             self.edges[k] = None
         return cand
+
+
+def _skew(a):
+    return np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+
+
+def relative_jacobians(Xa, Xb):
+    """(J_a, J_b): dvo_amd.h's J_from and J_to for an edge from a to b with Z = I, i.e. the derivatives of
+    e = (t, q_xyz)(Xa^-1 Xb) with respect to the increments of a and b at 0"""
+    Xa, Xb = np.asarray(Xa, dtype=np.float64), np.asarray(Xb, dtype=np.float64)
+    Ra, ta = Xa[:3, :3], Xa[:3, 3]
+    R = Ra.T @ Xb[:3, :3]
+    t = Ra.T @ (Xb[:3, 3] - ta)
+    # the unit quaternion of R with w >= 0 (the branch of largest magnitude, as Eigen's Quaternion(R))
+    tr = np.trace(R)
+    if tr > 0:
+        s = np.sqrt(tr + 1.0) * 2.0
+        q = np.array([0.25 * s, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s])
+    else:
+        i = int(np.argmax(np.diag(R)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0) * 2.0
+        q = np.zeros(4)
+        q[0] = (R[k, j] - R[j, k]) / s
+        q[1 + i] = 0.25 * s
+        q[1 + j] = (R[j, i] + R[i, j]) / s
+        q[1 + k] = (R[k, i] + R[i, k]) / s
+    q /= np.linalg.norm(q)
+    if q[0] < 0:
+        q = -q
+    w, v = q[0], q[1:]
+    Jb, Ja = np.zeros((6, 6)), np.zeros((6, 6))
+    Jb[:3, :3] = R
+    Jb[3:, 3:] = w * np.eye(3) + _skew(v)
+    Ja[:3, :3] = -np.eye(3)
+    Ja[:3, 3:] = 2.0 * _skew(t)
+    Ja[3:, 3:] = -(w * np.eye(3) - _skew(v))
+    return Ja, Jb
+
+
+def relative_covariance(Xa, Xb, S_aa, S_ab, S_bb) -> np.ndarray:
+    """First-order covariance of Delta = Xa^-1 Xb in the edge error's coordinates (t, q_xyz), from the marginal blocks of
+    PoseGraph.marginals (rotation="quaternion"): J_a S_aa J_a^T + J_a S_ab J_b^T + J_b S_ab^T J_a^T + J_b S_bb J_b^T.  Host numpy
+    only: what a candidate search gated by the uncertainty of the relative pose would call."""
+    Ja, Jb = relative_jacobians(Xa, Xb)
+    S_aa, S_ab, S_bb = (np.asarray(S, dtype=np.float64).reshape(6, 6) for S in (S_aa, S_ab, S_bb))
+    cross = Ja @ S_ab @ Jb.T
+    return Ja @ S_aa @ Ja.T + cross + cross.T + Jb @ S_bb @ Jb.T
 
 
 def _records(its, n):

@@ -683,6 +683,56 @@ typedef struct {
 int dvo_amd_optimize_graphs_batch(dvo_amd_context *ctx, int n_graphs, dvo_amd_graph_batch_item *items,
                                   const dvo_amd_graph_options *opt);
 
+/*
+ * Marginal covariances of pose-graph vertices: blocks of Sigma = H^-1 (g2o::SparseOptimizer::computeMarginals' role).
+ *  - The matrix.  H is exactly the first system dvo_amd_optimize_graph builds at the given poses: the linearisation, the
+ *    Cauchy weights (opt->robust_delta), rho1 Omega, no second-order term, the free active vertices in increasing index, and no
+ *    damping (lambda = 0).  Of opt only solver and robust_delta are read; the other fields are still validated as
+ *    dvo_amd_optimize_graph validates them.
+ *  - Coordinates.  Sigma is the covariance of the increment d = (tx, ty, tz, qx, qy, qz) of X <- X * inc(d): a perturbation on
+ *    the right, in the vertex's own frame, the rotation in quaternion-vector units (half a rotation vector to first order;
+ *    S Sigma S with S = diag(1, 1, 1, 2, 2, 2) is in rotation-vector units, radians).
+ *  - Requests.  Block k holds the rows of vertex block_a[k] and the columns of vertex block_b[k], column-major at
+ *    blocks + 36 k; a == b is a vertex's marginal covariance.  Any pair of vertices may be asked for, in any order, repeated
+ *    or not.  n_blocks == 0 is valid (stats only; block_a, block_b and blocks may then be NULL).
+ *  - Fixed and inactive vertices.  A block that touches a fixed vertex is all zeros (known exactly); otherwise a block that
+ *    touches an inactive vertex (no edge: unconstrained) is all NaN.  Both are counted in stats.
+ *  - Failure.  A pivot <= 0 or NaN (for instance a component with no fixed vertex) is not an error of the call: it returns
+ *    DVO_AMD_OK with factorized = 0, and every block that would have held numbers is NaN (the zeros of fixed vertices stay).
+ *    No free active vertex: DVO_AMD_OK, factorized = 1, n_free = 0.
+ *  - Symmetry.  A diagonal block is exactly symmetric and block (b, a) is the transpose of block (a, b) bit for bit: one
+ *    triangle of Sigma is computed and every reader takes entry (max, min).
+ *  - Determinism.  Fixed summation orders, no floating-point atomics: bit-identical between runs and between contexts on one
+ *    device, and a block's bits do not depend on which other blocks were requested with it.
+ *  - Solvers.  DVO_AMD_GRAPH_SOLVER_DENSE forms the whole lower triangle of Sigma on the device from the tiled Cholesky
+ *    factor (a blocked selected inversion over 64 x 64 tiles, which for a full matrix is the full inverse) and reads the
+ *    requested blocks from it.  DVO_AMD_GRAPH_SOLVER_SPARSE runs the selected inversion over the assembly tree of the
+ *    multifrontal factor, root to leaves (per front Y = L21 L11^-1, Z21 = -Z22 Y, Z11 = L11^-T L11^-1 - Y^T Z21, Z22 gathered
+ *    from the parent), at the cost of a small multiple of one factorization, and serves from it every pair whose two vertices
+ *    meet in one front: every diagonal block and every pair joined by an edge.  Any other pair takes the slow path: the block
+ *    column of the pair's lower free slot by 6 unit right-hand sides through the forward / backward substitution, once per
+ *    distinct such vertex (stats->solved_columns), each solve as serial as any solve of the sparse path.  The two solvers
+ *    agree to rounding, not bit for bit.
+ *  - Limits and errors.  The argument checks of dvo_amd_optimize_graph in its order, then DVO_AMD_ERR_INVALID_ARGUMENT for
+ *    n_blocks < 0, NULL block_a / block_b / blocks with n_blocks > 0 or a vertex index out of range; then the capacity rule of
+ *    the chosen solver (1024 / 65536 free active vertices: DVO_AMD_ERR_CAPACITY); all of these before any device is looked
+ *    for.  Then DVO_AMD_ERR_NO_DEVICE, DVO_AMD_ERR_INVALID_ARGUMENT for a NULL ctx or a context with queued pairs, and the
+ *    sparse solver's DVO_AMD_ERR_OUT_OF_MEMORY prediction, which here counts the storage of the inverse (a second set of front
+ *    matrices) as well.  poses is const; on any error nothing of the caller's is written except *stats (zeroed).
+ */
+typedef struct {
+  int n_free;            /* m: free active vertices */
+  int factorized;        /* 1: H was positive definite; 0: a pivot <= 0 or NaN was met, every block is NaN */
+  int fixed_blocks;      /* requested blocks that touch a fixed vertex (returned as zeros) */
+  int inactive_blocks;   /* requested blocks that touch an inactive vertex (returned as NaN) */
+  int solved_columns;    /* sparse solver: distinct vertices whose block column had to be obtained by 6 solves */
+  int reserved;
+} dvo_amd_graph_marginal_stats;
+
+int dvo_amd_graph_marginals(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,
+                            const dvo_amd_graph_edge *edges, const dvo_amd_graph_options *opt, int n_blocks, const int *block_a,
+                            const int *block_b, double *blocks, dvo_amd_graph_marginal_stats *stats);
+
 /* Host-side helpers (no GPU needed): the SE(3) exponential / logarithm with Sophus' tangent order (upsilon, omega) and the
  * pivoted LDL^T 6x6 solve the driver uses in place of Sophus::SE3d::exp/log and Eigen::LDLT (dense_tracking.cpp:238,259,347).
  * Exported so that bindings do not need Sophus to build a T_init or to compare poses. */
