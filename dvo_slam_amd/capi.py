@@ -40,6 +40,7 @@ EXPORTS = [
     "dvo_amd_debug_map_timing", "dvo_amd_default_graph_options", "dvo_amd_optimize_graph", "dvo_amd_graph_marginals", "dvo_amd_debug_graph_timing",
     "dvo_amd_debug_graph_system", "dvo_amd_debug_graph_system_sparse", "dvo_amd_debug_graph_symbolic",
     "dvo_amd_debug_graph_sparse_timing", "dvo_amd_optimize_graphs_batch", "dvo_amd_debug_graph_batch_records",
+    "dvo_amd_debug_tick_layout",
 ]
 
 
@@ -212,6 +213,8 @@ def lib():
     L.dvo_amd_debug_wire_layout.argtypes = [C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.dvo_amd_debug_take_wire.argtypes = [C.POINTER(C.c_uint), C.c_uint, C.c_int, C.POINTER(C.c_uint)]
     L.dvo_amd_debug_next_seq.argtypes = [C.c_uint]
+    ip = C.POINTER(C.c_int)
+    L.dvo_amd_debug_tick_layout.argtypes = [C.c_int, ip, ip, ip, ip, ip, C.c_int, C.c_int, ip, ip, ip, ip, ip, ip, ip, C.c_longlong, ip, ip]
     L.dvo_amd_debug_next_seq.restype = C.c_uint
     L.dvo_amd_point_cloud.argtypes = [vp, vp, C.c_int, dp, vp, C.c_int, vp]
     L.dvo_amd_map_cloud.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(vp), C.POINTER(C.c_int), C.c_float, vp,
@@ -914,6 +917,27 @@ def take_wire(wire: np.ndarray, tick: int, from_piece: int, record: np.ndarray) 
     if rc < 0:
         _check(-rc, "take_wire")
     return rc
+
+
+def tick_layout(res_blocks, ll_blocks, res_steps, ref_key, cur_key, share: int, max_blocks: int = 0) -> dict:
+    """Where the blocks of one k_tick launch of these synthetic work items go (host only: dvo_amd_debug_tick_layout).  Returns
+    order (launch position -> item), per launch position group_first / xcd_rot / tail_rot / set_size, compact, n_blocks and, for
+    a compact grid, block_item / block_index per block of the grid (-1: a block that exits at once)."""
+    ip = C.POINTER(C.c_int)
+    ins = [np.ascontiguousarray(a, np.int32) for a in (res_blocks, ll_blocks, res_steps, ref_key, cur_key)]
+    n = len(ins[0])
+    assert all(len(a) == n for a in ins)
+    order, rot, tail, size = (np.zeros(n, np.int32) for _ in range(4))
+    first = np.zeros(n + 1, np.int32)
+    compact, n_blocks = C.c_int(), C.c_int()
+    cap = 8 * 65536
+    b_item, b_index = np.full(cap, -2, np.int32), np.full(cap, -2, np.int32)
+    p = lambda a: a.ctypes.data_as(ip)
+    _check(lib().dvo_amd_debug_tick_layout(n, *[p(a) for a in ins], share, max_blocks, p(order), p(first), p(rot), p(tail), p(size),
+                                           C.byref(compact), C.byref(n_blocks), cap, p(b_item), p(b_index)), "tick_layout")
+    nb = n_blocks.value if compact.value else 0
+    return dict(order=order, group_first=first, xcd_rot=rot, tail_rot=tail, set_size=size, compact=compact.value,
+                n_blocks=n_blocks.value, block_item=b_item[:nb], block_index=b_index[:nb])
 
 
 def combine_bands(bands) -> np.ndarray:

@@ -217,6 +217,8 @@ struct dvo_amd_context {
   int fault_slot_alloc = -1;           // DVO_AMD_FAULT_SLOT_ALLOC: fail the allocation of this slot once (tests of the error path)
   bool fin_stamps = false;             // DVO_AMD_FIN_STAMPS=1: k_finalize records phase stamps (diagnostic)
   bool sort_items = true;              // longest-lived blocks first inside a launch (DVO_AMD_SORT_ITEMS=0: slot order)
+  int share_placement = 1;             // pairs of one keyframe level next to each other and on the same XCDs (DVO_AMD_SHARE_PLACEMENT=
+                                       // 0: every item placed on its own, 1: sets share a rotation, 2: ... and are dispatched interleaved)
   bool fin_priority = true;            // the batch reducer's waves run at raised issue priority (DVO_AMD_FIN_PRIORITY=0: off)
   bool small_args = true;              // ticks of at most kMaxSmallItems pairs use the small argument blocks (DVO_AMD_SMALL_ARGS=0: never)
   bool poll = true;                    // wait for a tick by polling the records' sequence words instead of hipStreamSynchronize

@@ -17,9 +17,11 @@
 // (deterministic run to run).
 //
 // This file is compiled with -ffp-contract=off: every a*b+c that may fuse is written as __builtin_fmaf explicitly.
+#include <algorithm>
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <mutex>
 #include <vector>
 
@@ -1111,24 +1113,40 @@ __device__ __forceinline__ void tick_body(const TickItem &it, const RcpTable &rc
 #endif
 }
 
+// Which of its owner's blocks is block `block` of the grid?  idx: the item whose range of block groups holds it (a set's first
+// item when the set is dispatched interleaved: TickArgs::set_size).  Returns the item and leaves its block in bx.  Shared with
+// the host's restatement (tick_args_locate).
+template <class Args>
+__host__ __device__ __forceinline__ int tick_place(const Args &args, int idx, int pos, const unsigned block, int &bx) {
+  if constexpr (Args::kSets) {
+    // (compact == 2: a launch-wide flag that is there with the kernel's first arguments, so that a launch without interleaved
+    //  sets does not put set_size's load in front of everything that depends on idx -- measured: 1.3 % of the batch)
+    if (args.compact > 1) {
+      const unsigned m = args.set_size[idx];
+      if (m > 1) {
+        const unsigned q = (unsigned)(((unsigned long long)(unsigned)pos * args.set_inv[idx]) >> 32);  // pos / m
+        idx += pos - (int)(q * m);
+        pos = (int)q;
+      }
+    }
+  }
+  const int rot = pos < (int)(args.items[idx].res_blocks >> 3) ? args.xcd_rot[idx] : args.tail_rot[idx];
+  bx = (pos << 3) | (int)((block + (unsigned)rot) & 7u);
+  return idx;
+}
+
 // Which item owns this block, and which of the item's blocks is it?  Two-dimensional grid: (block, item).  One-dimensional
 // ("compact") grid: lanes 0 .. n_items look at the items' first block groups; the owner is the last item that starts at or
 // before this block's group (every wave finds the same one).
 template <class Args>
 __device__ __forceinline__ int tick_locate(const Args &args, int &bx, const unsigned block = blockIdx.x) {
   constexpr int kSlots = (int)(sizeof(args.group_first) / sizeof(args.group_first[0]));
-  if (!args.compact) {
-    const int rot = args.xcd_rot[blockIdx.y];
-    bx = (int)((block & ~7u) | ((block + rot) & 7u));
-    return (int)blockIdx.y;
-  }
+  if (!args.compact) return tick_place(args, (int)blockIdx.y, (int)(block >> 3), block, bx);
   const int lane = threadIdx.x & (kWave - 1);
   const unsigned g = block >> 3;
   const unsigned first = lane <= args.n_items ? (unsigned)args.group_first[lane < kSlots ? lane : 0] : 0xFFFFFFFFu;
   const int idx = __builtin_amdgcn_readfirstlane(__popcll(__ballot(first <= g)) - 1);
-  bx = (int)block - ((int)args.group_first[idx] << 3);
-  bx = (bx & ~7) | ((bx + (int)args.xcd_rot[idx]) & 7);
-  return idx;
+  return tick_place(args, idx, (int)g - (int)args.group_first[idx], block, bx);
 }
 
 // ACC 1 (default): Gram matrix on the matrix pipe, 4 waves per SIMD.  ACC 0 (DVO_AMD_ACCUM=valu): 87 fp32 registers per lane,
@@ -1363,53 +1381,155 @@ static TickKernel pick_tick_kernel(const RcpTable &rcp) {
 // A tick's items are at different pyramid levels: the two-dimensional grid (blocks of the largest item x items) launches
 // mostly blocks that return at once, and the dispatcher starts only ~4 of them per nanosecond.  When more than half of the
 // grid would be such blocks the launch goes out one-dimensional with every item's blocks back to back.
+//
+// Where an item's blocks run (TickArgs::xcd_rot, tail_rot, set_size).  Loads are in units of ~0.1 us of block life as the block
+// trace measures it (a residual block: 3.3 us + 2.1 us per step; a likelihood block about half of that).
+//   share 0: greedy over the items in launch order, one rotation per item, the one that leaves the smallest maximum XCD load.
+//   share 1: the same greedy over SETS -- runs of neighbours in launch order that read the same reference level with the same
+//     geometry (tick_items_order puts them next to each other) -- with one rotation for all members, so that XCD x works on
+//     the same eighth of every member's segments and the members meet in its L2.  A set's remainder blocks repeat once per
+//     member; where the sets' rotations leave the XCDs' loads more than 2 % of their mean apart, all full groups of the
+//     launch stay unrotated and the greedy rotates every item's tail (partial residual group + likelihood blocks) instead.
+//   share 2: ... and each set of the compact grid is dispatched interleaved (TickArgs::set_size).
+// Sets of one item give the layout of share 0 exactly; so does the two-dimensional grid under every value.
+static bool same_set(const TickItem &a, const TickItem &b) {
+  return a.res_blocks > 0 && a.ref == b.ref && a.res_blocks == b.res_blocks && a.res_first == b.res_first &&
+         (a.steps_log2 & 15) == (b.steps_log2 & 15);
+}
+static int layout_tail_mode() {  // DVO_AMD_SHARE_TAIL=0 / 1: never / always rotate the tails alone (tuning; default: the 2 % rule)
+  static const int m = [] {
+    const char *e = getenv("DVO_AMD_SHARE_TAIL");
+    return e ? (e[0] == '0' ? 0 : 1) : 2;
+  }();
+  return m;
+}
 template <class Args>
-static int tick_args_layout_impl(Args &args, int max_blocks) {
+static int tick_args_layout_impl(Args &args, int max_blocks, int share) {
   constexpr int kSlots = (int)(sizeof(args.group_first) / sizeof(args.group_first[0]));
-  unsigned groups = 0;
-  for (int i = 0; i < args.n_items; ++i) {
-    args.group_first[i] = (uint16_t)groups;
-    groups += ((unsigned)args.items[i].res_blocks + args.items[i].ll_blocks + 7u) >> 3;
-  }
-  for (int i = args.n_items; i < kSlots; ++i) args.group_first[i] = (uint16_t)groups;
-  // even out the XCDs' shares (see TickArgs::xcd_rot): greedy over the items in launch order, loads in units of ~0.1 us of block
-  // life as the block trace measures it (a residual block: 3.3 us + 2.1 us per step; a likelihood block about half of that)
+  constexpr int kRots = (int)(sizeof(args.xcd_rot) / sizeof(args.xcd_rot[0]));
+  const int n = args.n_items;
+  if constexpr (!Args::kSets) share = 0;
   static const bool rotate = [] {
     const char *e = getenv("DVO_AMD_XCD_ROTATE");
     return !(e && e[0] == '0');
   }();
-  long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = 0; i < args.n_items; ++i) {
+  // the sets: set_len[i] = members of the set that starts at item i (0: item i belongs to an earlier item's set)
+  int set_len[kRots] = {};
+  bool any_set = false;
+  for (int i = 0; i < n;) {
+    int j = i + 1;
+    while (share > 0 && j < n && same_set(args.items[i], args.items[j])) ++j;
+    set_len[i] = j - i;
+    any_set = any_set || j - i > 1;
+    i = j;
+  }
+  // what item i puts on the XCD that runs its blocks of phase f (blocks f, f + 8, ... before the rotation)
+  long long phase[kRots][8];
+  for (int i = 0; i < n; ++i) {
     const TickItem &it = args.items[i];
     const int rb = it.res_blocks, lb = it.ll_blocks;
     const long long w_res = 33 + 21 * item_res_steps(it), w_ll = 40 + 7 * item_ll_steps(it);
-    long long phase[8];
     for (int f = 0; f < 8; ++f) {
       const int n_res = (rb >> 3) + (f < (rb & 7) ? 1 : 0);
       const int all = ((rb + lb) >> 3) + (f < ((rb + lb) & 7) ? 1 : 0);
-      phase[f] = w_res * n_res + w_ll * (all - n_res);
+      phase[i][f] = w_res * n_res + w_ll * (all - n_res);
     }
-    int best = 0;
-    long long best_max = -1;
-    for (int rot = 0; rotate && rot < 8; ++rot) {  // XCD x does the blocks of phase (x + rot) & 7
-      long long mx = 0;
-      for (int x = 0; x < 8; ++x) mx = std::max(mx, load[x] + phase[(x + rot) & 7]);
-      if (best_max < 0 || mx < best_max) best_max = mx, best = rot;
-    }
-    args.xcd_rot[i] = (uint8_t)best;
-    for (int x = 0; x < 8; ++x) load[x] += phase[(x + best) & 7];
   }
-  for (int i = args.n_items; i < (int)(sizeof(args.xcd_rot) / sizeof(args.xcd_rot[0])); ++i) args.xcd_rot[i] = 0;
+  long long load[8];
+  // greedy over runs of items [i, i + len(i)): XCD x does the blocks of phase (x + rot) & 7 of every item of the run
+  auto balance = [&](bool by_set, uint8_t *rot_out) {
+    for (int x = 0; x < 8; ++x) load[x] = 0;
+    for (int i = 0; i < n;) {
+      const int len = by_set ? set_len[i] : 1;
+      long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (int k = i; k < i + len; ++k)
+        for (int f = 0; f < 8; ++f) ph[f] += phase[k][f];
+      int best = 0;
+      long long best_max = -1;
+      for (int rot = 0; rotate && rot < 8; ++rot) {
+        long long mx = 0;
+        for (int x = 0; x < 8; ++x) mx = std::max(mx, load[x] + ph[(x + rot) & 7]);
+        if (best_max < 0 || mx < best_max) best_max = mx, best = rot;
+      }
+      for (int k = i; k < i + len; ++k) rot_out[k] = (uint8_t)best;
+      for (int x = 0; x < 8; ++x) load[x] += ph[(x + best) & 7];
+      i += len;
+    }
+  };
+  balance(true, args.xcd_rot);
+  for (int i = 0; i < n; ++i) args.tail_rot[i] = args.xcd_rot[i];
+  if (any_set && rotate) {
+    long long lo = load[0], hi = load[0], sum = 0;
+    for (int x = 0; x < 8; ++x) lo = std::min(lo, load[x]), hi = std::max(hi, load[x]), sum += load[x];
+    const int tail_mode = layout_tail_mode();
+    if (tail_mode == 1 || (tail_mode == 2 && (hi - lo) * 8 * 50 > sum)) {  // more than 2 % of the mean apart
+      balance(false, args.tail_rot);
+      for (int i = 0; i < n; ++i) args.xcd_rot[i] = 0;
+    }
+  }
+  for (int i = n; i < kRots; ++i) args.xcd_rot[i] = args.tail_rot[i] = 0;
+
+  const bool interleave = share > 1 && any_set;
+  unsigned groups = 0;
+  auto item_groups = [&](int i) { return ((unsigned)args.items[i].res_blocks + args.items[i].ll_blocks + 7u) >> 3; };
+  for (int i = 0; i < n;) {
+    const int len = interleave ? set_len[i] : 1;
+    unsigned widest = 0;
+    for (int k = i; k < i + len; ++k) widest = std::max(widest, item_groups(k));
+    args.group_first[i] = (uint16_t)groups;
+    groups += (unsigned)len * widest;
+    for (int k = i + 1; k < i + len; ++k) args.group_first[k] = (uint16_t)groups;
+    if constexpr (Args::kSets) {
+      for (int k = i; k < i + len; ++k) args.set_size[k] = 1, args.set_inv[k] = 0;
+      if (len > 1) args.set_size[i] = (uint8_t)len, args.set_inv[i] = (uint32_t)(0xFFFFFFFFull / (unsigned)len + 1ull);
+    }
+    i += len;
+  }
+  for (int i = n; i < kSlots; ++i) args.group_first[i] = (uint16_t)groups;
+  if constexpr (Args::kSets)
+    for (int i = n; i < kRots; ++i) args.set_size[i] = 1;
   const long long grid2d = (long long)((max_blocks + 7) & ~7) * args.n_items;
   static const int mode = [] {  // DVO_AMD_COMPACT_GRID=0 / 1 forces a layout (tuning)
     const char *e = getenv("DVO_AMD_COMPACT_GRID");
     return e ? (e[0] == '0' ? 0 : 1) : 2;
   }();
-  args.compact = groups > 0 && groups < 65536 && (mode == 1 || (mode == 2 && 2ll * 8 * groups < grid2d)) ? 1 : 0;
+  // (the surplus blocks of an interleaved set are few -- its members differ in their likelihood blocks only -- and are not
+  //  counted: the choice between the grids is the one share 0 makes)
+  unsigned own_groups = 0;
+  for (int i = 0; i < n; ++i) own_groups += item_groups(i);
+  args.compact = groups > 0 && groups < 65536 && (mode == 1 || (mode == 2 && 2ll * 8 * own_groups < grid2d)) ? (interleave ? 2 : 1) : 0;
+  if (!args.compact && share > 0) return tick_args_layout_impl(args, max_blocks, 0);  // the two-dimensional grid has no sets
   return (int)(groups * 8);
 }
-int tick_args_layout(TickArgs &args, int max_blocks) { return tick_args_layout_impl(args, max_blocks); }
-int tick_args_layout(TickArgsSmall &args, int max_blocks) { return tick_args_layout_impl(args, max_blocks); }
+int tick_args_layout(TickArgs &args, int max_blocks, int share) { return tick_args_layout_impl(args, max_blocks, share); }
+int tick_args_layout(TickArgsSmall &args, int max_blocks) { return tick_args_layout_impl(args, max_blocks, 0); }
+
+void tick_items_order(const TickItem *items, int n, bool sort, int share, int *order) {
+  for (int i = 0; i < n; ++i) order[i] = i;
+  if (!sort) return;
+  std::stable_sort(order, order + n, [&](int a, int b) {
+    const TickItem &x = items[a], &y = items[b];
+    const int kx = x.res_blocks ? item_res_steps(x) : 0, ky = y.res_blocks ? item_res_steps(y) : 0;
+    if (kx != ky || share <= 0) return kx > ky;
+    // one reference level's items together (a RefLevelDesc is one level of one keyframe), by current level inside the run
+    if (x.ref != y.ref) return std::less<const void *>()(x.ref, y.ref);
+    return std::less<const void *>()(x.cur, y.cur);
+  });
+}
+
+int tick_args_locate(const TickArgs &args, unsigned block, int *bx) {
+  *bx = -1;
+  if (!args.compact || (block >> 3) >= (unsigned)args.group_first[args.n_items]) return -1;
+  int idx = -1;
+  for (int i = 0; i <= args.n_items; ++i)
+    if ((unsigned)args.group_first[i] <= (block >> 3)) idx = i;
+  if (idx < 0 || idx >= args.n_items) return -1;
+  int b;
+  idx = tick_place(args, idx, (int)(block >> 3) - (int)args.group_first[idx], block, b);
+  if (idx >= args.n_items || b >= (int)args.items[idx].res_blocks + (int)args.items[idx].ll_blocks) return -1;  // a surplus block: exits at once
+  *bx = b;
+  return idx;
+}
 
 hipError_t launch_tick_small(const TickArgsSmall &args, int max_blocks, hipStream_t stream, hipEvent_t t_start, hipEvent_t t_stop) {
   if (acc_mode() != 1) return hipErrorNotSupported;  // (with or without the reciprocal table: launch_tick decides)

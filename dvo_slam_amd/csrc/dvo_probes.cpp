@@ -67,6 +67,45 @@ int dvo_amd_debug_take_wire(const unsigned *wire, unsigned tick, int from_piece,
   return next;
 }
 
+int dvo_amd_debug_tick_layout(int n_items, const int *res_blocks, const int *ll_blocks, const int *res_steps, const int *ref_key,
+                              const int *cur_key, int share, int max_blocks, int *order, int *group_first, int *xcd_rot,
+                              int *tail_rot, int *set_size, int *compact, int *n_blocks, long long capacity_blocks, int *block_item,
+                              int *block_index) {
+  if (n_items < 1 || n_items > kMaxItemsPerLaunch || !res_blocks || !ll_blocks || !res_steps || !ref_key || !cur_key || !order ||
+      !group_first || !xcd_rot || !tail_rot || !set_size || !compact || !n_blocks || share < 0 || share > 2 || !block_item != !block_index)
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  std::vector<TickItem> items((size_t)n_items);
+  int widest = 0;
+  for (int i = 0; i < n_items; ++i) {
+    TickItem &w = items[(size_t)i];
+    std::memset(&w, 0, sizeof(w));
+    if (res_blocks[i] < 0 || res_blocks[i] > 2048 || ll_blocks[i] < 0 || ll_blocks[i] > 2048 || ref_key[i] < 0 || cur_key[i] < 0)
+      return DVO_AMD_ERR_INVALID_ARGUMENT;
+    // (the keys stand in for the descriptors' addresses: never dereferenced on the host)
+    w.ref = reinterpret_cast<const RefLevelDesc *>(uintptr_t(4096) + sizeof(RefLevelDesc) * (size_t)ref_key[i]);
+    w.cur = reinterpret_cast<const CurLevelDesc *>(uintptr_t(4096) + sizeof(CurLevelDesc) * (size_t)cur_key[i]);
+    w.res_blocks = (uint16_t)res_blocks[i], w.ll_blocks = (uint16_t)ll_blocks[i];
+    item_set_steps(w, res_steps[i], res_steps[i]);
+    if (item_res_steps(w) != res_steps[i]) return DVO_AMD_ERR_INVALID_ARGUMENT;
+    widest = std::max(widest, res_blocks[i] + ll_blocks[i]);
+  }
+  tick_items_order(items.data(), n_items, true, share, order);
+  TickArgs ta;
+  ta.n_items = n_items, ta.compact = 0;
+  std::memset(&ta.rcp, 0, sizeof(ta.rcp));
+  for (int k = 0; k < n_items; ++k) ta.items[k] = items[(size_t)order[k]];
+  *n_blocks = tick_args_layout(ta, max_blocks > 0 ? max_blocks : widest, share);
+  *compact = ta.compact ? 1 : 0;
+  for (int k = 0; k < n_items; ++k)
+    group_first[k] = ta.group_first[k], xcd_rot[k] = ta.xcd_rot[k], tail_rot[k] = ta.tail_rot[k], set_size[k] = ta.set_size[k];
+  group_first[n_items] = ta.group_first[n_items];
+  if (block_item && ta.compact) {
+    if (capacity_blocks < (long long)*n_blocks) return DVO_AMD_ERR_INVALID_ARGUMENT;
+    for (int b = 0; b < *n_blocks; ++b) block_item[b] = tick_args_locate(ta, (unsigned)b, &block_index[b]);
+  }
+  return DVO_AMD_OK;
+}
+
 }  // extern "C"
 
 namespace dvo_amd {

@@ -687,16 +687,12 @@ int submit_tick(dvo_amd_context *ctx, std::vector<Job> &jobs, GroupTick &grp) {
     ta.rcp = ctx->rcp;
     int max_blocks = 0;
     // Blocks are dispatched in grid order and a launch ends with its last block: items whose blocks live longest (the most steps
-    // per wave segment) go first, so that the launch's tail is made of short blocks.  The order of the items inside a launch
-    // changes no result (every item's blocks, records and reducer are its own).  DVO_AMD_SORT_ITEMS=0: slot order.
+    // per wave segment) go first, so that the launch's tail is made of short blocks.  Inside such a class the pairs of one
+    // keyframe level go next to each other, ordered by current frame (share placement: tick_args_layout gives them one XCD
+    // rotation, and blocks that read the same lines are then dispatched close in time as well).  The order of the items inside
+    // a launch changes no result (every item's blocks, records and reducer are its own).  DVO_AMD_SORT_ITEMS=0: slot order.
     int order[kMaxItemsPerLaunch];
-    for (int i = 0; i < n_here; ++i) order[i] = i;
-    if (ctx->sort_items)
-      std::stable_sort(order, order + n_here, [&](int a, int b) {
-        const TickItem &x = items[first + (size_t)a], &y = items[first + (size_t)b];
-        const int kx = x.res_blocks ? item_res_steps(x) : 0, ky = y.res_blocks ? item_res_steps(y) : 0;
-        return kx > ky;
-      });
+    tick_items_order(items.data() + first, n_here, ctx->sort_items, ctx->share_placement, order);
     for (int i = 0; i < n_here; ++i) {
       ta.items[i] = items[first + (size_t)order[i]];
       max_blocks = std::max(max_blocks, (int)ta.items[i].res_blocks + (int)ta.items[i].ll_blocks);
@@ -748,7 +744,7 @@ int submit_tick(dvo_amd_context *ctx, std::vector<Job> &jobs, GroupTick &grp) {
       if (es != hipErrorNotSupported) return fail_hip("launch_tick", es);
       (void)hipGetLastError();  // DVO_AMD_ACCUM=valu selected the register form: the full-size launch below
     }
-    (void)tick_args_layout(ta, max_blocks);
+    (void)tick_args_layout(ta, max_blocks, ctx->share_placement);
     hipError_t e = launch_tick(ta, max_blocks, st, t0, t1);
     if (e != hipSuccess) return fail_hip("launch_tick", e);
     static_assert(kMaxFinItems >= kMaxItemsPerLaunch, "one reduce launch per tick launch");
@@ -1212,6 +1208,7 @@ int dvo_amd_context_create(int device, const dvo_amd_config *cfg, dvo_amd_contex
   const char *fp = getenv("DVO_AMD_FIN_PRIORITY");
   ctx->fin_priority = !(fp && fp[0] == '0');
   if (const char *so = getenv("DVO_AMD_SORT_ITEMS")) ctx->sort_items = so[0] != '0';
+  if (const char *sp = getenv("DVO_AMD_SHARE_PLACEMENT")) ctx->share_placement = sp[0] == '0' ? 0 : sp[0] == '2' ? 2 : 1;
   const char *sa = getenv("DVO_AMD_SMALL_ARGS");
   ctx->small_args = !(sa && sa[0] == '0');
   const char *hp = getenv("DVO_AMD_HOST_PROF");

@@ -197,16 +197,36 @@ static_assert(sizeof(Q7Rec) == 768, "Q7Rec: three 256-byte lines of the slot's b
 constexpr int kRcpNibbleWordsMax = 512;  // 2^12 cells: what fits beside four blocks' staging areas in a CU's LDS
 struct TickArgs {
   int n_items;
-  int compact;  // 0: grid (blocks of the largest item, n_items); 1: one-dimensional grid without the blocks no item owns
+  int compact;  // 0: grid (blocks of the largest item, n_items); 1: one-dimensional grid without the blocks no item owns;
+                // 2: ... in which some sets are dispatched interleaved (set_size)
   RcpTable rcp;
   // compact grid: item i owns block groups [group_first[i], group_first[i + 1]) of 8 blocks each (its blocks start on a
   // multiple of 8, so that "blocks b and b + 8 share an XCD" holds inside every item)
   uint16_t group_first[kMaxItemsPerLaunch + 4];
   // Workgroup i of a launch runs on XCD i mod 8, and an item's blocks start on a multiple of 8: without more, the blocks that
   // exist only on some XCDs (the item's count is no multiple of 8; its likelihood blocks are lighter than its residual blocks)
-  // always favour the same XCDs.  xcd_rot[i] rotates item i's blocks within their groups of eight -- block b of the grid does
-  // the work of block (b & ~7) | ((b + rot) & 7) -- chosen by tick_args_layout so that the XCDs' shares of the launch even out.
+  // always favour the same XCDs.  Two rotations per item undo that -- block b of the grid does the work of block
+  // (b & ~7) | ((b + rot) & 7): xcd_rot[i] for the item's full groups of eight residual blocks, tail_rot[i] for everything behind
+  // them (the last, partial group of residual blocks and the likelihood blocks).  The full groups load every XCD alike, so only
+  // the tails decide the XCDs' shares; what xcd_rot decides is WHICH eighth of the item's segments (xcd_contiguous_block) an
+  // XCD works on, i.e. which lines of the item's reference arrays and gather planes pass through its L2.
+  //   share placement off: one rotation per item for all of its blocks (tail_rot = xcd_rot), chosen greedily in launch order
+  //     so that the XCDs' shares even out; two items of equal shape get different rotations.
+  //   share placement on: the items of a set -- neighbours in launch order with the same reference level and geometry, see
+  //     tick_args_layout -- share xcd_rot, so that eighth r of every member meets the others' in one L2.  The balancer picks one
+  //     rotation per set; where that leaves the shares more than 2 % apart, every full group of the launch stays unrotated
+  //     (aligned across sets too: pairs of different keyframes share their current frame's planes) and the balancer rotates
+  //     the tails alone, item by item.
   uint8_t xcd_rot[kMaxItemsPerLaunch + 2] = {};
+  uint8_t tail_rot[kMaxItemsPerLaunch + 2] = {};
+  // Interleaved dispatch of a set (compact grid only): set_size[i] = m > 1 at the set's FIRST item i makes the m members one
+  // super-item of m x (the largest member's groups) block groups starting at group_first[i]; group g of it is group g / m of
+  // member i + g % m, so that segment p of all members is dispatched back to back on the same XCDs.  The other members carry
+  // set_size 1 and group_first = the set's end (they own no range of their own); blocks past a member's own count exit at once.
+  // set_inv[i] = ceil(2^32 / m): g / m = (g * set_inv) >> 32 exactly for g < 2^32 / m.
+  uint8_t set_size[kMaxItemsPerLaunch + 2] = {};
+  uint32_t set_inv[kMaxItemsPerLaunch] = {};
+  static constexpr bool kSets = true;
   TickItem items[kMaxItemsPerLaunch];
 };
 static_assert(sizeof(TickArgs) <= 8192, "kernel argument block too large");
@@ -308,6 +328,8 @@ struct TickArgsSmall {
   RcpTable rcp;
   uint16_t group_first[kMaxSmallItems + 4];
   uint8_t xcd_rot[kMaxSmallItems] = {};
+  uint8_t tail_rot[kMaxSmallItems] = {};  // (= xcd_rot: at most eight pairs have no sets worth placing)
+  static constexpr bool kSets = false;
   TickItem items[kMaxSmallItems];
 };
 struct FinArgsSmall {
@@ -324,9 +346,18 @@ struct FinArgsSmall {
 // grid: args.compact ? (args.group_first[n_items] * 8) blocks : (max_blocks rounded up to 8, n_items)
 hipError_t launch_tick(const TickArgs &args, int max_blocks, hipStream_t stream, hipEvent_t t_start = nullptr,
                        hipEvent_t t_stop = nullptr);
-// fills group_first / compact from the items' block counts; returns the number of blocks of the compact grid
-int tick_args_layout(TickArgs &args, int max_blocks);
+// fills group_first / compact / the rotations / the sets from the items' block counts; returns the number of blocks of the
+// compact grid.  share: 0 = every item placed on its own, 1 = sets share a rotation, 2 = ... and are dispatched interleaved
+// (DVO_AMD_SHARE_PLACEMENT; the small argument block has no sets).
+int tick_args_layout(TickArgs &args, int max_blocks, int share = 0);
 int tick_args_layout(TickArgsSmall &args, int max_blocks);
+// The launch order of a tick's items: order[k] = index of the item that goes k-th.  Longest-lived blocks first (the most steps
+// per wave segment); with share placement, inside such a class the items of one reference level next to each other and by
+// current level inside that run.  A pure function of the items.  sort = false: 0 .. n - 1.
+void tick_items_order(const TickItem *items, int n, bool sort, int share, int *order);
+// which item owns block `block` of the compact grid and which of the item's blocks it is (the host's restatement of k_tick's
+// tick_locate, same arithmetic); -1 for a block no item owns
+int tick_args_locate(const TickArgs &args, unsigned block, int *bx);
 // the same kernels with the small argument blocks (only the default k_tick form: returns hipErrorNotSupported when
 // DVO_AMD_ACCUM=valu selected the register form, and the caller falls back to the full-size launch)
 hipError_t launch_tick_small(const TickArgsSmall &args, int max_blocks, hipStream_t stream, hipEvent_t t_start = nullptr,

@@ -38,6 +38,20 @@ int dvo_amd_debug_combine_bands(int n_bands, const double *bands, double *out);
 unsigned dvo_amd_debug_next_seq(unsigned seq);
 int dvo_amd_debug_wire_layout(int *n_pieces, int *n_record_words);
 int dvo_amd_debug_take_wire(const unsigned *wire, unsigned tick, int from_piece, unsigned *record_words);
+/* host-only: where the blocks of one k_tick launch go (csrc/dvo_kernels.hip: tick_items_order, tick_args_layout and the host's
+ * restatement of tick_locate), for a synthetic list of `n_items` (<= 62) work items.  Item i: res_blocks[i] residual blocks
+ * of res_steps[i] steps per wave segment (one of the lengths a level can have: a power of two up to 64, or 6, 10, 12, 14, 18,
+ * 20, 24, 30, 40) and ll_blocks[i] likelihood blocks; ref_key[i] / cur_key[i] name its reference level and its current level
+ * (items with equal keys read the same arrays).  share: the value of DVO_AMD_SHARE_PLACEMENT (0, 1, 2); max_blocks: 0 = the
+ * largest item's.  Out: order[k] = the item that goes k-th in the launch; per POSITION k of the launch group_first[k] (n_items +
+ * 1 entries), xcd_rot[k], tail_rot[k], set_size[k]; *compact; *n_blocks = blocks of the one-dimensional grid; and, when the
+ * grid is compact and block_item / block_index are given (capacity_blocks >= *n_blocks, else an error), for every block of
+ * that grid the position of its item in the launch and which of the item's blocks it runs (-1, -1: a block that exits at once).
+ * Exported for the CPU tests. */
+int dvo_amd_debug_tick_layout(int n_items, const int *res_blocks, const int *ll_blocks, const int *res_steps, const int *ref_key,
+                              const int *cur_key, int share, int max_blocks, int *order, int *group_first, int *xcd_rot,
+                              int *tail_rot, int *set_size, int *compact, int *n_blocks, long long capacity_blocks, int *block_item,
+                              int *block_index);
 
 /* Stage-wise probe of ONE Gauss-Newton iteration body at a fixed pose (dense_tracking.cpp:271-347 without the accept test and
  * the solve): computeResidualsSse, computeWeightsSse (unit weights when precision_in is NULL = first iteration of a level,
