@@ -17,7 +17,13 @@ $(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_
 oracle:
 	$(MAKE) -C oracle
 
+# the C examples that need no input files (the tests build every example themselves, tests/test_*_adaptor.py)
+examples: $(LIB)
+	mkdir -p examples/_build
+	$(CC) -std=c99 -Wall -Iinclude examples/keyframe_map_example.c -o examples/_build/keyframe_map_example \
+	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+
 clean:
 	rm -f $(LIB)
 
-.PHONY: all oracle clean
+.PHONY: all oracle examples clean

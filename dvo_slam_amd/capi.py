@@ -41,6 +41,8 @@ EXPORTS = [
     "dvo_amd_debug_graph_system", "dvo_amd_debug_graph_system_sparse", "dvo_amd_debug_graph_symbolic",
     "dvo_amd_debug_graph_sparse_timing", "dvo_amd_optimize_graphs_batch", "dvo_amd_debug_graph_batch_records",
     "dvo_amd_debug_tick_layout",
+    "dvo_amd_map_create", "dvo_amd_map_destroy", "dvo_amd_map_insert", "dvo_amd_map_set_poses", "dvo_amd_map_remove",
+    "dvo_amd_map_stats", "dvo_amd_map_extract", "dvo_amd_debug_keyframe_map_timing",
 ]
 
 
@@ -222,6 +224,16 @@ def lib():
     L.dvo_amd_voxel_downsample.argtypes = [vp, C.c_longlong, vp, C.c_float, vp, C.c_longlong, C.POINTER(CCloudStats)]
     L.dvo_amd_write_pcd.argtypes = [C.c_char_p, vp, C.c_longlong, C.c_int, C.c_int]
     L.dvo_amd_debug_map_timing.argtypes = [vp, dp, dp, C.POINTER(C.c_longlong)]
+    L.dvo_amd_map_create.argtypes = [vp, C.c_float, C.POINTER(vp)]
+    L.dvo_amd_map_destroy.argtypes = [vp]
+    L.dvo_amd_map_destroy.restype = None
+    L.dvo_amd_map_insert.argtypes = [vp, C.c_int, vp, dp, vp, C.c_int]
+    L.dvo_amd_map_set_poses.argtypes = [vp, C.c_int, C.POINTER(C.c_int), dp]
+    L.dvo_amd_map_remove.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
+    L.dvo_amd_map_stats.argtypes = [vp, C.POINTER(CCloudStats), C.POINTER(C.c_int)]
+    L.dvo_amd_map_extract.argtypes = [vp, C.POINTER(C.c_float), vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.dvo_amd_debug_keyframe_map_timing.argtypes = [vp, dp, dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                                    C.POINTER(C.c_int)]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -870,6 +882,85 @@ class DenseTracker:
         n = C.c_longlong()
         _check(lib().dvo_amd_kernel_timing(self._h, int(enable), C.byref(ms), C.byref(n), int(reset)), "kernel_timing")
         return ms.value, n.value
+
+
+class KeyframeMap:
+    """The keyframe map kept on the device (dvo_amd_map_*): keyframes are inserted, moved and removed one event at a time and
+    extract() always equals DenseTracker.map_cloud over the keyframes now in the map, bit for bit.  Bound to `tracker`'s
+    context (its stream and buffers); the tracker is kept alive by the map."""
+
+    def __init__(self, tracker: "DenseTracker", leaf: float = 0.01):
+        self._trk = tracker
+        self._h = C.c_void_p()
+        _check(lib().dvo_amd_map_create(tracker._h, leaf, C.byref(self._h)), "dvo_amd_map_create")
+        self.leaf = leaf
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h and getattr(self._trk, "_h", None):
+            lib().dvo_amd_map_destroy(h)
+            self._h = None
+
+    def insert(self, id: int, pyramid: "RgbdImagePyramid", pose=None, bgr=None):
+        """level 0 of `pyramid` at `pose` (4x4, None = identity), coloured from `bgr` (uint8 HxWx3, None = grey).  The map retains
+        the pyramid and copies the image: both may be dropped right after the call."""
+        ptr, stride = None, 0
+        if bgr is not None:
+            w, h, _ = pyramid.level_info(0)
+            bgr = np.ascontiguousarray(bgr, dtype=np.uint8)
+            if bgr.shape != (h, w, 3):
+                raise ValueError(f"bgr must be ({h}, {w}, 3) uint8")
+            ptr, stride = bgr.ctypes.data, w * 3
+        T = None if pose is None else _pose_cm(pose)
+        _check(lib().dvo_amd_map_insert(self._h, id, pyramid._h, None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)),
+                                        ptr, stride), "dvo_amd_map_insert")
+
+    def set_poses(self, ids, poses):
+        """new poses (4x4 each) of the keyframes `ids`, in one update"""
+        ids = [int(i) for i in ids]
+        if len(poses) != len(ids):
+            raise ValueError("one pose per id")
+        n = len(ids)
+        arr = (C.c_int * max(1, n))(*ids)
+        T = np.ascontiguousarray(np.stack([_pose_cm(P) for P in poses])) if n else np.zeros((1, 4, 4))
+        _check(lib().dvo_amd_map_set_poses(self._h, n, arr, T.ctypes.data_as(C.POINTER(C.c_double))), "dvo_amd_map_set_poses")
+
+    def remove(self, ids):
+        ids = [int(i) for i in ids]
+        arr = (C.c_int * max(1, len(ids)))(*ids)
+        _check(lib().dvo_amd_map_remove(self._h, len(ids), arr), "dvo_amd_map_remove")
+
+    def stats(self) -> dict:
+        """the stats dict DenseTracker.map_cloud returns for the keyframes now in the map, and "keyframes" """
+        st, n = CCloudStats(), C.c_int()
+        _check(lib().dvo_amd_map_stats(self._h, C.byref(st), C.byref(n)), "dvo_amd_map_stats")
+        return {"points_in": st.points_in, "finite": st.finite, "out_of_range": st.out_of_range, "voxels": st.voxels,
+                "keyframes": n.value}
+
+    def extract(self, box=None):
+        """(xyz float32 [V, 3], rgb uint32 [V]) in voxel-key order; box = (xmin, ymin, zmin, xmax, ymax, zmax) keeps the voxels
+        whose centroid lies in [min, max) on every axis"""
+        bx = None
+        if box is not None:
+            bx = np.ascontiguousarray(box, dtype=np.float32).reshape(6)
+        bp = None if bx is None else _fp(bx)
+        n = C.c_longlong()
+        cap = self.stats()["voxels"] if box is None else 0
+        out = np.empty((max(1, cap), 4), np.float32)
+        rc = lib().dvo_amd_map_extract(self._h, bp, out.ctypes.data, cap, C.byref(n))
+        if rc == 7:  # DVO_AMD_ERR_CAPACITY: n is the size needed
+            cap = int(n.value)
+            out = np.empty((max(1, cap), 4), np.float32)
+            rc = lib().dvo_amd_map_extract(self._h, bp, out.ctypes.data, cap, C.byref(n))
+        _check(rc, "dvo_amd_map_extract")
+        return _split_points(out[:n.value])
+
+    def timing(self):
+        """(diagnostic) the last call: (device ms of its kernels, ms of the output copy, delta points, delta voxels, merge tile)"""
+        d, c, p, v, t = C.c_double(), C.c_double(), C.c_longlong(), C.c_longlong(), C.c_int()
+        _check(lib().dvo_amd_debug_keyframe_map_timing(self._h, C.byref(d), C.byref(c), C.byref(p), C.byref(v), C.byref(t)),
+               "dvo_amd_debug_keyframe_map_timing")
+        return d.value, c.value, p.value, v.value, t.value
 
 
 def se3_exp(xi) -> np.ndarray:

@@ -9,6 +9,11 @@
 //   k_heads        first position of every run of equal keys -> (scan) the voxel index of every sorted position
 //   k_accum        runs of a sorted chunk summed in registers, flushed into the voxel's integer sums with u64 atomics
 //   k_voxel_out    centroid and colour of every voxel from its integer sums
+// The map kept on the device (dvo_amd_map_*): the same input stage and sort with a sign per image, then
+//   k_delta_keys   the 63-bit key of every voxel of the sorted, signed delta
+//   k_merge        merge path over (store, delta), both in key order: sums of equal keys added, voxels left without points flagged
+//   k_compact      the flagged positions into the other store buffer
+//   k_box_flags / k_box_compact   the box rule of dvo_amd_map_extract on the output points, order kept
 // Every sum is an integer sum: the result does not depend on the order points arrive in, on the compaction order or on the
 // launch geometry -- bit for bit.
 #include <climits>
@@ -29,6 +34,9 @@ constexpr int kScanTile = kBlock * 16;            // items per block of the gene
 constexpr int kAccumChunk = 16;                   // sorted positions one k_accum thread sums before it flushes
 constexpr int kIndexBias = 1 << 20;               // voxel index range [-2^20, 2^20)
 constexpr double kFix = 16777216.0;               // 2^24: the fixed point of the centroid sums
+constexpr unsigned kNegBit = 0x80000000u;         // top bit of a value index: the point counts with sign -1 (k_accum)
+constexpr int kMergeItems = 8;                    // merged entries per thread of a merge tile
+constexpr int kMergeTile = kBlock * kMergeItems;  // 2048 entries of store + delta per k_merge block
 // At most 2^31 points per call: every position the kernels form in 32 bits (a radix tile's t0 + c * 256 + tid, a k_accum
 // chunk's start) then stays below 2^31 + 2^16 and cannot wrap.
 
@@ -38,6 +46,7 @@ struct MapImage {
   const unsigned char *bgr;  // device, tight (w * 3 bytes per row); null: grey from the intensity plane
   int w, h;
   float T[12];               // rows 0..2 of (float)pose, row-major
+  unsigned neg;              // 0, or kNegBit: the image's points are subtracted (the delta of a persistent map)
 };
 
 struct MapCtrl {
@@ -150,7 +159,8 @@ __device__ __forceinline__ unsigned long long compact_slot(bool keep, MapCtrl *c
 
 // aggregate input from images: grid (blocks over the largest image, images)
 __global__ void __launch_bounds__(kBlock) k_map_keys(const MapImage *images, int image0, float inv, float4 *pts,
-                                                     unsigned long long *keys, unsigned *vals, MapCtrl *ctrl) {
+                                                     unsigned long long *keys, unsigned *vals, MapCtrl *ctrl,
+                                                     unsigned long long *per_image) {
   const MapImage im = images[image0 + blockIdx.y];
   const long long n = (long long)im.w * im.h;
   Counts cnt;
@@ -166,7 +176,14 @@ __global__ void __launch_bounds__(kBlock) k_map_keys(const MapImage *images, int
     unsigned long long key;
     key_and_count(pt, inv, active, cnt, keep, key);
     const unsigned long long slot = compact_slot(keep, ctrl);
-    if (keep) pts[slot] = pt, keys[slot] = key, vals[slot] = (unsigned)slot;
+    if (keep) pts[slot] = pt, keys[slot] = key, vals[slot] = (unsigned)slot | im.neg;
+  }
+  if (per_image) {  // (finite, out of range) of every image on its own: the totals a persistent map keeps per keyframe
+    const unsigned long long fin = wave_sum(cnt.finite), oor = wave_sum(cnt.out_of_range);
+    if ((threadIdx.x & 63) == 0) {
+      if (fin) atomicAdd(&per_image[2 * (size_t)(image0 + blockIdx.y)], fin);
+      if (oor) atomicAdd(&per_image[2 * (size_t)(image0 + blockIdx.y) + 1], oor);
+    }
   }
   flush_counts(cnt, ctrl);
 }
@@ -320,15 +337,16 @@ __global__ void __launch_bounds__(kBlock) k_heads(const unsigned long long *keys
     flags[p] = (p == 0 || keys[p] != keys[p - 1]) ? 1u : 0u;
 }
 
-__device__ __forceinline__ void flush(VoxelAcc *acc, unsigned n_vox, unsigned v, unsigned long long cnt, const long long s[3],
-                                      const unsigned long long c[3]) {
+__device__ __forceinline__ void flush(VoxelAcc *acc, unsigned n_vox, unsigned v, unsigned long long cnt,
+                                      const unsigned long long s[3], const unsigned long long c[3]) {
   if (v >= n_vox) return;  // (never: v < the number of heads)
   VoxelAcc *a = acc + v;
   atomicAdd(&a->count, cnt);
-  for (int q = 0; q < 3; ++q) atomicAdd(&a->s[q], (unsigned long long)s[q]), atomicAdd(&a->c[q], c[q]);
+  for (int q = 0; q < 3; ++q) atomicAdd(&a->s[q], s[q]), atomicAdd(&a->c[q], c[q]);
 }
 
-// vidx = the exclusive scan of the head flags: the voxel of sorted position p is vidx[p] + flag(p) - 1; sums wrap modulo 2^64
+// vidx = the exclusive scan of the head flags: the voxel of sorted position p is vidx[p] + flag(p) - 1; sums wrap modulo 2^64.
+// A value index with kNegBit set subtracts its point: the count and every sum take the sign in integers (modulo 2^64).
 __global__ void __launch_bounds__(kBlock) k_accum(const unsigned long long *keys, const unsigned *vals, const unsigned *vidx,
                                                   unsigned n, const float4 *pts, VoxelAcc *acc, unsigned n_vox) {
   const unsigned p0 = (blockIdx.x * kBlock + threadIdx.x) * kAccumChunk;
@@ -336,8 +354,7 @@ __global__ void __launch_bounds__(kBlock) k_accum(const unsigned long long *keys
   const unsigned p1 = min(n, p0 + kAccumChunk);
   unsigned long long key = keys[p0];
   unsigned vox = vidx[p0] + ((p0 == 0 || keys[p0 - 1] != key) ? 1u : 0u) - 1u;
-  unsigned long long cnt = 0, c[3] = {0, 0, 0};
-  long long s[3] = {0, 0, 0};
+  unsigned long long cnt = 0, c[3] = {0, 0, 0}, s[3] = {0, 0, 0};
   for (unsigned p = p0; p < p1; ++p) {
     const unsigned long long k = keys[p];
     if (k != key) {
@@ -345,11 +362,19 @@ __global__ void __launch_bounds__(kBlock) k_accum(const unsigned long long *keys
       key = k, ++vox, cnt = 0;
       for (int q = 0; q < 3; ++q) s[q] = 0, c[q] = 0;
     }
-    const float4 pt = pts[vals[p]];
+    const unsigned val = vals[p];
+    const float4 pt = pts[val & ~kNegBit];
     const unsigned rgb = __float_as_uint(pt.w);
-    s[0] += llrint((double)pt.x * kFix), s[1] += llrint((double)pt.y * kFix), s[2] += llrint((double)pt.z * kFix);
-    c[0] += (rgb >> 16) & 0xFF, c[1] += (rgb >> 8) & 0xFF, c[2] += rgb & 0xFF;
-    ++cnt;
+    const unsigned long long q[3] = {(unsigned long long)llrint((double)pt.x * kFix), (unsigned long long)llrint((double)pt.y * kFix),
+                                     (unsigned long long)llrint((double)pt.z * kFix)};
+    const unsigned long long ch[3] = {(rgb >> 16) & 0xFF, (rgb >> 8) & 0xFF, rgb & 0xFF};
+    if (val & kNegBit) {
+      for (int a = 0; a < 3; ++a) s[a] -= q[a], c[a] -= ch[a];
+      --cnt;
+    } else {
+      for (int a = 0; a < 3; ++a) s[a] += q[a], c[a] += ch[a];
+      ++cnt;
+    }
   }
   flush(acc, n_vox, vox, cnt, s, c);
 }
@@ -365,6 +390,136 @@ __global__ void __launch_bounds__(kBlock) k_voxel_out(const VoxelAcc *acc, unsig
       ch[q] = (unsigned)((a.c[q] + a.count / 2) / a.count);
     }
     out[v] = make_float4(xyz[0], xyz[1], xyz[2], __uint_as_float((ch[0] << 16) | (ch[1] << 8) | ch[2]));
+  }
+}
+
+// ---- the persistent keyframe map (dvo_amd_map_*) ---------------------------------------------------------------------------
+// The store holds the occupied voxels in ascending 63-bit key order: keys[n], VoxelAcc[n].  One call's delta (signed points
+// through k_map_keys, the sort, k_accum) is one signed VoxelAcc per touched voxel in key order; k_merge merges the two sorted
+// sequences, k_compact drops the voxels whose count has become 0.
+
+// the 63-bit key of every voxel of a sorted delta, from the dense key of its first point
+__global__ void __launch_bounds__(kBlock) k_delta_keys(const unsigned long long *keys, const unsigned *vidx, unsigned n, Rekey r,
+                                                       unsigned long long *vkeys, unsigned n_vox) {
+  for (unsigned p = blockIdx.x * kBlock + threadIdx.x; p < n; p += gridDim.x * kBlock) {
+    const unsigned long long k = keys[p];
+    if (p != 0 && keys[p - 1] == k) continue;
+    const unsigned v = vidx[p];  // heads before p
+    if (v >= n_vox) continue;    // (never)
+    const unsigned long long i = k >> r.sh_i, j = (k >> r.sh_j) & ((1ull << (r.sh_i - r.sh_j)) - 1ull), kk = k & ((1ull << r.sh_j) - 1ull);
+    vkeys[v] = ((i + (unsigned long long)(r.mn[0] + kIndexBias)) << 42) | ((j + (unsigned long long)(r.mn[1] + kIndexBias)) << 21) |
+               (kk + (unsigned long long)(r.mn[2] + kIndexBias));
+  }
+}
+
+// merge path: how many of the first d merged entries come from a (ties: a first)
+__device__ __forceinline__ unsigned merge_split(const unsigned long long *a, unsigned na, const unsigned long long *b, unsigned nb,
+                                                unsigned d) {
+  unsigned lo = d > nb ? d - nb : 0u, hi = min(d, na);
+  while (lo < hi) {
+    const unsigned mid = (lo + hi) >> 1;
+    if (a[mid] <= b[d - mid - 1]) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+constexpr unsigned kNoMatch = 0xFFFFFFFFu, kDead = 0xFFFFFFFEu;
+
+// Merges the store (ka, va: na entries) and the delta (kb, vb: nb entries), both in ascending order of distinct keys, into
+// na + nb merged positions.  A store entry takes the sums of the delta entry of its key (the next merged position); that delta
+// entry is dead.  flags[o] = 1 where position o holds a voxel with a count other than 0.  Every position has one writer: the
+// block whose tile it lies in, found by a binary search along the tile's diagonals; no atomics.  Four lanes move one 64-byte
+// entry, 16 bytes each.
+__global__ void __launch_bounds__(kBlock) k_merge(const unsigned long long *ka, const VoxelAcc *va, unsigned na,
+                                                  const unsigned long long *kb, const VoxelAcc *vb, unsigned nb,
+                                                  unsigned long long *ko, VoxelAcc *vo, unsigned *flags) {
+  __shared__ unsigned long long sk[kMergeTile + 2];  // a[a0 - 1] | a[a0, a1) | b[b0, b1) | b[b1]
+  __shared__ unsigned s_src[kMergeTile], s_match[kMergeTile], s_split[2];
+  const unsigned total = na + nb;
+  const unsigned d0 = blockIdx.x * (unsigned)kMergeTile, d1 = min(total, d0 + (unsigned)kMergeTile);
+  if (threadIdx.x < 2) s_split[threadIdx.x] = merge_split(ka, na, kb, nb, threadIdx.x ? d1 : d0);
+  __syncthreads();
+  const unsigned a0 = s_split[0], a1 = s_split[1], b0 = d0 - a0, b1 = d1 - a1;
+  const unsigned la = a1 - a0, lb = b1 - b0, len = d1 - d0;
+  unsigned long long *sa = sk + 1, *sb = sk + 1 + la;
+  for (unsigned e = threadIdx.x; e < la; e += kBlock) sa[e] = ka[a0 + e];
+  for (unsigned e = threadIdx.x; e < lb; e += kBlock) sb[e] = kb[b0 + e];
+  if (threadIdx.x == 0) {
+    sk[0] = a0 > 0 ? ka[a0 - 1] : ~0ull;      // (~0 is no key: keys have 63 bits)
+    sb[lb] = b1 < nb ? kb[b1] : ~0ull;
+  }
+  __syncthreads();
+  const unsigned dl = min(threadIdx.x * (unsigned)kMergeItems, len);
+  unsigned a = merge_split(sa, la, sb, lb, dl), b = dl - a;
+  for (int it = 0; it < kMergeItems; ++it) {
+    const unsigned o = dl + it;
+    if (o >= len) break;
+    if (a < la && (b >= lb || sa[a] <= sb[b])) {
+      s_src[o] = a0 + a;
+      s_match[o] = sb[b] == sa[a] ? b0 + b : kNoMatch;  // sb[lb]: the first delta key of the next tile
+      ++a;
+    } else {
+      s_src[o] = (b0 + b) | kNegBit;
+      s_match[o] = sa[(int)a - 1] == sb[b] ? kDead : kNoMatch;  // sa[-1]: the last store key of the tile before
+      ++b;
+    }
+  }
+  __syncthreads();
+  const unsigned part = threadIdx.x & 3;
+  for (unsigned e = threadIdx.x >> 2; e < len; e += kBlock / 4) {
+    const unsigned src = s_src[e], mt = s_match[e], o = d0 + e;
+    if (mt == kDead) {
+      if (part == 0) flags[o] = 0u;
+      continue;
+    }
+    const bool from_b = (src & kNegBit) != 0;
+    const unsigned at = src & ~kNegBit;
+    ulonglong2 v = ((const ulonglong2 *)(from_b ? vb + at : va + at))[part];
+    if (mt != kNoMatch) {
+      const ulonglong2 w = ((const ulonglong2 *)(vb + mt))[part];
+      v.x += w.x, v.y += w.y;
+    }
+    ((ulonglong2 *)(vo + o))[part] = v;
+    if (part == 0) {
+      flags[o] = v.x != 0ull ? 1u : 0u;  // v.x: the count
+      ko[o] = from_b ? sb[at - b0] : sa[at - a0];
+    }
+  }
+}
+
+// ex = the exclusive scan of k_merge's flags, *grand its total: the flagged positions move to ex[o] of the other store buffer
+__global__ void __launch_bounds__(kBlock) k_compact(const unsigned long long *ki, const VoxelAcc *vi, const unsigned *ex,
+                                                    const unsigned *grand, unsigned total, unsigned long long *ko, VoxelAcc *vo) {
+  const unsigned part = threadIdx.x & 3;
+  for (unsigned long long t = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; t < 4ull * total;
+       t += (unsigned long long)gridDim.x * kBlock) {
+    const unsigned o = (unsigned)(t >> 2);
+    const unsigned at = ex[o], next = o + 1 < total ? ex[o + 1] : *grand;
+    if (next == at || at >= total) continue;
+    ((ulonglong2 *)(vo + at))[part] = ((const ulonglong2 *)(vi + o))[part];
+    if (part == 0) ko[at] = ki[o];
+  }
+}
+
+struct Box {
+  float mn[3], mx[3];
+};
+
+// the box rule of dvo_amd_map_extract on the output points
+__global__ void __launch_bounds__(kBlock) k_box_flags(const float4 *pts, unsigned n, Box box, unsigned *flags) {
+  for (unsigned v = blockIdx.x * kBlock + threadIdx.x; v < n; v += gridDim.x * kBlock) {
+    const float4 c = pts[v];
+    const bool in = c.x >= box.mn[0] && c.x < box.mx[0] && c.y >= box.mn[1] && c.y < box.mx[1] && c.z >= box.mn[2] && c.z < box.mx[2];
+    flags[v] = in ? 1u : 0u;
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_box_compact(const float4 *pts, const unsigned *ex, const unsigned *grand, unsigned n,
+                                                        float4 *out) {
+  for (unsigned v = blockIdx.x * kBlock + threadIdx.x; v < n; v += gridDim.x * kBlock) {
+    const unsigned at = ex[v], next = v + 1 < n ? ex[v + 1] : *grand;
+    if (next != at && at < n) out[at] = pts[v];
   }
 }
 
@@ -454,6 +609,48 @@ int scan(MapWorkspace &W, unsigned *a, unsigned n, unsigned *grand, hipStream_t 
   return DVO_AMD_OK;
 }
 
+// Sorts the m points the input stage left in keys[0] / vals[0] (c: the control block it filled, read back) by voxel key and
+// finds the voxels: *cur = the buffer pair that holds the sorted (dense key, value), W.flags = the voxel index of every sorted
+// position (k_accum), *n_vox = the voxels, *rk = how the dense keys were formed.  Events 2..3 time the segment.
+int sort_voxels(MapWorkspace &W, const map::MapCtrl &c, hipStream_t st, int *cur_out, unsigned *n_vox, map::Rekey *rk) {
+  const unsigned m = (unsigned)c.kept;
+  // the bits present: fields i | j | k of (index - min), packed densely -- order preserving
+  const int bi = bits_for(c.mx[0] - c.mn[0]), bj = bits_for(c.mx[1] - c.mn[1]), bk = bits_for(c.mx[2] - c.mn[2]);
+  map::Rekey r = {{c.mn[0], c.mn[1], c.mn[2]}, bj + bk, bk};
+  const int passes = (bi + bj + bk + map::kRadixBits - 1) / map::kRadixBits;
+  const unsigned nb = (m + map::kSortTile - 1) / map::kSortTile;
+  int rc = grow(W.counts, sizeof(unsigned) * map::kRadix * (size_t)nb);
+  // the scan scratch for the larger of the two scans (the digit table, the head flags), before anything is enqueued
+  if (!rc) rc = grow(W.bsum, sizeof(unsigned) * (std::max<size_t>((size_t)map::kRadix * nb, m) / map::kScanTile + 1));
+  if (rc) return rc;
+  unsigned long long *keys[2] = {(unsigned long long *)W.keys[0].p, (unsigned long long *)W.keys[1].p};
+  unsigned *vals[2] = {(unsigned *)W.vals[0].p, (unsigned *)W.vals[1].p};
+  unsigned *counts = (unsigned *)W.counts.p;
+  map::MapCtrl *dctrl = (map::MapCtrl *)W.ctrl.p;
+  HIP_TRY(hipEventRecord(W.ev[2], st));
+  hipLaunchKernelGGL(map::k_rekey, dim3(map::grid_for(m, map::kBlock)), dim3(map::kBlock), 0, st, keys[0], (unsigned long long)m, r);
+  int cur = 0;
+  for (int pass = 0; pass < passes; ++pass) {
+    const int shift = pass * map::kRadixBits;
+    hipLaunchKernelGGL(map::k_radix_hist, dim3(nb), dim3(map::kBlock), 0, st, keys[cur], m, shift, counts);
+    rc = scan(W, counts, map::kRadix * nb, nullptr, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(map::k_radix_scatter, dim3(nb), dim3(map::kBlock), 0, st, keys[cur], vals[cur], keys[cur ^ 1],
+                       vals[cur ^ 1], m, shift, (const unsigned *)counts);
+    cur ^= 1;
+  }
+  unsigned *flags = (unsigned *)W.flags.p;
+  hipLaunchKernelGGL(map::k_heads, dim3(map::grid_for(m, map::kBlock)), dim3(map::kBlock), 0, st, keys[cur], m, flags);
+  rc = scan(W, flags, m, &dctrl->voxels, st);
+  if (rc) return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(W.ev[3], st));
+  HIP_TRY(hipMemcpyAsync(n_vox, &dctrl->voxels, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  *cur_out = cur, *rk = r;
+  return DVO_AMD_OK;
+}
+
 // The aggregate of the m points the input stage left in keys[0] / vals[0] (c: the control block it filled, read back): sorts,
 // finds the voxels, checks the capacity, reduces and copies the voxels to `out`.  Events 2..5 time the two kernel segments.
 int reduce_voxels(MapWorkspace &W, const map::MapCtrl &c, const float4 *pts, dvo_amd_point *out, long long capacity,
@@ -461,39 +658,13 @@ int reduce_voxels(MapWorkspace &W, const map::MapCtrl &c, const float4 *pts, dvo
   const unsigned m = (unsigned)c.kept;
   unsigned n_vox = 0;
   if (m > 0) {
-    // the bits present: fields i | j | k of (index - min), packed densely -- order preserving
-    const int bi = bits_for(c.mx[0] - c.mn[0]), bj = bits_for(c.mx[1] - c.mn[1]), bk = bits_for(c.mx[2] - c.mn[2]);
-    map::Rekey r = {{c.mn[0], c.mn[1], c.mn[2]}, bj + bk, bk};
-    const int passes = (bi + bj + bk + map::kRadixBits - 1) / map::kRadixBits;
-    const unsigned nb = (m + map::kSortTile - 1) / map::kSortTile;
-    int rc = grow(W.counts, sizeof(unsigned) * map::kRadix * (size_t)nb);
-    // the scan scratch for the larger of the two scans (the digit table, the head flags), before anything is enqueued
-    if (!rc) rc = grow(W.bsum, sizeof(unsigned) * (std::max<size_t>((size_t)map::kRadix * nb, m) / map::kScanTile + 1));
-    if (rc) return rc;
-    unsigned long long *keys[2] = {(unsigned long long *)W.keys[0].p, (unsigned long long *)W.keys[1].p};
-    unsigned *vals[2] = {(unsigned *)W.vals[0].p, (unsigned *)W.vals[1].p};
-    unsigned *counts = (unsigned *)W.counts.p;
-    map::MapCtrl *dctrl = (map::MapCtrl *)W.ctrl.p;
-    HIP_TRY(hipEventRecord(W.ev[2], st));
-    hipLaunchKernelGGL(map::k_rekey, dim3(map::grid_for(m, map::kBlock)), dim3(map::kBlock), 0, st, keys[0], (unsigned long long)m, r);
     int cur = 0;
-    for (int pass = 0; pass < passes; ++pass) {
-      const int shift = pass * map::kRadixBits;
-      hipLaunchKernelGGL(map::k_radix_hist, dim3(nb), dim3(map::kBlock), 0, st, keys[cur], m, shift, counts);
-      rc = scan(W, counts, map::kRadix * nb, nullptr, st);
-      if (rc) return rc;
-      hipLaunchKernelGGL(map::k_radix_scatter, dim3(nb), dim3(map::kBlock), 0, st, keys[cur], vals[cur], keys[cur ^ 1],
-                         vals[cur ^ 1], m, shift, (const unsigned *)counts);
-      cur ^= 1;
-    }
-    unsigned *flags = (unsigned *)W.flags.p;
-    hipLaunchKernelGGL(map::k_heads, dim3(map::grid_for(m, map::kBlock)), dim3(map::kBlock), 0, st, keys[cur], m, flags);
-    rc = scan(W, flags, m, &dctrl->voxels, st);
+    map::Rekey r;
+    int rc = sort_voxels(W, c, st, &cur, &n_vox, &r);
     if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(W.ev[3], st));
-    HIP_TRY(hipMemcpyAsync(&n_vox, &dctrl->voxels, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    const unsigned long long *const keys[2] = {(unsigned long long *)W.keys[0].p, (unsigned long long *)W.keys[1].p};
+    const unsigned *const vals[2] = {(unsigned *)W.vals[0].p, (unsigned *)W.vals[1].p};
+    const unsigned *flags = (unsigned *)W.flags.p;
     if ((long long)n_vox <= capacity && out) {
       rc = grow(W.acc, sizeof(map::VoxelAcc) * (size_t)n_vox);
       if (!rc) rc = grow(W.out, sizeof(float4) * (size_t)n_vox);
@@ -575,7 +746,7 @@ int upload_images(MapWorkspace &W, int n, dvo_amd_pyramid *const *images, int le
   for (int k = 0; k < n; ++k) {
     const LevelData &L = images[k]->lv[level];
     map::MapImage &im = host[(size_t)k];
-    im.z = L.z_plane, im.i = L.i_plane, im.tx = L.tx, im.ty = L.ty, im.bgr = nullptr, im.w = L.w, im.h = L.h;
+    im.z = L.z_plane, im.i = L.i_plane, im.tx = L.tx, im.ty = L.ty, im.bgr = nullptr, im.w = L.w, im.h = L.h, im.neg = 0;
     float_pose(poses ? poses + (size_t)pose_stride * k : nullptr, im.T);
     if (bgrs && bgrs[k]) bgr_bytes += (size_t)L.w * L.h * 3;
   }
@@ -624,7 +795,466 @@ void map_workspace_release(dvo_amd_context *ctx) {
 }  // namespace host
 }  // namespace dvo_amd
 
+// ---- the persistent keyframe map ------------------------------------------------------------------------------------------
+
+struct dvo_amd_map {
+  struct Keyframe {
+    int id = 0;
+    dvo_amd_pyramid *pyr = nullptr;  // retained
+    float T[12] = {};                // the pose its contribution was generated at
+    void *bgr = nullptr;             // device, tight rows; null: grey
+    long long points = 0, finite = 0, out_of_range = 0;
+  };
+  using Buf = dvo_amd::host::MapWorkspace::Buf;
+  dvo_amd_context *ctx = nullptr;
+  float leaf = 0.0f;
+  std::vector<Keyframe> kfs;
+  Buf keys[2], acc[2];             // the store, double-buffered: keys[cur] / acc[cur] hold n voxels in ascending key order
+  Buf tkeys, tacc, flags;          // the merged sequence before compaction, its flags (and the box flags of an extract)
+  Buf dkeys, counts, images;       // the delta's keys; (finite, out of range) per image; the image descriptors
+  int cur = 0;
+  unsigned n = 0;
+  hipEvent_t ev[4] = {};
+  double device_ms = 0.0, copy_ms = 0.0;  // the last call
+  long long delta_points = 0, delta_voxels = 0;
+};
+
+namespace dvo_amd {
+namespace host {
+namespace {
+
+// one image of an update: a keyframe at a pose, added or subtracted
+struct DeltaItem {
+  const dvo_amd_map::Keyframe *kf;
+  float T[12];
+  bool negative;
+  int stats_of;  // index into the next keyframe list whose totals this pass produces; -1: none
+};
+
+// the store buffers grow geometrically: a session that gains a keyframe at a time reallocates O(log) times
+int grow_store(MapWorkspace::Buf &b, size_t bytes) { return bytes <= b.bytes ? DVO_AMD_OK : grow(b, std::max(bytes, 2 * b.bytes)); }
+
+int find_keyframe(const dvo_amd_map *M, int id) {
+  for (size_t k = 0; k < M->kfs.size(); ++k)
+    if (M->kfs[k].id == id) return (int)k;
+  return -1;
+}
+
+bool finite_pose(const double *pose) {
+  for (int e = 0; e < 16; ++e)
+    if (!std::isfinite(pose[e])) return false;
+  return true;
+}
+
+int entry_checks(const dvo_amd_map *M, const char *what) {
+  int rc = have_device();
+  if (rc) return rc;
+  if (!M) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = queue_must_be_idle(M->ctx, what);
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(M->ctx->device));
+  return DVO_AMD_OK;
+}
+
+// Applies the items to the store (from_scratch: to an empty store) and, when everything succeeded, makes `next` the keyframe
+// list.  Until then the map is untouched: the merge writes the other store buffer.
+int apply_delta(dvo_amd_map *M, const std::vector<DeltaItem> &items, bool from_scratch, std::vector<dvo_amd_map::Keyframe> &next) {
+  dvo_amd_context *ctx = M->ctx;
+  MapWorkspace *Wp = nullptr;
+  int rc = workspace(ctx, &Wp);
+  if (rc) return rc;
+  MapWorkspace &W = *Wp;
+  const hipStream_t st = ctx->stream;
+  unsigned long long total = 0;
+  int max_px = 1;
+  for (const DeltaItem &it : items) {
+    total += (unsigned long long)it.kf->points;
+    max_px = (int)std::max<long long>(max_px, it.kf->points);
+  }
+  if (total > (1ull << 31)) {
+    g_last_error = "keyframe map: more than 2^31 points in one update";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  const unsigned n_store = from_scratch ? 0u : M->n;
+  unsigned n_delta = 0, n_new = n_store;
+  double device_ms = 0.0;
+  const int n_items = (int)items.size();
+  if (n_items > 0) {
+    rc = grow_points(W, std::max<size_t>(1, total), true);
+    if (!rc) rc = grow(M->images, sizeof(map::MapImage) * (size_t)n_items);
+    if (!rc) rc = grow(M->counts, 2 * sizeof(unsigned long long) * (size_t)n_items);
+    if (rc) return rc;
+    std::vector<map::MapImage> im((size_t)n_items);
+    for (int k = 0; k < n_items; ++k) {
+      const LevelData &L = items[(size_t)k].kf->pyr->lv[0];
+      map::MapImage &d = im[(size_t)k];
+      d.z = L.z_plane, d.i = L.i_plane, d.tx = L.tx, d.ty = L.ty, d.bgr = (const unsigned char *)items[(size_t)k].kf->bgr;
+      d.w = L.w, d.h = L.h, d.neg = items[(size_t)k].negative ? map::kNegBit : 0u;
+      std::memcpy(d.T, items[(size_t)k].T, sizeof(d.T));
+    }
+    HIP_TRY(hipMemcpyAsync(M->images.p, im.data(), sizeof(map::MapImage) * (size_t)n_items, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(M->counts.p, 0, 2 * sizeof(unsigned long long) * (size_t)n_items, st));
+    rc = start_ctrl(W, st);
+    if (rc) return rc;
+    const float inv = 1.0f / M->leaf;
+    for (int k0 = 0; k0 < n_items; k0 += 65535) {
+      const int nk = std::min(65535, n_items - k0);
+      hipLaunchKernelGGL(map::k_map_keys, dim3(map::grid_for(max_px, map::kBlock, 64), nk), dim3(map::kBlock), 0, st,
+                         (const map::MapImage *)M->images.p, k0, inv, (float4 *)W.pts.p, (unsigned long long *)W.keys[0].p,
+                         (unsigned *)W.vals[0].p, (map::MapCtrl *)W.ctrl.p, (unsigned long long *)M->counts.p);
+    }
+    HIP_TRY(hipGetLastError());
+    map::MapCtrl c;
+    rc = read_ctrl(W, &c, (long long)total, nullptr, st);
+    if (rc) return rc;
+    device_ms = W.device_ms;
+    std::vector<unsigned long long> counts(2 * (size_t)n_items);
+    HIP_TRY(hipMemcpyAsync(counts.data(), M->counts.p, sizeof(unsigned long long) * counts.size(), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < n_items; ++k) {
+      const int at = items[(size_t)k].stats_of;
+      if (at < 0) continue;
+      next[(size_t)at].finite = (long long)counts[2 * (size_t)k];
+      next[(size_t)at].out_of_range = (long long)counts[2 * (size_t)k + 1];
+    }
+    if (c.kept > 0) {
+      int cur = 0;
+      map::Rekey r;
+      rc = sort_voxels(W, c, st, &cur, &n_delta, &r);
+      if (!rc) rc = grow(W.acc, sizeof(map::VoxelAcc) * (size_t)n_delta);
+      if (!rc) rc = grow(M->dkeys, sizeof(unsigned long long) * (size_t)n_delta);
+      if (rc) return rc;
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, W.ev[2], W.ev[3]));
+      device_ms += ms;
+      const unsigned m = (unsigned)c.kept;
+      map::VoxelAcc *acc = (map::VoxelAcc *)W.acc.p;
+      HIP_TRY(hipEventRecord(M->ev[0], st));
+      HIP_TRY(hipMemsetAsync(acc, 0, sizeof(map::VoxelAcc) * (size_t)n_delta, st));
+      const unsigned long long threads = ((unsigned long long)m + map::kAccumChunk - 1) / map::kAccumChunk;
+      hipLaunchKernelGGL(map::k_accum, dim3((unsigned)((threads + map::kBlock - 1) / map::kBlock)), dim3(map::kBlock), 0, st,
+                         (const unsigned long long *)W.keys[cur].p, (const unsigned *)W.vals[cur].p, (const unsigned *)W.flags.p, m,
+                         (const float4 *)W.pts.p, acc, n_delta);
+      hipLaunchKernelGGL(map::k_delta_keys, dim3(map::grid_for(m, map::kBlock)), dim3(map::kBlock), 0, st,
+                         (const unsigned long long *)W.keys[cur].p, (const unsigned *)W.flags.p, m, r,
+                         (unsigned long long *)M->dkeys.p, n_delta);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipEventRecord(M->ev[1], st));
+    }
+  }
+  const unsigned long long merged = (unsigned long long)n_store + n_delta;
+  if (merged >= (1ull << 31)) {
+    g_last_error = "keyframe map: 2^31 voxels or more";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  const bool merge = n_delta > 0;
+  if (merge) {
+    const int other = M->cur ^ 1;
+    rc = grow_store(M->keys[other], 8 * (size_t)merged);
+    if (!rc) rc = grow_store(M->acc[other], sizeof(map::VoxelAcc) * (size_t)merged);
+    if (!rc) rc = grow_store(M->tkeys, 8 * (size_t)merged);
+    if (!rc) rc = grow_store(M->tacc, sizeof(map::VoxelAcc) * (size_t)merged);
+    if (!rc) rc = grow_store(M->flags, 4 * (size_t)merged);
+    if (!rc) rc = grow(W.bsum, sizeof(unsigned) * ((size_t)merged / map::kScanTile + 1));
+    if (rc) return rc;
+    map::MapCtrl *dctrl = (map::MapCtrl *)W.ctrl.p;
+    HIP_TRY(hipEventRecord(M->ev[2], st));
+    hipLaunchKernelGGL(map::k_merge, dim3((unsigned)((merged + map::kMergeTile - 1) / map::kMergeTile)), dim3(map::kBlock), 0, st,
+                       (const unsigned long long *)M->keys[M->cur].p, (const map::VoxelAcc *)M->acc[M->cur].p, n_store,
+                       (const unsigned long long *)M->dkeys.p, (const map::VoxelAcc *)W.acc.p, n_delta,
+                       (unsigned long long *)M->tkeys.p, (map::VoxelAcc *)M->tacc.p, (unsigned *)M->flags.p);
+    rc = scan(W, (unsigned *)M->flags.p, (unsigned)merged, &dctrl->voxels, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(map::k_compact, dim3(map::grid_for(4 * merged, map::kBlock)), dim3(map::kBlock), 0, st,
+                       (const unsigned long long *)M->tkeys.p, (const map::VoxelAcc *)M->tacc.p, (const unsigned *)M->flags.p,
+                       (const unsigned *)&dctrl->voxels, (unsigned)merged, (unsigned long long *)M->keys[other].p,
+                       (map::VoxelAcc *)M->acc[other].p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(M->ev[3], st));
+    HIP_TRY(hipMemcpyAsync(&n_new, &dctrl->voxels, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float a = 0.f, b = 0.f;
+    HIP_TRY(hipEventElapsedTime(&a, M->ev[0], M->ev[1]));
+    HIP_TRY(hipEventElapsedTime(&b, M->ev[2], M->ev[3]));
+    device_ms += a + b;
+    M->cur = other;
+  } else if (from_scratch) {
+    n_new = 0;
+  }
+  M->n = n_new;
+  M->kfs.swap(next);
+  M->device_ms = device_ms, M->copy_ms = 0.0, M->delta_points = (long long)total, M->delta_voxels = n_delta;
+  return DVO_AMD_OK;
+}
+
+}  // namespace
+}  // namespace host
+}  // namespace dvo_amd
+
 extern "C" {
+
+int dvo_amd_map_create(dvo_amd_context *ctx, float leaf_size, dvo_amd_map **out) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx || !out || !host::valid_leaf(leaf_size)) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  HIP_TRY(hipSetDevice(ctx->device));
+  dvo_amd_map *M = new dvo_amd_map();
+  M->ctx = ctx, M->leaf = leaf_size;
+  for (hipEvent_t &e : M->ev) {
+    const hipError_t he = hipEventCreate(&e);
+    if (he != hipSuccess) {
+      dvo_amd_map_destroy(M);
+      return host::fail_hip("hipEventCreate (keyframe map)", he);
+    }
+  }
+  *out = M;
+  return DVO_AMD_OK;
+}
+
+void dvo_amd_map_destroy(dvo_amd_map *M) {
+  if (!M) return;
+  (void)hipSetDevice(M->ctx->device);
+  (void)hipStreamSynchronize(M->ctx->stream);
+  for (dvo_amd_map::Keyframe &k : M->kfs) {
+    if (k.bgr) (void)hipFree(k.bgr);
+    dvo_amd_pyramid_release(k.pyr);
+  }
+  for (dvo_amd_map::Buf *b : {&M->keys[0], &M->keys[1], &M->acc[0], &M->acc[1], &M->tkeys, &M->tacc, &M->flags, &M->dkeys, &M->counts,
+                              &M->images})
+    if (b->p) (void)hipFree(b->p);
+  for (hipEvent_t e : M->ev)
+    if (e) (void)hipEventDestroy(e);
+  delete M;
+}
+
+int dvo_amd_map_insert(dvo_amd_map *M, int id, dvo_amd_pyramid *image, const double *pose, const unsigned char *bgr,
+                       int bgr_stride_bytes) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!M || !image) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  rc = host::check_images(M->ctx, 1, &image, 0);
+  if (!rc) rc = host::entry_checks(M, "dvo_amd_map_insert");
+  if (rc) return rc;
+  if (host::find_keyframe(M, id) >= 0) {
+    g_last_error = "dvo_amd_map_insert: keyframe id " + std::to_string(id) + " is already in the map";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  if (pose && !host::finite_pose(pose)) {
+    g_last_error = "dvo_amd_map_insert: the pose of keyframe " + std::to_string(id) + " has a non-finite entry";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  const LevelData &L = image->lv[0];
+  const int stride = bgr_stride_bytes > 0 ? bgr_stride_bytes : L.w * 3;
+  if (bgr && stride < L.w * 3) {
+    g_last_error = "dvo_amd_map_insert: bgr_stride_bytes is smaller than a row";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  dvo_amd_map::Keyframe kf;
+  kf.id = id, kf.pyr = image, kf.points = (long long)L.w * L.h;
+  host::float_pose(pose, kf.T);
+  const hipStream_t st = M->ctx->stream;
+  if (bgr) {
+    const hipError_t e = hipMalloc(&kf.bgr, (size_t)L.w * L.h * 3);
+    if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
+    if (e != hipSuccess) return host::fail_hip("hipMalloc (keyframe map, bgr)", e);
+    const hipError_t c = hipMemcpy2DAsync(kf.bgr, (size_t)L.w * 3, bgr, (size_t)stride, (size_t)L.w * 3, L.h, hipMemcpyHostToDevice, st);
+    if (c != hipSuccess) {
+      (void)hipFree(kf.bgr);
+      return host::fail_hip("hipMemcpy2DAsync (keyframe map, bgr)", c);
+    }
+  }
+  std::vector<dvo_amd_map::Keyframe> next = M->kfs;
+  next.push_back(kf);
+  std::vector<host::DeltaItem> items(1);
+  items[0].kf = &kf, items[0].negative = false, items[0].stats_of = (int)next.size() - 1;
+  std::memcpy(items[0].T, kf.T, sizeof(kf.T));
+  rc = host::apply_delta(M, items, false, next);
+  if (rc) {
+    (void)hipStreamSynchronize(st);  // the copy of the caller's image may still be in flight
+    if (kf.bgr) (void)hipFree(kf.bgr);
+    return rc;
+  }
+  dvo_amd_pyramid_retain(image);
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_map_set_poses(dvo_amd_map *M, int n, const int *ids, const double *poses) {
+  int rc = host::entry_checks(M, "dvo_amd_map_set_poses");
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!ids || !poses))) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  std::vector<dvo_amd_map::Keyframe> next = M->kfs;
+  std::vector<int> moved;
+  std::vector<char> seen(next.size(), 0);
+  long long moved_points = 0, all_points = 0;
+  for (const dvo_amd_map::Keyframe &k : next) all_points += k.points;
+  for (int q = 0; q < n; ++q) {
+    const int at = host::find_keyframe(M, ids[q]);
+    if (at < 0 || seen[(size_t)at] || !host::finite_pose(poses + 16 * (size_t)q)) {
+      g_last_error = "dvo_amd_map_set_poses: keyframe id " + std::to_string(ids[q]) +
+                     (at < 0 ? " is not in the map" : seen[(size_t)at] ? " is given twice" : " has a non-finite pose entry");
+      return DVO_AMD_ERR_INVALID_ARGUMENT;
+    }
+    seen[(size_t)at] = 1;
+    float T[12];
+    host::float_pose(poses + 16 * (size_t)q, T);
+    if (std::memcmp(T, next[(size_t)at].T, sizeof(T)) == 0) continue;  // the same float pose: the same contribution
+    std::memcpy(next[(size_t)at].T, T, sizeof(T));
+    moved.push_back(at);
+    moved_points += next[(size_t)at].points;
+  }
+  if (moved.empty()) return DVO_AMD_OK;
+  // a delta of more points than the whole map holds: build the store again from every keyframe instead
+  const bool rebuild = 2 * moved_points > all_points;
+  std::vector<host::DeltaItem> items;
+  if (rebuild) {
+    for (size_t k = 0; k < next.size(); ++k) {
+      host::DeltaItem it;
+      it.kf = &M->kfs[k], it.negative = false, it.stats_of = (int)k;
+      std::memcpy(it.T, next[k].T, sizeof(it.T));
+      items.push_back(it);
+    }
+  } else {
+    for (int at : moved) {
+      host::DeltaItem it;
+      it.kf = &M->kfs[(size_t)at], it.negative = true, it.stats_of = -1;
+      std::memcpy(it.T, M->kfs[(size_t)at].T, sizeof(it.T));
+      items.push_back(it);
+      it.negative = false, it.stats_of = at;
+      std::memcpy(it.T, next[(size_t)at].T, sizeof(it.T));
+      items.push_back(it);
+    }
+  }
+  return host::apply_delta(M, items, rebuild, next);
+}
+
+int dvo_amd_map_remove(dvo_amd_map *M, int n, const int *ids) {
+  int rc = host::entry_checks(M, "dvo_amd_map_remove");
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && !ids)) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  std::vector<char> gone(M->kfs.size(), 0);
+  std::vector<host::DeltaItem> items;
+  for (int q = 0; q < n; ++q) {
+    const int at = host::find_keyframe(M, ids[q]);
+    if (at < 0 || gone[(size_t)at]) {
+      g_last_error = "dvo_amd_map_remove: keyframe id " + std::to_string(ids[q]) + (at < 0 ? " is not in the map" : " is given twice");
+      return DVO_AMD_ERR_INVALID_ARGUMENT;
+    }
+    gone[(size_t)at] = 1;
+    host::DeltaItem it;
+    it.kf = &M->kfs[(size_t)at], it.negative = true, it.stats_of = -1;
+    std::memcpy(it.T, M->kfs[(size_t)at].T, sizeof(it.T));
+    items.push_back(it);
+  }
+  if (items.empty()) return DVO_AMD_OK;
+  std::vector<dvo_amd_map::Keyframe> next, removed;
+  for (size_t k = 0; k < M->kfs.size(); ++k) (gone[k] ? removed : next).push_back(M->kfs[k]);
+  rc = host::apply_delta(M, items, false, next);  // (on success `next` holds the old list: the items stay valid throughout)
+  if (rc) return rc;
+  for (dvo_amd_map::Keyframe &k : removed) {
+    if (k.bgr) (void)hipFree(k.bgr);
+    dvo_amd_pyramid_release(k.pyr);
+  }
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_map_stats(const dvo_amd_map *M, dvo_amd_cloud_stats *stats, int *n_keyframes) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!M) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  if (stats) {
+    std::memset(stats, 0, sizeof(*stats));
+    for (const dvo_amd_map::Keyframe &k : M->kfs)
+      stats->points_in += k.points, stats->finite += k.finite, stats->out_of_range += k.out_of_range;
+    stats->voxels = M->n;
+  }
+  if (n_keyframes) *n_keyframes = (int)M->kfs.size();
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_map_extract(dvo_amd_map *M, const float *box, dvo_amd_point *out, long long capacity, long long *n_out) {
+  int rc = host::entry_checks(M, "dvo_amd_map_extract");
+  if (rc) return rc;
+  if (capacity < 0 || (capacity > 0 && !out)) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  map::Box bx = {};
+  if (box) {
+    for (int a = 0; a < 3; ++a) {
+      if (!(box[a] < box[a + 3])) {  // NaN included
+        g_last_error = "dvo_amd_map_extract: the box needs min < max on every axis";
+        return DVO_AMD_ERR_INVALID_ARGUMENT;
+      }
+      bx.mn[a] = box[a], bx.mx[a] = box[a + 3];
+    }
+  }
+  if (n_out) *n_out = 0;
+  M->device_ms = 0.0, M->copy_ms = 0.0, M->delta_points = 0, M->delta_voxels = 0;
+  const unsigned n = M->n;
+  if (n == 0) return DVO_AMD_OK;
+  if (!box && (long long)n > capacity) {
+    if (n_out) *n_out = n;
+    g_last_error = "dvo_amd_map_extract: " + std::to_string(n) + " voxels, capacity " + std::to_string(capacity);
+    return DVO_AMD_ERR_CAPACITY;
+  }
+  host::MapWorkspace *W = nullptr;
+  rc = host::workspace(M->ctx, &W);
+  if (!rc) rc = host::grow(W->out, sizeof(float4) * (size_t)n);
+  if (!rc && box) rc = host::grow(W->pts, sizeof(float4) * (size_t)n);
+  if (!rc && box) rc = host::grow_store(M->flags, 4 * (size_t)n);
+  if (!rc && box) rc = host::grow(W->ctrl, sizeof(map::MapCtrl));
+  if (!rc && box) rc = host::grow(W->bsum, sizeof(unsigned) * ((size_t)n / map::kScanTile + 1));
+  if (rc) return rc;
+  const hipStream_t st = M->ctx->stream;
+  const float4 *src = (const float4 *)W->out.p;
+  unsigned n_ret = n;
+  HIP_TRY(hipEventRecord(M->ev[0], st));
+  hipLaunchKernelGGL(map::k_voxel_out, dim3(map::grid_for(n, map::kBlock)), dim3(map::kBlock), 0, st,
+                     (const map::VoxelAcc *)M->acc[M->cur].p, n, (float4 *)W->out.p);
+  if (box) {
+    map::MapCtrl *dctrl = (map::MapCtrl *)W->ctrl.p;
+    hipLaunchKernelGGL(map::k_box_flags, dim3(map::grid_for(n, map::kBlock)), dim3(map::kBlock), 0, st, src, n, bx,
+                       (unsigned *)M->flags.p);
+    rc = host::scan(*W, (unsigned *)M->flags.p, n, &dctrl->voxels, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(map::k_box_compact, dim3(map::grid_for(n, map::kBlock)), dim3(map::kBlock), 0, st, src,
+                       (const unsigned *)M->flags.p, (const unsigned *)&dctrl->voxels, n, (float4 *)W->pts.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(M->ev[1], st));
+    HIP_TRY(hipMemcpyAsync(&n_ret, &dctrl->voxels, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    src = (const float4 *)W->pts.p;
+    if ((long long)n_ret > capacity) {
+      if (n_out) *n_out = n_ret;
+      g_last_error = "dvo_amd_map_extract: " + std::to_string(n_ret) + " voxels in the box, capacity " + std::to_string(capacity);
+      return DVO_AMD_ERR_CAPACITY;
+    }
+  } else {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(M->ev[1], st));
+  }
+  HIP_TRY(hipEventRecord(M->ev[2], st));
+  if (n_ret > 0) HIP_TRY(hipMemcpyAsync(out, src, sizeof(float4) * (size_t)n_ret, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(M->ev[3], st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float a = 0.f, b = 0.f;
+  HIP_TRY(hipEventElapsedTime(&a, M->ev[0], M->ev[1]));
+  HIP_TRY(hipEventElapsedTime(&b, M->ev[2], M->ev[3]));
+  M->device_ms = a, M->copy_ms = b;
+  if (n_out) *n_out = n_ret;
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_debug_keyframe_map_timing(const dvo_amd_map *M, double *device_ms, double *copy_ms, long long *delta_points,
+                                      long long *delta_voxels, int *merge_tile) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!M) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  if (device_ms) *device_ms = M->device_ms;
+  if (copy_ms) *copy_ms = M->copy_ms;
+  if (delta_points) *delta_points = M->delta_points;
+  if (delta_voxels) *delta_voxels = M->delta_voxels;
+  if (merge_tile) *merge_tile = map::kMergeTile;
+  return DVO_AMD_OK;
+}
+
 
 int dvo_amd_point_cloud(dvo_amd_context *ctx, dvo_amd_pyramid *image, int level, const double *pose, const unsigned char *bgr,
                         int bgr_stride_bytes, dvo_amd_point *out) {
@@ -692,7 +1322,7 @@ int dvo_amd_map_cloud(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *image
     const int nk = std::min(65535, n - k0);
     hipLaunchKernelGGL(map::k_map_keys, dim3(map::grid_for(max_px, map::kBlock, 64), nk), dim3(map::kBlock), 0, st,
                        (const map::MapImage *)W->images.p, k0, inv, (float4 *)W->pts.p, (unsigned long long *)W->keys[0].p,
-                       (unsigned *)W->vals[0].p, (map::MapCtrl *)W->ctrl.p);
+                       (unsigned *)W->vals[0].p, (map::MapCtrl *)W->ctrl.p, (unsigned long long *)nullptr);
   }
   HIP_TRY(hipGetLastError());
   map::MapCtrl c;

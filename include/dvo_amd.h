@@ -483,6 +483,53 @@ int dvo_amd_map_cloud(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *image
 int dvo_amd_voxel_downsample(dvo_amd_context *ctx, long long n, const dvo_amd_point *in, float leaf_size,
                              dvo_amd_point *out, long long capacity, dvo_amd_cloud_stats *stats);
 
+/*
+ * The keyframe map kept on the device: keyframes are inserted, moved and removed one event at a time, and the voxel aggregate
+ * is updated by the difference instead of being rebuilt.  A voxel is a set of integer sums (above) and the world point of a
+ * pixel at a pose is a pinned sequence of fp32 operations, so a keyframe's contribution at its old pose is recomputed and
+ * subtracted exactly.
+ *
+ * The contract: after any sequence of successful calls, dvo_amd_map_extract(map, NULL, ...) returns exactly what
+ * dvo_amd_map_cloud returns for the keyframes now in the map -- their current poses and BGR images, the map's leaf_size: the
+ * same voxels in the same ascending key order with the same coordinate and colour bits -- and dvo_amd_map_stats returns that
+ * call's points_in, finite, out_of_range and voxels.  The history does not show in the result: not the order of the
+ * operations, not how they were batched, not the launch geometry.  Every rule of the voxel aggregate carries over unchanged:
+ * the index rule and the 2^20 range with its out_of_range count, NaN points dropped, sums wrapping modulo 2^64 (for which
+ * subtraction is still exact), the leaf bounds.  At most 2^31 points per update.
+ *
+ * Box extraction: with a box {xmin,ymin,zmin,xmax,ymax,zmax} a voxel is returned when its output centroid c satisfies
+ * min <= c < max on all three axes, compared in fp32; the voxels keep their order: the result is the full extract filtered, bit
+ * for bit.  A box with a NaN or with min >= max on any axis: DVO_AMD_ERR_INVALID_ARGUMENT.
+ *
+ * Ownership: insert retains the pyramid (dvo_amd_pyramid_retain) and copies the BGR image to the device, packed to w*3 bytes
+ * per row; the map holds both until remove or destroy.  The caller may release its handle and free its image as soon as
+ * insert returns.
+ *
+ * Errors: a failed call leaves the map exactly as it was.  DVO_AMD_ERR_INVALID_ARGUMENT with a reason in dvo_amd_last_error()
+ * for: insert of an id already present; an unknown id in set_poses or remove; the same id twice in one call; a non-finite pose
+ * entry.  set_poses with a pose whose 16 doubles round to the same floats as the stored one does nothing for that keyframe.
+ * extract with too small a capacity returns DVO_AMD_ERR_CAPACITY with *n_out set to the size needed (out untouched).  Like
+ * every compute entry: DVO_AMD_ERR_NO_DEVICE without a GPU, DVO_AMD_ERR_DEVICE_MISMATCH for a pyramid of another device,
+ * DVO_AMD_ERR_INVALID_ARGUMENT while pairs are queued on the context.
+ *
+ * The map is bound to its context: it shares the context's stream and buffers and is no more thread-safe than the context.
+ * The context must outlive its maps; destroying a context with live maps is the caller's error (destroy the maps first).
+ */
+typedef struct dvo_amd_map dvo_amd_map;
+int dvo_amd_map_create(dvo_amd_context *ctx, float leaf_size, dvo_amd_map **out);
+void dvo_amd_map_destroy(dvo_amd_map *map);
+/* level 0 of the pyramid; pose: column-major 4x4, NULL = identity; bgr: NULL = grey, else w*h*3 with bgr_stride_bytes per row
+ * (0: tight rows) */
+int dvo_amd_map_insert(dvo_amd_map *map, int id, dvo_amd_pyramid *image, const double *pose, const unsigned char *bgr,
+                       int bgr_stride_bytes);
+/* poses: n x 16 doubles, column-major each */
+int dvo_amd_map_set_poses(dvo_amd_map *map, int n, const int *ids, const double *poses);
+int dvo_amd_map_remove(dvo_amd_map *map, int n, const int *ids);
+/* stats and n_keyframes may be NULL */
+int dvo_amd_map_stats(const dvo_amd_map *map, dvo_amd_cloud_stats *stats, int *n_keyframes);
+/* box: NULL, or {xmin,ymin,zmin,xmax,ymax,zmax} */
+int dvo_amd_map_extract(dvo_amd_map *map, const float *box, dvo_amd_point *out, long long capacity, long long *n_out);
+
 /* Binary PCD v0.7 as pcl::io::savePCDFileBinary writes a PointXYZRGB cloud: FIELDS x y z rgb, SIZE 4 4 4 4, TYPE F F F F
  * (rgb holds the packed bits), COUNT 1 1 1 1, WIDTH / HEIGHT as given (organized, or n x 1), VIEWPOINT 0 0 0 1 0 0 0,
  * POINTS width*height (= n), then the records.  Host code only. */

@@ -1,6 +1,7 @@
 // point_cloud.hpp -- header-only C++ adaptor of the keyframe map's point cloud over the C ABI (include/dvo_amd.h):
 //   dvo::visualization::AsyncPointCloudBuilder::{PointCloud, BuildJob}   dvo_core/include/dvo/visualization/async_point_cloud_builder.h
 //   dvo::visualization::PointCloudAggregator                             dvo_core/include/dvo/visualization/point_cloud_aggregator.h
+//   dvo::visualization::KeyframeMap                                      (no counterpart: the map kept on the device, dvo_amd_map_*)
 // PCL-free: PointCloud holds PointXYZRGB records with the members callers read (points, width, height, push_back, size,
 // reserve).  A BuildJob's cloud is dvo_amd_point_cloud at the job's pose; PointCloudAggregator::build keeps the reference's
 // std::map name order and its max(n / 50, 1) step and aggregates the clouds it picks in ONE call on the GPU: dvo_amd_map_cloud
@@ -234,6 +235,93 @@ class PointCloudAggregator {
   float leaf_;
   std::mutex mu_;
   std::map<std::string, Entry> entries_;
+};
+
+// The keyframe map kept on the device (dvo_amd.h: dvo_amd_map_*): insert / move / remove keyframes one event at a time;
+// extract() always equals one dvo_amd_map_cloud over the keyframes now in the map, bit for bit, without the rebuild.  This is
+// what replaces calling PointCloudAggregator::build() after every event.  Level-0 jobs only.  The map lives in
+// the shared cloud context of `device` (core::cloud::context), which outlives it; calls are serialised by that context's lock.
+class KeyframeMap {
+ public:
+  typedef AsyncPointCloudBuilder::PointCloud PointCloud;
+  typedef AsyncPointCloudBuilder::BuildJob BuildJob;
+
+  explicit KeyframeMap(float leaf_size = 0.01f, int device = 0) : device_(device), map_(nullptr) {
+    std::unique_lock<std::mutex> lock;
+    dvo_amd_context *ctx = core::cloud::context(device_, lock);
+    ::dvo::detail::check(dvo_amd_map_create(ctx, leaf_size, &map_), "KeyframeMap");
+  }
+  ~KeyframeMap() {
+    std::unique_lock<std::mutex> lock;
+    (void)core::cloud::context(device_, lock);
+    dvo_amd_map_destroy(map_);
+  }
+  KeyframeMap(const KeyframeMap &) = delete;
+  KeyframeMap &operator=(const KeyframeMap &) = delete;
+
+  // the job's image (level 0 of its pyramid) at the job's pose; the map keeps the pyramid and a copy of the colour image
+  void insert(int id, const BuildJob &job) {
+    if (job.level() != 0) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "KeyframeMap::insert: a level-0 image");
+    const std::vector<unsigned char> bgr = detail::bgr8(job.image);
+    std::unique_lock<std::mutex> lock;
+    (void)core::cloud::context(device_, lock);
+    ::dvo::detail::check(dvo_amd_map_insert(map_, id, job.owner()->handle(), core::data(job.pose), bgr.empty() ? nullptr : bgr.data(),
+                                            (int)job.image.width * 3),
+                         "KeyframeMap::insert");
+  }
+  void set_poses(const std::vector<int> &ids, const std::vector<core::AffineTransformd> &poses) {
+    if (ids.size() != poses.size()) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "KeyframeMap::set_poses: one pose per id");
+    std::vector<double> flat;
+    for (size_t i = 0; i < poses.size(); ++i) flat.insert(flat.end(), core::data(poses[i]), core::data(poses[i]) + 16);
+    std::unique_lock<std::mutex> lock;
+    (void)core::cloud::context(device_, lock);
+    ::dvo::detail::check(dvo_amd_map_set_poses(map_, (int)ids.size(), ids.data(), flat.data()), "KeyframeMap::set_poses");
+  }
+  void set_pose(int id, const core::AffineTransformd &pose) {
+    set_poses(std::vector<int>(1, id), std::vector<core::AffineTransformd>(1, pose));
+  }
+  void remove(const std::vector<int> &ids) {
+    std::unique_lock<std::mutex> lock;
+    (void)core::cloud::context(device_, lock);
+    ::dvo::detail::check(dvo_amd_map_remove(map_, (int)ids.size(), ids.data()), "KeyframeMap::remove");
+  }
+  void remove(int id) { remove(std::vector<int>(1, id)); }
+
+  dvo_amd_cloud_stats stats(int *n_keyframes = nullptr) const {
+    dvo_amd_cloud_stats st;
+    ::dvo::detail::check(dvo_amd_map_stats(map_, &st, n_keyframes), "KeyframeMap::stats");
+    return st;
+  }
+
+  // the voxels in key order; box: null, or {xmin, ymin, zmin, xmax, ymax, zmax}
+  void records(std::vector<dvo_amd_point> &out, const float *box = nullptr) {
+    std::unique_lock<std::mutex> lock;
+    (void)core::cloud::context(device_, lock);
+    dvo_amd_cloud_stats st;
+    ::dvo::detail::check(dvo_amd_map_stats(map_, &st, nullptr), "KeyframeMap::extract");
+    long long n = 0;
+    out.resize((size_t)(box ? 0 : st.voxels));
+    int rc = dvo_amd_map_extract(map_, box, out.data(), (long long)out.size(), &n);
+    if (rc == DVO_AMD_ERR_CAPACITY) {
+      out.resize((size_t)n);
+      rc = dvo_amd_map_extract(map_, box, out.data(), (long long)out.size(), &n);
+    }
+    ::dvo::detail::check(rc, "KeyframeMap::extract");
+    out.resize((size_t)n);
+  }
+  PointCloud::Ptr extract(const float *box = nullptr) {
+    std::vector<dvo_amd_point> voxels;
+    records(voxels, box);
+    PointCloud::Ptr out(new PointCloud);
+    out->reserve(voxels.size());
+    for (size_t i = 0; i < voxels.size(); ++i) out->points.push_back(detail::from_record(voxels[i]));
+    out->width = (std::uint32_t)voxels.size(), out->height = 1;
+    return out;
+  }
+
+ private:
+  int device_;
+  dvo_amd_map *map_;
 };
 
 }  // namespace visualization
