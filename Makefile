@@ -11,7 +11,8 @@ CPP := $(SRC)/dvo_kernels.hip $(SRC)/dvo_pyramid.cpp $(SRC)/dvo_tracker.cpp $(SR
        $(SRC)/dvo_validator.cpp $(SRC)/dvo_frontend.cpp $(SRC)/dvo_tum.cpp $(SRC)/dvo_map.cpp $(SRC)/dvo_graph.cpp \
        $(SRC)/dvo_graph_batch.cpp
 
-$(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_graph_device.h include/dvo_amd.h include/dvo_amd_debug.h
+$(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_graph_device.h $(SRC)/dvo_graph_host.h \
+        include/dvo_amd.h include/dvo_amd_debug.h
 	$(HIPCC) $(FLAGS) '-DDVO_AMD_BUILD_ID="$(BUILD_ID)"' -x hip $(CPP) -lz -o $@
 
 oracle:

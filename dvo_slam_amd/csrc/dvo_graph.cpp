@@ -20,10 +20,10 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <map>
+#include <optional>
 
 #include "dvo_graph_device.h"
-#include "dvo_internal.h"
+#include "dvo_graph_host.h"
 
 namespace dvo_amd {
 namespace graph {
@@ -797,19 +797,32 @@ __global__ void k_unit_vector(double *b, int n, int at) {
 
 namespace host {
 
+// Every device buffer of the workspace is named once, in one of three lists: the sparse memory check estimates the "held" ones
+// and adds what the context already holds of them to the free memory; the plain list's O(m + edges) buffers it leaves out.
+#define GRAPH_BUFS_PLAIN(X)                                                                                                  \
+  X(poses) X(saved) X(edges) X(rec) X(rho0) X(chi2) X(rho1) X(H) X(L) X(b) X(x) X(hsd) X(hdl) X(aux) X(block_rc)             \
+  X(block_ptr) X(block_c) X(b_ptr) X(b_c) X(vertex_of) X(scalars) X(flag)                                                    \
+  /* sparse: row pointers and (row, col) slots of the H blocks, the diagonal block of each slot, the level lists */          \
+  X(bsr_ptr) X(bsr_rc) X(diag_block) X(child_list) X(level_ids) X(small_ids)                                                 \
+  /* marginals: parents and child -> parent maps, a tile column of Y, a tile's inverse, requests, six columns, the output */ \
+  X(sel_info) X(up) X(ytiles) X(wtile) X(mreq) X(creq) X(cols) X(mout)
+// the sparse solver: the front matrices and vectors, the H blocks, the fronts' maps and records
+#define GRAPH_BUFS_HELD_SPARSE(X) X(A) X(V) X(Hs) X(hmap) X(inv) X(loc) X(fronts)
+// marginals: the fronts' Z (the factor's layout)
+#define GRAPH_BUFS_HELD_INVERSE(X) X(Zinv)
+
+#define GRAPH_BUFS(X) GRAPH_BUFS_PLAIN(X) GRAPH_BUFS_HELD_SPARSE(X) GRAPH_BUFS_HELD_INVERSE(X)
+#define HELD_BYTES(name) held += (double)name.bytes;
+
 struct GraphWorkspace {
-  struct Buf {
-    void *p = nullptr;
-    size_t bytes = 0;
-  };
-  Buf poses, saved, edges, rec, rho0, chi2, rho1, H, L, b, x, hsd, hdl, aux, block_rc, block_ptr, block_c, b_ptr, b_c,
-      vertex_of, scalars, flag;
-  // the sparse solver: H blocks, their row pointers and (row, col) slots, the diagonal block of each slot, the fronts and their
-  // maps, the level lists, the front matrices and vectors
-  Buf Hs, bsr_ptr, bsr_rc, diag_block, fronts, hmap, inv, child_list, loc, level_ids, small_ids, A, V;
-  // marginals: the fronts' Z (the factor's layout), the fronts' parents and child -> parent maps, one tile column of Y and the
-  // inverse of a diagonal tile, the requests, the six solved columns of a vertex, the output blocks
-  Buf Zinv, sel_info, up, ytiles, wtile, mreq, creq, cols, mout;
+  DEVICE_BUF_MEMBERS(GRAPH_BUFS)
+  // the bytes held of the buffers the sparse memory check estimates (with_inverse: the marginals' arena too)
+  double held_bytes(bool with_inverse) const {
+    double held = 0.0;
+    GRAPH_BUFS_HELD_SPARSE(HELD_BYTES)
+    if (with_inverse) { GRAPH_BUFS_HELD_INVERSE(HELD_BYTES) }
+    return held;
+  }
   hipEvent_t ev[6] = {};
   double lin_ms = 0.0, fac_ms = 0.0;
   int n_padded = 0, factorizations = 0;
@@ -820,16 +833,7 @@ struct GraphWorkspace {
 
 namespace {
 
-int grow(GraphWorkspace::Buf &b, size_t bytes) {
-  if (bytes <= b.bytes) return DVO_AMD_OK;
-  if (b.p) (void)hipFree(b.p), b.p = nullptr, b.bytes = 0;
-  bytes = align_up(std::max<size_t>(bytes, 256), 1 << 12);
-  const hipError_t e = hipMalloc(&b.p, bytes);
-  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
-  if (e != hipSuccess) return fail_hip("hipMalloc (graph workspace)", e);
-  b.bytes = bytes;
-  return DVO_AMD_OK;
-}
+int grow(DeviceBuf &b, size_t bytes) { return grow(b, bytes, "graph workspace"); }
 
 int workspace(dvo_amd_context *ctx, GraphWorkspace **out) {
   if (!ctx->graph_ws) {
@@ -881,11 +885,6 @@ int graph_check_arguments(const char *entry, int n_vertices, const double *poses
 }
 
 namespace {
-
-int check_arguments(int n_vertices, const double *poses, int n_edges, const dvo_amd_graph_edge *edges,
-                    const dvo_amd_graph_options *opt) {
-  return graph_check_arguments("dvo_amd_optimize_graph", n_vertices, poses, n_edges, edges, opt);
-}
 
 // ---- the sparse solver's symbolic phase (host, once per call): nested dissection on the m x m block pattern ---------------
 constexpr int kLeafVertices = 16;
@@ -1149,13 +1148,16 @@ struct Solver {
   int cholesky_failures = 0;
   bool timed_lin = false, timed_fac = false;
   // the sparse solver's schedule (null: the dense path)
-  struct Sparse {
+  struct SparsePlan {  // the fronts' device records and maps, and the launch schedule
     std::vector<int> level_begin, small_begin, small_count;  // per level: its fronts in level_ids, its small fronts in small_ids
     std::vector<std::vector<int>> wide;                      // per level: the wide fronts' ids
     std::vector<int> max_ld;                                 // per level
     std::vector<graph::Front> fronts;                        // host copy (wide fronts' offsets)
+    // what the sparse path uploads besides the contributor lists
+    std::vector<int2> slot_rc;  // (row, col) slots of the stored blocks
+    std::vector<int> bsr_ptr, diag_block, hmap, inv, child_list, loc, level_ids, small_ids;
   };
-  const Sparse *sp = nullptr;
+  const SparsePlan *sp = nullptr;
 
   double *poses() { return (double *)W.poses.p; }
   double *H() { return (double *)W.H.p; }
@@ -1245,10 +1247,40 @@ struct Solver {
     return DVO_AMD_OK;
   }
 
+  // blocked right-looking Cholesky of the leading P tile columns of a (ld x ld): the dense L (P = all tiles) or a wide front
+  // (P = its pivot tiles; the trailing tiles are left holding the update matrix)
+  void tiled_cholesky_enqueue(double *a, int ld, int P) {
+    const int T = ld / graph::kTile;
+    for (int t = 0; t < P; ++t) {
+      hipLaunchKernelGGL(graph::k_potrf_panel, dim3(1), dim3(graph::kBlock), 0, st, a, ld, t, flag());
+      if (t + 1 < T) {
+        hipLaunchKernelGGL(graph::k_trsm, dim3(T - t - 1), dim3(graph::kBlock), 0, st, a, ld, t, (const int *)flag());
+        hipLaunchKernelGGL(graph::k_syrk, dim3(T - t - 1, T - t - 1), dim3(graph::kBlock), 0, st, a, ld, t, (const int *)flag());
+      }
+    }
+  }
+
+  // the factorized fronts applied to `rhs`: forward substitution leaves first, backward root first, the solution into `out`
+  void sparse_solve_enqueue(const double *rhs, double *out) {
+    const graph::Front *fr = (const graph::Front *)W.fronts.p;
+    const int *ids = (const int *)W.level_ids.p;
+    const double *A = (const double *)W.A.p;
+    double *V = (double *)W.V.p;
+    const int levels = (int)sp->level_begin.size() - 1;
+    for (int l = 0; l < levels; ++l)
+      hipLaunchKernelGGL(graph::k_front_forward, dim3(sp->level_begin[l + 1] - sp->level_begin[l]), dim3(graph::kFrontThreads),
+                         0, st, fr, ids + sp->level_begin[l], A, (const int *)W.loc.p, (const int *)W.inv.p,
+                         (const int *)W.child_list.p, rhs, V, (const int *)flag());
+    for (int l = levels - 1; l >= 0; --l)
+      hipLaunchKernelGGL(graph::k_front_backward, dim3(sp->level_begin[l + 1] - sp->level_begin[l]),
+                         dim3(graph::kFrontThreads), 0, st, fr, ids + sp->level_begin[l], A, (const int *)W.loc.p, V, out,
+                         (const int *)flag());
+  }
+
   int sparse_factor_solve_enqueue(bool damp, double lambda, double *out) {
     const graph::Front *fr = (const graph::Front *)W.fronts.p;
     const int *ids = (const int *)W.level_ids.p, *small = (const int *)W.small_ids.p;
-    double *A = (double *)W.A.p, *V = (double *)W.V.p;
+    double *A = (double *)W.A.p;
     if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[2], st));
     HIP_TRY(hipMemsetAsync(flag(), 0xff, sizeof(int), st));
     const int levels = (int)sp->level_begin.size() - 1;
@@ -1261,30 +1293,12 @@ struct Solver {
       if (sp->small_count[l])
         hipLaunchKernelGGL(graph::k_front_factor, dim3(sp->small_count[l]), dim3(graph::kFrontThreads), 0, st, fr,
                            small + sp->small_begin[l], A, flag());
-      for (int k : sp->wide[l]) {  // the dense path's tiled kernels on the front, over its pivot tiles
-        const graph::Front &F = sp->fronts[k];
-        double *a = A + F.a_off;
-        const int T = F.ld / graph::kTile, P = F.ppad / graph::kTile;
-        for (int t = 0; t < P; ++t) {
-          hipLaunchKernelGGL(graph::k_potrf_panel, dim3(1), dim3(graph::kBlock), 0, st, a, F.ld, t, flag());
-          if (t + 1 < T) {
-            hipLaunchKernelGGL(graph::k_trsm, dim3(T - t - 1), dim3(graph::kBlock), 0, st, a, F.ld, t, (const int *)flag());
-            hipLaunchKernelGGL(graph::k_syrk, dim3(T - t - 1, T - t - 1), dim3(graph::kBlock), 0, st, a, F.ld, t,
-                               (const int *)flag());
-          }
-        }
-      }
+      for (int k : sp->wide[l])  // the dense path's tiled kernels on the front, over its pivot tiles
+        tiled_cholesky_enqueue(A + sp->fronts[k].a_off, sp->fronts[k].ld, sp->fronts[k].ppad / graph::kTile);
     }
     HIP_TRY(hipGetLastError());
     if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[3], st));
-    for (int l = 0; l < levels; ++l)
-      hipLaunchKernelGGL(graph::k_front_forward, dim3(sp->level_begin[l + 1] - sp->level_begin[l]), dim3(graph::kFrontThreads),
-                         0, st, fr, ids + sp->level_begin[l], (const double *)A, (const int *)W.loc.p, (const int *)W.inv.p,
-                         (const int *)W.child_list.p, (const double *)b(), V, (const int *)flag());
-    for (int l = levels - 1; l >= 0; --l)
-      hipLaunchKernelGGL(graph::k_front_backward, dim3(sp->level_begin[l + 1] - sp->level_begin[l]),
-                         dim3(graph::kFrontThreads), 0, st, fr, ids + sp->level_begin[l], (const double *)A,
-                         (const int *)W.loc.p, V, out, (const int *)flag());
+    sparse_solve_enqueue(b(), out);
     HIP_TRY(hipGetLastError());
     if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[4], st));
     ++W.factorizations;
@@ -1298,15 +1312,7 @@ struct Solver {
     HIP_TRY(hipMemsetAsync(flag(), 0xff, sizeof(int), st));
     hipLaunchKernelGGL(graph::k_damp_copy, dim3(std::min(4096, graph::grid_for((size_t)N * N, 256))), dim3(256), 0, st,
                        (const double *)H(), L(), N, n, lambda, damp ? 1 : 0);
-    const int T = N / graph::kTile;
-    for (int k = 0; k < T; ++k) {
-      hipLaunchKernelGGL(graph::k_potrf_panel, dim3(1), dim3(graph::kBlock), 0, st, L(), N, k, flag());
-      if (k + 1 < T) {
-        hipLaunchKernelGGL(graph::k_trsm, dim3(T - k - 1), dim3(graph::kBlock), 0, st, L(), N, k, (const int *)flag());
-        hipLaunchKernelGGL(graph::k_syrk, dim3(T - k - 1, T - k - 1), dim3(graph::kBlock), 0, st, L(), N, k,
-                           (const int *)flag());
-      }
-    }
+    tiled_cholesky_enqueue(L(), N, N / graph::kTile);
     HIP_TRY(hipGetLastError());
     if (!timed_fac) HIP_TRY(hipEventRecord(W.ev[3], st));
     hipLaunchKernelGGL(graph::k_trsv, dim3(1), dim3(graph::kSolveThreads), 0, st, (const double *)L(), N,
@@ -1340,17 +1346,36 @@ struct Solver {
     return DVO_AMD_OK;
   }
   int matvec(const double *v, double *y) {
-    if (sp) {
+    if (sp)
       hipLaunchKernelGGL(graph::k_bsr_matvec, dim3(graph::grid_for(n, 256)), dim3(256), 0, st, n, (const int *)W.bsr_ptr.p,
                          (const int2 *)W.bsr_rc.p, (const double *)W.Hs.p, v, y);
-      HIP_TRY(hipGetLastError());
-      return DVO_AMD_OK;
-    }
-    hipLaunchKernelGGL(graph::k_matvec, dim3(graph::grid_for(n, graph::kBlock / 64)), dim3(graph::kBlock), 0, st,
-                       (const double *)H(), N, n, v, y);
+    else
+      hipLaunchKernelGGL(graph::k_matvec, dim3(graph::grid_for(n, graph::kBlock / 64)), dim3(graph::kBlock), 0, st,
+                         (const double *)H(), N, n, v, y);
     HIP_TRY(hipGetLastError());
     return DVO_AMD_OK;
   }
+};
+
+// one graph as an entry was given it; `entry` prefixes dvo_amd_last_error()
+struct Problem {
+  const char *entry;
+  int n_vertices;
+  const double *poses;
+  const int *fixed;
+  int n_edges;
+  const dvo_amd_graph_edge *edges;
+};
+
+// prepare()'s result: the device holds the problem, the objective at the given estimate is known, nothing is linearised yet.
+// It owns every host array an asynchronous upload reads, so it lives until its driver's final synchronize.
+struct Prepared {
+  Unknowns U;
+  Contributors C;
+  Symbolic sym;     // sparse only
+  Solver::SparsePlan plan;  // sparse only
+  std::optional<Solver> solver;
+  double F0 = 0.0;  // the objective at the given estimate
 };
 
 // dvo_amd_graph_marginals: the requests between free active vertices, and what the device stage reports
@@ -1361,17 +1386,10 @@ struct MargJob {
   int failed_pivot = -1, solved_columns = 0;
 };
 
-#define GRAPH_TRY(expr)       \
-  do {                        \
-    const int rc_ = (expr);   \
-    if (rc_) return rc_;      \
-  } while (0)
-
 // one front's tile columns, last pivot tile first (the dense solver: the whole matrix, P = T)
 int tiled_selinv_enqueue(Solver &S, const double *L, double *Z, int ld, int P) {
-  GraphWorkspace &W = S.W;
   const int T = ld / graph::kTile;
-  double *Wt = (double *)W.wtile.p, *Y = (double *)W.ytiles.p;
+  double *Wt = (double *)S.W.wtile.p, *Y = (double *)S.W.ytiles.p;
   for (int t = P - 1; t >= 0; --t) {
     hipLaunchKernelGGL(graph::k_tile_inverse, dim3(1), dim3(graph::kBlock), 0, S.st, L, ld, t, Wt, (const int *)S.flag());
     if (t + 1 < T) {
@@ -1388,16 +1406,15 @@ int tiled_selinv_enqueue(Solver &S, const double *L, double *Z, int ld, int P) {
 }
 
 // after a successful undamped factorization: Z by selected inversion, then the requested blocks
-int marginals_stage(Solver &S, MargJob &J, const std::vector<int> &slot, const Symbolic *sym, const std::vector<int> &loc) {
+int marginals_stage(Prepared &P, MargJob &J) {
+  Solver &S = *P.solver;
+  const std::vector<int> &slot = P.U.slot, &loc = P.plan.loc;
+  const Symbolic *sym = &P.sym;
   GraphWorkspace &W = S.W;
   const hipStream_t st = S.st;
   const int n = S.n, N = S.N, m = S.m;
-  auto upload = [&](GraphWorkspace::Buf &b, const void *src, size_t bytes) {
-    const int rc = grow(b, std::max<size_t>(bytes, 1));
-    if (rc) return rc;
-    if (bytes && hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st) != hipSuccess)
-      return fail_hip("hipMemcpyAsync (marginals)", hipGetLastError());
-    return (int)DVO_AMD_OK;
+  auto upload = [&](DeviceBuf &b, const void *src, size_t bytes) {
+    return grow_upload(b, src, bytes, st, "graph workspace", "marginals");
   };
   GRAPH_TRY(grow(W.wtile, sizeof(double) * graph::kTile * graph::kTile));
   GRAPH_TRY(grow(W.mout, sizeof(double) * 36 * std::max(J.n, 1)));
@@ -1488,22 +1505,11 @@ int marginals_stage(Solver &S, MargJob &J, const std::vector<int> &slot, const S
     GRAPH_TRY(grow(W.cols, sizeof(double) * 6 * (size_t)n));
     for (const auto &kv : columns) all.insert(all.end(), kv.second.req.begin(), kv.second.req.end());
     GRAPH_TRY(upload(W.creq, all.data(), sizeof(graph::ColReq) * all.size()));
-    const graph::Front *dfr = (const graph::Front *)W.fronts.p;
-    const int *ids = (const int *)W.level_ids.p;
-    const int levels = (int)S.sp->level_begin.size() - 1;
     size_t first = 0;
     for (const auto &kv : columns) {
       for (int q = 0; q < 6; ++q) {
         hipLaunchKernelGGL(graph::k_unit_vector, dim3(graph::grid_for(n, 256)), dim3(256), 0, st, S.b(), n, 6 * kv.first + q);
-        for (int l = 0; l < levels; ++l)
-          hipLaunchKernelGGL(graph::k_front_forward, dim3(S.sp->level_begin[l + 1] - S.sp->level_begin[l]),
-                             dim3(graph::kFrontThreads), 0, st, dfr, ids + S.sp->level_begin[l], (const double *)W.A.p,
-                             (const int *)W.loc.p, (const int *)W.inv.p, (const int *)W.child_list.p, (const double *)S.b(),
-                             (double *)W.V.p, (const int *)S.flag());
-        for (int l = levels - 1; l >= 0; --l)
-          hipLaunchKernelGGL(graph::k_front_backward, dim3(S.sp->level_begin[l + 1] - S.sp->level_begin[l]),
-                             dim3(graph::kFrontThreads), 0, st, dfr, ids + S.sp->level_begin[l], (const double *)W.A.p,
-                             (const int *)W.loc.p, (double *)W.V.p, (double *)W.cols.p + (size_t)q * n, (const int *)S.flag());
+        S.sparse_solve_enqueue(S.b(), (double *)W.cols.p + (size_t)q * n);
       }
       const int cnt = (int)kv.second.req.size();
       hipLaunchKernelGGL(graph::k_marg_columns, dim3(graph::grid_for(36 * (size_t)cnt, 256)), dim3(256), 0, st, cnt,
@@ -1520,14 +1526,7 @@ int marginals_stage(Solver &S, MargJob &J, const std::vector<int> &slot, const S
 
 void record(dvo_amd_graph_iteration *iterations, int capacity, int it, double F, double step, double lambda, double delta,
             int trials, int accepted) {
-  if (!iterations || it >= capacity) return;
-  dvo_amd_graph_iteration &r = iterations[it];
-  r.objective = F;
-  r.step_norm = step;
-  r.lambda = lambda;
-  r.delta = delta;
-  r.trials = trials;
-  r.accepted = accepted;
+  if (iterations && it < capacity) iterations[it] = dvo_amd_graph_iteration{F, step, lambda, delta, trials, accepted};
 }
 
 // OptimizationAlgorithmLevenberg::solve, max_iterations times
@@ -1702,233 +1701,194 @@ int run_dogleg(Solver &S, const dvo_amd_graph_options &opt, double *F, dvo_amd_g
   return DVO_AMD_OK;
 }
 
-// dvo_amd_debug_graph_system: the first linear system and its undamped solve instead of an optimization
-struct Probe {
-  double *H, *b, *x, *F;
-  int *failed_pivot;
-  // the sparse probe: the stored blocks (row, col slots; 36 doubles each, row-major), capacity in / count out
-  int *block_rc = nullptr;
-  double *blocks = nullptr;
-  int block_capacity = 0;
-  int *n_blocks = nullptr;
-  MargJob *marg = nullptr;  // dvo_amd_graph_marginals: blocks of H^-1 instead of the probe's outputs
-};
-
-int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fixed, int n_edges,
-             const dvo_amd_graph_edge *edges, const dvo_amd_graph_options &opt, double *edge_chi2, double *edge_weight,
-             int capacity, dvo_amd_graph_iteration *iterations, dvo_amd_graph_stats &stats, const Probe *probe = nullptr) {
-  // the unknowns: free active vertices in increasing index
-  std::vector<char> active(n_vertices, 0);
-  for (int k = 0; k < n_edges; ++k) active[edges[k].from] = active[edges[k].to] = 1;
-  std::vector<int> slot(n_vertices, -1), vertex_of;
-  for (int v = 0; v < n_vertices; ++v)
-    if (active[v] && !(fixed && fixed[v])) {
-      slot[v] = (int)vertex_of.size();
-      vertex_of.push_back(v);
-    }
-  const int m = (int)vertex_of.size();
-  stats.n_free = m;
+// the unknowns of a single-graph entry, refused beyond the solver's capacity
+int checked_unknowns(const Problem &P, const dvo_amd_graph_options &opt, Unknowns &U) {
+  U = free_unknowns(P.n_vertices, P.fixed, P.n_edges, P.edges);
   const bool sparse = opt.solver == DVO_AMD_GRAPH_SOLVER_SPARSE;
-  const int cap = sparse ? DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE : DVO_AMD_GRAPH_MAX_FREE_VERTICES;
-  const std::string entry = probe && probe->marg ? "dvo_amd_graph_marginals" : "dvo_amd_optimize_graph";
-  if (m > cap) {
-    g_last_error = entry + ": " + std::to_string(m) + " free active vertices (the " +
-                   (sparse ? "sparse" : "dense") + " solver takes at most " + std::to_string(cap) + ")";
-    return DVO_AMD_ERR_CAPACITY;
+  return check_capacity(P.entry, U.m, sparse ? DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE : DVO_AMD_GRAPH_MAX_FREE_VERTICES,
+                        sparse ? "the sparse solver" : "the dense solver");
+}
+
+// What the sparse path grows with the problem: fronts, vectors, H blocks, maps, front records (its other buffers are O(m +
+// edges)).  marginal_requests >= 0 adds the inverse: a second arena of fronts, a tile column, six columns, maps, the blocks.
+double sparse_bytes_needed(const Symbolic &sym, size_t n_blocks, int m, int marginal_requests) {
+  double need = sizeof(double) * (sym.front_doubles + sym.vector_doubles + 36.0 * n_blocks) + sizeof(int) * sym.map_ints +
+                sizeof(graph::Front) * (double)sym.n_fronts;
+  if (marginal_requests >= 0) {
+    const int widest_ld = sym.ld.empty() ? 0 : *std::max_element(sym.ld.begin(), sym.ld.end());
+    need += sizeof(double) * (sym.front_doubles + (double)graph::kTile * (widest_ld + graph::kTile) + 36.0 * m +
+                              36.0 * marginal_requests) +
+            (sizeof(graph::SelInfo) + sizeof(int)) * (double)sym.n_fronts + sizeof(int) * (double)sym.upd.size() +
+            sizeof(graph::MargReq) * (double)marginal_requests;
   }
-  const int n = 6 * m, N = sparse ? n : std::max(graph::kTile, (int)align_up((size_t)n, graph::kTile));
-  // contributor lists (CSR by target block / by vertex slot), contributors in edge order
-  std::map<long long, std::vector<int>> blocks;
-  std::vector<std::vector<int>> bl(std::max(m, 1));
-  for (int k = 0; k < n_edges; ++k) {
-    const int f = slot[edges[k].from], t = slot[edges[k].to];
-    if (f >= 0) blocks[(long long)f * m + f].push_back(4 * k + 0), bl[f].push_back(2 * k + 0);
-    if (t >= 0) blocks[(long long)t * m + t].push_back(4 * k + 1), bl[t].push_back(2 * k + 1);
-    if (f >= 0 && t >= 0) {
-      blocks[(long long)f * m + t].push_back(4 * k + 2);
-      blocks[(long long)t * m + f].push_back(4 * k + 3);
+  return need;
+}
+
+// The fronts' device records and maps and the level schedule.  block_rc (the sorted (row, col) slots of the stored blocks) is
+// kept as slot_rc and rewritten in place to (k, 0): k_assemble_H then writes block k at Hs + 36 k with a row stride of 6.
+Solver::SparsePlan build_sparse_plan(const Symbolic &sym, std::vector<int2> &block_rc, int m) {
+  Solver::SparsePlan P;
+  Solver::SparsePlan &sched = P;
+  std::vector<int> &loc = P.loc, &hmap = P.hmap, &inv = P.inv, &child_list = P.child_list;
+  P.slot_rc = block_rc;
+  P.bsr_ptr.assign(m + 1, 0);
+  P.diag_block.assign(m, -1);
+  std::map<long long, int> block_index;
+  for (int k = 0; k < (int)block_rc.size(); ++k) {
+    ++P.bsr_ptr[block_rc[k].x + 1];
+    if (block_rc[k].x == block_rc[k].y) P.diag_block[block_rc[k].x] = k;
+    block_index[(long long)block_rc[k].x * m + block_rc[k].y] = k;
+    block_rc[k] = make_int2(k, 0);
+  }
+  for (int s = 0; s < m; ++s) P.bsr_ptr[s + 1] += P.bsr_ptr[s];
+  const int nf = sym.n_fronts;
+  sched.fronts.resize(nf);
+  long long a_off = 0, h_off = 0;
+  int v_off = 0;
+  for (int k = 0; k < nf; ++k) {
+    graph::Front &F = sched.fronts[k];
+    F.p = sym.piv_ptr[k + 1] - sym.piv_ptr[k];
+    F.u = sym.upd_ptr[k + 1] - sym.upd_ptr[k];
+    F.ld = sym.ld[k];
+    F.ppad = sym.ppad[k];
+    F.a_off = a_off;
+    F.v_off = v_off;
+    F.hmap_off = h_off;
+    F.loc_off = (int)loc.size();
+    a_off += (long long)F.ld * F.ld;
+    v_off += F.ld;
+    loc.insert(loc.end(), sym.piv.begin() + sym.piv_ptr[k], sym.piv.begin() + sym.piv_ptr[k + 1]);
+    loc.insert(loc.end(), sym.upd.begin() + sym.upd_ptr[k], sym.upd.begin() + sym.upd_ptr[k + 1]);
+    const int f = F.p + F.u;
+    hmap.resize(h_off + (long long)f * F.p, -1);
+    for (int r = 0; r < f; ++r)
+      for (int c = 0; c < F.p && c <= r; ++c) {
+        const auto it = block_index.find((long long)loc[F.loc_off + r] * m + loc[F.loc_off + c]);
+        if (it != block_index.end()) hmap[h_off + (long long)r * F.p + c] = it->second;
+      }
+    h_off += (long long)f * F.p;
+    F.ch_begin = (int)child_list.size();
+    child_list.insert(child_list.end(), sym.child.begin() + sym.child_ptr[k], sym.child.begin() + sym.child_ptr[k + 1]);
+    F.ch_end = (int)child_list.size();
+  }
+  // each child's map from its parent's local blocks into its own update set
+  std::vector<int> where(m, -1);
+  for (int k = 0; k < nf; ++k) {
+    const graph::Front &Pa = sched.fronts[k];
+    for (int q = sym.child_ptr[k]; q < sym.child_ptr[k + 1]; ++q) {
+      graph::Front &C = sched.fronts[sym.child[q]];
+      for (int j = 0; j < C.u; ++j) where[loc[C.loc_off + C.p + j]] = j;
+      C.inv_off = (int)inv.size();
+      for (int b = 0; b < Pa.p + Pa.u; ++b) inv.push_back(where[loc[Pa.loc_off + b]]);
+      for (int j = 0; j < C.u; ++j) where[loc[C.loc_off + C.p + j]] = -1;
     }
   }
-  std::vector<int2> block_rc;
-  std::vector<int> block_ptr(1, 0), block_c, b_ptr(1, 0), b_c;
-  for (const auto &kv : blocks) {
-    block_rc.push_back(make_int2((int)(kv.first / std::max(m, 1)), (int)(kv.first % std::max(m, 1))));
-    block_c.insert(block_c.end(), kv.second.begin(), kv.second.end());
-    block_ptr.push_back((int)block_c.size());
+  for (int k = 0; k < nf; ++k)
+    if (sym.parent[k] < 0) sched.fronts[k].inv_off = 0;  // roots have no parent and an empty update set
+  if (inv.empty()) inv.push_back(-1);
+  // the level schedule: fronts by level (leaves first), in front order within a level
+  const int L = sym.n_levels;
+  sched.level_begin.assign(1, 0);
+  sched.small_begin.assign(1, 0);
+  sched.small_count.assign(L, 0);
+  sched.wide.assign(L, {});
+  sched.max_ld.assign(L, 0);
+  for (int l = 0; l < L; ++l) {
+    for (int k = 0; k < nf; ++k) {
+      if (sym.level[k] != l) continue;
+      P.level_ids.push_back(k);
+      sched.max_ld[l] = std::max(sched.max_ld[l], sched.fronts[k].ld);
+      const bool wide = sched.fronts[k].ppad != 6 * sched.fronts[k].p || sched.fronts[k].ld > graph::kSmallMaxLd ||
+                        6 * sched.fronts[k].p > graph::kWidePivots;
+      if (wide)
+        sched.wide[l].push_back(k);
+      else
+        P.small_ids.push_back(k), ++sched.small_count[l];
+    }
+    sched.level_begin.push_back((int)P.level_ids.size());
+    sched.small_begin.push_back((int)P.small_ids.size());
   }
-  for (int s = 0; s < m; ++s) {
-    b_c.insert(b_c.end(), bl[s].begin(), bl[s].end());
-    b_ptr.push_back((int)b_c.size());
-  }
+  return P;
+}
 
-  // the sparse solver: symbolic phase, then the fronts' maps and the level schedule
-  Solver::Sparse sched;
-  Symbolic sym;
-  std::vector<int2> slot_rc;  // (row, col) slots of the stored blocks
-  std::vector<int> bsr_ptr, diag_block, hmap, inv, child_list, loc, level_ids, small_ids;
+// Puts the problem on the device for the unknowns U (checked by the caller): contributor lists; sparse: the symbolic phase, the
+// memory check and the plan; workspace growth, uploads, the cleared H and b, a Solver, the objective at the given estimate.
+int prepare(dvo_amd_context *ctx, const Problem &P, const dvo_amd_graph_options &opt, int marginal_requests, Unknowns &&U,
+            Prepared &out) {
+  out.U = std::move(U);
+  out.C = contributor_lists(out.U, P.n_edges, P.edges, false);
+  const bool sparse = opt.solver == DVO_AMD_GRAPH_SOLVER_SPARSE;
+  const int m = out.U.m, n = 6 * m, N = sparse ? n : std::max(graph::kTile, (int)align_up((size_t)n, graph::kTile));
+  const int n_vertices = P.n_vertices, n_edges = P.n_edges;
+  Contributors &C = out.C;
+  const Symbolic &sym = out.sym;
+  Solver::SparsePlan &plan = out.plan;
   double symbolic_ms = 0.0;
+  HIP_TRY(hipSetDevice(ctx->device));
   if (sparse) {
     const auto t0 = std::chrono::steady_clock::now();
-    sym = symbolic(block_adjacency(m, slot, n_edges, edges));
+    out.sym = symbolic(block_adjacency(m, out.U.slot, n_edges, P.edges));
     symbolic_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    // everything the sparse path grows: fronts, vectors, H blocks, the maps and the front records (the other buffers are the
-    // dense path's O(m + edges) ones); against 90 % of the free memory plus what the context already holds of these
-    double held = 0.0;
-    if (ctx->graph_ws)
-      for (const GraphWorkspace::Buf *b : {&ctx->graph_ws->A, &ctx->graph_ws->V, &ctx->graph_ws->Hs, &ctx->graph_ws->hmap,
-                                           &ctx->graph_ws->inv, &ctx->graph_ws->loc, &ctx->graph_ws->fronts})
-        held += (double)b->bytes;
-    double need = sizeof(double) * (sym.front_doubles + sym.vector_doubles + 36.0 * block_rc.size()) +
-                  sizeof(int) * sym.map_ints + sizeof(graph::Front) * (double)sym.n_fronts;
-    if (probe && probe->marg) {  // the inverse: a second arena of fronts, a tile column, six solved columns, maps, the blocks
-      if (ctx->graph_ws) held += (double)ctx->graph_ws->Zinv.bytes;
-      const int widest_ld = sym.ld.empty() ? 0 : *std::max_element(sym.ld.begin(), sym.ld.end());
-      need += sizeof(double) * (sym.front_doubles + (double)graph::kTile * (widest_ld + graph::kTile) + 36.0 * m +
-                                36.0 * probe->marg->n) +
-              (sizeof(graph::SelInfo) + sizeof(int)) * (double)sym.n_fronts + sizeof(int) * (double)sym.upd.size() +
-              sizeof(graph::MargReq) * (double)probe->marg->n;
-    }
+    // against 90 % of the free memory plus what the context already holds of the estimated buffers
+    const double held = ctx->graph_ws ? ctx->graph_ws->held_bytes(marginal_requests >= 0) : 0.0;
+    const double need = sparse_bytes_needed(sym, C.block_rc.size(), m, marginal_requests);
     if (need > ((double)free_b + held) * 0.9) {
-      g_last_error = entry + ": the sparse factorization needs " +
+      g_last_error = std::string(P.entry) + ": the sparse factorization needs " +
                      std::to_string((long long)(need / 1048576.0)) + " MiB of device storage";
       return DVO_AMD_ERR_OUT_OF_MEMORY;
     }
-    slot_rc = block_rc;
-    bsr_ptr.assign(m + 1, 0);
-    diag_block.assign(m, -1);
-    std::map<long long, int> block_index;
-    for (int k = 0; k < (int)block_rc.size(); ++k) {
-      ++bsr_ptr[block_rc[k].x + 1];
-      if (block_rc[k].x == block_rc[k].y) diag_block[block_rc[k].x] = k;
-      block_index[(long long)block_rc[k].x * m + block_rc[k].y] = k;
-      block_rc[k] = make_int2(k, 0);
-    }
-    for (int s = 0; s < m; ++s) bsr_ptr[s + 1] += bsr_ptr[s];
-    const int nf = sym.n_fronts;
-    sched.fronts.resize(nf);
-    long long a_off = 0, h_off = 0;
-    int v_off = 0;
-    for (int k = 0; k < nf; ++k) {
-      graph::Front &F = sched.fronts[k];
-      F.p = sym.piv_ptr[k + 1] - sym.piv_ptr[k];
-      F.u = sym.upd_ptr[k + 1] - sym.upd_ptr[k];
-      F.ld = sym.ld[k];
-      F.ppad = sym.ppad[k];
-      F.a_off = a_off;
-      F.v_off = v_off;
-      F.hmap_off = h_off;
-      F.loc_off = (int)loc.size();
-      a_off += (long long)F.ld * F.ld;
-      v_off += F.ld;
-      loc.insert(loc.end(), sym.piv.begin() + sym.piv_ptr[k], sym.piv.begin() + sym.piv_ptr[k + 1]);
-      loc.insert(loc.end(), sym.upd.begin() + sym.upd_ptr[k], sym.upd.begin() + sym.upd_ptr[k + 1]);
-      const int f = F.p + F.u;
-      hmap.resize(h_off + (long long)f * F.p, -1);
-      for (int r = 0; r < f; ++r)
-        for (int c = 0; c < F.p && c <= r; ++c) {
-          const auto it = block_index.find((long long)loc[F.loc_off + r] * m + loc[F.loc_off + c]);
-          if (it != block_index.end()) hmap[h_off + (long long)r * F.p + c] = it->second;
-        }
-      h_off += (long long)f * F.p;
-      F.ch_begin = (int)child_list.size();
-      child_list.insert(child_list.end(), sym.child.begin() + sym.child_ptr[k], sym.child.begin() + sym.child_ptr[k + 1]);
-      F.ch_end = (int)child_list.size();
-    }
-    // each child's map from its parent's local blocks into its own update set
-    std::vector<int> where(m, -1);
-    for (int k = 0; k < nf; ++k) {
-      const graph::Front &P = sched.fronts[k];
-      for (int q = sym.child_ptr[k]; q < sym.child_ptr[k + 1]; ++q) {
-        graph::Front &C = sched.fronts[sym.child[q]];
-        for (int j = 0; j < C.u; ++j) where[loc[C.loc_off + C.p + j]] = j;
-        C.inv_off = (int)inv.size();
-        for (int b = 0; b < P.p + P.u; ++b) inv.push_back(where[loc[P.loc_off + b]]);
-        for (int j = 0; j < C.u; ++j) where[loc[C.loc_off + C.p + j]] = -1;
-      }
-    }
-    for (int k = 0; k < nf; ++k)
-      if (sym.parent[k] < 0) sched.fronts[k].inv_off = 0;  // roots have no parent and an empty update set
-    if (inv.empty()) inv.push_back(-1);
-    // the level schedule: fronts by level (leaves first), in front order within a level
-    const int L = sym.n_levels;
-    sched.level_begin.assign(1, 0);
-    sched.small_begin.assign(1, 0);
-    sched.small_count.assign(L, 0);
-    sched.wide.assign(L, {});
-    sched.max_ld.assign(L, 0);
-    for (int l = 0; l < L; ++l) {
-      for (int k = 0; k < nf; ++k) {
-        if (sym.level[k] != l) continue;
-        level_ids.push_back(k);
-        sched.max_ld[l] = std::max(sched.max_ld[l], sched.fronts[k].ld);
-        const bool wide = sched.fronts[k].ppad != 6 * sched.fronts[k].p || sched.fronts[k].ld > graph::kSmallMaxLd ||
-                          6 * sched.fronts[k].p > graph::kWidePivots;
-        if (wide)
-          sched.wide[l].push_back(k);
-        else
-          small_ids.push_back(k), ++sched.small_count[l];
-      }
-      sched.level_begin.push_back((int)level_ids.size());
-      sched.small_begin.push_back((int)small_ids.size());
-    }
+    plan = build_sparse_plan(sym, C.block_rc, m);
   }
-
-  HIP_TRY(hipSetDevice(ctx->device));
   GraphWorkspace *Wp = nullptr;
   GRAPH_TRY(workspace(ctx, &Wp));
   GraphWorkspace &W = *Wp;
-  const size_t E = std::max(n_edges, 1), V = std::max(n_vertices, 1);
-  GRAPH_TRY(grow(W.poses, 16 * sizeof(double) * V));
-  GRAPH_TRY(grow(W.saved, 16 * sizeof(double) * V));
-  GRAPH_TRY(grow(W.edges, sizeof(dvo_amd_graph_edge) * E));
+  const size_t E = std::max(n_edges, 1);
+  const std::vector<int> &vertex_of = out.U.vertex_of;
+  const struct {
+    DeviceBuf &buf;
+    const void *src;
+    size_t bytes;
+  } uploads[] = {{W.poses, P.poses, 16 * sizeof(double) * n_vertices}, {W.edges, P.edges, sizeof(dvo_amd_graph_edge) * n_edges},
+                 {W.block_rc, C.block_rc.data(), sizeof(int2) * C.block_rc.size()},
+                 {W.block_ptr, C.block_ptr.data(), sizeof(int) * C.block_ptr.size()},
+                 {W.block_c, C.block_c.data(), sizeof(int) * C.block_c.size()},
+                 {W.b_ptr, C.b_ptr.data(), sizeof(int) * C.b_ptr.size()}, {W.b_c, C.b_c.data(), sizeof(int) * C.b_c.size()},
+                 {W.vertex_of, vertex_of.data(), sizeof(int) * vertex_of.size()}};
+  for (const auto &u : uploads) GRAPH_TRY(grow(u.buf, std::max<size_t>(1, u.bytes)));
+  GRAPH_TRY(grow(W.saved, 16 * sizeof(double) * std::max(n_vertices, 1)));
   GRAPH_TRY(grow(W.rec, sizeof(double) * graph::kRecord * E));
-  GRAPH_TRY(grow(W.rho0, sizeof(double) * E));
-  GRAPH_TRY(grow(W.chi2, sizeof(double) * E));
-  GRAPH_TRY(grow(W.rho1, sizeof(double) * E));
+  for (DeviceBuf *b : {&W.rho0, &W.chi2, &W.rho1}) GRAPH_TRY(grow(*b, sizeof(double) * E));
   if (!sparse) {
     GRAPH_TRY(grow(W.H, sizeof(double) * (size_t)N * N));
     GRAPH_TRY(grow(W.L, sizeof(double) * (size_t)N * N));
   }
   // at least one double: a sparse call with no free active vertex has N = 0 and still clears b
-  for (GraphWorkspace::Buf *b : {&W.b, &W.x, &W.hsd, &W.hdl, &W.aux}) GRAPH_TRY(grow(*b, sizeof(double) * std::max(N, 1)));
-  GRAPH_TRY(grow(W.block_rc, sizeof(int2) * std::max<size_t>(1, block_rc.size())));
-  GRAPH_TRY(grow(W.block_ptr, sizeof(int) * block_ptr.size()));
-  GRAPH_TRY(grow(W.block_c, sizeof(int) * std::max<size_t>(1, block_c.size())));
-  GRAPH_TRY(grow(W.b_ptr, sizeof(int) * b_ptr.size()));
-  GRAPH_TRY(grow(W.b_c, sizeof(int) * std::max<size_t>(1, b_c.size())));
-  GRAPH_TRY(grow(W.vertex_of, sizeof(int) * std::max<size_t>(1, vertex_of.size())));
+  for (DeviceBuf *b : {&W.b, &W.x, &W.hsd, &W.hdl, &W.aux}) GRAPH_TRY(grow(*b, sizeof(double) * std::max(N, 1)));
   GRAPH_TRY(grow(W.scalars, sizeof(double) * graph::kMaxDots));
   GRAPH_TRY(grow(W.flag, sizeof(int)));
   W.n_padded = N;
   W.factorizations = 0;
   W.lin_ms = W.fac_ms = 0.0;
   const hipStream_t st = ctx->stream;
-  auto up = [&](GraphWorkspace::Buf &b, const void *src, size_t bytes) {
-    return bytes ? hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-  };
   if (sparse) {
-    auto grow_up = [&](GraphWorkspace::Buf &b, const void *src, size_t bytes) {
-      const int rc = grow(b, std::max<size_t>(bytes, 1));
-      return rc ? rc : (up(b, src, bytes) == hipSuccess ? DVO_AMD_OK : fail_hip("hipMemcpyAsync (sparse maps)", hipGetLastError()));
+    auto grow_up = [&](DeviceBuf &b, const void *src, size_t bytes) {
+      return grow_upload(b, src, bytes, st, "graph workspace", "sparse maps");
     };
-    GRAPH_TRY(grow(W.Hs, sizeof(double) * 36 * std::max<size_t>(1, block_rc.size())));
-    GRAPH_TRY(grow_up(W.bsr_ptr, bsr_ptr.data(), sizeof(int) * bsr_ptr.size()));
-    GRAPH_TRY(grow_up(W.bsr_rc, slot_rc.data(), sizeof(int2) * slot_rc.size()));
-    GRAPH_TRY(grow_up(W.diag_block, diag_block.data(), sizeof(int) * diag_block.size()));
-    GRAPH_TRY(grow_up(W.fronts, sched.fronts.data(), sizeof(graph::Front) * sched.fronts.size()));
-    GRAPH_TRY(grow_up(W.hmap, hmap.data(), sizeof(int) * hmap.size()));
-    GRAPH_TRY(grow_up(W.inv, inv.data(), sizeof(int) * inv.size()));
-    GRAPH_TRY(grow_up(W.child_list, child_list.data(), sizeof(int) * child_list.size()));
-    GRAPH_TRY(grow_up(W.loc, loc.data(), sizeof(int) * loc.size()));
-    GRAPH_TRY(grow_up(W.level_ids, level_ids.data(), sizeof(int) * level_ids.size()));
-    GRAPH_TRY(grow_up(W.small_ids, small_ids.data(), sizeof(int) * small_ids.size()));
+    GRAPH_TRY(grow(W.Hs, sizeof(double) * 36 * std::max<size_t>(1, C.block_rc.size())));
+    GRAPH_TRY(grow_up(W.bsr_ptr, plan.bsr_ptr.data(), sizeof(int) * plan.bsr_ptr.size()));
+    GRAPH_TRY(grow_up(W.bsr_rc, plan.slot_rc.data(), sizeof(int2) * plan.slot_rc.size()));
+    GRAPH_TRY(grow_up(W.diag_block, plan.diag_block.data(), sizeof(int) * plan.diag_block.size()));
+    GRAPH_TRY(grow_up(W.fronts, plan.fronts.data(), sizeof(graph::Front) * plan.fronts.size()));
+    GRAPH_TRY(grow_up(W.hmap, plan.hmap.data(), sizeof(int) * plan.hmap.size()));
+    GRAPH_TRY(grow_up(W.inv, plan.inv.data(), sizeof(int) * plan.inv.size()));
+    GRAPH_TRY(grow_up(W.child_list, plan.child_list.data(), sizeof(int) * plan.child_list.size()));
+    GRAPH_TRY(grow_up(W.loc, plan.loc.data(), sizeof(int) * plan.loc.size()));
+    GRAPH_TRY(grow_up(W.level_ids, plan.level_ids.data(), sizeof(int) * plan.level_ids.size()));
+    GRAPH_TRY(grow_up(W.small_ids, plan.small_ids.data(), sizeof(int) * plan.small_ids.size()));
     GRAPH_TRY(grow(W.A, sizeof(double) * (size_t)sym.front_doubles));
-    size_t v_total = 0;
-    for (const graph::Front &F : sched.fronts) v_total += F.ld;
-    GRAPH_TRY(grow(W.V, sizeof(double) * v_total));
+    GRAPH_TRY(grow(W.V, sizeof(double) * (size_t)sym.vector_doubles));
     W.sp_symbolic_ms = symbolic_ms;
     W.sp_lin_ms = W.sp_fac_ms = W.sp_solve_ms = 0.0;
     W.sp_fronts = sym.n_fronts;
@@ -1937,56 +1897,37 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
     W.sp_factor_doubles = sym.factor_doubles;
     W.sp_flops = sym.flops;
   }
-  HIP_TRY(up(W.poses, poses, 16 * sizeof(double) * n_vertices));
-  HIP_TRY(up(W.edges, edges, sizeof(dvo_amd_graph_edge) * n_edges));
-  HIP_TRY(up(W.block_rc, block_rc.data(), sizeof(int2) * block_rc.size()));
-  HIP_TRY(up(W.block_ptr, block_ptr.data(), sizeof(int) * block_ptr.size()));
-  HIP_TRY(up(W.block_c, block_c.data(), sizeof(int) * block_c.size()));
-  HIP_TRY(up(W.b_ptr, b_ptr.data(), sizeof(int) * b_ptr.size()));
-  HIP_TRY(up(W.b_c, b_c.data(), sizeof(int) * b_c.size()));
-  HIP_TRY(up(W.vertex_of, vertex_of.data(), sizeof(int) * vertex_of.size()));
+  for (const auto &u : uploads)
+    if (u.bytes) HIP_TRY(hipMemcpyAsync(u.buf.p, u.src, u.bytes, hipMemcpyHostToDevice, st));
   // blocks no edge touches stay zero; the padding is the identity (its unknowns solve to 0)
   if (!sparse) HIP_TRY(hipMemsetAsync(W.H.p, 0, sizeof(double) * (size_t)N * N, st));
   HIP_TRY(hipMemsetAsync(W.b.p, 0, sizeof(double) * std::max(N, 1), st));
   if (N > n) hipLaunchKernelGGL(graph::k_pad_diag, dim3(graph::grid_for(N - n, 64)), dim3(64), 0, st, (double *)W.H.p, N, n);
   HIP_TRY(hipGetLastError());
+  out.solver.emplace(Solver{W, st, n_vertices, n_edges, m, n, N, (int)C.block_rc.size(), opt.robust_delta});
+  if (sparse) out.solver->sp = &plan;
+  return out.solver->objective(&out.F0);
+}
 
-  Solver S{W, st, n_vertices, n_edges, m, n, N, (int)block_rc.size(), opt.robust_delta};
-  if (sparse) S.sp = &sched;
-  double F = 0.0;
-  GRAPH_TRY(S.objective(&F));
+// dvo_amd_optimize_graph: LM or dogleg from the given estimate; the free active vertices' poses are written back
+int optimize(dvo_amd_context *ctx, const Problem &P, double *poses, const dvo_amd_graph_options &opt, double *edge_chi2,
+             double *edge_weight, int capacity, dvo_amd_graph_iteration *iterations, dvo_amd_graph_stats &stats) {
+  Unknowns U;
+  const int refused = checked_unknowns(P, opt, U);
+  stats.n_free = U.m;
+  if (refused) return refused;
+  Prepared R;
+  GRAPH_TRY(prepare(ctx, P, opt, -1, std::move(U), R));
+  Solver &S = *R.solver;
+  GraphWorkspace &W = S.W;
+  const hipStream_t st = S.st;
+  const int n_vertices = P.n_vertices, n_edges = P.n_edges;
+  double F = R.F0;
   stats.initial_objective = F;
-  if (probe) {
-    if (probe->F) *probe->F = F;
-    if (m == 0) return DVO_AMD_OK;
-    GRAPH_TRY(S.linearise());
-    GRAPH_TRY(S.factor_solve_enqueue(false, 0.0, S.x()));
-    int f = -1;
-    GRAPH_TRY(S.read(nullptr, 0, &f));
-    if (probe->failed_pivot) *probe->failed_pivot = f;
-    if (probe->marg) {
-      probe->marg->failed_pivot = f;
-      if (f >= 0) return DVO_AMD_OK;
-      return marginals_stage(S, *probe->marg, slot, sparse ? &sym : nullptr, loc);
-    }
-    if (sparse) {
-      const int nb = (int)slot_rc.size();
-      if (probe->n_blocks) *probe->n_blocks = nb;
-      if (probe->block_rc && nb <= probe->block_capacity)
-        for (int k = 0; k < nb; ++k) probe->block_rc[2 * k] = slot_rc[k].x, probe->block_rc[2 * k + 1] = slot_rc[k].y;
-      if (probe->blocks && nb <= probe->block_capacity)
-        HIP_TRY(hipMemcpyAsync(probe->blocks, W.Hs.p, sizeof(double) * 36 * nb, hipMemcpyDeviceToHost, st));
-    } else if (probe->H) HIP_TRY(hipMemcpy2DAsync(probe->H, sizeof(double) * n, W.H.p, sizeof(double) * N, sizeof(double) * n, n,
-                                           hipMemcpyDeviceToHost, st));
-    if (probe->b) HIP_TRY(hipMemcpyAsync(probe->b, W.b.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    if (probe->x) HIP_TRY(hipMemcpyAsync(probe->x, W.x.p, sizeof(double) * n, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return DVO_AMD_OK;
-  }
   stats.termination = DVO_AMD_GRAPH_ITERATIONS_EXHAUSTED;
   stats.delta = opt.algorithm == DVO_AMD_GRAPH_DOGLEG ? opt.initial_delta : 0.0;
   stats.lambda = opt.algorithm == DVO_AMD_GRAPH_DOGLEG ? opt.initial_lambda : 0.0;
-  if (m > 0) {
+  if (S.m > 0) {
     if (opt.algorithm == DVO_AMD_GRAPH_LEVENBERG)
       GRAPH_TRY(run_levenberg(S, opt, &F, iterations, capacity, stats));
     else
@@ -2004,12 +1945,12 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
   std::vector<double> out(16 * (size_t)std::max(n_vertices, 1));
   if (n_vertices) HIP_TRY(hipMemcpyAsync(out.data(), W.poses.p, 16 * sizeof(double) * n_vertices, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  for (int v : vertex_of) std::memcpy(poses + 16 * (size_t)v, out.data() + 16 * (size_t)v, 16 * sizeof(double));
+  for (int v : R.U.vertex_of) std::memcpy(poses + 16 * (size_t)v, out.data() + 16 * (size_t)v, 16 * sizeof(double));
   if (S.timed_lin) {
     float ms = 0.0f;
     if (hipEventElapsedTime(&ms, W.ev[0], W.ev[1]) == hipSuccess) W.lin_ms = ms;
     if (hipEventElapsedTime(&ms, W.ev[2], W.ev[3]) == hipSuccess) W.fac_ms = ms;
-    if (sparse) {
+    if (S.sp) {
       W.sp_lin_ms = W.lin_ms;
       W.sp_fac_ms = W.fac_ms;
       if (hipEventElapsedTime(&ms, W.ev[3], W.ev[4]) == hipSuccess) W.sp_solve_ms = ms;
@@ -2018,10 +1959,64 @@ int optimize(dvo_amd_context *ctx, int n_vertices, double *poses, const int *fix
   return DVO_AMD_OK;
 }
 
-int have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
+// the system at the given estimate and its undamped solve H x = b into x; *failed_pivot >= 0: H was not positive definite
+int undamped_system(Solver &S, int *failed_pivot) {
+  GRAPH_TRY(S.linearise());
+  GRAPH_TRY(S.factor_solve_enqueue(false, 0.0, S.x()));
+  return S.read(nullptr, 0, failed_pivot);
+}
+
+// dvo_amd_debug_graph_system and _sparse: the outputs of the first linear system (null: not wanted)
+struct FirstSystem {
+  double *H, *b, *x, *F;
+  int *n_free, *failed_pivot;
+  // the sparse entry: the stored blocks (row, col slots; 36 doubles each, row-major), capacity in / count out
+  int *block_rc = nullptr;
+  double *blocks = nullptr;
+  int block_capacity = 0;
+  int *n_blocks = nullptr;
+};
+
+int first_system(dvo_amd_context *ctx, const Problem &P, const dvo_amd_graph_options &opt, const FirstSystem &out) {
+  Unknowns U;
+  const int refused = checked_unknowns(P, opt, U);
+  if (out.n_free) *out.n_free = U.m;
+  if (refused) return refused;
+  Prepared R;
+  GRAPH_TRY(prepare(ctx, P, opt, -1, std::move(U), R));
+  Solver &S = *R.solver;
+  GraphWorkspace &W = S.W;
+  const int n = S.n;
+  if (out.F) *out.F = R.F0;
+  if (S.m == 0) return DVO_AMD_OK;
+  int f = -1;
+  GRAPH_TRY(undamped_system(S, &f));
+  if (out.failed_pivot) *out.failed_pivot = f;
+  if (S.sp) {
+    const std::vector<int2> &slot_rc = R.plan.slot_rc;
+    const int nb = (int)slot_rc.size();
+    if (out.n_blocks) *out.n_blocks = nb;
+    if (out.block_rc && nb <= out.block_capacity)
+      for (int k = 0; k < nb; ++k) out.block_rc[2 * k] = slot_rc[k].x, out.block_rc[2 * k + 1] = slot_rc[k].y;
+    if (out.blocks && nb <= out.block_capacity)
+      HIP_TRY(hipMemcpyAsync(out.blocks, W.Hs.p, sizeof(double) * 36 * nb, hipMemcpyDeviceToHost, S.st));
+  } else if (out.H)
+    HIP_TRY(hipMemcpy2DAsync(out.H, sizeof(double) * n, W.H.p, sizeof(double) * S.N, sizeof(double) * n, n,
+                             hipMemcpyDeviceToHost, S.st));
+  if (out.b) HIP_TRY(hipMemcpyAsync(out.b, W.b.p, sizeof(double) * n, hipMemcpyDeviceToHost, S.st));
+  if (out.x) HIP_TRY(hipMemcpyAsync(out.x, W.x.p, sizeof(double) * n, hipMemcpyDeviceToHost, S.st));
+  HIP_TRY(hipStreamSynchronize(S.st));
   return DVO_AMD_OK;
+}
+
+// dvo_amd_graph_marginals: the undamped factorization at the given estimate, then J's blocks of H^-1 (none if a pivot failed)
+int marginals(dvo_amd_context *ctx, const Problem &P, const dvo_amd_graph_options &opt, Unknowns &&U, MargJob &J) {
+  Prepared R;
+  GRAPH_TRY(prepare(ctx, P, opt, J.n, std::move(U), R));
+  if (R.U.m == 0) return DVO_AMD_OK;
+  GRAPH_TRY(undamped_system(*R.solver, &J.failed_pivot));
+  if (J.failed_pivot >= 0) return DVO_AMD_OK;
+  return marginals_stage(R, J);
 }
 
 }  // namespace
@@ -2029,13 +2024,9 @@ int have_device() {
 void graph_workspace_release(dvo_amd_context *ctx) {
   GraphWorkspace *w = ctx->graph_ws;
   if (!w) return;
-  for (GraphWorkspace::Buf *b : {&w->poses, &w->saved, &w->edges, &w->rec, &w->rho0, &w->chi2, &w->rho1, &w->H, &w->L, &w->b,
-                                 &w->x, &w->hsd, &w->hdl, &w->aux, &w->block_rc, &w->block_ptr, &w->block_c, &w->b_ptr,
-                                 &w->b_c, &w->vertex_of, &w->scalars, &w->flag, &w->Hs, &w->bsr_ptr, &w->bsr_rc,
-                                 &w->diag_block, &w->fronts, &w->hmap, &w->inv, &w->child_list, &w->loc, &w->level_ids,
-                                 &w->small_ids, &w->A, &w->V, &w->Zinv, &w->sel_info, &w->up, &w->ytiles, &w->wtile,
-                                 &w->mreq, &w->creq, &w->cols, &w->mout})
-    if (b->p) (void)hipFree(b->p);
+  w->each_buf([](DeviceBuf &b) {
+    if (b.p) (void)hipFree(b.p);
+  });
   for (hipEvent_t e : w->ev)
     if (e) (void)hipEventDestroy(e);
   delete w;
@@ -2072,15 +2063,15 @@ int dvo_amd_optimize_graph(dvo_amd_context *ctx, int n_vertices, double *poses, 
   dvo_amd_graph_stats local;
   dvo_amd_graph_stats &s = stats ? *stats : local;
   std::memset(&s, 0, sizeof(s));
-  int rc = host::check_arguments(n_vertices, poses, n_edges, edges, opt);
+  int rc = host::graph_check_arguments("dvo_amd_optimize_graph", n_vertices, poses, n_edges, edges, opt);
   if (rc) return rc;
   rc = host::have_device();
   if (rc) return rc;
   if (!ctx || iteration_capacity < 0 || (iteration_capacity > 0 && !iterations)) return DVO_AMD_ERR_INVALID_ARGUMENT;
   rc = queue_must_be_idle(ctx, "dvo_amd_optimize_graph");
   if (rc) return rc;
-  return host::optimize(ctx, n_vertices, poses, fixed, n_edges, edges, *opt, edge_chi2, edge_weight, iteration_capacity,
-                        iterations, s);
+  const host::Problem P{"dvo_amd_optimize_graph", n_vertices, poses, fixed, n_edges, edges};
+  return host::optimize(ctx, P, poses, *opt, edge_chi2, edge_weight, iteration_capacity, iterations, s);
 }
 
 int dvo_amd_graph_marginals(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,
@@ -2100,23 +2091,16 @@ int dvo_amd_graph_marginals(dvo_amd_context *ctx, int n_vertices, const double *
   for (int k = 0; k < n_blocks; ++k)
     if (block_a[k] < 0 || block_a[k] >= n_vertices || block_b[k] < 0 || block_b[k] >= n_vertices)
       return bad("vertex index out of range (block " + std::to_string(k) + ")");
-  std::vector<char> active(std::max(n_vertices, 1), 0);
-  for (int k = 0; k < n_edges; ++k) active[edges[k].from] = active[edges[k].to] = 1;
-  int m = 0;
-  for (int v = 0; v < n_vertices; ++v) m += active[v] && !(fixed && fixed[v]);
-  const bool sparse = opt->solver == DVO_AMD_GRAPH_SOLVER_SPARSE;
-  const int cap = sparse ? DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE : DVO_AMD_GRAPH_MAX_FREE_VERTICES;
-  if (m > cap) {
-    g_last_error = "dvo_amd_graph_marginals: " + std::to_string(m) + " free active vertices (the " +
-                   (sparse ? "sparse" : "dense") + " solver takes at most " + std::to_string(cap) + ")";
-    return DVO_AMD_ERR_CAPACITY;
-  }
+  const host::Problem P{"dvo_amd_graph_marginals", n_vertices, poses, fixed, n_edges, edges};
+  host::Unknowns U;
+  rc = host::checked_unknowns(P, *opt, U);  // before the device is asked for: a graph beyond the capacity is refused anywhere
+  if (rc) return rc;
   rc = host::have_device();
   if (rc) return rc;
   if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
   rc = queue_must_be_idle(ctx, "dvo_amd_graph_marginals");
   if (rc) return rc;
-  // blocks that touch a fixed vertex are zeros, else those that touch an inactive one NaN; the others go to the device
+  // blocks that touch a fixed vertex are zeros, else those that touch an inactive one (no slot) NaN; the others go to the device
   const double nan = std::numeric_limits<double>::quiet_NaN();
   std::vector<int> kind(std::max(n_blocks, 1), 0), qa, qb, at;
   int n_fixed = 0, n_inactive = 0;
@@ -2124,7 +2108,7 @@ int dvo_amd_graph_marginals(dvo_amd_context *ctx, int n_vertices, const double *
     const int a = block_a[k], b = block_b[k];
     if (fixed && (fixed[a] || fixed[b])) {
       kind[k] = 1, ++n_fixed;
-    } else if (!active[a] || !active[b]) {
+    } else if (U.slot[a] < 0 || U.slot[b] < 0) {
       kind[k] = 2, ++n_inactive;
     } else {
       qa.push_back(a), qb.push_back(b), at.push_back(k);
@@ -2136,19 +2120,15 @@ int dvo_amd_graph_marginals(dvo_amd_context *ctx, int n_vertices, const double *
   job.a = qa.data();
   job.b = qb.data();
   job.out = out.data();
-  std::vector<double> copy(poses, poses + 16 * (size_t)n_vertices);  // the entry does not move any pose
-  dvo_amd_graph_stats st;
-  std::memset(&st, 0, sizeof(st));
-  host::Probe probe{nullptr, nullptr, nullptr, nullptr, nullptr};
-  probe.marg = &job;
-  rc = host::optimize(ctx, n_vertices, copy.data(), fixed, n_edges, edges, *opt, nullptr, nullptr, 0, nullptr, st, &probe);
+  const int n_free = U.m;
+  rc = host::marginals(ctx, P, *opt, std::move(U), job);
   if (rc) return rc;
   const bool ok = job.failed_pivot < 0;
   for (int k = 0; k < n_blocks; ++k)
     for (int e = 0; e < 36; ++e) blocks[36 * (size_t)k + e] = kind[k] == 1 ? 0.0 : nan;
   if (ok)
     for (size_t i = 0; i < at.size(); ++i) std::memcpy(blocks + 36 * (size_t)at[i], out.data() + 36 * i, 36 * sizeof(double));
-  s.n_free = st.n_free;
+  s.n_free = n_free;
   s.factorized = ok ? 1 : 0;
   s.fixed_blocks = n_fixed;
   s.inactive_blocks = n_inactive;
@@ -2156,55 +2136,41 @@ int dvo_amd_graph_marginals(dvo_amd_context *ctx, int n_vertices, const double *
   return DVO_AMD_OK;
 }
 
-int dvo_amd_debug_graph_system(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,
-                               const dvo_amd_graph_edge *edges, double robust_delta, double *H, double *b, double *x,
-                               double *F, int *n_free, int *failed_pivot) {
+// both first-system entries: dogleg's defaults with the given robust_delta and solver; their refusals carry the optimizer's name
+static int debug_first_system(dvo_amd_context *ctx, const char *entry, int n_vertices, const double *poses, const int *fixed,
+                              int n_edges, const dvo_amd_graph_edge *edges, double robust_delta, int solver,
+                              const host::FirstSystem &out) {
   dvo_amd_graph_options opt;
   dvo_amd_default_graph_options(DVO_AMD_GRAPH_DOGLEG, &opt);
   opt.robust_delta = robust_delta;
-  int rc = host::check_arguments(n_vertices, poses, n_edges, edges, &opt);
+  opt.solver = solver;
+  const host::Problem P{"dvo_amd_optimize_graph", n_vertices, poses, fixed, n_edges, edges};
+  int rc = host::graph_check_arguments(P.entry, n_vertices, poses, n_edges, edges, &opt);
   if (rc) return rc;
+  if (out.block_capacity < 0) return DVO_AMD_ERR_INVALID_ARGUMENT;
   rc = host::have_device();
   if (rc) return rc;
   if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  rc = queue_must_be_idle(ctx, "dvo_amd_debug_graph_system");
+  rc = queue_must_be_idle(ctx, entry);
   if (rc) return rc;
-  std::vector<double> copy(poses, poses + 16 * (size_t)n_vertices);  // the entry does not move any pose
-  dvo_amd_graph_stats st;
-  std::memset(&st, 0, sizeof(st));
-  const host::Probe probe{H, b, x, F, failed_pivot};
-  rc = host::optimize(ctx, n_vertices, copy.data(), fixed, n_edges, edges, opt, nullptr, nullptr, 0, nullptr, st, &probe);
-  if (n_free) *n_free = st.n_free;
-  return rc;
+  return host::first_system(ctx, P, opt, out);
+}
+
+int dvo_amd_debug_graph_system(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed, int n_edges,
+                               const dvo_amd_graph_edge *edges, double robust_delta, double *H, double *b, double *x,
+                               double *F, int *n_free, int *failed_pivot) {
+  return debug_first_system(ctx, "dvo_amd_debug_graph_system", n_vertices, poses, fixed, n_edges, edges, robust_delta,
+                            DVO_AMD_GRAPH_SOLVER_DENSE, host::FirstSystem{H, b, x, F, n_free, failed_pivot});
 }
 
 int dvo_amd_debug_graph_system_sparse(dvo_amd_context *ctx, int n_vertices, const double *poses, const int *fixed,
                                       int n_edges, const dvo_amd_graph_edge *edges, double robust_delta, int block_capacity,
                                       int *n_blocks, int *block_rc, double *blocks, double *b, double *x, double *F,
                                       int *n_free, int *failed_pivot) {
-  dvo_amd_graph_options opt;
-  dvo_amd_default_graph_options(DVO_AMD_GRAPH_DOGLEG, &opt);
-  opt.robust_delta = robust_delta;
-  opt.solver = DVO_AMD_GRAPH_SOLVER_SPARSE;
-  int rc = host::check_arguments(n_vertices, poses, n_edges, edges, &opt);
-  if (rc) return rc;
-  if (block_capacity < 0) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  rc = host::have_device();
-  if (rc) return rc;
-  if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  rc = queue_must_be_idle(ctx, "dvo_amd_debug_graph_system_sparse");
-  if (rc) return rc;
-  std::vector<double> copy(poses, poses + 16 * (size_t)n_vertices);
-  dvo_amd_graph_stats st;
-  std::memset(&st, 0, sizeof(st));
   int nb = 0;
-  host::Probe probe{nullptr, b, x, F, failed_pivot};
-  probe.block_rc = block_rc;
-  probe.blocks = blocks;
-  probe.block_capacity = block_capacity;
-  probe.n_blocks = &nb;
-  rc = host::optimize(ctx, n_vertices, copy.data(), fixed, n_edges, edges, opt, nullptr, nullptr, 0, nullptr, st, &probe);
-  if (n_free) *n_free = st.n_free;
+  const host::FirstSystem out{nullptr, b, x, F, n_free, failed_pivot, block_rc, blocks, block_capacity, &nb};
+  const int rc = debug_first_system(ctx, "dvo_amd_debug_graph_system_sparse", n_vertices, poses, fixed, n_edges, edges,
+                                    robust_delta, DVO_AMD_GRAPH_SOLVER_SPARSE, out);
   if (n_blocks) *n_blocks = nb;
   if (!rc && nb > block_capacity && (block_rc || blocks)) return DVO_AMD_ERR_CAPACITY;
   return rc;
@@ -2219,15 +2185,11 @@ int dvo_amd_debug_graph_symbolic(int n_vertices, const int *fixed, int n_edges, 
     if (edges[k].from < 0 || edges[k].from >= n_vertices || edges[k].to < 0 || edges[k].to >= n_vertices ||
         edges[k].from == edges[k].to)
       return DVO_AMD_ERR_INVALID_ARGUMENT;
-  std::vector<char> active(n_vertices, 0);
-  for (int k = 0; k < n_edges; ++k) active[edges[k].from] = active[edges[k].to] = 1;
-  std::vector<int> slot(n_vertices, -1);
-  int m = 0;
-  for (int v = 0; v < n_vertices; ++v)
-    if (active[v] && !(fixed && fixed[v])) slot[v] = m++;
+  const host::Unknowns U = host::free_unknowns(n_vertices, fixed, n_edges, edges);
+  const int m = U.m;
   if (n_free) *n_free = m;
   if (m > DVO_AMD_GRAPH_MAX_FREE_VERTICES_SPARSE) return DVO_AMD_ERR_CAPACITY;
-  const host::Symbolic S = host::symbolic(host::block_adjacency(m, slot, n_edges, edges));
+  const host::Symbolic S = host::symbolic(host::block_adjacency(m, U.slot, n_edges, edges));
   const int nf = S.n_fronts, nu = (int)S.upd.size();
   if (n_fronts) *n_fronts = nf;
   if (n_update) *n_update = nu;

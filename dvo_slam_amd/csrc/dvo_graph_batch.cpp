@@ -25,12 +25,11 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
 #include "dvo_graph_device.h"
-#include "dvo_internal.h"
+#include "dvo_graph_host.h"
 
 namespace dvo_amd {
 namespace graph_batch {
@@ -567,12 +566,12 @@ __global__ void __launch_bounds__(kThreads) k_optimize_batch(Buffers B, Params P
 
 namespace host {
 
+#define GRAPH_BATCH_BUFS(X) \
+  X(items) X(edges) X(poses) X(saved) X(rec) X(chi2) X(rho1) X(H) X(block_rc) X(block_ptr) X(block_c) X(b_ptr) X(b_c) \
+  X(vertex_of) X(out) X(records)
+
 struct GraphBatchWorkspace {
-  struct Buf {
-    void *p = nullptr;
-    size_t bytes = 0;
-  };
-  Buf items, edges, poses, saved, rec, chi2, rho1, H, block_rc, block_ptr, block_c, b_ptr, b_c, vertex_of, out, records;
+  DEVICE_BUF_MEMBERS(GRAPH_BATCH_BUFS)
   // the last call, for dvo_amd_debug_graph_batch_records
   int last_graphs = 0, last_stride = 0;
   std::vector<int> last_iterations;
@@ -583,85 +582,31 @@ namespace {
 
 const char *const kEntry = "dvo_amd_optimize_graphs_batch";
 
-int grow(GraphBatchWorkspace::Buf &b, size_t bytes) {
-  if (bytes <= b.bytes) return DVO_AMD_OK;
-  if (b.p) (void)hipFree(b.p), b.p = nullptr, b.bytes = 0;
-  bytes = align_up(std::max<size_t>(bytes, 256), 1 << 12);
-  const hipError_t e = hipMalloc(&b.p, bytes);
-  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
-  if (e != hipSuccess) return fail_hip("hipMalloc (graph batch workspace)", e);
-  b.bytes = bytes;
-  return DVO_AMD_OK;
-}
-
-#define BATCH_TRY(expr)       \
-  do {                        \
-    const int rc_ = (expr);   \
-    if (rc_) return rc_;      \
-  } while (0)
-
-// the free active vertices of an item, in increasing vertex index
-void free_slots(const dvo_amd_graph_batch_item &it, std::vector<int> &slot, std::vector<int> &vertex_of) {
-  std::vector<char> active(it.n_vertices, 0);
-  for (int k = 0; k < it.n_edges; ++k) active[it.edges[k].from] = active[it.edges[k].to] = 1;
-  slot.assign(it.n_vertices, -1);
-  vertex_of.clear();
-  for (int v = 0; v < it.n_vertices; ++v)
-    if (active[v] && !(it.fixed && it.fixed[v])) {
-      slot[v] = (int)vertex_of.size();
-      vertex_of.push_back(v);
-    }
-}
+int grow(DeviceBuf &b, size_t bytes) { return grow(b, bytes, "graph batch workspace"); }
 
 int optimize_batch(dvo_amd_context *ctx, int n_graphs, dvo_amd_graph_batch_item *items, const dvo_amd_graph_options &opt) {
   // per graph: the unknowns and the contributor lists (CSR by lower block / by vertex slot, contributors in edge order)
   std::vector<graph_batch::Item> its(n_graphs);
   std::vector<int2> block_rc;
-  std::vector<int> block_ptr, block_c, b_ptr, b_c, vertex_of_all, slot, vertex_of;
+  std::vector<int> block_ptr, block_c, b_ptr, b_c, vertex_of_all;
   size_t n_vertices = 0, n_edges = 0;
   long long h_doubles = 0;
   int n_max = 0;
   for (int g = 0; g < n_graphs; ++g) {
     dvo_amd_graph_batch_item &it = items[g];
-    free_slots(it, slot, vertex_of);
-    const int m = (int)vertex_of.size();
-    std::map<long long, std::vector<int>> blocks;
-    std::vector<std::vector<int>> bl(std::max(m, 1));
-    for (int k = 0; k < it.n_edges; ++k) {
-      const int f = slot[it.edges[k].from], t = slot[it.edges[k].to];
-      if (f >= 0) blocks[(long long)f * m + f].push_back(4 * k + 0), bl[f].push_back(2 * k + 0);
-      if (t >= 0) blocks[(long long)t * m + t].push_back(4 * k + 1), bl[t].push_back(2 * k + 1);
-      if (f >= 0 && t >= 0) {  // the lower image only: block (f, t) holds Aft, block (t, f) its transpose
-        if (f > t)
-          blocks[(long long)f * m + t].push_back(4 * k + 2);
-        else
-          blocks[(long long)t * m + f].push_back(4 * k + 3);
-      }
-    }
-    graph_batch::Item &I = its[g];
-    I.h_off = h_doubles;
-    I.n_vertices = it.n_vertices;
-    I.n_edges = it.n_edges;
-    I.m = m;
-    I.nblocks = (int)blocks.size();
-    I.pose_off = (int)n_vertices;
-    I.edge_off = (int)n_edges;
-    I.slot_off = (int)vertex_of_all.size();
-    I.block_off = (int)block_rc.size();
-    I.bptr_off = (int)block_ptr.size();
-    I.gptr_off = (int)b_ptr.size();
-    block_ptr.push_back((int)block_c.size());
-    for (const auto &kv : blocks) {
-      block_rc.push_back(make_int2((int)(kv.first / std::max(m, 1)), (int)(kv.first % std::max(m, 1))));
-      block_c.insert(block_c.end(), kv.second.begin(), kv.second.end());
-      block_ptr.push_back((int)block_c.size());
-    }
-    b_ptr.push_back((int)b_c.size());
-    for (int s = 0; s < m; ++s) {
-      b_c.insert(b_c.end(), bl[s].begin(), bl[s].end());
-      b_ptr.push_back((int)b_c.size());
-    }
-    vertex_of_all.insert(vertex_of_all.end(), vertex_of.begin(), vertex_of.end());
+    const Unknowns U = free_unknowns(it.n_vertices, it.fixed, it.n_edges, it.edges);
+    const Contributors C = contributor_lists(U, it.n_edges, it.edges, true);
+    const int m = U.m;
+    // h_off, n_vertices, n_edges, m, nblocks, then what lies before this graph: pose, edge, slot, block, bptr, gptr offsets
+    its[g] = graph_batch::Item{h_doubles, it.n_vertices, it.n_edges, m, (int)C.block_rc.size(), (int)n_vertices, (int)n_edges,
+                               (int)vertex_of_all.size(), (int)block_rc.size(), (int)block_ptr.size(), (int)b_ptr.size()};
+    // the graph's pointers index the concatenated contributor arrays
+    for (int p : C.block_ptr) block_ptr.push_back((int)block_c.size() + p);
+    for (int p : C.b_ptr) b_ptr.push_back((int)b_c.size() + p);
+    block_rc.insert(block_rc.end(), C.block_rc.begin(), C.block_rc.end());
+    block_c.insert(block_c.end(), C.block_c.begin(), C.block_c.end());
+    b_c.insert(b_c.end(), C.b_c.begin(), C.b_c.end());
+    vertex_of_all.insert(vertex_of_all.end(), U.vertex_of.begin(), U.vertex_of.end());
     n_vertices += it.n_vertices;
     n_edges += it.n_edges;
     h_doubles += (long long)(6 * m) * (6 * m + 1) / 2;
@@ -685,29 +630,26 @@ int optimize_batch(dvo_amd_context *ctx, int n_graphs, dvo_amd_graph_batch_item 
   GraphBatchWorkspace &W = *ctx->graph_batch_ws;
   const hipStream_t st = ctx->stream;
   const int stride = std::max(1, std::min(opt.max_iterations, graph_batch::kMaxRecords));
-  auto grow_up = [&](GraphBatchWorkspace::Buf &b, const void *src, size_t bytes) {
-    const int rc = grow(b, std::max<size_t>(bytes, 1));
-    if (rc || !bytes) return rc;
-    const hipError_t e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-    return e == hipSuccess ? DVO_AMD_OK : fail_hip("hipMemcpyAsync (graph batch upload)", e);
+  auto grow_up = [&](DeviceBuf &b, const void *src, size_t bytes) {
+    return grow_upload(b, src, bytes, st, "graph batch workspace", "graph batch upload");
   };
-  BATCH_TRY(grow_up(W.items, its.data(), sizeof(graph_batch::Item) * its.size()));
-  BATCH_TRY(grow_up(W.edges, edges.data(), sizeof(dvo_amd_graph_edge) * n_edges));
-  BATCH_TRY(grow_up(W.poses, poses.data(), 16 * sizeof(double) * n_vertices));
-  BATCH_TRY(grow_up(W.block_rc, block_rc.data(), sizeof(int2) * block_rc.size()));
-  BATCH_TRY(grow_up(W.block_ptr, block_ptr.data(), sizeof(int) * block_ptr.size()));
-  BATCH_TRY(grow_up(W.block_c, block_c.data(), sizeof(int) * block_c.size()));
-  BATCH_TRY(grow_up(W.b_ptr, b_ptr.data(), sizeof(int) * b_ptr.size()));
-  BATCH_TRY(grow_up(W.b_c, b_c.data(), sizeof(int) * b_c.size()));
-  BATCH_TRY(grow_up(W.vertex_of, vertex_of_all.data(), sizeof(int) * vertex_of_all.size()));
+  GRAPH_TRY(grow_up(W.items, its.data(), sizeof(graph_batch::Item) * its.size()));
+  GRAPH_TRY(grow_up(W.edges, edges.data(), sizeof(dvo_amd_graph_edge) * n_edges));
+  GRAPH_TRY(grow_up(W.poses, poses.data(), 16 * sizeof(double) * n_vertices));
+  GRAPH_TRY(grow_up(W.block_rc, block_rc.data(), sizeof(int2) * block_rc.size()));
+  GRAPH_TRY(grow_up(W.block_ptr, block_ptr.data(), sizeof(int) * block_ptr.size()));
+  GRAPH_TRY(grow_up(W.block_c, block_c.data(), sizeof(int) * block_c.size()));
+  GRAPH_TRY(grow_up(W.b_ptr, b_ptr.data(), sizeof(int) * b_ptr.size()));
+  GRAPH_TRY(grow_up(W.b_c, b_c.data(), sizeof(int) * b_c.size()));
+  GRAPH_TRY(grow_up(W.vertex_of, vertex_of_all.data(), sizeof(int) * vertex_of_all.size()));
   const size_t E = std::max<size_t>(n_edges, 1);
-  BATCH_TRY(grow(W.saved, 16 * sizeof(double) * std::max<size_t>(n_vertices, 1)));
-  BATCH_TRY(grow(W.rec, sizeof(double) * graph_batch::kRecord * E));
-  BATCH_TRY(grow(W.chi2, sizeof(double) * E));
-  BATCH_TRY(grow(W.rho1, sizeof(double) * E));
-  BATCH_TRY(grow(W.H, sizeof(double) * (size_t)std::max<long long>(h_doubles, 1)));
-  BATCH_TRY(grow(W.out, sizeof(graph_batch::Out) * n_graphs));
-  BATCH_TRY(grow(W.records, sizeof(dvo_amd_graph_iteration) * (size_t)stride * n_graphs));
+  GRAPH_TRY(grow(W.saved, 16 * sizeof(double) * std::max<size_t>(n_vertices, 1)));
+  GRAPH_TRY(grow(W.rec, sizeof(double) * graph_batch::kRecord * E));
+  GRAPH_TRY(grow(W.chi2, sizeof(double) * E));
+  GRAPH_TRY(grow(W.rho1, sizeof(double) * E));
+  GRAPH_TRY(grow(W.H, sizeof(double) * (size_t)std::max<long long>(h_doubles, 1)));
+  GRAPH_TRY(grow(W.out, sizeof(graph_batch::Out) * n_graphs));
+  GRAPH_TRY(grow(W.records, sizeof(dvo_amd_graph_iteration) * (size_t)stride * n_graphs));
   // blocks no edge touches stay zero
   if (h_doubles) HIP_TRY(hipMemsetAsync(W.H.p, 0, sizeof(double) * (size_t)h_doubles, st));
   HIP_TRY(hipMemsetAsync(W.records.p, 0, sizeof(dvo_amd_graph_iteration) * (size_t)stride * n_graphs, st));
@@ -718,31 +660,14 @@ int optimize_batch(dvo_amd_context *ctx, int n_graphs, dvo_amd_graph_batch_item 
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     W.lds_allowed = lds;
   }
-  graph_batch::Buffers B;
-  B.items = (const graph_batch::Item *)W.items.p;
-  B.edges = (const dvo_amd_graph_edge *)W.edges.p;
-  B.poses = (double *)W.poses.p;
-  B.saved = (double *)W.saved.p;
-  B.rec = (double *)W.rec.p;
-  B.chi2 = (double *)W.chi2.p;
-  B.rho1 = (double *)W.rho1.p;
-  B.H = (double *)W.H.p;
-  B.block_rc = (const int2 *)W.block_rc.p;
-  B.block_ptr = (const int *)W.block_ptr.p;
-  B.block_c = (const int *)W.block_c.p;
-  B.b_ptr = (const int *)W.b_ptr.p;
-  B.b_c = (const int *)W.b_c.p;
-  B.vertex_of = (const int *)W.vertex_of.p;
-  B.out = (graph_batch::Out *)W.out.p;
-  B.records = (dvo_amd_graph_iteration *)W.records.p;
-  graph_batch::Params P;
-  P.algorithm = opt.algorithm;
-  P.max_iterations = opt.max_iterations;
-  P.max_trials = opt.max_trials;
-  P.record_stride = stride;
-  P.robust_delta = opt.robust_delta;
-  P.initial_lambda = opt.initial_lambda;
-  P.initial_delta = opt.initial_delta;
+  // both in the order of their declarations
+  const graph_batch::Buffers B{(const graph_batch::Item *)W.items.p, (const dvo_amd_graph_edge *)W.edges.p, (double *)W.poses.p,
+                               (double *)W.saved.p, (double *)W.rec.p, (double *)W.chi2.p, (double *)W.rho1.p, (double *)W.H.p,
+                               (const int2 *)W.block_rc.p, (const int *)W.block_ptr.p, (const int *)W.block_c.p,
+                               (const int *)W.b_ptr.p, (const int *)W.b_c.p, (const int *)W.vertex_of.p,
+                               (graph_batch::Out *)W.out.p, (dvo_amd_graph_iteration *)W.records.p};
+  const graph_batch::Params P{opt.algorithm, opt.max_iterations, opt.max_trials, stride,
+                              opt.robust_delta, opt.initial_lambda, opt.initial_delta};
   hipLaunchKernelGGL(graph_batch::k_optimize_batch, dim3(n_graphs), dim3(graph_batch::kThreads), lds, st, B, P);
   HIP_TRY(hipGetLastError());
 
@@ -780,21 +705,14 @@ int optimize_batch(dvo_amd_context *ctx, int n_graphs, dvo_amd_graph_batch_item 
   return DVO_AMD_OK;
 }
 
-int have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
-  return DVO_AMD_OK;
-}
-
 }  // namespace
 
 void graph_batch_workspace_release(dvo_amd_context *ctx) {
   GraphBatchWorkspace *w = ctx->graph_batch_ws;
   if (!w) return;
-  for (GraphBatchWorkspace::Buf *b : {&w->items, &w->edges, &w->poses, &w->saved, &w->rec, &w->chi2, &w->rho1, &w->H,
-                                      &w->block_rc, &w->block_ptr, &w->block_c, &w->b_ptr, &w->b_c, &w->vertex_of, &w->out,
-                                      &w->records})
-    if (b->p) (void)hipFree(b->p);
+  w->each_buf([](DeviceBuf &b) {
+    if (b.p) (void)hipFree(b.p);
+  });
   delete w;
   ctx->graph_batch_ws = nullptr;
 }
@@ -823,15 +741,11 @@ int dvo_amd_optimize_graphs_batch(dvo_amd_context *ctx, int n_graphs, dvo_amd_gr
     rc = graph_check_arguments(where.c_str(), items[g].n_vertices, items[g].poses, items[g].n_edges, items[g].edges, opt);
     if (rc) return rc;
   }
-  std::vector<int> slot, vertex_of;
   for (int g = 0; g < n_graphs; ++g) {
-    free_slots(items[g], slot, vertex_of);
-    if ((int)vertex_of.size() > DVO_AMD_GRAPH_BATCH_MAX_FREE_VERTICES) {
-      g_last_error = std::string(kEntry) + ": item " + std::to_string(g) + ": " + std::to_string(vertex_of.size()) +
-                     " free active vertices (a graph of the batch takes at most " +
-                     std::to_string(DVO_AMD_GRAPH_BATCH_MAX_FREE_VERTICES) + ")";
-      return DVO_AMD_ERR_CAPACITY;
-    }
+    rc = check_capacity(std::string(kEntry) + ": item " + std::to_string(g),
+                        free_unknowns(items[g].n_vertices, items[g].fixed, items[g].n_edges, items[g].edges).m,
+                        DVO_AMD_GRAPH_BATCH_MAX_FREE_VERTICES, "a graph of the batch");
+    if (rc) return rc;
   }
   rc = have_device();
   if (rc) return rc;

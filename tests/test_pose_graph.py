@@ -408,3 +408,69 @@ def test_gpu_loop_closure_end_to_end(trk, synth):
     after = R.rms_position([res.poses[v] for v in moved], truth)
     print(f"loop closure: {len(survivors)} constraints over {len(moved)} keyframes, RMS {before:.4f} -> {after:.5f} m")
     assert after < before
+
+
+def _result_arrays(res):
+    stats = [res.n_iterations, res.n_free, res.cholesky_failures, res.initial_objective, res.final_objective, res.lambda_,
+             res.delta]
+    return ([np.stack(res.poses), res.chi2, res.weight, np.array(stats, dtype=np.float64)] +
+            [np.asarray(v) for v in res.iterations.values()] + [np.frombuffer(res.termination.encode(), dtype=np.uint8)])
+
+
+def _marginal_arrays(out):
+    blocks, st = out
+    return [blocks, np.array([st.n_free, st.factorized, st.fixed_blocks, st.inactive_blocks, st.solved_columns])]
+
+
+def workspace_reuse_calls():
+    """The calls of test_gpu_workspace_reuse_across_entries_bit_for_bit, in order: (name, f(tracker) -> list of arrays).  Between
+    them they reach every buffer group of a context's graph workspaces: the dense H / L, the sparse fronts, Zinv / cols, the
+    batch workspace; call 6 is smaller than call 1, so a stale tail of a buffer would show."""
+    from dvo_slam_amd import graph
+
+    ring40 = R.ring_graph(41, n_chords=4, seed=61, drift=0.02)[0]  # 40 free vertices
+    ring12 = R.ring_graph(13, n_chords=2, seed=62, drift=0.02)[0]
+    trio = [R.ring_graph(16, n_chords=2, seed=63 + i, drift=0.02)[0] for i in range(3)]  # 15 free vertices each
+    # an adjacent pair, a diagonal, and two vertices far apart on the ring that share no edge (the sparse column path)
+    pairs = [(3, 4), (9, 9), (5, 25)]
+
+    def batch(t):
+        pgs = [to_pose_graph(g) for g in trio]
+        out = []
+        for i, res in enumerate(graph.optimize_batch(t, pgs, "levenberg", iterations=20)):
+            out += _result_arrays(res) + [np.asarray(v) for v in graph.debug_batch_records(t, i).values()]
+        return out
+
+    def all_fixed(t):
+        pg = to_pose_graph(ring12)
+        for v in range(len(pg.poses)):
+            pg.set_fixed(v)
+        return _result_arrays(pg.optimize(t, "levenberg", iterations=5, solver="sparse"))
+
+    return [
+        ("dense levenberg, 40 free", lambda t: _result_arrays(to_pose_graph(ring40).optimize(t, "levenberg", iterations=20))),
+        ("sparse dogleg, 40 free",
+         lambda t: _result_arrays(to_pose_graph(ring40).optimize(t, "dogleg", iterations=40, solver="sparse"))),
+        ("sparse marginals", lambda t: _marginal_arrays(to_pose_graph(ring40).marginals(t, pairs, solver="sparse"))),
+        ("dense marginals, 12 free", lambda t: _marginal_arrays(to_pose_graph(ring12).marginals(t, solver="dense"))),
+        ("batch of three", batch),
+        ("dense levenberg, 12 free", lambda t: _result_arrays(to_pose_graph(ring12).optimize(t, "levenberg", iterations=20))),
+        ("sparse levenberg, no free vertex", all_fixed),
+    ]
+
+
+@pytest.mark.gpu
+def test_gpu_workspace_reuse_across_entries_bit_for_bit(trk):
+    """Every graph entry in turn on one context gives the bits each gives on a fresh context of its own: nothing a call leaves
+    in the shared workspace (grown buffers, stale tails, the sparse maps, the inverse's arena) reaches the next call."""
+    from dvo_slam_amd import capi
+
+    shared = capi.DenseTracker()
+    for name, call in workspace_reuse_calls():
+        got, want = call(shared), call(capi.DenseTracker())
+        assert len(got) == len(want)
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert a.dtype == b.dtype and a.shape == b.shape, (name, k)
+            assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), (name, k)  # the raw bits: NaN blocks compare too
+        if name == "sparse marginals":
+            assert got[1][4] > 0, "the far-apart pair takes the column path"
