@@ -42,7 +42,7 @@ EXPORTS = [
     "dvo_amd_debug_graph_sparse_timing", "dvo_amd_optimize_graphs_batch", "dvo_amd_debug_graph_batch_records",
     "dvo_amd_debug_tick_layout",
     "dvo_amd_map_create", "dvo_amd_map_destroy", "dvo_amd_map_insert", "dvo_amd_map_set_poses", "dvo_amd_map_remove",
-    "dvo_amd_map_stats", "dvo_amd_map_extract", "dvo_amd_debug_keyframe_map_timing",
+    "dvo_amd_map_stats", "dvo_amd_map_extract", "dvo_amd_debug_keyframe_map_timing", "dvo_amd_debug_map_merge",
 ]
 
 
@@ -234,6 +234,7 @@ def lib():
     L.dvo_amd_map_extract.argtypes = [vp, C.POINTER(C.c_float), vp, C.c_longlong, C.POINTER(C.c_longlong)]
     L.dvo_amd_debug_keyframe_map_timing.argtypes = [vp, dp, dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                                     C.POINTER(C.c_int)]
+    L.dvo_amd_debug_map_merge.argtypes = [vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, vp, C.POINTER(C.c_longlong)]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -601,6 +602,20 @@ class DenseTracker:
         d, c, n = C.c_double(), C.c_double(), C.c_longlong()
         _check(lib().dvo_amd_debug_map_timing(self._h, C.byref(d), C.byref(c), C.byref(n)), "dvo_amd_debug_map_timing")
         return d.value, c.value, n.value
+
+    def debug_map_merge(self, keys_a, acc_a, keys_b, acc_b):
+        """(test entry) the keyframe map's merge of a store (keys uint64 [na] ascending and distinct, sums uint64 [na, 8]) and
+        a delta (the same, nb entries) on the device: (keys uint64 [n], sums uint64 [n, 8]) of the compacted store
+        (dvo_amd_debug_map_merge)."""
+        ka, kb = [np.ascontiguousarray(k, dtype=np.uint64).reshape(-1) for k in (keys_a, keys_b)]
+        va, vb = [np.ascontiguousarray(v, dtype=np.uint64).reshape(-1, 8) for v in (acc_a, acc_b)]
+        if len(va) != len(ka) or len(vb) != len(kb):
+            raise ValueError("eight uint64 of sums per key")
+        total = len(ka) + len(kb)
+        ko, vo, n = np.zeros(max(1, total), np.uint64), np.zeros((max(1, total), 8), np.uint64), C.c_longlong(-1)
+        _check(lib().dvo_amd_debug_map_merge(self._h, len(ka), ka.ctypes.data, va.ctypes.data, len(kb), kb.ctypes.data,
+                                             vb.ctypes.data, ko.ctypes.data, vo.ctypes.data, C.byref(n)), "dvo_amd_debug_map_merge")
+        return ko[:n.value].copy(), vo[:n.value].copy()
 
     def configure(self, config: Config):
         c = config._c()

@@ -856,6 +856,25 @@ int entry_checks(const dvo_amd_map *M, const char *what) {
   return DVO_AMD_OK;
 }
 
+// The merge of an update, enqueued on the stream: k_merge over the store (ka, va: na entries) and the delta (kb, vb: nb entries)
+// into the na + nb merged positions (kt, vt, flags), the scan of the flags (their total lands in the control block's voxels)
+// and k_compact into (ko, vo).  W.ctrl and W.bsum must already hold the control block and the scan scratch of na + nb entries.
+int merge_launches(MapWorkspace &W, const unsigned long long *ka, const map::VoxelAcc *va, unsigned na,
+                   const unsigned long long *kb, const map::VoxelAcc *vb, unsigned nb, unsigned long long *kt, map::VoxelAcc *vt,
+                   unsigned *flags, unsigned long long *ko, map::VoxelAcc *vo, hipStream_t st) {
+  const unsigned long long merged = (unsigned long long)na + nb;
+  map::MapCtrl *dctrl = (map::MapCtrl *)W.ctrl.p;
+  hipLaunchKernelGGL(map::k_merge, dim3((unsigned)((merged + map::kMergeTile - 1) / map::kMergeTile)), dim3(map::kBlock), 0, st,
+                     ka, va, na, kb, vb, nb, kt, vt, flags);
+  const int rc = scan(W, flags, (unsigned)merged, &dctrl->voxels, st);
+  if (rc) return rc;
+  hipLaunchKernelGGL(map::k_compact, dim3(map::grid_for(4 * merged, map::kBlock)), dim3(map::kBlock), 0, st,
+                     (const unsigned long long *)kt, (const map::VoxelAcc *)vt, (const unsigned *)flags,
+                     (const unsigned *)&dctrl->voxels, (unsigned)merged, ko, vo);
+  HIP_TRY(hipGetLastError());
+  return DVO_AMD_OK;
+}
+
 // Applies the items to the store (from_scratch: to an empty store) and, when everything succeeded, makes `next` the keyframe
 // list.  Until then the map is untouched: the merge writes the other store buffer.
 int apply_delta(dvo_amd_map *M, const std::vector<DeltaItem> &items, bool from_scratch, std::vector<dvo_amd_map::Keyframe> &next) {
@@ -959,17 +978,11 @@ int apply_delta(dvo_amd_map *M, const std::vector<DeltaItem> &items, bool from_s
     if (rc) return rc;
     map::MapCtrl *dctrl = (map::MapCtrl *)W.ctrl.p;
     HIP_TRY(hipEventRecord(M->ev[2], st));
-    hipLaunchKernelGGL(map::k_merge, dim3((unsigned)((merged + map::kMergeTile - 1) / map::kMergeTile)), dim3(map::kBlock), 0, st,
-                       (const unsigned long long *)M->keys[M->cur].p, (const map::VoxelAcc *)M->acc[M->cur].p, n_store,
-                       (const unsigned long long *)M->dkeys.p, (const map::VoxelAcc *)W.acc.p, n_delta,
-                       (unsigned long long *)M->tkeys.p, (map::VoxelAcc *)M->tacc.p, (unsigned *)M->flags.p);
-    rc = scan(W, (unsigned *)M->flags.p, (unsigned)merged, &dctrl->voxels, st);
+    rc = merge_launches(W, (const unsigned long long *)M->keys[M->cur].p, (const map::VoxelAcc *)M->acc[M->cur].p, n_store,
+                        (const unsigned long long *)M->dkeys.p, (const map::VoxelAcc *)W.acc.p, n_delta,
+                        (unsigned long long *)M->tkeys.p, (map::VoxelAcc *)M->tacc.p, (unsigned *)M->flags.p,
+                        (unsigned long long *)M->keys[other].p, (map::VoxelAcc *)M->acc[other].p, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(map::k_compact, dim3(map::grid_for(4 * merged, map::kBlock)), dim3(map::kBlock), 0, st,
-                       (const unsigned long long *)M->tkeys.p, (const map::VoxelAcc *)M->tacc.p, (const unsigned *)M->flags.p,
-                       (const unsigned *)&dctrl->voxels, (unsigned)merged, (unsigned long long *)M->keys[other].p,
-                       (map::VoxelAcc *)M->acc[other].p);
-    HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(M->ev[3], st));
     HIP_TRY(hipMemcpyAsync(&n_new, &dctrl->voxels, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1252,6 +1265,95 @@ int dvo_amd_debug_keyframe_map_timing(const dvo_amd_map *M, double *device_ms, d
   if (delta_points) *delta_points = M->delta_points;
   if (delta_voxels) *delta_voxels = M->delta_voxels;
   if (merge_tile) *merge_tile = map::kMergeTile;
+  return DVO_AMD_OK;
+}
+
+namespace {
+
+// device buffers of one dvo_amd_debug_map_merge call: freed when the call returns, whichever way
+struct MergeProbeBuffers {
+  host::MapWorkspace::Buf ka, va, kb, vb, kt, vt, flags, ko, vo;
+  ~MergeProbeBuffers() {
+    for (host::MapWorkspace::Buf *b : {&ka, &va, &kb, &vb, &kt, &vt, &flags, &ko, &vo})
+      if (b->p) (void)hipFree(b->p);
+  }
+};
+
+// ascending, distinct, 63 bits
+bool merge_probe_keys_ok(long long n, const unsigned long long *k) {
+  for (long long e = 0; e < n; ++e)
+    if ((k[e] >> 63) != 0 || (e > 0 && k[e] <= k[e - 1])) return false;
+  return true;
+}
+
+}  // namespace
+
+int dvo_amd_debug_map_merge(dvo_amd_context *ctx, long long na, const unsigned long long *keys_a, const unsigned long long *acc_a,
+                            long long nb, const unsigned long long *keys_b, const unsigned long long *acc_b,
+                            unsigned long long *keys_out, unsigned long long *acc_out, long long *n_out) {
+  int rc = host::have_device();
+  if (rc) return rc;
+  if (!ctx || !n_out || na < 0 || nb < 0 || (na > 0 && (!keys_a || !acc_a)) || (nb > 0 && (!keys_b || !acc_b)) ||
+      (na + nb > 0 && (!keys_out || !acc_out)))
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  *n_out = 0;
+  if ((unsigned long long)na + (unsigned long long)nb >= (1ull << 31)) {
+    g_last_error = "dvo_amd_debug_map_merge: 2^31 entries or more";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  if (!merge_probe_keys_ok(na, keys_a) || !merge_probe_keys_ok(nb, keys_b)) {
+    g_last_error = "dvo_amd_debug_map_merge: the keys of each side must be ascending, distinct and below 2^63";
+    return DVO_AMD_ERR_INVALID_ARGUMENT;
+  }
+  rc = queue_must_be_idle(ctx, "dvo_amd_debug_map_merge");
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const unsigned n_store = (unsigned)na, n_delta = (unsigned)nb, merged = n_store + n_delta;
+  if (merged == 0) return DVO_AMD_OK;
+  host::MapWorkspace *W = nullptr;
+  rc = host::workspace(ctx, &W);
+  MergeProbeBuffers B;
+  const size_t acc_bytes = sizeof(map::VoxelAcc);
+  if (!rc) rc = host::grow(B.ka, 8 * (size_t)n_store);
+  if (!rc) rc = host::grow(B.va, acc_bytes * n_store);
+  if (!rc) rc = host::grow(B.kb, 8 * (size_t)n_delta);
+  if (!rc) rc = host::grow(B.vb, acc_bytes * n_delta);
+  if (!rc) rc = host::grow(B.kt, 8 * (size_t)merged);
+  if (!rc) rc = host::grow(B.vt, acc_bytes * merged);
+  if (!rc) rc = host::grow(B.flags, 4 * (size_t)merged);
+  if (!rc) rc = host::grow(B.ko, 8 * (size_t)merged);
+  if (!rc) rc = host::grow(B.vo, acc_bytes * merged);
+  if (!rc) rc = host::grow(W->ctrl, sizeof(map::MapCtrl));
+  if (!rc) rc = host::grow(W->bsum, sizeof(unsigned) * ((size_t)merged / map::kScanTile + 1));
+  if (rc) return rc;
+  const hipStream_t st = ctx->stream;
+  if (n_store > 0) {
+    HIP_TRY(hipMemcpyAsync(B.ka.p, keys_a, 8 * (size_t)n_store, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(B.va.p, acc_a, acc_bytes * n_store, hipMemcpyHostToDevice, st));
+  }
+  if (n_delta > 0) {
+    HIP_TRY(hipMemcpyAsync(B.kb.p, keys_b, 8 * (size_t)n_delta, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(B.vb.p, acc_b, acc_bytes * n_delta, hipMemcpyHostToDevice, st));
+  }
+  // the launches of an update's merge (host::apply_delta), on the probe's buffers
+  map::MapCtrl *dctrl = (map::MapCtrl *)W->ctrl.p;
+  rc = host::merge_launches(*W, (const unsigned long long *)B.ka.p, (const map::VoxelAcc *)B.va.p, n_store,
+                            (const unsigned long long *)B.kb.p, (const map::VoxelAcc *)B.vb.p, n_delta, (unsigned long long *)B.kt.p,
+                            (map::VoxelAcc *)B.vt.p, (unsigned *)B.flags.p, (unsigned long long *)B.ko.p, (map::VoxelAcc *)B.vo.p, st);
+  if (rc) {
+    (void)hipStreamSynchronize(st);  // before the buffers go
+    return rc;
+  }
+  unsigned n_new = 0;
+  hipError_t e = hipMemcpyAsync(&n_new, &dctrl->voxels, sizeof(unsigned), hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);  // before the buffers go, whatever happened
+  if (e != hipSuccess || es != hipSuccess) return host::fail_hip("dvo_amd_debug_map_merge", e != hipSuccess ? e : es);
+  n_new = std::min(n_new, merged);  // (always: the flags are 0 or 1)
+  if (n_new > 0) {
+    HIP_TRY(hipMemcpy(keys_out, B.ko.p, 8 * (size_t)n_new, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(acc_out, B.vo.p, acc_bytes * n_new, hipMemcpyDeviceToHost));
+  }
+  *n_out = n_new;
   return DVO_AMD_OK;
 }
 

@@ -168,6 +168,16 @@ int dvo_amd_debug_map_timing(dvo_amd_context *ctx, double *device_ms, double *co
  * the delta it merged (0 for an extract), and the entries of one merge tile.  scripts/keyframe_map_timing.py */
 int dvo_amd_debug_keyframe_map_timing(const dvo_amd_map *map, double *device_ms, double *copy_ms, long long *delta_points,
                                       long long *delta_voxels, int *merge_tile);
+/* (test entry) the merge of a keyframe-map update on keys and sums the CALLER chooses: a store of na entries and a delta of nb
+ * entries, host arrays, each side's keys ascending, distinct and below 2^63, the sums as eight 64-bit words per entry (count,
+ * sx, sy, sz, r, g, b, pad).  The arrays are uploaded and merged by the launches of an update -- k_merge, the scan of its
+ * flags, k_compact: the same kernels, none copied -- and the compacted store comes back: *n_out entries in keys_out / acc_out,
+ * which hold na + nb entries each.  Sums of equal keys are added modulo 2^64; an entry whose count ends as 0 is dropped.  (An
+ * update skips the merge when its delta is empty; this entry runs it whenever there is an entry at all.)
+ * tests/test_voxel_edges.py */
+int dvo_amd_debug_map_merge(dvo_amd_context *ctx, long long na, const unsigned long long *keys_a, const unsigned long long *acc_a,
+                            long long nb, const unsigned long long *keys_b, const unsigned long long *acc_b,
+                            unsigned long long *keys_out, unsigned long long *acc_out, long long *n_out);
 /* the last dvo_amd_optimize_graph on the context: device ms of its first linearisation (linearise + assemble) and of its first
  * factorization (damped copy + blocked Cholesky), the padded system size, and the factorizations done */
 int dvo_amd_debug_graph_timing(dvo_amd_context *ctx, double *linearise_ms, double *factorize_ms, int *n_padded,
