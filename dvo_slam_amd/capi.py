@@ -42,7 +42,7 @@ EXPORTS = [
     "dvo_amd_debug_graph_sparse_timing", "dvo_amd_optimize_graphs_batch", "dvo_amd_debug_graph_batch_records",
     "dvo_amd_debug_tick_layout",
     "dvo_amd_map_create", "dvo_amd_map_destroy", "dvo_amd_map_insert", "dvo_amd_map_set_poses", "dvo_amd_map_remove",
-    "dvo_amd_map_stats", "dvo_amd_map_extract", "dvo_amd_debug_keyframe_map_timing", "dvo_amd_debug_map_merge",
+    "dvo_amd_map_stats", "dvo_amd_map_extract", "dvo_amd_map_render", "dvo_amd_map_render_pyramid", "dvo_amd_debug_keyframe_map_timing", "dvo_amd_debug_map_merge",
 ]
 
 
@@ -98,6 +98,15 @@ class CQ7Probe(C.Structure):
 
 class CCloudStats(C.Structure):
     _fields_ = [("points_in", C.c_longlong), ("finite", C.c_longlong), ("out_of_range", C.c_longlong), ("voxels", C.c_longlong)]
+
+
+class CView(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("ox", C.c_float),
+                ("oy", C.c_float), ("near_z", C.c_float)]
+
+
+class CRenderStats(C.Structure):
+    _fields_ = [(n, C.c_longlong) for n in ("voxels", "behind_near", "outside", "drawn", "covered_pixels")]
 
 
 class DvoAmdError(RuntimeError):
@@ -232,6 +241,8 @@ def lib():
     L.dvo_amd_map_remove.argtypes = [vp, C.c_int, C.POINTER(C.c_int)]
     L.dvo_amd_map_stats.argtypes = [vp, C.POINTER(CCloudStats), C.POINTER(C.c_int)]
     L.dvo_amd_map_extract.argtypes = [vp, C.POINTER(C.c_float), vp, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.dvo_amd_map_render.argtypes = [vp, dp, C.POINTER(CView), vp, vp, vp, vp, C.POINTER(CRenderStats)]
+    L.dvo_amd_map_render_pyramid.argtypes = [vp, dp, C.POINTER(CView), C.c_int, C.c_double, C.POINTER(vp), C.POINTER(CRenderStats)]
     L.dvo_amd_debug_keyframe_map_timing.argtypes = [vp, dp, dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                                     C.POINTER(C.c_int)]
     L.dvo_amd_debug_map_merge.argtypes = [vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, vp, C.POINTER(C.c_longlong)]
@@ -969,6 +980,48 @@ class KeyframeMap:
             rc = lib().dvo_amd_map_extract(self._h, bp, out.ctypes.data, cap, C.byref(n))
         _check(rc, "dvo_amd_map_extract")
         return _split_points(out[:n.value])
+
+    def _view(self, K, width, height, near):
+        fx, fy, ox, oy = [np.float32(k) for k in K]
+        if near is None:
+            near = max(np.float32(0.1), np.float32(self.leaf) * max(fx, fy) / np.float32(32))
+        return CView(int(width), int(height), fx, fy, ox, oy, np.float32(near))
+
+    def render(self, pose, K, width: int, height: int, near=None, planes=("depth", "rgb", "intensity", "index")):
+        """The map seen from `pose` (4x4 camera -> world, None = identity) through K = (fx, fy, ox, oy): every voxel splatted
+        over a square of its own size with a nearest-depth test (dvo_amd_map_render; the rule is pinned in dvo_amd.h).  A dict of
+        the requested planes, [height, width] each -- depth float32 (NaN where empty), rgb uint32, intensity float32, index
+        int32 (the voxel's position in extract(), -1 where empty) -- plus "stats".  near=None: max(0.1, leaf * max(fx, fy) / 32),
+        the closest the rule admits."""
+        kinds = {"depth": np.float32, "rgb": np.uint32, "intensity": np.float32, "index": np.int32}
+        unknown = [p for p in planes if p not in kinds]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}")
+        view = self._view(K, width, height, near)
+        ok = view.width >= 1 and view.height >= 1 and view.width * view.height <= 1 << 26  # (the entry rejects the rest)
+        out = {p: np.empty((view.height, view.width) if ok else (1, 1), kinds[p]) for p in kinds if p in planes}
+        T = None if pose is None else _pose_cm(pose)
+        st = CRenderStats()
+        ptr = [out[p].ctypes.data if p in out else None for p in ("depth", "rgb", "intensity", "index")]
+        _check(lib().dvo_amd_map_render(self._h, None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(view),
+                                        ptr[0], ptr[1], ptr[2], ptr[3], C.byref(st)), "dvo_amd_map_render")
+        out["stats"] = {n: getattr(st, n) for n, _ in CRenderStats._fields_}
+        return out
+
+    def render_pyramid(self, pose, K, width: int, height: int, levels: int, near=None, timestamp: float = 0.0):
+        """The same view as an RgbdImagePyramid built on the device from the rendered planes: level 0's intensity and depth are
+        render()'s (dvo_amd_map_render_pyramid).  `stats` of the render are left in the pyramid's `render_stats`."""
+        view = self._view(K, width, height, near)
+        T = None if pose is None else _pose_cm(pose)
+        st = CRenderStats()
+        pyr = RgbdImagePyramid.__new__(RgbdImagePyramid)
+        pyr._h = C.c_void_p()
+        _check(lib().dvo_amd_map_render_pyramid(self._h, None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)),
+                                                C.byref(view), levels, timestamp, C.byref(pyr._h), C.byref(st)),
+               "dvo_amd_map_render_pyramid")
+        pyr.device = self._trk.device
+        pyr.render_stats = {n: getattr(st, n) for n, _ in CRenderStats._fields_}
+        return pyr
 
     def timing(self):
         """(diagnostic) the last call: (device ms of its kernels, ms of the output copy, delta points, delta voxels, merge tile)"""

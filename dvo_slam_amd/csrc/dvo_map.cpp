@@ -14,6 +14,8 @@
 //   k_merge        merge path over (store, delta), both in key order: sums of equal keys added, voxels left without points flagged
 //   k_compact      the flagged positions into the other store buffer
 //   k_box_flags / k_box_compact   the box rule of dvo_amd_map_extract on the output points, order kept
+//   k_render_clear / k_render_splat / k_render_resolve   the store forward-projected into a camera view with a nearest-depth
+//                  test (dvo_amd_map_render): a 64-bit unsigned-min atomic per covered pixel, then one pass over the pixels
 // Every sum is an integer sum: the result does not depend on the order points arrive in, on the compaction order or on the
 // launch geometry -- bit for bit.
 #include <climits>
@@ -523,6 +525,141 @@ __global__ void __launch_bounds__(kBlock) k_box_compact(const float4 *pts, const
   }
 }
 
+// ---- the map rendered into a camera view (dvo_amd_map_render, dvo_amd_map_render_pyramid) ------------------------------------
+//   k_render_clear    the z-buffer (one 64-bit word per pixel) to all ones
+//   k_render_splat    every voxel of the store: centroid, world -> camera, cull, project, footprint; the footprint's pixels keep
+//                     the minimum of (bits(cz) << 32) | rank with one 64-bit unsigned-min atomic each
+//   k_render_resolve  per pixel: the winner's depth, colour, grey value and rank into the requested planes
+// The minimum does not depend on the order the atomics land in, and the words only decrease: the planes are a function of the
+// store and the view alone.
+
+struct RenderView {
+  int w, h;
+  float fx, fy, ox, oy, near_z, leaf;
+  float T[12];  // rows 0..2 of the float inverse pose (world -> camera), row-major
+};
+
+struct RenderCtrl {
+  unsigned long long behind_near, outside, drawn, covered;
+};
+
+constexpr unsigned long long kEmptyWord = ~0ull;
+constexpr int kSmallFootprint = 4;  // pixels a lane splats by itself; larger footprints are walked by the whole wave
+
+__global__ void __launch_bounds__(kBlock) k_render_clear(ulonglong2 *z, unsigned long long n2) {
+  for (unsigned long long p = (unsigned long long)blockIdx.x * kBlock + threadIdx.x; p < n2; p += (unsigned long long)gridDim.x * kBlock)
+    z[p] = make_ulonglong2(kEmptyWord, kEmptyWord);
+}
+
+// one axis of the footprint (dvo_amd.h, rule 5), compared in float; false: no pixel of the axis is covered
+__device__ __forceinline__ bool footprint_axis(float c, float half, int size, int &lo, int &hi) {
+  float a = ceilf(c - half), b = floorf(c + half);
+  if (b < a) a = b = floorf(c + 0.5f);
+  const float last = (float)(size - 1);
+  if (!(b >= 0.0f && a <= last)) return false;
+  lo = a > 0.0f ? (int)a : 0;
+  hi = b < last ? (int)b : size - 1;
+  return true;
+}
+
+// the stale value a plain load may return is never smaller than the word in memory: skipping the atomic on it is exact
+__device__ __forceinline__ void depth_min(unsigned long long *z, unsigned long long word) {
+  if (*z > word) atomicMin(z, word);
+}
+
+__global__ void __launch_bounds__(kBlock) k_render_splat(const VoxelAcc *acc, unsigned n_vox, RenderView V, unsigned long long *zbuf,
+                                                         RenderCtrl *ctrl) {
+  const int lane = threadIdx.x & 63;
+  unsigned long long behind = 0, outside = 0, drawn = 0;
+  for (unsigned base = blockIdx.x * kBlock; base < n_vox; base += gridDim.x * kBlock) {  // (uniform over the wave: ballots below)
+    const unsigned r = base + threadIdx.x;
+    int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+    unsigned long long word = kEmptyWord;
+    bool draw = false;
+    if (r < n_vox) {
+      const ulonglong2 *a = (const ulonglong2 *)(acc + r);
+      const ulonglong2 a0 = a[0], a1 = a[1];  // count, s[0] | s[1], s[2]
+      const double den = (double)a0.x * kFix;  // k_voxel_out's centroid
+      const float x = (float)((double)(long long)a0.y / den), y = (float)((double)(long long)a1.x / den),
+                  z = (float)((double)(long long)a1.y / den);
+      const float *T = V.T;
+      const float cx = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
+      const float cy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
+      const float cz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+      if (!(cz >= V.near_z)) {
+        ++behind;
+      } else {
+        const float u = (cx * V.fx) / cz + V.ox, v = (cy * V.fy) / cz + V.oy;
+        const float hx = 0.5f * ((V.leaf * V.fx) / cz), hy = 0.5f * ((V.leaf * V.fy) / cz);
+        const bool in_x = footprint_axis(u, hx, V.w, x0, x1), in_y = footprint_axis(v, hy, V.h, y0, y1);
+        draw = in_x && in_y;
+        if (draw) ++drawn, word = ((unsigned long long)__float_as_uint(cz) << 32) | r;
+        else ++outside;
+      }
+    }
+    const int fw = draw ? x1 - x0 + 1 : 0, fh = draw ? y1 - y0 + 1 : 0;  // (either may be < 1 past 2^24 pixels a side: nothing drawn)
+    const bool some = fw > 0 && fh > 0;
+    const bool small = some && (long long)fw * fh <= kSmallFootprint;
+    if (small)
+      for (int yy = y0; yy <= y1; ++yy)
+        for (int xx = x0; xx <= x1; ++xx) depth_min(zbuf + (size_t)yy * V.w + xx, word);
+    // the larger footprints of the wave, one after the other: a lane per pixel along the rows, so one atomic instruction
+    // touches runs of adjacent words
+    unsigned long long todo = __ballot(some && !small);
+    while (todo) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const int sx0 = __shfl(x0, src, 64), sy0 = __shfl(y0, src, 64), sfw = __shfl(fw, src, 64), sfh = __shfl(fh, src, 64);
+      const unsigned wlo = __shfl((unsigned)word, src, 64), whi = __shfl((unsigned)(word >> 32), src, 64);
+      const unsigned long long sword = ((unsigned long long)whi << 32) | wlo;
+      const int npx = sfw * sfh;  // (at most the view: 2^26)
+      for (int p = lane; p < npx; p += 64) {
+        const int row = p / sfw, col = p - row * sfw;
+        depth_min(zbuf + (size_t)(sy0 + row) * V.w + (sx0 + col), sword);
+      }
+    }
+  }
+  const unsigned long long b = wave_sum(behind), o = wave_sum(outside), d = wave_sum(drawn);
+  if (lane == 0) {
+    if (b) atomicAdd(&ctrl->behind_near, b);
+    if (o) atomicAdd(&ctrl->outside, o);
+    if (d) atomicAdd(&ctrl->drawn, d);
+  }
+}
+
+// any of the planes may be null
+__global__ void __launch_bounds__(kBlock) k_render_resolve(const unsigned long long *zbuf, unsigned long long n_px, const VoxelAcc *acc,
+                                                           unsigned n_vox, float *depth, unsigned *rgb, float *intensity, int *index,
+                                                           RenderCtrl *ctrl) {
+  unsigned long long covered = 0;
+  for (unsigned long long p0 = (unsigned long long)blockIdx.x * kBlock; p0 < n_px; p0 += (unsigned long long)gridDim.x * kBlock) {
+    const unsigned long long p = p0 + threadIdx.x;
+    if (p >= n_px) continue;
+    const unsigned long long w = zbuf[p];
+    const unsigned r = (unsigned)w;
+    float d = __uint_as_float(0x7FC00000u), g = 0.0f;
+    unsigned c = 0;
+    int at = -1;
+    if (w != kEmptyWord && r < n_vox) {  // (r < n_vox always: the ranks k_render_splat wrote)
+      const unsigned long long *a = (const unsigned long long *)(acc + r);
+      const unsigned long long cnt = a[0];
+      unsigned ch[3];
+      for (int q = 0; q < 3; ++q) ch[q] = (unsigned)((a[4 + q] + cnt / 2) / cnt);  // k_voxel_out's colour
+      d = __uint_as_float((unsigned)(w >> 32));
+      c = (ch[0] << 16) | (ch[1] << 8) | ch[2];
+      g = (float)((1868u * (c & 0xFF) + 9617u * ((c >> 8) & 0xFF) + 4899u * ((c >> 16) & 0xFF) + 8192u) >> 14);  // the ingest's grey
+      at = (int)r;
+      ++covered;
+    }
+    if (depth) depth[p] = d;
+    if (rgb) rgb[p] = c;
+    if (intensity) intensity[p] = g;
+    if (index) index[p] = at;
+  }
+  covered = wave_sum(covered);
+  if ((threadIdx.x & 63) == 0 && covered) atomicAdd(&ctrl->covered, covered);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
@@ -543,6 +680,7 @@ struct MapWorkspace {
     size_t bytes = 0;
   };
   Buf pts, keys[2], vals[2], flags, counts, bsum, acc, out, bgr, images, ctrl;
+  Buf zbuf, planes;  // a render: the 64-bit z-buffer, then depth | rgb | intensity | index of the view
   hipEvent_t ev[8] = {};  // input stage, sort, reduction, output copy: begin / end each
   double device_ms = 0.0, copy_ms = 0.0;  // the last map call: kernels (three timed segments), the output copy
   long long points = 0;
@@ -784,7 +922,7 @@ void map_workspace_release(dvo_amd_context *ctx) {
   MapWorkspace *w = ctx->map_ws;
   if (!w) return;
   for (MapWorkspace::Buf *b : {&w->pts, &w->keys[0], &w->keys[1], &w->vals[0], &w->vals[1], &w->flags, &w->counts, &w->bsum,
-                               &w->acc, &w->out, &w->bgr, &w->images, &w->ctrl})
+                               &w->acc, &w->out, &w->bgr, &w->images, &w->ctrl, &w->zbuf, &w->planes})
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : w->ev)
     if (e) (void)hipEventDestroy(e);
@@ -998,6 +1136,88 @@ int apply_delta(dvo_amd_map *M, const std::vector<DeltaItem> &items, bool from_s
   M->kfs.swap(next);
   M->device_ms = device_ms, M->copy_ms = 0.0, M->delta_points = (long long)total, M->delta_voxels = n_delta;
   return DVO_AMD_OK;
+}
+
+// the device planes of a rendered view (null where not asked for)
+struct RenderPlanes {
+  float *depth = nullptr;
+  unsigned *rgb = nullptr;
+  float *intensity = nullptr;
+  int *index = nullptr;
+};
+
+// the world -> camera transform of a view as the device takes it (dvo_amd.h, rule 2): the inverse of a rigid pose in double,
+// every product and sum rounded on its own, then cast to float
+void inverse_pose(const double *pose, float T[12]) {
+  static const double kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  const double *P = pose ? pose : kIdentity;  // column-major: R[i][j] = P[j * 4 + i], t[i] = P[12 + i]
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) T[r * 4 + c] = (float)P[r * 4 + c];  // Ri[r][c] = R[c][r]
+    T[r * 4 + 3] = (float)-((P[r * 4 + 0] * P[12] + P[r * 4 + 1] * P[13]) + P[r * 4 + 2] * P[14]);
+  }
+}
+
+int check_view(const dvo_amd_map *M, const double *pose, const dvo_amd_view *v, const char *what) {
+  const char *why = nullptr;
+  if (!v) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  if (v->width < 1 || v->height < 1 || (long long)v->width * v->height > (1ll << 26)) why = "width and height must be >= 1 and width*height <= 2^26";
+  else if (!(std::isfinite(v->fx) && v->fx > 0.0f && std::isfinite(v->fy) && v->fy > 0.0f)) why = "fx and fy must be finite and positive";
+  else if (!std::isfinite(v->ox) || !std::isfinite(v->oy)) why = "ox and oy must be finite";
+  else if (!std::isfinite(v->near_z) || !(v->near_z > 0.0f)) why = "near_z must be finite and positive";
+  else if (pose && !finite_pose(pose)) why = "the pose has a non-finite entry";
+  else if (v->near_z < (M->leaf * std::max(v->fx, v->fy)) / 32.0f)
+    why = "near_z is below leaf_size * max(fx, fy) / 32: a voxel at near_z would cover more than 32 pixels a side";
+  if (!why) return DVO_AMD_OK;
+  g_last_error = std::string(what) + ": " + why;
+  return DVO_AMD_ERR_INVALID_ARGUMENT;
+}
+
+// Enqueues a render on the context's stream: clear, splat, resolve into the workspace's planes (`want`: bit 0 depth, 1 rgb,
+// 2 intensity, 3 index), the control block into *ctrl.  The caller synchronises.  M->ev[0..1] time the kernels.
+int render_launches(dvo_amd_map *M, const double *pose, const dvo_amd_view *view, unsigned want, RenderPlanes *planes,
+                    map::RenderCtrl *ctrl) {
+  MapWorkspace *Wp = nullptr;
+  int rc = workspace(M->ctx, &Wp);
+  if (rc) return rc;
+  MapWorkspace &W = *Wp;
+  const size_t n_px = (size_t)view->width * view->height;
+  rc = grow(W.zbuf, 8 * (n_px + 1));  // (cleared 16 bytes at a time)
+  if (!rc) rc = grow(W.planes, 16 * n_px);
+  if (!rc) rc = grow(W.ctrl, std::max(sizeof(map::MapCtrl), sizeof(map::RenderCtrl)));
+  if (rc) return rc;
+  map::RenderView V;
+  V.w = view->width, V.h = view->height, V.fx = view->fx, V.fy = view->fy, V.ox = view->ox, V.oy = view->oy;
+  V.near_z = view->near_z, V.leaf = M->leaf;
+  inverse_pose(pose, V.T);
+  float *base = (float *)W.planes.p;
+  if (want & 1u) planes->depth = base;
+  if (want & 2u) planes->rgb = (unsigned *)(base + n_px);
+  if (want & 4u) planes->intensity = base + 2 * n_px;
+  if (want & 8u) planes->index = (int *)(base + 3 * n_px);
+  const hipStream_t st = M->ctx->stream;
+  unsigned long long *zbuf = (unsigned long long *)W.zbuf.p;
+  map::RenderCtrl *dctrl = (map::RenderCtrl *)W.ctrl.p;
+  const map::VoxelAcc *acc = (const map::VoxelAcc *)M->acc[M->cur].p;
+  HIP_TRY(hipEventRecord(M->ev[0], st));
+  HIP_TRY(hipMemsetAsync(dctrl, 0, sizeof(map::RenderCtrl), st));
+  hipLaunchKernelGGL(map::k_render_clear, dim3(map::grid_for((n_px + 1) / 2, map::kBlock)), dim3(map::kBlock), 0, st, (ulonglong2 *)zbuf,
+                     (unsigned long long)((n_px + 1) / 2));
+  if (M->n > 0)
+    hipLaunchKernelGGL(map::k_render_splat, dim3(map::grid_for(M->n, map::kBlock)), dim3(map::kBlock), 0, st, acc, M->n, V, zbuf, dctrl);
+  hipLaunchKernelGGL(map::k_render_resolve, dim3(map::grid_for(n_px, map::kBlock)), dim3(map::kBlock), 0, st,
+                     (const unsigned long long *)zbuf, (unsigned long long)n_px, acc, M->n, planes->depth, planes->rgb,
+                     planes->intensity, planes->index, dctrl);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(M->ev[1], st));
+  HIP_TRY(hipMemcpyAsync(ctrl, dctrl, sizeof(*ctrl), hipMemcpyDeviceToHost, st));
+  return DVO_AMD_OK;
+}
+
+void render_stats(const dvo_amd_map *M, const map::RenderCtrl &c, dvo_amd_render_stats *stats) {
+  if (!stats) return;
+  stats->voxels = M->n;
+  stats->behind_near = (long long)c.behind_near, stats->outside = (long long)c.outside, stats->drawn = (long long)c.drawn;
+  stats->covered_pixels = (long long)c.covered;
 }
 
 }  // namespace
@@ -1252,6 +1472,64 @@ int dvo_amd_map_extract(dvo_amd_map *M, const float *box, dvo_amd_point *out, lo
   HIP_TRY(hipEventElapsedTime(&b, M->ev[2], M->ev[3]));
   M->device_ms = a, M->copy_ms = b;
   if (n_out) *n_out = n_ret;
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_map_render(dvo_amd_map *M, const double *pose, const dvo_amd_view *view, float *depth, unsigned int *rgb, float *intensity,
+                       int *index, dvo_amd_render_stats *stats) {
+  int rc = host::entry_checks(M, "dvo_amd_map_render");
+  if (!rc) rc = host::check_view(M, pose, view, "dvo_amd_map_render");
+  if (rc) return rc;
+  M->device_ms = 0.0, M->copy_ms = 0.0, M->delta_points = 0, M->delta_voxels = 0;
+  host::RenderPlanes P;
+  map::RenderCtrl c;
+  rc = host::render_launches(M, pose, view, (depth ? 1u : 0u) | (rgb ? 2u : 0u) | (intensity ? 4u : 0u) | (index ? 8u : 0u), &P, &c);
+  if (rc) return rc;
+  const hipStream_t st = M->ctx->stream;
+  const size_t bytes = sizeof(float) * (size_t)view->width * view->height;
+  HIP_TRY(hipEventRecord(M->ev[2], st));
+  if (depth) HIP_TRY(hipMemcpyAsync(depth, P.depth, bytes, hipMemcpyDeviceToHost, st));
+  if (rgb) HIP_TRY(hipMemcpyAsync(rgb, P.rgb, bytes, hipMemcpyDeviceToHost, st));
+  if (intensity) HIP_TRY(hipMemcpyAsync(intensity, P.intensity, bytes, hipMemcpyDeviceToHost, st));
+  if (index) HIP_TRY(hipMemcpyAsync(index, P.index, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipEventRecord(M->ev[3], st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float a = 0.f, b = 0.f;
+  HIP_TRY(hipEventElapsedTime(&a, M->ev[0], M->ev[1]));
+  HIP_TRY(hipEventElapsedTime(&b, M->ev[2], M->ev[3]));
+  M->device_ms = a, M->copy_ms = b;
+  host::render_stats(M, c, stats);
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_map_render_pyramid(dvo_amd_map *M, const double *pose, const dvo_amd_view *view, int levels, double timestamp,
+                               dvo_amd_pyramid **out, dvo_amd_render_stats *stats) {
+  int rc = host::entry_checks(M, "dvo_amd_map_render_pyramid");
+  if (rc) return rc;
+  if (!out) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  rc = host::check_view(M, pose, view, "dvo_amd_map_render_pyramid");
+  if (rc) return rc;
+  if (levels < 1 || levels > DVO_AMD_MAX_LEVELS) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  for (int l = 0, w = view->width, h = view->height; l < levels; ++l, w /= 2, h /= 2)
+    if (w < 4 || h < 2 || (w % 4) != 0) {  // dvo_amd_pyramid_create_from_device's rule, before anything is rendered
+      g_last_error = "dvo_amd_map_render_pyramid: the view cannot hold a pyramid of " + std::to_string(levels) + " levels";
+      return DVO_AMD_ERR_INVALID_ARGUMENT;
+    }
+  M->device_ms = 0.0, M->copy_ms = 0.0, M->delta_points = 0, M->delta_voxels = 0;
+  host::RenderPlanes P;
+  map::RenderCtrl c;
+  rc = host::render_launches(M, pose, view, 1u | 4u, &P, &c);
+  if (rc) return rc;
+  HIP_TRY(hipStreamSynchronize(M->ctx->stream));
+  float a = 0.f;
+  HIP_TRY(hipEventElapsedTime(&a, M->ev[0], M->ev[1]));
+  M->device_ms = a;
+  // the pyramid copies the two planes device to device and builds its levels from them: the workspace is free again on return
+  rc = dvo_amd_pyramid_create_from_device(M->ctx->device, P.intensity, P.depth, view->width, view->height, view->width, view->fx,
+                                          view->fy, view->ox, view->oy, levels, timestamp, out);
+  if (rc) return rc;
+  host::render_stats(M, c, stats);
   return DVO_AMD_OK;
 }
 

@@ -530,6 +530,60 @@ int dvo_amd_map_stats(const dvo_amd_map *map, dvo_amd_cloud_stats *stats, int *n
 /* box: NULL, or {xmin,ymin,zmin,xmax,ymax,zmax} */
 int dvo_amd_map_extract(dvo_amd_map *map, const float *box, dvo_amd_point *out, long long capacity, long long *n_out);
 
+/*
+ * The keyframe map rendered into a camera view on the device: every voxel is forward-projected into the image with a
+ * nearest-depth test, the way RgbdImage::warpDepthForward / warpIntensityForward / warpDepthForwardAdvanced
+ * (rgbd_image.cpp:604-781) splat points.  The view's depth and intensity planes are an RgbdImagePyramid's level 0
+ * (dvo_amd_map_render_pyramid), so every tracker entry can align a live frame to the fused model.
+ *
+ * The rule, operation by operation; the result is a function of the map and the view alone -- not of the launch geometry, not
+ * of the order the atomics land in.  pose: camera -> world, column-major 4x4 doubles, NULL = identity (as dvo_amd_map_insert).
+ * Pixel centres sit at integer coordinates: the ray of column u is (u - ox) / fx.  For the voxel of rank r (its position in the
+ * store's ascending key order = its index in dvo_amd_map_extract(map, NULL, ...)):
+ *  1. centroid (x, y, z) and packed colour: the bits dvo_amd_map_extract returns;
+ *  2. world -> camera: the host forms the inverse of the pose in double, taking it as rigid (only finiteness is checked):
+ *     Ri = R^T, ti[r] = -((R[0][r]*t0 + R[1][r]*t1) + R[2][r]*t2), every product and sum rounded on its own; each entry is cast to
+ *     float; the device computes c = ((T0*x + T1*y) + T2*z) + T3 per row in fp32, uncontracted (the order of the point cloud);
+ *  3. cull: the voxel is dropped unless cz >= near_z (false for NaN) and counted in behind_near;
+ *  4. project, in fp32, every operation rounded: u = (cx*fx)/cz + ox, v = (cy*fy)/cz + oy, the division correctly rounded;
+ *  5. footprint: the voxel covers a square of its own size: hx = 0.5f*((leaf*fx)/cz); columns u0 = ceilf(u - hx) to
+ *     u1 = floorf(u + hx); if u1 < u0 the footprint holds no pixel centre and u0 = u1 = floorf(u + 0.5f); rows the same way with
+ *     fy.  The voxel is drawn only if u1 >= 0 && u0 <= (float)(width-1) && v1 >= 0 && v0 <= (float)(height-1), compared in float
+ *     before any conversion to int (false for NaN); otherwise it is counted in outside.  The footprint is then clamped to the
+ *     image: columns from (u0 > 0 ? (int)u0 : 0) to (u1 < (float)(width-1) ? (int)u1 : width-1), rows alike ((float)(width-1)
+ *     is exact up to 2^24; beyond, a range left empty by its rounding draws no pixel);
+ *  6. depth test: every covered pixel keeps the minimum of the 64-bit word (bits(cz) << 32) | r.  cz > 0, so its bit pattern
+ *     orders like its value; ties in depth go to the lower rank;
+ *  7. resolve, per pixel: covered: depth = cz, rgb = the voxel's packed colour, intensity = (float)((1868 B + 9617 G + 4899 R
+ *     + 8192) >> 14) (the ingest's grey rule: a grey keyframe's value comes back unchanged), index = r; empty: depth = NaN
+ *     (0x7FC00000), rgb = 0, intensity = 0, index = -1.
+ * There is no hole filling and no smoothing: a pixel no footprint covers stays empty.
+ *
+ * A footprint side is bounded by the view, not by clipping: near_z < (leaf * max(fx, fy)) / 32 (in fp32) is rejected, so no
+ * voxel spans more than 32 pixels (33 pixel centres).  DVO_AMD_ERR_INVALID_ARGUMENT with a reason in dvo_amd_last_error() for
+ * that and for: width or height < 1 or width*height > 2^26; fx or fy not finite and positive; ox, oy or near_z not finite;
+ * near_z <= 0; a non-finite pose entry; pairs queued on the context.  DVO_AMD_ERR_NO_DEVICE as for every compute entry.  An
+ * empty map renders an all-empty view and returns DVO_AMD_OK.  A render never changes the map.  stats (may be NULL):
+ * voxels = behind_near + outside + drawn; covered_pixels = the pixels that are not empty.
+ */
+typedef struct {
+  int width, height;
+  float fx, fy, ox, oy;
+  float near_z;
+} dvo_amd_view;
+
+typedef struct {
+  long long voxels, behind_near, outside, drawn, covered_pixels;
+} dvo_amd_render_stats;
+
+/* any of depth / rgb / intensity / index may be NULL; each is width*height, row-major, host memory */
+int dvo_amd_map_render(dvo_amd_map *map, const double *pose, const dvo_amd_view *view, float *depth, unsigned int *rgb,
+                       float *intensity, int *index, dvo_amd_render_stats *stats);
+/* the same view as a pyramid (dvo_amd_pyramid_create_from_device's rules for width, height and levels), built from the device
+ * planes without a host round trip: level 0's intensity and depth planes are exactly dvo_amd_map_render's */
+int dvo_amd_map_render_pyramid(dvo_amd_map *map, const double *pose, const dvo_amd_view *view, int levels, double timestamp,
+                               dvo_amd_pyramid **out, dvo_amd_render_stats *stats);
+
 /* Binary PCD v0.7 as pcl::io::savePCDFileBinary writes a PointXYZRGB cloud: FIELDS x y z rgb, SIZE 4 4 4 4, TYPE F F F F
  * (rgb holds the packed bits), COUNT 1 1 1 1, WIDTH / HEIGHT as given (organized, or n x 1), VIEWPOINT 0 0 0 1 0 0 0,
  * POINTS width*height (= n), then the records.  Host code only. */

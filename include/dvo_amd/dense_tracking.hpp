@@ -279,6 +279,11 @@ class RgbdImagePyramid {
       std::memcpy(&depth_[(size_t)y * width], depth + (size_t)y * stride, sizeof(float) * width);
     }
   }
+  // adopts a pyramid that was built on the device (visualization::KeyframeMap::renderPyramid): no host planes are kept; a
+  // later build() of more levels downloads level 0 once and rebuilds from it
+  RgbdImagePyramid(dvo_amd_pyramid *adopted, int width, int height, const IntrinsicMatrix &K, int device, double timestamp)
+      : width_(width), height_(height), K_(K), device_(device), timestamp_(timestamp), handle_(adopted),
+        levels_(dvo_amd_pyramid_levels(adopted)) {}
   ~RgbdImagePyramid() { dvo_amd_pyramid_release(handle_); }
   RgbdImagePyramid(const RgbdImagePyramid &) = delete;
   RgbdImagePyramid &operator=(const RgbdImagePyramid &) = delete;
@@ -288,6 +293,11 @@ class RgbdImagePyramid {
   void build(const size_t num_levels) {
     if ((size_t)levels_ >= num_levels && handle_) return;
     const int want = (int)std::max<size_t>(num_levels, (size_t)levels_);
+    if (intensity_.empty() && handle_) {  // an adopted pyramid: its level 0 is the base
+      intensity_.resize((size_t)width_ * height_), depth_.resize((size_t)width_ * height_);
+      detail::check(dvo_amd_pyramid_download_plane(handle_, 0, 0, intensity_.data()), "RgbdImagePyramid::build");
+      detail::check(dvo_amd_pyramid_download_plane(handle_, 0, 1, depth_.data()), "RgbdImagePyramid::build");
+    }
     dvo_amd_pyramid *fresh = nullptr;
     detail::check(dvo_amd_pyramid_create(device_, intensity_.data(), depth_.data(), width_, height_, width_, K_.fx(), K_.fy(),
                                          K_.ox(), K_.oy(), want, timestamp_, &fresh),

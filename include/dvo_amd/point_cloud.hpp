@@ -246,7 +246,17 @@ class KeyframeMap {
   typedef AsyncPointCloudBuilder::PointCloud PointCloud;
   typedef AsyncPointCloudBuilder::BuildJob BuildJob;
 
-  explicit KeyframeMap(float leaf_size = 0.01f, int device = 0) : device_(device), map_(nullptr) {
+  // a rendered view (dvo_amd.h: dvo_amd_map_render): width * height values per plane, row-major; empty pixels hold depth NaN,
+  // rgb 0, intensity 0, index -1
+  struct View {
+    int width, height;
+    std::vector<float> depth, intensity;
+    std::vector<unsigned int> rgb;
+    std::vector<int> index;
+    dvo_amd_render_stats stats;
+  };
+
+  explicit KeyframeMap(float leaf_size = 0.01f, int device = 0) : device_(device), map_(nullptr), leaf_(leaf_size) {
     std::unique_lock<std::mutex> lock;
     dvo_amd_context *ctx = core::cloud::context(device_, lock);
     ::dvo::detail::check(dvo_amd_map_create(ctx, leaf_size, &map_), "KeyframeMap");
@@ -319,9 +329,44 @@ class KeyframeMap {
     return out;
   }
 
+  // near_z <= 0: max(0.1, leaf * max(fx, fy) / 32), the closest the render rule admits
+  dvo_amd_view view(const core::IntrinsicMatrix &K, int width, int height, float near_z = 0.0f) const {
+    dvo_amd_view v;
+    v.width = width, v.height = height, v.fx = K.fx(), v.fy = K.fy(), v.ox = K.ox(), v.oy = K.oy();
+    v.near_z = near_z > 0.0f ? near_z : std::max(0.1f, (leaf_ * std::max(K.fx(), K.fy())) / 32.0f);
+    return v;
+  }
+  // the map seen from `pose` (camera -> world) through K: every voxel splatted over a square of its own size with a
+  // nearest-depth test, what RgbdImage::warpDepthForward / warpIntensityForward do with a point list (rgbd_image.cpp:604-781)
+  void render(const core::AffineTransformd &pose, const core::IntrinsicMatrix &K, int width, int height, View &out, float near_z = 0.0f) {
+    const dvo_amd_view v = view(K, width, height, near_z);
+    const size_t n = width > 0 && height > 0 ? (size_t)width * (size_t)height : 0;
+    out.width = width, out.height = height;
+    out.depth.resize(n), out.intensity.resize(n), out.rgb.resize(n), out.index.resize(n);
+    std::unique_lock<std::mutex> lock;
+    (void)core::cloud::context(device_, lock);
+    ::dvo::detail::check(dvo_amd_map_render(map_, core::data(pose), &v, out.depth.data(), out.rgb.data(), out.intensity.data(),
+                                            out.index.data(), &out.stats),
+                         "KeyframeMap::render");
+  }
+  // the same view as a pyramid built on the device from the rendered planes: a reference any tracker entry accepts
+  core::RgbdImagePyramidPtr renderPyramid(const core::AffineTransformd &pose, const core::IntrinsicMatrix &K, int width, int height,
+                                          int levels, float near_z = 0.0f, double timestamp = 0.0) {
+    const dvo_amd_view v = view(K, width, height, near_z);
+    dvo_amd_pyramid *pyr = nullptr;
+    std::unique_lock<std::mutex> lock;
+    (void)core::cloud::context(device_, lock);
+    ::dvo::detail::check(dvo_amd_map_render_pyramid(map_, core::data(pose), &v, levels, timestamp, &pyr, nullptr),
+                         "KeyframeMap::renderPyramid");
+    return core::RgbdImagePyramidPtr(new core::RgbdImagePyramid(pyr, width, height, K, device_, timestamp));
+  }
+
+  dvo_amd_map *handle() const { return map_; }
+
  private:
   int device_;
   dvo_amd_map *map_;
+  float leaf_;
 };
 
 }  // namespace visualization
