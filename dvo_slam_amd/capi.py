@@ -43,6 +43,8 @@ EXPORTS = [
     "dvo_amd_debug_tick_layout",
     "dvo_amd_map_create", "dvo_amd_map_destroy", "dvo_amd_map_insert", "dvo_amd_map_set_poses", "dvo_amd_map_remove",
     "dvo_amd_map_stats", "dvo_amd_map_extract", "dvo_amd_map_render", "dvo_amd_map_render_pyramid", "dvo_amd_debug_keyframe_map_timing", "dvo_amd_debug_map_merge",
+    "dvo_amd_default_covisibility_options", "dvo_amd_covisibility", "dvo_amd_find_constraint_candidates",
+    "dvo_amd_debug_covisibility_ms",
 ]
 
 
@@ -107,6 +109,20 @@ class CView(C.Structure):
 
 class CRenderStats(C.Structure):
     _fields_ = [(n, C.c_longlong) for n in ("voxels", "behind_near", "outside", "drawn", "covered_pixels")]
+
+
+class CKeyframe(C.Structure):
+    _fields_ = [("id", C.c_int), ("image", C.c_void_p), ("pose", C.c_double * 16), ("evaluation_kind", C.c_int),
+                ("evaluation_average", C.c_double), ("evaluation_n", C.c_double)]
+
+
+class CCovisibilityOptions(C.Structure):
+    _fields_ = [("level", C.c_int), ("near_z", C.c_float), ("depth_sigmas", C.c_float)]
+
+
+# dvo_amd_covisibility_counts, field for field
+COVISIBILITY_DTYPE = np.dtype([(name, np.uint32) for name in ("valid", "behind", "outside", "no_depth", "consistent", "occluded",
+                                                             "seen_through", "reserved")])
 
 
 class DvoAmdError(RuntimeError):
@@ -246,6 +262,14 @@ def lib():
     L.dvo_amd_debug_keyframe_map_timing.argtypes = [vp, dp, dp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
                                                     C.POINTER(C.c_int)]
     L.dvo_amd_debug_map_merge.argtypes = [vp, C.c_longlong, vp, vp, C.c_longlong, vp, vp, vp, vp, C.POINTER(C.c_longlong)]
+    L.dvo_amd_default_covisibility_options.argtypes = [C.POINTER(CCovisibilityOptions)]
+    L.dvo_amd_default_covisibility_options.restype = None
+    L.dvo_amd_covisibility.argtypes = [vp, C.c_int, C.POINTER(CKeyframe), C.POINTER(CCovisibilityOptions), C.c_int,
+                                       C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+    L.dvo_amd_find_constraint_candidates.argtypes = [vp, C.c_int, C.POINTER(CKeyframe), C.c_int, C.c_float, C.c_double,
+                                                     C.POINTER(CCovisibilityOptions), C.POINTER(C.c_int), dp, C.c_int,
+                                                     C.POINTER(C.c_int)]
+    L.dvo_amd_debug_covisibility_ms.argtypes = [vp, dp]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -1029,6 +1053,79 @@ class KeyframeMap:
         _check(lib().dvo_amd_debug_keyframe_map_timing(self._h, C.byref(d), C.byref(c), C.byref(p), C.byref(v), C.byref(t)),
                "dvo_amd_debug_keyframe_map_timing")
         return d.value, c.value, p.value, v.value, t.value
+
+
+def pack_keyframes(keyframes):
+    """dvo_amd_keyframe records of objects with .pose and, where they have them, .id, .image and .evaluation (a
+    constraints.Keyframe, or anything of that shape; an absent image becomes NULL)"""
+    ckf = (CKeyframe * max(len(keyframes), 1))()
+    for i, kf in enumerate(keyframes):
+        image = getattr(kf, "image", None)
+        ckf[i].id, ckf[i].image = int(getattr(kf, "id", i)), (image._h if image is not None else None)
+        ckf[i].pose = (C.c_double * 16)(*_pose_cm(kf.pose).reshape(-1))
+        ev = getattr(kf, "evaluation", None)
+        if ev is not None:
+            ckf[i].evaluation_kind, ckf[i].evaluation_average, ckf[i].evaluation_n = ev.kind, ev.average, ev.n
+    return ckf
+
+
+def covisibility_options(**options) -> CCovisibilityOptions:
+    """dvo_amd_default_covisibility_options (level 3, near_z 0.1, depth_sigmas 20) with level / near_z / depth_sigmas replaced"""
+    opt = CCovisibilityOptions()
+    lib().dvo_amd_default_covisibility_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in ("level", "near_z", "depth_sigmas"):
+            raise TypeError(f"unknown covisibility option {k!r}")
+        setattr(opt, k, v)
+    return opt
+
+
+def covisibility(tracker, keyframes, pairs, **options) -> np.ndarray:
+    """dvo_amd_covisibility: the eight counts (COVISIBILITY_DTYPE) of every ordered pair (a, b) of indices into `keyframes`,
+    in one call.  overlap = covisibility_overlap(counts)."""
+    pairs = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+    pa, pb = np.ascontiguousarray(pairs[:, 0]), np.ascontiguousarray(pairs[:, 1])
+    out = np.zeros(len(pairs), COVISIBILITY_DTYPE)
+    ip = C.POINTER(C.c_int)
+    opt = covisibility_options(**options)
+    _check(lib().dvo_amd_covisibility(tracker._h if tracker is not None else None, len(keyframes), pack_keyframes(keyframes),
+                                      C.byref(opt), len(pairs), pa.ctypes.data_as(ip), pb.ctypes.data_as(ip),
+                                      out.ctypes.data_as(C.c_void_p)), "dvo_amd_covisibility")
+    return out
+
+
+def covisibility_overlap(counts) -> np.ndarray:
+    """consistent / valid in double, 0 where valid == 0 (the library's rule)"""
+    c, v = counts["consistent"].astype(np.float64), counts["valid"].astype(np.float64)
+    return np.where(v > 0, c / np.where(v > 0, v, 1.0), 0.0)
+
+
+def covisibility_ms(tracker) -> float:
+    """device milliseconds of k_covis in the tracker's last covisibility call"""
+    ms = C.c_double()
+    _check(lib().dvo_amd_debug_covisibility_ms(tracker._h, C.byref(ms)), "dvo_amd_debug_covisibility_ms")
+    return ms.value
+
+
+def find_constraint_candidates(tracker, keyframes, keyframe: int, max_distance: float, min_overlap: float = 0.0,
+                               capacity: int | None = None, **options):
+    """dvo_amd_find_constraint_candidates: (indices of the candidates in ascending order, their overlaps -- NaN when
+    min_overlap <= 0).  tracker may be None when min_overlap <= 0: the radius search needs no device.  A capacity that is too
+    small raises DvoAmdError (DVO_AMD_ERR_CAPACITY) whose `needed` is the size asked for."""
+    capacity = len(keyframes) if capacity is None else capacity
+    cand = np.zeros(max(capacity, 1), np.int32)
+    over = np.zeros(max(capacity, 1), np.float64)
+    n = C.c_int()
+    opt = covisibility_options(**options)
+    status = lib().dvo_amd_find_constraint_candidates(
+        tracker._h if tracker is not None else None, len(keyframes), pack_keyframes(keyframes), keyframe, max_distance,
+        min_overlap, C.byref(opt), cand.ctypes.data_as(C.POINTER(C.c_int)), over.ctypes.data_as(C.POINTER(C.c_double)),
+        capacity, C.byref(n))
+    if status != 0:
+        err = DvoAmdError(status, "dvo_amd_find_constraint_candidates")
+        err.needed = n.value
+        raise err
+    return [int(k) for k in cand[:n.value]], over[:n.value].copy()
 
 
 def se3_exp(xi) -> np.ndarray:

@@ -21,9 +21,7 @@ EVAL_LOGLIKELIHOOD, EVAL_NORMALIZED_LOGLIKELIHOOD, EVAL_ENTROPY = 0, 1, 2
 VOTER_ODOMETRY_CONSTRAINT, VOTER_NAN_RESULT, VOTER_CONSTRAINT_RATIO, VOTER_TRACKING_RESULT_EVALUATION, VOTER_CROSS_VALIDATION = range(5)
 
 
-class CKeyframe(C.Structure):
-    _fields_ = [("id", C.c_int), ("image", C.c_void_p), ("pose", C.c_double * 16), ("evaluation_kind", C.c_int),
-                ("evaluation_average", C.c_double), ("evaluation_n", C.c_double)]
+CKeyframe = capi.CKeyframe  # dvo_amd_keyframe
 
 
 class CVoter(C.Structure):
@@ -298,3 +296,36 @@ def proposalsForCandidates(keyframe: Keyframe, candidates: list) -> list:
         out.append(ConstraintProposal.createWithIdentity(keyframe, c))
         out.append(ConstraintProposal.createWithRelative(keyframe, c))
     return out
+
+
+# ---- keyframe_constraint_search.h ------------------------------------------------------------------------------------------
+class NearestNeighborConstraintSearch:
+    """dvo_slam::NearestNeighborConstraintSearch (keyframe_constraint_search.h:35-58): the keyframes within max_distance of
+    `keyframe`, itself included, in ascending order of their position in `all` (dvo_amd_find_constraint_candidates).
+    min_overlap > 0 is this library's extension: candidates whose view overlap with `keyframe` (the larger of the two
+    directions, dvo_amd_covisibility with `options`: level, near_z, depth_sigmas) is below it are dropped before any alignment
+    runs.  With min_overlap = 0 no GPU is touched."""
+
+    def __init__(self, max_distance: float, min_overlap: float = 0.0, tracker: capi.DenseTracker | None = None, **options):
+        self._max_distance, self._min_overlap, self.tracker, self.options = float(max_distance), float(min_overlap), tracker, options
+        self.overlaps = np.zeros(0)  # of the last search, one per returned keyframe (NaN when min_overlap <= 0)
+
+    def maxDistance(self, d: float | None = None) -> float:
+        if d is not None:
+            self._max_distance = float(d)
+        return self._max_distance
+
+    def minOverlap(self, o: float | None = None) -> float:
+        if o is not None:
+            self._min_overlap = float(o)
+        return self._min_overlap
+
+    def findPossibleConstraints(self, all: list, keyframe: Keyframe) -> list:
+        at = next((i for i, kf in enumerate(all) if kf is keyframe), None)
+        if at is None:
+            raise ValueError("`keyframe` is not one of `all`")
+        if self._min_overlap > 0 and self.tracker is None:
+            self.tracker = capi.DenseTracker(device=keyframe.image.device)
+        found, self.overlaps = capi.find_constraint_candidates(self.tracker, all, at, self._max_distance, self._min_overlap,
+                                                               **self.options)
+        return [all[i] for i in found]

@@ -116,6 +116,7 @@ namespace host {
 struct MapWorkspace;  // the buffers of the map entries (dvo_map.cpp)
 struct GraphWorkspace;  // the buffers of dvo_amd_optimize_graph (dvo_graph.cpp)
 struct GraphBatchWorkspace;  // the buffers of dvo_amd_optimize_graphs_batch (dvo_graph_batch.cpp)
+struct CovisWorkspace;  // the buffers of dvo_amd_covisibility (dvo_covisibility.cpp)
 }  // namespace host
 }  // namespace dvo_amd
 
@@ -233,6 +234,7 @@ struct dvo_amd_context {
   host::MapWorkspace *map_ws = nullptr;  // dvo_amd_point_cloud / _map_cloud / _voxel_downsample: grown to the largest call
   host::GraphWorkspace *graph_ws = nullptr;  // dvo_amd_optimize_graph: grown to the largest call
   host::GraphBatchWorkspace *graph_batch_ws = nullptr;  // dvo_amd_optimize_graphs_batch: grown to the largest call
+  host::CovisWorkspace *covis_ws = nullptr;  // dvo_amd_covisibility: grown to the largest call
 };
 
 namespace dvo_amd {
@@ -394,6 +396,7 @@ int queue_must_be_idle(dvo_amd_context *ctx, const char *what);
 void map_workspace_release(dvo_amd_context *ctx);  // dvo_map.cpp
 void graph_workspace_release(dvo_amd_context *ctx);  // dvo_graph.cpp
 void graph_batch_workspace_release(dvo_amd_context *ctx);  // dvo_graph_batch.cpp
+void covis_workspace_release(dvo_amd_context *ctx);  // dvo_covisibility.cpp
 // the argument checks of the pose-graph entries (dvo_graph.cpp); `entry` prefixes dvo_amd_last_error()
 int graph_check_arguments(const char *entry, int n_vertices, const double *poses, int n_edges, const dvo_amd_graph_edge *edges,
                           const dvo_amd_graph_options *opt);

@@ -1269,6 +1269,7 @@ void dvo_amd_context_destroy(dvo_amd_context *ctx) {
   map_workspace_release(ctx);
   graph_workspace_release(ctx);
   graph_batch_workspace_release(ctx);
+  covis_workspace_release(ctx);
   if (ctx->out_wire) (void)hipHostFree(ctx->out_wire);
   if (ctx->ovf_host) (void)hipHostFree(ctx->ovf_host);
   if (ctx->rcp_table_dev) (void)hipFree(ctx->rcp_table_dev);

@@ -385,6 +385,89 @@ int dvo_amd_validate_proposals(dvo_amd_context *ctx, int n_keyframes, const dvo_
                                dvo_amd_constraint_proposal *proposals, int *n_out, int max_in_flight);
 
 /*
+ * Loop-closure candidates: what feeds dvo_amd_proposals_for_candidates.  dvo_amd_find_constraint_candidates is
+ * dvo_slam::NearestNeighborConstraintSearch::findPossibleConstraints (keyframe_constraint_search.cpp:41-72: a radius search on
+ * the keyframes' translations, called for a new keyframe at keyframe_graph.cpp:456 and for every keyframe at :233) and, with
+ * min_overlap > 0, THIS LIBRARY'S EXTENSION of it: the radius candidates are pruned by how much of one keyframe the other
+ * actually sees, counted on the device by dvo_amd_covisibility before any alignment runs.  (A keyframe half a metre away that
+ * looks the other way is a radius candidate; the validator spends four level-3 alignments on it before its voters reject it.)
+ *
+ * dvo_amd_covisibility: the seven counts of n_pairs ordered keyframe pairs (a, b) in one call.  The rule, operation by
+ * operation; the library is built without contraction, so every product and sum rounds on its own.  `level` is clamped to the
+ * coarsest level both pyramids of the pair have; where the two levels differ in size, the rays are a's own and the projection
+ * uses b's width, height and intrinsics.  For the ordered pair (a, b):
+ *  1. transform: the host forms T = pose_b^-1 * pose_a in double, the inverse taken as that of a rigid transform (R^T, -R^T t)
+ *     as dvo_amd_map_render does (only finiteness is checked): Ri = Rb^T, ti[r] = -((Rb[0][r]*tb0 + Rb[1][r]*tb1) + Rb[2][r]*tb2);
+ *     T[r][c] = (Ri[r][0]*Ra[0][c] + Ri[r][1]*Ra[1][c]) + Ri[r][2]*Ra[2][c] and
+ *     T[r][3] = ((Ri[r][0]*ta0 + Ri[r][1]*ta1) + Ri[r][2]*ta2) + ti[r]: products summed in index order; rows 0..2 are cast to
+ *     float;
+ *  2. point: for every pixel (u, v) of a with a finite depth z the camera point is (tx[u]*z, ty[v]*z, z) with the level's rays
+ *     tx[u] = (u - ox) / fx, ty[v] = (v - oy) / fy, moved into b's frame by q = ((T0*x + T1*y) + T2*z) + T3 per row in fp32 (the
+ *     arithmetic of the point cloud above); the pixel counts as `valid`;
+ *  3. near plane: if !(qz >= near_z) the pixel counts as `behind` (NaN included);
+ *  4. projection: pu = floorf(((qx*fx) / qz + ox) + 0.5f), pv = floorf(((qy*fy) / qz + oy) + 0.5f) with b's fx, fy, ox, oy, the
+ *     division correctly rounded; if !(pu >= 0 && pu <= (float)(w-1) && pv >= 0 && pv <= (float)(h-1)) the pixel counts as
+ *     `outside`: the test is made in float before any conversion to int, so NaN and 1e30 are outside, never an overflow;
+ *  5. depth lookup: Zb = depth_b[pv, pu]; if it is NaN the pixel counts as `no_depth`;
+ *  6. tolerance: s = qz - 0.4f, tol = depth_sigmas * (0.0012f + 0.0019f * (s*s)): the reference's own depth noise model and
+ *     factor of its occlusion test (dense_tracking_impl.cpp:122-128,275; default depth_sigmas 20);
+ *  7. classification: d = Zb - qz; d < -tol counts as `occluded` (b sees a nearer surface), d > tol as `seen_through` (b sees
+ *     past the point), anything else as `consistent`.
+ * By construction valid = behind + outside + no_depth + consistent + occluded + seen_through.  The overlap of (a, b) is
+ * (double)consistent / (double)valid, and 0 when valid == 0.  Pair (a, a) and repeated pairs are legal.  All counts are
+ * integers: the result does not depend on the launch geometry, on the order of the pairs or on what else is in the call.
+ * One launch, one copy back and one synchronisation per call whatever n_pairs is; buffers are the context's, grown to the
+ * largest call and kept.
+ *
+ * Errors of dvo_amd_covisibility.  DVO_AMD_ERR_INVALID_ARGUMENT (reason in dvo_amd_last_error()), before a device is looked
+ * for: a NULL array with n_pairs > 0, an index outside [0, n_keyframes), a keyframe of a pair without an image or with a
+ * non-finite pose entry, level < 0, depth_sigmas non-finite or negative, near_z non-finite or <= 0.  Then DVO_AMD_ERR_NO_DEVICE
+ * without a GPU, DVO_AMD_ERR_INVALID_ARGUMENT for a NULL context, DVO_AMD_ERR_DEVICE_MISMATCH for a pyramid of another device,
+ * DVO_AMD_ERR_INVALID_ARGUMENT while pairs are queued on the context.  n_pairs == 0 is DVO_AMD_OK.
+ *
+ * dvo_amd_find_constraint_candidates.  Radius stage (host code): translations are cast to float (pcl::PointXYZ stores them so),
+ * d2 = ((dx*dx + dy*dy) + dz*dz) in fp32, and keyframe k is a candidate iff d2 <= max_distance * max_distance (fp32).  The query
+ * keyframe itself is included, as in the reference (the odometry voter rejects it later).  Candidates come out in ascending
+ * keyframe index.  The reference delegates the boundary and the order to FLANN (pcl::KdTreeFLANN::radiusSearch), whose source
+ * is not in its tree: `<=` and ascending index are this library's rule.
+ * Overlap stage, when min_overlap > 0 (opt is then required, and every keyframe within the radius needs an image): one
+ * dvo_amd_covisibility call over both directions of every radius candidate; a candidate c is kept iff
+ * max(overlap(q -> c), overlap(c -> q)) >= min_overlap -- the maximum, so that a close-up of part of a wider view still counts --
+ * and overlap[] (may be NULL) receives that maximum for every kept candidate.  When min_overlap <= 0 the entry is exactly the
+ * reference's search: no device is needed and none is looked for, ctx may be NULL, and overlap[] is filled with NaN.
+ * DVO_AMD_ERR_INVALID_ARGUMENT for: NULL keyframes or n_out, n_keyframes < 1, `keyframe` out of range, capacity < 0 or a NULL
+ * candidate array with capacity > 0, max_distance non-finite or negative, a NaN min_overlap, a non-finite pose entry of any
+ * keyframe; with min_overlap > 0 the errors of dvo_amd_covisibility as well.  If capacity is too small: DVO_AMD_ERR_CAPACITY
+ * with *n_out set to the size needed (candidates untouched).
+ */
+typedef struct {
+  unsigned valid;        /* pixels of a with finite depth at the level */
+  unsigned behind;       /* ... whose point has !(qz >= near_z) in b */
+  unsigned outside;      /* ... that project outside b's image */
+  unsigned no_depth;     /* ... that land on a NaN depth of b */
+  unsigned consistent;   /* |Zb - qz| <= tol */
+  unsigned occluded;     /* Zb - qz < -tol : b sees a nearer surface */
+  unsigned seen_through; /* Zb - qz >  tol : b sees past the point */
+  unsigned reserved;
+} dvo_amd_covisibility_counts;
+
+typedef struct {
+  int level;           /* default 3 */
+  float near_z;        /* default 0.1 */
+  float depth_sigmas;  /* default 20 */
+} dvo_amd_covisibility_options;
+
+void dvo_amd_default_covisibility_options(dvo_amd_covisibility_options *opt);
+
+int dvo_amd_covisibility(dvo_amd_context *ctx, int n_keyframes, const dvo_amd_keyframe *keyframes,
+                         const dvo_amd_covisibility_options *opt, int n_pairs, const int *pair_a, const int *pair_b,
+                         dvo_amd_covisibility_counts *out);
+
+int dvo_amd_find_constraint_candidates(dvo_amd_context *ctx, int n_keyframes, const dvo_amd_keyframe *keyframes, int keyframe,
+                                       float max_distance, double min_overlap, const dvo_amd_covisibility_options *opt,
+                                       int *candidates, double *overlap, int capacity, int *n_out);
+
+/*
  * Dual-match front-end step: the two alignments LocalTracker::update runs per frame with
  * tbb::parallel_invoke (local_tracker.cpp:170-186) -- keyframe -> frame starting from last_keyframe_pose^-1 and
  * last frame -> frame starting from identity -- as ONE two-pair batch sharing the frame's pyramid, plus the quantities the

@@ -4,6 +4,8 @@
 //   dvo_slam::TrackingResultEvaluation (+ LogLikelihood / NormalizedLogLikelihood / EntropyRatio)
 //                                                        dvo_slam/include/dvo_slam/tracking_result_evaluation.h:31-77
 //   dvo_slam::Keyframe {id, image, pose, evaluation}     dvo_slam/include/dvo_slam/keyframe.h
+//   dvo_slam::KeyframeConstraintSearchInterface, dvo_slam::NearestNeighborConstraintSearch
+//                                                        dvo_slam/include/dvo_slam/keyframe_constraint_search.h:30-58
 //   dvo_slam::constraints::ConstraintProposal            .../constraints/constraint_proposal.h:34-90
 //   dvo_slam::constraints::{CrossValidation, TrackingResultEvaluation, ConstraintRatio, NaNResult, OdometryConstraint}Voter
 //                                                        .../constraints/constraint_proposal_voter.h
@@ -110,6 +112,71 @@ class Keyframe {
 };
 typedef std::shared_ptr<Keyframe> KeyframePtr;
 typedef std::vector<KeyframePtr> KeyframeVector;
+
+// keyframe_constraint_search.h:30-39
+class KeyframeConstraintSearchInterface {
+ public:
+  virtual ~KeyframeConstraintSearchInterface() {}
+  virtual void findPossibleConstraints(const KeyframeVector &all, const KeyframePtr &keyframe, KeyframeVector &candidates) = 0;
+};
+typedef std::shared_ptr<KeyframeConstraintSearchInterface> KeyframeConstraintSearchInterfacePtr;
+
+// keyframe_constraint_search.h:41-58 over dvo_amd_find_constraint_candidates: the keyframes within maxDistance() of `keyframe`
+// (itself included), in the order of `all`.  minOverlap() > 0 is this library's extension: candidates whose view overlap with
+// `keyframe` (dvo_amd_covisibility, the larger of the two directions, with overlapOptions()) is below it are dropped before any
+// alignment runs; their images are then built to overlapOptions().level + 1 levels.  With minOverlap() == 0 (the default) the
+// search is the reference's and touches no GPU.
+class NearestNeighborConstraintSearch : public KeyframeConstraintSearchInterface {
+ public:
+  explicit NearestNeighborConstraintSearch(float max_distance, double min_overlap = 0.0, int device = 0)
+      : max_distance_(max_distance), min_overlap_(min_overlap), device_(device) {
+    dvo_amd_default_covisibility_options(&options_);
+  }
+  virtual ~NearestNeighborConstraintSearch() {}
+
+  float maxDistance() const { return max_distance_; }
+  void maxDistance(const float &d) { max_distance_ = d; }
+  double minOverlap() const { return min_overlap_; }
+  void minOverlap(const double &o) { min_overlap_ = o; }
+  dvo_amd_covisibility_options &overlapOptions() { return options_; }
+  // of the last search, one per candidate returned (NaN when minOverlap() <= 0)
+  const std::vector<double> &overlaps() const { return overlaps_; }
+
+  void findPossibleConstraints(const KeyframeVector &all, const KeyframePtr &keyframe, KeyframeVector &candidates) override {
+    const bool prune = min_overlap_ > 0.0;
+    std::vector<dvo_amd_keyframe> ckf(std::max<size_t>(all.size(), 1));
+    int at = -1;
+    for (size_t i = 0; i < all.size(); ++i) {
+      const Keyframe &kf = *all[i];
+      std::memset(&ckf[i], 0, sizeof(ckf[i]));
+      ckf[i].id = kf.id();
+      if (prune && kf.image()) {
+        kf.image()->build((size_t)std::max(options_.level, 0) + 1);
+        ckf[i].image = kf.image()->handle();
+      }
+      std::memcpy(ckf[i].pose, dvo::core::data(kf.pose()), sizeof(ckf[i].pose));
+      if (all[i] == keyframe) at = (int)i;
+    }
+    if (prune && !tracker_) tracker_.reset(new dvo::DenseTracker(dvo::DenseTracker::getDefaultConfig(), device_));
+    std::vector<int> found(std::max<size_t>(all.size(), 1));
+    overlaps_.assign(found.size(), 0.0);
+    int n = 0;
+    dvo::detail::check(dvo_amd_find_constraint_candidates(prune ? tracker_->handle() : nullptr, (int)all.size(), ckf.data(), at,
+                                                          max_distance_, min_overlap_, &options_, found.data(), overlaps_.data(),
+                                                          (int)all.size(), &n),
+                       "NearestNeighborConstraintSearch::findPossibleConstraints");
+    overlaps_.resize((size_t)n);
+    for (int i = 0; i < n; ++i) candidates.push_back(all[(size_t)found[(size_t)i]]);
+  }
+
+ private:
+  float max_distance_;
+  double min_overlap_;
+  int device_;
+  dvo_amd_covisibility_options options_;
+  std::unique_ptr<dvo::DenseTracker> tracker_;
+  std::vector<double> overlaps_;
+};
 
 namespace constraints {
 

@@ -163,6 +163,9 @@ int dvo_amd_debug_ll_overflow(dvo_amd_context *ctx, const float *residuals, int 
  * call (input stage, sort, reduction; host gaps between them excluded), the time of the copy of the voxels to the host, and
  * the points it was handed.  scripts/map_cloud_timing.py */
 int dvo_amd_debug_map_timing(dvo_amd_context *ctx, double *device_ms, double *copy_ms, long long *points);
+/* the last dvo_amd_covisibility of the context (dvo_amd_find_constraint_candidates calls it too): device time of k_covis from
+ * hipEvents inside the call.  scripts/covisibility_timing.py */
+int dvo_amd_debug_covisibility_ms(const dvo_amd_context *ctx, double *device_ms);
 /* the last dvo_amd_map_insert / _set_poses / _remove / _extract of a keyframe map: device time of its kernels from hipEvents
  * inside the call (host gaps excluded), the time of the copy of the voxels to the host (extract), the points and the voxels of
  * the delta it merged (0 for an extract), and the entries of one merge tile.  scripts/keyframe_map_timing.py */
