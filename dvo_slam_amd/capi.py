@@ -45,6 +45,8 @@ EXPORTS = [
     "dvo_amd_map_stats", "dvo_amd_map_extract", "dvo_amd_map_render", "dvo_amd_map_render_pyramid", "dvo_amd_debug_keyframe_map_timing", "dvo_amd_debug_map_merge",
     "dvo_amd_default_covisibility_options", "dvo_amd_covisibility", "dvo_amd_find_constraint_candidates",
     "dvo_amd_debug_covisibility_ms",
+    "dvo_amd_remap_create", "dvo_amd_remap_create_undistort", "dvo_amd_remap_retain", "dvo_amd_remap_release", "dvo_amd_remap_info",
+    "dvo_amd_remap_download", "dvo_amd_pyramid_create_raw_remapped", "dvo_amd_debug_ingest_timing",
 ]
 
 
@@ -270,6 +272,18 @@ def lib():
                                                      C.POINTER(CCovisibilityOptions), C.POINTER(C.c_int), dp, C.c_int,
                                                      C.POINTER(C.c_int)]
     L.dvo_amd_debug_covisibility_ms.argtypes = [vp, dp]
+    L.dvo_amd_remap_create.argtypes = [C.c_int, C.c_int, C.c_int, fp, fp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.dvo_amd_remap_create_undistort.argtypes = [C.c_int, C.c_int, C.c_int, fp, C.c_int, C.c_int, fp, fp, C.POINTER(vp)]
+    L.dvo_amd_remap_retain.argtypes = [vp]
+    L.dvo_amd_remap_retain.restype = None
+    L.dvo_amd_remap_release.argtypes = [vp]
+    L.dvo_amd_remap_release.restype = None
+    L.dvo_amd_remap_info.argtypes = [vp, ip, ip, ip, ip, ip]
+    L.dvo_amd_remap_download.argtypes = [vp, fp, fp]
+    L.dvo_amd_pyramid_create_raw_remapped.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_float, C.c_int, vp,
+                                                      C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_double,
+                                                      C.POINTER(vp)]
+    L.dvo_amd_debug_ingest_timing.argtypes = [C.c_int, C.c_int, dp]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -360,6 +374,74 @@ class Config:
                        int(self.SegmentGeometry), 0)
 
 
+class Remap:
+    """A dvo_amd_remap: the device-resident table pair through which `RgbdImagePyramid.from_raw(..., remap=)` resamples a raw
+    frame (what image_proc's cv::initUndistortRectifyMap + cv::remap do on the CPU in front of the reference).  Immutable,
+    shareable between trackers and threads; the rules are pinned in include/dvo_amd.h."""
+
+    def __init__(self):
+        raise TypeError("use Remap.from_maps or Remap.undistort")
+
+    @classmethod
+    def from_maps(cls, map_x, map_y, src_size, device: int = 0):
+        """map_x, map_y: float32 [h, w] source positions of every output pixel (cv::remap's CV_32FC1 pair); src_size = (width,
+        height) of the source image they refer to."""
+        map_x = np.ascontiguousarray(map_x, dtype=np.float32)
+        map_y = np.ascontiguousarray(map_y, dtype=np.float32)
+        if map_x.shape != map_y.shape or map_x.ndim != 2:
+            raise ValueError("map_x and map_y must be 2-D arrays of the same shape")
+        h, w = map_x.shape
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        _check(lib().dvo_amd_remap_create(device, w, h, _fp(map_x), _fp(map_y), w, int(src_size[0]), int(src_size[1]),
+                                          C.byref(self._h)), "dvo_amd_remap_create")
+        self.device = device
+        return self
+
+    @classmethod
+    def undistort(cls, size, K_out, src_size, K_src, dist, device: int = 0):
+        """The map of the five-coefficient lens model, computed on the device: size = (width, height) and K_out = (fx, fy, ox, oy)
+        of the rectified camera, src_size and K_src of the real one, dist = (k1, k2, p1, p2, k3) in OpenCV's order."""
+        k_out = np.ascontiguousarray(K_out, dtype=np.float32).reshape(4)
+        k_src = np.ascontiguousarray(K_src, dtype=np.float32).reshape(4)
+        d = np.ascontiguousarray(dist, dtype=np.float32).reshape(5)
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        _check(lib().dvo_amd_remap_create_undistort(device, int(size[0]), int(size[1]), _fp(k_out), int(src_size[0]),
+                                                    int(src_size[1]), _fp(k_src), _fp(d), C.byref(self._h)),
+               "dvo_amd_remap_create_undistort")
+        self.device = device
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().dvo_amd_remap_release(h)
+            self._h = None
+
+    def info(self) -> dict:
+        """{"width", "height", "src_width", "src_height", "n_inside"}: n_inside = output pixels whose source position lies
+        inside the source (the others become 0 / NaN)"""
+        v = [C.c_int() for _ in range(5)]
+        _check(lib().dvo_amd_remap_info(self._h, *[C.byref(x) for x in v]), "dvo_amd_remap_info")
+        return dict(zip(("width", "height", "src_width", "src_height", "n_inside"), (x.value for x in v)))
+
+    def download(self):
+        """(map_x, map_y), float32 [h, w] each"""
+        i = self.info()
+        mx, my = np.empty((i["height"], i["width"]), np.float32), np.empty((i["height"], i["width"]), np.float32)
+        _check(lib().dvo_amd_remap_download(self._h, _fp(mx), _fp(my)), "dvo_amd_remap_download")
+        return mx, my
+
+
+def ingest_timing(enable: bool = True, device: int = 0) -> float:
+    """(instrumentation) switches the event bracket around every pyramid build of `device` on or off and returns the device time
+    of the most recent bracketed build in ms (dvo_amd_debug_ingest_timing)"""
+    ms = C.c_double()
+    _check(lib().dvo_amd_debug_ingest_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_ingest_timing")
+    return ms.value
+
+
 class RgbdImagePyramid:
     """RgbdCameraPyramid(w, h, K).create(intensity, depth) with `levels` levels built on the GPU."""
 
@@ -390,9 +472,11 @@ class RgbdImagePyramid:
 
     @classmethod
     def from_raw(cls, image, depth, K, levels: int, depth_scale: float = 1.0 / 5000.0, device: int = 0,
-                 timestamp: float = 0.0):
+                 timestamp: float = 0.0, remap: "Remap | None" = None):
         """Frame ingest on the device: uint8 image (HxW gray or HxWx3 BGR) + uint16 depth (0 = invalid), as a camera or a
-        TUM PNG pair delivers them (benchmark_slam.cpp:46-93).  Gray conversion and depth scaling run on the GPU."""
+        TUM PNG pair delivers them (benchmark_slam.cpp:46-93).  Gray conversion and depth scaling run on the GPU.
+        With `remap` the frame has the remap's source size and is resampled through it (dvo_amd_pyramid_create_raw_remapped):
+        the pyramid has the remap's output size and K is the rectified camera's."""
         image = np.ascontiguousarray(image, dtype=np.uint8)
         depth = np.ascontiguousarray(depth, dtype=np.uint16)
         if image.shape[:2] != depth.shape or depth.ndim != 2 or image.ndim not in (2, 3):
@@ -400,22 +484,34 @@ class RgbdImagePyramid:
         channels = 1 if image.ndim == 2 else image.shape[2]
         h, w = depth.shape
         return cls._raw(image.ctypes.data, channels, w * channels, depth.ctypes.data, w, depth_scale, 0, w, h, K, levels,
-                        device, timestamp)
+                        device, timestamp, remap)
 
     @classmethod
     def from_raw_device(cls, d_image: int, channels: int, d_depth: int, width: int, height: int, K, levels: int,
                         depth_scale: float = 1.0 / 5000.0, device: int = 0, timestamp: float = 0.0,
-                        image_stride_bytes: int | None = None, depth_stride: int | None = None):
-        """As from_raw, for raw frames already resident in HBM (device pointers)."""
+                        image_stride_bytes: int | None = None, depth_stride: int | None = None,
+                        remap: "Remap | None" = None):
+        """As from_raw, for raw frames already resident in HBM (device pointers).  With `remap`, width and height are the raw
+        frame's (the remap's source size)."""
         return cls._raw(d_image, channels, image_stride_bytes or width * channels, d_depth, depth_stride or width,
-                        depth_scale, 1, width, height, K, levels, device, timestamp)
+                        depth_scale, 1, width, height, K, levels, device, timestamp, remap)
 
     @classmethod
     def _raw(cls, image_ptr, channels, image_stride, depth_ptr, depth_stride, depth_scale, on_device, w, h, K, levels,
-             device, timestamp):
+             device, timestamp, remap=None):
         self = cls.__new__(cls)
         fx, fy, ox, oy = [float(k) for k in K]
         self._h = C.c_void_p()
+        if remap is not None:
+            i = remap.info()
+            if (w, h) != (i["src_width"], i["src_height"]):
+                raise ValueError(f"the raw frame is {w}x{h} but the remap's source is {i['src_width']}x{i['src_height']}")
+            _check(lib().dvo_amd_pyramid_create_raw_remapped(device, C.c_void_p(image_ptr), channels, image_stride,
+                                                             C.c_void_p(depth_ptr), depth_stride, depth_scale, on_device,
+                                                             remap._h, fx, fy, ox, oy, levels, timestamp, C.byref(self._h)),
+                   "dvo_amd_pyramid_create_raw_remapped")
+            self.device = device
+            return self
         _check(lib().dvo_amd_pyramid_create_raw(device, C.c_void_p(image_ptr), channels, image_stride,
                                                 C.c_void_p(depth_ptr), depth_stride, depth_scale, on_device, w, h, fx, fy,
                                                 ox, oy, levels, timestamp, C.byref(self._h)),

@@ -7,6 +7,7 @@
 //   dvo_map.cpp       the keyframe map's point cloud: organized clouds at a pose, the deterministic voxel aggregate
 //   dvo_graph.cpp     the pose-graph optimizer: edge linearisation, dense fp64 Cholesky, Levenberg-Marquardt and dogleg
 //   dvo_graph_batch.cpp  many small pose graphs in one launch: one workgroup per graph, the whole optimization on the device
+//   dvo_rectify.cpp   remap tables (lens undistortion, arbitrary maps) and the frame ingest that resamples through one
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -104,6 +105,28 @@ struct dvo_amd_pyramid {
   // entries are never moved or removed while the pyramid lives: a pointer handed out by pyramid_selection() stays valid and may
   // be read without the lock (only the vector itself needs `mu`)
   std::vector<std::unique_ptr<Selection>> selections;
+};
+
+// one remap table (dvo_rectify.cpp): immutable after create, refcounted, shareable between contexts and threads
+struct dvo_amd_remap {
+  std::atomic<int> refs{1};
+  int device = 0;
+  int w = 0, h = 0;    // the output image
+  int sw = 0, sh = 0;  // the source image the positions refer to
+  int n_inside = 0;    // output pixels whose source position lies inside the source (the sampling rule's step 1)
+  void *mem = nullptr;                        // one allocation: the two planes and the counter
+  float *map_x = nullptr, *map_y = nullptr;   // device, [w * h] each, 256-byte aligned
+  int *counter = nullptr;                     // device: where the kernels count n_inside
+};
+
+// a raw sensor frame (frame ingest on the device)
+struct RawFrame {
+  const unsigned char *image;  // uint8, `channels` interleaved channels (1 = gray, 3 = BGR)
+  int channels, image_stride_bytes;
+  const unsigned short *depth;  // uint16, 0 = invalid
+  int depth_stride;             // in elements
+  float depth_scale;
+  const dvo_amd_remap *remap;   // null: the frame has the pyramid's size; else it has the remap's source size and is resampled
 };
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -353,6 +376,14 @@ int desc_alloc(int device, void **out);
 void desc_free(int device, void *p);
 void slab_free(int device, size_t bytes, void *p);
 int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const Selection **out);
+std::mutex &device_mutex(int device);  // the mutex of the device's shared state (never held across one of the calls above)
+int pyramid_build(int device, const float *src_i, const float *src_z, const RawFrame *raw, bool src_on_device, int width,
+                  int height, int stride, float fx, float fy, float ox, float oy, int levels, double timestamp,
+                  dvo_amd_pyramid **out);
+int ingest_timing(int device, int enable, double *last_ms);  // dvo_amd_debug_ingest_timing
+
+// ---- dvo_rectify.cpp
+int rectify_level0(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st);
 
 // ---- dvo_tracker.cpp
 dvo_amd_iteration_stats *stats_push(Job &j);

@@ -28,6 +28,10 @@ struct DeviceState {
   hipStream_t prep_stream = nullptr;
   std::vector<std::pair<size_t, void *>> free_slabs;
   std::vector<void *> desc_chunks, desc_free;
+  // dvo_amd_debug_ingest_timing: two events around a build's work on the prep stream (off unless asked for)
+  std::atomic<bool> timing{false};
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  double last_ms = 0.0;
 };
 DeviceState g_dev[kMaxDevices];
 
@@ -36,6 +40,20 @@ int device_prep_stream(int device, hipStream_t *s) {
   std::lock_guard<std::mutex> lk(d.mu);
   if (!d.prep_stream) HIP_TRY(hipStreamCreateWithFlags(&d.prep_stream, hipStreamNonBlocking));
   *s = d.prep_stream;
+  return DVO_AMD_OK;
+}
+
+std::mutex &device_mutex(int device) { return g_dev[device].mu; }
+
+int ingest_timing(int device, int enable, double *last_ms) {
+  DeviceState &d = g_dev[device];
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (enable && !d.ev[0]) {
+    HIP_TRY(hipSetDevice(device));
+    for (hipEvent_t &e : d.ev) HIP_TRY(hipEventCreate(&e));
+  }
+  d.timing = enable != 0;
+  if (last_ms) *last_ms = d.last_ms;
   return DVO_AMD_OK;
 }
 
@@ -115,15 +133,6 @@ size_t pyramid_layout(dvo_amd_pyramid *p, char *base) {
   return off;
 }
 
-// a raw sensor frame (frame ingest on the device)
-struct RawFrame {
-  const unsigned char *image;  // uint8, `channels` interleaved channels (1 = gray, 3 = BGR)
-  int channels, image_stride_bytes;
-  const unsigned short *depth;  // uint16, 0 = invalid
-  int depth_stride;             // in elements
-  float depth_scale;
-};
-
 int pyramid_build(int device, const float *src_i, const float *src_z, const RawFrame *raw, bool src_on_device, int width,
                   int height, int stride, float fx, float fy, float ox, float oy, int levels, double timestamp,
                   dvo_amd_pyramid **out) {
@@ -131,8 +140,9 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   *out = nullptr;
   if (width < 4 || height < 2 || levels < 1 || levels > DVO_AMD_MAX_LEVELS) return DVO_AMD_ERR_INVALID_ARGUMENT;
   if (raw) {
+    const int raw_width = raw->remap ? raw->remap->sw : width;
     if (!raw->image || !raw->depth || (raw->channels != 1 && raw->channels != 3) ||
-        raw->image_stride_bytes < width * raw->channels || raw->depth_stride < width || !(raw->depth_scale > 0.0f))
+        raw->image_stride_bytes < raw_width * raw->channels || raw->depth_stride < raw_width || !(raw->depth_scale > 0.0f))
       return DVO_AMD_ERR_INVALID_ARGUMENT;
   } else if (!src_i || !src_z || stride < width) {
     return DVO_AMD_ERR_INVALID_ARGUMENT;
@@ -192,7 +202,17 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   };
   LevelData &L0 = p->lv[0];
   hipError_t e;
-  if (raw) {
+  DeviceState &dev = g_dev[device];
+  const bool timed = dev.timing.load();
+  if (timed && (e = hipEventRecord(dev.ev[0], st)) != hipSuccess) return bail(fail_hip("ingest timing", e));
+  if (raw && raw->remap) {
+    rc = rectify_level0(device, *raw, src_on_device, L0.i_plane, L0.z_plane, st);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return bail(rc);
+    }
+    e = hipSuccess;
+  } else if (raw) {
     const unsigned char *d_img = raw->image;
     const unsigned short *d_z = raw->depth;
     int img_stride = raw->image_stride_bytes, z_stride = raw->depth_stride;
@@ -256,8 +276,13 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   }
   e = hipMemcpyAsync(p->cur_desc, cur_host, sizeof(CurLevelDesc) * levels, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return bail(fail_hip("pyramid descriptors", e));
+  if (timed && (e = hipEventRecord(dev.ev[1], st)) != hipSuccess) return bail(fail_hip("ingest timing", e));
   e = hipStreamSynchronize(st);
   if (e != hipSuccess) return bail(fail_hip("pyramid build", e));
+  if (timed) {
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, dev.ev[0], dev.ev[1]) == hipSuccess) dev.last_ms = ms;
+  }
   *out = p;
   return DVO_AMD_OK;
 }
@@ -368,7 +393,7 @@ int dvo_amd_pyramid_create_raw(int device, const unsigned char *image, int chann
                                const unsigned short *depth, int depth_stride, float depth_scale, int on_device, int width,
                                int height, float fx, float fy, float ox, float oy, int levels, double timestamp,
                                dvo_amd_pyramid **out) {
-  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale};
+  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale, nullptr};
   return pyramid_build(device, nullptr, nullptr, &raw, on_device != 0, width, height, width, fx, fy, ox, oy, levels,
                        timestamp, out);
 }

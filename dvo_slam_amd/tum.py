@@ -111,12 +111,16 @@ def read_groundtruth(path: str):
 
 
 def load(K, rgb_file: str, depth_file: str, levels: int, device: int = 0, timestamp: float = 0.0,
-         depth_scale: float = TUM_DEPTH_SCALE) -> capi.RgbdImagePyramid:
+         depth_scale: float = TUM_DEPTH_SCALE, remap: "capi.Remap | None" = None) -> capi.RgbdImagePyramid:
     """`load()` of benchmark_slam.cpp:46-93: imread both files, BGR -> gray float, raw depth -> metres with 0 -> NaN,
-    camera.create(...).  Decoding happens on the host, both conversions and the pyramid on the GPU."""
+    camera.create(...).  Decoding happens on the host, both conversions and the pyramid on the GPU.
+    remap: a capi.Remap through which both images are resampled on the way in (K is then the rectified camera's).  There is no
+    preset: TUM's depth PNGs were registered by the driver with default intrinsics, so whether to resample them with the
+    colour camera's distortion is the caller's decision."""
     bgr = imread_color(rgb_file)
     depth = imread_depth(depth_file)
-    return capi.RgbdImagePyramid.from_raw(bgr, depth, K, levels, depth_scale=depth_scale, device=device, timestamp=timestamp)
+    return capi.RgbdImagePyramid.from_raw(bgr, depth, K, levels, depth_scale=depth_scale, device=device, timestamp=timestamp,
+                                          remap=remap)
 
 
 def format_trajectory_line(timestamp: float, T) -> str:
@@ -130,10 +134,10 @@ def format_trajectory_line(timestamp: float, T) -> str:
 
 
 def replay(assoc_path: str, trajectory_path: str | None = None, K=TUM_FR1_INTRINSICS, config: capi.Config | None = None,
-           device: int = 0, max_frames: int | None = None):
+           device: int = 0, max_frames: int | None = None, remap: "capi.Remap | None" = None):
     """Frame-to-frame odometry over an association file (the EstimateTrajectory mode of dvo_benchmark without the SLAM back
     end): pose_t = pose_{t-1} * T_t^-1 with T_t = match(frame_{t-1}, frame_t), one trajectory line per frame.
-    Returns [(timestamp, 4x4 pose)]."""
+    Returns [(timestamp, 4x4 pose)].  remap: see load()."""
     cfg = config or capi.Config(FirstLevel=3, LastLevel=1)
     trk = capi.DenseTracker(cfg, device=device)
     base = os.path.dirname(os.path.abspath(assoc_path))
@@ -147,7 +151,7 @@ def replay(assoc_path: str, trajectory_path: str | None = None, K=TUM_FR1_INTRIN
     try:
         for p in pairs:
             cur = load(K, os.path.join(base, p.RgbFile), os.path.join(base, p.DepthFile), cfg.getNumLevels(), device,
-                       p.RgbTimestamp)
+                       p.RgbTimestamp, remap=remap)
             if prev is not None:
                 r = trk.match(prev, cur)
                 if not r.isNaN():

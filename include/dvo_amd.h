@@ -201,6 +201,91 @@ int dvo_amd_pyramid_create_raw(int device, const unsigned char *image, int chann
                                const unsigned short *depth, int depth_stride, float depth_scale, int on_device, int width,
                                int height, float fx, float fy, float ox, float oy, int levels, double timestamp,
                                dvo_amd_pyramid **out);
+
+/*
+ * Rectification at ingest: remap tables on the device and a frame ingest that resamples through one.
+ *
+ * The reference assumes a rectified image: camera_keyframe_tracking.cpp:89 builds its intrinsics from CameraInfo::P, the
+ * projection matrix of the rectified camera, and relies on image_proc having run cv::initUndistortRectifyMap + cv::remap on the
+ * CPU upstream.  These entries are that step for a caller that holds the sensor's own frame: a dvo_amd_remap is made once per
+ * camera, and dvo_amd_pyramid_create_raw_remapped takes every raw frame through it on the way into level 0 -- a frame that is
+ * already in HBM never comes back to the host to be rectified.
+ *
+ * A dvo_amd_remap is an immutable, refcounted, device-resident pair of float planes map_x[n], map_y[n] (n = width * height of
+ * the OUTPUT image, row-major, one plane after the other): output pixel i takes its value from position (map_x[i], map_y[i]) of
+ * the source image, in pixels, the convention of cv::remap with a CV_32FC1 pair.  It also stores the size of the source it
+ * refers to.  Like a pyramid it may be shared between contexts and threads; a pyramid built through it does not retain it (the
+ * pyramid holds planes, not positions), so the two may be released in either order.
+ *   dvo_amd_remap_create            the two planes from the host (stride in floats, >= width): any map -- a stereo
+ *                                   rectification, a fisheye model, a crop or a resize
+ *   dvo_amd_remap_create_undistort  the planes computed on the device from the five-coefficient lens model, by the rule below
+ *   dvo_amd_remap_info              sizes and n_inside (any output may be NULL)
+ *   dvo_amd_remap_download          the two planes back to the host (width * height floats each)
+ * k_out, k_src = {fx, fy, ox, oy} of the rectified (output) and the real (source) camera; dist = {k1, k2, p1, p2, k3} in OpenCV's
+ * order.  The output obeys dvo_amd_pyramid_create_raw's size rules (width >= 4 and a multiple of 4, height >= 2; for the pyramid
+ * entry on every level asked for) and holds at most 2^30 pixels; the source is at least 2x2 and at most 2^20 pixels a side.
+ *
+ * The undistortion rule.  cv::initUndistortRectifyMap with R = I and newCameraMatrix = k_out, in fp32 throughout and in this
+ * order.  (The reference's tree holds no OpenCV, and OpenCV itself works in double and rounds at the end: the order below is this
+ * library's rule, as with FLANN above.)  Every operation is fp32 and rounds once -- the library is built with -ffp-contract=off
+ * -- and the two divisions are correctly rounded, as in the ray tables of a pyramid level.  For output pixel (u, v):
+ *     x  = ((float)u - ox) / fx            y  = ((float)v - oy) / fy                         (k_out)
+ *     xx = x*x    yy = y*y    r2 = xx + yy    xy = x*y
+ *     rad = ((k3*r2 + k2)*r2 + k1)*r2 + 1
+ *     xd = x*rad + ((2p1*xy) + p2*(r2 + (xx + xx)))
+ *     yd = y*rad + (p1*(r2 + (yy + yy)) + (2p2*xy))            with 2p1 = 2.0f*p1, 2p2 = 2.0f*p2
+ *     map_x = xd*fx_src + ox_src           map_y = yd*fy_src + oy_src                        (k_src)
+ *
+ * The sampling rule.  For output pixel i with (sx, sy) = (map_x[i], map_y[i]) and a source of sw x sh pixels:
+ *  1. inside = sx >= 0 && sx < (float)(sw - 1) && sy >= 0 && sy < (float)(sh - 1).  The test is made in float before any
+ *     conversion to int: NaN, +-inf and 1e30 are outside, never an overflow; -0.0 is inside and is position 0.  n_inside counts
+ *     these pixels.
+ *  2. Outside: intensity 0.0f (cv::remap's BORDER_CONSTANT with a zero border value), depth NaN.
+ *  3. Intensity, bilinear on the grey values of the four taps:
+ *       x0 = floorf(sx), ax = sx - x0; y0 = floorf(sy), ay = sy - y0;
+ *       g00, g01, g10, g11 = the grey values at (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) as floats: the byte itself, or for
+ *         a BGR source dvo_amd_pyramid_create_raw's integer rule (1868 B + 9617 G + 4899 R + 8192) >> 14 applied PER TAP (the
+ *         library converts the frame to a 1 B/px grey plane once and gathers from that: the same integers);
+ *       top = g00 + ax*(g01 - g00), bot = g10 + ax*(g11 - g10), I = top + ay*(bot - top).
+ *     The result stays float.  Stated deviation: cv::remap on 8-bit data quantises the weights to 5 bits and rounds the result
+ *     to a byte; this rule keeps the fp32 weights and the fp32 value.
+ *  4. Depth, nearest and never blended, so that no depth is invented across a discontinuity:
+ *       px = floorf(sx + 0.5f), py = floorf(sy + 0.5f), the fp32 sums as written, including where they round up
+ *       (0.49999997f + 0.5f is 1.0f); raw 0 -> NaN, else (float)raw * depth_scale.
+ * Consequences.  An identity map (sx = u, sy = v, source and output of one size) reproduces dvo_amd_pyramid_create_raw's level-0
+ * planes bit for bit except in the last row and the last column, which are outside (0 / NaN).  A valid pixel next to an outside
+ * one gets NaN depth derivatives, so the point selection and the gather skip it exactly as they skip the rim of a sensor hole.
+ * Every output pixel has one writer and there is no floating-point sum across pixels: the planes do not depend on the launch
+ * geometry, and the levels above level 0 are built from them as for any other pyramid.
+ *
+ * dvo_amd_pyramid_create_raw_remapped is dvo_amd_pyramid_create_raw with the resampling in front: the raw frame has the remap's
+ * SOURCE size (image_stride_bytes >= src_width * channels, depth_stride >= src_width), the pyramid has the remap's OUTPUT size,
+ * and fx..oy are the intrinsics of the rectified camera, which the pyramid carries (k_out for an undistortion map).  A raw frame
+ * from the host is uploaded into a per-device staging area that grows to the largest source seen and is kept.
+ *
+ * Errors.  DVO_AMD_ERR_INVALID_ARGUMENT, with a reason in dvo_amd_last_error(), before a device is looked for: a NULL pointer; a
+ * size that breaks the rules above; stride < width; src_width or src_height < 2; a non-finite entry of k_out, k_src or dist, or
+ * fx or fy of either camera <= 0; a stride of the raw frame smaller than the remap's source row; depth_scale not > 0; channels
+ * other than 1 or 3; levels outside 1..DVO_AMD_MAX_LEVELS.  Then DVO_AMD_ERR_NO_DEVICE without a GPU, and
+ * DVO_AMD_ERR_DEVICE_MISMATCH for a remap that lives on another device than `device`.
+ *
+ * Not covered: depth-to-colour registration; lens models other than the five-coefficient one (they come in as tables through
+ * dvo_amd_remap_create); remapping float planes.
+ */
+typedef struct dvo_amd_remap dvo_amd_remap;
+int dvo_amd_remap_create(int device, int width, int height, const float *map_x, const float *map_y, int stride, int src_width,
+                         int src_height, dvo_amd_remap **out);
+int dvo_amd_remap_create_undistort(int device, int width, int height, const float k_out[4], int src_width, int src_height,
+                                   const float k_src[4], const float dist[5], dvo_amd_remap **out);
+void dvo_amd_remap_retain(dvo_amd_remap *r);
+void dvo_amd_remap_release(dvo_amd_remap *r);
+int dvo_amd_remap_info(const dvo_amd_remap *r, int *width, int *height, int *src_width, int *src_height, int *n_inside);
+int dvo_amd_remap_download(const dvo_amd_remap *r, float *map_x, float *map_y);
+int dvo_amd_pyramid_create_raw_remapped(int device, const unsigned char *image, int channels, int image_stride_bytes,
+                                        const unsigned short *depth, int depth_stride, float depth_scale, int on_device,
+                                        const dvo_amd_remap *remap, float fx, float fy, float ox, float oy, int levels,
+                                        double timestamp, dvo_amd_pyramid **out);
+
 void dvo_amd_pyramid_retain(dvo_amd_pyramid *p);
 void dvo_amd_pyramid_release(dvo_amd_pyramid *p);
 int dvo_amd_pyramid_levels(const dvo_amd_pyramid *p);

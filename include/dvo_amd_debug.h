@@ -222,6 +222,10 @@ int dvo_amd_debug_graph_symbolic(int n_vertices, const int *fixed, int n_edges, 
 int dvo_amd_debug_graph_sparse_timing(dvo_amd_context *ctx, double *symbolic_ms, double *linearise_ms, double *factorize_ms,
                                       double *solve_ms, int *fronts, int *levels, int *widest, double *factor_doubles,
                                       double *flops);
+/* with enable != 0 every later pyramid build on `device` (any dvo_amd_pyramid_create* entry) is bracketed by two events on the
+ * device's internal stream; *last_ms (may be NULL) receives the device time of the most recent bracketed build: uploads,
+ * ingest or remap, every level's planes */
+int dvo_amd_debug_ingest_timing(int device, int enable, double *last_ms);
 
 #ifdef __cplusplus
 }
