@@ -9,7 +9,7 @@ all: $(LIB)
 
 CPP := $(SRC)/dvo_kernels.hip $(SRC)/dvo_pyramid.cpp $(SRC)/dvo_tracker.cpp $(SRC)/dvo_sharded.cpp $(SRC)/dvo_probes.cpp \
        $(SRC)/dvo_validator.cpp $(SRC)/dvo_frontend.cpp $(SRC)/dvo_tum.cpp $(SRC)/dvo_map.cpp $(SRC)/dvo_graph.cpp \
-       $(SRC)/dvo_graph_batch.cpp $(SRC)/dvo_covisibility.cpp $(SRC)/dvo_rectify.cpp
+       $(SRC)/dvo_graph_batch.cpp $(SRC)/dvo_covisibility.cpp $(SRC)/dvo_rectify.cpp $(SRC)/dvo_register.cpp
 
 $(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_graph_device.h $(SRC)/dvo_graph_host.h \
         include/dvo_amd.h include/dvo_amd_debug.h
@@ -26,6 +26,8 @@ examples: $(LIB)
 	$(CC) -std=c99 -Wall -Iinclude examples/constraint_search_example.c -o examples/_build/constraint_search_example \
 	    -Ldvo_slam_amd -ldvo_amd -lm -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 	$(CC) -std=c99 -Wall -Iinclude examples/rectified_ingest_example.c -o examples/_build/rectified_ingest_example \
+	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CC) -std=c99 -Wall -Iinclude examples/registered_ingest_example.c -o examples/_build/registered_ingest_example \
 	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 
 clean:

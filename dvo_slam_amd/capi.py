@@ -9,6 +9,7 @@ no CPU path here, and loading fails loudly if the library is missing.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 import os
 
 import numpy as np
@@ -47,6 +48,7 @@ EXPORTS = [
     "dvo_amd_debug_covisibility_ms",
     "dvo_amd_remap_create", "dvo_amd_remap_create_undistort", "dvo_amd_remap_retain", "dvo_amd_remap_release", "dvo_amd_remap_info",
     "dvo_amd_remap_download", "dvo_amd_pyramid_create_raw_remapped", "dvo_amd_debug_ingest_timing",
+    "dvo_amd_default_registration", "dvo_amd_pyramid_create_raw_registered",
 ]
 
 
@@ -111,6 +113,15 @@ class CView(C.Structure):
 
 class CRenderStats(C.Structure):
     _fields_ = [(n, C.c_longlong) for n in ("voxels", "behind_near", "outside", "drawn", "covered_pixels")]
+
+
+class CRegistration(C.Structure):
+    _fields_ = [("depth_width", C.c_int), ("depth_height", C.c_int), ("k_depth", C.c_float * 4), ("T", C.c_double * 16),
+                ("min_z", C.c_float), ("fill", C.c_int)]
+
+
+class CRegistrationStats(C.Structure):
+    _fields_ = [(n, C.c_longlong) for n in ("measurements", "behind", "outside", "drawn", "covered_pixels")]
 
 
 class CKeyframe(C.Structure):
@@ -284,6 +295,12 @@ def lib():
                                                       C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_double,
                                                       C.POINTER(vp)]
     L.dvo_amd_debug_ingest_timing.argtypes = [C.c_int, C.c_int, dp]
+    L.dvo_amd_default_registration.argtypes = [C.POINTER(CRegistration)]
+    L.dvo_amd_default_registration.restype = None
+    L.dvo_amd_pyramid_create_raw_registered.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp, C.c_int, C.c_float, C.c_int,
+                                                        C.POINTER(CRegistration), vp, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                        C.c_float, C.c_float, C.c_int, C.c_double, C.POINTER(vp),
+                                                        C.POINTER(CRegistrationStats)]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -434,6 +451,33 @@ class Remap:
         return mx, my
 
 
+@dataclasses.dataclass
+class Registration:
+    """A dvo_amd_registration: how `RgbdImagePyramid.from_raw(..., registration=)` takes raw depth of the depth camera into the
+    colour camera (what depth_image_proc/register does on the CPU in front of the reference; the rule is pinned in
+    include/dvo_amd.h).  depth_size = (width, height) of the raw depth frame (None: the shape of the depth array given to
+    from_raw), K_depth = (fx, fy, ox, oy) of the depth camera, T = 4x4 depth camera -> colour camera, min_z >= 0: a measurement is
+    kept only if its colour-frame z > min_z, fill: False one pixel per measurement, True the measurement's footprint."""
+    depth_size: "tuple | None" = None
+    K_depth: tuple = (0.0, 0.0, 0.0, 0.0)
+    T: "np.ndarray | None" = None
+    min_z: float = 0.0
+    fill: bool = False
+
+    def _c(self, depth_size=None) -> CRegistration:
+        c = CRegistration()
+        lib().dvo_amd_default_registration(C.byref(c))
+        size = depth_size if depth_size is not None else self.depth_size
+        if size is None:
+            raise ValueError("the registration has no depth_size")
+        c.depth_width, c.depth_height = int(size[0]), int(size[1])
+        c.k_depth[:] = [float(k) for k in self.K_depth]
+        if self.T is not None:
+            c.T[:] = [float(v) for v in _pose_cm(self.T).ravel()]
+        c.min_z, c.fill = float(self.min_z), int(self.fill)
+        return c
+
+
 def ingest_timing(enable: bool = True, device: int = 0) -> float:
     """(instrumentation) switches the event bracket around every pyramid build of `device` on or off and returns the device time
     of the most recent bracketed build in ms (dvo_amd_debug_ingest_timing)"""
@@ -472,36 +516,60 @@ class RgbdImagePyramid:
 
     @classmethod
     def from_raw(cls, image, depth, K, levels: int, depth_scale: float = 1.0 / 5000.0, device: int = 0,
-                 timestamp: float = 0.0, remap: "Remap | None" = None):
+                 timestamp: float = 0.0, remap: "Remap | None" = None, registration: "Registration | None" = None):
         """Frame ingest on the device: uint8 image (HxW gray or HxWx3 BGR) + uint16 depth (0 = invalid), as a camera or a
         TUM PNG pair delivers them (benchmark_slam.cpp:46-93).  Gray conversion and depth scaling run on the GPU.
         With `remap` the frame has the remap's source size and is resampled through it (dvo_amd_pyramid_create_raw_remapped):
-        the pyramid has the remap's output size and K is the rectified camera's."""
+        the pyramid has the remap's output size and K is the rectified camera's.
+        With `registration` the depth array is the depth camera's own frame, of any size, and is registered into the colour camera
+        K (dvo_amd_pyramid_create_raw_registered): only the image goes through `remap`, and the pyramid carries
+        `registration_stats`."""
         image = np.ascontiguousarray(image, dtype=np.uint8)
         depth = np.ascontiguousarray(depth, dtype=np.uint16)
-        if image.shape[:2] != depth.shape or depth.ndim != 2 or image.ndim not in (2, 3):
+        if depth.ndim != 2 or image.ndim not in (2, 3) or (registration is None and image.shape[:2] != depth.shape):
             raise ValueError("image must be HxW or HxWx3 uint8 and depth HxW uint16 of the same size")
         channels = 1 if image.ndim == 2 else image.shape[2]
-        h, w = depth.shape
-        return cls._raw(image.ctypes.data, channels, w * channels, depth.ctypes.data, w, depth_scale, 0, w, h, K, levels,
-                        device, timestamp, remap)
+        h, w = image.shape[:2]
+        dh, dw = depth.shape
+        return cls._raw(image.ctypes.data, channels, w * channels, depth.ctypes.data, dw, depth_scale, 0, w, h, K, levels,
+                        device, timestamp, remap, registration, (dw, dh) if registration is not None else None)
 
     @classmethod
     def from_raw_device(cls, d_image: int, channels: int, d_depth: int, width: int, height: int, K, levels: int,
                         depth_scale: float = 1.0 / 5000.0, device: int = 0, timestamp: float = 0.0,
                         image_stride_bytes: int | None = None, depth_stride: int | None = None,
-                        remap: "Remap | None" = None):
+                        remap: "Remap | None" = None, registration: "Registration | None" = None, depth_size=None):
         """As from_raw, for raw frames already resident in HBM (device pointers).  With `remap`, width and height are the raw
-        frame's (the remap's source size)."""
-        return cls._raw(d_image, channels, image_stride_bytes or width * channels, d_depth, depth_stride or width,
-                        depth_scale, 1, width, height, K, levels, device, timestamp, remap)
+        frame's (the remap's source size).  With `registration`, width and height are the image's and depth_size = (width,
+        height) of the depth frame (None: the registration's own depth_size)."""
+        if registration is not None and depth_size is None:
+            depth_size = registration.depth_size
+        depth_width = depth_size[0] if registration is not None and depth_size is not None else width
+        return cls._raw(d_image, channels, image_stride_bytes or width * channels, d_depth, depth_stride or depth_width,
+                        depth_scale, 1, width, height, K, levels, device, timestamp, remap, registration, depth_size)
 
     @classmethod
     def _raw(cls, image_ptr, channels, image_stride, depth_ptr, depth_stride, depth_scale, on_device, w, h, K, levels,
-             device, timestamp, remap=None):
+             device, timestamp, remap=None, registration=None, depth_size=None):
         self = cls.__new__(cls)
         fx, fy, ox, oy = [float(k) for k in K]
         self._h = C.c_void_p()
+        self.registration_stats = None
+        if registration is not None:
+            if remap is not None:
+                i = remap.info()
+                if (w, h) != (i["src_width"], i["src_height"]):
+                    raise ValueError(f"the raw image is {w}x{h} but the remap's source is {i['src_width']}x{i['src_height']}")
+                w, h = i["width"], i["height"]
+            reg, st = registration._c(depth_size), CRegistrationStats()
+            _check(lib().dvo_amd_pyramid_create_raw_registered(device, C.c_void_p(image_ptr), channels, image_stride,
+                                                               C.c_void_p(depth_ptr), depth_stride, depth_scale, on_device,
+                                                               C.byref(reg), None if remap is None else remap._h, w, h, fx, fy,
+                                                               ox, oy, levels, timestamp, C.byref(self._h), C.byref(st)),
+                   "dvo_amd_pyramid_create_raw_registered")
+            self.registration_stats = {n: getattr(st, n) for n, _ in CRegistrationStats._fields_}
+            self.device = device
+            return self
         if remap is not None:
             i = remap.info()
             if (w, h) != (i["src_width"], i["src_height"]):

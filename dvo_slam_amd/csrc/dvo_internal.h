@@ -8,6 +8,7 @@
 //   dvo_graph.cpp     the pose-graph optimizer: edge linearisation, dense fp64 Cholesky, Levenberg-Marquardt and dogleg
 //   dvo_graph_batch.cpp  many small pose graphs in one launch: one workgroup per graph, the whole optimization on the device
 //   dvo_rectify.cpp   remap tables (lens undistortion, arbitrary maps) and the frame ingest that resamples through one
+//   dvo_register.cpp  depth-to-colour registration at ingest: raw depth of another camera splatted into level 0's depth plane
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -127,6 +128,17 @@ struct RawFrame {
   int depth_stride;             // in elements
   float depth_scale;
   const dvo_amd_remap *remap;   // null: the frame has the pyramid's size; else it has the remap's source size and is resampled
+  const struct Registration *reg;  // null: the depth frame is the image's; else it is another camera's and is registered
+};
+
+// a depth-to-colour registration as the kernels take it (dvo_register.cpp; the rule is pinned in include/dvo_amd.h)
+struct Registration {
+  int dw, dh;                 // the raw depth frame
+  float fxd, fyd, oxd, oyd;   // the depth camera
+  float T[12];                // rows 0..2 of depth camera -> colour camera, row-major, cast from double
+  float min_z, mx, my;        // mx = fx / fxd, my = fy / fyd
+  int fill;
+  unsigned long long *counts; // host, 4 words: behind, outside, drawn, covered (written before pyramid_build returns)
 };
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -384,6 +396,19 @@ int ingest_timing(int device, int enable, double *last_ms);  // dvo_amd_debug_in
 
 // ---- dvo_rectify.cpp
 int rectify_level0(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st);
+int rectify_level0_locked(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st);
+// the per-device staging area of host raw frames, BGR sources and the registration's counters: grown to the largest seen and
+// kept; used with the device's mutex held
+struct Staging {
+  void *img = nullptr, *z = nullptr, *grey = nullptr, *reg = nullptr;
+  size_t img_bytes = 0, z_bytes = 0, grey_bytes = 0, reg_bytes = 0;
+};
+Staging &staging(int device);
+int staging_grow(void **p, size_t *have, size_t bytes);
+
+// ---- dvo_register.cpp
+int register_level0(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, int width, int height,
+                    float fx, float fy, float ox, float oy, unsigned long long *ctrl, hipStream_t st);
 
 // ---- dvo_tracker.cpp
 dvo_amd_iteration_stats *stats_push(Job &j);

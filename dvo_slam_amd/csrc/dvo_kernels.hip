@@ -2280,6 +2280,8 @@ hipError_t launch_copy_strided(const float *src, int stride, float *dst, int w, 
 //   gray : (B*1868 + G*9617 + R*4899 + 2^13) >> 14      (cv::cvtColor(CV_BGR2GRAY) 8-bit rule + convertTo(CV_32F),
 //          or the byte itself for 1-channel input        benchmark_slam.cpp:60-68, camera_dense_tracking.cpp:219-229)
 // One thread converts 4 consecutive pixels of a row (level widths are multiples of 4): 12 + 8 bytes in, 2 x 16 bytes out.
+// kDepth = false writes the intensity plane alone (the registered ingest fills the depth plane by its own rule, dvo_register.cpp).
+template <bool kDepth>
 __global__ void k_ingest(const unsigned char *__restrict__ img, int channels, int img_stride_bytes,
                          const unsigned short *__restrict__ raw_z, int z_stride, float z_scale, float *__restrict__ i_plane,
                          float *__restrict__ z_plane, int w, int h) {
@@ -2312,6 +2314,11 @@ __global__ void k_ingest(const unsigned char *__restrict__ img, int channels, in
       g[k] = (float)px[k];
     }
   }
+  const size_t o = (size_t)y * w + (size_t)x4 * 4;
+  if (!kDepth) {
+    *(float4 *)(i_plane + o) = make_float4(g[0], g[1], g[2], g[3]);
+    return;
+  }
   const unsigned short *zp = raw_z + (size_t)y * z_stride + (size_t)x4 * 4;
   unsigned short zr[4];
   if ((((size_t)zp) & 7) == 0) {
@@ -2325,7 +2332,6 @@ __global__ void k_ingest(const unsigned char *__restrict__ img, int channels, in
   float z[4];
 #pragma unroll
   for (int k = 0; k < 4; ++k) z[k] = zr[k] == 0 ? __builtin_nanf("") : (float)zr[k] * z_scale;
-  const size_t o = (size_t)y * w + (size_t)x4 * 4;
   *(float4 *)(i_plane + o) = make_float4(g[0], g[1], g[2], g[3]);
   *(float4 *)(z_plane + o) = make_float4(z[0], z[1], z[2], z[3]);
 }
@@ -2334,8 +2340,17 @@ hipError_t launch_ingest(const unsigned char *img, int channels, int img_stride_
                          int z_stride, float z_scale, float *i_plane, float *z_plane, int w, int h, hipStream_t stream) {
   LaunchGuard guard;
   const int wq = w / 4;
-  hipLaunchKernelGGL(k_ingest, dim3((unsigned)((wq + 63) / 64), (unsigned)h), dim3(64), 0, stream, img, channels,
+  hipLaunchKernelGGL(k_ingest<true>, dim3((unsigned)((wq + 63) / 64), (unsigned)h), dim3(64), 0, stream, img, channels,
                      img_stride_bytes, raw_z, z_stride, z_scale, i_plane, z_plane, w, h);
+  return hipGetLastError();
+}
+
+hipError_t launch_ingest_intensity(const unsigned char *img, int channels, int img_stride_bytes, float *i_plane, int w, int h,
+                                   hipStream_t stream) {
+  LaunchGuard guard;
+  const int wq = w / 4;
+  hipLaunchKernelGGL(k_ingest<false>, dim3((unsigned)((wq + 63) / 64), (unsigned)h), dim3(64), 0, stream, img, channels,
+                     img_stride_bytes, (const unsigned short *)nullptr, 0, 0.0f, i_plane, (float *)nullptr, w, h);
   return hipGetLastError();
 }
 

@@ -140,9 +140,9 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   *out = nullptr;
   if (width < 4 || height < 2 || levels < 1 || levels > DVO_AMD_MAX_LEVELS) return DVO_AMD_ERR_INVALID_ARGUMENT;
   if (raw) {
-    const int raw_width = raw->remap ? raw->remap->sw : width;
+    const int raw_width = raw->remap ? raw->remap->sw : width, z_width = raw->reg ? raw->reg->dw : raw_width;
     if (!raw->image || !raw->depth || (raw->channels != 1 && raw->channels != 3) ||
-        raw->image_stride_bytes < raw_width * raw->channels || raw->depth_stride < raw_width || !(raw->depth_scale > 0.0f))
+        raw->image_stride_bytes < raw_width * raw->channels || raw->depth_stride < z_width || !(raw->depth_scale > 0.0f))
       return DVO_AMD_ERR_INVALID_ARGUMENT;
   } else if (!src_i || !src_z || stride < width) {
     return DVO_AMD_ERR_INVALID_ARGUMENT;
@@ -205,7 +205,16 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   DeviceState &dev = g_dev[device];
   const bool timed = dev.timing.load();
   if (timed && (e = hipEventRecord(dev.ev[0], st)) != hipSuccess) return bail(fail_hip("ingest timing", e));
-  if (raw && raw->remap) {
+  if (raw && raw->reg) {
+    // the four counters live in the room of the first selection's descriptors, which nothing writes before this build returns
+    rc = register_level0(device, *raw, src_on_device, L0.i_plane, L0.z_plane, width, height, fx, fy, ox, oy,
+                         (unsigned long long *)p->ref_desc0, st);
+    if (rc) {
+      (void)hipStreamSynchronize(st);
+      return bail(rc);
+    }
+    e = hipSuccess;
+  } else if (raw && raw->remap) {
     rc = rectify_level0(device, *raw, src_on_device, L0.i_plane, L0.z_plane, st);
     if (rc) {
       (void)hipStreamSynchronize(st);
@@ -276,6 +285,10 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   }
   e = hipMemcpyAsync(p->cur_desc, cur_host, sizeof(CurLevelDesc) * levels, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return bail(fail_hip("pyramid descriptors", e));
+  if (raw && raw->reg) {
+    e = hipMemcpyAsync(raw->reg->counts, p->ref_desc0, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+    if (e != hipSuccess) return bail(fail_hip("registration counters", e));
+  }
   if (timed && (e = hipEventRecord(dev.ev[1], st)) != hipSuccess) return bail(fail_hip("ingest timing", e));
   e = hipStreamSynchronize(st);
   if (e != hipSuccess) return bail(fail_hip("pyramid build", e));
@@ -393,7 +406,7 @@ int dvo_amd_pyramid_create_raw(int device, const unsigned char *image, int chann
                                const unsigned short *depth, int depth_stride, float depth_scale, int on_device, int width,
                                int height, float fx, float fy, float ox, float oy, int levels, double timestamp,
                                dvo_amd_pyramid **out) {
-  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale, nullptr};
+  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale, nullptr, nullptr};
   return pyramid_build(device, nullptr, nullptr, &raw, on_device != 0, width, height, width, fx, fy, ox, oy, levels,
                        timestamp, out);
 }

@@ -108,7 +108,9 @@ __global__ void __launch_bounds__(64) k_grey_plane(const unsigned char *__restri
   *(unsigned *)(grey + (size_t)y * grey_stride + x) = out;
 }
 
-// `grey` is a 1 B/px plane: the caller's own image for a 1-channel source, k_grey_plane's output for a BGR one
+// `grey` is a 1 B/px plane: the caller's own image for a 1-channel source, k_grey_plane's output for a BGR one.
+// kDepth = false writes the intensity plane alone (the registered ingest, dvo_register.cpp: its depth does not go through the map).
+template <bool kDepth>
 __global__ void __launch_bounds__(64) k_ingest_remap(const float *__restrict__ map_x, const float *__restrict__ map_y,
                                                      const unsigned char *__restrict__ grey, int grey_stride,
                                                      const unsigned short *__restrict__ raw_z, int z_stride, float z_scale,
@@ -133,13 +135,15 @@ __global__ void __launch_bounds__(64) k_ingest_remap(const float *__restrict__ m
       const float g00 = (float)t[0], g01 = (float)t[1], g10 = (float)t[grey_stride], g11 = (float)t[grey_stride + 1];
       const float top = g00 + ax * (g01 - g00), bot = g10 + ax * (g11 - g10);
       I[k] = top + ay * (bot - top);
-      const float px = floorf(sx + 0.5f), py = floorf(sy + 0.5f);
-      const unsigned short zr = raw_z[(size_t)(int)py * z_stride + (int)px];
-      if (zr != 0) Z[k] = (float)zr * z_scale;
+      if (kDepth) {
+        const float px = floorf(sx + 0.5f), py = floorf(sy + 0.5f);
+        const unsigned short zr = raw_z[(size_t)(int)py * z_stride + (int)px];
+        if (zr != 0) Z[k] = (float)zr * z_scale;
+      }
     }
   }
   *(float4 *)(i_plane + o) = make_float4(I[0], I[1], I[2], I[3]);
-  *(float4 *)(z_plane + o) = make_float4(Z[0], Z[1], Z[2], Z[3]);
+  if (kDepth) *(float4 *)(z_plane + o) = make_float4(Z[0], Z[1], Z[2], Z[3]);
 }
 
 }  // namespace rectify
@@ -155,14 +159,13 @@ int invalid(const char *entry, const std::string &why) {
   return DVO_AMD_ERR_INVALID_ARGUMENT;
 }
 
-// the per-device staging area of host raw frames and BGR sources: grown to the largest source and kept
-struct Staging {
-  void *img = nullptr, *z = nullptr, *grey = nullptr;
-  size_t img_bytes = 0, z_bytes = 0, grey_bytes = 0;
-};
 Staging g_stage[kMaxDevices];
 
-int grow(void **p, size_t *have, size_t bytes) {
+}  // namespace
+
+Staging &staging(int device) { return g_stage[device]; }
+
+int staging_grow(void **p, size_t *have, size_t bytes) {
   if (bytes <= *have) return DVO_AMD_OK;
   if (*p) (void)hipFree(*p), *p = nullptr, *have = 0;  // (hipFree waits for whatever still reads the old area)
   bytes = align_up(bytes, 1 << 16);
@@ -172,6 +175,10 @@ int grow(void **p, size_t *have, size_t bytes) {
   *have = bytes;
   return DVO_AMD_OK;
 }
+
+namespace {
+
+int grow(void **p, size_t *have, size_t bytes) { return staging_grow(p, have, bytes); }
 
 int check_output_size(const char *entry, int width, int height) {
   if (width < 4 || height < 2 || (width % 4) != 0) return invalid(entry, "the output must be at least 4x2 with a width that is a multiple of 4");
@@ -238,8 +245,13 @@ int remap_finish(dvo_amd_remap *r, hipError_t e, hipStream_t st, dvo_amd_remap *
 // is enqueued on `st`, the device's prep stream; the device's mutex is held from the first upload to the last launch, so two
 // threads' uses of the staging area reach the stream one after the other and the stream's order does the rest.
 int rectify_level0(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st) {
-  const dvo_amd_remap *r = raw.remap;
   std::lock_guard<std::mutex> lk(device_mutex(device));
+  return rectify_level0_locked(device, raw, on_device, i_plane, z_plane, st);
+}
+
+// the same with the device's mutex held by the caller; z_plane == nullptr: the intensity plane alone, raw.depth is not read
+int rectify_level0_locked(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st) {
+  const dvo_amd_remap *r = raw.remap;
   Staging &S = g_stage[device];
   const unsigned char *d_img = raw.image;
   const unsigned short *d_z = raw.depth;
@@ -248,10 +260,10 @@ int rectify_level0(int device, const RawFrame &raw, bool on_device, float *i_pla
   if (!on_device) {
     const size_t row_img = (size_t)r->sw * raw.channels, row_z = sizeof(unsigned short) * (size_t)r->sw;
     int rc = grow(&S.img, &S.img_bytes, row_img * r->sh);
-    if (!rc) rc = grow(&S.z, &S.z_bytes, row_z * r->sh);
+    if (!rc && z_plane) rc = grow(&S.z, &S.z_bytes, row_z * r->sh);
     if (rc) return rc;
     e = hipMemcpy2DAsync(S.img, row_img, raw.image, (size_t)raw.image_stride_bytes, row_img, r->sh, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
+    if (e == hipSuccess && z_plane)
       e = hipMemcpy2DAsync(S.z, row_z, raw.depth, sizeof(unsigned short) * (size_t)raw.depth_stride, row_z, r->sh,
                            hipMemcpyHostToDevice, st);
     if (e != hipSuccess) return fail_hip("raw frame upload", e);
@@ -267,9 +279,14 @@ int rectify_level0(int device, const RawFrame &raw, bool on_device, float *i_pla
     if (e != hipSuccess) return fail_hip("k_grey_plane", e);
     d_img = (const unsigned char *)S.grey, img_stride = grey_stride;
   }
-  hipLaunchKernelGGL(rectify::k_ingest_remap, dim3((unsigned)((r->w / 4 + 63) / 64), (unsigned)r->h), dim3(64), 0, st, r->map_x,
-                     r->map_y, d_img, img_stride, d_z, z_stride, raw.depth_scale, (float)(r->sw - 1), (float)(r->sh - 1), i_plane,
-                     z_plane, r->w, r->h);
+  const dim3 grid((unsigned)((r->w / 4 + 63) / 64), (unsigned)r->h);
+  if (z_plane)
+    hipLaunchKernelGGL(rectify::k_ingest_remap<true>, grid, dim3(64), 0, st, r->map_x, r->map_y, d_img, img_stride, d_z, z_stride,
+                       raw.depth_scale, (float)(r->sw - 1), (float)(r->sh - 1), i_plane, z_plane, r->w, r->h);
+  else
+    hipLaunchKernelGGL(rectify::k_ingest_remap<false>, grid, dim3(64), 0, st, r->map_x, r->map_y, d_img, img_stride,
+                       (const unsigned short *)nullptr, 0, 0.0f, (float)(r->sw - 1), (float)(r->sh - 1), i_plane, (float *)nullptr,
+                       r->w, r->h);
   e = hipGetLastError();
   if (e != hipSuccess) return fail_hip("k_ingest_remap", e);
   return DVO_AMD_OK;
@@ -386,7 +403,7 @@ int dvo_amd_pyramid_create_raw_remapped(int device, const unsigned char *image, 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
   if (remap->device != device) return DVO_AMD_ERR_DEVICE_MISMATCH;
-  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale, remap};
+  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale, remap, nullptr};
   return pyramid_build(device, nullptr, nullptr, &raw, on_device != 0, remap->w, remap->h, remap->w, fx, fy, ox, oy, levels,
                        timestamp, out);
 }

@@ -408,6 +408,8 @@ hipError_t launch_select(const float *z_plane, const float4 *c_a, const float2 *
 // raw frame -> float base planes of level 0 (uint8 gray or BGR, uint16 depth with 0 = invalid)
 hipError_t launch_ingest(const unsigned char *img, int channels, int img_stride_bytes, const unsigned short *raw_z,
                          int z_stride, float z_scale, float *i_plane, float *z_plane, int w, int h, hipStream_t stream);
+hipError_t launch_ingest_intensity(const unsigned char *img, int channels, int img_stride_bytes, float *i_plane, int w, int h,
+                                   hipStream_t stream);
 hipError_t launch_copy_strided(const float *src, int stride, float *dst, int w, int h, hipStream_t stream);
 hipError_t launch_compact(const float *zsel, const float *r_i, const float *r_ix, const float *r_iy, const float *tx, const float *ty, int w,
                           int n, int n_pad, const int2 *block_partials, int *prefix, const int *counters, float *cz, float *ci, float *cix,

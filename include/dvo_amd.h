@@ -269,8 +269,8 @@ int dvo_amd_pyramid_create_raw(int device, const unsigned char *image, int chann
  * other than 1 or 3; levels outside 1..DVO_AMD_MAX_LEVELS.  Then DVO_AMD_ERR_NO_DEVICE without a GPU, and
  * DVO_AMD_ERR_DEVICE_MISMATCH for a remap that lives on another device than `device`.
  *
- * Not covered: depth-to-colour registration; lens models other than the five-coefficient one (they come in as tables through
- * dvo_amd_remap_create); remapping float planes.
+ * Not covered: lens models other than the five-coefficient one (they come in as tables through dvo_amd_remap_create);
+ * remapping float planes.  Depth-to-colour registration is dvo_amd_pyramid_create_raw_registered below.
  */
 typedef struct dvo_amd_remap dvo_amd_remap;
 int dvo_amd_remap_create(int device, int width, int height, const float *map_x, const float *map_y, int stride, int src_width,
@@ -285,6 +285,74 @@ int dvo_amd_pyramid_create_raw_remapped(int device, const unsigned char *image, 
                                         const unsigned short *depth, int depth_stride, float depth_scale, int on_device,
                                         const dvo_amd_remap *remap, float fx, float fy, float ox, float oy, int levels,
                                         double timestamp, dvo_amd_pyramid **out);
+
+/*
+ * Depth-to-colour registration at ingest: raw depth in the DEPTH camera's frame and a raw colour image, straight into a pyramid.
+ *
+ * The reference never sees an unregistered frame: dvo_ros/src/camera_base.cpp:31-33 subscribes to
+ * camera/depth_registered/image_rect_raw, the output of depth_image_proc/register on the CPU upstream, and TUM's PNGs were
+ * registered by the driver.  A caller that holds the sensor's own two streams has depth in the IR camera's frame: a few
+ * centimetres beside the colour camera, with other intrinsics and often another resolution.  This entry is that step on the
+ * device: every depth measurement is back-projected, moved into the colour camera and splatted into level 0's depth plane with a
+ * nearest-depth test.
+ *
+ * width, height and fx..oy describe the pyramid's level 0, the colour camera the tracker sees; the size rules are
+ * dvo_amd_pyramid_create_raw's.  With remap == NULL the image is width x height and the intensity plane is exactly what
+ * dvo_amd_pyramid_create_raw writes.  With a remap the image has the remap's source size, width x height must equal the remap's
+ * output size, and the intensity plane is exactly what dvo_amd_pyramid_create_raw_remapped writes.  In both cases the raw depth
+ * has reg->depth_width x reg->depth_height elements with depth_stride >= depth_width; it does NOT go through the remap (k_depth
+ * is a rectified pinhole camera) but through the rule below.  A raw frame from the host is uploaded into the per-device staging
+ * area of the remapped ingest; the depth frame takes its own size there.
+ *
+ * The registration rule.  Every operation is fp32 and rounds once (-ffp-contract=off); the divisions are correctly rounded.  The
+ * host casts rows 0..2 of T to float -- it takes the transform as rigid and checks only that the entries are finite -- and
+ * computes mx = fx / fx_d, my = fy / fy_d in float.  For depth pixel (u, v) with raw value d:
+ *  1. d == 0: no measurement.  Else z = (float)d * depth_scale, counted in `measurements`.
+ *  2. Back-project: rx = ((float)u - ox_d) / fx_d, ry = ((float)v - oy_d) / fy_d, X = rx*z, Y = ry*z.
+ *  3. Transform: c = ((T0*X + T1*Y) + T2*z) + T3 per row (cx, cy, cz), the order of the point cloud and of the render.
+ *  4. Cull: the measurement is dropped and counted in `behind` unless cz > min_z (false for NaN).  min_z >= 0, so every kept
+ *     cz is > 0 and its bit pattern, read as an unsigned word, orders like its value.
+ *  5. Project and footprint: uc = (cx*fx)/cz + ox, vc = (cy*fy)/cz + oy.
+ *       fill == 0: the footprint is the single pixel floorf(uc + 0.5f), floorf(vc + 0.5f).
+ *       fill == 1: hx = fminf(0.5f*(mx*(z/cz)), 4.0f), hy = fminf(0.5f*(my*(z/cz)), 4.0f) (fminf returns the other operand for a
+ *         NaN: 4.0f); columns and rows then follow rule 5 of dvo_amd_map_render word for word: ceilf(uc - hx) .. floorf(uc + hx),
+ *         and floorf(uc + 0.5f) alone when that range is empty (a footprint narrower than a pixel that holds no centre).
+ *     The visibility test is made in float before any conversion to int -- the footprint is visible on an axis iff
+ *     last >= 0 && first <= (float)(size - 1); NaN and +-inf are outside -- and the footprint is then clamped to the image.  The
+ *     4.0 cap bounds a side at 9 pixel centres.  A measurement is counted in `outside` or in `drawn`.
+ *  6. Depth test: every covered pixel of level 0's depth plane keeps the minimum of bits(cz) as an unsigned 32-bit word.  The
+ *     plane is first cleared to NaN 0x7FC00000, which lies above every finite pattern: a pixel nothing covers stays NaN and no
+ *     resolve pass is needed.  The written depth is cz, metres in the colour camera's frame.  `covered_pixels` counts the non-NaN
+ *     pixels afterwards.
+ * No value depends on the launch geometry or on the order the atomics land in.  measurements == behind + outside + drawn.
+ * Consequence: with T = I, equal sizes and equal intrinsics a measurement lands on its own pixel with cz = z, and the plane is
+ * dvo_amd_pyramid_create_raw's (tested for power-of-two and for the synthetic camera's intrinsics; not a theorem for every K).
+ * Stated deviations from depth_image_proc/register: it works in double and re-quantises to uint16, and in fill mode it averages
+ * the two corner depths and projects the two corners; this rule keeps fp32, the centre's cz and a centred footprint.
+ *
+ * Errors.  DVO_AMD_ERR_INVALID_ARGUMENT, with a reason in dvo_amd_last_error(), before a device is looked for: a NULL reg, image,
+ * depth or out; a depth side outside 1..2^20; depth_stride < depth_width; a non-finite entry of k_depth, of the first three rows
+ * of T or of fx..oy; fx_d, fy_d, fx or fy <= 0; min_z negative or not finite; fill other than 0 or 1; a remap whose output size
+ * differs from width x height; an image stride smaller than the row it must hold; everything dvo_amd_pyramid_create_raw rejects.
+ * Then DVO_AMD_ERR_NO_DEVICE without a GPU, and DVO_AMD_ERR_DEVICE_MISMATCH for a remap on another device.
+ *
+ * Not covered: a distortion model for the depth camera; hole filling beyond the footprint; smoothing; float depth planes.
+ */
+typedef struct {
+  int   depth_width, depth_height;  /* size of the raw depth frame: 1..2^20 a side */
+  float k_depth[4];                 /* fx, fy, ox, oy of the depth camera */
+  double T[16];                     /* depth camera -> colour camera, column-major 4x4 like every pose here */
+  float min_z;                      /* >= 0; a measurement is kept only if its colour-frame z > min_z */
+  int   fill;                       /* 0: one pixel per measurement; 1: the measurement's footprint (rule 5) */
+} dvo_amd_registration;
+typedef struct { long long measurements, behind, outside, drawn, covered_pixels; } dvo_amd_registration_stats;
+
+void dvo_amd_default_registration(dvo_amd_registration *reg);   /* identity T, min_z 0, fill 0, sizes and k_depth zero */
+int dvo_amd_pyramid_create_raw_registered(int device, const unsigned char *image, int channels, int image_stride_bytes,
+        const unsigned short *depth, int depth_stride, float depth_scale, int on_device,
+        const dvo_amd_registration *reg, const dvo_amd_remap *remap /* may be NULL */,
+        int width, int height, float fx, float fy, float ox, float oy, int levels, double timestamp,
+        dvo_amd_pyramid **out, dvo_amd_registration_stats *stats /* may be NULL */);
 
 void dvo_amd_pyramid_retain(dvo_amd_pyramid *p);
 void dvo_amd_pyramid_release(dvo_amd_pyramid *p);
