@@ -119,17 +119,6 @@ int grow_covis(void **p, size_t *have, size_t bytes) {
   return DVO_AMD_OK;
 }
 
-int invalid(const char *entry, const std::string &why) {
-  g_last_error = std::string(entry) + ": " + why;
-  return DVO_AMD_ERR_INVALID_ARGUMENT;
-}
-
-bool finite16(const double *pose) {
-  for (int e = 0; e < 16; ++e)
-    if (!std::isfinite(pose[e])) return false;
-  return true;
-}
-
 int check_options(const char *entry, const dvo_amd_covisibility_options *opt) {
   if (!opt) return invalid(entry, "the options are NULL");
   if (opt->level < 0) return invalid(entry, "level must be >= 0");
@@ -147,7 +136,7 @@ int check_pairs(const char *entry, int n_keyframes, const dvo_amd_keyframe *keyf
     for (const int k : {pair_a[i], pair_b[i]}) {
       if (k < 0 || k >= n_keyframes) return invalid(entry, "pair " + std::to_string(i) + " names keyframe " + std::to_string(k) + " out of range");
       if (!keyframes[k].image) return invalid(entry, "keyframe " + std::to_string(k) + " has no image");
-      if (!finite16(keyframes[k].pose)) return invalid(entry, "keyframe " + std::to_string(k) + " has a non-finite pose entry");
+      if (!finite_all(keyframes[k].pose, 16)) return invalid(entry, "keyframe " + std::to_string(k) + " has a non-finite pose entry");
     }
   }
   return n_pairs > 0 || opt ? check_options(entry, opt) : DVO_AMD_OK;
@@ -168,8 +157,8 @@ int covisibility(dvo_amd_context *ctx, int n_keyframes, const dvo_amd_keyframe *
                  int n_pairs, const int *pair_a, const int *pair_b, dvo_amd_covisibility_counts *out, const char *entry) {
   int rc = check_pairs(entry, n_keyframes, keyframes, opt, n_pairs, pair_a, pair_b, out);
   if (rc) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
+  rc = have_device();
+  if (rc) return rc;
   if (!ctx) return invalid(entry, "the context is NULL");
   for (int i = 0; i < n_pairs; ++i)
     if (keyframes[pair_a[i]].image->device != ctx->device || keyframes[pair_b[i]].image->device != ctx->device)
@@ -270,7 +259,7 @@ int dvo_amd_find_constraint_candidates(dvo_amd_context *ctx, int n_keyframes, co
   if (!std::isfinite(max_distance) || max_distance < 0.0f) return host::invalid(entry, "max_distance must be finite and >= 0");
   if (std::isnan(min_overlap)) return host::invalid(entry, "min_overlap is NaN");
   for (int k = 0; k < n_keyframes; ++k)
-    if (!host::finite16(keyframes[k].pose)) return host::invalid(entry, "keyframe " + std::to_string(k) + " has a non-finite pose entry");
+    if (!host::finite_all(keyframes[k].pose, 16)) return host::invalid(entry, "keyframe " + std::to_string(k) + " has a non-finite pose entry");
   const bool prune = min_overlap > 0.0;
   if (prune) {
     const int rc = host::check_options(entry, opt);

@@ -845,12 +845,6 @@ int workspace(dvo_amd_context *ctx, GraphWorkspace **out) {
   return DVO_AMD_OK;
 }
 
-bool finite_all(const double *p, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(p[i])) return false;
-  return true;
-}
-
 }  // namespace
 
 int graph_check_arguments(const char *entry, int n_vertices, const double *poses, int n_edges, const dvo_amd_graph_edge *edges,

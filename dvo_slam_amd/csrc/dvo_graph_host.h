@@ -14,12 +14,6 @@ namespace host {
     if (rc_) return rc_;      \
   } while (0)
 
-inline int have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
-  return DVO_AMD_OK;
-}
-
 // a device buffer of a graph workspace: grown to the largest call (in 4 KiB steps), never shrunk; `what` names the workspace
 // in dvo_amd_last_error().  (The map workspace keeps its own: it grows in 64 KiB steps.)
 struct DeviceBuf {

@@ -1,5 +1,7 @@
 // Internal declarations shared by the host-side translation units of libdvo_amd.so (NOT part of any interface):
-//   dvo_pyramid.cpp   device pools, pyramid construction, point selection, the dvo_amd_pyramid_* entries
+//   dvo_pyramid.cpp   device pools, pyramid construction, point selection, the dvo_amd_pyramid_* entries that read a pyramid
+//   dvo_ingest.cpp    where level 0 comes from: the five dvo_amd_pyramid_create* entries and their argument checks, the staging
+//                     area of host raw frames, the driver that fills level 0's two base planes from any source
 //   dvo_tracker.cpp   contexts, the Gauss-Newton driver (ticks), the queue behind a context, the match entries
 //   dvo_sharded.cpp   one pair tile-sharded into bands / over several GPUs: band pipeline, record exchange, RCCL fallback
 //   dvo_probes.cpp    entries that work in slot 0 outside the match driver: residuals / error image, the stage probe, the kernel
@@ -7,14 +9,15 @@
 //   dvo_map.cpp       the keyframe map's point cloud: organized clouds at a pose, the deterministic voxel aggregate
 //   dvo_graph.cpp     the pose-graph optimizer: edge linearisation, dense fp64 Cholesky, Levenberg-Marquardt and dogleg
 //   dvo_graph_batch.cpp  many small pose graphs in one launch: one workgroup per graph, the whole optimization on the device
-//   dvo_rectify.cpp   remap tables (lens undistortion, arbitrary maps) and the frame ingest that resamples through one
-//   dvo_register.cpp  depth-to-colour registration at ingest: raw depth of another camera splatted into level 0's depth plane
+//   dvo_rectify.cpp   remap tables (lens undistortion, arbitrary maps) and the kernels that resample a frame through one
+//   dvo_register.cpp  depth-to-colour registration: the kernels that splat another camera's raw depth into level 0's depth plane
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include <atomic>
+#include <cmath>
 #include <deque>
 #include <memory>
 #include <mutex>
@@ -40,6 +43,26 @@ int fail_hip(const char *what, hipError_t e);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// the argument checks' common end: `entry: why` behind dvo_amd_last_error()
+inline int invalid(const char *entry, const std::string &why) {
+  g_last_error = std::string(entry) + ": " + why;
+  return DVO_AMD_ERR_INVALID_ARGUMENT;
+}
+
+template <typename T>
+inline bool finite_all(const T *v, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(v[i])) return false;
+  return true;
+}
+
+// is there a device at all (and how many: a `device` argument is checked against *count, after this status)
+inline int have_device(int *count = nullptr) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
+  if (count) *count = ndev;
+  return DVO_AMD_OK;
+}
 
 constexpr int kSpecLevelsMaxPairs = 8;  // speculative level starts (context::spec_levels) up to this many resident pairs
 constexpr size_t kTickLogFields = 8;  // doubles per logged launch (dvo_amd_debug_tick_log)
@@ -139,6 +162,23 @@ struct Registration {
   float min_z, mx, my;        // mx = fx / fxd, my = fy / fyd
   int fill;
   unsigned long long *counts; // host, 4 words: behind, outside, drawn, covered (written before pyramid_build returns)
+};
+
+// what a pyramid is ...
+struct PyramidSpec {
+  int width, height;
+  float fx, fy, ox, oy;
+  int levels;
+  double timestamp;
+};
+
+// ... and where its level 0 comes from: two float planes (raw == nullptr) or a raw frame, which says by itself whether it is
+// resampled (raw->remap) and whether its depth is registered (raw->reg); either of them in host or in device memory
+struct Level0Source {
+  const float *intensity, *depth;  // float planes, NaN = no depth
+  int stride;                      // ... their row stride in elements
+  const RawFrame *raw;
+  bool on_device;
 };
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -389,26 +429,27 @@ void desc_free(int device, void *p);
 void slab_free(int device, size_t bytes, void *p);
 int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const Selection **out);
 std::mutex &device_mutex(int device);  // the mutex of the device's shared state (never held across one of the calls above)
-int pyramid_build(int device, const float *src_i, const float *src_z, const RawFrame *raw, bool src_on_device, int width,
-                  int height, int stride, float fx, float fy, float ox, float oy, int levels, double timestamp,
-                  dvo_amd_pyramid **out);
+int pyramid_build(int device, const PyramidSpec &spec, const Level0Source &src, dvo_amd_pyramid **out);  // checked arguments
 int ingest_timing(int device, int enable, double *last_ms);  // dvo_amd_debug_ingest_timing
 
-// ---- dvo_rectify.cpp
-int rectify_level0(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st);
-int rectify_level0_locked(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st);
-// the per-device staging area of host raw frames, BGR sources and the registration's counters: grown to the largest seen and
-// kept; used with the device's mutex held
-struct Staging {
-  void *img = nullptr, *z = nullptr, *grey = nullptr, *reg = nullptr;
-  size_t img_bytes = 0, z_bytes = 0, grey_bytes = 0, reg_bytes = 0;
-};
-Staging &staging(int device);
-int staging_grow(void **p, size_t *have, size_t bytes);
+// ---- dvo_ingest.cpp
+// level 0's two base planes (L0.i_plane, L0.z_plane) from `src`, enqueued on `st`, the device's prep stream.  A host raw frame is
+// staged in L0.c_a (plain) or in the device's shared staging area (remapped, registered: under the device's mutex, from the first
+// use of the area to the last launch that reads it).  `ctrl`: 4 device words of the pyramid's own for a registration's counters.
+int ingest_level0(int device, const PyramidSpec &spec, const Level0Source &src, const LevelData &L0, unsigned long long *ctrl,
+                  hipStream_t st);
+// every level at least 4x2 with a width that is a multiple of 4, 1..DVO_AMD_MAX_LEVELS of them; `of` names whose levels they are
+int check_levels(const char *entry, int w, int h, int levels, const char *of = "");
 
-// ---- dvo_register.cpp
-int register_level0(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, int width, int height,
-                    float fx, float fy, float ox, float oy, unsigned long long *ctrl, hipStream_t st);
+// ---- dvo_rectify.cpp: a raw frame in device memory through a remap into i_plane and (unless null) z_plane.  A BGR image is
+// first converted into `grey` (rows of grey_stride bytes, a multiple of 4 that holds the remap's source width)
+int launch_remap_ingest(const dvo_amd_remap *r, const unsigned char *d_img, int channels, int img_stride, unsigned char *grey,
+                        int grey_stride, const unsigned short *d_z, int z_stride, float z_scale, float *i_plane, float *z_plane,
+                        hipStream_t st);
+
+// ---- dvo_register.cpp: raw depth in device memory into z_plane by the registration rule (clear, splat, count into `ctrl`)
+int launch_register_depth(const Registration &R, const unsigned short *d_z, int z_stride, float z_scale, float *z_plane,
+                          const PyramidSpec &view, unsigned long long *ctrl, hipStream_t st);
 
 // ---- dvo_tracker.cpp
 dvo_amd_iteration_stats *stats_push(Job &j);

@@ -715,12 +715,6 @@ int workspace(dvo_amd_context *ctx, MapWorkspace **out) {
   return DVO_AMD_OK;
 }
 
-int have_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
-  return DVO_AMD_OK;
-}
-
 bool valid_leaf(float leaf) { return std::isfinite(leaf) && leaf > 0.0f && leaf <= 65536.0f; }
 
 void float_pose(const double *pose, float T[12]) {
@@ -978,12 +972,6 @@ int find_keyframe(const dvo_amd_map *M, int id) {
   return -1;
 }
 
-bool finite_pose(const double *pose) {
-  for (int e = 0; e < 16; ++e)
-    if (!std::isfinite(pose[e])) return false;
-  return true;
-}
-
 int entry_checks(const dvo_amd_map *M, const char *what) {
   int rc = have_device();
   if (rc) return rc;
@@ -1164,7 +1152,7 @@ int check_view(const dvo_amd_map *M, const double *pose, const dvo_amd_view *v, 
   else if (!(std::isfinite(v->fx) && v->fx > 0.0f && std::isfinite(v->fy) && v->fy > 0.0f)) why = "fx and fy must be finite and positive";
   else if (!std::isfinite(v->ox) || !std::isfinite(v->oy)) why = "ox and oy must be finite";
   else if (!std::isfinite(v->near_z) || !(v->near_z > 0.0f)) why = "near_z must be finite and positive";
-  else if (pose && !finite_pose(pose)) why = "the pose has a non-finite entry";
+  else if (pose && !finite_all(pose, 16)) why = "the pose has a non-finite entry";
   else if (v->near_z < (M->leaf * std::max(v->fx, v->fy)) / 32.0f)
     why = "near_z is below leaf_size * max(fx, fy) / 32: a voxel at near_z would cover more than 32 pixels a side";
   if (!why) return DVO_AMD_OK;
@@ -1272,7 +1260,7 @@ int dvo_amd_map_insert(dvo_amd_map *M, int id, dvo_amd_pyramid *image, const dou
     g_last_error = "dvo_amd_map_insert: keyframe id " + std::to_string(id) + " is already in the map";
     return DVO_AMD_ERR_INVALID_ARGUMENT;
   }
-  if (pose && !host::finite_pose(pose)) {
+  if (pose && !host::finite_all(pose, 16)) {
     g_last_error = "dvo_amd_map_insert: the pose of keyframe " + std::to_string(id) + " has a non-finite entry";
     return DVO_AMD_ERR_INVALID_ARGUMENT;
   }
@@ -1322,7 +1310,7 @@ int dvo_amd_map_set_poses(dvo_amd_map *M, int n, const int *ids, const double *p
   for (const dvo_amd_map::Keyframe &k : next) all_points += k.points;
   for (int q = 0; q < n; ++q) {
     const int at = host::find_keyframe(M, ids[q]);
-    if (at < 0 || seen[(size_t)at] || !host::finite_pose(poses + 16 * (size_t)q)) {
+    if (at < 0 || seen[(size_t)at] || !host::finite_all(poses + 16 * (size_t)q, 16)) {
       g_last_error = "dvo_amd_map_set_poses: keyframe id " + std::to_string(ids[q]) +
                      (at < 0 ? " is not in the map" : seen[(size_t)at] ? " is given twice" : " has a non-finite pose entry");
       return DVO_AMD_ERR_INVALID_ARGUMENT;
@@ -1510,12 +1498,9 @@ int dvo_amd_map_render_pyramid(dvo_amd_map *M, const double *pose, const dvo_amd
   *out = nullptr;
   rc = host::check_view(M, pose, view, "dvo_amd_map_render_pyramid");
   if (rc) return rc;
-  if (levels < 1 || levels > DVO_AMD_MAX_LEVELS) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  for (int l = 0, w = view->width, h = view->height; l < levels; ++l, w /= 2, h /= 2)
-    if (w < 4 || h < 2 || (w % 4) != 0) {  // dvo_amd_pyramid_create_from_device's rule, before anything is rendered
-      g_last_error = "dvo_amd_map_render_pyramid: the view cannot hold a pyramid of " + std::to_string(levels) + " levels";
-      return DVO_AMD_ERR_INVALID_ARGUMENT;
-    }
+  // dvo_amd_pyramid_create_from_device's rule, before anything is rendered
+  rc = host::check_levels("dvo_amd_map_render_pyramid", view->width, view->height, levels, " of the levels asked of the view");
+  if (rc) return rc;
   M->device_ms = 0.0, M->copy_ms = 0.0, M->delta_points = 0, M->delta_voxels = 0;
   host::RenderPlanes P;
   map::RenderCtrl c;

@@ -133,28 +133,10 @@ size_t pyramid_layout(dvo_amd_pyramid *p, char *base) {
   return off;
 }
 
-int pyramid_build(int device, const float *src_i, const float *src_z, const RawFrame *raw, bool src_on_device, int width,
-                  int height, int stride, float fx, float fy, float ox, float oy, int levels, double timestamp,
-                  dvo_amd_pyramid **out) {
-  if (!out) return DVO_AMD_ERR_INVALID_ARGUMENT;
+// the arguments are the entries' business (dvo_ingest.cpp): nothing is checked again here
+int pyramid_build(int device, const PyramidSpec &spec, const Level0Source &src, dvo_amd_pyramid **out) {
   *out = nullptr;
-  if (width < 4 || height < 2 || levels < 1 || levels > DVO_AMD_MAX_LEVELS) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  if (raw) {
-    const int raw_width = raw->remap ? raw->remap->sw : width, z_width = raw->reg ? raw->reg->dw : raw_width;
-    if (!raw->image || !raw->depth || (raw->channels != 1 && raw->channels != 3) ||
-        raw->image_stride_bytes < raw_width * raw->channels || raw->depth_stride < z_width || !(raw->depth_scale > 0.0f))
-      return DVO_AMD_ERR_INVALID_ARGUMENT;
-  } else if (!src_i || !src_z || stride < width) {
-    return DVO_AMD_ERR_INVALID_ARGUMENT;
-  }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
-  if (device < 0 || device >= ndev || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  {
-    int w = width, h = height;
-    for (int l = 0; l < levels; ++l, w /= 2, h /= 2)
-      if (w < 4 || h < 2 || (w % 4) != 0) return DVO_AMD_ERR_INVALID_ARGUMENT;  // see header: width % 4 on every level
-  }
+  const int levels = spec.levels;
   HIP_TRY(hipSetDevice(device));
   hipStream_t st;
   int rc = device_prep_stream(device, &st);
@@ -163,11 +145,11 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   dvo_amd_pyramid *p = new dvo_amd_pyramid();
   p->device = device;
   p->n_levels = levels;
-  p->timestamp = timestamp;
+  p->timestamp = spec.timestamp;
   for (int l = 0; l < levels; ++l) {
     LevelData &L = p->lv[l];
     if (l == 0) {
-      L.w = width, L.h = height, L.fx = fx, L.fy = fy, L.ox = ox, L.oy = oy;
+      L.w = spec.width, L.h = spec.height, L.fx = spec.fx, L.fy = spec.fy, L.ox = spec.ox, L.oy = spec.oy;
     } else {
       // RgbdCameraPyramid::build (rgbd_image.cpp:283-296) with IntrinsicMatrix::scale(0.5f) (intrinsic_matrix.cpp:90-93)
       const LevelData &P = p->lv[l - 1];
@@ -193,70 +175,23 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   p->cur_desc = (CurLevelDesc *)p->desc_entry;
   p->ref_desc0 = (RefLevelDesc *)((char *)p->desc_entry + 640);
 
-  // everything below is enqueued on the device's prep stream; the mutex serialises users of that stream's ordering needs
+  // everything below is enqueued on the device's prep stream, and whatever fails, the stream is drained before the slab goes
+  // back to the pool: a copy or a launch may still be on its way into it
   auto bail = [&](int code) {
+    (void)hipStreamSynchronize(st);
     slab_free(device, p->slab_bytes, p->slab);
     desc_free(device, p->desc_entry);
     delete p;
     return code;
   };
-  LevelData &L0 = p->lv[0];
   hipError_t e;
   DeviceState &dev = g_dev[device];
   const bool timed = dev.timing.load();
   if (timed && (e = hipEventRecord(dev.ev[0], st)) != hipSuccess) return bail(fail_hip("ingest timing", e));
-  if (raw && raw->reg) {
-    // the four counters live in the room of the first selection's descriptors, which nothing writes before this build returns
-    rc = register_level0(device, *raw, src_on_device, L0.i_plane, L0.z_plane, width, height, fx, fy, ox, oy,
-                         (unsigned long long *)p->ref_desc0, st);
-    if (rc) {
-      (void)hipStreamSynchronize(st);
-      return bail(rc);
-    }
-    e = hipSuccess;
-  } else if (raw && raw->remap) {
-    rc = rectify_level0(device, *raw, src_on_device, L0.i_plane, L0.z_plane, st);
-    if (rc) {
-      (void)hipStreamSynchronize(st);
-      return bail(rc);
-    }
-    e = hipSuccess;
-  } else if (raw) {
-    const unsigned char *d_img = raw->image;
-    const unsigned short *d_z = raw->depth;
-    int img_stride = raw->image_stride_bytes, z_stride = raw->depth_stride;
-    if (!src_on_device) {
-      // stage the raw bytes (5 B/px instead of 8 B/px of float planes over PCIe) in level 0's gather plane, which is only
-      // written by launch_level_planes further down the same stream
-      unsigned char *stage_img = (unsigned char *)L0.c_a;
-      unsigned short *stage_z = (unsigned short *)(stage_img + align_up((size_t)L0.n * raw->channels, 256));
-      const size_t row_img = (size_t)width * raw->channels, row_z = sizeof(unsigned short) * (size_t)width;
-      e = hipMemcpy2DAsync(stage_img, row_img, raw->image, (size_t)raw->image_stride_bytes, row_img, height,
-                           hipMemcpyHostToDevice, st);
-      if (e == hipSuccess)
-        e = hipMemcpy2DAsync(stage_z, row_z, raw->depth, sizeof(unsigned short) * (size_t)raw->depth_stride, row_z, height,
-                             hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) return bail(fail_hip("raw frame upload", e));
-      d_img = stage_img, d_z = stage_z, img_stride = (int)row_img, z_stride = width;
-    }
-    e = launch_ingest(d_img, raw->channels, img_stride, d_z, z_stride, raw->depth_scale, L0.i_plane, L0.z_plane, width,
-                      height, st);
-  } else if (src_on_device) {
-    if (stride == width) {
-      e = hipMemcpyAsync(L0.i_plane, src_i, sizeof(float) * L0.n, hipMemcpyDeviceToDevice, st);
-      if (e == hipSuccess) e = hipMemcpyAsync(L0.z_plane, src_z, sizeof(float) * L0.n, hipMemcpyDeviceToDevice, st);
-    } else {
-      e = launch_copy_strided(src_i, stride, L0.i_plane, width, height, st);
-      if (e == hipSuccess) e = launch_copy_strided(src_z, stride, L0.z_plane, width, height, st);
-    }
-  } else {
-    e = hipMemcpy2DAsync(L0.i_plane, sizeof(float) * width, src_i, sizeof(float) * stride, sizeof(float) * width, height,
-                         hipMemcpyHostToDevice, st);
-    if (e == hipSuccess)
-      e = hipMemcpy2DAsync(L0.z_plane, sizeof(float) * width, src_z, sizeof(float) * stride, sizeof(float) * width, height,
-                           hipMemcpyHostToDevice, st);
-  }
-  if (e != hipSuccess) return bail(fail_hip("pyramid upload", e));
+  // (a registration's four counters live in the room of the first selection's descriptors, which nothing writes before this
+  // build returns)
+  rc = ingest_level0(device, spec, src, p->lv[0], (unsigned long long *)p->ref_desc0, st);
+  if (rc) return bail(rc);
   for (int l = 0; l < levels; ++l) {
     LevelData &L = p->lv[l];
     if (l > 0) {
@@ -285,8 +220,8 @@ int pyramid_build(int device, const float *src_i, const float *src_z, const RawF
   }
   e = hipMemcpyAsync(p->cur_desc, cur_host, sizeof(CurLevelDesc) * levels, hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return bail(fail_hip("pyramid descriptors", e));
-  if (raw && raw->reg) {
-    e = hipMemcpyAsync(raw->reg->counts, p->ref_desc0, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
+  if (src.raw && src.raw->reg) {
+    e = hipMemcpyAsync(src.raw->reg->counts, p->ref_desc0, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) return bail(fail_hip("registration counters", e));
   }
   if (timed && (e = hipEventRecord(dev.ev[1], st)) != hipSuccess) return bail(fail_hip("ingest timing", e));
@@ -389,27 +324,6 @@ using namespace dvo_amd;
 using namespace dvo_amd::host;
 
 extern "C" {
-
-int dvo_amd_pyramid_create(int device, const float *intensity, const float *depth, int width, int height, int stride,
-                           float fx, float fy, float ox, float oy, int levels, double timestamp, dvo_amd_pyramid **out) {
-  return pyramid_build(device, intensity, depth, nullptr, false, width, height, stride, fx, fy, ox, oy, levels, timestamp, out);
-}
-
-int dvo_amd_pyramid_create_from_device(int device, const float *d_intensity, const float *d_depth, int width, int height,
-                                       int stride, float fx, float fy, float ox, float oy, int levels, double timestamp,
-                                       dvo_amd_pyramid **out) {
-  return pyramid_build(device, d_intensity, d_depth, nullptr, true, width, height, stride, fx, fy, ox, oy, levels, timestamp,
-                       out);
-}
-
-int dvo_amd_pyramid_create_raw(int device, const unsigned char *image, int channels, int image_stride_bytes,
-                               const unsigned short *depth, int depth_stride, float depth_scale, int on_device, int width,
-                               int height, float fx, float fy, float ox, float oy, int levels, double timestamp,
-                               dvo_amd_pyramid **out) {
-  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale, nullptr, nullptr};
-  return pyramid_build(device, nullptr, nullptr, &raw, on_device != 0, width, height, width, fx, fy, ox, oy, levels,
-                       timestamp, out);
-}
 
 void dvo_amd_pyramid_retain(dvo_amd_pyramid *p) {
   if (p) p->refs.fetch_add(1);

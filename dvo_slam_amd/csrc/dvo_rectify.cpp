@@ -154,34 +154,8 @@ namespace {
 
 constexpr int kMaxSourceSide = 1 << 20;  // (float)(s - 1) and s + 0.5f are exact below 2^23; a side this long is no camera's
 
-int invalid(const char *entry, const std::string &why) {
-  g_last_error = std::string(entry) + ": " + why;
-  return DVO_AMD_ERR_INVALID_ARGUMENT;
-}
-
-Staging g_stage[kMaxDevices];
-
-}  // namespace
-
-Staging &staging(int device) { return g_stage[device]; }
-
-int staging_grow(void **p, size_t *have, size_t bytes) {
-  if (bytes <= *have) return DVO_AMD_OK;
-  if (*p) (void)hipFree(*p), *p = nullptr, *have = 0;  // (hipFree waits for whatever still reads the old area)
-  bytes = align_up(bytes, 1 << 16);
-  const hipError_t e = hipMalloc(p, bytes);
-  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
-  if (e != hipSuccess) return fail_hip("hipMalloc (rectification staging)", e);
-  *have = bytes;
-  return DVO_AMD_OK;
-}
-
-namespace {
-
-int grow(void **p, size_t *have, size_t bytes) { return staging_grow(p, have, bytes); }
-
 int check_output_size(const char *entry, int width, int height) {
-  if (width < 4 || height < 2 || (width % 4) != 0) return invalid(entry, "the output must be at least 4x2 with a width that is a multiple of 4");
+  if (check_levels(entry, width, height, 1)) return invalid(entry, "the output must be at least 4x2 with a width that is a multiple of 4");
   if ((long long)width * height > (1ll << 30)) return invalid(entry, "the output holds more than 2^30 pixels");
   return DVO_AMD_OK;
 }
@@ -192,20 +166,15 @@ int check_source_size(const char *entry, int src_width, int src_height) {
   return DVO_AMD_OK;
 }
 
-bool finite_all(const float *v, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
 // the remap object with its two planes allocated and the counter cleared (on the prep stream); the caller fills the planes
 int remap_alloc(const char *entry, int device, int width, int height, int src_width, int src_height, dvo_amd_remap **out,
                 hipStream_t *st) {
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
+  int rc = have_device(&ndev);
+  if (rc) return rc;
   if (device < 0 || device >= ndev || device >= kMaxDevices) return invalid(entry, "no such device");
   HIP_TRY(hipSetDevice(device));
-  int rc = device_prep_stream(device, st);
+  rc = device_prep_stream(device, st);
   if (rc) return rc;
   const size_t n = (size_t)width * height, plane = align_up(sizeof(float) * n, 256);
   void *mem = nullptr;
@@ -241,48 +210,23 @@ int remap_finish(dvo_amd_remap *r, hipError_t e, hipStream_t st, dvo_amd_remap *
 
 }  // namespace
 
-// Level 0's two base planes from a raw frame through a remap (pyramid_build calls this in place of launch_ingest).  Everything
-// is enqueued on `st`, the device's prep stream; the device's mutex is held from the first upload to the last launch, so two
-// threads' uses of the staging area reach the stream one after the other and the stream's order does the rest.
-int rectify_level0(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st) {
-  std::lock_guard<std::mutex> lk(device_mutex(device));
-  return rectify_level0_locked(device, raw, on_device, i_plane, z_plane, st);
-}
-
-// the same with the device's mutex held by the caller; z_plane == nullptr: the intensity plane alone, raw.depth is not read
-int rectify_level0_locked(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, hipStream_t st) {
-  const dvo_amd_remap *r = raw.remap;
-  Staging &S = g_stage[device];
-  const unsigned char *d_img = raw.image;
-  const unsigned short *d_z = raw.depth;
-  int img_stride = raw.image_stride_bytes, z_stride = raw.depth_stride;
+// Level 0's base planes from a raw frame in device memory through a remap, enqueued on `st` (ingest_level0 calls this in place of
+// launch_ingest); z_plane == nullptr: the intensity plane alone, d_z is not read
+int launch_remap_ingest(const dvo_amd_remap *r, const unsigned char *d_img, int channels, int img_stride, unsigned char *grey,
+                        int grey_stride, const unsigned short *d_z, int z_stride, float z_scale, float *i_plane, float *z_plane,
+                        hipStream_t st) {
   hipError_t e = hipSuccess;
-  if (!on_device) {
-    const size_t row_img = (size_t)r->sw * raw.channels, row_z = sizeof(unsigned short) * (size_t)r->sw;
-    int rc = grow(&S.img, &S.img_bytes, row_img * r->sh);
-    if (!rc && z_plane) rc = grow(&S.z, &S.z_bytes, row_z * r->sh);
-    if (rc) return rc;
-    e = hipMemcpy2DAsync(S.img, row_img, raw.image, (size_t)raw.image_stride_bytes, row_img, r->sh, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && z_plane)
-      e = hipMemcpy2DAsync(S.z, row_z, raw.depth, sizeof(unsigned short) * (size_t)raw.depth_stride, row_z, r->sh,
-                           hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail_hip("raw frame upload", e);
-    d_img = (const unsigned char *)S.img, d_z = (const unsigned short *)S.z, img_stride = (int)row_img, z_stride = r->sw;
-  }
-  if (raw.channels == 3) {
-    const int grey_stride = (int)align_up((size_t)r->sw, 4);
-    const int rc = grow(&S.grey, &S.grey_bytes, (size_t)grey_stride * r->sh);
-    if (rc) return rc;
+  if (channels == 3) {
     hipLaunchKernelGGL(rectify::k_grey_plane, dim3((unsigned)((grey_stride / 4 + 63) / 64), (unsigned)r->sh), dim3(64), 0, st, d_img,
-                       img_stride, r->sw, r->sh, (unsigned char *)S.grey, grey_stride);
+                       img_stride, r->sw, r->sh, grey, grey_stride);
     e = hipGetLastError();
     if (e != hipSuccess) return fail_hip("k_grey_plane", e);
-    d_img = (const unsigned char *)S.grey, img_stride = grey_stride;
+    d_img = grey, img_stride = grey_stride;
   }
   const dim3 grid((unsigned)((r->w / 4 + 63) / 64), (unsigned)r->h);
   if (z_plane)
     hipLaunchKernelGGL(rectify::k_ingest_remap<true>, grid, dim3(64), 0, st, r->map_x, r->map_y, d_img, img_stride, d_z, z_stride,
-                       raw.depth_scale, (float)(r->sw - 1), (float)(r->sh - 1), i_plane, z_plane, r->w, r->h);
+                       z_scale, (float)(r->sw - 1), (float)(r->sh - 1), i_plane, z_plane, r->w, r->h);
   else
     hipLaunchKernelGGL(rectify::k_ingest_remap<false>, grid, dim3(64), 0, st, r->map_x, r->map_y, d_img, img_stride,
                        (const unsigned short *)nullptr, 0, 0.0f, (float)(r->sw - 1), (float)(r->sh - 1), i_plane, (float *)nullptr,
@@ -383,36 +327,6 @@ int dvo_amd_remap_download(const dvo_amd_remap *r, float *map_x, float *map_y) {
   HIP_TRY(hipMemcpyAsync(map_y, r->map_y, bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   return DVO_AMD_OK;
-}
-
-int dvo_amd_pyramid_create_raw_remapped(int device, const unsigned char *image, int channels, int image_stride_bytes,
-                                        const unsigned short *depth, int depth_stride, float depth_scale, int on_device,
-                                        const dvo_amd_remap *remap, float fx, float fy, float ox, float oy, int levels,
-                                        double timestamp, dvo_amd_pyramid **out) {
-  static const char *entry = "dvo_amd_pyramid_create_raw_remapped";
-  if (out) *out = nullptr;
-  if (!out || !image || !depth || !remap) return invalid(entry, "a NULL pointer");
-  if (channels != 1 && channels != 3) return invalid(entry, "channels must be 1 or 3");
-  if (!(depth_scale > 0.0f)) return invalid(entry, "depth_scale must be > 0");
-  if ((long long)image_stride_bytes < (long long)remap->sw * channels || depth_stride < remap->sw)
-    return invalid(entry, "a stride of the raw frame is smaller than the remap's source row");
-  if (levels < 1 || levels > DVO_AMD_MAX_LEVELS) return invalid(entry, "levels must be 1.." + std::to_string(DVO_AMD_MAX_LEVELS));
-  for (int l = 0, w = remap->w, h = remap->h; l < levels; ++l, w /= 2, h /= 2)
-    if (w < 4 || h < 2 || (w % 4) != 0)
-      return invalid(entry, "level " + std::to_string(l) + " of the remap's output would not be at least 4x2 with a width that is a multiple of 4");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
-  if (remap->device != device) return DVO_AMD_ERR_DEVICE_MISMATCH;
-  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale, remap, nullptr};
-  return pyramid_build(device, nullptr, nullptr, &raw, on_device != 0, remap->w, remap->h, remap->w, fx, fy, ox, oy, levels,
-                       timestamp, out);
-}
-
-/* instrumentation: with enable != 0 every later pyramid build on `device` is bracketed by two events on the prep stream;
- * *last_ms (may be NULL) receives the device time of the most recent bracketed build */
-int dvo_amd_debug_ingest_timing(int device, int enable, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  return ingest_timing(device, enable, last_ms);
 }
 
 }  // extern "C"

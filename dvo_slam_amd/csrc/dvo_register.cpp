@@ -20,7 +20,7 @@ namespace registration {
 
 constexpr int kBlock = 256;
 constexpr unsigned kEmptyWord = 0x7FC00000u;
-constexpr int kMaxBlocks = 256;     // of k_register_splat (a quarter of it for k_register_count): see register_level0
+constexpr int kMaxBlocks = 256;     // of k_register_splat (a quarter of it for k_register_count): see launch_register_depth
 constexpr int kSmallFootprint = 4;  // pixels a lane splats by itself; larger footprints are walked by the whole wave
 
 struct View {
@@ -131,71 +131,21 @@ __global__ void __launch_bounds__(kBlock) k_register_count(const uint4 *__restri
 
 namespace host {
 
-namespace {
-
-constexpr int kMaxDepthSide = 1 << 20;  // (float)u is exact far beyond it; a side this long is no camera's
-
-int invalid(const char *entry, const std::string &why) {
-  g_last_error = std::string(entry) + ": " + why;
-  return DVO_AMD_ERR_INVALID_ARGUMENT;
-}
-
-bool finite_all(const float *v, int n) {
-  for (int i = 0; i < n; ++i)
-    if (!std::isfinite(v[i])) return false;
-  return true;
-}
-
-}  // namespace
-
-// Level 0's two base planes of a registered frame (pyramid_build calls this in place of launch_ingest): the intensity plane as
-// the plain or the remapped ingest writes it, the depth plane by the registration rule.  `ctrl` is device memory of the
-// pyramid's own (4 words: behind, outside, drawn, covered).  Everything is enqueued on `st`, the device's prep stream, with the
-// device's mutex held from the first upload to the last launch, as in rectify_level0.
-int register_level0(int device, const RawFrame &raw, bool on_device, float *i_plane, float *z_plane, int width, int height,
-                    float fx, float fy, float ox, float oy, unsigned long long *ctrl, hipStream_t st) {
-  const Registration &R = *raw.reg;
-  std::lock_guard<std::mutex> lk(device_mutex(device));
-  Staging &S = staging(device);
-  hipError_t e = hipSuccess;
-  if (raw.remap) {
-    const int rc = rectify_level0_locked(device, raw, on_device, i_plane, nullptr, st);
-    if (rc) return rc;
-  } else {
-    const unsigned char *d_img = raw.image;
-    int img_stride = raw.image_stride_bytes;
-    if (!on_device) {
-      const size_t row_img = (size_t)width * raw.channels;
-      const int rc = staging_grow(&S.img, &S.img_bytes, row_img * height);
-      if (rc) return rc;
-      e = hipMemcpy2DAsync(S.img, row_img, raw.image, (size_t)raw.image_stride_bytes, row_img, height, hipMemcpyHostToDevice, st);
-      if (e != hipSuccess) return fail_hip("raw image upload", e);
-      d_img = (const unsigned char *)S.img, img_stride = (int)row_img;
-    }
-    e = launch_ingest_intensity(d_img, raw.channels, img_stride, i_plane, width, height, st);
-    if (e != hipSuccess) return fail_hip("k_ingest", e);
-  }
-  const unsigned short *d_z = raw.depth;
-  int z_stride = raw.depth_stride;
-  if (!on_device) {
-    const size_t row_z = sizeof(unsigned short) * (size_t)R.dw;
-    const int rc = staging_grow(&S.z, &S.z_bytes, row_z * R.dh);
-    if (rc) return rc;
-    e = hipMemcpy2DAsync(S.z, row_z, raw.depth, sizeof(unsigned short) * (size_t)raw.depth_stride, row_z, R.dh, hipMemcpyHostToDevice, st);
-    if (e != hipSuccess) return fail_hip("raw depth upload", e);
-    d_z = (const unsigned short *)S.z, z_stride = R.dw;
-  }
-  const size_t n = (size_t)width * height;
-  e = hipMemsetD32Async((hipDeviceptr_t)z_plane, (int)registration::kEmptyWord, n, st);
+// Level 0's depth plane of a registered frame from raw depth in device memory, enqueued on `st` (ingest_level0 calls this after the
+// intensity plane is on its way).  `ctrl` is device memory of the pyramid's own (4 words: behind, outside, drawn, covered).
+int launch_register_depth(const Registration &R, const unsigned short *d_z, int z_stride, float z_scale, float *z_plane,
+                          const PyramidSpec &view, unsigned long long *ctrl, hipStream_t st) {
+  const size_t n = (size_t)view.width * view.height;
+  hipError_t e = hipMemsetD32Async((hipDeviceptr_t)z_plane, (int)registration::kEmptyWord, n, st);
   if (e == hipSuccess) e = hipMemsetAsync(ctrl, 0, sizeof(registration::Ctrl), st);
   if (e != hipSuccess) return fail_hip("registration clear", e);
-  const registration::View V{width, height, fx, fy, ox, oy};
+  const registration::View V{view.width, view.height, view.fx, view.fy, view.ox, view.oy};
   // About one block per compute unit, and the kernel strides over the rest: every wave ends with up to three atomic adds on one
   // cache line, which the memory side serialises at about 12 ns each (measured: a block per 256 pixels, 4800 waves at 640x480,
   // spent 61 us in the splat).
   const unsigned gx = (unsigned)std::min(registration::kMaxBlocks, (R.dw + registration::kBlock - 1) / registration::kBlock);
   const unsigned gy = (unsigned)std::min<long long>(R.dh, std::max(1u, (unsigned)registration::kMaxBlocks / gx));
-  hipLaunchKernelGGL(registration::k_register_splat, dim3(gx, gy), dim3(registration::kBlock), 0, st, d_z, z_stride, raw.depth_scale, R, V,
+  hipLaunchKernelGGL(registration::k_register_splat, dim3(gx, gy), dim3(registration::kBlock), 0, st, d_z, z_stride, z_scale, R, V,
                      (unsigned *)z_plane, (registration::Ctrl *)ctrl);
   e = hipGetLastError();
   if (e != hipSuccess) return fail_hip("k_register_splat", e);
@@ -219,59 +169,6 @@ void dvo_amd_default_registration(dvo_amd_registration *reg) {
   if (!reg) return;
   std::memset(reg, 0, sizeof(*reg));
   reg->T[0] = reg->T[5] = reg->T[10] = reg->T[15] = 1.0;
-}
-
-int dvo_amd_pyramid_create_raw_registered(int device, const unsigned char *image, int channels, int image_stride_bytes,
-                                          const unsigned short *depth, int depth_stride, float depth_scale, int on_device,
-                                          const dvo_amd_registration *reg, const dvo_amd_remap *remap, int width, int height,
-                                          float fx, float fy, float ox, float oy, int levels, double timestamp,
-                                          dvo_amd_pyramid **out, dvo_amd_registration_stats *stats) {
-  static const char *entry = "dvo_amd_pyramid_create_raw_registered";
-  if (out) *out = nullptr;
-  if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (!out || !image || !depth || !reg) return invalid(entry, "a NULL pointer");
-  if (channels != 1 && channels != 3) return invalid(entry, "channels must be 1 or 3");
-  if (!(depth_scale > 0.0f)) return invalid(entry, "depth_scale must be > 0");
-  if (reg->depth_width < 1 || reg->depth_height < 1 || reg->depth_width > kMaxDepthSide || reg->depth_height > kMaxDepthSide)
-    return invalid(entry, "a side of the depth frame is outside 1..2^20");
-  if (depth_stride < reg->depth_width) return invalid(entry, "depth_stride < depth_width");
-  const float k[4] = {fx, fy, ox, oy};
-  float T[12];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 4; ++c) T[4 * r + c] = (float)reg->T[4 * c + r];  // column-major double -> row-major float
-  if (!finite_all(reg->k_depth, 4) || !finite_all(T, 12) || !finite_all(k, 4))
-    return invalid(entry, "a non-finite intrinsic or entry of the transform");
-  if (!(reg->k_depth[0] > 0.0f && reg->k_depth[1] > 0.0f && fx > 0.0f && fy > 0.0f))
-    return invalid(entry, "fx and fy of both cameras must be positive");
-  if (!(reg->min_z >= 0.0f) || !std::isfinite(reg->min_z)) return invalid(entry, "min_z must be finite and >= 0");
-  if (reg->fill != 0 && reg->fill != 1) return invalid(entry, "fill must be 0 or 1");
-  if (remap && (remap->w != width || remap->h != height)) return invalid(entry, "the remap's output size differs from width x height");
-  const int image_width = remap ? remap->sw : width;
-  if ((long long)image_stride_bytes < (long long)image_width * channels)
-    return invalid(entry, "the image stride is smaller than the row it must hold");
-  if (levels < 1 || levels > DVO_AMD_MAX_LEVELS) return invalid(entry, "levels must be 1.." + std::to_string(DVO_AMD_MAX_LEVELS));
-  if ((long long)width * height > (1ll << 30)) return invalid(entry, "the pyramid's level 0 holds more than 2^30 pixels");
-  for (int l = 0, w = width, h = height; l < levels; ++l, w /= 2, h /= 2)
-    if (w < 4 || h < 2 || (w % 4) != 0)
-      return invalid(entry, "level " + std::to_string(l) + " would not be at least 4x2 with a width that is a multiple of 4");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
-  if (remap && remap->device != device) return DVO_AMD_ERR_DEVICE_MISMATCH;
-  unsigned long long counts[4] = {0, 0, 0, 0};
-  Registration R;
-  R.dw = reg->depth_width, R.dh = reg->depth_height;
-  R.fxd = reg->k_depth[0], R.fyd = reg->k_depth[1], R.oxd = reg->k_depth[2], R.oyd = reg->k_depth[3];
-  std::memcpy(R.T, T, sizeof(T));
-  R.min_z = reg->min_z, R.mx = fx / R.fxd, R.my = fy / R.fyd, R.fill = reg->fill, R.counts = counts;
-  RawFrame raw{image, channels, image_stride_bytes, depth, depth_stride, depth_scale, remap, &R};
-  const int rc = pyramid_build(device, nullptr, nullptr, &raw, on_device != 0, width, height, width, fx, fy, ox, oy, levels,
-                               timestamp, out);
-  if (rc == DVO_AMD_OK && stats) {
-    stats->behind = (long long)counts[0], stats->outside = (long long)counts[1], stats->drawn = (long long)counts[2];
-    stats->measurements = stats->behind + stats->outside + stats->drawn;
-    stats->covered_pixels = (long long)counts[3];
-  }
-  return rc;
 }
 
 }  // extern "C"

@@ -1185,12 +1185,13 @@ int dvo_amd_context_create(int device, const dvo_amd_config *cfg, dvo_amd_contex
   if (!out) return DVO_AMD_ERR_INVALID_ARGUMENT;
   *out = nullptr;
   int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return DVO_AMD_ERR_NO_DEVICE;
+  int rc = have_device(&ndev);
+  if (rc) return rc;
   if (device < 0 || device >= ndev || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
   dvo_amd_config c;
   dvo_amd_default_config(&c);
   if (cfg) c = *cfg;
-  int rc = check_config(&c);
+  rc = check_config(&c);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(device));
   dvo_amd_context *ctx = new dvo_amd_context();
