@@ -30,6 +30,8 @@ examples: $(LIB)
 	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 	$(CC) -std=c99 -Wall -Iinclude examples/registered_ingest_example.c -o examples/_build/registered_ingest_example \
 	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CC) -std=c99 -Wall -Iinclude examples/batch_ingest_example.c -o examples/_build/batch_ingest_example \
+	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 
 clean:
 	rm -f $(LIB)

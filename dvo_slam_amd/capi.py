@@ -49,6 +49,7 @@ EXPORTS = [
     "dvo_amd_remap_create", "dvo_amd_remap_create_undistort", "dvo_amd_remap_retain", "dvo_amd_remap_release", "dvo_amd_remap_info",
     "dvo_amd_remap_download", "dvo_amd_pyramid_create_raw_remapped", "dvo_amd_debug_ingest_timing",
     "dvo_amd_default_registration", "dvo_amd_pyramid_create_raw_registered",
+    "dvo_amd_pyramid_create_raw_batch", "dvo_amd_debug_batch_build_stats",
 ]
 
 
@@ -118,6 +119,15 @@ class CRenderStats(C.Structure):
 class CRegistration(C.Structure):
     _fields_ = [("depth_width", C.c_int), ("depth_height", C.c_int), ("k_depth", C.c_float * 4), ("T", C.c_double * 16),
                 ("min_z", C.c_float), ("fill", C.c_int)]
+
+
+class CRawBatch(C.Structure):
+    _fields_ = [("count", C.c_int), ("images", C.POINTER(C.c_void_p)), ("depths", C.POINTER(C.c_void_p)),
+                ("timestamps", C.POINTER(C.c_double)), ("channels", C.c_int), ("image_stride_bytes", C.c_int),
+                ("depth_stride", C.c_int), ("depth_scale", C.c_float), ("on_device", C.c_int), ("width", C.c_int),
+                ("height", C.c_int), ("fx", C.c_float), ("fy", C.c_float), ("ox", C.c_float), ("oy", C.c_float),
+                ("levels", C.c_int), ("build_selection", C.c_int), ("intensity_threshold", C.c_float),
+                ("depth_threshold", C.c_float)]
 
 
 class CRegistrationStats(C.Structure):
@@ -301,6 +311,8 @@ def lib():
                                                         C.POINTER(CRegistration), vp, C.c_int, C.c_int, C.c_float, C.c_float,
                                                         C.c_float, C.c_float, C.c_int, C.c_double, C.POINTER(vp),
                                                         C.POINTER(CRegistrationStats)]
+    L.dvo_amd_pyramid_create_raw_batch.argtypes = [C.c_int, C.POINTER(CRawBatch), C.POINTER(vp)]
+    L.dvo_amd_debug_batch_build_stats.argtypes = [C.c_int, ip, ip, ip]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -486,6 +498,14 @@ def ingest_timing(enable: bool = True, device: int = 0) -> float:
     return ms.value
 
 
+def batch_build_stats(device: int = 0) -> dict:
+    """(instrumentation) what the most recent RgbdImagePyramid.from_raw_batch on `device` enqueued:
+    {"kernel_launches", "copies", "synchronisations"} (dvo_amd_debug_batch_build_stats)"""
+    v = [C.c_int() for _ in range(3)]
+    _check(lib().dvo_amd_debug_batch_build_stats(device, *[C.byref(x) for x in v]), "dvo_amd_debug_batch_build_stats")
+    return dict(zip(("kernel_launches", "copies", "synchronisations"), (x.value for x in v)))
+
+
 class RgbdImagePyramid:
     """RgbdCameraPyramid(w, h, K).create(intensity, depth) with `levels` levels built on the GPU."""
 
@@ -586,6 +606,56 @@ class RgbdImagePyramid:
                "dvo_amd_pyramid_create_raw")
         self.device = device
         return self
+
+    @classmethod
+    def from_raw_batch(cls, images, depths, K, levels: int, depth_scale: float = 1.0 / 5000.0, device: int = 0, timestamps=None,
+                       selection=None, size=None, channels: int | None = None, image_stride_bytes: int | None = None,
+                       depth_stride: int | None = None):
+        """from_raw for many frames of one camera in one call (dvo_amd_pyramid_create_raw_batch): a list of pyramids, each
+        bit-identical to from_raw's of the same frame, built in a number of kernel launches that does not depend on how many
+        frames there are.  images / depths: sequences of numpy arrays (uint8 HxW or HxWx3, uint16 HxW, all of one shape), or of
+        device pointers (ints) together with size = (width, height) and channels -- and, when the rows are not packed,
+        image_stride_bytes / depth_stride --, as from_raw_device takes them.  timestamps: one per frame, or None for 0.0.
+        selection: None, or (intensity_threshold, depth_threshold) to leave every pyramid with that point selection already
+        built, so that the first match() with those thresholds launches nothing for it."""
+        n = len(images)
+        if n < 1 or len(depths) != n or (timestamps is not None and len(timestamps) != n):
+            raise ValueError("images, depths and timestamps must name the same number of frames, at least one")
+        on_device = not isinstance(images[0], np.ndarray) and isinstance(images[0], int)
+        if on_device:
+            if size is None or channels is None:
+                raise ValueError("device pointers need size=(width, height) and channels")
+            w, h = int(size[0]), int(size[1])
+            keep, img_ptrs, z_ptrs = None, [int(p) for p in images], [int(p) for p in depths]
+        else:
+            ims = [np.ascontiguousarray(a, dtype=np.uint8) for a in images]
+            zs = [np.ascontiguousarray(a, dtype=np.uint16) for a in depths]
+            if any(a.shape != ims[0].shape for a in ims) or any(z.shape != zs[0].shape for z in zs) or zs[0].ndim != 2 or \
+                    ims[0].ndim not in (2, 3) or ims[0].shape[:2] != zs[0].shape:
+                raise ValueError("every image must be HxW or HxWx3 uint8 and every depth HxW uint16, all of one size")
+            channels = 1 if ims[0].ndim == 2 else ims[0].shape[2]
+            h, w = zs[0].shape
+            image_stride_bytes = depth_stride = None
+            keep, img_ptrs, z_ptrs = (ims, zs), [a.ctypes.data for a in ims], [z.ctypes.data for z in zs]
+        b = CRawBatch()
+        b.count = n
+        b.images, b.depths = (C.c_void_p * n)(*img_ptrs), (C.c_void_p * n)(*z_ptrs)
+        b.timestamps = None if timestamps is None else (C.c_double * n)(*[float(t) for t in timestamps])
+        b.channels, b.image_stride_bytes, b.depth_stride = channels, image_stride_bytes or w * channels, depth_stride or w
+        b.depth_scale, b.on_device, b.width, b.height = depth_scale, int(on_device), w, h
+        b.fx, b.fy, b.ox, b.oy = [float(k) for k in K]
+        b.levels, b.build_selection = levels, int(selection is not None)
+        if selection is not None:
+            b.intensity_threshold, b.depth_threshold = float(selection[0]), float(selection[1])
+        out = (C.c_void_p * n)()
+        _check(lib().dvo_amd_pyramid_create_raw_batch(device, C.byref(b), out), "dvo_amd_pyramid_create_raw_batch")
+        del keep
+        pyramids = []
+        for f in range(n):
+            self = cls.__new__(cls)
+            self._h, self.device, self.registration_stats = C.c_void_p(out[f]), device, None
+            pyramids.append(self)
+        return pyramids
 
     def __del__(self):
         h = getattr(self, "_h", None)

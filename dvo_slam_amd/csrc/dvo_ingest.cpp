@@ -2,7 +2,8 @@
 // resampled through a remap (dvo_rectify.cpp), or with its depth registered from another camera (dvo_register.cpp) -- are one
 // description (Level0Source, dvo_internal.h) and go through one driver, ingest_level0, which owns everything that is not a kernel:
 // the per-device staging area of host raw frames, the span of the device's mutex over it, and the row upload.  The five
-// dvo_amd_pyramid_create* entries stand side by side below it and check their arguments through the same helpers.
+// single-frame dvo_amd_pyramid_create* entries stand side by side below it and check their arguments through the same helpers; so does
+// the batched raw entry, whose driver (pyramid_build_batch, dvo_pyramid.cpp) stages its host frames the way ingest_raw does.
 #include "dvo_internal.h"
 
 #include <cstring>
@@ -193,6 +194,28 @@ int dvo_amd_pyramid_create_raw(int device, const unsigned char *image, int chann
                        Level0Source{nullptr, nullptr, 0, &raw, on_device != 0}, out);
 }
 
+int dvo_amd_pyramid_create_raw_batch(int device, const dvo_amd_raw_batch *batch, dvo_amd_pyramid **out) {
+  static const char *entry = "dvo_amd_pyramid_create_raw_batch";
+  if (out && batch)
+    for (int f = 0; f < batch->count; ++f) out[f] = nullptr;
+  if (!out || !batch) return invalid(entry, "a NULL pointer");
+  const dvo_amd_raw_batch &b = *batch;
+  if (b.count < 1) return invalid(entry, "count must be >= 1");
+  if (!b.images || !b.depths) return invalid(entry, "a NULL pointer");
+  for (int f = 0; f < b.count; ++f)
+    if (!b.images[f] || !b.depths[f]) return invalid(entry, "a NULL pointer at frame " + std::to_string(f) + " of images or depths");
+  const RawFrame raw{b.images[0], b.channels, b.image_stride_bytes, b.depths[0], b.depth_stride, b.depth_scale, nullptr, nullptr};
+  int rc = check_raw(entry, raw, b.width, b.width, "the image stride is smaller than the row it must hold", "depth_stride < width");
+  if (rc) return rc;
+  if (b.build_selection != 0 && b.build_selection != 1) return invalid(entry, "build_selection must be 0 or 1");
+  if (b.build_selection && !(std::isfinite(b.intensity_threshold) && std::isfinite(b.depth_threshold)))
+    return invalid(entry, "a non-finite selection threshold");
+  rc = check_levels(entry, b.width, b.height, b.levels);
+  if (!rc) rc = check_device(device, nullptr);
+  if (rc) return rc;
+  return pyramid_build_batch(device, b, out);
+}
+
 int dvo_amd_pyramid_create_raw_remapped(int device, const unsigned char *image, int channels, int image_stride_bytes,
                                         const unsigned short *depth, int depth_stride, float depth_scale, int on_device,
                                         const dvo_amd_remap *remap, float fx, float fy, float ox, float oy, int levels,
@@ -260,6 +283,12 @@ int dvo_amd_pyramid_create_raw_registered(int device, const unsigned char *image
 int dvo_amd_debug_ingest_timing(int device, int enable, double *last_ms) {
   if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
   return ingest_timing(device, enable, last_ms);
+}
+
+/* instrumentation: what the most recent batched build on `device` enqueued */
+int dvo_amd_debug_batch_build_stats(int device, int *kernel_launches, int *copies, int *synchronisations) {
+  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  return batch_build_stats(device, kernel_launches, copies, synchronisations);
 }
 
 }  // extern "C"

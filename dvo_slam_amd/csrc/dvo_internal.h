@@ -431,6 +431,10 @@ int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const Selection **
 std::mutex &device_mutex(int device);  // the mutex of the device's shared state (never held across one of the calls above)
 int pyramid_build(int device, const PyramidSpec &spec, const Level0Source &src, dvo_amd_pyramid **out);  // checked arguments
 int ingest_timing(int device, int enable, double *last_ms);  // dvo_amd_debug_ingest_timing
+// N pyramids of N raw frames of one geometry, each with its first selection when the batch asks for it, in a number of launches
+// that depends on the level count alone (checked arguments; out: b.count entries, NULL on entry and after any failure)
+int pyramid_build_batch(int device, const dvo_amd_raw_batch &b, dvo_amd_pyramid **out);
+int batch_build_stats(int device, int *kernel_launches, int *copies, int *synchronisations);  // dvo_amd_debug_batch_build_stats
 
 // ---- dvo_ingest.cpp
 // level 0's two base planes (L0.i_plane, L0.z_plane) from `src`, enqueued on `st`, the device's prep stream.  A host raw frame is

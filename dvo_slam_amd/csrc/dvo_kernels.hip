@@ -2387,4 +2387,339 @@ hipError_t launch_unpack_plane(const float4 *c_a, const float2 *c_b, int plane, 
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// pyramid construction, N frames per launch (dvo_amd_pyramid_create_raw_batch)
+// ------------------------------------------------------------------------------------------------------------------
+// The kernels above with the frame as the grid's y dimension: a frame is a row of the BatchFrame table, a level a set of offsets
+// from the frame's slab (BatchLevel).  What a pixel's thread computes -- every operation, its order, its rounding, the padding
+// values -- is the single-frame kernel's, statement for statement, so a batched pyramid is the singly built one bit for bit.
+// Only the tiling differs: these are streaming kernels, so a thread takes the i-th pixel (or group of four) of the whole
+// level in scan order instead of the x-th of row blockIdx.y, and no lane idles at a row's end (of the three 64-thread blocks
+// k_ingest gives a 640-pixel row the third is half empty, and k_pyr_down's one 256-thread block of an 80-pixel row holds 80
+// pixels; here every block but a frame's last is full).  Consecutive lanes still touch consecutive addresses.  The two
+// single-block kernels of the selection become one block per frame.
+
+constexpr unsigned kBatchGridFrames = 65535;  // gridDim.y's limit: a launcher splits a larger batch
+
+template <typename T>
+__device__ __forceinline__ T *batch_at(const BatchFrame &f, size_t offset) {
+  return (T *)(f.slab + offset);
+}
+
+// k_ingest<true>
+__global__ __launch_bounds__(256) void k_ingest_batch(const BatchFrame *__restrict__ frames, int frame0, int channels,
+                                                      int img_stride_bytes, int z_stride, float z_scale, size_t off_i, size_t off_z,
+                                                      int w, int h) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x, wq = w / 4;
+  if (q >= wq * h) return;
+  const int y = q / wq, x4 = q - y * wq;
+  const BatchFrame f = frames[frame0 + blockIdx.y];
+  float *__restrict__ i_plane = batch_at<float>(f, off_i), *__restrict__ z_plane = batch_at<float>(f, off_z);
+  const unsigned char *ip = f.img + (size_t)y * img_stride_bytes + (size_t)x4 * 4 * channels;
+  unsigned char px[12];
+  const int nb = 4 * channels;
+  if ((((size_t)ip) & 3) == 0) {
+    const unsigned *ip4 = (const unsigned *)ip;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+      if (k < channels) {
+        const unsigned v = ip4[k];
+        px[4 * k] = (unsigned char)v, px[4 * k + 1] = (unsigned char)(v >> 8), px[4 * k + 2] = (unsigned char)(v >> 16),
+               px[4 * k + 3] = (unsigned char)(v >> 24);
+      }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 12; ++k)
+      if (k < nb) px[k] = ip[k];
+  }
+  float g[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (channels == 3) {
+      const int b = px[3 * k], gg = px[3 * k + 1], r = px[3 * k + 2];
+      g[k] = (float)((b * 1868 + gg * 9617 + r * 4899 + (1 << 13)) >> 14);
+    } else {
+      g[k] = (float)px[k];
+    }
+  }
+  const size_t o = (size_t)y * w + (size_t)x4 * 4;
+  const unsigned short *zp = f.z + (size_t)y * z_stride + (size_t)x4 * 4;
+  unsigned short zr[4];
+  if ((((size_t)zp) & 7) == 0) {
+    const uint2 v = *(const uint2 *)zp;
+    zr[0] = (unsigned short)v.x, zr[1] = (unsigned short)(v.x >> 16), zr[2] = (unsigned short)v.y,
+    zr[3] = (unsigned short)(v.y >> 16);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) zr[k] = zp[k];
+  }
+  float z[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) z[k] = zr[k] == 0 ? __builtin_nanf("") : (float)zr[k] * z_scale;
+  *(float4 *)(i_plane + o) = make_float4(g[0], g[1], g[2], g[3]);
+  *(float4 *)(z_plane + o) = make_float4(z[0], z[1], z[2], z[3]);
+}
+
+// k_pyr_down
+__global__ __launch_bounds__(256) void k_pyr_down_batch(const BatchFrame *__restrict__ frames, int frame0, size_t off_ip, size_t off_zp,
+                                                        int wp, size_t off_io, size_t off_zo, int w, int h) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= w * h) return;
+  const int y = i / w, x = i - y * w;
+  const BatchFrame f = frames[frame0 + blockIdx.y];
+  const float *__restrict__ ip = batch_at<const float>(f, off_ip), *__restrict__ zp = batch_at<const float>(f, off_zp);
+  float *__restrict__ io = batch_at<float>(f, off_io), *__restrict__ zo = batch_at<float>(f, off_zo);
+  const float *r0 = ip + (size_t)(2 * y) * wp + 2 * x;
+  const float *r1 = r0 + wp;
+  io[(size_t)y * w + x] = (((r0[0] + r0[1]) + r1[0]) + r1[1]) / 4.0f;
+  zo[(size_t)y * w + x] = zp[(size_t)(2 * y) * wp + 2 * x];
+}
+
+// k_level_planes
+__global__ __launch_bounds__(256) void k_level_planes_batch(const BatchFrame *__restrict__ frames, int frame0, BatchLevel L) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int w = L.w, h = L.h, n = L.n;
+  const float fx = L.fx, fy = L.fy, ox = L.ox, oy = L.oy;
+  const BatchFrame f = frames[frame0 + blockIdx.y];
+  const float *__restrict__ ip = batch_at<const float>(f, L.i_plane), *__restrict__ zp = batch_at<const float>(f, L.z_plane);
+  float4 *__restrict__ c_a = batch_at<float4>(f, L.c_a);
+  float2 *__restrict__ c_b = batch_at<float2>(f, L.c_b);
+  float *__restrict__ r_i = batch_at<float>(f, L.r_i), *__restrict__ r_ix = batch_at<float>(f, L.r_ix),
+                     *__restrict__ r_iy = batch_at<float>(f, L.r_iy);
+  float *__restrict__ tx = batch_at<float>(f, L.tx), *__restrict__ ty = batch_at<float>(f, L.ty);
+  if (i < w) tx[i] = ((float)i - ox) / fx;
+  if (i < h) ty[i] = ((float)i - oy) / fy;
+  if (i >= L.n_pad) return;
+  if (i >= n) {
+    r_i[i] = 0.0f, r_ix[i] = 0.0f, r_iy[i] = 0.0f;
+    return;
+  }
+  const int y = i / w, x = i - y * w;
+  const int xp = x > 0 ? x - 1 : 0, xn = x < w - 1 ? x + 1 : w - 1;
+  const int yp = y > 0 ? y - 1 : 0, yn = y < h - 1 ? y + 1 : h - 1;
+  const float I = ip[i], Z = zp[i];
+  const float Ix = (ip[y * w + xn] - ip[y * w + xp]) * 0.5f;
+  const float Iy = (ip[yn * w + x] - ip[yp * w + x]) * 0.5f;
+  const float Zx = (zp[y * w + xn] - zp[y * w + xp]) * 0.5f;
+  const float Zy = (zp[yn * w + x] - zp[yp * w + x]) * 0.5f;
+  c_a[i] = make_float4(I, Z, Ix, Iy);
+  c_b[i] = make_float2(Zx, Zy);
+  r_i[i] = I, r_ix[i] = Ix, r_iy[i] = Iy;
+}
+
+// One block per frame, one thread per level: the frame's level descriptors (what pyramid_build and pyramid_selection copy from
+// the host, one small copy per pyramid) from the call's one set, whose pointers are offsets from a slab's base.
+__global__ __launch_bounds__(64) void k_batch_descs(const BatchFrame *__restrict__ frames, int frame0, BatchDescs D) {
+  const int l = threadIdx.x;
+  if (l >= D.levels) return;
+  const BatchFrame f = frames[frame0 + blockIdx.x];
+  CurLevelDesc c = D.cur[l];
+  c.c_a = batch_at<const float4>(f, (size_t)c.c_a), c.c_b = batch_at<const float2>(f, (size_t)c.c_b);
+  ((CurLevelDesc *)f.desc)[l] = c;
+  if (!D.with_ref) return;
+  RefLevelDesc r = D.ref[l];
+  r.r_zsel = batch_at<const float>(f, (size_t)r.r_zsel);
+  r.r_i = batch_at<const float>(f, (size_t)r.r_i), r.r_ix = batch_at<const float>(f, (size_t)r.r_ix),
+  r.r_iy = batch_at<const float>(f, (size_t)r.r_iy);
+  r.tx = batch_at<const float>(f, (size_t)r.tx), r.ty = batch_at<const float>(f, (size_t)r.ty);
+  ((RefLevelDesc *)(f.desc + D.ref_offset))[l] = r;
+}
+
+// k_select
+__global__ __launch_bounds__(256) void k_select_batch(const BatchFrame *__restrict__ frames, int frame0, size_t off_z, size_t off_ca,
+                                                      size_t off_cb, int n, int n_pad, float ti, float td, size_t off_zsel,
+                                                      size_t off_partials) {
+  const BatchFrame f = frames[frame0 + blockIdx.y];
+  const float *__restrict__ zp = batch_at<const float>(f, off_z);
+  const float4 *__restrict__ c_a = batch_at<const float4>(f, off_ca);
+  const float2 *__restrict__ c_b = batch_at<const float2>(f, off_cb);
+  float *__restrict__ zsel = batch_at<float>(f, off_zsel);
+  int2 *__restrict__ block_partials = batch_at<int2>(f, off_partials);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  float out = u2f(0x7fc00000u);
+  bool ok = false;
+  if (i < n) {
+    const float z = zp[i];
+    const float4 a = c_a[i];
+    const float2 b = c_b[i];
+    ok = (z == z) && (b.x == b.x) && (b.y == b.y) &&
+         (__builtin_fabsf(a.z) > ti || __builtin_fabsf(a.w) > ti || __builtin_fabsf(b.x) > td || __builtin_fabsf(b.y) > td);
+    if (ok) out = z;
+  }
+  if (i < n_pad) zsel[i] = out;
+  __shared__ int sh_cnt[4], sh_last[4];
+  const unsigned long long m = __ballot(ok);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    sh_cnt[wave] = __popcll(m);
+    sh_last[wave] = m ? (int)(blockIdx.x * blockDim.x) + wave * kWave + (63 - __builtin_clzll(m)) : -1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0, last = -1;
+    for (int w = 0; w < 4; ++w) c += sh_cnt[w], last = sh_last[w] > last ? sh_last[w] : last;
+    block_partials[blockIdx.x] = make_int2(c, last);
+  }
+}
+
+// k_select_finish, one block per frame; the two counters go to the pyramid's own slab (k_compact_batch reads them there) and to
+// the call's table, from where one copy takes every frame's to the host
+__global__ __launch_bounds__(256) void k_select_finish_batch(const BatchFrame *__restrict__ frames, int frame0, size_t off_partials,
+                                                             int n_blocks, size_t off_zsel, size_t off_counters,
+                                                             int *__restrict__ all_counters, int level, int levels) {
+  const int fi = frame0 + blockIdx.x;
+  const BatchFrame f = frames[fi];
+  const int2 *__restrict__ block_partials = batch_at<const int2>(f, off_partials);
+  float *zsel = batch_at<float>(f, off_zsel);
+  int *__restrict__ counters = batch_at<int>(f, off_counters);
+  int c = 0, last = -1;
+  for (int b = threadIdx.x; b < n_blocks; b += 256) {
+    const int2 p = block_partials[b];
+    c += p.x, last = p.y > last ? p.y : last;
+  }
+  __shared__ int sh_c[256], sh_l[256];
+  sh_c[threadIdx.x] = c, sh_l[threadIdx.x] = last;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      sh_c[threadIdx.x] += sh_c[threadIdx.x + s];
+      sh_l[threadIdx.x] = sh_l[threadIdx.x + s] > sh_l[threadIdx.x] ? sh_l[threadIdx.x + s] : sh_l[threadIdx.x];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    counters[0] = sh_c[0], counters[1] = sh_l[0];
+    int *mine = all_counters + 2 * ((size_t)fi * levels + level);
+    mine[0] = sh_c[0], mine[1] = sh_l[0];
+    if ((sh_c[0] & 1) && sh_l[0] >= 0) zsel[sh_l[0]] = u2f(0x7fc00000u);
+  }
+}
+
+// k_select_prefix, one block per frame
+__global__ __launch_bounds__(256) void k_select_prefix_batch(const BatchFrame *__restrict__ frames, int frame0, size_t off_partials,
+                                                             int n_blocks, size_t off_prefix) {
+  const BatchFrame f = frames[frame0 + blockIdx.x];
+  const int2 *__restrict__ block_partials = batch_at<const int2>(f, off_partials);
+  int *__restrict__ prefix = batch_at<int>(f, off_prefix);
+  const int chunk = (n_blocks + 255) / 256;
+  const int b0 = (int)threadIdx.x * chunk, b1 = b0 + chunk < n_blocks ? b0 + chunk : n_blocks;
+  int c = 0;
+  for (int b = b0; b < b1; ++b) c += block_partials[b].x;
+  __shared__ int sh[256];
+  sh[threadIdx.x] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int t = 0; t < 256; ++t) {
+      const int v = sh[t];
+      sh[t] = run, run += v;
+    }
+  }
+  __syncthreads();
+  int run = sh[threadIdx.x];
+  for (int b = b0; b < b1; ++b) prefix[b] = run, run += block_partials[b].x;
+}
+
+// k_compact
+__global__ __launch_bounds__(256) void k_compact_batch(const BatchFrame *__restrict__ frames, int frame0, BatchLevel L) {
+  const BatchFrame f = frames[frame0 + blockIdx.y];
+  const float *__restrict__ zsel = batch_at<const float>(f, L.zsel);
+  const float *__restrict__ r_i = batch_at<const float>(f, L.r_i), *__restrict__ r_ix = batch_at<const float>(f, L.r_ix),
+                           *__restrict__ r_iy = batch_at<const float>(f, L.r_iy);
+  const float *__restrict__ tx = batch_at<const float>(f, L.tx), *__restrict__ ty = batch_at<const float>(f, L.ty);
+  const int *__restrict__ prefix = batch_at<const int>(f, L.prefix), *__restrict__ counters = batch_at<const int>(f, L.counters);
+  float *__restrict__ cz = batch_at<float>(f, L.pts[0]), *__restrict__ ci = batch_at<float>(f, L.pts[1]),
+                     *__restrict__ cix = batch_at<float>(f, L.pts[2]), *__restrict__ ciy = batch_at<float>(f, L.pts[3]),
+                     *__restrict__ ctx = batch_at<float>(f, L.pts[4]), *__restrict__ cty = batch_at<float>(f, L.pts[5]);
+  int *__restrict__ cpix = batch_at<int>(f, L.pts[6]);
+  const int w = L.w, n = L.n, n_pad = L.n_pad;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n_pts = counters[0] & ~1;  // Q3: an odd trailing point is never looked at (its zsel entry is NaN already)
+  const float z = i < n ? zsel[i] : u2f(0x7fc00000u);
+  const bool ok = z == z;
+  const unsigned long long m = __ballot(ok);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  __shared__ int sh_cnt[4];
+  if (lane == 0) sh_cnt[wave] = __popcll(m);
+  __syncthreads();
+  int before = prefix[blockIdx.x];
+  for (int k = 0; k < wave; ++k) before += sh_cnt[k];
+  if (ok) {
+    const int p = before + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    const int row = i / w, col = i - row * w;
+    cz[p] = z, ci[p] = r_i[i], cix[p] = r_ix[i], ciy[p] = r_iy[i], ctx[p] = tx[col], cty[p] = ty[row], cpix[p] = i;
+  }
+  if (i >= n_pts && i < n_pad) cz[i] = u2f(0x7fc00000u), ci[i] = 0.0f, cix[i] = 0.0f, ciy[i] = 0.0f, ctx[i] = 0.0f, cty[i] = 0.0f, cpix[i] = -1;
+}
+
+// frames [0, count) in launches of at most kBatchGridFrames each: launch(first frame, frames of this launch)
+template <typename F>
+static hipError_t batch_launches(int count, int *launches, F launch) {
+  LaunchGuard guard;
+  for (int f0 = 0; f0 < count; f0 += (int)kBatchGridFrames) {
+    const int nf = count - f0 < (int)kBatchGridFrames ? count - f0 : (int)kBatchGridFrames;
+    launch(f0, (unsigned)nf);
+    *launches += 1;
+  }
+  return hipGetLastError();
+}
+
+static unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
+
+hipError_t launch_ingest_batch(const BatchFrame *frames, int count, int channels, int img_stride_bytes, int z_stride, float z_scale,
+                               const BatchLevel &L0, hipStream_t stream, int *launches) {
+  return batch_launches(count, launches, [&](int f0, unsigned nf) {
+    hipLaunchKernelGGL(k_ingest_batch, dim3(blocks256((long long)(L0.w / 4) * L0.h), nf), dim3(256), 0, stream, frames, f0, channels,
+                       img_stride_bytes, z_stride, z_scale, L0.i_plane, L0.z_plane, L0.w, L0.h);
+  });
+}
+
+hipError_t launch_pyr_down_batch(const BatchFrame *frames, int count, const BatchLevel &prev, const BatchLevel &L, hipStream_t stream,
+                                 int *launches) {
+  return batch_launches(count, launches, [&](int f0, unsigned nf) {
+    hipLaunchKernelGGL(k_pyr_down_batch, dim3(blocks256(L.n), nf), dim3(256), 0, stream, frames, f0, prev.i_plane, prev.z_plane, prev.w,
+                       L.i_plane, L.z_plane, L.w, L.h);
+  });
+}
+
+hipError_t launch_level_planes_batch(const BatchFrame *frames, int count, const BatchLevel &L, hipStream_t stream, int *launches) {
+  int span = L.n_pad > L.h ? L.n_pad : L.h;
+  if (L.w > span) span = L.w;
+  return batch_launches(count, launches, [&](int f0, unsigned nf) {
+    hipLaunchKernelGGL(k_level_planes_batch, dim3(blocks256(span), nf), dim3(256), 0, stream, frames, f0, L);
+  });
+}
+
+hipError_t launch_batch_descs(const BatchFrame *frames, int count, const BatchDescs &descs, hipStream_t stream, int *launches) {
+  static_assert(kBatchMaxLevels <= 64, "k_batch_descs: one thread per level");
+  return batch_launches(count, launches, [&](int f0, unsigned nf) {
+    hipLaunchKernelGGL(k_batch_descs, dim3(nf), dim3(64), 0, stream, frames, f0, descs);
+  });
+}
+
+hipError_t launch_select_batch(const BatchFrame *frames, int count, const BatchLevel &L, float ti, float td, int *all_counters,
+                               int level, int levels, hipStream_t stream, int *launches) {
+  const int n_blocks = (L.n_pad + 255) / 256;
+  hipError_t e = batch_launches(count, launches, [&](int f0, unsigned nf) {
+    hipLaunchKernelGGL(k_select_batch, dim3((unsigned)n_blocks, nf), dim3(256), 0, stream, frames, f0, L.z_plane, L.c_a, L.c_b, L.n,
+                       L.n_pad, ti, td, L.zsel, L.partials);
+  });
+  if (e != hipSuccess) return e;
+  return batch_launches(count, launches, [&](int f0, unsigned nf) {
+    hipLaunchKernelGGL(k_select_finish_batch, dim3(nf), dim3(256), 0, stream, frames, f0, L.partials, n_blocks, L.zsel, L.counters,
+                       all_counters, level, levels);
+  });
+}
+
+hipError_t launch_compact_batch(const BatchFrame *frames, int count, const BatchLevel &L, hipStream_t stream, int *launches) {
+  const int n_blocks = (L.n_pad + 255) / 256;
+  hipError_t e = batch_launches(count, launches, [&](int f0, unsigned nf) {
+    hipLaunchKernelGGL(k_select_prefix_batch, dim3(nf), dim3(256), 0, stream, frames, f0, L.partials, n_blocks, L.prefix);
+  });
+  if (e != hipSuccess) return e;
+  return batch_launches(count, launches, [&](int f0, unsigned nf) {
+    hipLaunchKernelGGL(k_compact_batch, dim3((unsigned)n_blocks, nf), dim3(256), 0, stream, frames, f0, L);
+  });
+}
+
 }  // namespace dvo_amd

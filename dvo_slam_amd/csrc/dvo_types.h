@@ -417,4 +417,41 @@ hipError_t launch_compact(const float *zsel, const float *r_i, const float *r_ix
 hipError_t launch_mask_from_zsel(const float *zsel, int n, int last_dropped, unsigned char *mask, hipStream_t stream);
 hipError_t launch_unpack_plane(const float4 *c_a, const float2 *c_b, int plane, int n, float *dst, hipStream_t stream);
 
+// ---- the batched forms of the prep kernels: N frames of one geometry share every launch (dvo_amd_pyramid_create_raw_batch)
+// One frame of a batch as the kernels find it, in a device table uploaded once per call.  Every slab of a call has the same
+// layout, so a frame is its slab's base and a level is a set of byte offsets from it that travels in the kernel arguments.
+struct BatchFrame {
+  char *slab;                  // the pyramid's slab
+  char *desc;                  // the pyramid's entry of the descriptor arena
+  const unsigned char *img;    // the raw frame in device memory (a host frame: where it was staged in the slab)
+  const unsigned short *z;
+};
+struct BatchLevel {  // byte offsets from a slab's base, and what the single-frame launchers take by value
+  size_t i_plane, z_plane, c_a, c_b, r_i, r_ix, r_iy, tx, ty;
+  size_t zsel, pts[7];                  // the first selection: its mask plane and its compacted arrays (CompactLevel's order)
+  size_t counters, partials, prefix;    // this level's two counters; the selection kernels' scratch (shared by the levels)
+  int w, h, n, n_pad;
+  float fx, fy, ox, oy;
+};
+// a pyramid's level descriptors with offsets from the slab's base in the place of pointers: k_batch_descs adds each frame's base
+constexpr int kBatchMaxLevels = 8;  // DVO_AMD_MAX_LEVELS of include/dvo_amd.h (asserted where both are seen)
+struct BatchDescs {
+  CurLevelDesc cur[kBatchMaxLevels];
+  RefLevelDesc ref[kBatchMaxLevels];
+  int levels, with_ref;
+  unsigned ref_offset;  // where the first selection's descriptors start inside a descriptor entry
+};
+// Each launcher enqueues frames [0, count) of `frames` (device) and adds the launches it made to *launches: one, or one per
+// 65 535 frames above that many (the frame is the grid's y dimension).
+hipError_t launch_ingest_batch(const BatchFrame *frames, int count, int channels, int img_stride_bytes, int z_stride, float z_scale,
+                               const BatchLevel &L0, hipStream_t stream, int *launches);
+hipError_t launch_pyr_down_batch(const BatchFrame *frames, int count, const BatchLevel &prev, const BatchLevel &L, hipStream_t stream,
+                                 int *launches);
+hipError_t launch_level_planes_batch(const BatchFrame *frames, int count, const BatchLevel &L, hipStream_t stream, int *launches);
+hipError_t launch_batch_descs(const BatchFrame *frames, int count, const BatchDescs &descs, hipStream_t stream, int *launches);
+// all_counters (device): 2 ints per (frame, level), frame-major, next to the copy each pyramid keeps in its slab
+hipError_t launch_select_batch(const BatchFrame *frames, int count, const BatchLevel &L, float ti, float td, int *all_counters,
+                               int level, int levels, hipStream_t stream, int *launches);
+hipError_t launch_compact_batch(const BatchFrame *frames, int count, const BatchLevel &L, hipStream_t stream, int *launches);
+
 }  // namespace dvo_amd

@@ -123,6 +123,19 @@ def load(K, rgb_file: str, depth_file: str, levels: int, device: int = 0, timest
                                           remap=remap)
 
 
+def load_batch(entries, K, levels: int, device: int = 0, base: str = "", depth_scale: float = TUM_DEPTH_SCALE, selection=None):
+    """load() for several entries of an association file (RgbdPair: RgbFile, DepthFile, RgbTimestamp; file names relative to
+    `base`) in ONE pyramid build (capi.RgbdImagePyramid.from_raw_batch): the PNGs are decoded on the host one after the other,
+    then every frame's conversions and pyramid share the same few kernel launches.  Returns the pyramids in the entries' order,
+    each with its entry's RgbTimestamp, each what load() makes of that entry.  selection: None, or (intensity_threshold,
+    depth_threshold) -- a tracker's two derivative thresholds -- to have every pyramid's point selection built in the same call.
+    Resampling through a remap stays with load()."""
+    bgr = [imread_color(os.path.join(base, p.RgbFile)) for p in entries]
+    depth = [imread_depth(os.path.join(base, p.DepthFile)) for p in entries]
+    return capi.RgbdImagePyramid.from_raw_batch(bgr, depth, K, levels, depth_scale=depth_scale, device=device,
+                                                timestamps=[p.RgbTimestamp for p in entries], selection=selection)
+
+
 def format_trajectory_line(timestamp: float, T) -> str:
     """One line of the estimated trajectory as benchmark_slam.cpp:490-504 prints it (including the trailing blank)."""
     Tc = np.ascontiguousarray(np.asarray(T, dtype=np.float64).T)

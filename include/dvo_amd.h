@@ -203,6 +203,41 @@ int dvo_amd_pyramid_create_raw(int device, const unsigned char *image, int chann
                                dvo_amd_pyramid **out);
 
 /*
+ * Many pyramids in one call: dvo_amd_pyramid_create_raw for `count` raw frames that share one geometry, one set of intrinsics
+ * and one level count (a caller with several cameras makes one call per camera), optionally with each pyramid's first point
+ * selection.  One frame at a time costs about two dozen dependent kernel launches, three small copies and two host
+ * synchronisations, and the launch chain, not the pixel work, sets the rate; here the frames share every launch -- the number of
+ * launches of a call depends on `levels` alone -- and the call synchronises once, at its end.
+ *   images, depths : `count` pointers each, to frames laid out as dvo_amd_pyramid_create_raw's; all in host memory
+ *                    (on_device == 0) or all in device memory on `device`
+ *   timestamps     : `count` values, or NULL for 0.0
+ *   build_selection: 1 = every pyramid leaves the call with the selection for (intensity_threshold, depth_threshold) in its
+ *                    cache, exactly as the first dvo_amd_pyramid_select / match with those thresholds would have built it
+ *                    (a later match with them builds nothing); 0 = selections are built on first use, as ever
+ * The results are `count` ordinary pyramids -- refcounted, immutable, released one by one, accepted by every entry -- and
+ * bit-identical, selection included, to the ones dvo_amd_pyramid_create_raw makes from the same frames.
+ * DVO_AMD_ERR_INVALID_ARGUMENT (all before DVO_AMD_ERR_NO_DEVICE, with a sentence in dvo_amd_last_error()): count < 1; a NULL
+ * pointer, in either array too; everything dvo_amd_pyramid_create_raw rejects; build_selection outside {0, 1}; with
+ * build_selection, a non-finite threshold.  After any failure every one of the `count` entries of `out` is NULL and nothing of
+ * the call is left on the device's pools' books.
+ */
+typedef struct dvo_amd_raw_batch {
+  int count;                               /* frames, >= 1 */
+  const unsigned char *const *images;      /* count pointers, uint8 grey or BGR */
+  const unsigned short *const *depths;     /* count pointers, uint16 */
+  const double *timestamps;                /* count values, or NULL for 0.0 */
+  int channels, image_stride_bytes, depth_stride;
+  float depth_scale;
+  int on_device;                           /* all frames in host, or all in device memory */
+  int width, height;
+  float fx, fy, ox, oy;
+  int levels;
+  int build_selection;                     /* 0 or 1 */
+  float intensity_threshold, depth_threshold;   /* used when build_selection != 0 */
+} dvo_amd_raw_batch;
+int dvo_amd_pyramid_create_raw_batch(int device, const dvo_amd_raw_batch *batch, dvo_amd_pyramid **out /* count entries */);
+
+/*
  * Rectification at ingest: remap tables on the device and a frame ingest that resamples through one.
  *
  * The reference assumes a rectified image: camera_keyframe_tracking.cpp:89 builds its intrinsics from CameraInfo::P, the

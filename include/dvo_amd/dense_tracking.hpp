@@ -284,6 +284,42 @@ class RgbdImagePyramid {
   RgbdImagePyramid(dvo_amd_pyramid *adopted, int width, int height, const IntrinsicMatrix &K, int device, double timestamp)
       : width_(width), height_(height), K_(K), device_(device), timestamp_(timestamp), handle_(adopted),
         levels_(dvo_amd_pyramid_levels(adopted)) {}
+  // (not in the reference) the raw frames of one camera -- uint8 grey or B,G,R, uint16 depth with 0 = no measurement -- as
+  // `levels`-level pyramids built in ONE call (dvo_amd_pyramid_create_raw_batch): the frames share every kernel launch, so a
+  // recorded sequence or a burst of frames costs a few dozen launches instead of a few dozen per frame.  A stride of 0 means
+  // packed rows; timestamps: one per frame, or null for 0.0.  With with_selection every pyramid leaves the call with the point
+  // selection for the two thresholds already built (pass DenseTracker::Config's IntensityDerivativeThreshold and
+  // DepthDerivativeThreshold: the first match() then builds none).  Each result is what the single-frame raw create makes.
+  static std::vector<Ptr> createRawBatch(int width, int height, const IntrinsicMatrix &K, const std::vector<const unsigned char *> &images,
+                                         int channels, int image_stride_bytes, const std::vector<const unsigned short *> &depths,
+                                         int depth_stride, float depth_scale, int levels, const double *timestamps = nullptr,
+                                         bool with_selection = false, float intensity_threshold = 0.0f, float depth_threshold = 0.0f,
+                                         int device = 0, bool on_device = false) {
+    if (images.empty() || images.size() != depths.size()) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "RgbdImagePyramid::createRawBatch");
+    dvo_amd_raw_batch b;
+    std::memset(&b, 0, sizeof(b));
+    b.count = (int)images.size(), b.images = images.data(), b.depths = depths.data(), b.timestamps = timestamps;
+    b.channels = channels, b.image_stride_bytes = image_stride_bytes ? image_stride_bytes : width * channels;
+    b.depth_stride = depth_stride ? depth_stride : width, b.depth_scale = depth_scale, b.on_device = on_device ? 1 : 0;
+    b.width = width, b.height = height, b.fx = K.fx(), b.fy = K.fy(), b.ox = K.ox(), b.oy = K.oy(), b.levels = levels;
+    b.build_selection = with_selection ? 1 : 0, b.intensity_threshold = intensity_threshold, b.depth_threshold = depth_threshold;
+    std::vector<dvo_amd_pyramid *> handles(images.size(), nullptr);
+    detail::check(dvo_amd_pyramid_create_raw_batch(device, &b, handles.data()), "RgbdImagePyramid::createRawBatch");
+    std::vector<Ptr> out;
+    size_t adopted = 0;
+    try {
+      out.reserve(handles.size());
+      for (; adopted < handles.size(); ++adopted) {
+        RgbdImagePyramid *p = new RgbdImagePyramid(handles[adopted], width, height, K, device, timestamps ? timestamps[adopted] : 0.0);
+        handles[adopted] = nullptr;  // p owns it now (releasing NULL is a no-op)
+        out.push_back(Ptr(p));
+      }
+    } catch (...) {
+      for (size_t f = adopted; f < handles.size(); ++f) dvo_amd_pyramid_release(handles[f]);
+      throw;
+    }
+    return out;
+  }
   ~RgbdImagePyramid() { dvo_amd_pyramid_release(handle_); }
   RgbdImagePyramid(const RgbdImagePyramid &) = delete;
   RgbdImagePyramid &operator=(const RgbdImagePyramid &) = delete;

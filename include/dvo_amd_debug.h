@@ -222,10 +222,16 @@ int dvo_amd_debug_graph_symbolic(int n_vertices, const int *fixed, int n_edges, 
 int dvo_amd_debug_graph_sparse_timing(dvo_amd_context *ctx, double *symbolic_ms, double *linearise_ms, double *factorize_ms,
                                       double *solve_ms, int *fronts, int *levels, int *widest, double *factor_doubles,
                                       double *flops);
-/* with enable != 0 every later pyramid build on `device` (any dvo_amd_pyramid_create* entry) is bracketed by two events on the
- * device's internal stream; *last_ms (may be NULL) receives the device time of the most recent bracketed build: uploads,
- * ingest or remap, every level's planes */
+/* with enable != 0 every later pyramid build on `device` (any dvo_amd_pyramid_create* entry, the batched one as a whole) and
+ * every later build of a point selection (the first dvo_amd_pyramid_select or match with a threshold pair; a selection found in
+ * the pyramid's cache builds nothing and leaves the figure alone) is bracketed by two events on the device's internal stream;
+ * *last_ms (may be NULL) receives the device time of the most recent bracketed build: uploads, ingest or remap, every level's
+ * planes -- or a selection's kernels and its counter copy */
 int dvo_amd_debug_ingest_timing(int device, int enable, double *last_ms);
+/* what the most recent successful dvo_amd_pyramid_create_raw_batch on `device` enqueued: kernel launches (a function of the
+ * level count and of build_selection alone, whatever the frame count), copies (two per host frame, the frame table, the
+ * counters) and host synchronisations (one).  Any output may be NULL; all zero before the first such call */
+int dvo_amd_debug_batch_build_stats(int device, int *kernel_launches, int *copies, int *synchronisations);
 
 #ifdef __cplusplus
 }
