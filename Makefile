@@ -10,7 +10,7 @@ all: $(LIB)
 CPP := $(SRC)/dvo_kernels.hip $(SRC)/dvo_pyramid.cpp $(SRC)/dvo_tracker.cpp $(SRC)/dvo_sharded.cpp $(SRC)/dvo_probes.cpp \
        $(SRC)/dvo_validator.cpp $(SRC)/dvo_frontend.cpp $(SRC)/dvo_tum.cpp $(SRC)/dvo_map.cpp $(SRC)/dvo_graph.cpp \
        $(SRC)/dvo_graph_batch.cpp $(SRC)/dvo_covisibility.cpp $(SRC)/dvo_rectify.cpp $(SRC)/dvo_register.cpp \
-       $(SRC)/dvo_ingest.cpp
+       $(SRC)/dvo_ingest.cpp $(SRC)/dvo_mask.cpp
 
 $(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_graph_device.h $(SRC)/dvo_graph_host.h \
         include/dvo_amd.h include/dvo_amd_debug.h

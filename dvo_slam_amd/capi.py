@@ -50,6 +50,8 @@ EXPORTS = [
     "dvo_amd_remap_download", "dvo_amd_pyramid_create_raw_remapped", "dvo_amd_debug_ingest_timing",
     "dvo_amd_default_registration", "dvo_amd_pyramid_create_raw_registered",
     "dvo_amd_pyramid_create_raw_batch", "dvo_amd_debug_batch_build_stats",
+    "dvo_amd_mask_create", "dvo_amd_mask_create_levels", "dvo_amd_mask_retain", "dvo_amd_mask_release", "dvo_amd_mask_info",
+    "dvo_amd_mask_download", "dvo_amd_pyramid_select_masked", "dvo_amd_match_masked", "dvo_amd_match_many_masked",
 ]
 
 
@@ -313,6 +315,17 @@ def lib():
                                                         C.POINTER(CRegistrationStats)]
     L.dvo_amd_pyramid_create_raw_batch.argtypes = [C.c_int, C.POINTER(CRawBatch), C.POINTER(vp)]
     L.dvo_amd_debug_batch_build_stats.argtypes = [C.c_int, ip, ip, ip]
+    L.dvo_amd_mask_create.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+    L.dvo_amd_mask_create_levels.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp), ip, C.c_int, C.POINTER(vp)]
+    L.dvo_amd_mask_retain.argtypes = [vp]
+    L.dvo_amd_mask_retain.restype = None
+    L.dvo_amd_mask_release.argtypes = [vp]
+    L.dvo_amd_mask_release.restype = None
+    L.dvo_amd_mask_info.argtypes = [vp, ip, ip, ip, C.POINTER(C.c_longlong)]
+    L.dvo_amd_mask_download.argtypes = [vp, C.c_int, C.POINTER(C.c_ubyte)]
+    L.dvo_amd_pyramid_select_masked.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, C.POINTER(C.c_int), C.POINTER(C.c_ubyte)]
+    L.dvo_amd_match_masked.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, dp, C.POINTER(CResult)]
+    L.dvo_amd_match_many_masked.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(CResult), C.c_int]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -461,6 +474,91 @@ class Remap:
         mx, my = np.empty((i["height"], i["width"]), np.float32), np.empty((i["height"], i["width"]), np.float32)
         _check(lib().dvo_amd_remap_download(self._h, _fp(mx), _fp(my)), "dvo_amd_remap_download")
         return mx, my
+
+
+def _mask_bytes(a):
+    """a mask plane as contiguous uint8 (bytes as they are: the library normalises; anything else by != 0)"""
+    a = np.asarray(a)
+    return np.ascontiguousarray(a if a.dtype == np.uint8 else a != 0, dtype=np.uint8)
+
+
+MASK_ALL, MASK_ANY = 0, 1
+MAX_MASKED_SELECTIONS = 8
+
+
+class SelectionMask:
+    """A dvo_amd_mask: which reference pixels may take part in an alignment, as a device-resident pyramid of byte planes (1 = keep,
+    0 = drop) -- the device form of a user-defined PointSelectionPredicate.  `RgbdImagePyramid.select(..., mask=)`,
+    `DenseTracker.match(..., mask=)` and `DenseTracker.match_batch(..., masks=)` take one.  Immutable, shareable between trackers
+    and threads; a selection built behind it outlives it.  The rules are pinned in include/dvo_amd.h."""
+
+    def __init__(self):
+        raise TypeError("use SelectionMask.from_level0 or SelectionMask.from_levels")
+
+    @classmethod
+    def from_level0(cls, mask0, levels: int, rule: int = MASK_ALL, device: int = 0):
+        """mask0: [h, w] bytes or bools of level 0 (non-zero = keep); levels 1..levels-1 are derived on the device, a pixel kept iff
+        all (MASK_ALL) or any (MASK_ANY) of the four pixels under it are kept."""
+        m = _mask_bytes(mask0)
+        if m.ndim != 2:
+            raise ValueError("mask0 must be a 2-D array")
+        h, w = m.shape
+        return cls._level0(m.ctypes.data, w, h, w, levels, rule, 0, device)
+
+    @classmethod
+    def from_level0_device(cls, d_mask0: int, width: int, height: int, levels: int, rule: int = MASK_ALL, device: int = 0,
+                           stride: int | None = None):
+        """As from_level0, for a byte plane already resident in HBM (a raw device pointer, e.g. torch.Tensor.data_ptr() of a
+        segmentation network's uint8 output)."""
+        return cls._level0(d_mask0, width, height, width if stride is None else stride, levels, rule, 1, device)
+
+    @classmethod
+    def _level0(cls, ptr, w, h, stride, levels, rule, on_device, device):
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        _check(lib().dvo_amd_mask_create(device, w, h, levels, C.c_void_p(ptr), stride, on_device, int(rule), C.byref(self._h)),
+               "dvo_amd_mask_create")
+        self.device = device
+        return self
+
+    @classmethod
+    def from_levels(cls, planes, device: int = 0):
+        """planes: one [h >> l, w >> l] array of bytes or bools per level, every level given (what a per-level predicate needs)"""
+        ps = [_mask_bytes(p) for p in planes]
+        if not ps or any(p.ndim != 2 for p in ps):
+            raise ValueError("one 2-D array per level")
+        h, w = ps[0].shape
+        n = len(ps)
+        ptrs = (C.c_void_p * n)(*[p.ctypes.data for p in ps])
+        strides = (C.c_int * n)(*[p.shape[1] for p in ps])
+        for l, p in enumerate(ps):
+            if p.shape != (h >> l, w >> l):
+                raise ValueError(f"level {l} must be {(h >> l, w >> l)}, not {p.shape}")
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        _check(lib().dvo_amd_mask_create_levels(device, w, h, n, ptrs, strides, 0, C.byref(self._h)), "dvo_amd_mask_create_levels")
+        self.device = device
+        return self
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().dvo_amd_mask_release(h)
+            self._h = None
+
+    def info(self) -> dict:
+        """{"width", "height", "levels", "kept"}: kept[l] = the kept pixels of level l"""
+        w, h, n = C.c_int(), C.c_int(), C.c_int()
+        kept = (C.c_longlong * MAX_LEVELS)()
+        _check(lib().dvo_amd_mask_info(self._h, C.byref(w), C.byref(h), C.byref(n), kept), "dvo_amd_mask_info")
+        return {"width": w.value, "height": h.value, "levels": n.value, "kept": [int(kept[l]) for l in range(n.value)]}
+
+    def download(self, level: int) -> np.ndarray:
+        """the plane of a level, uint8 [h >> level, w >> level] of 0 / 1"""
+        i = self.info()
+        out = np.empty((i["height"] >> level, i["width"] >> level), np.uint8)
+        _check(lib().dvo_amd_mask_download(self._h, level, out.ctypes.data_as(C.POINTER(C.c_ubyte))), "dvo_amd_mask_download")
+        return out
 
 
 @dataclasses.dataclass
@@ -682,14 +780,19 @@ class RgbdImagePyramid:
         _check(lib().dvo_amd_pyramid_download_plane(self._h, level, plane, _fp(out)), "download_plane")
         return out
 
-    def select(self, level: int, ti: float = 0.0, td: float = 0.0):
-        """PointSelection::select: (count, mask[h, w])."""
+    def select(self, level: int, ti: float = 0.0, td: float = 0.0, mask: "SelectionMask | None" = None):
+        """PointSelection::select: (count, mask[h, w]).  With `mask` (a SelectionMask) a pixel is selected iff the mask keeps it
+        and the threshold predicate does (dvo_amd_pyramid_select_masked)."""
         w, h, _ = self.level_info(level)
-        mask = np.empty((h, w), np.uint8)
+        out = np.empty((h, w), np.uint8)
         cnt = C.c_int()
+        if mask is not None:
+            _check(lib().dvo_amd_pyramid_select_masked(self._h, level, ti, td, mask._h, C.byref(cnt),
+                                                       out.ctypes.data_as(C.POINTER(C.c_ubyte))), "pyramid_select_masked")
+            return cnt.value, out
         _check(lib().dvo_amd_pyramid_select(self._h, level, ti, td, C.byref(cnt),
-                                            mask.ctypes.data_as(C.POINTER(C.c_ubyte))), "pyramid_select")
-        return cnt.value, mask
+                                            out.ctypes.data_as(C.POINTER(C.c_ubyte))), "pyramid_select")
+        return cnt.value, out
 
 
     def point_cloud(self, pose=None, bgr=None, level: int = 0, tracker: "DenseTracker | None" = None):
@@ -902,13 +1005,21 @@ class DenseTracker:
             res[i].iterations_capacity = cap
         return res, its
 
-    def match(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, T_init=None) -> Result:
+    def match(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, T_init=None, mask: "SelectionMask | None" = None,
+              thresholds=None) -> Result:
+        """mask: only the reference pixels it keeps take part; thresholds = (intensity, depth): the selection thresholds of this
+        call instead of the configuration's (dvo_amd_match_masked; with thresholds alone, dvo_amd_match_selection)"""
         res, its = self._alloc_results(1)
         T0 = None
         if T_init is not None:
             T0a = np.ascontiguousarray(np.asarray(T_init, dtype=np.float64).T)
             T0 = T0a.ctypes.data_as(C.POINTER(C.c_double))
-        _check(lib().dvo_amd_match(self._h, reference._h, current._h, T0, C.byref(res[0])), "dvo_amd_match")
+        if mask is None and thresholds is None:
+            _check(lib().dvo_amd_match(self._h, reference._h, current._h, T0, C.byref(res[0])), "dvo_amd_match")
+            return Result(res[0], its[0])
+        ti, td = thresholds if thresholds is not None else (self._cfg.IntensityDerivativeThreshold, self._cfg.DepthDerivativeThreshold)
+        _check(lib().dvo_amd_match_masked(self._h, reference._h, None if mask is None else mask._h, ti, td, current._h, T0,
+                                          C.byref(res[0])), "dvo_amd_match_masked")
         return Result(res[0], its[0])
 
     def alloc_results(self, n):
@@ -916,11 +1027,12 @@ class DenseTracker:
         return self._alloc_results(n)
 
     def match_batch(self, references, currents, T_inits=None, stats: bool = True, in_flight: int = 0, raw: bool = False,
-                    results=None):
+                    results=None, masks=None):
         """n independent match() calls on this tracker's GPU.  in_flight = 0: all advanced in lock step; otherwise at most
         in_flight pairs are resident and a finished pair hands its slot to the next one.  raw=True returns the array of C
         result structs as the library filled them (no per-pair Python objects: for throughput loops).  results: a pair from
-        alloc_results(n) to fill (per-iteration statistics included) instead of allocating new ones."""
+        alloc_results(n) to fill (per-iteration statistics included) instead of allocating new ones.  masks: one SelectionMask
+        or None per pair (dvo_amd_match_many_masked)."""
         n = len(references)
         assert len(currents) == n
         if results is not None:
@@ -935,7 +1047,12 @@ class DenseTracker:
         if T_inits is not None:
             T0a = np.ascontiguousarray(np.stack([np.asarray(T, dtype=np.float64).T for T in T_inits]))
             T0 = T0a.ctypes.data_as(C.POINTER(C.c_double))
-        _check(lib().dvo_amd_match_many(self._h, n, refs, curs, T0, res, in_flight), "dvo_amd_match_many")
+        if masks is not None:
+            assert len(masks) == n
+            ms = (C.c_void_p * n)(*[None if m is None else m._h for m in masks])
+            _check(lib().dvo_amd_match_many_masked(self._h, n, refs, ms, curs, T0, res, in_flight), "dvo_amd_match_many_masked")
+        else:
+            _check(lib().dvo_amd_match_many(self._h, n, refs, curs, T0, res, in_flight), "dvo_amd_match_many")
         if raw:
             res._keepalive = its  # the iteration arrays the structs point into
             return res

@@ -10,6 +10,7 @@
 //   dvo_graph.cpp     the pose-graph optimizer: edge linearisation, dense fp64 Cholesky, Levenberg-Marquardt and dogleg
 //   dvo_graph_batch.cpp  many small pose graphs in one launch: one workgroup per graph, the whole optimization on the device
 //   dvo_rectify.cpp   remap tables (lens undistortion, arbitrary maps) and the kernels that resample a frame through one
+//   dvo_mask.cpp      selection masks: the device-resident mask pyramid behind a masked point selection
 //   dvo_register.cpp  depth-to-colour registration: the kernels that splat another camera's raw depth into level 0's depth plane
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
@@ -88,6 +89,7 @@ struct CompactLevel {
 constexpr size_t kCompactBytesPerPoint = 7 * sizeof(float);
 struct Selection {
   float ti, td;
+  unsigned long long mask_serial = 0;  // the serial of the mask the selection was built behind (0: none): third part of the cache key
   float *zsel[DVO_AMD_MAX_LEVELS];        // pixel space: depth where selected, NaN elsewhere (the mask; the source of the compaction)
   CompactLevel pts[DVO_AMD_MAX_LEVELS];   // what the residual pass reads
   int count[DVO_AMD_MAX_LEVELS];  // PointSelection size (includes an odd trailing point)
@@ -141,6 +143,18 @@ struct dvo_amd_remap {
   void *mem = nullptr;                        // one allocation: the two planes and the counter
   float *map_x = nullptr, *map_y = nullptr;   // device, [w * h] each, 256-byte aligned
   int *counter = nullptr;                     // device: where the kernels count n_inside
+};
+
+// one selection mask (dvo_mask.cpp): immutable after create, refcounted, shareable between contexts and threads
+struct dvo_amd_mask {
+  std::atomic<int> refs{1};
+  int device = 0;
+  int w = 0, h = 0, levels = 0;  // level l is (w >> l) x (h >> l), as a pyramid's
+  unsigned long long serial = 0;  // process-wide, never 0, never reused: the mask's identity in selection caches
+  void *mem = nullptr;            // one allocation: the planes and the counters
+  unsigned char *plane[DVO_AMD_MAX_LEVELS] = {};  // device, row-major, 0 / 1, 256-byte aligned
+  int *counters = nullptr;                        // device, [levels]: where the kernels count the kept pixels
+  long long kept[DVO_AMD_MAX_LEVELS] = {};
 };
 
 // a raw sensor frame (frame ingest on the device)
@@ -392,6 +406,7 @@ struct Pending {
   bool has_init = false;
   double T_init[16];
   float ti = 0.0f, td = 0.0f;  // the point-selection thresholds of the configuration the pair was submitted under
+  dvo_amd_mask *mask = nullptr;  // the pair's selection mask (null: none), retained until the pair's selection has been resolved
 };
 struct Batch {
   unsigned long long id = 0;
@@ -427,7 +442,14 @@ int slab_alloc(int device, size_t bytes, void **out);
 int desc_alloc(int device, void **out);
 void desc_free(int device, void *p);
 void slab_free(int device, size_t bytes, void *p);
-int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const Selection **out);
+// the selection of `p` for (ti, td, mask): mask == nullptr is the unmasked selection.  mask_fits first (it needs no device)
+int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const dvo_amd_mask *mask, const Selection **out);
+inline int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const Selection **out) {
+  return pyramid_selection(p, ti, td, nullptr, out);
+}
+// may `mask` select on `p`: DVO_AMD_ERR_INVALID_ARGUMENT for another level-0 size or fewer levels than the pyramid has, then
+// DVO_AMD_ERR_DEVICE_MISMATCH (a null mask fits every pyramid)
+int mask_fits(const char *entry, const dvo_amd_pyramid *p, const dvo_amd_mask *mask);
 std::mutex &device_mutex(int device);  // the mutex of the device's shared state (never held across one of the calls above)
 int pyramid_build(int device, const PyramidSpec &spec, const Level0Source &src, dvo_amd_pyramid **out);  // checked arguments
 int ingest_timing(int device, int enable, double *last_ms);  // dvo_amd_debug_ingest_timing

@@ -2200,6 +2200,99 @@ hipError_t launch_select(const float *z_plane, const float4 *c_a, const float2 *
   return hipGetLastError();
 }
 
+// k_select behind a selection mask (dvo_amd_mask, dvo_mask.cpp): keep = mask[i] != 0 && the threshold predicate.  The mask is a
+// byte plane of the level in scan order, so a wave's 64 bytes are one coalesced load next to the 36 bytes per pixel k_select
+// streams anyway.  Same zsel, same {count, last index} partials, one writer per pixel and no atomics: k_select_finish,
+// k_select_prefix and k_compact run behind it unchanged, and the result cannot depend on the launch geometry.  A kernel of its
+// own and not a template of k_select, so that the unmasked kernel stays the code it was.
+__global__ __launch_bounds__(256) void k_select_masked(const float *__restrict__ zp, const float4 *__restrict__ c_a,
+                                                       const float2 *__restrict__ c_b, const unsigned char *__restrict__ mask, int n,
+                                                       int n_pad, float ti, float td, float *__restrict__ zsel,
+                                                       int2 *__restrict__ block_partials) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  float out = u2f(0x7fc00000u);
+  bool ok = false;
+  if (i < n) {
+    const unsigned char keep = mask[i];
+    const float z = zp[i];
+    const float4 a = c_a[i];
+    const float2 b = c_b[i];
+    ok = keep != 0 && (z == z) && (b.x == b.x) && (b.y == b.y) &&
+         (__builtin_fabsf(a.z) > ti || __builtin_fabsf(a.w) > ti || __builtin_fabsf(b.x) > td || __builtin_fabsf(b.y) > td);
+    if (ok) out = z;
+  }
+  if (i < n_pad) zsel[i] = out;
+  __shared__ int sh_cnt[4], sh_last[4];
+  const unsigned long long m = __ballot(ok);
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  if (lane == 0) {
+    sh_cnt[wave] = __popcll(m);
+    sh_last[wave] = m ? (int)(blockIdx.x * blockDim.x) + wave * kWave + (63 - __builtin_clzll(m)) : -1;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0, last = -1;
+    for (int w = 0; w < 4; ++w) c += sh_cnt[w], last = sh_last[w] > last ? sh_last[w] : last;
+    block_partials[blockIdx.x] = make_int2(c, last);
+  }
+}
+
+hipError_t launch_select_masked(const float *z_plane, const float4 *c_a, const float2 *c_b, const unsigned char *mask, int n, int n_pad,
+                                float ti, float td, float *zsel, int *counters, int2 *block_partials, hipStream_t stream) {
+  LaunchGuard guard;
+  const int n_blocks = (n_pad + 255) / 256;
+  hipLaunchKernelGGL(k_select_masked, dim3((unsigned)n_blocks), dim3(256), 0, stream, z_plane, c_a, c_b, mask, n, n_pad, ti, td, zsel,
+                     block_partials);
+  hipLaunchKernelGGL(k_select_finish, dim3(1), dim3(256), 0, stream, (const int2 *)block_partials, n_blocks, zsel, counters);
+  return hipGetLastError();
+}
+
+// The planes of a selection mask (dvo_mask.cpp).  k_mask_plane: a level as the caller gave it (rows of `stride` bytes) into the
+// mask's own packed plane, any non-zero byte as 1; src == dst with stride == w normalises a plane in place (every byte is read
+// and written by the same lane).  k_mask_down: level l + 1 from the normalised level l, kept iff all (any_rule == 0) or any
+// (any_rule != 0) of the four pixels under it are kept; an odd trailing row or column of the parent has no child, as in
+// k_pyr_down.  Both count the kept pixels of the plane they write: one integer atomic per wave (ballots), as k_count_inside.
+__global__ __launch_bounds__(256) void k_mask_plane(const unsigned char *src, int stride, unsigned char *dst, int w, int h,
+                                                    int *__restrict__ kept) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  bool keep = false;  // (no early return: every lane takes part in the ballot)
+  if (x < w && y < h) {
+    keep = src[(size_t)y * stride + x] != 0;
+    dst[(size_t)y * w + x] = keep ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(keep);
+  if ((threadIdx.x & (kWave - 1)) == 0 && m) atomicAdd(kept, __popcll(m));
+}
+
+__global__ __launch_bounds__(256) void k_mask_down(const unsigned char *__restrict__ mp, int wp, unsigned char *__restrict__ mo, int w,
+                                                   int h, int any_rule, int *__restrict__ kept) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  bool keep = false;
+  if (x < w && y < h) {
+    // 2 * x is even and the parent's rows are a multiple of 4 bytes long in a 256-byte aligned plane: two aligned 2-byte loads
+    const unsigned char *r0 = mp + (size_t)(2 * y) * wp + 2 * x;
+    const unsigned a = *(const unsigned short *)r0, b = *(const unsigned short *)(r0 + wp);
+    keep = any_rule ? (a | b) != 0u : (a & b) == 0x0101u;
+    mo[(size_t)y * w + x] = keep ? 1 : 0;
+  }
+  const unsigned long long m = __ballot(keep);
+  if ((threadIdx.x & (kWave - 1)) == 0 && m) atomicAdd(kept, __popcll(m));
+}
+
+hipError_t launch_mask_plane(const unsigned char *src, int stride, unsigned char *dst, int w, int h, int *kept, hipStream_t stream) {
+  LaunchGuard guard;
+  hipLaunchKernelGGL(k_mask_plane, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, stream, src, stride, dst, w, h, kept);
+  return hipGetLastError();
+}
+
+hipError_t launch_mask_down(const unsigned char *m_prev, int w_prev, unsigned char *m_out, int w, int h, int any_rule, int *kept,
+                            hipStream_t stream) {
+  LaunchGuard guard;
+  hipLaunchKernelGGL(k_mask_down, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, stream, m_prev, w_prev, m_out, w, h,
+                     any_rule, kept);
+  return hipGetLastError();
+}
+
 // The selected pixels of a level in scan order, compacted (round 5, end): what the residual pass walks.  The reference compacts
 // too -- PointSelection::select fills a dense array of the selected points (point_selection.cpp:119-152) and computeResidualsSse
 // walks that array -- so the pass's cost follows the selection, not the image.  One exclusive prefix over k_select's per-block

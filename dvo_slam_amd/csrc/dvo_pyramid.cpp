@@ -287,20 +287,44 @@ static void ref_level_descs(const dvo_amd_pyramid *p, const Selection &s, RefLev
 
 // PointSelection::select for every level, cached per threshold pair (the reference caches per PointSelection object until
 // setRgbdImagePyramid, point_selection.cpp:51-59,100; pyramids are immutable here, so the cache never goes stale)
-int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const Selection **out) {
+// A selection mask (dvo_mask.cpp) is the third part of the key, by its serial (0: no mask): a released mask's address may come
+// back, its serial never does.  The selection holds planes, not the mask: once built it stays valid for the life of the pyramid
+// whatever becomes of the mask.  At most DVO_AMD_MAX_MASKED_SELECTIONS masked selections per pyramid; unmasked ones are not counted.
+int mask_fits(const char *entry, const dvo_amd_pyramid *p, const dvo_amd_mask *mask) {
+  if (!mask) return DVO_AMD_OK;
+  if (mask->w != p->lv[0].w || mask->h != p->lv[0].h)
+    return invalid(entry, "the mask is " + std::to_string(mask->w) + "x" + std::to_string(mask->h) + " but the pyramid is " +
+                              std::to_string(p->lv[0].w) + "x" + std::to_string(p->lv[0].h));
+  if (mask->levels < p->n_levels)
+    return invalid(entry, "the mask has " + std::to_string(mask->levels) + " levels but the pyramid has " + std::to_string(p->n_levels));
+  if (mask->device != p->device) return DVO_AMD_ERR_DEVICE_MISMATCH;
+  return DVO_AMD_OK;
+}
+
+int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const dvo_amd_mask *mask, const Selection **out) {
+  int rc = mask_fits("point selection", p, mask);
+  if (rc) return rc;
+  const unsigned long long serial = mask ? mask->serial : 0ull;
   std::lock_guard<std::mutex> lk(p->mu);
-  for (size_t i = 0; i < p->selections.size(); ++i)
-    if (p->selections[i]->ti == ti && p->selections[i]->td == td) {
+  int masked = 0;
+  for (size_t i = 0; i < p->selections.size(); ++i) {
+    if (p->selections[i]->ti == ti && p->selections[i]->td == td && p->selections[i]->mask_serial == serial) {
       *out = p->selections[i].get();
       return DVO_AMD_OK;
     }
+    if (p->selections[i]->mask_serial) ++masked;
+  }
+  if (mask && masked >= DVO_AMD_MAX_MASKED_SELECTIONS) {
+    g_last_error = "point selection: the pyramid already caches " + std::to_string(DVO_AMD_MAX_MASKED_SELECTIONS) + " masked selections";
+    return DVO_AMD_ERR_CAPACITY;
+  }
   HIP_TRY(hipSetDevice(p->device));
   hipStream_t st;
-  int rc = device_prep_stream(p->device, &st);
+  rc = device_prep_stream(p->device, &st);
   if (rc) return rc;
   std::unique_ptr<Selection> sp(new Selection());
   Selection &s = *sp;
-  s.ti = ti, s.td = td, s.extra_slab = nullptr, s.extra_bytes = 0;
+  s.ti = ti, s.td = td, s.mask_serial = serial, s.extra_slab = nullptr, s.extra_bytes = 0;
   if (p->selections.empty()) {
     selection_in_slab(p, s);
   } else {
@@ -340,7 +364,10 @@ int pyramid_selection(dvo_amd_pyramid *p, float ti, float td, const Selection **
   if (e != hipSuccess) return fail("selection descriptors", e);
   for (int l = 0; l < p->n_levels; ++l) {
     const LevelData &L = p->lv[l];
-    e = launch_select(L.z_plane, L.c_a, L.c_b, L.n, L.n_pad, ti, td, s.zsel[l], p->counters + 2 * l, p->sel_partials, st);
+    // (a pair without a mask takes the path it always took: the unmasked kernel, the same launches)
+    e = mask ? launch_select_masked(L.z_plane, L.c_a, L.c_b, mask->plane[l], L.n, L.n_pad, ti, td, s.zsel[l], p->counters + 2 * l,
+                                    p->sel_partials, st)
+             : launch_select(L.z_plane, L.c_a, L.c_b, L.n, L.n_pad, ti, td, s.zsel[l], p->counters + 2 * l, p->sel_partials, st);
     if (e != hipSuccess) return fail("select", e);
     // (the partials and the prefix are scratch of the pyramid shared by its levels: the prep stream runs them in order)
     e = launch_compact(s.zsel[l], L.r_i, L.r_ix, L.r_iy, L.tx, L.ty, L.w, L.n, L.n_pad, p->sel_partials, p->sel_prefix, p->counters + 2 * l,
@@ -596,10 +623,11 @@ int dvo_amd_pyramid_download_plane(const dvo_amd_pyramid *p, int level, int plan
   return DVO_AMD_OK;
 }
 
-int dvo_amd_pyramid_select(dvo_amd_pyramid *p, int level, float ti, float td, int *count, unsigned char *mask) {
+// dvo_amd_pyramid_select and dvo_amd_pyramid_select_masked (sel_mask == nullptr: the former)
+static int select_entry(dvo_amd_pyramid *p, int level, float ti, float td, const dvo_amd_mask *sel_mask, int *count, unsigned char *mask) {
   if (!p || level < 0 || level >= p->n_levels) return DVO_AMD_ERR_INVALID_ARGUMENT;
   const Selection *sp = nullptr;
-  int rc = pyramid_selection(p, ti, td, &sp);
+  int rc = pyramid_selection(p, ti, td, sel_mask, &sp);
   if (rc) return rc;
   const Selection &s = *sp;
   if (count) *count = s.count[level];
@@ -619,6 +647,15 @@ int dvo_amd_pyramid_select(dvo_amd_pyramid *p, int level, float ti, float td, in
     if (e != hipSuccess) return fail_hip("select mask", e);
   }
   return DVO_AMD_OK;
+}
+
+int dvo_amd_pyramid_select(dvo_amd_pyramid *p, int level, float ti, float td, int *count, unsigned char *mask) {
+  return select_entry(p, level, ti, td, nullptr, count, mask);
+}
+
+int dvo_amd_pyramid_select_masked(dvo_amd_pyramid *p, int level, float ti, float td, const dvo_amd_mask *mask, int *count,
+                                  unsigned char *out_mask) {
+  return select_entry(p, level, ti, td, mask, count, out_mask);
 }
 
 }  // extern "C"

@@ -891,6 +891,7 @@ int runner_fail(dvo_amd_context *ctx, int code) {
   for (Pending &q : R.pending) {
     dvo_amd_pyramid_release(q.ref);
     dvo_amd_pyramid_release(q.cur);
+    dvo_amd_mask_release(q.mask);
   }
   R.pending.clear();
   for (Batch &b : R.batches) {
@@ -962,7 +963,9 @@ int runner_step(dvo_amd_context *ctx, size_t g) {
     j.cfg = &ctx->cfg;
     R.batch_of_slot[sidx] = q.batch;
     R.resident++;
-    rc = pyramid_selection(j.ref, q.ti, q.td, &j.sel);
+    // the selection holds planes of its own: once it is resolved the queue needs nothing of the mask any more
+    rc = pyramid_selection(j.ref, q.ti, q.td, q.mask, &j.sel);
+    dvo_amd_mask_release(q.mask);
     if (rc) return rc;
     dvo_amd_result *r = j.result;
     r->n_levels = 0, r->n_iterations = 0, r->n_ticks = 0, r->n_residual_passes = 0, r->alg_bytes = 0.0, r->alg_bytes_discarded = 0.0, r->is_nan = 0;
@@ -1387,8 +1390,10 @@ int dvo_amd_get_config(const dvo_amd_context *ctx, dvo_amd_config *cfg) {
   return DVO_AMD_OK;
 }
 
-int dvo_amd_match_submit(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *references, dvo_amd_pyramid *const *currents,
-                         const double *T_inits, dvo_amd_result *results, int max_in_flight, unsigned long long *ticket) {
+// dvo_amd_match_submit with one selection mask per pair (masks == nullptr or masks[i] == nullptr: that pair is unmasked)
+static int match_submit(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *references, dvo_amd_mask *const *masks,
+                        dvo_amd_pyramid *const *currents, const double *T_inits, dvo_amd_result *results, int max_in_flight,
+                        unsigned long long *ticket) {
   if (!ctx || !ticket || n < 0 || (n > 0 && (!references || !currents || !results))) return DVO_AMD_ERR_INVALID_ARGUMENT;
   *ticket = 0;
   const dvo_amd_config &cfg = ctx->cfg;
@@ -1405,6 +1410,7 @@ int dvo_amd_match_submit(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *re
     for (int l = cfg.last_level; l <= cfg.first_level; ++l)
       if (references[i]->lv[l].w != currents[i]->lv[l].w || references[i]->lv[l].h != currents[i]->lv[l].h)
         return DVO_AMD_ERR_INVALID_ARGUMENT;
+    if (masks && (rc = mask_fits("masked match", references[i], masks[i])) != DVO_AMD_OK) return rc;
     n_pad = std::max(n_pad, references[i]->lv[cfg.last_level].n_pad);
     const int its_needed = (cfg.first_level - cfg.last_level + 1) * (cfg.max_iterations_per_level + 1);
     if (results[i].iterations && results[i].iterations_capacity > 0 && results[i].iterations_capacity < its_needed)
@@ -1436,6 +1442,9 @@ int dvo_amd_match_submit(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *re
     // the queue holds its own references: the caller may release a pyramid right after submitting
     dvo_amd_pyramid_retain(q.ref);
     dvo_amd_pyramid_retain(q.cur);
+    // ... and a pair's mask, from here until the pair's selection has been resolved (runner_step)
+    q.mask = masks ? masks[i] : nullptr;
+    dvo_amd_mask_retain(q.mask);
     R.pending.push_back(q);
   }
   *ticket = b.id;
@@ -1446,6 +1455,11 @@ int dvo_amd_match_submit(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *re
       if (rc) return runner_fail_told(ctx, rc);
     }
   return DVO_AMD_OK;
+}
+
+int dvo_amd_match_submit(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *references, dvo_amd_pyramid *const *currents,
+                         const double *T_inits, dvo_amd_result *results, int max_in_flight, unsigned long long *ticket) {
+  return match_submit(ctx, n, references, nullptr, currents, T_inits, results, max_in_flight, ticket);
 }
 
 int dvo_amd_match_wait(dvo_amd_context *ctx, unsigned long long ticket) {
@@ -1524,6 +1538,35 @@ int dvo_amd_match_selection(dvo_amd_context *ctx, dvo_amd_pyramid *reference, fl
   ctx->cfg.intensity_derivative_threshold = intensity_threshold;
   ctx->cfg.depth_derivative_threshold = depth_threshold;
   const int rc = dvo_amd_match(ctx, reference, current, T_init, result);
+  ctx->cfg.intensity_derivative_threshold = keep_i;
+  ctx->cfg.depth_derivative_threshold = keep_d;
+  return rc;
+}
+
+int dvo_amd_match_many_masked(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *references, dvo_amd_mask *const *masks,
+                              dvo_amd_pyramid *const *currents, const double *T_inits, dvo_amd_result *results, int max_in_flight) {
+  if (!ctx || n < 0 || (n > 0 && (!references || !currents || !results))) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  if (n == 0) return DVO_AMD_OK;
+  unsigned long long ticket = 0;
+  int rc = match_submit(ctx, n, references, masks, currents, T_inits, results, max_in_flight, &ticket);
+  if (rc) return rc;
+  return dvo_amd_match_wait(ctx, ticket);
+}
+
+int dvo_amd_match_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_mask *mask, float intensity_threshold,
+                         float depth_threshold, dvo_amd_pyramid *current, const double *T_init, dvo_amd_result *result) {
+  if (!ctx) return DVO_AMD_ERR_INVALID_ARGUMENT;
+  {
+    int rc = queue_must_be_idle(ctx, "dvo_amd_match_masked");
+    if (rc) return rc;
+  }
+  // as dvo_amd_match_selection: the thresholds given decide, not the configuration's, for this call
+  const float keep_i = ctx->cfg.intensity_derivative_threshold, keep_d = ctx->cfg.depth_derivative_threshold;
+  ctx->cfg.intensity_derivative_threshold = intensity_threshold;
+  ctx->cfg.depth_derivative_threshold = depth_threshold;
+  dvo_amd_pyramid *r[1] = {reference}, *c[1] = {current};
+  dvo_amd_mask *m[1] = {mask};
+  const int rc = dvo_amd_match_many_masked(ctx, 1, r, m, c, T_init, result, 0);
   ctx->cfg.intensity_derivative_threshold = keep_i;
   ctx->cfg.depth_derivative_threshold = keep_d;
   return rc;

@@ -405,6 +405,14 @@ hipError_t launch_level_planes(const float *i_plane, const float *z_plane, int w
 // block_partials: scratch of n_pad / 256 int2 (per-block count and last index; no atomics)
 hipError_t launch_select(const float *z_plane, const float4 *c_a, const float2 *c_b, int n, int n_pad, float ti, float td,
                          float *zsel, int *counters, int2 *block_partials, hipStream_t stream);
+// the same behind a selection mask: `mask` is the level's byte plane (n bytes, 0 = drop); everything else as launch_select
+hipError_t launch_select_masked(const float *z_plane, const float4 *c_a, const float2 *c_b, const unsigned char *mask, int n, int n_pad,
+                                float ti, float td, float *zsel, int *counters, int2 *block_partials, hipStream_t stream);
+// a selection mask's planes: a given level normalised to 0 / 1 into its packed plane (src == dst: in place), a derived level from
+// the one above it (any_rule 0: all four kept, else any); *kept (device, zeroed by the caller) counts the plane's kept pixels
+hipError_t launch_mask_plane(const unsigned char *src, int stride, unsigned char *dst, int w, int h, int *kept, hipStream_t stream);
+hipError_t launch_mask_down(const unsigned char *m_prev, int w_prev, unsigned char *m_out, int w, int h, int any_rule, int *kept,
+                            hipStream_t stream);
 // raw frame -> float base planes of level 0 (uint8 gray or BGR, uint16 depth with 0 = invalid)
 hipError_t launch_ingest(const unsigned char *img, int channels, int img_stride_bytes, const unsigned short *raw_z,
                          int z_stride, float z_scale, float *i_plane, float *z_plane, int w, int h, hipStream_t stream);

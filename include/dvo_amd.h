@@ -414,6 +414,81 @@ int dvo_amd_match(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyra
 int dvo_amd_match_selection(dvo_amd_context *ctx, dvo_amd_pyramid *reference, float intensity_threshold, float depth_threshold,
                             dvo_amd_pyramid *current, const double *T_init, dvo_amd_result *result);
 
+/*
+ * Selection masks: any predicate over the reference pixels.
+ *
+ * The reference's PointSelection takes any PointSelectionPredicate, and isPointOk sees the pixel's position
+ * (point_selection.h:32-37, point_selection.cpp:128-147): a caller may cut out a region, follow a segmentation, keep a region of
+ * interest.  Here that decision arrives as a dvo_amd_mask: an immutable, refcounted, device-resident pyramid of byte planes, one
+ * per level, row-major, level l of size (width >> l) x (height >> l) under the size rules of dvo_amd_pyramid_create_raw.  Planes
+ * are stored normalised: any non-zero input byte is 1 (keep), 0 is drop, and a download returns 0 or 1.  A mask is shareable
+ * between contexts and threads and is retained and released independently of any pyramid.  It carries a process-wide 64-bit
+ * serial number, never 0 and never reused, which is its identity in a pyramid's selection cache (a released mask's address may
+ * come back; its serial does not).
+ *
+ *   dvo_amd_mask_create          level 0 is given (stride in bytes, >= width), in host memory or -- on_device != 0 -- in device
+ *                                memory on `device` (a segmentation network's output tensor); levels 1..levels-1 are derived on
+ *                                the device: with DVO_AMD_MASK_ALL pixel (x, y) of level l+1 is kept iff all of (2x, 2y),
+ *                                (2x+1, 2y), (2x, 2y+1), (2x+1, 2y+1) of level l are kept (the conservative rule for excluding
+ *                                things), with DVO_AMD_MASK_ANY iff any of them is.  An odd trailing row of a level has no
+ *                                parent, as in the pyramid itself.  The number of kernel launches depends on `levels` alone.
+ *   dvo_amd_mask_create_levels   every level is given (planes[l], strides[l] >= width >> l): what a per-level predicate needs
+ *   dvo_amd_mask_info            sizes, and kept[l] = the kept pixels of level l for l < levels (any output may be NULL)
+ *   dvo_amd_mask_download        one level back to the host, (width >> level) * (height >> level) bytes of 0 / 1
+ *
+ * Errors of the two create entries.  DVO_AMD_ERR_INVALID_ARGUMENT, with a reason in dvo_amd_last_error(), before a device is
+ * looked for: a NULL pointer (inside planes / strides too); a size that breaks the pyramid size rules on any level asked for;
+ * a stride smaller than the width of its level; levels outside 1..DVO_AMD_MAX_LEVELS; an unknown rule.  Then
+ * DVO_AMD_ERR_NO_DEVICE.
+ *
+ * The predicate of a masked selection is
+ *     keep(l, i) = mask[l][i] != 0  &&  ValidPointAndGradientThresholdPredicate(ti, td)(pixel i of level l)
+ * with thresholds of -1 leaving validity only, as for dvo_amd_match_selection.  Stated deviation: a pixel with NaN z, zdx or zdy
+ * is never selected, whatever the mask says (a reference predicate that admitted such a point would put it into the point list).
+ * The mask enters in the select kernel and nowhere else: the compaction, the residual passes and the reducers walk the selected
+ * pixels in scan order as they always did, so a masked alignment whose mask keeps what a threshold pair keeps IS the alignment
+ * of dvo_amd_match_selection with that pair, bit for bit (tests/test_selection_mask.py).
+ *
+ * Cache.  A pyramid's selections are keyed by (intensity_threshold, depth_threshold, mask serial), serial 0 meaning no mask.  A
+ * masked selection holds planes of its own, not the mask: once built, the mask may be released and the selection stays valid
+ * for the life of the pyramid.  A pyramid caches at most DVO_AMD_MAX_MASKED_SELECTIONS masked selections: one more distinct mask
+ * returns DVO_AMD_ERR_CAPACITY and leaves the pyramid as it was (unmasked selections are not counted and not limited).  Checked
+ * before any device work, in this order: DVO_AMD_ERR_INVALID_ARGUMENT for a mask whose level-0 size differs from the pyramid's
+ * or that has fewer levels than the pyramid; DVO_AMD_ERR_DEVICE_MISMATCH for a mask on another device.
+ *
+ *   dvo_amd_pyramid_select_masked  dvo_amd_pyramid_select behind `mask` (NULL: exactly dvo_amd_pyramid_select); count includes
+ *                                  an odd trailing point and out_mask marks it, as there
+ *   dvo_amd_match_masked           dvo_amd_match_selection behind `mask`: the queue must be idle, the thresholds given override
+ *                                  the configuration's for this call; mask == NULL is exactly dvo_amd_match_selection
+ *   dvo_amd_match_many_masked      dvo_amd_match_many with one mask per pair and the configuration's thresholds; masks == NULL
+ *                                  or masks[i] == NULL: that pair is unmasked.  The queue retains a mask from submission until
+ *                                  that pair's selection has been resolved.  (There is no submit / wait / poll form.)
+ * Guarantees, all bit for bit: a pair with a NULL mask gives dvo_amd_match's result; a pair with an all-ones mask gives the
+ * unmasked result; any pair's result is a function of its inputs, its mask and the configuration alone, at any max_in_flight
+ * and whatever shares the batch (the determinism contract of dvo_amd_match_batch, extended).
+ *
+ * Not covered: dvo_amd_track_frame, dvo_amd_validate_proposals, dvo_amd_match_banded / _sharded, dvo_amd_residuals,
+ * dvo_amd_error_image, the debug and bench entries and the build_selection of dvo_amd_pyramid_create_raw_batch keep their
+ * thresholds-only selection and take no mask.  There are no masks on the current side: the current image is gathered wherever
+ * the warp lands, which is the reference's behaviour.
+ */
+#define DVO_AMD_MASK_ALL 0
+#define DVO_AMD_MASK_ANY 1
+#define DVO_AMD_MAX_MASKED_SELECTIONS 8
+typedef struct dvo_amd_mask dvo_amd_mask;
+int dvo_amd_mask_create(int device, int width, int height, int levels, const unsigned char *mask0, int stride, int on_device, int rule,
+                        dvo_amd_mask **out);
+int dvo_amd_mask_create_levels(int device, int width, int height, int levels, const unsigned char *const *planes, const int *strides,
+                               int on_device, dvo_amd_mask **out);
+void dvo_amd_mask_retain(dvo_amd_mask *mask);
+void dvo_amd_mask_release(dvo_amd_mask *mask);
+int dvo_amd_mask_info(const dvo_amd_mask *mask, int *width, int *height, int *levels, long long *kept /* [levels] */);
+int dvo_amd_mask_download(const dvo_amd_mask *mask, int level, unsigned char *dst);
+int dvo_amd_pyramid_select_masked(dvo_amd_pyramid *p, int level, float intensity_threshold, float depth_threshold,
+                                  const dvo_amd_mask *mask, int *count, unsigned char *out_mask);
+int dvo_amd_match_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_mask *mask, float intensity_threshold,
+                         float depth_threshold, dvo_amd_pyramid *current, const double *T_init, dvo_amd_result *result);
+
 /* n independent match() calls advanced in lock step on one GPU (the shape of LocalTracker::update's tbb::parallel_invoke,
  * local_tracker.cpp:184, and of the loop-closure validator's parallel_reduce, keyframe_graph.cpp:576-593).
  * T_inits: n x 16 doubles or NULL.  Results are identical to n dvo_amd_match() calls BIT FOR BIT: a pair's result is a function
@@ -430,6 +505,9 @@ int dvo_amd_match_batch(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *ref
  * loop-closure validator working through a proposal list, keyframe_graph.cpp:576-593).  max_in_flight <= 0: all n at once. */
 int dvo_amd_match_many(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *references, dvo_amd_pyramid *const *currents,
                        const double *T_inits, dvo_amd_result *results, int max_in_flight);
+/* ... with one selection mask per pair (see "Selection masks" above) */
+int dvo_amd_match_many_masked(dvo_amd_context *ctx, int n, dvo_amd_pyramid *const *references, dvo_amd_mask *const *masks,
+                              dvo_amd_pyramid *const *currents, const double *T_inits, dvo_amd_result *results, int max_in_flight);
 
 /*
  * The same queue without draining between calls.  A tracker that works through proposals as they come (the loop-closure

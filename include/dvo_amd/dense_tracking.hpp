@@ -443,9 +443,85 @@ struct PointWithIntensityAndDepth {
   IntensityAndDepth intensity_and_depth;
 };
 
-// point_selection.h:32-67.  The selection runs on the GPU, so a predicate must be expressible as the two gradient thresholds
-// of the reference's own predicates; deviceThresholds() says how.  A user-defined predicate with other logic cannot run on
-// the device: PointSelection throws DvoAmdError for it instead of silently selecting something else.
+// (not in the reference) A selection mask on the device (dvo_amd_mask): which reference pixels may take part, one byte plane per
+// pyramid level, 1 = keep.  RAII over the C ABI, shared by value (shared ownership of one device object, like
+// dvo::core::Rectification): a predicate hands one out through deviceMask(), a selection built behind it outlives it.
+class SelectionMask {
+ public:
+  enum Rule { All = DVO_AMD_MASK_ALL, Any = DVO_AMD_MASK_ANY };
+  SelectionMask() : device_(0) {}  // empty: valid() is false
+
+  // level 0 given (stride in bytes, 0 = packed; on_device: device memory of `device`, e.g. a segmentation network's output), the
+  // coarser levels derived on the device: a pixel is kept iff all (All) or any (Any) of the four pixels under it are kept
+  static SelectionMask fromLevel0(int width, int height, int levels, const unsigned char *mask0, int stride = 0, Rule rule = All,
+                                  int device = 0, bool on_device = false) {
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_create(device, width, height, levels, mask0, stride ? stride : width, on_device ? 1 : 0, (int)rule, &m),
+                  "SelectionMask::fromLevel0");
+    return SelectionMask(m, device);
+  }
+  // every level given: planes[l] holds (width >> l) x (height >> l) bytes, packed
+  static SelectionMask fromLevels(int width, int height, const std::vector<std::vector<unsigned char> > &planes, int device = 0) {
+    std::vector<const unsigned char *> ptr(planes.size());
+    std::vector<int> strides(planes.size());
+    for (size_t l = 0; l < planes.size(); ++l) {
+      if (planes[l].size() != (size_t)(width >> l) * (size_t)(height >> l))
+        throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "SelectionMask::fromLevels");
+      ptr[l] = planes[l].data(), strides[l] = width >> l;
+    }
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_create_levels(device, width, height, (int)planes.size(), ptr.data(), strides.data(), 0, &m),
+                  "SelectionMask::fromLevels");
+    return SelectionMask(m, device);
+  }
+
+  bool valid() const { return (bool)handle_; }
+  dvo_amd_mask *handle() const { return handle_.get(); }
+  int device() const { return device_; }
+
+  struct Info {
+    int width, height, levels;
+    long long kept[DVO_AMD_MAX_LEVELS];  // kept pixels per level
+  };
+  Info info() const {
+    Info i;
+    std::memset(&i, 0, sizeof(i));
+    detail::check(dvo_amd_mask_info(need(), &i.width, &i.height, &i.levels, i.kept), "SelectionMask::info");
+    return i;
+  }
+  std::vector<unsigned char> download(int level) const {
+    const Info i = info();
+    if (level < 0 || level >= i.levels) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "SelectionMask::download");
+    std::vector<unsigned char> out((size_t)(i.width >> level) * (size_t)(i.height >> level));
+    detail::check(dvo_amd_mask_download(need(), level, out.data()), "SelectionMask::download");
+    return out;
+  }
+
+ private:
+  struct Release {
+    void operator()(dvo_amd_mask *m) const { dvo_amd_mask_release(m); }
+  };
+  SelectionMask(dvo_amd_mask *m, int device) : handle_(m, Release()), device_(device) {}
+  dvo_amd_mask *need() const {
+    if (!handle_) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "SelectionMask: empty");
+    return handle_.get();
+  }
+  std::shared_ptr<dvo_amd_mask> handle_;
+  int device_;
+};
+
+// point_selection.h:32-67.  The selection runs on the GPU.  A predicate says how in one of three ways:
+//   deviceThresholds()   the two gradient thresholds of the reference's own predicates: evaluated by the select kernel
+//   deviceMask()         a SelectionMask the predicate holds (next to its thresholds, or -1 / -1 if it has none): the kernel
+//                        keeps a pixel iff the mask does and the threshold predicate does
+//   neither              any user-defined predicate, as a caller of the reference writes it.  PointSelection then evaluates
+//                        isPointOk(x, y, z, idx, idy, zdx, zdy) itself, on the host: once per pyramid and per level in use it
+//                        downloads the level's six planes, calls the predicate for every pixel in scan order, and uploads the
+//                        answers as a mask (dvo_amd_mask_create_levels) that it keeps until setRgbdImagePyramid / recycle --
+//                        when the reference drops its own cache.  The cost is that host pass over the planes, once per
+//                        pyramid; the alignment itself runs on the device as always, behind that mask with thresholds -1 / -1.
+// One deviation, for the two mask forms: a pixel with NaN z, zdx or zdy is never selected, whatever the predicate says (the
+// reference would put a point its predicate admits into the point list, NaN or not).
 class PointSelectionPredicate {
  public:
   virtual ~PointSelectionPredicate() {}
@@ -455,6 +531,7 @@ class PointSelectionPredicate {
     (void)intensity_threshold, (void)depth_threshold;
     return false;
   }
+  virtual const SelectionMask *deviceMask() const { return nullptr; }
 };
 
 class ValidPointPredicate : public PointSelectionPredicate {
@@ -489,10 +566,25 @@ class ValidPointAndGradientThresholdPredicate : public PointSelectionPredicate {
   }
 };
 
+// (not in the reference) a device mask and the two gradient thresholds: keep = mask && ValidPointAndGradientThresholdPredicate.
+// isPointOk is the threshold part alone -- the call does not say which level a pixel belongs to, so the mask part exists on the
+// device only; PointSelection never calls it for a predicate that has a device form.
+class MaskedGradientThresholdPredicate : public ValidPointAndGradientThresholdPredicate {
+ public:
+  SelectionMask mask;
+  MaskedGradientThresholdPredicate() {}
+  explicit MaskedGradientThresholdPredicate(const SelectionMask &m, float intensity = 0.0f, float depth = 0.0f) : mask(m) {
+    intensity_threshold = intensity, depth_threshold = depth;
+  }
+  virtual ~MaskedGradientThresholdPredicate() {}
+  virtual const SelectionMask *deviceMask() const { return mask.valid() ? &mask : nullptr; }
+};
+
 // point_selection.h:70-117.  The reference caches the compacted 48-byte records per level until setRgbdImagePyramid(); here
 // the selection lives with the device pyramid (a NaN-masked depth plane per threshold pair, cached for the pyramid's
-// lifetime), so this class only carries the pyramid pointer and the predicate.  select() materialises host records for
-// callers that want to look at them; match() never does.
+// lifetime), so this class only carries the pyramid pointer and the predicate -- and, for a predicate without a device form,
+// the predicate's answers as a device mask (hostMask).  select() materialises host records for callers that want to look at
+// them; match() never does.
 class PointSelection {
  public:
   typedef PointWithIntensityAndDepth::VectorType PointVector;
@@ -510,6 +602,7 @@ class PointSelection {
   void setRgbdImagePyramid(RgbdImagePyramid &pyramid) {
     pyramid_ = &pyramid;
     storage_.clear();  // point_selection.cpp:51-59: the cache belongs to the previous pyramid
+    host_mask_ = SelectionMask(), host_planes_.clear(), host_mask_of_ = nullptr;  // ... and so does a host-evaluated mask
   }
   void recycle(RgbdImagePyramid &pyramid) { setRgbdImagePyramid(pyramid); }
 
@@ -519,20 +612,33 @@ class PointSelection {
     return size_t((double)((size_t)p.width() * (size_t)p.height()) * std::pow(0.25, double(level)));
   }
 
-  // the thresholds the device selection runs with (throws for a predicate the device cannot evaluate)
+  // the thresholds of a predicate that is its two thresholds and nothing else (throws for any other: see deviceForm)
   void thresholds(float &ti, float &td) const {
-    if (!predicate_.deviceThresholds(ti, td))
-      throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "PointSelection: predicate has no device form (deviceThresholds)");
+    if (predicate_.deviceMask() || !predicate_.deviceThresholds(ti, td))
+      throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "PointSelection: predicate is not a threshold pair (deviceForm)");
+  }
+
+  // What the device selection of levels first_level..last_level of the pyramid runs with: a mask (null: none) and the two
+  // thresholds.  A predicate without a device form is evaluated here, on the host, for the levels asked for that have not been
+  // evaluated for this pyramid yet (PointSelectionPredicate's comment); the pyramid must hold the levels already.
+  void deviceForm(size_t first_level, size_t last_level, const SelectionMask *&mask, float &ti, float &td) {
+    mask = predicate_.deviceMask();
+    if (predicate_.deviceThresholds(ti, td)) return;
+    ti = -1.0f, td = -1.0f;
+    if (mask) return;
+    mask = &hostMask(first_level, last_level);
   }
 
   // number of selected pixels of a level (the distance last_point - first_point of select())
   size_t size(const size_t &level) {
     RgbdImagePyramid &p = getRgbdImagePyramid();
     p.build(level + 1);
+    const SelectionMask *m;
     float ti, td;
-    thresholds(ti, td);
+    deviceForm(level, level, m, ti, td);
     int count = 0;
-    detail::check(dvo_amd_pyramid_select(p.handle(), (int)level, ti, td, &count, nullptr), "PointSelection::size");
+    detail::check(dvo_amd_pyramid_select_masked(p.handle(), (int)level, ti, td, m ? m->handle() : nullptr, &count, nullptr),
+                  "PointSelection::size");
     return (size_t)count;
   }
 
@@ -543,12 +649,14 @@ class PointSelection {
     if (storage_.size() < level + 1) storage_.resize(level + 1);
     Storage &st = storage_[level];
     if (!st.is_cached || debug_) {
+      const SelectionMask *m;
       float ti, td;
-      thresholds(ti, td);
+      deviceForm(level, level, m, ti, td);
       const size_t n = img.width * img.height;
       std::vector<unsigned char> mask(n);
       int count = 0;
-      detail::check(dvo_amd_pyramid_select(p.handle(), (int)level, ti, td, &count, mask.data()), "PointSelection::select");
+      detail::check(dvo_amd_pyramid_select_masked(p.handle(), (int)level, ti, td, m ? m->handle() : nullptr, &count, mask.data()),
+                    "PointSelection::select");
       std::vector<float> pl[6];
       for (int k = 0; k < 6; ++k) pl[k] = img.plane(k);
       st.points.assign((size_t)count, PointWithIntensityAndDepth());
@@ -591,10 +699,50 @@ class PointSelection {
     std::vector<unsigned char> debug_idx;
     Storage() : is_cached(false) {}
   };
+  // The predicate's answers for levels first..last of the pyramid as a device mask.  A level is evaluated once per pyramid;
+  // levels nobody has asked for yet are all-drop planes.  Asking for a further level later evaluates that one and uploads a new
+  // mask -- a new identity in the pyramid's selection cache (at most DVO_AMD_MAX_MASKED_SELECTIONS of them per pyramid), so a
+  // caller does well to ask for the levels it tracks over in one go, as DenseTracker::match does.
+  const SelectionMask &hostMask(size_t first_level, size_t last_level) {
+    RgbdImagePyramid &p = getRgbdImagePyramid();
+    p.build(last_level + 1);
+    const size_t levels = (size_t)dvo_amd_pyramid_levels(p.handle());
+    if (host_mask_of_ != p.handle() || host_planes_.size() != levels) {  // (the pyramid was rebuilt with more levels)
+      host_mask_ = SelectionMask(), host_mask_of_ = p.handle();
+      host_planes_.assign(levels, std::vector<unsigned char>());
+      host_done_.assign(levels, false);
+    }
+    bool fresh = !host_mask_.valid();
+    for (size_t l = first_level; l <= last_level && l < levels; ++l) {
+      if (host_done_[l]) continue;
+      RgbdImage &img = p.level(l);
+      std::vector<float> pl[6];
+      for (int k = 1; k < 6; ++k) pl[k] = img.plane(k);  // (isPointOk does not see the intensity itself)
+      std::vector<unsigned char> &out = host_planes_[l];
+      out.assign(img.width * img.height, 0);
+      for (size_t y = 0; y < img.height; ++y)
+        for (size_t x = 0; x < img.width; ++x) {
+          const size_t i = y * img.width + x;
+          out[i] = predicate_.isPointOk(x, y, pl[1][i], pl[2][i], pl[3][i], pl[4][i], pl[5][i]) ? 1 : 0;
+        }
+      host_done_[l] = true, fresh = true;
+    }
+    if (fresh) {
+      for (size_t l = 0; l < levels; ++l)
+        if (host_planes_[l].empty()) host_planes_[l].assign((size_t)(p.width() >> l) * (size_t)(p.height() >> l), 0);
+      host_mask_ = SelectionMask::fromLevels(p.width(), p.height(), host_planes_, p.device());
+    }
+    return host_mask_;
+  }
+
   RgbdImagePyramid *pyramid_;
   std::vector<Storage> storage_;
   const PointSelectionPredicate &predicate_;
   bool debug_;
+  SelectionMask host_mask_;                               // a predicate without a device form, evaluated on the host ...
+  std::vector<std::vector<unsigned char> > host_planes_;  // ... its answers per level (all-drop where not evaluated yet)
+  std::vector<bool> host_done_;
+  const dvo_amd_pyramid *host_mask_of_ = nullptr;         // ... and the device pyramid they belong to
 };
 
 // surface_pyramid.h:34-49 / surface_pyramid.cpp:44-105: uint16 raw depth -> float metres, 0 -> NaN, one fp32 multiply per pixel.
@@ -844,8 +992,11 @@ class DenseTracker {
     core::RgbdImagePyramid &ref_pyramid = reference.getRgbdImagePyramid();
     ref_pyramid.compute(cfg.getNumLevels());
     current.compute(cfg.getNumLevels());
+    // the predicate's device form for the levels this match walks (a user-defined predicate is evaluated on the host here, once
+    // per pyramid); a predicate of two thresholds takes the path it always took (mask == NULL is dvo_amd_match_selection)
+    const core::SelectionMask *mask = nullptr;
     float ti = 0.0f, td = 0.0f;
-    reference.thresholds(ti, td);
+    reference.deviceForm((size_t)cfg.LastLevel, (size_t)cfg.FirstLevel, mask, ti, td);
     const int cap = (cfg.FirstLevel - cfg.LastLevel + 1) * (cfg.MaxIterationsPerLevel + 1);
     std::vector<dvo_amd_iteration_stats> its((size_t)cap);
     dvo_amd_result r;
@@ -854,8 +1005,8 @@ class DenseTracker {
     r.iterations_capacity = cap;
     double T0[16];
     std::memcpy(T0, core::data(result.Transformation), sizeof(T0));
-    detail::check(dvo_amd_match_selection(ctx_, ref_pyramid.handle(), ti, td, current.handle(),
-                                          cfg.UseInitialEstimate ? T0 : nullptr, &r),
+    detail::check(dvo_amd_match_masked(ctx_, ref_pyramid.handle(), mask ? mask->handle() : nullptr, ti, td, current.handle(),
+                                       cfg.UseInitialEstimate ? T0 : nullptr, &r),
                   "DenseTracker::match");
     std::memcpy(core::data(result.Transformation), r.transformation, sizeof(r.transformation));
     std::memcpy(core::data(result.Information), r.information, sizeof(r.information));
