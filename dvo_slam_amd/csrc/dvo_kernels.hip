@@ -365,6 +365,9 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
   constexpr int kBufs = 2;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x >> 6;
+  // the wave's number as a scalar, for the staging addresses formed inside the steps and after them: as a vector value the
+  // wave's staging offset is one more register that lives through the whole pass
+  const int wave_s = __builtin_amdgcn_readfirstlane(wave);
   const int seg = lb * kWavesPerBlock + wave;
   const int steps = item_res_steps(it);  // a segment is steps * 64 points
   unsigned idx = (unsigned)(seg * (kStepPx * steps) + lane);  // a POINT of the compacted selection (k_compact), not a pixel
@@ -407,12 +410,20 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
                          *const p_tx = (const DVO_GLOBAL void *)d.tx, *const p_ty = (const DVO_GLOBAL void *)d.ty;
   DVO_GLOBAL char *const p_res = (DVO_GLOBAL char *)((it.flags & kItemResBuf) ? d.res[1] : d.res[0]);  // no dynamic index: keeps d in registers
 
-  // the points of the step about to be processed (depth, intensity, derivatives, ray: six coalesced dword loads, one step ahead);
-  // all accesses are uniform base + 32-bit offset
+  // the points of the step about to be processed (depth, intensity, derivatives, ray: six coalesced dword loads, issued behind
+  // the Gram stage of the step before -- about two thirds of a step ahead of their first use); all accesses are uniform base +
+  // 32-bit offset
   // (a two-step lead with two alternating register sets was measured: +10 VGPRs, +9 VALU per step, no gain in or out of cache)
-  float n_z = ld_off<float>(p_z, 4u * idx), n_i = ld_off<float>(p_i, 4u * idx), n_ix = ld_off<float>(p_ix, 4u * idx),
-        n_iy = ld_off<float>(p_iy, 4u * idx);
-  float n_tx = ld_off<float>(p_tx, 4u * idx), n_ty = ld_off<float>(p_ty, 4u * idx);  // the point's ray (padding: zeros under a NaN depth)
+  // (the first step's loads stand in each arm of the step-count branch below -- load_first: issued once in front of the branch,
+  //  the six values are live across the code of the arm not taken, and at 128 VGPRs the register allocator spills them)
+  float n_z, n_i, n_ix, n_iy, n_tx, n_ty;  // (n_tx, n_ty: the point's ray; padding: zeros under a NaN depth)
+  auto load_first = [&](const bool opaque) __attribute__((always_inline)) {
+    unsigned at = idx;
+    if (opaque) DVO_OPAQUE(at);  // keeps the two arms' loads apart
+    n_z = ld_off<float>(p_z, 4u * at), n_i = ld_off<float>(p_i, 4u * at), n_ix = ld_off<float>(p_ix, 4u * at),
+    n_iy = ld_off<float>(p_iy, 4u * at);
+    n_tx = ld_off<float>(p_tx, 4u * at), n_ty = ld_off<float>(p_ty, 4u * at);
+  };
 
   // Operand fetch of the Gram-matrix accumulation: lane l supplies component l & 15 of points 4 m + (l >> 4), m = 0..15, of
   // the 64 points a step staged.  With the write swizzle below, chunk (comp >> 2) of point p sits at chunk position
@@ -463,14 +474,13 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
     // ---- round-to-nearest: reference point = pixel ray * depth (RgbdCamera::buildPointCloud, rgbd_image.cpp:245-262)
     float z = n_z, ri = n_i, rix = n_ix, riy = n_iy;
     float x = n_tx * z, y = n_ty * z;
-    // prefetch the next step's reference scalars; they are consumed a whole step later
+    // the next step's reference scalars are prefetched behind the Gram stage below (prefetch_next) and consumed in the next step
     idx += kWave;
     auto prefetch_next = [&]() __attribute__((always_inline)) {
       n_z = ld_off<float>(p_z, 4u * idx), n_i = ld_off<float>(p_i, 4u * idx), n_ix = ld_off<float>(p_ix, 4u * idx),
       n_iy = ld_off<float>(p_iy, 4u * idx);
       n_tx = ld_off<float>(p_tx, 4u * idx), n_ty = ld_off<float>(p_ty, 4u * idx);
     };
-    if (prefetch) prefetch_next();
 
     // ---- switch to round-toward-zero: every float that crosses is made opaque on both sides of the s_setreg
     DVO_OPAQUE(x); DVO_OPAQUE(y); DVO_OPAQUE(z); DVO_OPAQUE(ri); DVO_OPAQUE(rix); DVO_OPAQUE(riy);
@@ -487,16 +497,24 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
         DVO_KEEP(p.base);
       } else {
         g = gather_pixel(d, p.base);
+        // Pin the six gather loads in front of the Gram stage: left to itself the scheduler sinks them, with their offset
+        // arithmetic, behind 28 to 31 of the 36 v_mfma, and the gather latency then starts where the matrix work ends.
+        if (ACC >= 1 && !(DVO_ABLATE & 1) && step > 0) __builtin_amdgcn_sched_barrier(0);
       }
 
-      // While this step's gathers are in flight, feed the matrix pipe with the vectors the PREVIOUS step staged
+      // The gathers are in flight (the barrier above): feed the matrix pipe with the vectors the PREVIOUS step staged
       // (v_mfma_f32 ignores MODE.FP_ROUND -- probed on gfx950, scripts/probes/mfma_round.hip -- so it may sit in
-      // the toward-zero window).  This overlaps ~512 matrix-pipe cycles with the gather latency and with the next
-      // wave's arithmetic instead of serialising them behind this wave's own VALU work.
+      // the toward-zero window).  The 36 instructions -- 36 x 8 = 288 issue cycles by the cycle model of DESIGN.md section 4.1,
+      // a model figure, not a measurement -- now run under the gather latency instead of in front of it; the first use of the
+      // gathered data (v_fract, the blend) follows the last v_mfma.
       if (ACC >= 1 && !(DVO_ABLATE & 1) && step > 0) {
         gram_from_stage(q ^ 1);
         __builtin_amdgcn_sched_barrier(0);
       }
+      // The next step's reference scalars go out here, not at the top of the step: across the Gram stage the 24 gathered
+      // registers and the 36 accumulators are live together, and six prefetch targets on top of them cost scratch at 128
+      // VGPRs.  They still lead their first use by the blend, the weights, the Jacobian and the staging: ~2/3 of a step.
+      if (prefetch) prefetch_next();
       finish_pixel_rtz<ACC == 0>(d, p, g, z, ri, rix, riy, r0, r1, e2, e3, e4, e5, ok);
     }
     // ---- back to round-to-nearest
@@ -595,7 +613,7 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
     } else {
       // stage sqrt(w) * v for this lane's pixel; chunk c of point p sits at chunk position c ^ ((p >> 1) & 3).
       // Two buffers alternate: the matrix pipe consumes this one during the NEXT step (see above).
-      float *buf = stage + ((wave * kBufs + (q & (kBufs - 1))) * kWave) * 16;
+      float *buf = stage + ((wave_s * kBufs + (q & (kBufs - 1))) * kWave) * 16;
       v4f *row = reinterpret_cast<v4f *>(buf + lane * 16);
       const int swz = (lane >> 1) & 3;
       v4f c0 = {Ja[0], Ja[1], Ja[2], Ja[3]};  // the rows carry sqrt(w) already
@@ -652,6 +670,7 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
   // the last pair of steps is peeled so that "is there a next step to prefetch" is a compile-time fact in every copy
   if (!(DVO_ABLATE & 16)) {  // (ablation 16: prologue + epilogue only)
     if (steps == 1) {
+      load_first(true);
       do_step(0, 1, false);  // a one-step segment stages into buffer 1, which the epilogue consumes
 #if defined(DVO_TRACE_BLOCKS) && !defined(DVO_TRACE_DESC)
       if (threadIdx.x == 0) trace_first = trace_clock();
@@ -660,6 +679,7 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
 #ifdef DVO_TRACE_BLOCKS
       bool marked = false;
 #endif
+      load_first(false);
       for (int step = 0; step + 2 < steps; step += 2) {
         do_step(step, 0, true);
 #if defined(DVO_TRACE_BLOCKS) && !defined(DVO_TRACE_DESC)
@@ -695,7 +715,7 @@ __device__ void residual_pass(const TickItem &it, const LevelPairDesc &d_in, con
   } else {
     // C/D layout of the 16x16 MFMA: register r of lane l is G[row = (l>>4)*4 + r][col = l&15]
     // into the start of the wave's own staging area (its reads of it are behind it in the in-order LDS queue)
-    float *gsm = stage + wave * kBufs * kWave * 16;
+    float *gsm = stage + wave_s * kBufs * kWave * 16;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     if (DVO_GRAM_BLOCKS) {
