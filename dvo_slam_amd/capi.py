@@ -52,6 +52,7 @@ EXPORTS = [
     "dvo_amd_pyramid_create_raw_batch", "dvo_amd_debug_batch_build_stats",
     "dvo_amd_mask_create", "dvo_amd_mask_create_levels", "dvo_amd_mask_retain", "dvo_amd_mask_release", "dvo_amd_mask_info",
     "dvo_amd_mask_download", "dvo_amd_pyramid_select_masked", "dvo_amd_match_masked", "dvo_amd_match_many_masked",
+    "dvo_amd_default_budget_options", "dvo_amd_mask_create_budget",
 ]
 
 
@@ -143,6 +144,13 @@ class CKeyframe(C.Structure):
 
 class CCovisibilityOptions(C.Structure):
     _fields_ = [("level", C.c_int), ("near_z", C.c_float), ("depth_sigmas", C.c_float)]
+
+
+class BudgetOptions(C.Structure):
+    """dvo_amd_budget_options, field for field"""
+    _fields_ = [("rule", C.c_int), ("budget", C.c_longlong * MAX_LEVELS), ("cell", C.c_int * MAX_LEVELS),
+                ("intensity_threshold", C.c_float), ("depth_threshold", C.c_float), ("depth_weight", C.c_float),
+                ("within", C.c_void_p)]
 
 
 # dvo_amd_covisibility_counts, field for field
@@ -326,6 +334,9 @@ def lib():
     L.dvo_amd_pyramid_select_masked.argtypes = [vp, C.c_int, C.c_float, C.c_float, vp, C.POINTER(C.c_int), C.POINTER(C.c_ubyte)]
     L.dvo_amd_match_masked.argtypes = [vp, vp, vp, C.c_float, C.c_float, vp, dp, C.POINTER(CResult)]
     L.dvo_amd_match_many_masked.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(CResult), C.c_int]
+    L.dvo_amd_default_budget_options.argtypes = [C.POINTER(BudgetOptions)]
+    L.dvo_amd_default_budget_options.restype = None
+    L.dvo_amd_mask_create_budget.argtypes = [vp, C.POINTER(BudgetOptions), C.POINTER(vp)]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -484,6 +495,25 @@ def _mask_bytes(a):
 
 MASK_ALL, MASK_ANY = 0, 1
 MAX_MASKED_SELECTIONS = 8
+BUDGET_TOPK, BUDGET_GRID = 0, 1
+
+
+def level_budgets(k0: int, levels: int, minimum: int = 0) -> list:
+    """A level-0 point budget as per-level budgets for SelectionMask.from_budget: level l has a quarter of the pixels of level
+    l - 1, so it gets max(minimum, k0 >> 2l)."""
+    return [max(int(minimum), int(k0) >> (2 * l)) for l in range(levels)]
+
+
+def _per_level(value, default, what):
+    """one entry per level from a scalar (every level) or a sequence (level l = value[l]); the rest keeps the default"""
+    out = [default] * MAX_LEVELS
+    if value is None:
+        return out
+    vals = [int(v) for v in value] if hasattr(value, "__len__") else [int(value)] * MAX_LEVELS
+    if len(vals) > MAX_LEVELS:
+        raise ValueError(f"{what}: more than {MAX_LEVELS} levels")
+    out[:len(vals)] = vals
+    return out
 
 
 class SelectionMask:
@@ -493,7 +523,7 @@ class SelectionMask:
     and threads; a selection built behind it outlives it.  The rules are pinned in include/dvo_amd.h."""
 
     def __init__(self):
-        raise TypeError("use SelectionMask.from_level0 or SelectionMask.from_levels")
+        raise TypeError("use SelectionMask.from_level0, SelectionMask.from_levels or SelectionMask.from_budget")
 
     @classmethod
     def from_level0(cls, mask0, levels: int, rule: int = MASK_ALL, device: int = 0):
@@ -538,6 +568,29 @@ class SelectionMask:
         self._h = C.c_void_p()
         _check(lib().dvo_amd_mask_create_levels(device, w, h, n, ptrs, strides, 0, C.byref(self._h)), "dvo_amd_mask_create_levels")
         self.device = device
+        return self
+
+    @classmethod
+    def from_budget(cls, pyramid, rule: int = BUDGET_TOPK, budget=None, cell=None, thresholds=(0.0, 0.0), depth_weight: float = 0.0,
+                    within: "SelectionMask | None" = None):
+        """A point budget over the levels of `pyramid` (an RgbdImagePyramid), ranked on the device (dvo_amd_mask_create_budget).
+        BUDGET_TOPK: level l keeps its budget[l] strongest candidates (None or negative: every candidate; `level_budgets` makes
+        the list from a level-0 budget).  BUDGET_GRID: level l keeps the strongest candidate of every cell[l] x cell[l] cell.
+        budget / cell: one value per level, or one value for every level.  A candidate passes the threshold predicate of
+        `thresholds` = (intensity, depth) and, if given, the mask `within`; strength is Ix^2 + Iy^2 + depth_weight * (Zx^2 + Zy^2),
+        ties go to the lowest pixel index.  The rules are pinned in include/dvo_amd.h."""
+        opt = BudgetOptions()
+        lib().dvo_amd_default_budget_options(C.byref(opt))
+        opt.rule = int(rule)
+        opt.budget[:] = _per_level(budget, -1, "budget")
+        opt.cell[:] = _per_level(cell, 1, "cell")
+        opt.intensity_threshold, opt.depth_threshold = float(thresholds[0]), float(thresholds[1])
+        opt.depth_weight = float(depth_weight)
+        opt.within = None if within is None else within._h
+        self = cls.__new__(cls)
+        self._h = C.c_void_p()
+        _check(lib().dvo_amd_mask_create_budget(pyramid._h, C.byref(opt), C.byref(self._h)), "dvo_amd_mask_create_budget")
+        self.device = pyramid.device
         return self
 
     def __del__(self):

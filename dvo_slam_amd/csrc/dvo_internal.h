@@ -11,6 +11,7 @@
 //   dvo_graph_batch.cpp  many small pose graphs in one launch: one workgroup per graph, the whole optimization on the device
 //   dvo_rectify.cpp   remap tables (lens undistortion, arbitrary maps) and the kernels that resample a frame through one
 //   dvo_mask.cpp      selection masks: the device-resident mask pyramid behind a masked point selection
+//   dvo_budget.cpp    point-budget masks: a mask ranked on the device from a resident pyramid (top-K radix select, per-cell argmax)
 //   dvo_register.cpp  depth-to-colour registration: the kernels that splat another camera's raw depth into level 0's depth plane
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
@@ -466,6 +467,14 @@ int ingest_level0(int device, const PyramidSpec &spec, const Level0Source &src, 
                   hipStream_t st);
 // every level at least 4x2 with a width that is a multiple of 4, 1..DVO_AMD_MAX_LEVELS of them; `of` names whose levels they are
 int check_levels(const char *entry, int w, int h, int levels, const char *of = "");
+
+// ---- dvo_mask.cpp: what every producer of a mask shares (dvo_budget.cpp builds masks too)
+// the geometry a mask may have: a pyramid's (check_levels), within what one launch's grid holds
+int check_mask_size(const char *entry, int width, int height, int levels);
+// the mask object with its planes allocated and its counters cleared (on the prep stream, returned in *st); the caller fills the planes
+int mask_alloc(const char *entry, int device, int width, int height, int levels, dvo_amd_mask **out, hipStream_t *st);
+// the kept counts to the host and the stream drained (the call's one synchronisation); on failure the mask is gone
+int mask_finish(dvo_amd_mask *m, hipError_t e, hipStream_t st, dvo_amd_mask **out);
 
 // ---- dvo_rectify.cpp: a raw frame in device memory through a remap into i_plane and (unless null) z_plane.  A BGR image is
 // first converted into `grey` (rows of grey_stride bytes, a multiple of 4 that holds the remap's source width)

@@ -19,6 +19,8 @@ namespace {
 
 std::atomic<unsigned long long> g_mask_serial{0};
 
+}  // namespace
+
 // the geometry a mask may have: a pyramid's (check_levels), within what one launch's grid holds
 int check_mask_size(const char *entry, int width, int height, int levels) {
   const int rc = check_levels(entry, width, height, levels, " of the mask");
@@ -89,8 +91,6 @@ int mask_finish(dvo_amd_mask *m, hipError_t e, hipStream_t st, dvo_amd_mask **ou
   *out = m;
   return DVO_AMD_OK;
 }
-
-}  // namespace
 
 }  // namespace host
 }  // namespace dvo_amd

@@ -489,6 +489,65 @@ int dvo_amd_pyramid_select_masked(dvo_amd_pyramid *p, int level, float intensity
 int dvo_amd_match_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_mask *mask, float intensity_threshold,
                          float depth_threshold, dvo_amd_pyramid *current, const double *T_init, dvo_amd_result *result);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Point-budget masks: a selection mask built on the device from a resident pyramid.
+ *
+ * The residual pass walks the compacted selection, so a thinner selection is a cheaper alignment.  The two gradient thresholds
+ * thin it only by trial; a budget says how many points to keep, or how to spread them.  dvo_amd_mask_create_budget ranks the
+ * pixels of every level of `pyramid` on the device and returns an ordinary dvo_amd_mask (level-0 size, level count and device of
+ * the pyramid) that enters wherever a mask enters: dvo_amd_pyramid_select_masked, dvo_amd_match_masked,
+ * dvo_amd_match_many_masked.  The pyramid is only read.
+ *
+ * Saliency.  For pixel i of level l, in fp32, round to nearest, every product and sum rounded by itself (no contraction):
+ *     a = Ix*Ix + Iy*Iy
+ *     s = a                                   if depth_weight == 0 (the depth term is not formed)
+ *     s = a + depth_weight * (Zx*Zx + Zy*Zy)  otherwise
+ * The sort key of the pixel is the bit pattern of s as an unsigned 32-bit integer: s >= 0, so integer order is value order,
+ * and +inf sorts highest.
+ *
+ * Candidates.  Pixel i of level l is a candidate iff ValidPointAndGradientThresholdPredicate(intensity_threshold,
+ * depth_threshold) keeps it (the predicate of the selection; thresholds of -1 leave validity only), and `within` is NULL or
+ * within[l][i] != 0, and s == s.  C_l, the candidates of level l, are ordered by (key descending, pixel index ascending): a
+ * total order.
+ *
+ *   DVO_AMD_BUDGET_TOPK  level l keeps the first min(budget[l], |C_l|) candidates in that order -- exactly that many, whatever
+ *                        ties exist: among equal keys the lowest pixel indices.  budget[l] == 0 keeps none, budget[l] < 0 keeps
+ *                        every candidate.
+ *   DVO_AMD_BUDGET_GRID  level l is cut into cells of cell[l] x cell[l] pixels anchored at (0, 0) (the cells of the last column
+ *                        and row may be partial); each cell keeps its first candidate in that order, a cell without a candidate
+ *                        keeps nothing.  cell[l] == 1 keeps every candidate.
+ * Entries of budget / cell beyond the pyramid's levels are not looked at, and neither is the array of the other rule.
+ *
+ * Result.  kept[l] (dvo_amd_mask_info) is the number of pixels kept on level l.  Every kept pixel passes the predicate the mask
+ * was built with, so tracking behind the mask with those thresholds or with (-1, -1) selects exactly the kept pixels (an odd
+ * trailing point stays the selection's business, Q3, as for every mask).  The planes are a function of the pyramid and the
+ * options alone.
+ *
+ * Errors, before any device work, *out NULL on every failure: DVO_AMD_ERR_INVALID_ARGUMENT (reason in dvo_amd_last_error()) for a
+ * NULL pointer, an unknown rule, GRID with cell[l] < 1 on a level the pyramid has, a non-finite threshold, a depth_weight that
+ * is negative or not finite; then `within` as dvo_amd_pyramid_select_masked checks a mask: DVO_AMD_ERR_INVALID_ARGUMENT for
+ * another level-0 size or fewer levels than the pyramid, DVO_AMD_ERR_DEVICE_MISMATCH for another device.
+ *
+ * Cost.  The number of kernel launches depends on the pyramid's level count and the rule alone (12 per level for TOPK, 2 for
+ * GRID); nothing comes back to the host between them -- the digits of the exact radix select over the keys and the tie count
+ * are chosen by a device kernel -- and the call synchronises once, at its end.
+ *
+ * Not covered: whatever takes no mask takes no budget (the list under "Selection masks").
+ */
+#define DVO_AMD_BUDGET_TOPK 0
+#define DVO_AMD_BUDGET_GRID 1
+typedef struct dvo_amd_budget_options {
+  int rule;                                   /* DVO_AMD_BUDGET_TOPK | DVO_AMD_BUDGET_GRID */
+  long long budget[DVO_AMD_MAX_LEVELS];       /* TOPK: points kept on level l; < 0 = every candidate of that level */
+  int cell[DVO_AMD_MAX_LEVELS];               /* GRID: cell edge in pixels of level l, >= 1 (1 = every candidate) */
+  float intensity_threshold, depth_threshold; /* the predicate that makes a pixel a candidate */
+  float depth_weight;                         /* >= 0, finite */
+  const dvo_amd_mask *within;                 /* optional: candidates only where this mask keeps */
+} dvo_amd_budget_options;
+/* TOPK, every budget -1, every cell 1, thresholds 0, depth_weight 0, within NULL */
+void dvo_amd_default_budget_options(dvo_amd_budget_options *opt);
+int dvo_amd_mask_create_budget(dvo_amd_pyramid *pyramid, const dvo_amd_budget_options *opt, dvo_amd_mask **out);
+
 /* n independent match() calls advanced in lock step on one GPU (the shape of LocalTracker::update's tbb::parallel_invoke,
  * local_tracker.cpp:184, and of the loop-closure validator's parallel_reduce, keyframe_graph.cpp:576-593).
  * T_inits: n x 16 doubles or NULL.  Results are identical to n dvo_amd_match() calls BIT FOR BIT: a pair's result is a function

@@ -475,6 +475,32 @@ class SelectionMask {
     return SelectionMask(m, device);
   }
 
+  // A point budget, ranked on the device from the resident pyramid (dvo_amd_mask_create_budget; the rules are pinned in
+  // dvo_amd.h).  A candidate passes the threshold predicate and, if given, `within`; its strength is
+  // Ix^2 + Iy^2 + depth_weight * (Zx^2 + Zy^2), ties go to the lowest pixel index.
+  //   topK   level l keeps its budgets[l] strongest candidates (negative, or no entry for the level: every candidate)
+  //   grid   level l keeps the strongest candidate of every cells[l] x cells[l] cell (no entry for the level: 1, every candidate)
+  // The pyramid is built to at least budgets.size() / cells.size() levels first (RgbdImagePyramid::build); the mask has the
+  // levels the pyramid has then, so build the levels the tracker will use before asking for the mask.
+  static SelectionMask topK(RgbdImagePyramid &pyramid, const std::vector<long long> &budgets, float intensity_threshold = 0.0f,
+                            float depth_threshold = 0.0f, float depth_weight = 0.0f, const SelectionMask *within = nullptr) {
+    dvo_amd_budget_options o;
+    dvo_amd_default_budget_options(&o);
+    o.rule = DVO_AMD_BUDGET_TOPK;
+    for (size_t l = 0; l < budgets.size() && l < (size_t)DVO_AMD_MAX_LEVELS; ++l) o.budget[l] = budgets[l];
+    pyramid.build(std::max<size_t>(budgets.size(), 1));
+    return budget(pyramid, o, intensity_threshold, depth_threshold, depth_weight, within, "SelectionMask::topK");
+  }
+  static SelectionMask grid(RgbdImagePyramid &pyramid, const std::vector<int> &cells, float intensity_threshold = 0.0f,
+                            float depth_threshold = 0.0f, float depth_weight = 0.0f, const SelectionMask *within = nullptr) {
+    dvo_amd_budget_options o;
+    dvo_amd_default_budget_options(&o);
+    o.rule = DVO_AMD_BUDGET_GRID;
+    for (size_t l = 0; l < cells.size() && l < (size_t)DVO_AMD_MAX_LEVELS; ++l) o.cell[l] = cells[l];
+    pyramid.build(std::max<size_t>(cells.size(), 1));
+    return budget(pyramid, o, intensity_threshold, depth_threshold, depth_weight, within, "SelectionMask::grid");
+  }
+
   bool valid() const { return (bool)handle_; }
   dvo_amd_mask *handle() const { return handle_.get(); }
   int device() const { return device_; }
@@ -502,6 +528,14 @@ class SelectionMask {
     void operator()(dvo_amd_mask *m) const { dvo_amd_mask_release(m); }
   };
   SelectionMask(dvo_amd_mask *m, int device) : handle_(m, Release()), device_(device) {}
+  static SelectionMask budget(const RgbdImagePyramid &pyramid, dvo_amd_budget_options &o, float intensity_threshold,
+                              float depth_threshold, float depth_weight, const SelectionMask *within, const char *where) {
+    o.intensity_threshold = intensity_threshold, o.depth_threshold = depth_threshold, o.depth_weight = depth_weight;
+    o.within = within ? within->need() : nullptr;
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_create_budget(pyramid.handle(), &o, &m), where);
+    return SelectionMask(m, pyramid.device());
+  }
   dvo_amd_mask *need() const {
     if (!handle_) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "SelectionMask: empty");
     return handle_.get();
