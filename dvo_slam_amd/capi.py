@@ -53,6 +53,8 @@ EXPORTS = [
     "dvo_amd_mask_create", "dvo_amd_mask_create_levels", "dvo_amd_mask_retain", "dvo_amd_mask_release", "dvo_amd_mask_info",
     "dvo_amd_mask_download", "dvo_amd_pyramid_select_masked", "dvo_amd_match_masked", "dvo_amd_match_many_masked",
     "dvo_amd_default_budget_options", "dvo_amd_mask_create_budget",
+    "dvo_amd_default_mask_warp_options", "dvo_amd_mask_combine", "dvo_amd_mask_morph", "dvo_amd_mask_warp", "dvo_amd_mask_warp_many",
+    "dvo_amd_debug_mask_ops_timing",
 ]
 
 
@@ -152,6 +154,15 @@ class BudgetOptions(C.Structure):
                 ("intensity_threshold", C.c_float), ("depth_threshold", C.c_float), ("depth_weight", C.c_float),
                 ("within", C.c_void_p)]
 
+
+class MaskWarpOptions(C.Structure):
+    """dvo_amd_mask_warp_options, field for field"""
+    _fields_ = [("near_z", C.c_float), ("depth_sigmas", C.c_float), ("unseen_keep", C.c_int), ("inconsistent_keep", C.c_int)]
+
+
+# one record of dvo_amd_mask_warp's counts, field for field
+MASK_WARP_COUNTS = ("valid", "behind", "outside", "no_depth", "consistent", "occluded", "seen_through", "dropped_by_source")
+MASK_WARP_DTYPE = np.dtype([(name, np.int64) for name in MASK_WARP_COUNTS])
 
 # dvo_amd_covisibility_counts, field for field
 COVISIBILITY_DTYPE = np.dtype([(name, np.uint32) for name in ("valid", "behind", "outside", "no_depth", "consistent", "occluded",
@@ -337,6 +348,14 @@ def lib():
     L.dvo_amd_default_budget_options.argtypes = [C.POINTER(BudgetOptions)]
     L.dvo_amd_default_budget_options.restype = None
     L.dvo_amd_mask_create_budget.argtypes = [vp, C.POINTER(BudgetOptions), C.POINTER(vp)]
+    L.dvo_amd_default_mask_warp_options.argtypes = [C.POINTER(MaskWarpOptions)]
+    L.dvo_amd_default_mask_warp_options.restype = None
+    L.dvo_amd_mask_combine.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
+    L.dvo_amd_mask_morph.argtypes = [vp, C.c_int, ip, C.POINTER(vp)]
+    L.dvo_amd_mask_warp.argtypes = [vp, vp, vp, dp, C.POINTER(MaskWarpOptions), C.POINTER(vp), C.POINTER(C.c_longlong)]
+    L.dvo_amd_mask_warp_many.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(MaskWarpOptions),
+                                         C.POINTER(vp), C.POINTER(C.c_longlong)]
+    L.dvo_amd_debug_mask_ops_timing.argtypes = [C.c_int, C.c_int, dp]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -496,12 +515,41 @@ def _mask_bytes(a):
 MASK_ALL, MASK_ANY = 0, 1
 MAX_MASKED_SELECTIONS = 8
 BUDGET_TOPK, BUDGET_GRID = 0, 1
+MASK_AND, MASK_OR, MASK_ANDNOT, MASK_NOT = 0, 1, 2, 3
+MASK_DILATE, MASK_ERODE = 0, 1
+MASK_MAX_RADIUS = 64
 
 
 def level_budgets(k0: int, levels: int, minimum: int = 0) -> list:
     """A level-0 point budget as per-level budgets for SelectionMask.from_budget: level l has a quarter of the pixels of level
     l - 1, so it gets max(minimum, k0 >> 2l)."""
     return [max(int(minimum), int(k0) >> (2 * l)) for l in range(levels)]
+
+
+def level_radii(r0: int, levels: int) -> list:
+    """A radius in pixels of level 0 as per-level radii for SelectionMask.dilate / erode: level l has half the resolution of
+    level l - 1, so it gets r0 / 2^l rounded up, (r0 + (1 << l) - 1) >> l."""
+    return [(int(r0) + (1 << l) - 1) >> l for l in range(levels)]
+
+
+def mask_warp_options(**options) -> MaskWarpOptions:
+    """dvo_amd_default_mask_warp_options (near_z 0.1, depth_sigmas 20, unseen_keep 1, inconsistent_keep 1) with the given fields
+    replaced"""
+    opt = MaskWarpOptions()
+    lib().dvo_amd_default_mask_warp_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in ("near_z", "depth_sigmas", "unseen_keep", "inconsistent_keep"):
+            raise TypeError(f"unknown mask warp option {k!r}")
+        setattr(opt, k, int(v) if k.endswith("_keep") else float(v))
+    return opt
+
+
+def mask_ops_timing(enable: bool = True, device: int = 0) -> float:
+    """(instrumentation) switches the event bracket around every mask operation (combine, dilate / erode, warp) of `device` on or
+    off and returns the device time of the most recent bracketed call in ms (dvo_amd_debug_mask_ops_timing)"""
+    ms = C.c_double()
+    _check(lib().dvo_amd_debug_mask_ops_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_mask_ops_timing")
+    return ms.value
 
 
 def _per_level(value, default, what):
@@ -592,6 +640,87 @@ class SelectionMask:
         _check(lib().dvo_amd_mask_create_budget(pyramid._h, C.byref(opt), C.byref(self._h)), "dvo_amd_mask_create_budget")
         self.device = pyramid.device
         return self
+
+    # ---- masks from masks, on the device (the rules are pinned in include/dvo_amd.h under "Mask operations")
+
+    @classmethod
+    def _own(cls, handle, device):
+        self = cls.__new__(cls)
+        self._h, self.device = handle, device
+        return self
+
+    def _combine(self, other, op):
+        if other is not None and not isinstance(other, SelectionMask):
+            return NotImplemented
+        out = C.c_void_p()
+        _check(lib().dvo_amd_mask_combine(self._h, None if other is None else other._h, op, C.byref(out)), "dvo_amd_mask_combine")
+        return SelectionMask._own(out, self.device)
+
+    def __and__(self, other):
+        """kept where both keep, level by level (dvo_amd_mask_combine)"""
+        return self._combine(other, MASK_AND)
+
+    def __or__(self, other):
+        """kept where either keeps"""
+        return self._combine(other, MASK_OR)
+
+    def __invert__(self):
+        """kept where this mask drops"""
+        return self._combine(None, MASK_NOT)
+
+    def andnot(self, other):
+        """kept where this mask keeps and `other` drops"""
+        return self._combine(other, MASK_ANDNOT)
+
+    def _morph(self, op, radius):
+        levels = self.info()["levels"]
+        radii = [int(r) for r in radius] if hasattr(radius, "__len__") else level_radii(radius, levels)
+        if len(radii) < levels:
+            raise ValueError(f"{len(radii)} radii for a mask of {levels} levels")
+        out = C.c_void_p()
+        _check(lib().dvo_amd_mask_morph(self._h, op, (C.c_int * len(radii))(*radii), C.byref(out)), "dvo_amd_mask_morph")
+        return SelectionMask._own(out, self.device)
+
+    def dilate(self, radius):
+        """Grown by a square window: a pixel is kept iff any pixel of the (2 r + 1)^2 window around it, clipped to the plane, is
+        kept.  radius: an int in pixels of level 0 (level l gets level_radii(radius, levels)[l]) or one radius per level.  Every
+        level is grown on its own (dvo_amd_mask_morph)."""
+        return self._morph(MASK_DILATE, radius)
+
+    def erode(self, radius):
+        """Shrunk by a square window: a pixel is kept iff every pixel of the clipped window around it is kept; radius as for
+        dilate"""
+        return self._morph(MASK_ERODE, radius)
+
+    def warp(self, source, target, T, counts: bool = False, **options):
+        """This mask, on the pixels of the pyramid `source`, carried onto the pixels of the pyramid `target` (dvo_amd_mask_warp).
+        T: 4x4, maps points of the target camera frame into the source camera frame -- for tracker.match(source, target) that is
+        result.Transformation as returned.  options: near_z, depth_sigmas, unseen_keep, inconsistent_keep.  Returns the mask, or
+        with counts=True (mask, counts): one MASK_WARP_DTYPE record per level."""
+        masks, cnt = SelectionMask.warp_many([self], [source], [target], [T], counts=True, **options)
+        return (masks[0], cnt[0]) if counts else masks[0]
+
+    @staticmethod
+    def warp_many(masks, sources, targets, Ts, counts: bool = False, **options):
+        """n warps in one call and one kernel launch (dvo_amd_mask_warp_many): masks[k] on sources[k] onto targets[k] by Ts[k].
+        Returns the list of masks, or with counts=True (masks, [counts of pair k: one MASK_WARP_DTYPE record per level])."""
+        n = len(masks)
+        if not (len(sources) == len(targets) == len(Ts) == n):
+            raise ValueError("one source, one target and one transformation per mask")
+        opt = mask_warp_options(**options)
+        vp = C.c_void_p
+        T = np.ascontiguousarray(np.stack([_pose_cm(t) for t in Ts]) if n else np.zeros((0, 4, 4)), dtype=np.float64)
+        levels = [t.levels() for t in targets]
+        cnt = np.zeros(max(1, sum(levels)), MASK_WARP_DTYPE)
+        out = (vp * max(1, n))()
+        _check(lib().dvo_amd_mask_warp_many(n, (vp * max(1, n))(*[m._h for m in masks]), (vp * max(1, n))(*[p._h for p in sources]),
+                                            (vp * max(1, n))(*[p._h for p in targets]), T.ctypes.data_as(C.POINTER(C.c_double)),
+                                            C.byref(opt), out, cnt.ctypes.data_as(C.POINTER(C.c_longlong))), "dvo_amd_mask_warp_many")
+        made = [SelectionMask._own(vp(out[k]), targets[k].device) for k in range(n)]
+        if not counts:
+            return made
+        at = np.concatenate([[0], np.cumsum(levels)]).astype(int)
+        return made, [cnt[at[k]:at[k + 1]].copy() for k in range(n)]
 
     def __del__(self):
         h = getattr(self, "_h", None)

@@ -12,6 +12,7 @@
 //   dvo_rectify.cpp   remap tables (lens undistortion, arbitrary maps) and the kernels that resample a frame through one
 //   dvo_mask.cpp      selection masks: the device-resident mask pyramid behind a masked point selection
 //   dvo_budget.cpp    point-budget masks: a mask ranked on the device from a resident pyramid (top-K radix select, per-cell argmax)
+//   dvo_mask_ops.cpp  masks from masks: combine, dilate / erode, warp onto another frame through both frames' depth
 //   dvo_register.cpp  depth-to-colour registration: the kernels that splat another camera's raw depth into level 0's depth plane
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once

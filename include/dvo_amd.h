@@ -548,6 +548,91 @@ typedef struct dvo_amd_budget_options {
 void dvo_amd_default_budget_options(dvo_amd_budget_options *opt);
 int dvo_amd_mask_create_budget(dvo_amd_pyramid *pyramid, const dvo_amd_budget_options *opt, dvo_amd_mask **out);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Mask operations: combine two masks, grow or shrink one, carry one onto another frame -- on the device.
+ *
+ * What a user of a segmentation mask does next: "not a person" AND "a GRID budget"; dilate a border that is never pixel-exact;
+ * take the mask of the keyframe the network saw to the frame it did not see.  Every entry below reads its inputs only and
+ * returns a new dvo_amd_mask -- immutable, refcounted, with a serial of its own -- that enters wherever a mask enters.  *out is
+ * NULL on every failure.  Argument errors (DVO_AMD_ERR_INVALID_ARGUMENT with a reason in dvo_amd_last_error(), then
+ * DVO_AMD_ERR_DEVICE_MISMATCH) are reported before any device work and before DVO_AMD_ERR_NO_DEVICE.  The number of kernel
+ * launches does not depend on the content, only on the level count at most: each call is ONE launch (combine and morph over all
+ * levels, warp over all pairs and levels of the call), and it synchronises once, at its end.
+ *
+ * dvo_amd_mask_combine(a, b, op, out).  Level by level, out[l][i] = op(a[l][i] != 0, b[l][i] != 0) with op one of
+ *     DVO_AMD_MASK_AND      a && b
+ *     DVO_AMD_MASK_OR       a || b
+ *     DVO_AMD_MASK_ANDNOT   a && !b
+ *     DVO_AMD_MASK_NOT      !a         (b must be NULL; for every other op b must not be)
+ * a and b must have the same level-0 size and the same level count (else INVALID_ARGUMENT) and live on one device (else
+ * DEVICE_MISMATCH).
+ *
+ * dvo_amd_mask_morph(mask, op, radius, out).  op is DVO_AMD_MASK_DILATE or DVO_AMD_MASK_ERODE, the structuring element of level l
+ * the square of edge 2 * radius[l] + 1.  With W(x, y) the window around (x, y) CLIPPED TO THE PLANE:
+ *     dilate   out[l](x, y) = 1  iff  any pixel of W(x, y) is kept in mask[l]
+ *     erode    out[l](x, y) = 1  iff  every pixel of W(x, y) is kept in mask[l]
+ * Pixels outside the plane have no vote (OpenCV's default border for both operations), so erode(m) == NOT dilate(NOT m).
+ * radius[l] == 0 copies the level; a radius at least as large as the plane saturates it and is no error.
+ * 0 <= radius[l] <= DVO_AMD_MASK_MAX_RADIUS on every level the mask has, else INVALID_ARGUMENT; entries beyond the mask's levels
+ * are not read.  Every level is processed on its own from the same level of the input: that is NOT morphing level 0 and deriving
+ * the coarser levels again (a caller who wants that downloads level 0 of the result and calls dvo_amd_mask_create).  A radius of
+ * r0 pixels of level 0 is (r0 + (1 << l) - 1) >> l pixels of level l, rounded up.
+ *
+ * dvo_amd_mask_warp_many(n, masks, sources, targets, T, opt, out, counts); dvo_amd_mask_warp is the case n = 1.  masks[k], a mask
+ * on the pixels of the pyramid sources[k], is carried onto the pixels of the pyramid targets[k].  T: n x 16 doubles, column-major
+ * like every transformation of this interface; T[k] maps points of the TARGET camera frame into the SOURCE camera frame.  For
+ * dvo_amd_match(reference = source, current = target) that is result.transformation as returned (dense_tracking.cpp:371 returns
+ * the inverse of the estimate).  The output has the target's level-0 size and level count; level l comes from level l of the
+ * mask and of both pyramids.  The sizes and intrinsics of source and target may differ.
+ * The rule is a gather over the target's pixels -- no scatter, no holes -- and is dvo_amd_covisibility's rule with a = target and
+ * b = source.  The host casts rows 0..2 of T to float.  A target pixel (u, v) of level l whose depth z is not finite has the
+ * outcome no_target_depth.  Otherwise, in fp32, every operation rounded on its own:
+ *     (x, y, z) = (tx[u] z, ty[v] z, z)                          the target level's rays
+ *     q         = ((T0 x + T1 y) + T2 z) + T3                    per row of T
+ *     !(qz >= near_z)                                            -> behind
+ *     pu = floorf(((qx fx) / qz + ox) + 0.5f), pv likewise       the source level's intrinsics
+ *     !(0 <= pu <= ws - 1 && 0 <= pv <= hs - 1), tested in float -> outside
+ *     Zs = source depth at (pu, pv) is NaN                       -> no_depth
+ *     d = Zs - qz, tol = depth_sigmas * (0.0012f + 0.0019f * (qz - 0.4f)^2)
+ *     d < -tol -> occluded,  d > tol -> seen_through,  else consistent
+ *     out[l](u, v) = masks[k][l][pv * ws + pu] != 0      if consistent
+ *                  = opt->inconsistent_keep != 0         if occluded or seen_through
+ *                  = opt->unseen_keep != 0               for every other outcome
+ * The defaults (near_z 0.1, depth_sigmas 20, unseen_keep 1, inconsistent_keep 1) transport the source's verdicts and add none of
+ * their own; inconsistent_keep = 0 drops what moved or was disoccluded between the two frames.
+ * counts (may be NULL): for pair k, in pair order, one record of eight long long per level of targets[k]:
+ *     valid, behind, outside, no_depth, consistent, occluded, seen_through, dropped_by_source
+ * valid = target pixels with a finite depth = the sum of the next six; dropped_by_source = consistent pixels whose source mask
+ * byte is 0.  The first seven are dvo_amd_covisibility's of the ordered pair (target, source) at that level.
+ * Errors: INVALID_ARGUMENT for a NULL pointer (inside the arrays too), n < 0, a non-finite entry of T, near_z not finite or
+ * <= 0, depth_sigmas not finite or < 0, a source with fewer levels than its target, a mask that does not fit its source as
+ * dvo_amd_pyramid_select_masked checks it; then DEVICE_MISMATCH unless all objects of the call live on one device.
+ *
+ * Not covered: there are still no masks on the current side (see "Selection masks").
+ */
+#define DVO_AMD_MASK_AND 0
+#define DVO_AMD_MASK_OR 1
+#define DVO_AMD_MASK_ANDNOT 2
+#define DVO_AMD_MASK_NOT 3
+#define DVO_AMD_MASK_DILATE 0
+#define DVO_AMD_MASK_ERODE 1
+#define DVO_AMD_MASK_MAX_RADIUS 64
+typedef struct dvo_amd_mask_warp_options {
+  float near_z;          /* > 0, finite */
+  float depth_sigmas;    /* >= 0, finite */
+  int unseen_keep;       /* the output where the target pixel has no depth or lands behind, outside or on no depth */
+  int inconsistent_keep; /* the output where the two depths disagree (occluded, seen_through) */
+} dvo_amd_mask_warp_options;
+/* near_z 0.1, depth_sigmas 20, unseen_keep 1, inconsistent_keep 1 */
+void dvo_amd_default_mask_warp_options(dvo_amd_mask_warp_options *opt);
+int dvo_amd_mask_combine(const dvo_amd_mask *a, const dvo_amd_mask *b, int op, dvo_amd_mask **out);
+int dvo_amd_mask_morph(const dvo_amd_mask *mask, int op, const int *radius /* [levels] */, dvo_amd_mask **out);
+int dvo_amd_mask_warp(const dvo_amd_mask *mask, const dvo_amd_pyramid *source, const dvo_amd_pyramid *target, const double *T,
+                      const dvo_amd_mask_warp_options *opt, dvo_amd_mask **out, long long *counts /* [levels][8] or NULL */);
+int dvo_amd_mask_warp_many(int n, const dvo_amd_mask *const *masks, const dvo_amd_pyramid *const *sources,
+                           const dvo_amd_pyramid *const *targets, const double *T, const dvo_amd_mask_warp_options *opt,
+                           dvo_amd_mask **out, long long *counts /* packed in pair order, or NULL */);
+
 /* n independent match() calls advanced in lock step on one GPU (the shape of LocalTracker::update's tbb::parallel_invoke,
  * local_tracker.cpp:184, and of the loop-closure validator's parallel_reduce, keyframe_graph.cpp:576-593).
  * T_inits: n x 16 doubles or NULL.  Results are identical to n dvo_amd_match() calls BIT FOR BIT: a pair's result is a function

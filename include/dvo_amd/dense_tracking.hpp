@@ -501,6 +501,41 @@ class SelectionMask {
     return budget(pyramid, o, intensity_threshold, depth_threshold, depth_weight, within, "SelectionMask::grid");
   }
 
+  // Masks from masks, on the device (dvo_amd.h, "Mask operations"): every result is a new mask, the operands are only read.
+  //   a & b, a | b, ~a, a.andNot(b)   level by level; a and b of one size and level count
+  //   dilated(r) / eroded(r)          by the square of edge 2 r + 1 clipped to the plane; r in pixels of level 0 (level l gets
+  //                                   r / 2^l rounded up) or one radius per level; every level on its own
+  //   warped(source, target, T)       this mask, on the pixels of `source`, carried onto the pixels of `target`: T maps points of
+  //                                   the target camera frame into the source camera frame -- for tracker.match(source, target,
+  //                                   result) that is result.Transformation as returned.  Both pyramids must hold their levels
+  //                                   (RgbdImagePyramid::build; a match has built them); the result has the target's.
+  SelectionMask operator&(const SelectionMask &other) const { return combine(&other, DVO_AMD_MASK_AND, "SelectionMask::operator&"); }
+  SelectionMask operator|(const SelectionMask &other) const { return combine(&other, DVO_AMD_MASK_OR, "SelectionMask::operator|"); }
+  SelectionMask operator~() const { return combine(nullptr, DVO_AMD_MASK_NOT, "SelectionMask::operator~"); }
+  SelectionMask andNot(const SelectionMask &other) const { return combine(&other, DVO_AMD_MASK_ANDNOT, "SelectionMask::andNot"); }
+  SelectionMask dilated(int radius) const { return morph(DVO_AMD_MASK_DILATE, levelRadii(radius), "SelectionMask::dilated"); }
+  SelectionMask dilated(const std::vector<int> &radii) const { return morph(DVO_AMD_MASK_DILATE, radii, "SelectionMask::dilated"); }
+  SelectionMask eroded(int radius) const { return morph(DVO_AMD_MASK_ERODE, levelRadii(radius), "SelectionMask::eroded"); }
+  SelectionMask eroded(const std::vector<int> &radii) const { return morph(DVO_AMD_MASK_ERODE, radii, "SelectionMask::eroded"); }
+
+  struct WarpOptions : dvo_amd_mask_warp_options {
+    WarpOptions() { dvo_amd_default_mask_warp_options(this); }
+  };
+  struct WarpCounts {  // one level's record
+    long long valid, behind, outside, no_depth, consistent, occluded, seen_through, dropped_by_source;
+  };
+  SelectionMask warped(const RgbdImagePyramid &source, const RgbdImagePyramid &target, const AffineTransformd &transformation,
+                       const WarpOptions &options = WarpOptions(), std::vector<WarpCounts> *counts = nullptr) const {
+    static_assert(sizeof(WarpCounts) == 8 * sizeof(long long), "a WarpCounts is one record of dvo_amd_mask_warp's counts");
+    WarpCounts records[DVO_AMD_MAX_LEVELS];
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_warp(need(), source.handle(), target.handle(), data(transformation), &options, &m, &records[0].valid),
+                  "SelectionMask::warped");
+    SelectionMask out(m, target.device());
+    if (counts) counts->assign(records, records + out.info().levels);
+    return out;
+  }
+
   bool valid() const { return (bool)handle_; }
   dvo_amd_mask *handle() const { return handle_.get(); }
   int device() const { return device_; }
@@ -535,6 +570,25 @@ class SelectionMask {
     dvo_amd_mask *m = nullptr;
     detail::check(dvo_amd_mask_create_budget(pyramid.handle(), &o, &m), where);
     return SelectionMask(m, pyramid.device());
+  }
+  SelectionMask combine(const SelectionMask *other, int op, const char *where) const {
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_combine(need(), other ? other->need() : nullptr, op, &m), where);
+    return SelectionMask(m, device_);
+  }
+  SelectionMask morph(int op, const std::vector<int> &radii, const char *where) const {
+    int r[DVO_AMD_MAX_LEVELS] = {0};
+    if (radii.size() < (size_t)info().levels) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+    for (size_t l = 0; l < radii.size() && l < (size_t)DVO_AMD_MAX_LEVELS; ++l) r[l] = radii[l];
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_morph(need(), op, r, &m), where);
+    return SelectionMask(m, device_);
+  }
+  // a radius in pixels of level 0 on every level: (r0 + (1 << l) - 1) >> l
+  static std::vector<int> levelRadii(int r0) {
+    std::vector<int> r(DVO_AMD_MAX_LEVELS);
+    for (int l = 0; l < DVO_AMD_MAX_LEVELS; ++l) r[l] = (r0 + (1 << l) - 1) >> l;
+    return r;
   }
   dvo_amd_mask *need() const {
     if (!handle_) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "SelectionMask: empty");

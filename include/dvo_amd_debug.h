@@ -232,6 +232,10 @@ int dvo_amd_debug_ingest_timing(int device, int enable, double *last_ms);
  * level count and of build_selection alone, whatever the frame count), copies (two per host frame, the frame table, the
  * counters) and host synchronisations (one).  Any output may be NULL; all zero before the first such call */
 int dvo_amd_debug_batch_build_stats(int device, int *kernel_launches, int *copies, int *synchronisations);
+/* with enable != 0 every later dvo_amd_mask_combine, dvo_amd_mask_morph, dvo_amd_mask_warp and dvo_amd_mask_warp_many on `device`
+ * is bracketed by two events on the device's internal stream, from before its first upload to behind its last kernel; *last_ms
+ * (may be NULL) receives the device time of the most recent bracketed call */
+int dvo_amd_debug_mask_ops_timing(int device, int enable, double *last_ms);
 
 #ifdef __cplusplus
 }
