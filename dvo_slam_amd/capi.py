@@ -55,6 +55,7 @@ EXPORTS = [
     "dvo_amd_default_budget_options", "dvo_amd_mask_create_budget",
     "dvo_amd_default_mask_warp_options", "dvo_amd_mask_combine", "dvo_amd_mask_morph", "dvo_amd_mask_warp", "dvo_amd_mask_warp_many",
     "dvo_amd_debug_mask_ops_timing",
+    "dvo_amd_default_residual_mask_options", "dvo_amd_mask_from_residuals", "dvo_amd_mask_from_residuals_many",
 ]
 
 
@@ -159,6 +160,17 @@ class MaskWarpOptions(C.Structure):
     """dvo_amd_mask_warp_options, field for field"""
     _fields_ = [("near_z", C.c_float), ("depth_sigmas", C.c_float), ("unseen_keep", C.c_int), ("inconsistent_keep", C.c_int)]
 
+
+class ResidualMaskOptions(C.Structure):
+    """dvo_amd_residual_mask_options, field for field"""
+    _fields_ = [("precision", (C.c_float * 4) * MAX_LEVELS), ("max_distance", C.c_float * MAX_LEVELS), ("invalid_keep", C.c_int),
+                ("unevaluated_keep", C.c_int)]
+
+
+# one record of dvo_amd_mask_from_residuals' counts, field for field
+RESIDUAL_MASK_COUNTS = ("evaluated", "invalid", "inlier", "outlier", "kept")
+RESIDUAL_MASK_DTYPE = np.dtype([(name, np.int64) for name in RESIDUAL_MASK_COUNTS])
+RESIDUAL_MASK_MAX_DISTANCE = 9.2103  # -2 ln 0.01: the 99 % point of chi-square with two degrees of freedom
 
 # one record of dvo_amd_mask_warp's counts, field for field
 MASK_WARP_COUNTS = ("valid", "behind", "outside", "no_depth", "consistent", "occluded", "seen_through", "dropped_by_source")
@@ -356,6 +368,12 @@ def lib():
     L.dvo_amd_mask_warp_many.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(MaskWarpOptions),
                                          C.POINTER(vp), C.POINTER(C.c_longlong)]
     L.dvo_amd_debug_mask_ops_timing.argtypes = [C.c_int, C.c_int, dp]
+    L.dvo_amd_default_residual_mask_options.argtypes = [C.POINTER(ResidualMaskOptions)]
+    L.dvo_amd_default_residual_mask_options.restype = None
+    L.dvo_amd_mask_from_residuals.argtypes = [vp, vp, vp, dp, C.POINTER(ResidualMaskOptions), C.POINTER(vp), C.POINTER(C.c_longlong),
+                                              C.POINTER(C.POINTER(C.c_float))]
+    L.dvo_amd_mask_from_residuals_many.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(ResidualMaskOptions),
+                                                   C.POINTER(vp), C.POINTER(C.c_longlong)]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -544,6 +562,48 @@ def mask_warp_options(**options) -> MaskWarpOptions:
     return opt
 
 
+def residual_mask_options(result=None, levels: int = MAX_LEVELS, max_distance=RESIDUAL_MASK_MAX_DISTANCE, **keeps) -> ResidualMaskOptions:
+    """dvo_amd_default_residual_mask_options (max_distance 9.2103 on every level, both keeps 0) with precision[l] filled from a
+    `Result` for l < levels: the TDistributionPrecision of the last iteration of level l.  A level the match did not run (level 0
+    under the default configuration) takes the precision of the nearest level that ran, ties to the finer one.  ValueError if the
+    result holds no iteration statistics.  result=None leaves the precisions unset (the library refuses them).  max_distance: one
+    value for every level, or one per level; keeps: invalid_keep, unevaluated_keep."""
+    opt = ResidualMaskOptions()
+    lib().dvo_amd_default_residual_mask_options(C.byref(opt))
+    if not 1 <= int(levels) <= MAX_LEVELS:
+        raise ValueError(f"levels must be 1..{MAX_LEVELS}")
+    dist = [float(v) for v in max_distance] if hasattr(max_distance, "__len__") else [float(max_distance)] * MAX_LEVELS
+    if len(dist) > MAX_LEVELS:
+        raise ValueError(f"max_distance: more than {MAX_LEVELS} levels")
+    for l, v in enumerate(dist):
+        opt.max_distance[l] = v
+    for k, v in keeps.items():
+        if k not in ("invalid_keep", "unevaluated_keep"):
+            raise TypeError(f"unknown residual mask option {k!r}")
+        setattr(opt, k, int(v))
+    if result is not None:
+        ran = {int(L["Id"]): L["Iterations"][-1]["TDistributionPrecision"] for L in result.Levels if L["Iterations"]}
+        if not ran:
+            raise ValueError("the result holds no iteration statistics (match with stats=True)")
+        for l in range(int(levels)):
+            nearest = min(ran, key=lambda have: (abs(have - l), have))
+            P = np.asarray(ran[nearest], np.float64)
+            opt.precision[l][:] = [P[0, 0], P[1, 0], P[0, 1], P[1, 1]]  # column-major
+    return opt
+
+
+def rigid_inverse(T) -> np.ndarray:
+    """inv(T) of a rigid 4x4 transformation as (R^T, -R^T t), every sum in a fixed order: the same sixteen doubles as
+    dvo::core::SelectionMask::rigidInverse and examples/residual_mask_example.c form"""
+    T = np.asarray(T, dtype=np.float64)
+    out = np.eye(4)
+    for i in range(3):
+        for j in range(3):
+            out[i, j] = T[j, i]
+        out[i, 3] = -((T[0, i] * T[0, 3] + T[1, i] * T[1, 3]) + T[2, i] * T[2, 3])
+    return out
+
+
 def mask_ops_timing(enable: bool = True, device: int = 0) -> float:
     """(instrumentation) switches the event bracket around every mask operation (combine, dilate / erode, warp) of `device` on or
     off and returns the device time of the most recent bracketed call in ms (dvo_amd_debug_mask_ops_timing)"""
@@ -717,6 +777,74 @@ class SelectionMask:
                                             (vp * max(1, n))(*[p._h for p in targets]), T.ctypes.data_as(C.POINTER(C.c_double)),
                                             C.byref(opt), out, cnt.ctypes.data_as(C.POINTER(C.c_longlong))), "dvo_amd_mask_warp_many")
         made = [SelectionMask._own(vp(out[k]), targets[k].device) for k in range(n)]
+        if not counts:
+            return made
+        at = np.concatenate([[0], np.cumsum(levels)]).astype(int)
+        return made, [cnt[at[k]:at[k + 1]].copy() for k in range(n)]
+
+    # ---- a mask from an alignment's residuals (the rule is pinned in include/dvo_amd.h under "Residual masks")
+
+    @staticmethod
+    def _residual_T(T, result):
+        if T is None:
+            if result is None:
+                raise ValueError("give T (reference -> current, the estimate) or result=")
+            T = rigid_inverse(result.Transformation)
+        return _pose_cm(T)
+
+    @classmethod
+    def from_residuals(cls, tracker, reference, current, T=None, result=None, options=None, counts: bool = False,
+                       distance: bool = False):
+        """The inliers of the alignment of `current` against `reference` at T, on the reference's pixels
+        (dvo_amd_mask_from_residuals): a pixel is kept iff its residual pair is valid and its Mahalanobis distance under the
+        level's precision is at most the level's max_distance.  T: 4x4, reference -> current, the ESTIMATE -- what
+        computeIntensityErrorImage takes.  tracker.match returns the inverse of the estimate, so with result= and no T the
+        binding passes inv(result.Transformation), formed by rigid_inverse.  options: a ResidualMaskOptions; None:
+        residual_mask_options(result, reference.levels()).  Returns the mask; with counts=True also one RESIDUAL_MASK_DTYPE record per level; with
+        distance=True also the per-level float32 planes of the distance (NaN where the pixel is unevaluated or invalid)."""
+        levels = reference.levels()
+        opt = options if options is not None else residual_mask_options(result, levels)
+        Tc = cls._residual_T(T, result)
+        cnt = np.zeros(levels, RESIDUAL_MASK_DTYPE)
+        planes = []
+        for l in range(levels):
+            w, h, _ = reference.level_info(l)
+            planes.append(np.empty((h, w), np.float32))
+        ptrs = (C.POINTER(C.c_float) * levels)(*[_fp(p) for p in planes])
+        out = C.c_void_p()
+        _check(lib().dvo_amd_mask_from_residuals(tracker._h, reference._h, current._h, Tc.ctypes.data_as(C.POINTER(C.c_double)),
+                                                 C.byref(opt), C.byref(out), cnt.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                                 ptrs if distance else None), "dvo_amd_mask_from_residuals")
+        got = (cls._own(out, reference.device),) + ((cnt,) if counts else ()) + ((planes,) if distance else ())
+        return got[0] if len(got) == 1 else got
+
+    @staticmethod
+    def from_residuals_many(tracker, references, currents, Ts=None, results=None, options=None, counts: bool = False):
+        """n inlier masks in one call and one kernel launch (dvo_amd_mask_from_residuals_many): pair k is (references[k],
+        currents[k]) at Ts[k] (reference -> current; None: inv(results[k].Transformation)) under options[k] (None:
+        residual_mask_options(results[k], levels)).  Returns the list of masks, or with counts=True (masks, [counts of pair k:
+        one RESIDUAL_MASK_DTYPE record per level])."""
+        n = len(references)
+        Ts = [None] * n if Ts is None else list(Ts)
+        results = [None] * n if results is None else list(results)
+        options = [None] * n if options is None else list(options)
+        if not (len(currents) == len(Ts) == len(results) == len(options) == n):
+            raise ValueError("one current, one transformation or result and one option set per reference")
+        vp = C.c_void_p
+        levels = [r.levels() for r in references]
+        opts = (ResidualMaskOptions * max(1, n))()
+        for k in range(n):
+            opts[k] = options[k] if options[k] is not None else residual_mask_options(results[k], levels[k])
+        T = np.ascontiguousarray(np.stack([SelectionMask._residual_T(Ts[k], results[k]) for k in range(n)]) if n
+                                 else np.zeros((0, 4, 4)), dtype=np.float64)
+        cnt = np.zeros(max(1, sum(levels)), RESIDUAL_MASK_DTYPE)
+        out = (vp * max(1, n))()
+        _check(lib().dvo_amd_mask_from_residuals_many(tracker._h, n, (vp * max(1, n))(*[p._h for p in references]),
+                                                      (vp * max(1, n))(*[p._h for p in currents]),
+                                                      T.ctypes.data_as(C.POINTER(C.c_double)), opts, out,
+                                                      cnt.ctypes.data_as(C.POINTER(C.c_longlong))),
+               "dvo_amd_mask_from_residuals_many")
+        made = [SelectionMask._own(vp(out[k]), references[k].device) for k in range(n)]
         if not counts:
             return made
         at = np.concatenate([[0], np.cumsum(levels)]).astype(int)

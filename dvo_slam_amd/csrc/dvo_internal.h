@@ -13,6 +13,7 @@
 //   dvo_mask.cpp      selection masks: the device-resident mask pyramid behind a masked point selection
 //   dvo_budget.cpp    point-budget masks: a mask ranked on the device from a resident pyramid (top-K radix select, per-cell argmax)
 //   dvo_mask_ops.cpp  masks from masks: combine, dilate / erode, warp onto another frame through both frames' depth
+//   dvo_mask_residual.cpp  masks from an alignment's residuals: inliers of the t-distribution at a transformation
 //   dvo_register.cpp  depth-to-colour registration: the kernels that splat another camera's raw depth into level 0's depth plane
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
@@ -537,6 +538,11 @@ int runner_step(dvo_amd_context *ctx, size_t g);
 int runner_drain(dvo_amd_context *ctx);
 int runner_configure(dvo_amd_context *ctx, int in_flight, int n_pad);
 int check_config(const dvo_amd_config *c);
+
+// ---- dvo_probes.cpp
+void kt_from_float_transform(const LevelData &C, const float *T, float kt[12]);
+// may level `level` of the two pyramids be aligned in `ctx`: TOO_FEW_LEVELS, DEVICE_MISMATCH, INVALID_ARGUMENT (sizes differ)
+int check_level_pair(const dvo_amd_context *ctx, const dvo_amd_pyramid *reference, const dvo_amd_pyramid *current, int level);
 
 // ---- dvo_sharded.cpp
 void combine_bands(const FinOut *const *recs, int n, FinOut &out);

@@ -2313,6 +2313,205 @@ hipError_t launch_mask_down(const unsigned char *m_prev, int w_prev, unsigned ch
   return hipGetLastError();
 }
 
+// ---- inlier masks from an alignment's residuals (dvo_amd_mask_from_residuals, dvo_mask_residual.cpp; the rule is pinned in
+// include/dvo_amd.h under "Residual masks") ---------------------------------------------------------------------------------------
+// k_residual_mask: ONE launch over all (pair, level) records of a call, laid out as k_mask_warp is: blockIdx.y walks the records,
+// striding by gridDim.y, blockIdx.x a chunk of the reference level; a lane owns four consecutive pixels of one row.  It is a gather
+// over the REFERENCE's pixels in the image, not over a compacted selection: four coalesced plane loads per lane (depth, {Zx, Zy},
+// intensity), the residual stage of the tracker -- project_pixel_rtz<0> / gather_pixel / finish_pixel_rtz above, the very
+// functions k_tick calls, in round-toward-zero behind k_tick's fencing -- then the Mahalanobis distance in round-to-nearest, every
+// operation rounded on its own (this file is compiled without contraction), the verdict, one 32-bit store of four mask bytes and,
+// when asked for, one 16-byte store of four distances.  Counts: ballots and popcounts per wave, LDS per block, one integer atomic
+// per non-zero count, as k_mask_warp.
+//
+// Q3 (dense_tracking_impl.cpp:169-171): the tracker walks its point list two points at a time and never looks at an odd trailing
+// point, so dvo_amd_residuals has no residual there.  Which pixel that is -- the last evaluated one of the level, if their number
+// is odd -- is known only when the whole level has been counted: the blocks of a record count themselves done (kRmDone), and the
+// block that draws the last number re-evaluates that one pixel and moves it to `invalid` in the plane, the distance plane and the
+// counts.  The hand-off is the counter form of an agent-scope release / acquire: every wave waits for its own stores, the block
+// meets at a barrier, one lane releases, waits and adds; the last arriver acquires.  Its patch is ordered behind every other
+// block's stores by that chain, whatever XCD they ran on; the counts it reads were written by atomics and are read by atomics.
+
+// the residual stage and the verdict for N pixels of one row (N = 4: a lane's pixels; N = 1: the Q3 pixel).  cls: -1 unevaluated,
+// else kRmInvalid / kRmInlier / kRmOutlier; dist: the distance, NaN where there is none
+template <int N>
+__device__ __forceinline__ void residual_mask_pixels(const LevelPairDesc &d, const float *kt, const float *P, const float max_distance,
+                                                     const float (&z_in)[N], const float (&zx)[N], const float (&zy)[N],
+                                                     const float (&ri_in)[N], const float (&tx)[N], const float ty, int (&cls)[N],
+                                                     float (&dist)[N]) {
+  // ---- round-to-nearest: reference point = pixel ray * depth, as the residual pass forms it
+  float x[N], y[N], z[N], ri[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) z[k] = z_in[k], ri[k] = ri_in[k], x[k] = tx[k] * z[k], y[k] = ty * z[k];
+  // ---- switch to round-toward-zero: every float that crosses is made opaque on both sides of the s_setreg
+#pragma unroll
+  for (int k = 0; k < N; ++k) { DVO_OPAQUE(x[k]); DVO_OPAQUE(y[k]); DVO_OPAQUE(z[k]); DVO_OPAQUE(ri[k]); }
+  round_toward_zero();
+#pragma unroll
+  for (int k = 0; k < N; ++k) { DVO_OPAQUE(x[k]); DVO_OPAQUE(y[k]); DVO_OPAQUE(z[k]); DVO_OPAQUE(ri[k]); }
+  float r0[N], r1[N];
+  bool ok[N];
+  {
+    Proj p[N];
+    Gathered g[N];
+#pragma unroll
+    for (int k = 0; k < N; ++k) p[k] = project_pixel_rtz<0>(kt, d, x[k], y[k], z[k]);
+#pragma unroll
+    for (int k = 0; k < N; ++k) g[k] = gather_pixel(d, p[k].base);  // (a pixel that is not evaluated or falls outside gathers at 0)
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      float e2, e3, e4, e5;
+      finish_pixel_rtz<true>(d, p[k], g[k], z[k], ri[k], 0.0f, 0.0f, r0[k], r1[k], e2, e3, e4, e5, ok[k]);
+    }
+  }
+  // ---- back to round-to-nearest
+#pragma unroll
+  for (int k = 0; k < N; ++k) { DVO_OPAQUE(r0[k]); DVO_OPAQUE(r1[k]); }
+  round_to_nearest();
+#pragma unroll
+  for (int k = 0; k < N; ++k) { DVO_OPAQUE(r0[k]); DVO_OPAQUE(r1[k]); }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    // the validity predicate of the select kernels (k_select with thresholds of -1): z, Zx, Zy are no NaN
+    const bool evaluated = (z_in[k] == z_in[k]) && (zx[k] == zx[k]) && (zy[k] == zy[k]);
+    // mahalanobis() of computeWeightsSse, product by product, mean 0 (Q4): r^T P r with P column-major
+    const float t0 = r0[k] * P[0] + r1[k] * P[1];
+    const float t1 = r0[k] * P[2] + r1[k] * P[3];
+    const float dd = t0 * r0[k] + t1 * r1[k];
+    const bool valid = evaluated && ok[k];
+    cls[k] = !evaluated ? -1 : !ok[k] ? (int)kRmInvalid : dd <= max_distance ? (int)kRmInlier : (int)kRmOutlier;  // (a NaN distance: outlier)
+    dist[k] = valid ? dd : u2f(0x7fc00000u);
+  }
+}
+
+// what a block needs of the current level's descriptor, through the constant address space as load_desc reads it
+__device__ __forceinline__ LevelPairDesc residual_mask_desc(const CurLevelDesc *cur) {
+  const DVO_CONST CurLevelDesc *c = (const DVO_CONST CurLevelDesc *)cur;
+  LevelPairDesc d = {};
+  d.c_a = c->c_a, d.c_b = c->c_b;
+  d.w = c->w, d.h = c->h;
+#pragma unroll
+  for (int i = 0; i < 6; ++i) d.wc[i] = c->wc[i];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) d.wr[i] = c->wr[i];
+  d.ub_x = c->ub_x, d.ub_y = c->ub_y;
+  return d;
+}
+
+__global__ void __launch_bounds__(kResidualMaskBlock) k_residual_mask(const ResidualMaskRecord *__restrict__ records, int n_records) {
+  constexpr int kWaves = kResidualMaskBlock / kWave, kLanePixels = kResidualMaskLanePixels;
+  constexpr int kCnt = 6;  // evaluated, invalid, inlier, outlier (the record's words), kept, index + 1 of the last evaluated pixel
+  __shared__ unsigned s_cnt[kWaves][kCnt];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  for (int rec = blockIdx.y; rec < n_records; rec += gridDim.y) {
+    const ResidualMaskRecord R = records[rec];  // uniform over the block
+    if (blockIdx.x * kResidualMaskChunk >= R.n) continue;  // (block-uniform: no barrier is skipped by part of a block)
+    const LevelPairDesc d = residual_mask_desc(R.cur);
+    float kt[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) kt[i] = R.kt[i];
+    const int p0 = (blockIdx.x * kResidualMaskBlock + threadIdx.x) * kLanePixels;
+    const bool live = p0 < R.n;  // (n is a multiple of 4: four pixels or none, all in one row)
+    const float qnan = u2f(0x7fc00000u);
+    float z[kLanePixels] = {qnan, qnan, qnan, qnan}, zx[kLanePixels] = {qnan, qnan, qnan, qnan}, zy[kLanePixels] = {qnan, qnan, qnan, qnan};
+    float ri[kLanePixels] = {0.f, 0.f, 0.f, 0.f}, tx[kLanePixels] = {0.f, 0.f, 0.f, 0.f};
+    float ty = 0.f;
+    if (live) {
+      const float4 z4 = *(const float4 *)(R.z + p0), i4 = *(const float4 *)(R.ri + p0);
+      const float4 za = *(const float4 *)(R.zd + p0), zb = *(const float4 *)(R.zd + p0 + 2);
+      z[0] = z4.x, z[1] = z4.y, z[2] = z4.z, z[3] = z4.w;
+      ri[0] = i4.x, ri[1] = i4.y, ri[2] = i4.z, ri[3] = i4.w;
+      zx[0] = za.x, zy[0] = za.y, zx[1] = za.z, zy[1] = za.w, zx[2] = zb.x, zy[2] = zb.y, zx[3] = zb.z, zy[3] = zb.w;
+      const int v = p0 / R.w, u0 = p0 - v * R.w;
+#pragma unroll
+      for (int k = 0; k < kLanePixels; ++k) tx[k] = R.tx[u0 + k];
+      ty = R.ty[v];
+    }
+    int cls[kLanePixels];
+    float dist[kLanePixels];
+    residual_mask_pixels<kLanePixels>(d, kt, R.P, R.max_distance, z, zx, zy, ri, tx, ty, cls, dist);
+    unsigned cnt[kCnt] = {0u, 0u, 0u, 0u, 0u, 0u};
+    unsigned word = 0u, last = 0u;
+#pragma unroll
+    for (int k = 0; k < kLanePixels; ++k) {
+      const int c = live ? cls[k] : -2;  // -2: no pixel
+      const bool keep = c == (int)kRmInlier || (c == (int)kRmInvalid && R.invalid_keep != 0) || (c == -1 && R.unevaluated_keep != 0);
+      word |= keep ? (1u << (8 * k)) : 0u;
+      last = c >= 0 ? (unsigned)(p0 + k + 1) : last;
+      cnt[kRmEvaluated] += (unsigned)__popcll(__ballot(c >= 0));
+      cnt[kRmInvalid] += (unsigned)__popcll(__ballot(c == (int)kRmInvalid));
+      cnt[kRmInlier] += (unsigned)__popcll(__ballot(c == (int)kRmInlier));
+      cnt[kRmOutlier] += (unsigned)__popcll(__ballot(c == (int)kRmOutlier));
+      cnt[4] += (unsigned)__popcll(__ballot(keep));
+    }
+    if (live) {
+      *(unsigned *)(R.out + p0) = word;
+      if (R.distance) *(float4 *)(R.distance + p0) = make_float4(dist[0], dist[1], dist[2], dist[3]);
+    }
+#pragma unroll
+    for (int m = kWave / 2; m >= 1; m >>= 1) {  // the wave's last evaluated pixel
+      const unsigned o = (unsigned)__shfl_xor((int)last, m, kWave);
+      last = o > last ? o : last;
+    }
+    cnt[5] = last;
+    if (lane == 0) {
+#pragma unroll
+      for (int c = 0; c < kCnt; ++c) s_cnt[wave][c] = cnt[c];
+    }
+    __syncthreads();
+    if (threadIdx.x < kCnt) {
+      unsigned sum = 0u;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) sum = threadIdx.x == 5 ? (s_cnt[w][5] > sum ? s_cnt[w][5] : sum) : sum + s_cnt[w][threadIdx.x];
+      if (sum) {
+        if (threadIdx.x < 4) atomicAdd(R.counts + threadIdx.x, sum);
+        else if (threadIdx.x == 4) atomicAdd(R.kept, (int)sum);
+        else atomicMax(R.counts + kRmLast, sum);
+      }
+    }
+    // this block is done with the record: every wave's stores and atomics have completed, then one lane publishes them and counts
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();  // (also: s_cnt may be written again for the block's next record)
+    if (threadIdx.x == 0) {
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned n_blocks = (unsigned)((R.n + kResidualMaskChunk - 1) / kResidualMaskChunk);
+      const unsigned drawn = __hip_atomic_fetch_add(R.counts + kRmDone, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (drawn == n_blocks - 1u) {  // the level is complete: Q3
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const unsigned n_eval = __hip_atomic_load(R.counts + kRmEvaluated, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned last1 = __hip_atomic_load(R.counts + kRmLast, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((n_eval & 1u) && last1 >= 1u && last1 <= (unsigned)R.n) {
+          const int q = (int)last1 - 1, v = q / R.w, u = q - v * R.w;
+          const float2 zd = R.zd[q];
+          const float qz[1] = {R.z[q]}, qzx[1] = {zd.x}, qzy[1] = {zd.y}, qri[1] = {R.ri[q]}, qtx[1] = {R.tx[u]};
+          int qcls[1];
+          float qd[1];
+          residual_mask_pixels<1>(d, kt, R.P, R.max_distance, qz, qzx, qzy, qri, qtx, R.ty[v], qcls, qd);
+          if (qcls[0] == (int)kRmInlier || qcls[0] == (int)kRmOutlier) {
+            atomicSub(R.counts + qcls[0], 1u);
+            atomicAdd(R.counts + kRmInvalid, 1u);
+            const int was = qcls[0] == (int)kRmInlier ? 1 : 0, now = R.invalid_keep != 0 ? 1 : 0;
+            if (now != was) atomicAdd(R.kept, now - was);
+            R.out[q] = (unsigned char)now;
+            if (R.distance) R.distance[q] = qnan;
+          }
+        }
+      }
+    }
+  }
+}
+
+hipError_t launch_residual_mask(const ResidualMaskRecord *records, int n_records, int max_n, hipStream_t stream) {
+  LaunchGuard guard;
+  const unsigned gx = (unsigned)((max_n + kResidualMaskChunk - 1) / kResidualMaskChunk);
+  // a launch holds fewer than 2^31 threads and at most 65535 rows of blocks: a block takes further records in steps of gridDim.y
+  const long long fit = (1ll << 31) / ((long long)gx * kResidualMaskBlock);
+  const unsigned gy = (unsigned)std::max<long long>(1, std::min<long long>(std::min<long long>((long long)n_records, 65535), fit));
+  hipLaunchKernelGGL(k_residual_mask, dim3(gx, gy), dim3(kResidualMaskBlock), 0, stream, records, n_records);
+  return hipGetLastError();
+}
+
 // The selected pixels of a level in scan order, compacted (round 5, end): what the residual pass walks.  The reference compacts
 // too -- PointSelection::select fills a dense array of the selected points (point_selection.cpp:119-152) and computeResidualsSse
 // walks that array -- so the pass's cost follows the selection, not the image.  One exclusive prefix over k_select's per-block

@@ -111,6 +111,15 @@ int dvo_amd_debug_tick_layout(int n_items, const int *res_blocks, const int *ll_
 namespace dvo_amd {
 namespace host {
 
+// K * T[0:3,0:4] of a float transformation (column-major) at the intrinsics of the current level, row-major: what the stage-wise
+// entries and dvo_amd_mask_from_residuals hand to the residual stage
+void kt_from_float_transform(const LevelData &C, const float *T, float kt[12]) {
+  const float K[9] = {C.fx, 0.0f, C.ox, 0.0f, C.fy, C.oy, 0.0f, 0.0f, 1.0f};
+  for (int i = 0; i < 3; ++i)
+    for (int c = 0; c < 4; ++c)
+      kt[i * 4 + c] = (K[i * 3 + 0] * T[c * 4 + 0] + K[i * 3 + 1] * T[c * 4 + 1]) + K[i * 3 + 2] * T[c * 4 + 2];
+}
+
 // One k_tick + k_finalize over slot 0 outside the match driver (the stage-wise parity entries): optionally the residual pass
 // at the float transform T (into residual buffer 0) and / or the log-likelihood pass over residual buffer 0.
 int single_tick(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const Selection *sel, const float *T,
@@ -143,10 +152,7 @@ int single_tick(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyrami
   f.seq = ctx->tick_seq = next_seq(ctx->tick_seq);
   if (residual_pass) {
     w.res_blocks = (uint16_t)nb;
-    const float K[9] = {C.fx, 0.0f, C.ox, 0.0f, C.fy, C.oy, 0.0f, 0.0f, 1.0f};
-    for (int i = 0; i < 3; ++i)
-      for (int c = 0; c < 4; ++c)
-        w.kt[i * 4 + c] = (K[i * 3 + 0] * T[c * 4 + 0] + K[i * 3 + 1] * T[c * 4 + 1]) + K[i * 3 + 2] * T[c * 4 + 2];
+    kt_from_float_transform(C, T, w.kt);
     f.records = s.records;
     f.n_blocks = (uint16_t)nb, f.level_blocks = (uint16_t)nb;
   }
@@ -199,7 +205,7 @@ int scatter_points_to_image(dvo_amd_context *ctx, const Selection *sel, int leve
   return DVO_AMD_OK;
 }
 
-int check_level_pair(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level) {
+int check_level_pair(const dvo_amd_context *ctx, const dvo_amd_pyramid *reference, const dvo_amd_pyramid *current, int level) {
   if (level >= reference->n_levels || level >= current->n_levels) return DVO_AMD_ERR_TOO_FEW_LEVELS;
   if (reference->device != ctx->device || current->device != ctx->device) return DVO_AMD_ERR_DEVICE_MISMATCH;
   if (reference->lv[level].w != current->lv[level].w || reference->lv[level].h != current->lv[level].h)
@@ -437,10 +443,7 @@ int dvo_amd_bench_residual_pass_pairs(dvo_amd_context *ctx, int n_items, dvo_amd
         w.ref = sels[(size_t)(first + i)]->ref_desc + level;
         w.cur = currents[first + i]->cur_desc + level;
         w.slot = ctx->slot_desc + (first + i);
-        const float K[9] = {C.fx, 0.0f, C.ox, 0.0f, C.fy, C.oy, 0.0f, 0.0f, 1.0f};
-        for (int r = 0; r < 3; ++r)
-          for (int cc = 0; cc < 4; ++cc)
-            w.kt[r * 4 + cc] = (K[r * 3 + 0] * T[cc * 4 + 0] + K[r * 3 + 1] * T[cc * 4 + 1]) + K[r * 3 + 2] * T[cc * 4 + 2];
+        kt_from_float_transform(C, T, w.kt);
       }
       hipError_t e = launch_tick(ta, max_blocks, ctx->stream, e0, e1);  // stamped by the dispatch itself
       if (e != hipSuccess) return fail_hip("launch_tick", e);

@@ -462,4 +462,30 @@ hipError_t launch_select_batch(const BatchFrame *frames, int count, const BatchL
                                int level, int levels, hipStream_t stream, int *launches);
 hipError_t launch_compact_batch(const BatchFrame *frames, int count, const BatchLevel &L, hipStream_t stream, int *launches);
 
+// ---- inlier masks from an alignment's residuals (dvo_amd_mask_from_residuals, dvo_mask_residual.cpp; the rule is pinned in
+// include/dvo_amd.h under "Residual masks").  One (pair, level) as k_residual_mask reads it, in a device table uploaded per call.
+constexpr int kResidualMaskBlock = 256;
+constexpr int kResidualMaskLanePixels = 4;  // a lane owns four consecutive pixels of one row (level widths are multiples of 4)
+constexpr int kResidualMaskChunk = kResidualMaskBlock * kResidualMaskLanePixels;  // pixels per block
+// the words of a record's counter block (device, zeroed before the launch): the four counted outcomes, then what the kernel needs
+// for itself -- the index + 1 of the last evaluated pixel and the blocks of the record that are done (Q3, see the kernel)
+enum { kRmEvaluated = 0, kRmInvalid, kRmInlier, kRmOutlier, kRmLast, kRmDone, kRmWords = 8 };
+struct ResidualMaskRecord {
+  const float *z;            // reference: depth plane of the level
+  const float2 *zd;          // ... its {Zx, Zy} plane (c_b)
+  const float *ri;           // ... its intensity plane (r_i)
+  const float *tx, *ty;      // ... the rays of its columns and rows
+  const CurLevelDesc *cur;   // current: the level's descriptor (gather planes, wc, wr, ub_x, ub_y)
+  unsigned char *out;        // the result's plane of the level
+  float *distance;           // the level's distance plane (null: not asked for)
+  int *kept;                 // the result's counter of the level
+  unsigned *counts;          // [kRmWords]
+  int w, n;                  // width and pixels of the level
+  float kt[12];              // K * T[0:3,0:4] as the residual pass takes it
+  float P[4];                // column-major 2x2 precision
+  float max_distance;
+  int invalid_keep, unevaluated_keep;
+};
+hipError_t launch_residual_mask(const ResidualMaskRecord *records, int n_records, int max_n, hipStream_t stream);
+
 }  // namespace dvo_amd

@@ -470,7 +470,8 @@ int dvo_amd_match_selection(dvo_amd_context *ctx, dvo_amd_pyramid *reference, fl
  * Not covered: dvo_amd_track_frame, dvo_amd_validate_proposals, dvo_amd_match_banded / _sharded, dvo_amd_residuals,
  * dvo_amd_error_image, the debug and bench entries and the build_selection of dvo_amd_pyramid_create_raw_batch keep their
  * thresholds-only selection and take no mask.  There are no masks on the current side: the current image is gathered wherever
- * the warp lands, which is the reference's behaviour.
+ * the warp lands, which is the reference's behaviour.  (A mask made FROM an alignment's residuals: "Residual masks" below; that
+ * entry reads the pyramids' planes and needs neither dvo_amd_residuals nor a selection.)
  */
 #define DVO_AMD_MASK_ALL 0
 #define DVO_AMD_MASK_ANY 1
@@ -632,6 +633,73 @@ int dvo_amd_mask_warp(const dvo_amd_mask *mask, const dvo_amd_pyramid *source, c
 int dvo_amd_mask_warp_many(int n, const dvo_amd_mask *const *masks, const dvo_amd_pyramid *const *sources,
                            const dvo_amd_pyramid *const *targets, const double *T, const dvo_amd_mask_warp_options *opt,
                            dvo_amd_mask **out, long long *counts /* packed in pair order, or NULL */);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Residual masks: a mask from what the tracker itself knows -- the inliers of an alignment's residuals, on the device.
+ *
+ * After an alignment the pixels whose residuals the t-distribution down-weights are the moving objects, the specular surfaces and
+ * the depth ghosts.  dvo_amd_mask_from_residuals keeps the others, so that
+ *     match -> inlier mask -> dvo_amd_mask_morph (erode) -> dvo_amd_mask_warp to the next keyframe -> dvo_amd_match_masked
+ * needs no segmentation network and nothing leaves the device between the steps.  The result is an ordinary dvo_amd_mask --
+ * immutable, refcounted, with a serial of its own -- of the REFERENCE's level-0 size and level count; *out (every out[k]) is NULL
+ * on every failure.  A call is ONE kernel launch for all its pairs and levels and synchronises once, at its end.  The context
+ * gives its device and its reciprocal mode, nothing else: no tracker slot is used, no selection is built, looked up or cached, and
+ * the context's queue need not be idle.
+ *
+ * dvo_amd_mask_from_residuals_many(ctx, n, references, currents, T, opts, out, counts); dvo_amd_mask_from_residuals is the case
+ * n = 1 with the per-pixel distances on request.  T: n x 16 doubles, column-major, reference -> current: the ESTIMATE, exactly
+ * what dvo_amd_error_image takes, and the host casts it to float as that entry does.  For dvo_amd_match(reference, current) that
+ * is the INVERSE of result.transformation as returned (dense_tracking.cpp:371 returns the inverse of the estimate; see the mask
+ * warp above, which takes it as returned).  opts: one dvo_amd_residual_mask_options per pair.  The rule, for pair k, every level l
+ * of the reference and every pixel i of that level, with P = opts[k].precision[l] a column-major 2 x 2:
+ *     unevaluated   unless z, zdx and zdy of pixel i are all no NaN: ValidPointAndGradientThresholdPredicate(-1, -1) as the select
+ *                   kernels test it, the set of pixels a selection can ever keep (the stated deviation of "Selection masks")
+ *                       out[l][i] = opts[k].unevaluated_keep != 0
+ *     (r0, r1, valid) otherwise: the residual stage of the tracker for that pixel, in round-toward-zero, with the level's K T, wcur,
+ *                   wref and bounds as dvo_amd_residuals builds them -- the pair of floats dvo_amd_residuals returns for the
+ *                   pixel under thresholds (-1, -1), bit for bit, and valid false exactly where it returns NaN:
+ *     invalid       !valid: out of bounds, a NaN among the blended channels, the occlusion test -- and Q3: where the number of
+ *                   evaluated pixels of the level is odd, the last of them in scan order, which the tracker's point list never
+ *                   reaches (dense_tracking_impl.cpp:169-171)
+ *                       out[l][i] = opts[k].invalid_keep != 0
+ *     distance      otherwise, in round-to-nearest fp32, every operation rounded on its own, mahalanobis()'s order:
+ *                       t0 = r0 P[0] + r1 P[1],  t1 = r0 P[2] + r1 P[3],  d = t0 r0 + t1 r1
+ *                   the d whose weight 7 / (5 + d) computeWeightsSse forms; the mean is zero (quirk Q4)
+ *     verdict       d <= opts[k].max_distance[l] -> inlier, out = 1; otherwise, a NaN d included -> outlier, out = 0
+ * Defaults: precision all 0, which means "not set" and is refused (the caller copies tdist_precision of the last iteration of each
+ * level from a dvo_amd_result's statistics); max_distance 9.2103f on every level, -2 ln 0.01, the 99 % point of chi-square with
+ * two degrees of freedom; both keeps 0.
+ * distance (may be NULL, and so may any distance[l]): distance[l] receives d per pixel of level l, NaN where the pixel is
+ * unevaluated or invalid -- the soft form of the mask.
+ * counts (may be NULL): for pair k, in pair order, one record of DVO_AMD_RESIDUAL_MASK_COUNTS long long per level of references[k]:
+ *     evaluated, invalid, inlier, outlier, kept
+ * evaluated = invalid + inlier + outlier; kept = the ones of the output = dvo_amd_mask_info's kept[l].  All counts are integers
+ * and no value depends on the launch geometry or on the order atomics land in.
+ * Errors, before any device work: DVO_AMD_ERR_INVALID_ARGUMENT, with a reason in dvo_amd_last_error() that starts with the entry's
+ * name, for a NULL pointer (inside the arrays too); n < 0; a non-finite entry of T; a non-finite entry of a used precision[l] or
+ * one that is all zero; a max_distance[l] that is NaN or negative (+inf is allowed); a level of the reference that the current
+ * lacks or has in another size (dvo_amd_residuals' check); a context in the host-rcpps reciprocal mode
+ * (dvo_amd_set_reciprocal_mode), whose residual stage this entry does not cover.  Then DVO_AMD_ERR_DEVICE_MISMATCH unless both
+ * pyramids live on the context's device, then DVO_AMD_ERR_NO_DEVICE.  n == 0 is OK and does nothing.
+ *
+ * Not covered: the host-rcpps reciprocal mode; a mean other than zero; a distance under another selection than validity (the
+ * residual of a pixel does not depend on which other pixels are selected, but Q3's pixel does: it is the validity selection's).
+ */
+#define DVO_AMD_RESIDUAL_MASK_COUNTS 5 /* evaluated, invalid, inlier, outlier, kept */
+typedef struct dvo_amd_residual_mask_options {
+  float precision[DVO_AMD_MAX_LEVELS][4]; /* per level: column-major 2 x 2, finite, not all zero on the reference's levels */
+  float max_distance[DVO_AMD_MAX_LEVELS]; /* per level: >= 0, +inf allowed */
+  int invalid_keep, unevaluated_keep;
+} dvo_amd_residual_mask_options;
+/* precision all 0 (not set), max_distance 9.2103f on every level, both keeps 0; a NULL opt is a no-op */
+void dvo_amd_default_residual_mask_options(dvo_amd_residual_mask_options *opt);
+int dvo_amd_mask_from_residuals(dvo_amd_context *ctx, const dvo_amd_pyramid *reference, const dvo_amd_pyramid *current, const double *T,
+                                const dvo_amd_residual_mask_options *opt, dvo_amd_mask **out,
+                                long long *counts /* [levels][5] or NULL */, float *const *distance /* [levels] host planes or NULL */);
+int dvo_amd_mask_from_residuals_many(dvo_amd_context *ctx, int n, const dvo_amd_pyramid *const *references,
+                                     const dvo_amd_pyramid *const *currents, const double *T /* n x 16 */,
+                                     const dvo_amd_residual_mask_options *opts /* n */, dvo_amd_mask **out /* n */,
+                                     long long *counts /* packed in pair order, or NULL */);
 
 /* n independent match() calls advanced in lock step on one GPU (the shape of LocalTracker::update's tbb::parallel_invoke,
  * local_tracker.cpp:184, and of the loop-closure validator's parallel_reduce, keyframe_graph.cpp:576-593).

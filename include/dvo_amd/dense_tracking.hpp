@@ -536,6 +536,66 @@ class SelectionMask {
     return out;
   }
 
+  // A mask from what the tracker itself knows (dvo_amd.h, "Residual masks"): the pixels of `reference` whose residuals against
+  // `current` are inliers of the t-distribution -- valid, and with a Mahalanobis distance of at most maxDistance (default: the
+  // 99 % point of chi-square with two degrees of freedom) under the level's precision -- at the estimate of
+  // tracker.match(reference, current, result).  match() returns the inverse of its estimate (dense_tracking.cpp:371), so the
+  // estimate passed on is the rigid inverse of result.Transformation (rigidInverse below).  The precision of level l is the
+  // TDistributionPrecision of the last iteration of that level in result.Statistics; a level the match did not run (level 0
+  // under the default configuration) takes the nearest level that ran, ties to the finer one.  Throws INVALID_ARGUMENT if the
+  // result holds no iteration at all.  Both pyramids hold their levels (the match has built them); the mask has the reference's.
+  // Tracker: dvo::DenseTracker, MatchResult: dvo::DenseTracker::Result (templates only because both are declared further down).
+  struct ResidualCounts {  // one level's record
+    long long evaluated, invalid, inlier, outlier, kept;
+  };
+  template <class Tracker, class MatchResult>
+  static SelectionMask fromResiduals(const Tracker &tracker, const RgbdImagePyramid &reference, const RgbdImagePyramid &current,
+                                     const MatchResult &result, float maxDistance = 9.2103f, bool invalidKeep = false,
+                                     bool unevaluatedKeep = false, std::vector<ResidualCounts> *counts = nullptr) {
+    static_assert(sizeof(ResidualCounts) == DVO_AMD_RESIDUAL_MASK_COUNTS * sizeof(long long),
+                  "a ResidualCounts is one record of dvo_amd_mask_from_residuals' counts");
+    const char *where = "SelectionMask::fromResiduals";
+    dvo_amd_residual_mask_options o;
+    dvo_amd_default_residual_mask_options(&o);
+    const int levels = dvo_amd_pyramid_levels(reference.handle());
+    for (int l = 0; l < levels && l < DVO_AMD_MAX_LEVELS; ++l) {
+      long best = -1, best_distance = 0;
+      for (size_t i = 0; i < result.Statistics.Levels.size(); ++i) {
+        if (result.Statistics.Levels[i].Iterations.empty()) continue;
+        const long id = (long)result.Statistics.Levels[i].Id, distance = id > l ? id - l : l - id;
+        if (best < 0 || distance < best_distance || (distance == best_distance && id < (long)result.Statistics.Levels[(size_t)best].Id))
+          best = (long)i, best_distance = distance;
+      }
+      if (best < 0) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+      const Matrix2d &P = result.Statistics.Levels[(size_t)best].Iterations.back().TDistributionPrecision;
+      for (int i = 0; i < 4; ++i) o.precision[l][i] = (float)P(i % 2, i / 2);  // column-major
+      o.max_distance[l] = maxDistance;
+    }
+    o.invalid_keep = invalidKeep ? 1 : 0, o.unevaluated_keep = unevaluatedKeep ? 1 : 0;
+    const AffineTransformd estimate = rigidInverse(result.Transformation);
+    ResidualCounts records[DVO_AMD_MAX_LEVELS];
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_from_residuals(tracker.handle(), reference.handle(), current.handle(), data(estimate), &o, &m,
+                                              &records[0].evaluated, nullptr),
+                  where);
+    SelectionMask out(m, reference.device());
+    if (counts) counts->assign(records, records + out.info().levels);
+    return out;
+  }
+  // (R^T, -R^T t) of a rigid transformation, every sum in this order: the inverse the Python binding and the C example form too,
+  // so that all three hand the library the same sixteen doubles
+  static AffineTransformd rigidInverse(const AffineTransformd &transformation) {
+    const double *t = data(transformation);  // column-major
+    AffineTransformd inverse;
+    inverse.setIdentity();
+    double *o = data(inverse);
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) o[j * 4 + i] = t[i * 4 + j];
+      o[12 + i] = -((t[i * 4 + 0] * t[12] + t[i * 4 + 1] * t[13]) + t[i * 4 + 2] * t[14]);
+    }
+    return inverse;
+  }
+
   bool valid() const { return (bool)handle_; }
   dvo_amd_mask *handle() const { return handle_.get(); }
   int device() const { return device_; }
