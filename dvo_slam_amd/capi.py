@@ -56,6 +56,7 @@ EXPORTS = [
     "dvo_amd_default_mask_warp_options", "dvo_amd_mask_combine", "dvo_amd_mask_morph", "dvo_amd_mask_warp", "dvo_amd_mask_warp_many",
     "dvo_amd_debug_mask_ops_timing",
     "dvo_amd_default_residual_mask_options", "dvo_amd_mask_from_residuals", "dvo_amd_mask_from_residuals_many",
+    "dvo_amd_default_fuse_options", "dvo_amd_pyramid_fuse_depth", "dvo_amd_pyramid_fuse_depth_many", "dvo_amd_debug_fuse_timing",
 ]
 
 
@@ -166,6 +167,20 @@ class ResidualMaskOptions(C.Structure):
     _fields_ = [("precision", (C.c_float * 4) * MAX_LEVELS), ("max_distance", C.c_float * MAX_LEVELS), ("invalid_keep", C.c_int),
                 ("unevaluated_keep", C.c_int)]
 
+
+class FuseOptions(C.Structure):
+    """dvo_amd_fuse_options, field for field"""
+    _fields_ = [("near_z", C.c_float), ("depth_sigmas", C.c_float), ("min_cos", C.c_float), ("sample", C.c_int),
+                ("min_observations", C.c_int), ("drop_unconfirmed", C.c_int)]
+
+
+FUSE_BILINEAR, FUSE_NEAREST = 0, 1
+FUSE_MAX_FRAMES = 255
+# one record of dvo_amd_pyramid_fuse_depth's frame counts and of its keyframe counts, field for field
+FUSE_FRAME_COUNTS = ("valid", "behind", "outside", "no_depth", "consistent", "occluded", "seen_through", "fused")
+FUSE_FRAME_DTYPE = np.dtype([(name, np.int64) for name in FUSE_FRAME_COUNTS])
+FUSE_KEYFRAME_COUNTS = ("with_depth", "confirmed", "unconfirmed_kept", "unconfirmed_dropped")
+FUSE_KEYFRAME_DTYPE = np.dtype([(name, np.int64) for name in FUSE_KEYFRAME_COUNTS])
 
 # one record of dvo_amd_mask_from_residuals' counts, field for field
 RESIDUAL_MASK_COUNTS = ("evaluated", "invalid", "inlier", "outlier", "kept")
@@ -374,6 +389,13 @@ def lib():
                                               C.POINTER(C.POINTER(C.c_float))]
     L.dvo_amd_mask_from_residuals_many.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(ResidualMaskOptions),
                                                    C.POINTER(vp), C.POINTER(C.c_longlong)]
+    L.dvo_amd_default_fuse_options.argtypes = [C.POINTER(FuseOptions)]
+    L.dvo_amd_default_fuse_options.restype = None
+    L.dvo_amd_pyramid_fuse_depth.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
+                                             C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_ubyte)]
+    L.dvo_amd_pyramid_fuse_depth_many.argtypes = [C.c_int, C.POINTER(vp), ip, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
+                                                  C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(vp)]
+    L.dvo_amd_debug_fuse_timing.argtypes = [C.c_int, C.c_int, dp]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -609,6 +631,26 @@ def mask_ops_timing(enable: bool = True, device: int = 0) -> float:
     off and returns the device time of the most recent bracketed call in ms (dvo_amd_debug_mask_ops_timing)"""
     ms = C.c_double()
     _check(lib().dvo_amd_debug_mask_ops_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_mask_ops_timing")
+    return ms.value
+
+
+def fuse_options(**options) -> FuseOptions:
+    """dvo_amd_default_fuse_options (near_z 0.1, depth_sigmas 5, min_cos 0.5, sample FUSE_BILINEAR, min_observations 0,
+    drop_unconfirmed 0) with the given fields replaced"""
+    opt = FuseOptions()
+    lib().dvo_amd_default_fuse_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in ("near_z", "depth_sigmas", "min_cos", "sample", "min_observations", "drop_unconfirmed"):
+            raise TypeError(f"unknown fuse option {k!r}")
+        setattr(opt, k, float(v) if k in ("near_z", "depth_sigmas", "min_cos") else int(v))
+    return opt
+
+
+def fuse_timing(enable: bool = True, device: int = 0) -> float:
+    """(instrumentation) switches the event bracket around the fusion launch of every fuse_depth / fuse_depth_many of `device` on
+    or off and returns the device time of the most recent bracketed launch in ms (dvo_amd_debug_fuse_timing)"""
+    ms = C.c_double()
+    _check(lib().dvo_amd_debug_fuse_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_fuse_timing")
     return ms.value
 
 
@@ -1104,6 +1146,63 @@ class RgbdImagePyramid:
                                             out.ctypes.data_as(C.POINTER(C.c_ubyte))), "pyramid_select")
         return cnt.value, out
 
+    # ---- depth fusion (the rule is pinned in include/dvo_amd.h under "Depth fusion")
+
+    def fuse_depth(self, frames, transformations, options=None, counts: bool = False, observations: bool = False):
+        """This keyframe with the level-0 depth of `frames` averaged into its own (dvo_amd_pyramid_fuse_depth): a new pyramid of
+        this one's size, intrinsics, level count and timestamp; this one is only read.  transformations[k]: 4x4, for
+        tracker.match(self, frames[k]) the result's Transformation as returned.  options: None, a FuseOptions or a dict of its
+        fields (near_z, depth_sigmas, min_cos, sample, min_observations, drop_unconfirmed).  Returns the pyramid; with counts=True
+        also the frame counts (one FUSE_FRAME_DTYPE record per frame) and the keyframe counts (one FUSE_KEYFRAME_DTYPE record);
+        with observations=True also the observations per pixel (uint8 [h, w]) -- as a tuple, in this order."""
+        got = RgbdImagePyramid.fuse_depth_many([self], [frames], [transformations], options, counts=counts, observations=observations)
+        return tuple(part[0] for part in got) if counts or observations else got[0]
+
+    @staticmethod
+    def fuse_depth_many(keyframes, frames_per_keyframe, transformations_per_keyframe, options=None, counts: bool = False,
+                        observations: bool = False):
+        """fuse_depth for many keyframes in one call and one kernel launch (dvo_amd_pyramid_fuse_depth_many): keyframes[j] with
+        frames_per_keyframe[j] at transformations_per_keyframe[j].  Returns the list of pyramids; with counts=True also the list of
+        frame counts (per keyframe one FUSE_FRAME_DTYPE record per frame) and the keyframe counts (a FUSE_KEYFRAME_DTYPE array);
+        with observations=True also the list of observation planes (uint8 [h, w]) -- as a tuple, in this order."""
+        nk = len(keyframes)
+        if not (len(frames_per_keyframe) == len(transformations_per_keyframe) == nk):
+            raise ValueError("one list of frames and one list of transformations per keyframe")
+        if any(len(f) != len(t) for f, t in zip(frames_per_keyframe, transformations_per_keyframe)):
+            raise ValueError("one transformation per frame")
+        opt = options if isinstance(options, FuseOptions) else fuse_options(**(options or {}))
+        vp = C.c_void_p
+        offsets = np.concatenate([[0], np.cumsum([len(f) for f in frames_per_keyframe])]).astype(np.int32)
+        total = int(offsets[-1])
+        flat = [p for f in frames_per_keyframe for p in f]
+        T = np.ascontiguousarray(np.stack([_pose_cm(t) for ts in transformations_per_keyframe for t in ts]) if total
+                                 else np.zeros((1, 4, 4)), dtype=np.float64)
+        frame_cnt = np.zeros(max(1, total), FUSE_FRAME_DTYPE)
+        key_cnt = np.zeros(max(1, nk), FUSE_KEYFRAME_DTYPE)
+        planes = []
+        for kf in keyframes:
+            w, h, _ = kf.level_info(0)
+            planes.append(np.zeros((h, w), np.uint8))
+        out = (vp * max(1, nk))()
+        obs = (vp * max(1, nk))(*[p.ctypes.data for p in planes]) if observations else None
+        ll = C.POINTER(C.c_longlong)
+        _check(lib().dvo_amd_pyramid_fuse_depth_many(nk, (vp * max(1, nk))(*[p._h for p in keyframes]),
+                                                     offsets.ctypes.data_as(C.POINTER(C.c_int)),
+                                                     (vp * max(1, total))(*[p._h for p in flat]), T.ctypes.data_as(C.POINTER(C.c_double)),
+                                                     C.byref(opt), out, frame_cnt.ctypes.data_as(ll) if counts else None,
+                                                     key_cnt.ctypes.data_as(ll) if counts else None, obs),
+               "dvo_amd_pyramid_fuse_depth_many")
+        made = []
+        for j in range(nk):
+            p = RgbdImagePyramid.__new__(RgbdImagePyramid)
+            p._h, p.device, p.registration_stats = vp(out[j]), keyframes[j].device, None
+            made.append(p)
+        result = (made,)
+        if counts:
+            result += ([frame_cnt[offsets[j]:offsets[j + 1]].copy() for j in range(nk)], key_cnt[:nk].copy())
+        if observations:
+            result += (planes,)
+        return result if len(result) > 1 else made
 
     def point_cloud(self, pose=None, bgr=None, level: int = 0, tracker: "DenseTracker | None" = None):
         """RgbdCamera::buildPointCloud of a level transformed by `pose` (4x4, None = identity) and coloured from `bgr` (uint8

@@ -701,6 +701,105 @@ int dvo_amd_mask_from_residuals_many(dvo_amd_context *ctx, int n, const dvo_amd_
                                      const dvo_amd_residual_mask_options *opts /* n */, dvo_amd_mask **out /* n */,
                                      long long *counts /* packed in pair order, or NULL */);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Depth fusion: the depth of the frames tracked against a keyframe averaged into the keyframe, on the device.
+ *
+ * A keyframe's depth plane is one raw sensor frame with that frame's noise, and everything that follows is tracked against it.
+ * The frames tracked against it measured the same surfaces again, and their poses relative to it are what dvo_amd_match returned.
+ * dvo_amd_pyramid_fuse_depth_many(n_keyframes, keyframes, frame_offsets, frames, T, opt, out, ...) carries each frame's depth onto
+ * its keyframe's pixels by dvo_amd_covisibility's rule and averages what agrees, weighted by the inverse variance of the sensor
+ * model; dvo_amd_pyramid_fuse_depth is the case n_keyframes = 1.  Keyframe j owns frames[frame_offsets[j] .. frame_offsets[j+1])
+ * and the transformations at the same positions of T (16 doubles each, column-major).  The entries take no context: like the mask
+ * operations they run on the device's internal stream, use no tracker slot, and may be called while pairs are queued elsewhere.
+ * (The reference has no counterpart: it tracks against the raw keyframe.)
+ *
+ * The result out[j] is a new ordinary pyramid -- immutable, refcounted, accepted by every entry that accepts a pyramid -- with the
+ * keyframe's size, intrinsics, level count and timestamp.  Its level-0 intensity is the keyframe's, bit for bit; its level-0 depth
+ * is the fused plane; every other level and plane is what the builder derives from those two: it equals, plane for plane,
+ * dvo_amd_pyramid_create called with the same two float planes.  It has no selection yet (the keyframe's cached selections do not
+ * carry over).  The inputs are only read.  *out, and in the many form every out[j], is NULL on every failure.  All keyframes of a
+ * call are fused in ONE kernel launch and the call synchronises once for it, then as the builder does per keyframe.
+ *
+ * The rule, operation by operation; the library is built without contraction, so every product, sum and quotient rounds on its
+ * own, and divisions are correctly rounded.  T[k] is result.transformation of dvo_amd_match(reference = keyframe, current =
+ * frames[k]) AS RETURNED: it maps points of frame k's camera into the keyframe's camera.  The host inverts it as a rigid
+ * transformation in double with the summation order of dvo_amd_covisibility's step 1 (Ri = R^T, ti[r] = -((R[0][r] t0 + R[1][r] t1)
+ * + R[2][r] t2)) and casts rows 0..2 to float: M, with rows M0..M2 and columns 0..3.  Only level 0 of every pyramid is read; a
+ * frame may differ from its keyframe in size, intrinsics and level count.  sigma(z) = 0.0012f + 0.0019f * ((z - 0.4f) * (z - 0.4f))
+ * (depthStdDevZ, dense_tracking_impl.cpp:122-128).  For the keyframe pixel (u, v) with depth z0, in fp32:
+ *  1. no depth: if z0 is not finite the output depth is NaN and observations = 0; the pixel is not counted in with_depth and no
+ *     frame count moves;
+ *  2. the keyframe's own observation: w = 1 / (sigma(z0) * sigma(z0)); sw = w; swz = w * z0; n_obs = 0; the pixel counts as
+ *     with_depth;
+ *  3. for k = 0 .. n - 1, in this order:
+ *       (x, y) = (tx[u] * z0, ty[v] * z0)                          the keyframe's level-0 rays
+ *       q_r = ((M_r0 * x + M_r1 * y) + M_r2 * z0) + M_r3           per row r; frame k counts `valid`
+ *       !(qz >= near_z)                                            -> behind
+ *       px = (qx * fx) / qz + ox, py = (qy * fy) / qz + oy         frame k's intrinsics
+ *     DVO_AMD_FUSE_NEAREST:
+ *       pu = floorf(px + 0.5f), pv = floorf(py + 0.5f)
+ *       !(0 <= pu <= w_k - 1 && 0 <= pv <= h_k - 1), in float      -> outside
+ *       Zs = Z_k[pv, pu] is NaN                                    -> no_depth
+ *     DVO_AMD_FUSE_BILINEAR:
+ *       x0 = floorf(px), y0 = floorf(py)
+ *       !(0 <= x0 <= w_k - 2 && 0 <= y0 <= h_k - 2), in float      -> outside
+ *       a = px - x0, b = py - y0
+ *       any of z00, z10, z01, z11 is NaN                           -> no_depth     (column x0 / x0 + 1, row y0 / y0 + 1)
+ *       top = z00 + a * (z10 - z00); bot = z01 + a * (z11 - z01); Zs = top + b * (bot - top)
+ *     then
+ *       d = Zs - qz, tol = depth_sigmas * sigma(qz)
+ *       d < -tol -> occluded,  d > tol -> seen_through,  else consistent
+ *       where consistent: c = (M_20 * tx[u] + M_21 * ty[v]) + M_22   the change of qz per unit of z0
+ *       !(c >= min_cos)                                            -> grazing: the pixel contributes nothing
+ *       otherwise fused: z_obs = z0 + d / c; w = 1 / (sigma(Zs) * sigma(Zs)); sw = sw + w; swz = swz + w * z_obs; n_obs += 1
+ *  4. output: fusedz = swz / sw.  If n_obs >= min_observations the depth is fusedz and the pixel counts as confirmed; otherwise
+ *     the depth is NaN when drop_unconfirmed != 0 (unconfirmed_dropped) and fusedz when it is 0 (unconfirmed_kept).
+ *     observations[v * w + u] = n_obs (n <= DVO_AMD_FUSE_MAX_FRAMES: it fits a byte).
+ * frame_counts (may be NULL): DVO_AMD_FUSE_FRAME_COUNTS long long per (keyframe, frame), in frame order over the packed list:
+ *     valid, behind, outside, no_depth, consistent, occluded, seen_through, fused
+ * valid = keyframe pixels with a finite depth = the sum of the next six; grazing = consistent - fused.  With DVO_AMD_FUSE_NEAREST
+ * the first seven are dvo_amd_covisibility's counts at level 0 for the ordered pair (keyframe, frame) at those poses, near_z and
+ * depth_sigmas.
+ * keyframe_counts (may be NULL): DVO_AMD_FUSE_KEYFRAME_COUNTS long long per keyframe:
+ *     with_depth, confirmed, unconfirmed_kept, unconfirmed_dropped
+ * with_depth is the sum of the other three.  observations (may be NULL; in the many form any entry may be NULL): host memory, w * h
+ * bytes per keyframe.  All counts are integers and every pixel's sums are taken in frame order: no value depends on the launch
+ * geometry, on the order atomics land in or on what else is in the call.
+ * n = 0 is legal (frames and T may then be NULL): the result is (w * z0) / w wherever z0 is finite.  A keyframe among its own
+ * frames and a frame repeated are legal.  n_keyframes == 0 is DVO_AMD_OK and does nothing.
+ * Errors, in this order and before any device work.  DVO_AMD_ERR_INVALID_ARGUMENT with a reason in dvo_amd_last_error() that starts
+ * with the entry's name: a NULL pointer (inside the arrays too; frames and T only where the call has frames); n < 0 or
+ * n > DVO_AMD_FUSE_MAX_FRAMES for a keyframe; n_keyframes < 0; offsets that do not start at 0 or that decrease; a non-finite entry of
+ * T; near_z or min_cos not finite or <= 0; depth_sigmas not finite or < 0; an unknown sample; min_observations outside
+ * 0 .. DVO_AMD_FUSE_MAX_FRAMES.  Then DVO_AMD_ERR_DEVICE_MISMATCH unless every object of the call lives on one device, then
+ * DVO_AMD_ERR_NO_DEVICE.
+ *
+ * Not covered: holes are not filled (a keyframe pixel without depth stays without); no per-pixel variance is kept in the pyramid
+ * (sw is dropped after the division); the intensity is not fused; the frames' levels above 0 are not read.
+ */
+#define DVO_AMD_FUSE_BILINEAR 0
+#define DVO_AMD_FUSE_NEAREST 1
+#define DVO_AMD_FUSE_MAX_FRAMES 255
+#define DVO_AMD_FUSE_FRAME_COUNTS 8    /* valid, behind, outside, no_depth, consistent, occluded, seen_through, fused */
+#define DVO_AMD_FUSE_KEYFRAME_COUNTS 4 /* with_depth, confirmed, unconfirmed_kept, unconfirmed_dropped */
+typedef struct dvo_amd_fuse_options {
+  float near_z;           /* > 0, finite; default 0.1 */
+  float depth_sigmas;     /* >= 0, finite; default 5 */
+  float min_cos;          /* finite, > 0; default 0.5: see `grazing` */
+  int sample;             /* DVO_AMD_FUSE_BILINEAR (default) | DVO_AMD_FUSE_NEAREST */
+  int min_observations;   /* 0 .. DVO_AMD_FUSE_MAX_FRAMES; default 0 */
+  int drop_unconfirmed;   /* default 0 */
+} dvo_amd_fuse_options;
+/* near_z 0.1, depth_sigmas 5, min_cos 0.5, BILINEAR, min_observations 0, drop_unconfirmed 0; a NULL opt is a no-op */
+void dvo_amd_default_fuse_options(dvo_amd_fuse_options *opt);
+int dvo_amd_pyramid_fuse_depth(const dvo_amd_pyramid *keyframe, int n, const dvo_amd_pyramid *const *frames, const double *T,
+                               const dvo_amd_fuse_options *opt, dvo_amd_pyramid **out, long long *frame_counts /* [n][8] or NULL */,
+                               long long *keyframe_counts /* [4] or NULL */, unsigned char *observations /* host, w*h, or NULL */);
+int dvo_amd_pyramid_fuse_depth_many(int n_keyframes, const dvo_amd_pyramid *const *keyframes, const int *frame_offsets /* [n_keyframes+1] */,
+                                    const dvo_amd_pyramid *const *frames, const double *T, const dvo_amd_fuse_options *opt,
+                                    dvo_amd_pyramid **out, long long *frame_counts, long long *keyframe_counts,
+                                    unsigned char *const *observations /* NULL, or n_keyframes pointers each NULL or w*h */);
+
 /* n independent match() calls advanced in lock step on one GPU (the shape of LocalTracker::update's tbb::parallel_invoke,
  * local_tracker.cpp:184, and of the loop-closure validator's parallel_reduce, keyframe_graph.cpp:576-593).
  * T_inits: n x 16 doubles or NULL.  Results are identical to n dvo_amd_match() calls BIT FOR BIT: a pair's result is a function

@@ -360,6 +360,55 @@ class RgbdImagePyramid {
     return img;
   }
 
+  // (not in the reference, which tracks against the raw keyframe) This keyframe with the level-0 depth of the frames tracked
+  // against it averaged into its own, on the device (dvo_amd.h, "Depth fusion"): a new pyramid of this one's size, intrinsics,
+  // level count and timestamp; this one and the frames are only read.  transformations[k]: for tracker.match(*this, *frames[k],
+  // result) that is result.Transformation as returned.  All pyramids must hold their levels (RgbdImagePyramid::build; a match has
+  // built them).  frame_counts: one record per frame; keyframe_counts: one record; observations: width * height bytes.
+  struct FuseOptions : dvo_amd_fuse_options {
+    FuseOptions() { dvo_amd_default_fuse_options(this); }
+  };
+  struct FuseFrameCounts {
+    long long valid, behind, outside, no_depth, consistent, occluded, seen_through, fused;
+  };
+  struct FuseKeyframeCounts {
+    long long with_depth, confirmed, unconfirmed_kept, unconfirmed_dropped;
+  };
+  Ptr fuseDepth(const std::vector<Ptr> &frames, const std::vector<AffineTransformd> &transformations,
+                const FuseOptions &options = FuseOptions(), std::vector<FuseFrameCounts> *frame_counts = nullptr,
+                FuseKeyframeCounts *keyframe_counts = nullptr, std::vector<unsigned char> *observations = nullptr) const {
+    static_assert(sizeof(FuseFrameCounts) == DVO_AMD_FUSE_FRAME_COUNTS * sizeof(long long) &&
+                      sizeof(FuseKeyframeCounts) == DVO_AMD_FUSE_KEYFRAME_COUNTS * sizeof(long long),
+                  "the count records are dvo_amd_pyramid_fuse_depth's");
+    const char *where = "RgbdImagePyramid::fuseDepth";
+    if (frames.size() != transformations.size() || frames.size() > (size_t)DVO_AMD_FUSE_MAX_FRAMES)
+      throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+    std::vector<const dvo_amd_pyramid *> handles(frames.size());
+    std::vector<double> T(16 * frames.size());
+    for (size_t k = 0; k < frames.size(); ++k) {
+      if (!frames[k]) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+      handles[k] = frames[k]->handle();
+      std::memcpy(&T[16 * k], data(transformations[k]), 16 * sizeof(double));  // column-major
+    }
+    std::vector<FuseFrameCounts> records(frames.size() + 1);
+    FuseKeyframeCounts key_record;
+    if (observations) observations->assign((size_t)width_ * height_, 0);
+    dvo_amd_pyramid *fused = nullptr;
+    detail::check(dvo_amd_pyramid_fuse_depth(handle_, (int)frames.size(), handles.data(), T.data(), &options, &fused, &records[0].valid,
+                                             &key_record.with_depth, observations ? observations->data() : nullptr),
+                  where);
+    Ptr out;
+    try {
+      out = Ptr(new RgbdImagePyramid(fused, width_, height_, K_, device_, timestamp_));
+    } catch (...) {
+      dvo_amd_pyramid_release(fused);
+      throw;
+    }
+    if (frame_counts) frame_counts->assign(records.begin(), records.end() - 1);
+    if (keyframe_counts) *keyframe_counts = key_record;
+    return out;
+  }
+
   double timestamp() const { return timestamp_; }
   int device() const { return device_; }
   int width() const { return width_; }

@@ -236,6 +236,10 @@ int dvo_amd_debug_batch_build_stats(int device, int *kernel_launches, int *copie
  * is bracketed by two events on the device's internal stream, from before its first upload to behind its last kernel; *last_ms
  * (may be NULL) receives the device time of the most recent bracketed call */
 int dvo_amd_debug_mask_ops_timing(int device, int enable, double *last_ms);
+/* with enable != 0 the fusion launch of every later dvo_amd_pyramid_fuse_depth and dvo_amd_pyramid_fuse_depth_many on `device` is
+ * bracketed by two events on the device's internal stream (the launch alone: not the tables' upload, not the pyramids' build);
+ * *last_ms (may be NULL) receives the device time of the most recent bracketed launch */
+int dvo_amd_debug_fuse_timing(int device, int enable, double *last_ms);
 
 #ifdef __cplusplus
 }
