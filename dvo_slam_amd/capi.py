@@ -57,6 +57,9 @@ EXPORTS = [
     "dvo_amd_debug_mask_ops_timing",
     "dvo_amd_default_residual_mask_options", "dvo_amd_mask_from_residuals", "dvo_amd_mask_from_residuals_many",
     "dvo_amd_default_fuse_options", "dvo_amd_pyramid_fuse_depth", "dvo_amd_pyramid_fuse_depth_many", "dvo_amd_debug_fuse_timing",
+    "dvo_amd_default_place_options", "dvo_amd_default_place_query_options", "dvo_amd_place_index_create", "dvo_amd_place_index_destroy",
+    "dvo_amd_place_index_add", "dvo_amd_place_index_info", "dvo_amd_place_index_download", "dvo_amd_place_scores", "dvo_amd_place_query",
+    "dvo_amd_place_query_frames", "dvo_amd_debug_place_timing",
 ]
 
 
@@ -173,6 +176,20 @@ class FuseOptions(C.Structure):
     _fields_ = [("near_z", C.c_float), ("depth_sigmas", C.c_float), ("min_cos", C.c_float), ("sample", C.c_int),
                 ("min_observations", C.c_int), ("drop_unconfirmed", C.c_int)]
 
+
+class PlaceOptions(C.Structure):
+    """dvo_amd_place_options, field for field"""
+    _fields_ = [("level", C.c_int), ("gain", C.c_float)]
+
+
+class PlaceQueryOptions(C.Structure):
+    """dvo_amd_place_query_options, field for field"""
+    _fields_ = [("k", C.c_int), ("min_score", C.c_double), ("exclude_recent", C.c_int)]
+
+
+PLACE_MAX_K = 64
+PLACE_MAX_DIM = 65536
+PLACE_INITIAL_CAPACITY = 64
 
 FUSE_BILINEAR, FUSE_NEAREST = 0, 1
 FUSE_MAX_FRAMES = 255
@@ -396,6 +413,20 @@ def lib():
     L.dvo_amd_pyramid_fuse_depth_many.argtypes = [C.c_int, C.POINTER(vp), ip, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
                                                   C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(vp)]
     L.dvo_amd_debug_fuse_timing.argtypes = [C.c_int, C.c_int, dp]
+    L.dvo_amd_default_place_options.argtypes = [C.POINTER(PlaceOptions)]
+    L.dvo_amd_default_place_options.restype = None
+    L.dvo_amd_default_place_query_options.argtypes = [C.POINTER(PlaceQueryOptions)]
+    L.dvo_amd_default_place_query_options.restype = None
+    L.dvo_amd_place_index_create.argtypes = [C.c_int, C.POINTER(PlaceOptions), C.POINTER(vp)]
+    L.dvo_amd_place_index_destroy.argtypes = [vp]
+    L.dvo_amd_place_index_destroy.restype = None
+    L.dvo_amd_place_index_add.argtypes = [vp, C.c_int, C.POINTER(vp), ip]
+    L.dvo_amd_place_index_info.argtypes = [vp, ip, ip, ip, ip]
+    L.dvo_amd_place_index_download.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_byte), ip]
+    L.dvo_amd_place_scores.argtypes = [vp, C.c_int, ip, C.c_int, C.c_int, ip]
+    L.dvo_amd_place_query.argtypes = [vp, C.c_int, ip, C.POINTER(PlaceQueryOptions), ip, dp, ip]
+    L.dvo_amd_place_query_frames.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(PlaceQueryOptions), ip, dp, ip]
+    L.dvo_amd_debug_place_timing.argtypes = [C.c_int, C.c_int, dp]
     L.dvo_amd_se3_exp.argtypes = [dp, dp]
     L.dvo_amd_se3_exp.restype = None
     L.dvo_amd_se3_log.argtypes = [dp, dp]
@@ -1886,6 +1917,127 @@ def find_constraint_candidates(tracker, keyframes, keyframe: int, max_distance: 
         err.needed = n.value
         raise err
     return [int(k) for k in cand[:n.value]], over[:n.value].copy()
+
+
+def place_options(**options) -> PlaceOptions:
+    """dvo_amd_default_place_options (level 3, gain 1) with the given fields replaced"""
+    opt = PlaceOptions()
+    lib().dvo_amd_default_place_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in ("level", "gain"):
+            raise TypeError(f"unknown place option {k!r}")
+        setattr(opt, k, int(v) if k == "level" else float(v))
+    return opt
+
+
+def place_query_options(**options) -> PlaceQueryOptions:
+    """dvo_amd_default_place_query_options (k 5, min_score 0, exclude_recent 0) with the given fields replaced"""
+    opt = PlaceQueryOptions()
+    lib().dvo_amd_default_place_query_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in ("k", "min_score", "exclude_recent"):
+            raise TypeError(f"unknown place query option {k!r}")
+        setattr(opt, k, float(v) if k == "min_score" else int(v))
+    return opt
+
+
+def place_timing(enable: bool = True, device: int = 0) -> float:
+    """(instrumentation) switches the event bracket around the kernel launches of every PlaceIndex.scores / query / query_frames of
+    `device` on or off and returns the device time of the most recent bracketed call in ms (dvo_amd_debug_place_timing)"""
+    ms = C.c_double()
+    _check(lib().dvo_amd_debug_place_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_place_timing")
+    return ms.value
+
+
+class PlaceIndex:
+    """dvo_amd_place_index: loop-closure candidates by appearance.  One int8 descriptor per keyframe on the device (the rule is
+    pinned in include/dvo_amd.h under "Place index"); ids are consecutive from 0 in insertion order; nothing is ever removed."""
+
+    def __init__(self, level: int | None = None, gain: float | None = None, device: int = 0):
+        options = {k: v for k, v in (("level", level), ("gain", gain)) if v is not None}
+        opt = place_options(**options)
+        self._h = C.c_void_p()
+        _check(lib().dvo_amd_place_index_create(device, C.byref(opt), C.byref(self._h)), "dvo_amd_place_index_create")
+        self.device, self.level, self.gain = device, opt.level, opt.gain
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().dvo_amd_place_index_destroy(h)
+            self._h = None
+
+    def add(self, pyramids) -> range:
+        """the descriptors of `pyramids` appended in ONE kernel launch (dvo_amd_place_index_add); returns their ids"""
+        pyramids = list(pyramids)
+        n = len(pyramids)
+        first = C.c_int()
+        _check(lib().dvo_amd_place_index_add(self._h, n, (C.c_void_p * max(1, n))(*[p._h for p in pyramids]), C.byref(first)),
+               "dvo_amd_place_index_add")
+        return range(first.value, first.value + n)
+
+    def info(self) -> dict:
+        """{"size", "width", "height", "dim"}: width, height and dim are 0 before the first add"""
+        v = [C.c_int() for _ in range(4)]
+        _check(lib().dvo_amd_place_index_info(self._h, *[C.byref(x) for x in v]), "dvo_amd_place_index_info")
+        return dict(zip(("size", "width", "height", "dim"), (x.value for x in v)))
+
+    def __len__(self) -> int:
+        return self.info()["size"]
+
+    def _range(self, first, n):
+        return int(first), len(self) - int(first) if n is None else int(n)
+
+    def descriptors(self, first: int = 0, n: int | None = None):
+        """(int8 [n, dim], int32 norms [n]) of rows first .. first + n (n None: to the end)"""
+        first, n = self._range(first, n)
+        dim = self.info()["dim"]
+        rows, norms = np.zeros((max(n, 0), dim), np.int8), np.zeros(max(n, 0), np.int32)
+        _check(lib().dvo_amd_place_index_download(self._h, first, n, rows.ctypes.data_as(C.POINTER(C.c_byte)),
+                                                  norms.ctypes.data_as(C.POINTER(C.c_int))), "dvo_amd_place_index_download")
+        return rows, norms
+
+    def scores(self, query_ids, first: int = 0, n: int | None = None) -> np.ndarray:
+        """the exact int32 dot products [len(query_ids), n] of the rows `query_ids` with rows first .. first + n"""
+        first, n = self._range(first, n)
+        ids = np.ascontiguousarray(query_ids, dtype=np.int32).reshape(-1)
+        dots = np.zeros((len(ids), max(n, 0)), np.int32)
+        _check(lib().dvo_amd_place_scores(self._h, len(ids), ids.ctypes.data_as(C.POINTER(C.c_int)), first, n,
+                                          dots.ctypes.data_as(C.POINTER(C.c_int))), "dvo_amd_place_scores")
+        return dots
+
+    @staticmethod
+    def _query_options(options, k, min_score, exclude_recent):
+        if isinstance(options, PlaceQueryOptions):
+            return options
+        given = {name: v for name, v in (("k", k), ("min_score", min_score), ("exclude_recent", exclude_recent)) if v is not None}
+        return place_query_options(**given)
+
+    @staticmethod
+    def _found(nq, k):
+        return np.full((nq, k), -1, np.int32), np.full((nq, k), np.nan, np.float64), np.zeros(max(nq, 1), np.int32)
+
+    def query(self, ids, k: int | None = None, min_score: float | None = None, exclude_recent: int | None = None, options=None):
+        """per row id of `ids` the k most similar other rows (dvo_amd_place_query): (candidates int32 [n, k], scores float64 [n, k],
+        counts int32 [n]); behind counts[i] a row holds -1 / NaN.  A key within exclude_recent ids of the query is not eligible."""
+        opt = self._query_options(options, k, min_score, exclude_recent)
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        cand, score, counts = self._found(len(ids), max(opt.k, 1))
+        ip = C.POINTER(C.c_int)
+        _check(lib().dvo_amd_place_query(self._h, len(ids), ids.ctypes.data_as(ip), C.byref(opt), cand.ctypes.data_as(ip),
+                                         score.ctypes.data_as(C.POINTER(C.c_double)), counts.ctypes.data_as(ip)), "dvo_amd_place_query")
+        return cand, score, counts[:len(ids)]
+
+    def query_frames(self, pyramids, k: int | None = None, min_score: float | None = None, options=None):
+        """query for pyramids that are not in the index (dvo_amd_place_query_frames): no key is excluded"""
+        opt = self._query_options(options, k, min_score, None)
+        pyramids = list(pyramids)
+        n = len(pyramids)
+        cand, score, counts = self._found(n, max(opt.k, 1))
+        ip = C.POINTER(C.c_int)
+        _check(lib().dvo_amd_place_query_frames(self._h, n, (C.c_void_p * max(1, n))(*[p._h for p in pyramids]), C.byref(opt),
+                                                cand.ctypes.data_as(ip), score.ctypes.data_as(C.POINTER(C.c_double)),
+                                                counts.ctypes.data_as(ip)), "dvo_amd_place_query_frames")
+        return cand, score, counts[:n]
 
 
 def se3_exp(xi) -> np.ndarray:

@@ -329,3 +329,40 @@ class NearestNeighborConstraintSearch:
         found, self.overlaps = capi.find_constraint_candidates(self.tracker, all, at, self._max_distance, self._min_overlap,
                                                                **self.options)
         return [all[i] for i in found]
+
+
+class AppearanceConstraintSearch:
+    """This library's second candidate source, beside the radius search: the keyframes that LOOK like `keyframe`, whatever the
+    estimated poses say (capi.PlaceIndex, dvo_amd_place_query).  Same call and return type as NearestNeighborConstraintSearch, so
+    proposalsForCandidates and the validator take its output unchanged; the query keyframe itself is never returned.  Keyframe
+    all[i] has index id i: a search adds the keyframes of `all` that the index does not hold yet, so `all` may only grow at its
+    end between searches.  findForFrame asks the same of a pyramid that is no keyframe (relocalisation: no pose is needed).
+    `scores` holds the cosines of the last search, one per returned keyframe, best first."""
+
+    def __init__(self, index: capi.PlaceIndex | None = None, k: int = 5, min_score: float = 0.0, exclude_recent: int = 0, device: int = 0,
+                 **index_options):
+        self.index = index if index is not None else capi.PlaceIndex(device=device, **index_options)
+        self.k, self.min_score, self.exclude_recent = int(k), float(min_score), int(exclude_recent)
+        self.scores = np.zeros(0)
+
+    def _sync(self, all: list):
+        have = len(self.index)
+        if have > len(all):
+            raise ValueError("the index holds more keyframes than `all`")
+        if have < len(all):
+            self.index.add([kf.image for kf in all[have:]])
+
+    def findPossibleConstraints(self, all: list, keyframe: Keyframe) -> list:
+        at = next((i for i, kf in enumerate(all) if kf is keyframe), None)
+        if at is None:
+            raise ValueError("`keyframe` is not one of `all`")
+        self._sync(all)
+        cand, scores, counts = self.index.query([at], k=self.k, min_score=self.min_score, exclude_recent=self.exclude_recent)
+        self.scores = scores[0, :counts[0]].copy()
+        return [all[i] for i in cand[0, :counts[0]]]
+
+    def findForFrame(self, all: list, pyramid: capi.RgbdImagePyramid) -> list:
+        self._sync(all)
+        cand, scores, counts = self.index.query_frames([pyramid], k=self.k, min_score=self.min_score)
+        self.scores = scores[0, :counts[0]].copy()
+        return [all[i] for i in cand[0, :counts[0]]]

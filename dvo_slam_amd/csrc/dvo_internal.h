@@ -15,6 +15,7 @@
 //   dvo_mask_ops.cpp  masks from masks: combine, dilate / erode, warp onto another frame through both frames' depth
 //   dvo_mask_residual.cpp  masks from an alignment's residuals: inliers of the t-distribution at a transformation
 //   dvo_fuse.cpp      depth fusion: the frames tracked against a keyframe averaged into its depth plane, a new pyramid from it
+//   dvo_place.cpp     the place index: int8 appearance descriptors of keyframes, their dot products, the best k per query
 //   dvo_register.cpp  depth-to-colour registration: the kernels that splat another camera's raw depth into level 0's depth plane
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once

@@ -3034,4 +3034,216 @@ hipError_t launch_compact_batch(const BatchFrame *frames, int count, const Batch
   });
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// the place index (dvo_amd_place_*, dvo_place.cpp): int8 appearance descriptors, their dot products, the best k per query
+// ------------------------------------------------------------------------------------------------------------------
+// The rule is pinned in include/dvo_amd.h under "Place index"; tests/place_ref.py restates it.  Everything a kernel below leaves in
+// memory is an integer or a double formed from integers by two products in a fixed order: nothing depends on the launch geometry.
+
+// One block per pyramid.  A thread takes four consecutive pixels at a time (dim is a multiple of 64): four int8 values, one
+// 32-bit store, the zero padding behind w * h included.  The row's norm is one reduction over the block: no atomics.
+__global__ __launch_bounds__(kPlaceBlock) void k_place_describe(const float *const *__restrict__ planes, int w, int h, int dim, float gain,
+                                                               signed char *__restrict__ rows, int *__restrict__ nn) {
+  __shared__ int s_sum[kPlaceBlock / kWave];
+  const float *__restrict__ I = planes[blockIdx.x];
+  signed char *__restrict__ row = rows + (size_t)blockIdx.x * (size_t)dim;
+  const int n = w * h;
+  int sum = 0;
+  for (int p0 = (int)threadIdx.x * 4; p0 < dim; p0 += kPlaceBlock * 4) {
+    unsigned word = 0u;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int p = p0 + i;
+      int q = 0;
+      if (p < n) {
+        const int v = p / w, u = p - v * w;
+        const int v0 = v > 0 ? v - 1 : 0, v1 = v < h - 1 ? v + 1 : h - 1;
+        const int u0 = u > 0 ? u - 1 : 0, u1 = u < w - 1 ? u + 1 : w - 1;
+        float s = 0.0f;
+        for (int y = v0; y <= v1; ++y)
+          for (int x = u0; x <= u1; ++x) s = s + I[y * w + x];
+        const float c = (float)((v1 - v0 + 1) * (u1 - u0 + 1));
+        const float m = s / c;
+        const float d = (I[p] - m) * gain;
+        if (fabsf(d) <= 3.402823466e38f) q = (int)fminf(127.0f, fmaxf(-127.0f, rintf(d)));  // (false for NaN: q stays 0)
+      }
+      sum += q * q;
+      word |= (unsigned)(q & 0xff) << (8 * i);
+    }
+    *(unsigned *)(row + p0) = word;  // (p0 + 3 < dim; rows are 64-byte aligned)
+  }
+#pragma unroll
+  for (int off = kWave / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+  if ((threadIdx.x & (kWave - 1)) == 0) s_sum[threadIdx.x / kWave] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int total = 0;
+#pragma unroll
+    for (int k = 0; k < kPlaceBlock / kWave; ++k) total += s_sum[k];
+    nn[blockIdx.x] = total;  // <= 65536 * 127 * 127 < 2^31
+  }
+}
+
+hipError_t launch_place_describe(const float *const *planes, int n, int w, int h, int dim, float gain, signed char *rows, int *nn,
+                                 hipStream_t stream) {
+  LaunchGuard guard;
+  hipLaunchKernelGGL(k_place_describe, dim3((unsigned)n), dim3(kPlaceBlock), 0, stream, planes, w, h, dim, gain, rows, nn);
+  return hipGetLastError();
+}
+
+// dots = Q . X^T with v_mfma_i32_16x16x64_i8.  A workgroup owns a tile of T x T blocks of 16 queries x 16 keys; its four waves
+// split the k-steps of 64 bytes between them (wave s takes steps s, s + 4, ...: integer sums, any order gives the same result) and
+// wave 0 adds the other three's partial tiles through LDS and writes.  Both operands are rows contiguous along k: lane l's
+// fragment of either is the 16 bytes at [row l & 15][64 * step + 16 * (l >> 4)] -- one 16-byte load -- and because both sides use
+// the same lane -> k rule the order of k inside the instruction does not matter to a dot product.  The result block has its key on
+// the lane and its queries in the registers: D[query 4 * (l >> 4) + reg][key l & 15].
+// A partial tile reads, for the rows it lacks, the last row that exists instead of zeros: an element of D depends on its own
+// query row and its own key row alone, so every load is unconditional and in bounds and the elements outside n_queries x n are
+// simply not written.
+typedef int place_i4 __attribute__((ext_vector_type(4)));
+
+template <int T>
+__global__ __launch_bounds__(kPlaceBlock) void k_place_dots(const signed char *__restrict__ index, const int *__restrict__ query_ids,
+                                                           const signed char *__restrict__ queries, int n_queries,
+                                                           const signed char *__restrict__ keys, int n, int dim, int *__restrict__ dots) {
+  constexpr int kWaves = kPlaceBlock / kWave;
+  constexpr int kRegs = T * T * 4;  // accumulator registers of a wave
+  __shared__ int s_part[(kWaves - 1) * kRegs * kWave];
+  const int lane = (int)threadIdx.x & (kWave - 1), wave = (int)threadIdx.x / kWave;
+  const int q0 = (int)blockIdx.y * (16 * T), k0 = (int)blockIdx.x * (16 * T);
+  const int in_block = lane & 15, at = (lane >> 4) * 16;
+  const signed char *a_row[T], *b_row[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+    const int q = min(q0 + 16 * t + in_block, n_queries - 1), j = min(k0 + 16 * t + in_block, n - 1);
+    a_row[t] = (query_ids ? index + (size_t)query_ids[q] * (size_t)dim : queries + (size_t)q * (size_t)dim) + at;
+    b_row[t] = keys + (size_t)j * (size_t)dim + at;
+  }
+  place_i4 acc[T][T];
+#pragma unroll
+  for (int i = 0; i < T; ++i)
+#pragma unroll
+    for (int j = 0; j < T; ++j) acc[i][j] = place_i4{0, 0, 0, 0};
+  const int steps = dim / 64;
+  // pipelined by one step: the fragments of the wave's next step are in flight while this step's feed the matrix pipe (behind
+  // the wave's last step the same fragments are loaded once more: in bounds, not used)
+  place_i4 a[T], b[T];
+  {
+    const size_t off = (size_t)min(wave, steps - 1) * 64;
+#pragma unroll
+    for (int t = 0; t < T; ++t) a[t] = *(const place_i4 *)(a_row[t] + off), b[t] = *(const place_i4 *)(b_row[t] + off);
+  }
+  for (int s = wave; s < steps; s += kWaves) {
+    const size_t off = (size_t)(s + kWaves < steps ? s + kWaves : s) * 64;
+    place_i4 an[T], bn[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) an[t] = *(const place_i4 *)(a_row[t] + off), bn[t] = *(const place_i4 *)(b_row[t] + off);
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < T; ++t) a[t] = an[t], b[t] = bn[t];
+  }
+  if (wave > 0) {
+#pragma unroll
+    for (int i = 0; i < T; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j)
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) s_part[((wave - 1) * kRegs + (i * T + j) * 4 + reg) * kWave + lane] = acc[i][j][reg];
+  }
+  __syncthreads();
+  if (wave > 0) return;
+#pragma unroll
+  for (int i = 0; i < T; ++i)
+#pragma unroll
+    for (int j = 0; j < T; ++j) {
+      const int key = k0 + 16 * j + in_block;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int q = q0 + 16 * i + 4 * (lane >> 4) + reg;
+        int v = acc[i][j][reg];
+#pragma unroll
+        for (int o = 0; o < kWaves - 1; ++o) v += s_part[(o * kRegs + (i * T + j) * 4 + reg) * kWave + lane];
+        if (q < n_queries && key < n) dots[(size_t)q * (size_t)n + (size_t)key] = v;
+      }
+    }
+}
+
+hipError_t launch_place_dots(const signed char *index, const int *query_ids, const signed char *queries, int n_queries,
+                             const signed char *keys, int n, int dim, int *dots, int tile, hipStream_t stream) {
+  if (n_queries <= 0 || n <= 0) return hipSuccess;
+  LaunchGuard guard;
+  // the 1 x N query is bound by reading N rows: small tiles spread them over the device; many queries want reuse of a fragment
+  if (tile != 1 && tile != 2 && tile != 4) tile = n_queries <= 16 ? 1 : n_queries <= 32 ? 2 : 4;
+  const int side = 16 * tile;
+  const dim3 grid((unsigned)((n + side - 1) / side), (unsigned)((n_queries + side - 1) / side));
+  if (tile == 1)
+    hipLaunchKernelGGL(k_place_dots<1>, grid, dim3(kPlaceBlock), 0, stream, index, query_ids, queries, n_queries, keys, n, dim, dots);
+  else if (tile == 2)
+    hipLaunchKernelGGL(k_place_dots<2>, grid, dim3(kPlaceBlock), 0, stream, index, query_ids, queries, n_queries, keys, n, dim, dots);
+  else
+    hipLaunchKernelGGL(k_place_dots<4>, grid, dim3(kPlaceBlock), 0, stream, index, query_ids, queries, n_queries, keys, n, dim, dots);
+  return hipGetLastError();
+}
+
+// One block per query: k rounds of arg-max over the query's row of dots.  The order is (score descending, id ascending), so the
+// pick of a round is the best key that comes strictly after the previous pick in that order: nothing is marked, nothing is sorted.
+// score = ((double)dot * r_query) * r[j]: two double products, each rounded on its own (no contraction).
+__global__ __launch_bounds__(kPlaceBlock) void k_place_topk(const int *__restrict__ dots, int n, const int *__restrict__ query_ids,
+                                                           const double *__restrict__ r_query, const double *__restrict__ r, int k,
+                                                           double min_score, int exclude_recent, int *__restrict__ candidates,
+                                                           double *__restrict__ scores, int *__restrict__ counts) {
+  constexpr int kWaves = kPlaceBlock / kWave;
+  constexpr int kNone = 0x7fffffff;
+  __shared__ double s_score[kWaves];
+  __shared__ int s_id[kWaves];
+  const int i = (int)blockIdx.x;
+  const int *__restrict__ row = dots + (size_t)i * (size_t)n;
+  const int qid = query_ids[i];  // < 0: a frame, no key is excluded
+  const double rq = r_query[i];
+  double prev_score = __builtin_huge_val();
+  int prev_id = -1, found = 0;
+  for (int round = 0; round < k; ++round) {
+    double best = -__builtin_huge_val();
+    int best_id = kNone;
+    for (int j = (int)threadIdx.x; j < n; j += kPlaceBlock) {
+      const int apart = j > qid ? j - qid : qid - j;
+      const bool eligible = qid < 0 || apart > exclude_recent;  // (exclude_recent >= 0: the query's own row is never eligible)
+      const double s = ((double)row[j] * rq) * r[j];
+      const bool after = s < prev_score || (s == prev_score && j > prev_id);
+      if (eligible && s >= min_score && after && (s > best || (s == best && j < best_id))) best = s, best_id = j;
+    }
+#pragma unroll
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+      const double os = __shfl_xor(best, off);
+      const int oi = __shfl_xor(best_id, off);
+      if (os > best || (os == best && oi < best_id)) best = os, best_id = oi;
+    }
+    if ((threadIdx.x & (kWave - 1)) == 0) s_score[threadIdx.x / kWave] = best, s_id[threadIdx.x / kWave] = best_id;
+    __syncthreads();
+    best = s_score[0], best_id = s_id[0];
+#pragma unroll
+    for (int wv = 1; wv < kWaves; ++wv)
+      if (s_score[wv] > best || (s_score[wv] == best && s_id[wv] < best_id)) best = s_score[wv], best_id = s_id[wv];
+    __syncthreads();  // (the next round writes s_score again)
+    if (best_id == kNone) break;  // (the same in every thread: nothing is left)
+    if (threadIdx.x == 0) candidates[(size_t)i * k + round] = best_id, scores[(size_t)i * k + round] = best;
+    prev_score = best, prev_id = best_id, ++found;
+  }
+  for (int t = found + (int)threadIdx.x; t < k; t += kPlaceBlock) candidates[(size_t)i * k + t] = -1, scores[(size_t)i * k + t] = __builtin_nan("");
+  if (threadIdx.x == 0) counts[i] = found;
+}
+
+hipError_t launch_place_topk(const int *dots, int n_queries, int n, const int *query_ids, const double *r_query, const double *r,
+                             int k, double min_score, int exclude_recent, int *candidates, double *scores, int *counts,
+                             hipStream_t stream) {
+  if (n_queries <= 0) return hipSuccess;
+  LaunchGuard guard;
+  hipLaunchKernelGGL(k_place_topk, dim3((unsigned)n_queries), dim3(kPlaceBlock), 0, stream, dots, n, query_ids, r_query, r, k, min_score,
+                     exclude_recent, candidates, scores, counts);
+  return hipGetLastError();
+}
+
 }  // namespace dvo_amd

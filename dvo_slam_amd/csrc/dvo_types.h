@@ -488,4 +488,20 @@ struct ResidualMaskRecord {
 };
 hipError_t launch_residual_mask(const ResidualMaskRecord *records, int n_records, int max_n, hipStream_t stream);
 
+// ---- the place index (dvo_amd_place_*, dvo_place.cpp; the rule is pinned in include/dvo_amd.h under "Place index")
+constexpr int kPlaceBlock = 256;
+// k_place_describe: one block per pyramid; planes[i] is the intensity plane (w x h) of pyramid i, row i of `rows` (dim bytes, dim a
+// multiple of 64, zero behind w * h) and nn[i] are its descriptor and its norm
+hipError_t launch_place_describe(const float *const *planes, int n, int w, int h, int dim, float gain, signed char *rows, int *nn,
+                                 hipStream_t stream);
+// k_place_dots: dots[i * n + j] = query i . key j over dim bytes.  Key j is row j of `keys`; query i is row query_ids[i] of `index`
+// or, with query_ids == nullptr, row i of `queries`.  tile: 16-row blocks per side of a workgroup's tile (1, 2 or 4; 0 = by n_queries)
+hipError_t launch_place_dots(const signed char *index, const int *query_ids, const signed char *queries, int n_queries,
+                             const signed char *keys, int n, int dim, int *dots, int tile, hipStream_t stream);
+// k_place_topk: one block per query over its row of dots[n_queries x n]; key j has id j (the whole index).  query_ids[i] < 0: a
+// frame, to which no exclusion applies.  candidates / scores: k per query, counts: one
+hipError_t launch_place_topk(const int *dots, int n_queries, int n, const int *query_ids, const double *r_query, const double *r,
+                             int k, double min_score, int exclude_recent, int *candidates, double *scores, int *counts,
+                             hipStream_t stream);
+
 }  // namespace dvo_amd

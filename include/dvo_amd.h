@@ -1044,6 +1044,91 @@ int dvo_amd_find_constraint_candidates(dvo_amd_context *ctx, int n_keyframes, co
                                        float max_distance, double min_overlap, const dvo_amd_covisibility_options *opt,
                                        int *candidates, double *overlap, int capacity, int *n_out);
 
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Place index: loop-closure candidates by appearance, on the device.
+ *
+ * dvo_amd_find_constraint_candidates trusts the estimated poses in both of its stages.  After a long loop the true revisit lies
+ * outside max_distance and is never proposed; when tracking is lost there is no pose to search around.  A dvo_amd_place_index
+ * answers "which keyframes look like this one / like this frame" without any pose: it keeps one int8 descriptor per keyframe on the
+ * device and returns, per query, the k keys of highest cosine.  Its output is a candidate list like the radius search's: it feeds
+ * dvo_amd_proposals_for_candidates and the validator unchanged.  (The reference has no counterpart: keyframe_constraint_search.cpp is
+ * all it has.)  The entries take no context: like the mask operations and the depth fusion they run on the device's internal
+ * stream, use no tracker slot and may be called while pairs are queued.  Pyramids are only read.  Calls on one index are serialised
+ * by the index; different indices are independent.
+ *
+ * The descriptor of a pyramid is its intensity plane I at level `level` (width w, height h), high-passed and quantised.  Per
+ * pixel p = (u, v), in fp32, operation by operation (the library is built without contraction; the division is correctly rounded):
+ *  1. s = the sum of I over the 3x3 neighbourhood of p clipped to the plane, rows ascending, columns ascending within a row, added
+ *     one after the other starting from 0.0f; c = the number of pixels summed (4, 6 or 9) as a float;
+ *  2. m = s / c; d = (I[p] - m) * gain;
+ *  3. q[p] = 0 if d is not finite, otherwise (int8) min(127, max(-127, rintf(d))), ties to even.  -128 never occurs.
+ * A descriptor is the w * h values in row-major order, zero-padded to dim = 64 * ceil(w * h / 64) bytes; its norm is nn = sum q * q,
+ * an int32 (dim <= DVO_AMD_PLACE_MAX_DIM, so the sum cannot overflow: a larger level is refused).  Removing the local mean makes the
+ * descriptor invariant to a brightness offset, the cosine below makes the score invariant to a gain.
+ *
+ * The index is a growable row-major N x dim int8 matrix on the device with nn and r per row.  r = 1.0 / sqrt((double)nn), formed in
+ * double ON THE HOST when the row is added (correctly rounded square root and quotient), and 0 when nn == 0.  Ids are the rows'
+ * positions: consecutive from 0 in insertion order.  The first add fixes (w, h).  The capacity starts at
+ * DVO_AMD_PLACE_INITIAL_CAPACITY rows and doubles: growth allocates anew and copies on the device.
+ *
+ * dvo_amd_place_index_add describes all n pyramids in ONE kernel launch and synchronises once; *first_id (may be NULL) receives
+ * the id of pyramids[0].  dvo_amd_place_index_info: any of the four outputs may be NULL; width, height and dim are 0 before the
+ * first add.  dvo_amd_place_index_download: rows [first, first + n) as n * dim bytes and n norms (either may be NULL).
+ * dvo_amd_place_scores: dots[i * n + j] = sum_k q_{query_ids[i]}[k] * q_{first + j}[k], an exact int32, computed on the int8 matrix
+ * instruction.
+ * dvo_amd_place_query: key j is eligible for query i iff |j - query_ids[i]| > exclude_recent (so never the query's own row) and
+ * score >= min_score, where score = ((double)dot * r_query) * r_j: two double products, each rounded on its own.  The result of a
+ * query is the k eligible keys of highest score, ties going to the lower id, ordered by descending score, then ascending id:
+ * candidates[i * k + t] and scores[i * k + t] for t < counts[i], -1 and NaN behind.  dvo_amd_place_query_frames does the same for
+ * pyramids that are not in the index: their descriptors are built into scratch with the index's options, their norms come back to
+ * the host for r_query (one more synchronisation), and no key is excluded, a frame having no id.  Against an empty index every
+ * count is 0.  The dots of a query call live in device scratch; above DVO_AMD_PLACE_DOTS_CAP_MB they are processed in panels of query
+ * rows.  Every value is an integer or a double formed from integers in a fixed order: no result depends on the launch geometry, on
+ * the panels or on what else is in the call.
+ *
+ * Errors, before any device work.  DVO_AMD_ERR_INVALID_ARGUMENT with a reason in dvo_amd_last_error() that starts with the entry's
+ * name: a NULL pointer (inside the arrays too; an array only where its count is positive); a negative count; an id or a range
+ * outside the index; level outside 0 .. DVO_AMD_MAX_LEVELS - 1; gain not finite or <= 0; k outside 1 .. DVO_AMD_PLACE_MAX_K; a NaN
+ * min_score; a negative exclude_recent; a pyramid with fewer than level + 1 levels; a pyramid whose level has another size than the
+ * index's (in the first add: than the call's first pyramid's); w * h > DVO_AMD_PLACE_MAX_DIM.  Then DVO_AMD_ERR_DEVICE_MISMATCH for
+ * a pyramid of another device than the index's, then DVO_AMD_ERR_NO_DEVICE.  n == 0 / n_queries == 0 is DVO_AMD_OK and does nothing.
+ * dvo_amd_place_index_create needs a device: DVO_AMD_ERR_NO_DEVICE without one, then DVO_AMD_ERR_INVALID_ARGUMENT for a device that
+ * does not exist; *out is NULL on every failure.
+ *
+ * Not covered: rows are never removed or re-ordered; one image size per index; no viewpoint invariance beyond what a coarse level
+ * gives; no depth in the descriptor.  The entry only proposes: the validator still decides.
+ */
+#define DVO_AMD_PLACE_MAX_K 64
+#define DVO_AMD_PLACE_MAX_DIM 65536
+#define DVO_AMD_PLACE_INITIAL_CAPACITY 64
+#define DVO_AMD_PLACE_DOTS_CAP_MB 256
+typedef struct dvo_amd_place_index dvo_amd_place_index;
+typedef struct dvo_amd_place_options {
+  int level;   /* default 3 */
+  float gain;  /* default 1; finite, > 0 */
+} dvo_amd_place_options;
+typedef struct dvo_amd_place_query_options {
+  int k;               /* 1 .. DVO_AMD_PLACE_MAX_K; default 5 */
+  double min_score;    /* default 0; NaN refused */
+  int exclude_recent;  /* default 0; >= 0 */
+} dvo_amd_place_query_options;
+/* level 3, gain 1 / k 5, min_score 0, exclude_recent 0; a NULL opt is a no-op */
+void dvo_amd_default_place_options(dvo_amd_place_options *opt);
+void dvo_amd_default_place_query_options(dvo_amd_place_query_options *opt);
+int dvo_amd_place_index_create(int device, const dvo_amd_place_options *opt, dvo_amd_place_index **out);
+void dvo_amd_place_index_destroy(dvo_amd_place_index *index);
+int dvo_amd_place_index_add(dvo_amd_place_index *index, int n, const dvo_amd_pyramid *const *pyramids, int *first_id);
+int dvo_amd_place_index_info(const dvo_amd_place_index *index, int *size, int *width, int *height, int *dim);
+int dvo_amd_place_index_download(const dvo_amd_place_index *index, int first, int n, signed char *descriptors /* n * dim, or NULL */,
+                                 int *norms /* n, or NULL */);
+int dvo_amd_place_scores(const dvo_amd_place_index *index, int n_queries, const int *query_ids, int first, int n,
+                         int *dots /* n_queries * n */);
+int dvo_amd_place_query(const dvo_amd_place_index *index, int n_queries, const int *query_ids,
+                        const dvo_amd_place_query_options *opt, int *candidates /* n_queries * k */, double *scores /* n_queries * k */,
+                        int *counts /* n_queries */);
+int dvo_amd_place_query_frames(const dvo_amd_place_index *index, int n_queries, const dvo_amd_pyramid *const *frames,
+                               const dvo_amd_place_query_options *opt, int *candidates, double *scores, int *counts);
+
 /*
  * Dual-match front-end step: the two alignments LocalTracker::update runs per frame with
  * tbb::parallel_invoke (local_tracker.cpp:170-186) -- keyframe -> frame starting from last_keyframe_pose^-1 and

@@ -6,6 +6,8 @@
 //   dvo_slam::Keyframe {id, image, pose, evaluation}     dvo_slam/include/dvo_slam/keyframe.h
 //   dvo_slam::KeyframeConstraintSearchInterface, dvo_slam::NearestNeighborConstraintSearch
 //                                                        dvo_slam/include/dvo_slam/keyframe_constraint_search.h:30-58
+//   dvo_slam::AppearanceConstraintSearch                 (not in the reference) the same interface over dvo_amd_place_index:
+//                                                        candidates by appearance, no pose asked for
 //   dvo_slam::constraints::ConstraintProposal            .../constraints/constraint_proposal.h:34-90
 //   dvo_slam::constraints::{CrossValidation, TrackingResultEvaluation, ConstraintRatio, NaNResult, OdometryConstraint}Voter
 //                                                        .../constraints/constraint_proposal_voter.h
@@ -176,6 +178,86 @@ class NearestNeighborConstraintSearch : public KeyframeConstraintSearchInterface
   dvo_amd_covisibility_options options_;
   std::unique_ptr<dvo::DenseTracker> tracker_;
   std::vector<double> overlaps_;
+};
+
+// This library's second candidate source, beside the radius search: the keyframes that LOOK like `keyframe`, whatever the estimated
+// poses say (dvo_amd_place_index; the rule is pinned in dvo_amd.h under "Place index").  After a long loop the true revisit lies
+// outside maxDistance(), and when tracking is lost there is no pose to search around: this search needs none.  The interface is
+// the reference's, so validateKeyframeConstraintsParallel's proposals and the validator take its output unchanged; the query
+// keyframe itself is never returned, the candidates come best first.  Keyframe all[i] has index id i: a search adds the keyframes
+// of `all` that the index does not hold yet (their images are built to indexOptions().level + 1 levels), so `all` may only grow
+// at its end between searches.  findForFrame asks the same of an image that is no keyframe (relocalisation).
+class AppearanceConstraintSearch : public KeyframeConstraintSearchInterface {
+ public:
+  explicit AppearanceConstraintSearch(int k = 5, double min_score = 0.0, int exclude_recent = 0, int device = 0)
+      : index_(nullptr), device_(device) {
+    dvo_amd_default_place_options(&options_);
+    dvo_amd_default_place_query_options(&query_);
+    query_.k = k, query_.min_score = min_score, query_.exclude_recent = exclude_recent;
+  }
+  virtual ~AppearanceConstraintSearch() { dvo_amd_place_index_destroy(index_); }
+  AppearanceConstraintSearch(const AppearanceConstraintSearch &) = delete;
+  AppearanceConstraintSearch &operator=(const AppearanceConstraintSearch &) = delete;
+
+  dvo_amd_place_options &indexOptions() { return options_; }  // read when the first search creates the index
+  dvo_amd_place_query_options &queryOptions() { return query_; }
+  // of the last search, one per candidate returned: the cosine of the two descriptors
+  const std::vector<double> &scores() const { return scores_; }
+  // the index (NULL before the first search): dvo_amd_place_scores, dvo_amd_place_index_download and the rest take it
+  const dvo_amd_place_index *index() const { return index_; }
+
+  void findPossibleConstraints(const KeyframeVector &all, const KeyframePtr &keyframe, KeyframeVector &candidates) override {
+    static const char *where = "AppearanceConstraintSearch::findPossibleConstraints";
+    int at = -1;
+    for (size_t i = 0; i < all.size(); ++i)
+      if (all[i] == keyframe) at = (int)i;
+    if (at < 0) throw dvo::DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+    sync(all, where);
+    std::vector<int> found((size_t)query_.k, -1);
+    int count = 0;
+    scores_.assign((size_t)query_.k, 0.0);
+    dvo::detail::check(dvo_amd_place_query(index_, 1, &at, &query_, found.data(), scores_.data(), &count), where);
+    take(all, found, count, candidates);
+  }
+
+  void findForFrame(const KeyframeVector &all, dvo::core::RgbdImagePyramid &frame, KeyframeVector &candidates) {
+    static const char *where = "AppearanceConstraintSearch::findForFrame";
+    sync(all, where);
+    frame.build((size_t)std::max(options_.level, 0) + 1);
+    const dvo_amd_pyramid *handle = frame.handle();
+    std::vector<int> found((size_t)query_.k, -1);
+    int count = 0;
+    scores_.assign((size_t)query_.k, 0.0);
+    dvo::detail::check(dvo_amd_place_query_frames(index_, 1, &handle, &query_, found.data(), scores_.data(), &count), where);
+    take(all, found, count, candidates);
+  }
+
+ private:
+  void sync(const KeyframeVector &all, const char *where) {
+    if (query_.k < 1 || query_.k > DVO_AMD_PLACE_MAX_K) throw dvo::DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+    if (!index_) dvo::detail::check(dvo_amd_place_index_create(device_, &options_, &index_), where);
+    int have = 0;
+    dvo::detail::check(dvo_amd_place_index_info(index_, &have, nullptr, nullptr, nullptr), where);
+    if ((size_t)have > all.size()) throw dvo::DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+    std::vector<const dvo_amd_pyramid *> fresh;
+    for (size_t i = (size_t)have; i < all.size(); ++i) {
+      if (!all[i]->image()) throw dvo::DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+      all[i]->image()->build((size_t)std::max(options_.level, 0) + 1);
+      fresh.push_back(all[i]->image()->handle());
+    }
+    if (!fresh.empty()) dvo::detail::check(dvo_amd_place_index_add(index_, (int)fresh.size(), fresh.data(), nullptr), where);
+  }
+
+  void take(const KeyframeVector &all, const std::vector<int> &found, int count, KeyframeVector &candidates) {
+    scores_.resize((size_t)count);
+    for (int i = 0; i < count; ++i) candidates.push_back(all[(size_t)found[(size_t)i]]);
+  }
+
+  dvo_amd_place_index *index_;
+  int device_;
+  dvo_amd_place_options options_;
+  dvo_amd_place_query_options query_;
+  std::vector<double> scores_;
 };
 
 namespace constraints {

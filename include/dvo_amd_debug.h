@@ -240,6 +240,11 @@ int dvo_amd_debug_mask_ops_timing(int device, int enable, double *last_ms);
  * bracketed by two events on the device's internal stream (the launch alone: not the tables' upload, not the pyramids' build);
  * *last_ms (may be NULL) receives the device time of the most recent bracketed launch */
 int dvo_amd_debug_fuse_timing(int device, int enable, double *last_ms);
+/* with enable != 0 the kernel launches of every later dvo_amd_place_scores, dvo_amd_place_query and dvo_amd_place_query_frames on
+ * `device` are bracketed by two events on the device's internal stream, from before the first dot-product launch to behind the last
+ * launch of the call (not the uploads, not a frame's descriptor, not the copies back); *last_ms (may be NULL) receives the device
+ * time of the most recent bracketed call */
+int dvo_amd_debug_place_timing(int device, int enable, double *last_ms);
 
 #ifdef __cplusplus
 }
