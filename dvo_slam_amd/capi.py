@@ -60,6 +60,7 @@ EXPORTS = [
     "dvo_amd_default_place_options", "dvo_amd_default_place_query_options", "dvo_amd_place_index_create", "dvo_amd_place_index_destroy",
     "dvo_amd_place_index_add", "dvo_amd_place_index_info", "dvo_amd_place_index_download", "dvo_amd_place_scores", "dvo_amd_place_query",
     "dvo_amd_place_query_frames", "dvo_amd_debug_place_timing",
+    "dvo_amd_debug_residuals_masked", "dvo_amd_debug_iteration_masked", "dvo_amd_debug_weights_masked",
 ]
 
 
@@ -306,6 +307,9 @@ def lib():
     L.dvo_amd_debug_hw_queue.argtypes = [vp, C.POINTER(C.c_int)]
     L.dvo_amd_debug_level_geometry.argtypes = [vp, vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.dvo_amd_debug_weights.argtypes = [vp, vp, vp, C.c_int, fp, fp, fp, C.POINTER(CQ7Probe)]
+    L.dvo_amd_debug_residuals_masked.argtypes = [vp, vp, vp, C.c_int, fp, vp, fp, C.POINTER(C.c_int)]
+    L.dvo_amd_debug_iteration_masked.argtypes = [vp, vp, vp, C.c_int, fp, fp, fp, vp, C.POINTER(CIterationProbe)]
+    L.dvo_amd_debug_weights_masked.argtypes = [vp, vp, vp, C.c_int, fp, fp, vp, fp, C.POINTER(CQ7Probe)]
     L.dvo_amd_kernel_timing.argtypes = [vp, C.c_int, dp, C.POINTER(C.c_longlong), C.c_int]
     L.dvo_amd_bench_residual_pass.argtypes = [vp, vp, vp, C.c_int, fp, C.c_int, C.c_int, C.c_int, dp, dp,
                                               C.POINTER(C.c_int)]
@@ -1605,29 +1609,35 @@ class DenseTracker:
         _check(lib().dvo_amd_match_sharded(self._h, reference._h, current._h, T0, C.byref(res[0])), "dvo_amd_match_sharded")
         return Result(res[0], its[0])
 
-    def residuals(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, level: int, T):
-        """computeResidualsAndValidFlagsSse: (residuals[h, w, 2] with NaN = invalid, n_valid)."""
+    def residuals(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, level: int, T, mask: "SelectionMask | None" = None):
+        """computeResidualsAndValidFlagsSse: (residuals[h, w, 2] with NaN = invalid, n_valid).  mask (test entry,
+        dvo_amd_debug.h): the pass walks the points the mask leaves of the selection."""
         w, h, _ = reference.level_info(level)
         out = np.empty((h, w, 2), np.float32)
         Tf = np.ascontiguousarray(np.asarray(T, dtype=np.float64).astype(np.float32).T)
         n = C.c_int()
-        _check(lib().dvo_amd_residuals(self._h, reference._h, current._h, level, _fp(Tf), _fp(out), C.byref(n)),
-               "dvo_amd_residuals")
+        if mask is None:
+            _check(lib().dvo_amd_residuals(self._h, reference._h, current._h, level, _fp(Tf), _fp(out), C.byref(n)),
+                   "dvo_amd_residuals")
+        else:
+            _check(lib().dvo_amd_debug_residuals_masked(self._h, reference._h, current._h, level, _fp(Tf), mask._h, _fp(out),
+                                                        C.byref(n)), "dvo_amd_debug_residuals_masked")
         return out, n.value
 
     def iteration_probe(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, level: int, T, precision_in=None,
-                        precision_eval=None):
+                        precision_eval=None, mask: "SelectionMask | None" = None):
         """One Gauss-Newton iteration body at the fixed pose T (dense_tracking.cpp:271-347 minus accept test and solve)
         through the kernels and host arithmetic match() uses: unit weights when precision_in is None, else t-distribution
         weights from the 2x2 precision_in.  precision_eval: evaluate A / b / ll with this 2x2 precision instead of the computed
-        one.  Returns dict(n, scale, precision, ll, A, b, moments, scale_sums)."""
+        one.  mask: over the points the mask leaves of the selection.  Returns dict(n, scale, precision, ll, A, b, moments,
+        scale_sums)."""
         Tf = np.ascontiguousarray(np.asarray(T, dtype=np.float64).astype(np.float32).T)
         pin = None if precision_in is None else np.ascontiguousarray(np.asarray(precision_in, np.float32).T).ravel()
         pev = None if precision_eval is None else np.ascontiguousarray(np.asarray(precision_eval, np.float32).T).ravel()
         pr = CIterationProbe()
-        _check(lib().dvo_amd_debug_iteration(self._h, reference._h, current._h, level, _fp(Tf),
-                                             None if pin is None else _fp(pin), None if pev is None else _fp(pev),
-                                             C.byref(pr)), "dvo_amd_debug_iteration")
+        _check(lib().dvo_amd_debug_iteration_masked(self._h, reference._h, current._h, level, _fp(Tf),
+                                                    None if pin is None else _fp(pin), None if pev is None else _fp(pev),
+                                                    None if mask is None else mask._h, C.byref(pr)), "dvo_amd_debug_iteration")
         return {"n": pr.valid_constraints, "scale": np.array(pr.scale[:], np.float32).reshape(2, 2).T.copy(),
                 "precision": np.array(pr.precision[:], np.float32).reshape(2, 2).T.copy(), "ll": float(pr.loglik),
                 "A": np.array(pr.information[:]).reshape(6, 6).T.copy(), "b": np.array(pr.rhs[:]),
@@ -1647,7 +1657,8 @@ class DenseTracker:
                "dvo_amd_debug_level_geometry")
         return steps.value, blocks.value, points.value
 
-    def weights_probe(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, level: int, T, precision_in):
+    def weights_probe(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, level: int, T, precision_in,
+                      mask: "SelectionMask | None" = None):
         """(test entry, dvo_amd_debug.h; host-rcpps mode only) the t-distribution weights of one residual pass at T under the 2x2
         precision_in as the product kernel formed them -- [h, w], NaN where the pixel is no constraint -- and what k_q7_tail did
         about the last V mod 4 of them (Q7): dict(n_tail, n, n_counted, recomputed_equal, pixel, w_table, w_exact, scale_sums_delta,
@@ -1657,8 +1668,8 @@ class DenseTracker:
         Tf = np.ascontiguousarray(np.asarray(T, dtype=np.float64).astype(np.float32).T)
         pin = np.ascontiguousarray(np.asarray(precision_in, np.float32).T).ravel()
         q = CQ7Probe()
-        _check(lib().dvo_amd_debug_weights(self._h, reference._h, current._h, level, _fp(Tf), _fp(pin), _fp(out), C.byref(q)),
-               "dvo_amd_debug_weights")
+        _check(lib().dvo_amd_debug_weights_masked(self._h, reference._h, current._h, level, _fp(Tf), _fp(pin),
+                                                  None if mask is None else mask._h, _fp(out), C.byref(q)), "dvo_amd_debug_weights")
         return out, {"n_tail": q.n_tail, "n": q.valid_constraints, "n_counted": q.valid_counted,
                      "recomputed_equal": bool(q.recomputed_equal), "pixel": list(q.pixel[:]),
                      "w_table": np.array(q.weight_table[:], np.float32), "w_exact": np.array(q.weight_exact[:], np.float32),

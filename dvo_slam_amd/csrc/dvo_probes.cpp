@@ -216,19 +216,23 @@ int check_level_pair(const dvo_amd_context *ctx, const dvo_amd_pyramid *referenc
 }  // namespace host
 }  // namespace dvo_amd
 
-extern "C" {
+// The bodies of dvo_amd_residuals, dvo_amd_debug_iteration and dvo_amd_debug_weights, shared with their _masked siblings
+// (include/dvo_amd_debug.h): `mask` restricts the selection the pass walks, null = the unmasked selection.
+namespace {
 
-int dvo_amd_residuals(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
-                      float *residuals, int *n_valid) {
+int residuals_entry(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
+                    const dvo_amd_mask *mask, float *residuals, int *n_valid) {
   if (!ctx || !reference || !current || !T || level < 0) return DVO_AMD_ERR_INVALID_ARGUMENT;
   int rc = check_level_pair(ctx, reference, current, level);
+  if (rc) return rc;
+  rc = mask_fits("dvo_amd_debug_residuals_masked", reference, mask);
   if (rc) return rc;
   rc = queue_must_be_idle(ctx, "dvo_amd_residuals / dvo_amd_error_image");
   if (rc) return rc;
   const LevelData &R = reference->lv[level];
   HIP_TRY(hipSetDevice(ctx->device));
   const Selection *sel = nullptr;
-  rc = pyramid_selection(reference, ctx->cfg.intensity_derivative_threshold, ctx->cfg.depth_derivative_threshold, &sel);
+  rc = pyramid_selection(reference, ctx->cfg.intensity_derivative_threshold, ctx->cfg.depth_derivative_threshold, mask, &sel);
   if (rc) return rc;
   rc = ensure_slots(ctx, 1, R.n_pad);
   if (rc) return rc;
@@ -245,18 +249,20 @@ int dvo_amd_residuals(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_
   return DVO_AMD_OK;
 }
 
-int dvo_amd_debug_iteration(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level,
-                            const float *T, const float *precision_in, const float *precision_eval,
-                            dvo_amd_iteration_probe *out) {
+int iteration_entry(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
+                    const float *precision_in, const float *precision_eval, const dvo_amd_mask *mask,
+                    dvo_amd_iteration_probe *out) {
   if (!ctx || !reference || !current || !T || !out || level < 0) return DVO_AMD_ERR_INVALID_ARGUMENT;
   int rc = check_level_pair(ctx, reference, current, level);
+  if (rc) return rc;
+  rc = mask_fits("dvo_amd_debug_iteration_masked", reference, mask);
   if (rc) return rc;
   rc = queue_must_be_idle(ctx, "dvo_amd_debug_iteration");
   if (rc) return rc;
   const LevelData &R = reference->lv[level];
   HIP_TRY(hipSetDevice(ctx->device));
   const Selection *sel = nullptr;
-  rc = pyramid_selection(reference, ctx->cfg.intensity_derivative_threshold, ctx->cfg.depth_derivative_threshold, &sel);
+  rc = pyramid_selection(reference, ctx->cfg.intensity_derivative_threshold, ctx->cfg.depth_derivative_threshold, mask, &sel);
   if (rc) return rc;
   rc = ensure_slots(ctx, 1, R.n_pad);
   if (rc) return rc;
@@ -299,8 +305,8 @@ int dvo_amd_debug_iteration(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dv
   return DVO_AMD_OK;
 }
 
-int dvo_amd_debug_weights(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
-                          const float *precision_in, float *weights, dvo_amd_q7_probe *tail) {
+int weights_entry(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
+                  const float *precision_in, const dvo_amd_mask *mask, float *weights, dvo_amd_q7_probe *tail) {
   if (!ctx || !reference || !current || !T || !precision_in || !weights || !tail || level < 0) return DVO_AMD_ERR_INVALID_ARGUMENT;
   if (!ctx->rcp.table) {
     g_last_error = "dvo_amd_debug_weights: only the host-rcpps kernels can store their weights (dvo_amd_set_reciprocal_mode)";
@@ -308,12 +314,14 @@ int dvo_amd_debug_weights(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_
   }
   int rc = check_level_pair(ctx, reference, current, level);
   if (rc) return rc;
+  rc = mask_fits("dvo_amd_debug_weights_masked", reference, mask);
+  if (rc) return rc;
   rc = queue_must_be_idle(ctx, "dvo_amd_debug_weights");
   if (rc) return rc;
   const LevelData &R = reference->lv[level];
   HIP_TRY(hipSetDevice(ctx->device));
   const Selection *sel = nullptr;
-  rc = pyramid_selection(reference, ctx->cfg.intensity_derivative_threshold, ctx->cfg.depth_derivative_threshold, &sel);
+  rc = pyramid_selection(reference, ctx->cfg.intensity_derivative_threshold, ctx->cfg.depth_derivative_threshold, mask, &sel);
   if (rc) return rc;
   rc = ensure_slots(ctx, 1, R.n_pad);
   if (rc) return rc;
@@ -347,6 +355,43 @@ int dvo_amd_debug_weights(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_
   for (int i = 0; i < kNumAcc; ++i) tail->moments_delta[i] = q.acc[i];
   tail->valid_counted = q.valid;
   return DVO_AMD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dvo_amd_residuals(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
+                      float *residuals, int *n_valid) {
+  return residuals_entry(ctx, reference, current, level, T, nullptr, residuals, n_valid);
+}
+
+int dvo_amd_debug_residuals_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
+                             const dvo_amd_mask *mask, float *residuals, int *n_valid) {
+  return residuals_entry(ctx, reference, current, level, T, mask, residuals, n_valid);
+}
+
+int dvo_amd_debug_iteration(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level,
+                            const float *T, const float *precision_in, const float *precision_eval,
+                            dvo_amd_iteration_probe *out) {
+  return iteration_entry(ctx, reference, current, level, T, precision_in, precision_eval, nullptr, out);
+}
+
+int dvo_amd_debug_iteration_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level,
+                                   const float *T, const float *precision_in, const float *precision_eval,
+                                   const dvo_amd_mask *mask, dvo_amd_iteration_probe *out) {
+  return iteration_entry(ctx, reference, current, level, T, precision_in, precision_eval, mask, out);
+}
+
+int dvo_amd_debug_weights(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
+                          const float *precision_in, float *weights, dvo_amd_q7_probe *tail) {
+  return weights_entry(ctx, reference, current, level, T, precision_in, nullptr, weights, tail);
+}
+
+int dvo_amd_debug_weights_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level,
+                                 const float *T, const float *precision_in, const dvo_amd_mask *mask, float *weights,
+                                 dvo_amd_q7_probe *tail) {
+  return weights_entry(ctx, reference, current, level, T, precision_in, mask, weights, tail);
 }
 
 int dvo_amd_debug_level_geometry(dvo_amd_context *ctx, dvo_amd_pyramid *reference, int level, int *steps, int *blocks, int *points) {

@@ -98,6 +98,22 @@ typedef struct {
 int dvo_amd_debug_weights(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
                           const float *precision_in, float *weights, dvo_amd_q7_probe *tail);
 
+/* (test entries) dvo_amd_residuals, dvo_amd_debug_iteration and dvo_amd_debug_weights over a MASKED selection: the points the pass
+ * walks are those `mask` leaves of the selection of the context's thresholds, as for dvo_amd_match_masked (the same rules: the
+ * mask's level-0 size and level count must fit the reference pyramid, DVO_AMD_ERR_INVALID_ARGUMENT / _DEVICE_MISMATCH otherwise; a
+ * pyramid caches at most eight masked selections).  Everything else is the unmasked entry's body, shared, and a null mask IS the
+ * unmasked entry.  They exist so that the parity tests can hold the order-dependent parts of the pass -- valid ranks carried across
+ * wave segments, the Q5 parity stitch, the Q6 cut, the Q7 tail -- to their CPU checker on sparse selections, whose segments hold
+ * few, one or no valid point (tests/test_sparse_passes.py). */
+int dvo_amd_debug_residuals_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level, const float *T,
+                             const dvo_amd_mask *mask, float *residuals, int *n_valid);
+int dvo_amd_debug_iteration_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level,
+                                   const float *T, const float *precision_in, const float *precision_eval,
+                                   const dvo_amd_mask *mask, dvo_amd_iteration_probe *out);
+int dvo_amd_debug_weights_masked(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_pyramid *current, int level,
+                                 const float *T, const float *precision_in, const dvo_amd_mask *mask, float *weights,
+                                 dvo_amd_q7_probe *tail);
+
 /* Diagnostic: the hardware queue the context's main stream runs on, asked of the GPU by a one-wave kernel on that stream (HW_ID:
  * pipe << 3 | queue).  The runtime maps streams onto its four hardware queues and a hardware queue runs one kernel at a time, so
  * how the trackers of a GPU are spread over them decides up to a third of a batch's throughput

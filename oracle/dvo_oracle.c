@@ -43,6 +43,7 @@ typedef struct {
   int n_sel;
   int sel_ok;
   float sel_ti, sel_td;
+  unsigned char *keep; /* test instrumentation (orc_pyramid_set_keep): w*h bytes or NULL */
 } orc_level;
 
 struct orc_pyramid {
@@ -146,6 +147,7 @@ static void level_finish(orc_level *L) {
   L->sel_idx = NULL;
   L->sel_ok = 0;
   L->n_sel = 0;
+  L->keep = NULL;
 }
 
 orc_pyramid *orc_pyramid_create(const float *intensity, const float *depth, int width, int height, float fx,
@@ -198,6 +200,7 @@ void orc_pyramid_destroy(orc_pyramid *p) {
     free(L->cloud);
     free(L->sel);
     free(L->sel_idx);
+    free(L->keep);
   }
   free(p);
 }
@@ -220,6 +223,7 @@ const float *orc_level_plane(orc_pyramid *p, int level, int plane) { return p->l
 static void level_select(orc_level *L, float ti, float td) {
   if (L->sel_ok && L->sel_ti == ti && L->sel_td == td) return;
   const size_t n = (size_t)L->w * L->h;
+  const unsigned char *keep = L->keep; /* test instrumentation: NULL in every reference path */
   if (!L->sel) {
     L->sel = (orc_record *)xalloc(n * sizeof(orc_record));
     L->sel_idx = (int *)xalloc(n * sizeof(int));
@@ -231,6 +235,7 @@ static void level_select(orc_level *L, float ti, float td) {
     const float z = c[2], idx = a[2], idy = a[3], zdx = a[4], zdy = a[5];
     int ok = z == z && zdx == zdx && zdy == zdy &&
              (fabsf(idx) > ti || fabsf(idy) > ti || fabsf(zdx) > td || fabsf(zdy) > td);
+    if (ok && keep && !keep[i]) ok = 0;
     if (ok) {
       memcpy(L->sel[cnt].p, c, 4 * sizeof(float));
       memcpy(L->sel[cnt].e, a, 8 * sizeof(float));
@@ -242,6 +247,20 @@ static void level_select(orc_level *L, float ti, float td) {
   L->sel_ok = 1;
   L->sel_ti = ti;
   L->sel_td = td;
+}
+
+/* TEST INSTRUMENTATION (dvo_oracle.h): a keep plane restricts the selection of one level; the cached selection is dropped */
+void orc_pyramid_set_keep(orc_pyramid *p, int level, const unsigned char *keep) {
+  if (!p || level < 0 || level >= p->n_levels) return;
+  orc_level *L = &p->lv[level];
+  const size_t n = (size_t)L->w * L->h;
+  free(L->keep);
+  L->keep = NULL;
+  if (keep) {
+    L->keep = (unsigned char *)xalloc(n);
+    memcpy(L->keep, keep, n);
+  }
+  L->sel_ok = 0;
 }
 
 int orc_select(orc_pyramid *p, int level, float ti, float td, const float **records) {

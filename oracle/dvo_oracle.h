@@ -135,6 +135,15 @@ int orc_select(orc_pyramid *p, int level, float ti, float td, const float **reco
 /* pixel index (y*w+x) of every selected record, same order */
 const int *orc_select_index(orc_pyramid *p, int level, float ti, float td);
 
+/* TEST INSTRUMENTATION (not a reference entry, like sum_mode and orc_match_from): a keep plane on one level of a pyramid.
+ * While a plane is set, the level's selection keeps a pixel iff the reference predicate (point_selection.h:63-66) holds AND
+ * keep[y*w+x] != 0 -- the selection a masked alignment of the HIP path walks.  Everything behind the selection follows by
+ * itself: orc_select, orc_select_index, orc_compute_residuals, orc_iteration, orc_match, orc_match_from; the Q3 rule (an odd
+ * trailing point is counted but never walked) applies to the kept points.  keep: w*h bytes of that level, copied; NULL removes
+ * the plane.  Setting or removing a plane drops the level's cached selection.  With no plane set (every reference path, and
+ * bench.py's CPU baseline) the selection is what it always was. */
+void orc_pyramid_set_keep(orc_pyramid *p, int level, const unsigned char *keep);
+
 /*
  * computeResidualsSse (dense_tracking_impl.cpp:133-393) on one level for the float transform T (column-major 4x4).
  * out_points_error: n x 12 floats, out_residuals: n x 2 floats, out_valid: one byte per processed selected point

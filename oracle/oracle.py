@@ -138,6 +138,8 @@ def lib():
         L.orc_level_intrinsics.argtypes = [C.c_void_p, C.c_int, fp]
         L.orc_level_plane.restype = fp
         L.orc_level_plane.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.orc_pyramid_set_keep.restype = None
+        L.orc_pyramid_set_keep.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_ubyte)]
         L.orc_select.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.POINTER(fp)]
         L.orc_select_index.restype = C.POINTER(C.c_int)
         L.orc_select_index.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float]
@@ -211,6 +213,17 @@ class Pyramid:
         w, h = self.size(level)
         p = lib().orc_level_plane(self.h, level, plane)
         return np.ctypeslib.as_array(p, shape=(h, w)).copy()
+
+    def set_keep(self, level, plane):
+        """orc_pyramid_set_keep (test instrumentation): the level's selection keeps only pixels where plane (h x w) is non-zero;
+        None removes the plane.  The level's cached selection is dropped either way."""
+        if plane is None:
+            lib().orc_pyramid_set_keep(self.h, level, None)
+            return
+        w, h = self.size(level)
+        keep = np.ascontiguousarray(np.asarray(plane) != 0, dtype=np.uint8)
+        assert keep.shape == (h, w), (keep.shape, (h, w))
+        lib().orc_pyramid_set_keep(self.h, level, keep.ctypes.data_as(C.POINTER(C.c_ubyte)))
 
     def select(self, level, ti=0.0, td=0.0):
         rec = C.POINTER(C.c_float)()

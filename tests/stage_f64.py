@@ -3,9 +3,17 @@ import numpy as np
 
 
 def f64_iteration(orc, orr, occ, level, T, prec_in, P_eval, ti=0.0, td=0.0, rcp_mode=None):
+    """(n, cov, A, b, cs, ll) of f64_iteration_terms"""
+    return f64_iteration_terms(orc, orr, occ, level, T, prec_in, P_eval, ti, td, rcp_mode)[:6]
+
+
+def f64_iteration_terms(orc, orr, occ, level, T, prec_in, P_eval, ti=0.0, td=0.0, rcp_mode=None):
     """A third, independent restatement of one iteration body (numpy, float64 sums) on the oracle's bit-exact residual
     records: what the sums would be without any accumulation error.  Q5 pairing and Q6 cut included.  Returns
-    (n, cov 2x2, A 6x6 under P_eval, b 6 under P_eval, Cauchy-Schwarz scale of b, ll under P_eval)."""
+    (n, cov 2x2, A 6x6 under P_eval, b 6 under P_eval, Cauchy-Schwarz scale of b, ll under P_eval, ll_abs): ll_abs is the sum
+    of the absolute values of ll's terms -- the determinant term and the Q6 sum --, the normaliser of a likelihood whose two
+    parts cancel (a sparse pass: few terms, or none at all below fifty constraints).  The reference selection follows the oracle
+    pyramid's keep plane by itself (Pyramid.set_keep)."""
     # ti, td: the point-selection thresholds; rcp_mode: the reciprocal the residual records are formed with (default: exact)
     pe, res, _ = orc.compute_residuals(orr, occ, level, T, orc.RCP_EXACT if rcp_mode is None else rcp_mode, ti, td)
     r = res.astype(np.float64)
@@ -43,6 +51,7 @@ def f64_iteration(orc, orr, occ, level, T, prec_in, P_eval, ti=0.0, td=0.0, rcp_
     b = -np.einsum("n,nai,ab,nb->i", wg, J, P, r)
     cs = np.sqrt(np.diag(A) * np.einsum("n,na,ab,nb->", wg, r, P, r))  # |b_k| <= sqrt(A_kk * sum w r^T P r)
     m = 50 * (n // 50)  # Q6
-    ll = 0.5 * n * np.log(np.float32(P[0, 0] * P[1, 1] - P[1, 0] * P[0, 1])) \
-        - 3.5 * np.log1p(0.2 * np.einsum("ni,ij,nj->n", r[:m], P, r[:m])).sum()
-    return n, cov, A, b, cs, ll
+    ll_det = 0.5 * n * np.log(np.float32(P[0, 0] * P[1, 1] - P[1, 0] * P[0, 1]))
+    ll_sum = 3.5 * np.log1p(0.2 * np.einsum("ni,ij,nj->n", r[:m], P, r[:m])).sum()
+    ll = ll_det - ll_sum
+    return n, cov, A, b, cs, ll, abs(ll_det) + abs(ll_sum)

@@ -167,6 +167,8 @@ import fork_criterion  # noqa: E402  (tests/fork_criterion.py)
 #    reference's own error bars.
 F64_SCALE_RTOL, F64_A_RTOL, F64_B_CS, F64_LL_RTOL = 1e-6, 1e-6, 5e-7, 1e-6  # measured on MI355X: 1.2e-7, 1.2e-7, 5.3e-8, 1.3e-7
 REF_SCALE_RTOL, REF_A_RTOL, REF_B_CS, REF_LL_RTOL = 1e-3, 1e-3, 3e-5, 2e-6    # measured: 1.9e-4, 2.0e-4, 8.6e-6, 0
+# the same bars on sparse and gappy passes (tests/test_sparse_passes.py: 0 .. 1 025 points, empty segments and blocks), measured on
+# MI355X: F64 1.4e-7, 2.1e-7, 1.2e-7, 1.4e-7; REF 6.6e-7 (precision 5.3e-7), 1.0e-6, 5.5e-7, 0 -- few terms, little summation noise
 
 
 @pytest.mark.parametrize("case", ["640x480 levels 3..0", "640x480 swapped", "336x250 levels 2..0", "1280x960 levels 4..0"])
@@ -292,14 +294,16 @@ def _oracle_levels(ro):
 
 
 def _check_match(capi, orc, synth, g_ref, g_cur, o_ref, o_cur, cfg_kw, T_init=None, tol=POSE_TOL, paths=None, label=None,
-                 count_slack=None, increment_band=0.0):
+                 count_slack=None, increment_band=0.0, mask=None):
+    # mask: a capi.SelectionMask of the GPU's match; o_ref then carries the same restriction as its keep plane (Pyramid.set_keep),
+    # which every oracle entry used below follows by itself
     import inspect
 
     _PATHS = paths if paths is not None else globals()["_PATHS"]  # (the sensor-regime suite keeps its own book)
     label = label or (inspect.stack()[1].function + repr(sorted(cfg_kw.items())))
     gcfg = capi.Config(**cfg_kw)
     trk = capi.DenseTracker(gcfg)
-    rg = trk.match(g_ref, g_cur, T_init)
+    rg = trk.match(g_ref, g_cur, T_init, mask=mask)
     ocfg = fork_criterion.oracle_config_of(orc, gcfg)
     ro = orc.match(ocfg, o_ref, o_cur, T_init)
     err = synth.pose_error(ro["T"], rg.Transformation)

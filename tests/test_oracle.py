@@ -658,3 +658,96 @@ def test_q7_tail_weights_are_below_every_sums_rounding(orc, synth, capsys):
     with capsys.disabled():
         print(f"\n[Q7 tail] all-table weights vs the reference's exact-division tail: a weighted sum of the pass moves by at most {worst:.1e} relative")
     assert worst < 1e-7
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the keep plane (test instrumentation, dvo_oracle.h: orc_pyramid_set_keep): equality only
+# ---------------------------------------------------------------------------------------------------------------------
+def _same_bytes(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def _same_match(a, b):
+    """two orc.match results byte for byte, iteration statistics included"""
+    if not (_same_bytes(a["T"], b["T"]) and _same_bytes(a["information"], b["information"]) and a["is_nan"] == b["is_nan"]
+            and np.float64(a["loglik"]).tobytes() == np.float64(b["loglik"]).tobytes() and len(a["levels"]) == len(b["levels"])):
+        return False
+    for La, Lb in zip(a["levels"], b["levels"]):
+        if any(La[k] != Lb[k] for k in ("id", "max_valid_pixels", "valid_pixels", "termination")) or len(La["iterations"]) != len(Lb["iterations"]):
+            return False
+        for ia, ib in zip(La["iterations"], Lb["iterations"]):
+            if sorted(ia) != sorted(ib) or not all(_same_bytes(np.asarray(ia[k]), np.asarray(ib[k])) for k in ia):
+                return False
+    return True
+
+
+def _keep_pair(orc, small_pair, levels=3):
+    (Ir, Zr), (Ic, Zc), Tgt, K = small_pair
+    mk = lambda: orc.Pyramid(Ir, Zr, K, levels)  # noqa: E731
+    return mk, orc.Pyramid(Ic, Zc, K, levels), Tgt
+
+
+def test_an_all_ones_keep_plane_changes_nothing(orc, small_pair):
+    mk, cur, _ = _keep_pair(orc, small_pair)
+    plain, kept = mk(), mk()
+    for level in range(3):
+        w, h = kept.size(level)
+        kept.set_keep(level, np.ones((h, w), np.uint8))
+    for level in range(3):
+        (ra, ia), (rb, ib) = plain.select(level), kept.select(level)
+        assert _same_bytes(ra, rb) and _same_bytes(ia, ib) and len(ia) > 0
+    cfg = orc.default_config(first_level=2, last_level=0, rcp_mode=orc.RCP_EXACT)
+    assert _same_match(orc.match(cfg, plain, cur), orc.match(cfg, kept, cur))
+
+
+def test_a_keep_plane_that_restates_a_threshold_pair_is_that_threshold_pair(orc, synth, small_pair):
+    """the predicate of thresholds (2.5, 0.01) (point_selection.h:63-66) restated in numpy from the planes and handed over as keep
+    planes, with thresholds (-1, -1) -- every finite point passes the gradient test -- gives what (2.5, 0.01) give without a plane"""
+    mk, cur, Tgt = _keep_pair(orc, small_pair)
+    plain, kept = mk(), mk()
+    ti, td = 2.5, 0.01
+    for level in range(3):
+        Ix, Iy, Zx, Zy = (np.abs(kept.plane(level, k)) for k in (2, 3, 4, 5))
+        with np.errstate(invalid="ignore"):
+            kept.set_keep(level, (Ix > f32(ti)) | (Iy > f32(ti)) | (Zx > f32(td)) | (Zy > f32(td)))
+    poses = (np.eye(4), synth.se3_exp([0.05, -0.08, 0.1, 0.03, -0.02, 0.04]))
+    for level in range(3):
+        (ra, ia), (rb, ib) = plain.select(level, ti, td), kept.select(level, -1.0, -1.0)
+        assert _same_bytes(ra, rb) and _same_bytes(ia, ib) and 0 < len(ia) < len(mk().select(level)[1])
+        for T in poses:
+            a = orc.compute_residuals(plain, cur, level, T, orc.RCP_EXACT, ti, td)
+            b = orc.compute_residuals(kept, cur, level, T, orc.RCP_EXACT, -1.0, -1.0)
+            assert all(_same_bytes(x, y) for x, y in zip(a, b)) and len(a[1]) > 0
+    kw = dict(first_level=2, last_level=0, rcp_mode=orc.RCP_EXACT)
+    a = orc.match(orc.default_config(intensity_derivative_threshold=ti, depth_derivative_threshold=td, **kw), plain, cur)
+    b = orc.match(orc.default_config(intensity_derivative_threshold=-1.0, depth_derivative_threshold=-1.0, **kw), kept, cur)
+    assert _same_match(a, b) and sum(len(L["iterations"]) for L in a["levels"]) >= 6
+
+
+def test_a_counted_keep_plane_keeps_exactly_n_and_removing_it_restores_the_selection(orc, small_pair):
+    import counted_selection_cases
+    import sparse_pass_cases
+
+    mk, cur, _ = _keep_pair(orc, small_pair, levels=2)
+    p = mk()
+    rec0, idx0 = p.select(1)
+    selected = np.zeros(p.size(1)[0] * p.size(1)[1], np.uint8)
+    selected[idx0] = 1
+    selected = selected.reshape(p.size(1)[1], p.size(1)[0])
+    for n in sparse_pass_cases.COUNTS:
+        plane = counted_selection_cases.count_mask_planes(selected, n)[1]
+        p.set_keep(1, plane)
+        rec, idx = p.select(1)
+        assert len(idx) == len(rec) == n
+        assert np.array_equal(idx, np.flatnonzero(plane.ravel()))  # scan order
+        assert _same_bytes(rec, rec0[np.isin(idx0, idx)])
+        # Q3: an odd trailing point is counted but never walked -- 1 walks nothing, 65 walks 64
+        _, _, valid = orc.compute_residuals(p, cur, 1, np.eye(4), orc.RCP_EXACT)
+        assert len(valid) == n - n % 2
+    assert {1, 65} <= set(sparse_pass_cases.COUNTS)
+    p.set_keep(1, None)
+    rec, idx = p.select(1)
+    assert _same_bytes(rec, rec0) and _same_bytes(idx, idx0)
+    # the other level never had a plane
+    assert _same_bytes(p.select(0)[1], mk().select(0)[1])
