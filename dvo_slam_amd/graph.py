@@ -238,22 +238,25 @@ class PoseGraph:
             ce[i].information[:] = list(O.T.reshape(-1))
         return live, nv, ne, P, fixed, ce
 
-    def debug_system(self, tracker: "capi.DenseTracker", robust_delta: float = 5.0):
+    def debug_system(self, tracker: "capi.DenseTracker", robust_delta: float = 5.0, with_H: bool = True):
         """(diagnostic) the first linear system of optimize() on the current poses (dvo_amd_debug_graph_system):
-        (H n x n, b, x of the undamped solve or None when a pivot failed, F, index of the failed pivot or -1)"""
+        (H n x n, b, x of the undamped solve or None when a pivot failed, F, index of the failed pivot or -1).  with_H=False
+        passes NULL for H (the entry's outputs are optional) and returns None in its place: at the dense cap H is 302 MB."""
         L = _lib()
         live, nv, ne, P, fixed, ce = self._pack()
         active = {v for k in live for v in self.edges[k][:2]}
         n = 6 * sum(1 for v in range(nv) if v in active and not self.fixed[v])
-        H, b, x = np.zeros((max(n, 1), max(n, 1))), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        H = np.zeros((max(n, 1), max(n, 1))) if with_H else None
+        b, x = np.zeros(max(n, 1)), np.zeros(max(n, 1))
         F, nf, fp = C.c_double(), C.c_int(), C.c_int()
         dp = C.POINTER(C.c_double)
         capi._check(L.dvo_amd_debug_graph_system(tracker._h, nv, P.ctypes.data_as(dp), fixed.ctypes.data_as(C.POINTER(C.c_int)),
-                                                 ne, ce, float(robust_delta), H.ctypes.data_as(dp), b.ctypes.data_as(dp),
-                                                 x.ctypes.data_as(dp), C.byref(F), C.byref(nf), C.byref(fp)),
+                                                 ne, ce, float(robust_delta), H.ctypes.data_as(dp) if with_H else None,
+                                                 b.ctypes.data_as(dp), x.ctypes.data_as(dp), C.byref(F), C.byref(nf),
+                                                 C.byref(fp)),
                     "dvo_amd_debug_graph_system")
         assert 6 * nf.value == n
-        return H[:n, :n], b[:n], (x[:n] if fp.value < 0 else None), F.value, fp.value
+        return (H[:n, :n] if with_H else None), b[:n], (x[:n] if fp.value < 0 else None), F.value, fp.value
 
     def debug_system_sparse(self, tracker: "capi.DenseTracker", robust_delta: float = 5.0):
         """(diagnostic) the first linear system of optimize(solver="sparse") (dvo_amd_debug_graph_system_sparse):
