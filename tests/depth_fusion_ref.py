@@ -39,7 +39,9 @@ def sigma(z):
     return F(0.0012) + F(0.0019) * (s * s)
 
 
-def fuse_ref(key, frames, Ts, options=None):
+def fuse_ref(key, frames, Ts, options=None, info=None):
+    """info: None, or a list that receives one dict per frame: 'cls' (int [h, w]: -1 no depth, else the index into FRAME_COUNTS of
+    the pixel's outcome), 'fused' (bool), 'qz', 'px', 'py' (the projection before the floor), 'd', 'tol', 'c' and 'M'"""
     o = dict(DEFAULTS, **(options or {}))
     assert len(frames) == len(Ts) <= MAX_FRAMES and o["sample"] in (BILINEAR, NEAREST)
     near, sig, min_cos = F(o["near_z"]), F(o["depth_sigmas"]), F(o["min_cos"])
@@ -101,6 +103,11 @@ def fuse_ref(key, frames, Ts, options=None):
             assert all(v.dtype == F for v in (x, qz, px, d, tol, c, z_obs, wk_, sw, swz))
             masks = (has, behind, outside, no_depth, consistent, occluded, seen, fused)
             frame_counts.append({name: int(m.sum()) for name, m in zip(FRAME_COUNTS, masks)})
+            if info is not None:
+                cls = np.full((h, w), -1, np.int64)
+                for k in range(1, 7):
+                    cls[masks[k]] = k
+                info.append(dict(cls=cls, fused=fused.copy(), qz=qz, px=px, py=py, d=d, tol=tol, c=c, M=M))
         fusedz = swz / sw
         confirmed = has & (n_obs >= int(o["min_observations"]))
         dropped = has & ~confirmed & bool(o["drop_unconfirmed"])
