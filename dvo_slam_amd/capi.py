@@ -61,6 +61,8 @@ EXPORTS = [
     "dvo_amd_place_index_add", "dvo_amd_place_index_info", "dvo_amd_place_index_download", "dvo_amd_place_scores", "dvo_amd_place_query",
     "dvo_amd_place_query_frames", "dvo_amd_debug_place_timing",
     "dvo_amd_debug_residuals_masked", "dvo_amd_debug_iteration_masked", "dvo_amd_debug_weights_masked",
+    "dvo_amd_default_normal_options", "dvo_amd_pyramid_normals", "dvo_amd_mask_from_normals", "dvo_amd_point_cloud_normals",
+    "dvo_amd_write_pcd_normals", "dvo_amd_debug_normals_timing",
 ]
 
 
@@ -176,6 +178,19 @@ class FuseOptions(C.Structure):
     """dvo_amd_fuse_options, field for field"""
     _fields_ = [("near_z", C.c_float), ("depth_sigmas", C.c_float), ("min_cos", C.c_float), ("sample", C.c_int),
                 ("min_observations", C.c_int), ("drop_unconfirmed", C.c_int)]
+
+
+class NormalOptions(C.Structure):
+    """dvo_amd_normal_options, field for field"""
+    _fields_ = [("radius", C.c_int * MAX_LEVELS), ("depth_step_ratio", C.c_float), ("facing", C.c_int), ("toward_camera", C.c_int)]
+
+
+NORMAL_MAX_RADIUS = 8
+NORMAL_FACING_AXIS, NORMAL_FACING_RAY = 0, 1
+# dvo_amd_pyramid_normals' counts and one level of dvo_amd_mask_from_normals' counts, field for field
+NORMAL_COUNTS = ("defined", "undefined")
+NORMAL_MASK_COUNTS = ("defined", "undefined", "kept")
+NORMAL_MASK_DTYPE = np.dtype([(name, np.int64) for name in NORMAL_MASK_COUNTS])
 
 
 class PlaceOptions(C.Structure):
@@ -417,6 +432,13 @@ def lib():
     L.dvo_amd_pyramid_fuse_depth_many.argtypes = [C.c_int, C.POINTER(vp), ip, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
                                                   C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(vp)]
     L.dvo_amd_debug_fuse_timing.argtypes = [C.c_int, C.c_int, dp]
+    L.dvo_amd_default_normal_options.argtypes = [C.POINTER(NormalOptions)]
+    L.dvo_amd_default_normal_options.restype = None
+    L.dvo_amd_pyramid_normals.argtypes = [vp, C.c_int, C.POINTER(NormalOptions), fp, fp, C.POINTER(C.c_longlong)]
+    L.dvo_amd_mask_from_normals.argtypes = [vp, C.POINTER(NormalOptions), fp, C.c_int, C.POINTER(vp), C.POINTER(C.c_longlong)]
+    L.dvo_amd_point_cloud_normals.argtypes = [vp, vp, C.c_int, dp, vp, C.c_int, C.POINTER(NormalOptions), vp, fp]
+    L.dvo_amd_write_pcd_normals.argtypes = [C.c_char_p, vp, fp, C.c_longlong, C.c_int, C.c_int]
+    L.dvo_amd_debug_normals_timing.argtypes = [C.c_int, C.c_int, ip, ip, dp]
     L.dvo_amd_default_place_options.argtypes = [C.POINTER(PlaceOptions)]
     L.dvo_amd_default_place_options.restype = None
     L.dvo_amd_default_place_query_options.argtypes = [C.POINTER(PlaceQueryOptions)]
@@ -681,6 +703,37 @@ def fuse_options(**options) -> FuseOptions:
     return opt
 
 
+def normal_options(radius=None, depth_step_ratio: float | None = None, facing: int | None = None,
+                   toward_camera: int | None = None) -> NormalOptions:
+    """dvo_amd_default_normal_options (everything 0: RgbdImage::calculateNormals) with the given fields replaced.  radius: one
+    window radius per level, or one value for every level (0..NORMAL_MAX_RADIUS); depth_step_ratio: a window member is summed
+    only within this fraction of the centre's depth (0: no test); facing: NORMAL_FACING_AXIS or NORMAL_FACING_RAY"""
+    opt = NormalOptions()
+    lib().dvo_amd_default_normal_options(C.byref(opt))
+    if radius is not None:
+        opt.radius[:] = _per_level(radius, 0, "radius")
+    if depth_step_ratio is not None:
+        opt.depth_step_ratio = float(depth_step_ratio)
+    if facing is not None:
+        opt.facing = int(facing)
+    if toward_camera is not None:
+        opt.toward_camera = int(toward_camera)
+    return opt
+
+
+def _normal_options(options) -> NormalOptions:
+    return options if isinstance(options, NormalOptions) else normal_options(**(options or {}))
+
+
+def normals_timing(enable: bool = True, device: int = 0) -> dict:
+    """(instrumentation) what the most recent normals call of `device` enqueued -- kernel launches, host synchronisations -- and,
+    once switched on, the device time of its launch in ms (dvo_amd_debug_normals_timing)"""
+    launches, syncs, ms = C.c_int(), C.c_int(), C.c_double()
+    _check(lib().dvo_amd_debug_normals_timing(device, int(enable), C.byref(launches), C.byref(syncs), C.byref(ms)),
+           "dvo_amd_debug_normals_timing")
+    return {"launches": launches.value, "synchronisations": syncs.value, "ms": ms.value}
+
+
 def fuse_timing(enable: bool = True, device: int = 0) -> float:
     """(instrumentation) switches the event bracket around the fusion launch of every fuse_depth / fuse_depth_many of `device` on
     or off and returns the device time of the most recent bracketed launch in ms (dvo_amd_debug_fuse_timing)"""
@@ -926,6 +979,24 @@ class SelectionMask:
             return made
         at = np.concatenate([[0], np.cumsum(levels)]).astype(int)
         return made, [cnt[at[k]:at[k + 1]].copy() for k in range(n)]
+
+    @classmethod
+    def from_normals(cls, pyramid, min_facing, options=None, undefined_keep: bool = False, counts: bool = False):
+        """The pixels of `pyramid` whose surface faces the camera well enough (dvo_amd_mask_from_normals): kept iff the pixel's
+        normal is defined and its facing value is at least min_facing (one value per level, or one for every level); a pixel
+        without a normal is kept iff undefined_keep.  options: None, a NormalOptions or a dict of normal_options' arguments.
+        Every level in one kernel launch.  With counts=True also one NORMAL_MASK_DTYPE record per level."""
+        opt = _normal_options(options)
+        n = pyramid.levels()
+        mf = np.zeros(MAX_LEVELS, np.float32)
+        mf[:] = np.float32(min_facing) if np.ndim(min_facing) == 0 else (list(min_facing) + [0.0] * MAX_LEVELS)[:MAX_LEVELS]
+        cnt = np.zeros(MAX_LEVELS, NORMAL_MASK_DTYPE)
+        out = C.c_void_p()
+        _check(lib().dvo_amd_mask_from_normals(pyramid._h, C.byref(opt), _fp(mf), int(bool(undefined_keep)), C.byref(out),
+                                               cnt.ctypes.data_as(C.POINTER(C.c_longlong)) if counts else None),
+               "dvo_amd_mask_from_normals")
+        mask = cls._own(out, pyramid.device)
+        return (mask, cnt[:n].copy()) if counts else mask
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -1239,13 +1310,26 @@ class RgbdImagePyramid:
             result += (planes,)
         return result if len(result) > 1 else made
 
-    def point_cloud(self, pose=None, bgr=None, level: int = 0, tracker: "DenseTracker | None" = None):
+    def normals(self, level: int = 0, options=None, **fields):
+        """The surface normals of a level (dvo_amd_pyramid_normals; the rule is pinned in include/dvo_amd.h under "Surface
+        normals"): (normals float32 [h, w, 4], facing float32 [h, w], {"defined": n, "undefined": n}).  options: None, a
+        NormalOptions or a dict of normal_options' arguments; keyword arguments are normal_options' too."""
+        opt = _normal_options(dict(options or {}, **fields) if not isinstance(options, NormalOptions) else options)
+        w, h, _ = self.level_info(level)
+        normals, facing = np.empty((h, w, 4), np.float32), np.empty((h, w), np.float32)
+        cnt = (C.c_longlong * 2)()
+        _check(lib().dvo_amd_pyramid_normals(self._h, level, C.byref(opt), _fp(normals), _fp(facing), cnt), "dvo_amd_pyramid_normals")
+        return normals, facing, dict(zip(NORMAL_COUNTS, cnt))
+
+    def point_cloud(self, pose=None, bgr=None, level: int = 0, tracker: "DenseTracker | None" = None, normals=None):
         """RgbdCamera::buildPointCloud of a level transformed by `pose` (4x4, None = identity) and coloured from `bgr` (uint8
         HxWx3 of the level, None = grey from the intensity plane): (xyz float32 [h, w, 3], rgb uint32 [h, w]) in scan order,
         NaN points included (dvo_amd_point_cloud).  The entry runs in a tracker's context: `tracker` when one is given,
         otherwise a shared DenseTracker of the pyramid's device that this module creates on the first such call and keeps for
         the life of the process (with the buffers of the largest cloud it built; nothing is allocated per call once warm).
-        Pass `tracker=` to choose the context -- and with it where the buffers live and when they are freed."""
+        Pass `tracker=` to choose the context -- and with it where the buffers live and when they are freed.
+        With `normals` (True, a NormalOptions or a dict of normal_options' arguments) the result is (xyz, rgb, normals float32
+        [h, w, 4]): every point's surface normal in the pose's frame as well (dvo_amd_point_cloud_normals)."""
         w, h, _ = self.level_info(level)
         out = np.empty((h * w, 4), np.float32)
         T = None if pose is None else _pose_cm(pose)
@@ -1256,6 +1340,15 @@ class RgbdImagePyramid:
                 raise ValueError(f"bgr must be ({h}, {w}, 3) uint8 for level {level}")
             bgr_ptr, stride = bgr.ctypes.data, w * 3
         trk = tracker or _cloud_tracker(self.device)
+        if normals is not None and normals is not False:
+            opt = _normal_options(None if normals is True else normals)
+            nrm = np.empty((h, w, 4), np.float32)
+            _check(lib().dvo_amd_point_cloud_normals(trk._h, self._h, level,
+                                                     None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)),
+                                                     bgr_ptr, stride, C.byref(opt), out.ctypes.data, _fp(nrm)),
+                   "dvo_amd_point_cloud_normals")
+            xyz, rgb = _split_points(out)
+            return xyz.reshape(h, w, 3), rgb.reshape(h, w), nrm
         _check(lib().dvo_amd_point_cloud(trk._h, self._h, level,
                                          None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)),
                                          bgr_ptr, stride, out.ctypes.data), "dvo_amd_point_cloud")

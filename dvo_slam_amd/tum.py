@@ -179,9 +179,10 @@ def replay(assoc_path: str, trajectory_path: str | None = None, K=TUM_FR1_INTRIN
     return out
 
 
-def write_pcd(path: str, xyz, rgb):
+def write_pcd(path: str, xyz, rgb, normals=None):
     """Binary PCD v0.7 of a coloured cloud as pcl::io::savePCDFileBinary writes PointXYZRGB (dvo_amd_write_pcd).  xyz [h, w, 3]
-    with rgb [h, w] is written organized (WIDTH w, HEIGHT h); xyz [n, 3] with rgb [n] as n x 1."""
+    with rgb [h, w] is written organized (WIDTH w, HEIGHT h); xyz [n, 3] with rgb [n] as n x 1.  With normals ([h, w, 4] or
+    [n, 4], as point_cloud(normals=...) returns them) the file is a PointXYZRGBNormal cloud (dvo_amd_write_pcd_normals)."""
     xyz = np.asarray(xyz, dtype=np.float32)
     rgb = np.asarray(rgb, dtype=np.uint32)
     if xyz.ndim == 3:
@@ -189,4 +190,11 @@ def write_pcd(path: str, xyz, rgb):
     else:
         height, width = 1, len(xyz)
     pts = capi._pack_points(xyz, rgb)
+    if normals is not None:
+        nrm = np.ascontiguousarray(np.asarray(normals, dtype=np.float32).reshape(-1, 4))
+        if len(nrm) != len(pts):
+            raise ValueError("xyz and normals must hold the same number of points")
+        capi._check(_lib().dvo_amd_write_pcd_normals(os.fsencode(path), pts.ctypes.data, capi._fp(nrm), len(pts), width, height),
+                    "dvo_amd_write_pcd_normals")
+        return
     capi._check(_lib().dvo_amd_write_pcd(os.fsencode(path), pts.ctypes.data, len(pts), width, height), "dvo_amd_write_pcd")

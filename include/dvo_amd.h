@@ -1334,6 +1334,82 @@ int dvo_amd_map_render_pyramid(dvo_amd_map *map, const double *pose, const dvo_a
  * POINTS width*height (= n), then the records.  Host code only. */
 int dvo_amd_write_pcd(const char *path, const dvo_amd_point *points, long long n, int width, int height);
 
+/*
+ * Surface normals (RgbdImage::calculateNormals, rgbd_image.cpp:502-532; its members `normals`, CV_32FC4, and `angles`, CV_32FC1).
+ *
+ * Which way the surface under a pixel faces, from a pyramid level's depth plane and rays.  The reference takes the cross
+ * product of the one-pixel central differences of the back-projected points; on sensor depth (noise of depthStdDevZ, 1/5000 m
+ * steps) that alone is off by tens of degrees, so the rule here is the reference's plus a windowed, depth-aware sum of the
+ * un-normalised cross products (DESIGN.md 4.18 has the measured errors).  With every option 0 it IS the reference's rule.
+ *
+ * The rule for level l of a pyramid, size w x h, pixel (u, v).  All arithmetic is fp32, round to nearest; every product, sum,
+ * quotient and square root is rounded on its own (no contraction), sqrtf and / are the correctly rounded ones, denormals are kept.
+ *  1. point: P(u,v) = (tx[u]*z, ty[v]*z, z), z the level's depth plane, tx / ty the level's rays: the bits dvo_amd_point_cloud
+ *     produces at the identity pose;
+ *  2. raw cross product c(u,v), with the reference's clamped indices:
+ *       a = P(min(u+1,w-1), v) - P(max(u-1,0), v),   b = P(u, min(v+1,h-1)) - P(u, max(v-1,0)),
+ *       c = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x);  c is USABLE iff its three components are finite;
+ *  3. window sum, r = opt.radius[l] (0 <= r <= DVO_AMD_NORMAL_MAX_RADIUS): the pixel is UNDEFINED if its own z is not finite.
+ *     Otherwise the members (u+du, v+dv) are visited with dv = -r..r outer and du = -r..r inner; a member is added iff it lies
+ *     inside the plane, its c is usable and, when opt.depth_step_ratio > 0, fabsf(z_member - z) <= opt.depth_step_ratio * z.
+ *     m is the first added member's c as it is; every later member is added to it component by component, in that order.  No
+ *     member added: the pixel is undefined.  (r = 0 with ratio 0 is exactly the reference's per-pixel rule.)
+ *  4. normalise: s = (m.x*m.x + m.y*m.y) + m.z*m.z; if !(s >= 1e-30f) the pixel is undefined; len = sqrtf(s);
+ *     n = (m.x/len, m.y/len, m.z/len, 0);
+ *  5. orientation: d = (n.x*P.x + n.y*P.y) + n.z*P.z with the centre's P; with opt.toward_camera != 0 and d > 0 the three
+ *     components are negated (the default 0 keeps the reference's sign);
+ *  6. facing value: DVO_AMD_NORMAL_FACING_AXIS (the reference's `angles`): fabsf(n.z); DVO_AMD_NORMAL_FACING_RAY:
+ *     fabsf(d) / sqrtf((P.x*P.x + P.y*P.y) + P.z*P.z), the cosine between the normal and the viewing ray, NaN when that
+ *     square is not > 0;
+ *  7. undefined pixels: all four normal components are NaN (what normalize() of a NaN vector leaves in the reference), and so
+ *     is the facing value.
+ * The result is a function of the pyramid and the options alone: not of the launch geometry, not of the tiles a level is cut
+ * into.  There is no floating-point atomic; the counts are integers.
+ *
+ * Departures from the reference: Eigen's cross3 / normalize take their sums in Eigen's order, which is not pinned here (like
+ * the point cloud's transform): the two agree to fp32 rounding, not bit for bit.  A zero-length cross product (s < 1e-30) is
+ * undefined here; the reference divides by its length.
+ *
+ * dvo_amd_pyramid_normals: one level into host memory, one kernel launch and one synchronisation.
+ * dvo_amd_mask_from_normals: an ordinary mask (dvo_amd_mask_create's kind: erode it, warp it, match behind it) of the
+ * pyramid's size and level count: 1 iff the pixel is defined and its facing value >= min_facing[l] (a NaN facing value: 0);
+ * an undefined pixel: undefined_keep != 0.  One kernel launch for all levels and one synchronisation.
+ * dvo_amd_point_cloud_normals: dvo_amd_point_cloud (the same arguments, the same bits in `out`) plus every point's normal in
+ * the pose's frame: R = (float)pose's rotation element by element, n' = ((R_r0*n.x + R_r1*n.y) + R_r2*n.z) per row r, the
+ * fourth component carried over; an undefined pixel stays four NaNs.  pose NULL: the identity, applied the same way.
+ * dvo_amd_write_pcd_normals: binary PCD v0.7 as pcl::io::savePCDFileBinary writes a PointXYZRGBNormal cloud: FIELDS x y z rgb
+ * normal_x normal_y normal_z curvature, SIZE 4 x 8, TYPE F x 8, COUNT 1 x 8, 32-byte records (curvature 0); `normals` holds
+ * four floats per point, of which the first three are written.  Host code only.
+ *
+ * No context is needed except by the cloud; the entries run on the device's internal stream with storage of the call's own and
+ * keep nothing: the pyramid is only read.  DVO_AMD_ERR_INVALID_ARGUMENT comes first and needs no device, with a reason in
+ * dvo_amd_last_error() that starts with the entry's name: a NULL pyramid, options, min_facing or output; a level the pyramid
+ * does not have; a radius outside 0..DVO_AMD_NORMAL_MAX_RADIUS on a level the pyramid has; a depth_step_ratio that is negative
+ * or not finite; an unknown `facing`; a NaN min_facing[l]; a non-finite pose entry.  Then DVO_AMD_ERR_DEVICE_MISMATCH, then
+ * DVO_AMD_ERR_NO_DEVICE.  *out is NULL after every failure.
+ */
+#define DVO_AMD_NORMAL_MAX_RADIUS 8
+#define DVO_AMD_NORMAL_FACING_AXIS 0
+#define DVO_AMD_NORMAL_FACING_RAY 1
+typedef struct dvo_amd_normal_options {
+  int radius[DVO_AMD_MAX_LEVELS];   /* 0..DVO_AMD_NORMAL_MAX_RADIUS per level */
+  float depth_step_ratio;           /* >= 0, finite; 0: no test */
+  int facing;                       /* DVO_AMD_NORMAL_FACING_AXIS | DVO_AMD_NORMAL_FACING_RAY */
+  int toward_camera;
+} dvo_amd_normal_options;
+/* all 0: RgbdImage::calculateNormals; a NULL opt is a no-op */
+void dvo_amd_default_normal_options(dvo_amd_normal_options *opt);
+/* normals: w*h*4 floats, facing: w*h floats, host memory, either may be NULL; counts: {defined, undefined} or NULL */
+int dvo_amd_pyramid_normals(const dvo_amd_pyramid *p, int level, const dvo_amd_normal_options *opt, float *normals, float *facing,
+                            long long *counts);
+/* min_facing: one value per level of p; counts: per level {defined, undefined, kept}, or NULL */
+int dvo_amd_mask_from_normals(const dvo_amd_pyramid *p, const dvo_amd_normal_options *opt, const float *min_facing,
+                              int undefined_keep, dvo_amd_mask **out, long long *counts);
+/* out: w*h points of the level; normals: w*h*4 floats */
+int dvo_amd_point_cloud_normals(dvo_amd_context *ctx, dvo_amd_pyramid *image, int level, const double *pose, const unsigned char *bgr,
+                                int bgr_stride_bytes, const dvo_amd_normal_options *opt, dvo_amd_point *out, float *normals);
+int dvo_amd_write_pcd_normals(const char *path, const dvo_amd_point *points, const float *normals, long long n, int width, int height);
+
 /* dvo::core::computeResidualsAndValidFlagsSse (dense_tracking_impl.cpp:400-403) for one level and one float transform
  * (column-major 4x4, reference -> current).  residuals: width*height x 2 floats in pixel order, NaN where the pixel is not
  * selected or its warp is invalid.  Used by the parity tests and by dvo_amd_error_image. */

@@ -232,9 +232,36 @@ class PointCloudMatrix {
   mutable std::vector<float> xyzw_;
 };
 
+// RgbdImage::normals / RgbdImage::angles without OpenCV (rgbd_image.h: cv::Mat CV_32FC4 / CV_32FC1): a level's normal plane
+// (x, y, z, 0 per pixel, four NaNs where the surface has no normal) and |n.z| per pixel, row-major.  Filled by
+// dvo_amd_pyramid_normals with the default options -- RgbdImage::calculateNormals' own rule (dvo_amd.h, "Surface normals") -- on
+// the first access and kept, like PointCloudMatrix.
+class NormalPlane {
+ public:
+  explicit NormalPlane(int channels) : owner_(nullptr), level_(0), channels_(channels), filled_(false) {}
+  inline long rows() const;
+  inline long cols() const;
+  int channels() const { return channels_; }
+  inline const float *data() const;
+  float operator()(long row, long col, int channel = 0) const { return data()[((size_t)row * (size_t)cols() + (size_t)col) * channels_ + channel]; }
+
+ private:
+  friend class RgbdImagePyramid;
+  inline void fill() const;
+  const RgbdImagePyramid *owner_;
+  int level_, channels_;
+  mutable bool filled_;
+  mutable long rows_ = 0, cols_ = 0;
+  mutable std::vector<float> values_;
+};
+
 class RgbdImage {
  public:
+#ifdef DVO_AMD_HAVE_OPENCV
   RgbdImage() : width(0), height(0), owner_(nullptr), level_(0) {}
+#else
+  RgbdImage() : width(0), height(0), normals(4), angles(1), owner_(nullptr), level_(0) {}
+#endif
   size_t width, height;
   IntrinsicMatrix intrinsics;  // of this level (RgbdCamera::intrinsics())
   // the colour image callers attach (camera_keyframe_tracking.cpp:252): float B, G, R in 0..255, width * height pixels.  Read
@@ -246,6 +273,16 @@ class RgbdImage {
   std::vector<float> rgb;  // interleaved B, G, R
 #endif
   PointCloudMatrix pointcloud;
+  // rgbd_image.cpp:502-532: the surface normal of every pixel (CV_32FC4: x, y, z, 0) and `angles`, |n.z| (CV_32FC1), computed on
+  // the device by the reference's own rule (dvo_amd_pyramid_normals with the default options).  With OpenCV the two members are
+  // the reference's cv::Mat, filled by calculateNormals(); without, they fill themselves on first access and calculateNormals()
+  // only forces that.
+#ifdef DVO_AMD_HAVE_OPENCV
+  cv::Mat normals, angles;
+#else
+  NormalPlane normals, angles;
+#endif
+  inline void calculateNormals();
   void initialize() {}
   void calculateDerivatives() {}
   bool calculateIntensityDerivatives() { return false; }
@@ -356,6 +393,10 @@ class RgbdImagePyramid {
       img.intrinsics = IntrinsicMatrix::create(k[0], k[1], k[2], k[3]);
       img.owner_ = this, img.level_ = (int)idx;
       img.pointcloud.owner_ = this, img.pointcloud.level_ = (int)idx, img.pointcloud.filled_ = false;
+#ifndef DVO_AMD_HAVE_OPENCV
+      img.normals.owner_ = img.angles.owner_ = this, img.normals.level_ = img.angles.level_ = (int)idx;
+      img.normals.filled_ = img.angles.filled_ = false;
+#endif
     }
     return img;
   }
@@ -471,6 +512,47 @@ inline void PointCloudMatrix::fill() const {
   for (size_t p = 0; p < pts.size(); ++p)
     xyzw_[4 * p] = pts[p].x, xyzw_[4 * p + 1] = pts[p].y, xyzw_[4 * p + 2] = pts[p].z, xyzw_[4 * p + 3] = 1.0f;
   filled_ = true;
+}
+
+inline void NormalPlane::fill() const {
+  if (filled_) return;
+  if (!owner_) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "RgbdImage::normals");
+  int w = 0, h = 0;
+  ::dvo::detail::check(dvo_amd_pyramid_level_info(owner_->handle(), level_, &w, &h, nullptr), "RgbdImage::normals");
+  values_.resize((size_t)w * h * channels_);
+  dvo_amd_normal_options o;
+  dvo_amd_default_normal_options(&o);
+  ::dvo::detail::check(dvo_amd_pyramid_normals(owner_->handle(), level_, &o, channels_ == 4 ? values_.data() : nullptr,
+                                               channels_ == 4 ? nullptr : values_.data(), nullptr),
+                       "RgbdImage::calculateNormals");
+  rows_ = h, cols_ = w;
+  filled_ = true;
+}
+inline long NormalPlane::rows() const {
+  fill();
+  return rows_;
+}
+inline long NormalPlane::cols() const {
+  fill();
+  return cols_;
+}
+inline const float *NormalPlane::data() const {
+  fill();
+  return values_.data();
+}
+inline void RgbdImage::calculateNormals() {
+#ifdef DVO_AMD_HAVE_OPENCV
+  if (!owner_) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "RgbdImage::calculateNormals");
+  if (!normals.empty() && !angles.empty()) return;  // (rgbd_image.cpp:504: computed once)
+  cv::Mat n((int)height, (int)width, CV_MAKETYPE(CV_32F, 4)), a((int)height, (int)width, CV_MAKETYPE(CV_32F, 1));
+  dvo_amd_normal_options o;
+  dvo_amd_default_normal_options(&o);
+  ::dvo::detail::check(dvo_amd_pyramid_normals(owner_->handle(), level_, &o, n.ptr<float>(), a.ptr<float>(), nullptr),
+                       "RgbdImage::calculateNormals");
+  normals = n, angles = a;
+#else
+  (void)normals.data(), (void)angles.data();
+#endif
 }
 
 // rgbd_image.h:39-89: the 48-byte record PointSelection::select hands out ({x, y, z, 1; I, Z, Ix, Iy, Zx, Zy, 0, 0})
@@ -628,6 +710,31 @@ class SelectionMask {
                                               &records[0].evaluated, nullptr),
                   where);
     SelectionMask out(m, reference.device());
+    if (counts) counts->assign(records, records + out.info().levels);
+    return out;
+  }
+  // A mask from which way the surfaces face (dvo_amd.h, "Surface normals"): the pixels of `pyramid` whose normal is defined and
+  // whose facing value is at least minFacing[l] on level l (no entry for the level: the last entry); a pixel without a normal is
+  // kept iff undefinedKeep.  The pixels it drops are the ones seen at a grazing angle, where depth noise and flying pixels are
+  // worst.  The pyramid holds its levels (RgbdImagePyramid::build); the mask has the pyramid's, every level from one launch.
+  struct NormalOptions : dvo_amd_normal_options {
+    NormalOptions() { dvo_amd_default_normal_options(this); }
+  };
+  struct NormalCounts {  // one level's record
+    long long defined, undefined, kept;
+  };
+  static SelectionMask fromNormals(const RgbdImagePyramid &pyramid, const std::vector<float> &minFacing,
+                                   const NormalOptions &options = NormalOptions(), bool undefinedKeep = false,
+                                   std::vector<NormalCounts> *counts = nullptr) {
+    static_assert(sizeof(NormalCounts) == 3 * sizeof(long long), "a NormalCounts is one record of dvo_amd_mask_from_normals' counts");
+    if (minFacing.empty()) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "SelectionMask::fromNormals");
+    float min_facing[DVO_AMD_MAX_LEVELS];
+    for (size_t l = 0; l < (size_t)DVO_AMD_MAX_LEVELS; ++l) min_facing[l] = minFacing[std::min(l, minFacing.size() - 1)];
+    NormalCounts records[DVO_AMD_MAX_LEVELS];
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_from_normals(pyramid.handle(), &options, min_facing, undefinedKeep ? 1 : 0, &m, &records[0].defined),
+                  "SelectionMask::fromNormals");
+    SelectionMask out(m, pyramid.device());
     if (counts) counts->assign(records, records + out.info().levels);
     return out;
   }

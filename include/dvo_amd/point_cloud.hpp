@@ -31,6 +31,13 @@ struct PointXYZRGB {
   PointXYZRGB() : x(0.0f), y(0.0f), z(0.0f), r(0), g(0), b(0) {}
 };
 
+// pcl::PointXYZRGBNormal as far as a mesher or a shader reads it: the point, its colour, its surface normal (NaN where the
+// surface has none) and PCL's curvature, which is not computed here (0)
+struct PointXYZRGBNormal : PointXYZRGB {
+  float normal_x, normal_y, normal_z, curvature;
+  PointXYZRGBNormal() : normal_x(0.0f), normal_y(0.0f), normal_z(0.0f), curvature(0.0f) {}
+};
+
 namespace detail {
 inline PointXYZRGB from_record(const dvo_amd_point &p) {
   PointXYZRGB q;
@@ -117,6 +124,44 @@ class AsyncPointCloudBuilder {
       ::dvo::detail::check(dvo_amd_point_cloud(ctx, pyr->handle(), level(), core::data(pose), bgr.empty() ? nullptr : bgr.data(),
                                                (int)image.width * 3, out.data()),
                            "AsyncPointCloudBuilder::BuildJob::build");
+    }
+
+    // (not in the reference) the same cloud with every point's surface normal in the pose's frame (dvo_amd_point_cloud_normals;
+    // the rule is pinned in dvo_amd.h under "Surface normals"): `options` default to RgbdImage::calculateNormals' own rule
+    struct NormalCloud {
+      typedef PointXYZRGBNormal PointType;
+      typedef std::shared_ptr<NormalCloud> Ptr;
+      std::vector<PointXYZRGBNormal> points;
+      std::uint32_t width, height;
+      NormalCloud() : width(0), height(1) {}
+      size_t size() const { return points.size(); }
+    };
+    NormalCloud::Ptr buildWithNormals(const core::SelectionMask::NormalOptions &options = core::SelectionMask::NormalOptions()) const {
+      std::vector<dvo_amd_point> pts;
+      std::vector<float> normals;
+      recordsWithNormals(pts, normals, options);
+      NormalCloud::Ptr cloud(new NormalCloud);
+      cloud->points.resize(pts.size());
+      for (size_t i = 0; i < pts.size(); ++i) {
+        PointXYZRGBNormal &q = cloud->points[i];
+        static_cast<PointXYZRGB &>(q) = detail::from_record(pts[i]);
+        q.normal_x = normals[4 * i], q.normal_y = normals[4 * i + 1], q.normal_z = normals[4 * i + 2];
+      }
+      cloud->width = (std::uint32_t)image.width, cloud->height = (std::uint32_t)image.height;
+      return cloud;
+    }
+    // ... as the C ABI's records and four floats per point (what dvo_amd_write_pcd_normals takes)
+    void recordsWithNormals(std::vector<dvo_amd_point> &out, std::vector<float> &normals,
+                            const core::SelectionMask::NormalOptions &options = core::SelectionMask::NormalOptions()) const {
+      const core::RgbdImagePyramid *pyr = owner();
+      const std::vector<unsigned char> bgr = detail::bgr8(image);
+      out.resize(image.width * image.height);
+      normals.resize(image.width * image.height * 4);
+      std::unique_lock<std::mutex> lock;
+      dvo_amd_context *ctx = core::cloud::context(pyr->device(), lock);
+      ::dvo::detail::check(dvo_amd_point_cloud_normals(ctx, pyr->handle(), level(), core::data(pose), bgr.empty() ? nullptr : bgr.data(),
+                                                       (int)image.width * 3, &options, out.data(), normals.data()),
+                           "AsyncPointCloudBuilder::BuildJob::buildWithNormals");
     }
 
     const core::RgbdImagePyramid *owner() const {

@@ -261,6 +261,12 @@ int dvo_amd_debug_fuse_timing(int device, int enable, double *last_ms);
  * launch of the call (not the uploads, not a frame's descriptor, not the copies back); *last_ms (may be NULL) receives the device
  * time of the most recent bracketed call */
 int dvo_amd_debug_place_timing(int device, int enable, double *last_ms);
+/* what the most recent successful dvo_amd_pyramid_normals, dvo_amd_mask_from_normals or normal pass of
+ * dvo_amd_point_cloud_normals on `device` enqueued: kernel launches (one, however many levels) and host synchronisations (one);
+ * with enable != 0 the launch of every later such call is bracketed by two events on the device's internal stream (the launch
+ * alone: not the table's upload, not the copies back) and *last_ms receives the device time of the most recent bracketed launch.
+ * Any output may be NULL; all zero before the first such call */
+int dvo_amd_debug_normals_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms);
 
 #ifdef __cplusplus
 }
