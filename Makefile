@@ -11,7 +11,8 @@ CPP := $(SRC)/dvo_kernels.hip $(SRC)/dvo_pyramid.cpp $(SRC)/dvo_tracker.cpp $(SR
        $(SRC)/dvo_validator.cpp $(SRC)/dvo_frontend.cpp $(SRC)/dvo_tum.cpp $(SRC)/dvo_map.cpp $(SRC)/dvo_graph.cpp \
        $(SRC)/dvo_graph_batch.cpp $(SRC)/dvo_covisibility.cpp $(SRC)/dvo_rectify.cpp $(SRC)/dvo_register.cpp \
        $(SRC)/dvo_ingest.cpp $(SRC)/dvo_mask.cpp $(SRC)/dvo_budget.cpp $(SRC)/dvo_mask_ops.cpp \
-       $(SRC)/dvo_mask_residual.cpp $(SRC)/dvo_fuse.cpp $(SRC)/dvo_place.cpp $(SRC)/dvo_normals.cpp
+       $(SRC)/dvo_mask_residual.cpp $(SRC)/dvo_fuse.cpp $(SRC)/dvo_place.cpp $(SRC)/dvo_normals.cpp \
+       $(SRC)/dvo_depth_filter.cpp
 
 $(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_graph_device.h $(SRC)/dvo_graph_host.h \
         include/dvo_amd.h include/dvo_amd_debug.h
@@ -20,7 +21,7 @@ $(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_
 oracle:
 	$(MAKE) -C oracle
 
-# the C examples that need no input files, and budget_selection_example, mask_ops_example, residual_mask_example, depth_fusion_example, place_index_example and the two normals examples, which take their frames as float32 files (the tests
+# the C examples that need no input files, and budget_selection_example, mask_ops_example, residual_mask_example, depth_fusion_example, place_index_example, the two normals examples and the two depth_filter examples, which take their frames as float32 files (the tests
 # build every example themselves, tests/test_*_adaptor.py)
 examples: $(LIB)
 	mkdir -p examples/_build
@@ -48,6 +49,10 @@ examples: $(LIB)
 	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 	$(CXX) -std=c++11 -Wall -pthread -Iinclude/dvo_amd_compat -Iinclude examples/normals_adaptor_example.cpp \
 	    -o examples/_build/normals_adaptor_example -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CC) -std=c99 -Wall -Iinclude examples/depth_filter_example.c -o examples/_build/depth_filter_example \
+	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CXX) -std=c++11 -Wall -pthread -Iinclude/dvo_amd_compat -Iinclude examples/depth_filter_adaptor_example.cpp \
+	    -o examples/_build/depth_filter_adaptor_example -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 
 clean:
 	rm -f $(LIB)

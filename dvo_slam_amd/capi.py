@@ -63,6 +63,8 @@ EXPORTS = [
     "dvo_amd_debug_residuals_masked", "dvo_amd_debug_iteration_masked", "dvo_amd_debug_weights_masked",
     "dvo_amd_default_normal_options", "dvo_amd_pyramid_normals", "dvo_amd_mask_from_normals", "dvo_amd_point_cloud_normals",
     "dvo_amd_write_pcd_normals", "dvo_amd_debug_normals_timing",
+    "dvo_amd_default_depth_filter_options", "dvo_amd_pyramid_filter_depth", "dvo_amd_pyramid_filter_depth_many",
+    "dvo_amd_debug_depth_filter_timing",
 ]
 
 
@@ -178,6 +180,18 @@ class FuseOptions(C.Structure):
     """dvo_amd_fuse_options, field for field"""
     _fields_ = [("near_z", C.c_float), ("depth_sigmas", C.c_float), ("min_cos", C.c_float), ("sample", C.c_int),
                 ("min_observations", C.c_int), ("drop_unconfirmed", C.c_int)]
+
+
+class DepthFilterOptions(C.Structure):
+    """dvo_amd_depth_filter_options, field for field"""
+    _fields_ = [("radius", C.c_int), ("range_sigmas", C.c_float), ("min_support", C.c_int), ("fill_radius", C.c_int),
+                ("min_fill_support", C.c_int)]
+
+
+DEPTH_FILTER_MAX_RADIUS = 8
+# one record of dvo_amd_pyramid_filter_depth's counts, field for field
+DEPTH_FILTER_COUNTS = ("with_depth", "kept", "dropped", "holes", "filled")
+DEPTH_FILTER_DTYPE = np.dtype([(name, np.int64) for name in DEPTH_FILTER_COUNTS])
 
 
 class NormalOptions(C.Structure):
@@ -432,6 +446,13 @@ def lib():
     L.dvo_amd_pyramid_fuse_depth_many.argtypes = [C.c_int, C.POINTER(vp), ip, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
                                                   C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(vp)]
     L.dvo_amd_debug_fuse_timing.argtypes = [C.c_int, C.c_int, dp]
+    L.dvo_amd_default_depth_filter_options.argtypes = [C.POINTER(DepthFilterOptions)]
+    L.dvo_amd_default_depth_filter_options.restype = None
+    L.dvo_amd_pyramid_filter_depth.argtypes = [vp, C.POINTER(DepthFilterOptions), C.POINTER(vp), C.POINTER(C.c_longlong),
+                                               C.POINTER(C.c_ushort)]
+    L.dvo_amd_pyramid_filter_depth_many.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(DepthFilterOptions), C.POINTER(vp),
+                                                    C.POINTER(C.c_longlong), C.POINTER(vp)]
+    L.dvo_amd_debug_depth_filter_timing.argtypes = [C.c_int, C.c_int, dp]
     L.dvo_amd_default_normal_options.argtypes = [C.POINTER(NormalOptions)]
     L.dvo_amd_default_normal_options.restype = None
     L.dvo_amd_pyramid_normals.argtypes = [vp, C.c_int, C.POINTER(NormalOptions), fp, fp, C.POINTER(C.c_longlong)]
@@ -701,6 +722,60 @@ def fuse_options(**options) -> FuseOptions:
             raise TypeError(f"unknown fuse option {k!r}")
         setattr(opt, k, float(v) if k in ("near_z", "depth_sigmas", "min_cos") else int(v))
     return opt
+
+
+def depth_filter_options(**options) -> DepthFilterOptions:
+    """dvo_amd_default_depth_filter_options (radius 2, range_sigmas 3, min_support 1, fill_radius 0, min_fill_support 3) with the
+    given fields replaced"""
+    opt = DepthFilterOptions()
+    lib().dvo_amd_default_depth_filter_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in ("radius", "range_sigmas", "min_support", "fill_radius", "min_fill_support"):
+            raise TypeError(f"unknown depth filter option {k!r}")
+        setattr(opt, k, float(v) if k == "range_sigmas" else int(v))
+    return opt
+
+
+def filter_depth_many(pyramids, options=None, counts: bool = False, support: bool = False):
+    """Many pyramids' level-0 depth filtered in one call and one kernel launch (dvo_amd_pyramid_filter_depth_many; the rule is
+    pinned in include/dvo_amd.h under "Depth filtering"); the pyramids may differ in size.  options: None, a DepthFilterOptions
+    or a dict of its fields (radius, range_sigmas, min_support, fill_radius, min_fill_support).  Returns the list of new pyramids;
+    with counts=True also the counts (a DEPTH_FILTER_DTYPE array, one record per pyramid); with support=True also the list of
+    support planes (uint16 [h, w]: the members of every pixel's window) -- as a tuple, in this order."""
+    pyramids = list(pyramids)
+    n = len(pyramids)
+    opt = options if isinstance(options, DepthFilterOptions) else depth_filter_options(**(options or {}))
+    vp = C.c_void_p
+    cnt = np.zeros(max(1, n), DEPTH_FILTER_DTYPE)
+    planes = []
+    if support:
+        for p in pyramids:
+            w, h, _ = p.level_info(0)
+            planes.append(np.zeros((h, w), np.uint16))
+    out = (vp * max(1, n))()
+    sup = (vp * max(1, n))(*[p.ctypes.data for p in planes]) if support else None
+    _check(lib().dvo_amd_pyramid_filter_depth_many(n, (vp * max(1, n))(*[p._h for p in pyramids]), C.byref(opt), out,
+                                                   cnt.ctypes.data_as(C.POINTER(C.c_longlong)) if counts else None, sup),
+           "dvo_amd_pyramid_filter_depth_many")
+    made = []
+    for j in range(n):
+        p = RgbdImagePyramid.__new__(RgbdImagePyramid)
+        p._h, p.device, p.registration_stats = vp(out[j]), pyramids[j].device, None
+        made.append(p)
+    result = (made,)
+    if counts:
+        result += (cnt[:n].copy(),)
+    if support:
+        result += (planes,)
+    return result if len(result) > 1 else made
+
+
+def depth_filter_timing(enable: bool = True, device: int = 0) -> float:
+    """(instrumentation) switches the event bracket around the filter launch of every filter_depth / filter_depth_many of `device`
+    on or off and returns the device time of the most recent bracketed launch in ms (dvo_amd_debug_depth_filter_timing)"""
+    ms = C.c_double()
+    _check(lib().dvo_amd_debug_depth_filter_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_depth_filter_timing")
+    return ms.value
 
 
 def normal_options(radius=None, depth_step_ratio: float | None = None, facing: int | None = None,
@@ -1309,6 +1384,14 @@ class RgbdImagePyramid:
         if observations:
             result += (planes,)
         return result if len(result) > 1 else made
+
+    def filter_depth(self, options=None, counts: bool = False, support: bool = False):
+        """This pyramid with its level-0 depth filtered (dvo_amd_pyramid_filter_depth; the rule is pinned in include/dvo_amd.h
+        under "Depth filtering"): a new pyramid of this one's size, intrinsics, level count and timestamp; this one is only read.
+        options: None, a DepthFilterOptions or a dict of its fields.  Returns the pyramid; with counts=True also the counts (one
+        DEPTH_FILTER_DTYPE record); with support=True also the support plane (uint16 [h, w]) -- as a tuple, in this order."""
+        got = filter_depth_many([self], options, counts=counts, support=support)
+        return tuple(part[0] for part in got) if counts or support else got[0]
 
     def normals(self, level: int = 0, options=None, **fields):
         """The surface normals of a level (dvo_amd_pyramid_normals; the rule is pinned in include/dvo_amd.h under "Surface

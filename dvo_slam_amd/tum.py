@@ -111,29 +111,36 @@ def read_groundtruth(path: str):
 
 
 def load(K, rgb_file: str, depth_file: str, levels: int, device: int = 0, timestamp: float = 0.0,
-         depth_scale: float = TUM_DEPTH_SCALE, remap: "capi.Remap | None" = None) -> capi.RgbdImagePyramid:
+         depth_scale: float = TUM_DEPTH_SCALE, remap: "capi.Remap | None" = None, depth_filter=None) -> capi.RgbdImagePyramid:
     """`load()` of benchmark_slam.cpp:46-93: imread both files, BGR -> gray float, raw depth -> metres with 0 -> NaN,
     camera.create(...).  Decoding happens on the host, both conversions and the pyramid on the GPU.
     remap: a capi.Remap through which both images are resampled on the way in (K is then the rectified camera's).  There is no
     preset: TUM's depth PNGs were registered by the driver with default intrinsics, so whether to resample them with the
-    colour camera's distortion is the caller's decision."""
+    colour camera's distortion is the caller's decision.
+    depth_filter: None, or what RgbdImagePyramid.filter_depth takes as options (a capi.DepthFilterOptions or a dict of its fields;
+    {} for the defaults): the pyramid's level-0 depth is filtered on the device after ingest and the filtered pyramid returned."""
     bgr = imread_color(rgb_file)
     depth = imread_depth(depth_file)
-    return capi.RgbdImagePyramid.from_raw(bgr, depth, K, levels, depth_scale=depth_scale, device=device, timestamp=timestamp,
-                                          remap=remap)
+    pyramid = capi.RgbdImagePyramid.from_raw(bgr, depth, K, levels, depth_scale=depth_scale, device=device, timestamp=timestamp,
+                                             remap=remap)
+    return pyramid if depth_filter is None else pyramid.filter_depth(depth_filter)
 
 
-def load_batch(entries, K, levels: int, device: int = 0, base: str = "", depth_scale: float = TUM_DEPTH_SCALE, selection=None):
+def load_batch(entries, K, levels: int, device: int = 0, base: str = "", depth_scale: float = TUM_DEPTH_SCALE, selection=None,
+               depth_filter=None):
     """load() for several entries of an association file (RgbdPair: RgbFile, DepthFile, RgbTimestamp; file names relative to
     `base`) in ONE pyramid build (capi.RgbdImagePyramid.from_raw_batch): the PNGs are decoded on the host one after the other,
     then every frame's conversions and pyramid share the same few kernel launches.  Returns the pyramids in the entries' order,
     each with its entry's RgbTimestamp, each what load() makes of that entry.  selection: None, or (intensity_threshold,
     depth_threshold) -- a tracker's two derivative thresholds -- to have every pyramid's point selection built in the same call.
-    Resampling through a remap stays with load()."""
+    Resampling through a remap stays with load().  depth_filter: see load(); all pyramids are filtered in one further call
+    (capi.filter_depth_many).  A filtered pyramid has no selection yet: `selection` is then built with the first use, not here."""
     bgr = [imread_color(os.path.join(base, p.RgbFile)) for p in entries]
     depth = [imread_depth(os.path.join(base, p.DepthFile)) for p in entries]
-    return capi.RgbdImagePyramid.from_raw_batch(bgr, depth, K, levels, depth_scale=depth_scale, device=device,
-                                                timestamps=[p.RgbTimestamp for p in entries], selection=selection)
+    pyramids = capi.RgbdImagePyramid.from_raw_batch(bgr, depth, K, levels, depth_scale=depth_scale, device=device,
+                                                    timestamps=[p.RgbTimestamp for p in entries],
+                                                    selection=selection if depth_filter is None else None)
+    return pyramids if depth_filter is None else capi.filter_depth_many(pyramids, depth_filter)
 
 
 def format_trajectory_line(timestamp: float, T) -> str:

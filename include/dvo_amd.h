@@ -371,7 +371,8 @@ int dvo_amd_pyramid_create_raw_remapped(int device, const unsigned char *image, 
  * differs from width x height; an image stride smaller than the row it must hold; everything dvo_amd_pyramid_create_raw rejects.
  * Then DVO_AMD_ERR_NO_DEVICE without a GPU, and DVO_AMD_ERR_DEVICE_MISMATCH for a remap on another device.
  *
- * Not covered: a distortion model for the depth camera; hole filling beyond the footprint; smoothing; float depth planes.
+ * Not covered: a distortion model for the depth camera; hole filling beyond the footprint; smoothing (both are what
+ * dvo_amd_pyramid_filter_depth does to the pyramid this entry returns: "Depth filtering"); float depth planes.
  */
 typedef struct {
   int   depth_width, depth_height;  /* size of the raw depth frame: 1..2^20 a side */
@@ -799,6 +800,87 @@ int dvo_amd_pyramid_fuse_depth_many(int n_keyframes, const dvo_amd_pyramid *cons
                                     const dvo_amd_pyramid *const *frames, const double *T, const dvo_amd_fuse_options *opt,
                                     dvo_amd_pyramid **out, long long *frame_counts, long long *keyframe_counts,
                                     unsigned char *const *observations /* NULL, or n_keyframes pointers each NULL or w*h */);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
+ * Depth filtering: one frame's level-0 depth denoised, its unsupported pixels dropped and its small holes filled, on the device.
+ *
+ * Depth fusion above cures the noise of a keyframe that has had frames tracked against it.  The first keyframe, every current frame
+ * and every frame handed to the place index or the map have none: their depth is one raw sensor frame.  The single-frame
+ * counterpart is an edge-preserving filter over a (2 radius + 1)^2 window whose range scale is the sensor's own noise model, so that
+ * a depth step larger than the noise is never smoothed across; a pixel too few of whose neighbours agree with it (a flying pixel
+ * at a depth discontinuity) can be dropped, and a hole can be filled from the farthest surface around it.
+ * dvo_amd_pyramid_filter_depth_many(n, p, opt, out, ...) filters n pyramids, which may differ in size, intrinsics and level count;
+ * dvo_amd_pyramid_filter_depth is the case n = 1.  The entries take no context: like depth fusion they run on the device's internal
+ * stream, use no tracker slot, and may be called while pairs are queued elsewhere.  (The reference has no counterpart.)
+ *
+ * The result out[j] is a new ordinary pyramid -- immutable, refcounted, accepted by every entry that accepts a pyramid -- with the
+ * input's size, intrinsics, level count and timestamp.  Its level-0 intensity is the input's, bit for bit; its level-0 depth is the
+ * filtered plane; every other level and plane is what the builder derives from those two: it equals, plane for plane,
+ * dvo_amd_pyramid_create called with the same two float planes.  It has no selection yet.  The input is only read.  *out, and in the
+ * many form every out[j], is NULL on every failure.  All pyramids of a call are filtered in ONE kernel launch and the call
+ * synchronises once for it, then as the builder does per pyramid.
+ *
+ * The rule, operation by operation; the library is built without contraction, so every product, sum and quotient rounds on its
+ * own, and divisions are correctly rounded.  All arithmetic is fp32.
+ *   sigma(z) = 0.0012f + 0.0019f * ((z - 0.4f) * (z - 0.4f))      depthStdDevZ, dense_tracking_impl.cpp:122-128
+ *   B_r[d] = (float) C(2r, r + d), d = -r .. r                     binomial weights: exact integers (at most 12870), no
+ *                                                                  transcendental; their standard deviation is sqrt(r / 2) pixels
+ *   ws(dy, dx) = B_r[dy] * B_r[dx]                                 one rounded product
+ * Only the input plane Z is read: nothing cascades from pixel to pixel.  For the pixel (u, v) with zc = Z[v, u]:
+ *  1. a pixel with depth: zc is finite; the pixel counts in with_depth.  s = range_sigmas * sigma(zc); sw = 0, swd = 0, n = 0.
+ *     For dy = -radius .. radius (outer), dx = -radius .. radius (inner), skipping a position outside the plane:
+ *       zm = Z[v + dy, u + dx]; d = zm - zc
+ *       member iff fabsf(d) <= s                                   (a NaN zm is never a member)
+ *       for a member, in this order:
+ *         wr = 1.0f - (d * d) / (s * s)
+ *         w  = ws(dy, dx) * wr
+ *         sw = sw + w; swd = swd + w * d; n = n + 1
+ *     The centre is always a member, with wr = 1.
+ *  2. keep or drop: if n >= min_support the output is zc + swd / sw and the pixel counts as kept; otherwise the output is NaN and
+ *     the pixel counts as dropped.  support[v * w + u] = n (at most 289).
+ *  3. a hole: zc is not finite (NaN or an infinity); the pixel counts in holes and support is 0.  With fill_radius == 0 the output
+ *     is NaN.  Otherwise, over the (2 fill_radius + 1)^2 window in the same order: zfar is the largest finite zm; if there is none
+ *     the output is NaN.  s = range_sigmas * sigma(zfar); sw = 0, swd = 0, n = 0.
+ *       member iff zm is finite and zfar - zm <= s
+ *       for a member, with ws from B_fill_radius:
+ *         sw = sw + ws; swd = swd + ws * (zm - zfar); n = n + 1
+ *     If n >= min_fill_support the output is zfar + swd / sw and the pixel counts as filled; otherwise the output is NaN.
+ *     (Why the farthest surface: holes in structured-light depth are occlusion shadows, and they lie on the background.)
+ *  4. counts (may be NULL): DVO_AMD_DEPTH_FILTER_COUNTS long long per pyramid: with_depth, kept, dropped, holes, filled.
+ *     with_depth = kept + dropped; with_depth + holes = w * h; filled <= holes.  All counts are integers and every pixel's sums are
+ *     taken in window order: no value depends on the launch geometry, on the order atomics land in or on what else is in the call.
+ * Every NaN of the output is the one quiet NaN 0x7FC00000.
+ * Consequences.  With radius 0 and fill_radius 0 the output plane is the input plane bit for bit (d = 0, so swd = 0 and
+ * zc + 0 / sw = zc), a NaN's payload and the sign of a zero depth apart.  A window whose members all have the same depth leaves
+ * that depth bit for bit.  A range_sigmas so small that s * s underflows to 0 makes the centre's quotient 0 / 0: keep it above 1e-15.
+ * support (may be NULL; in the many form any entry may be NULL): host memory, w * h unsigned shorts per pyramid.
+ * n == 0 is DVO_AMD_OK and does nothing.
+ * Errors, in this order and before any device work.  DVO_AMD_ERR_INVALID_ARGUMENT with a reason in dvo_amd_last_error() that starts
+ * with the entry's name: a NULL pointer (inside the array too); n < 0; radius or fill_radius outside
+ * 0 .. DVO_AMD_DEPTH_FILTER_MAX_RADIUS; range_sigmas not finite or <= 0; min_support outside 1 .. (2 radius + 1)^2; with
+ * fill_radius > 0, min_fill_support outside 1 .. (2 fill_radius + 1)^2.  Then DVO_AMD_ERR_DEVICE_MISMATCH unless every pyramid of
+ * the call lives on one device, then DVO_AMD_ERR_NO_DEVICE.
+ *
+ * Not covered: the intensity is not filtered; no per-pixel variance is kept in the pyramid (sw is dropped after the division); the
+ * filter is not folded into the ingest kernels (the raw entries are untouched: filter what they return); there is no sensor model
+ * other than depthStdDevZ scaled by range_sigmas; a hole wider than the fill window keeps its centre.
+ */
+#define DVO_AMD_DEPTH_FILTER_MAX_RADIUS 8
+#define DVO_AMD_DEPTH_FILTER_COUNTS 5   /* with_depth, kept, dropped, holes, filled */
+typedef struct dvo_amd_depth_filter_options {
+  int   radius;            /* 0 .. 8; default 2: the window is (2 radius + 1)^2, clipped to the plane */
+  float range_sigmas;      /* finite, > 0; default 3 */
+  int   min_support;       /* 1 .. (2 radius + 1)^2; default 1 = nothing is ever dropped */
+  int   fill_radius;       /* 0 .. 8; default 0 = holes stay holes */
+  int   min_fill_support;  /* 1 .. (2 fill_radius + 1)^2 when fill_radius > 0; default 3 */
+} dvo_amd_depth_filter_options;
+/* radius 2, range_sigmas 3, min_support 1, fill_radius 0, min_fill_support 3; a NULL opt is a no-op */
+void dvo_amd_default_depth_filter_options(dvo_amd_depth_filter_options *opt);
+int dvo_amd_pyramid_filter_depth(const dvo_amd_pyramid *p, const dvo_amd_depth_filter_options *opt, dvo_amd_pyramid **out,
+                                 long long *counts /* [5] or NULL */, unsigned short *support /* host, w*h, or NULL */);
+int dvo_amd_pyramid_filter_depth_many(int n, const dvo_amd_pyramid *const *p, const dvo_amd_depth_filter_options *opt,
+                                      dvo_amd_pyramid **out, long long *counts /* [n][5] or NULL */,
+                                      unsigned short *const *support /* NULL, or n pointers each NULL or w*h */);
 
 /* n independent match() calls advanced in lock step on one GPU (the shape of LocalTracker::update's tbb::parallel_invoke,
  * local_tracker.cpp:184, and of the loop-closure validator's parallel_reduce, keyframe_graph.cpp:576-593).
@@ -1302,7 +1384,8 @@ int dvo_amd_map_extract(dvo_amd_map *map, const float *box, dvo_amd_point *out, 
  *  7. resolve, per pixel: covered: depth = cz, rgb = the voxel's packed colour, intensity = (float)((1868 B + 9617 G + 4899 R
  *     + 8192) >> 14) (the ingest's grey rule: a grey keyframe's value comes back unchanged), index = r; empty: depth = NaN
  *     (0x7FC00000), rgb = 0, intensity = 0, index = -1.
- * There is no hole filling and no smoothing: a pixel no footprint covers stays empty.
+ * There is no hole filling and no smoothing: a pixel no footprint covers stays empty (dvo_amd_pyramid_filter_depth on the rendered
+ * pyramid does both).
  *
  * A footprint side is bounded by the view, not by clipping: near_z < (leaf * max(fx, fy)) / 32 (in fp32) is rejected, so no
  * voxel spans more than 32 pixels (33 pixel centres).  DVO_AMD_ERR_INVALID_ARGUMENT with a reason in dvo_amd_last_error() for

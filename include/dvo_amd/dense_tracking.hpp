@@ -450,6 +450,36 @@ class RgbdImagePyramid {
     return out;
   }
 
+  // (not in the reference, which tracks raw sensor depth) This frame with its level-0 depth filtered on the device (dvo_amd.h,
+  // "Depth filtering"): an edge-preserving filter whose range scale is the sensor's noise model, unsupported pixels dropped, small
+  // holes filled.  A new pyramid of this one's size, intrinsics, level count and timestamp; this one is only read and must hold
+  // its levels (RgbdImagePyramid::build; a match has built them).  counts: one record; support: width * height window members.
+  struct DepthFilterOptions : dvo_amd_depth_filter_options {
+    DepthFilterOptions() { dvo_amd_default_depth_filter_options(this); }
+  };
+  struct DepthFilterCounts {
+    long long with_depth, kept, dropped, holes, filled;
+  };
+  Ptr filterDepth(const DepthFilterOptions &options = DepthFilterOptions(), DepthFilterCounts *counts = nullptr,
+                  std::vector<unsigned short> *support = nullptr) const {
+    static_assert(sizeof(DepthFilterCounts) == DVO_AMD_DEPTH_FILTER_COUNTS * sizeof(long long),
+                  "the count record is dvo_amd_pyramid_filter_depth's");
+    const char *where = "RgbdImagePyramid::filterDepth";
+    DepthFilterCounts record;
+    if (support) support->assign((size_t)width_ * height_, 0);
+    dvo_amd_pyramid *filtered = nullptr;
+    detail::check(dvo_amd_pyramid_filter_depth(handle_, &options, &filtered, &record.with_depth, support ? support->data() : nullptr), where);
+    Ptr out;
+    try {
+      out = Ptr(new RgbdImagePyramid(filtered, width_, height_, K_, device_, timestamp_));
+    } catch (...) {
+      dvo_amd_pyramid_release(filtered);
+      throw;
+    }
+    if (counts) *counts = record;
+    return out;
+  }
+
   double timestamp() const { return timestamp_; }
   int device() const { return device_; }
   int width() const { return width_; }

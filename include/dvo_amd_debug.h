@@ -267,6 +267,10 @@ int dvo_amd_debug_place_timing(int device, int enable, double *last_ms);
  * alone: not the table's upload, not the copies back) and *last_ms receives the device time of the most recent bracketed launch.
  * Any output may be NULL; all zero before the first such call */
 int dvo_amd_debug_normals_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms);
+/* with enable != 0 the filter launch of every later dvo_amd_pyramid_filter_depth and dvo_amd_pyramid_filter_depth_many on `device`
+ * is bracketed by two events on the device's internal stream (the launch alone: not the tables' upload, not the pyramids' build);
+ * *last_ms (may be NULL) receives the device time of the most recent bracketed launch */
+int dvo_amd_debug_depth_filter_timing(int device, int enable, double *last_ms);
 
 #ifdef __cplusplus
 }
