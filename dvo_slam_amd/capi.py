@@ -65,6 +65,8 @@ EXPORTS = [
     "dvo_amd_write_pcd_normals", "dvo_amd_debug_normals_timing",
     "dvo_amd_default_depth_filter_options", "dvo_amd_pyramid_filter_depth", "dvo_amd_pyramid_filter_depth_many",
     "dvo_amd_debug_depth_filter_timing",
+    "dvo_amd_default_component_options", "dvo_amd_mask_filter_components", "dvo_amd_mask_filter_components_many",
+    "dvo_amd_mask_components", "dvo_amd_debug_components_timing",
 ]
 
 
@@ -192,6 +194,20 @@ DEPTH_FILTER_MAX_RADIUS = 8
 # one record of dvo_amd_pyramid_filter_depth's counts, field for field
 DEPTH_FILTER_COUNTS = ("with_depth", "kept", "dropped", "holes", "filled")
 DEPTH_FILTER_DTYPE = np.dtype([(name, np.int64) for name in DEPTH_FILTER_COUNTS])
+
+
+class ComponentOptions(C.Structure):
+    """dvo_amd_component_options, field for field"""
+    _fields_ = [("connectivity", C.c_int), ("max_step", C.c_float), ("depth_sigmas", C.c_float), ("min_area", C.c_int * MAX_LEVELS),
+                ("max_area", C.c_int * MAX_LEVELS), ("keep_largest", C.c_int)]
+
+
+COMPONENTS_MAX_LARGEST = 8
+COMPONENTS_FIRST_CAPACITY = 4096  # records the binding makes room for in its first dvo_amd_mask_components call
+# one record of dvo_amd_mask_filter_components' counts and one dvo_amd_component, field for field
+COMPONENT_COUNTS = ("foreground", "components", "kept_components", "kept_pixels", "largest_area", "edges_cut")
+COMPONENT_COUNTS_DTYPE = np.dtype([(name, np.int64) for name in COMPONENT_COUNTS])
+COMPONENT_DTYPE = np.dtype([(name, np.int32) for name in ("root", "area", "x0", "y0", "x1", "y1", "seeded")])
 
 
 class NormalOptions(C.Structure):
@@ -453,6 +469,13 @@ def lib():
     L.dvo_amd_pyramid_filter_depth_many.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(DepthFilterOptions), C.POINTER(vp),
                                                     C.POINTER(C.c_longlong), C.POINTER(vp)]
     L.dvo_amd_debug_depth_filter_timing.argtypes = [C.c_int, C.c_int, dp]
+    L.dvo_amd_default_component_options.argtypes = [C.POINTER(ComponentOptions)]
+    L.dvo_amd_default_component_options.restype = None
+    L.dvo_amd_mask_filter_components.argtypes = [vp, vp, vp, C.POINTER(ComponentOptions), C.POINTER(vp), C.POINTER(C.c_longlong)]
+    L.dvo_amd_mask_filter_components_many.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(ComponentOptions),
+                                                      C.POINTER(vp), C.POINTER(C.c_longlong)]
+    L.dvo_amd_mask_components.argtypes = [vp, vp, vp, C.POINTER(ComponentOptions), C.c_int, ip, vp, C.c_int, ip]
+    L.dvo_amd_debug_components_timing.argtypes = [C.c_int, C.c_int, dp]
     L.dvo_amd_default_normal_options.argtypes = [C.POINTER(NormalOptions)]
     L.dvo_amd_default_normal_options.restype = None
     L.dvo_amd_pyramid_normals.argtypes = [vp, C.c_int, C.POINTER(NormalOptions), fp, fp, C.POINTER(C.c_longlong)]
@@ -702,6 +725,48 @@ def rigid_inverse(T) -> np.ndarray:
             out[i, j] = T[j, i]
         out[i, 3] = -((T[0, i] * T[0, 3] + T[1, i] * T[1, 3]) + T[2, i] * T[2, 3])
     return out
+
+
+def level_areas(a0: int, levels: int) -> list:
+    """An area in pixels of level 0 as per-level areas for SelectionMask.filter_components: level l has a quarter of the pixels of
+    level l - 1, so it gets max(1, ceil(a0 / 4^l))."""
+    return [max(1, -(-int(a0) // 4 ** l)) for l in range(levels)]
+
+
+def component_options(**options) -> ComponentOptions:
+    """dvo_amd_default_component_options (connectivity 8, max_step 0, depth_sigmas 10, every min_area 0, every max_area -1,
+    keep_largest 0) with the given fields replaced.  min_area / max_area: one value for every level, or one per level."""
+    opt = ComponentOptions()
+    lib().dvo_amd_default_component_options(C.byref(opt))
+    for k, v in options.items():
+        if k in ("min_area", "max_area"):
+            per_level = [int(a) for a in v] if hasattr(v, "__len__") else [int(v)] * MAX_LEVELS
+            if len(per_level) > MAX_LEVELS:
+                raise ValueError(f"{k}: more than {MAX_LEVELS} levels")
+            for l, a in enumerate(per_level):
+                getattr(opt, k)[l] = a
+        elif k in ("connectivity", "keep_largest"):
+            setattr(opt, k, int(v))
+        elif k in ("max_step", "depth_sigmas"):
+            setattr(opt, k, float(v))
+        else:
+            raise TypeError(f"unknown component option {k!r}")
+    return opt
+
+
+def _component_options(options, fields) -> ComponentOptions:
+    if options is not None and fields:
+        raise TypeError("give options= or option fields, not both")
+    return options if options is not None else component_options(**fields)
+
+
+def components_timing(enable: bool = True, device: int = 0) -> float:
+    """(instrumentation) switches the event bracket around every component call (filter_components, filter_components_many,
+    components) of `device` on or off and returns the device time of the most recent bracketed call in ms
+    (dvo_amd_debug_components_timing)"""
+    ms = C.c_double()
+    _check(lib().dvo_amd_debug_components_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_components_timing")
+    return ms.value
 
 
 def mask_ops_timing(enable: bool = True, device: int = 0) -> float:
@@ -1073,6 +1138,56 @@ class SelectionMask:
         mask = cls._own(out, pyramid.device)
         return (mask, cnt[:n].copy()) if counts else mask
 
+    # ---- connected components (the rules are pinned in include/dvo_amd.h under "Mask components")
+
+    def filter_components(self, depth=None, seeds=None, counts: bool = False, options=None, **fields):
+        """The components of this mask -- cut further by the depth of the pyramid `depth` when given -- that pass the area band,
+        touch `seeds` when given and are among the keep_largest largest when asked (dvo_amd_mask_filter_components).  fields:
+        component_options' (connectivity, max_step, depth_sigmas, min_area, max_area, keep_largest).  Returns the mask, or with
+        counts=True (mask, counts): one COMPONENT_COUNTS_DTYPE record per level."""
+        masks, cnt = SelectionMask.filter_components_many([self], [depth], [seeds], counts=True, options=options, **fields)
+        return (masks[0], cnt[0]) if counts else masks[0]
+
+    @staticmethod
+    def filter_components_many(masks, depths=None, seeds=None, counts: bool = False, options=None, **fields):
+        """n component filters in one call of five kernel launches (dvo_amd_mask_filter_components_many): item k is masks[k] (a
+        SelectionMask or None), depths[k] (an RgbdImagePyramid or None) and seeds[k] (a SelectionMask or None); depths and seeds
+        may be None altogether.  Returns the list of masks, or with counts=True (masks, [counts of item k: one
+        COMPONENT_COUNTS_DTYPE record per level])."""
+        n = len(masks)
+        depths = [None] * n if depths is None else list(depths)
+        seeds = [None] * n if seeds is None else list(seeds)
+        if not (len(depths) == len(seeds) == n):
+            raise ValueError("one depth pyramid (or None) and one seed mask (or None) per mask")
+        opt = _component_options(options, fields)
+        vp = C.c_void_p
+        handles = lambda items: (vp * max(1, n))(*[None if i is None else i._h for i in items])  # noqa: E731
+        levels, devices = [], []
+        for m, d in zip(masks, depths):
+            levels.append(m.info()["levels"] if m is not None else d.levels() if d is not None else 0)
+            devices.append(m.device if m is not None else d.device if d is not None else 0)
+        cnt = np.zeros(max(1, sum(levels)), COMPONENT_COUNTS_DTYPE)
+        out = (vp * max(1, n))()
+        _check(lib().dvo_amd_mask_filter_components_many(n, handles(masks), handles(depths), handles(seeds), C.byref(opt), out,
+                                                         cnt.ctypes.data_as(C.POINTER(C.c_longlong))),
+               "dvo_amd_mask_filter_components_many")
+        made = [SelectionMask._own(vp(out[k]), devices[k]) for k in range(n)]
+        if not counts:
+            return made
+        at = np.concatenate([[0], np.cumsum(levels)]).astype(int)
+        return made, [cnt[at[k]:at[k + 1]].copy() for k in range(n)]
+
+    def components(self, level: int, depth=None, seeds=None, options=None, **fields):
+        """One level's components (dvo_amd_mask_components): (labels, records) -- labels int32 [h >> level, w >> level], root + 1
+        on a component's pixels and 0 on the background; records a COMPONENT_DTYPE array in ascending root order.  Of the options
+        only the edge rule (connectivity, max_step, depth_sigmas) is read."""
+        return _components(self, depth, seeds, level, _component_options(options, fields))
+
+    def reconstruct(self, seeds):
+        """The components of this mask that `seeds` still touches: with seeds = self.erode(r), an erosion's speckle removal
+        without its loss of shape.  Shorthand for filter_components(seeds=seeds)."""
+        return self.filter_components(seeds=seeds)
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
@@ -1092,6 +1207,31 @@ class SelectionMask:
         out = np.empty((i["height"] >> level, i["width"] >> level), np.uint8)
         _check(lib().dvo_amd_mask_download(self._h, level, out.ctypes.data_as(C.POINTER(C.c_ubyte))), "dvo_amd_mask_download")
         return out
+
+
+def _components(mask, depth, seeds, level, opt):
+    """dvo_amd_mask_components for a mask (or None) and a depth pyramid (or None): one call with room for COMPONENTS_FIRST_CAPACITY
+    records, a second one only when the level has more components than that"""
+    if mask is not None:
+        i = mask.info()
+        w, h = (i["width"] >> level, i["height"] >> level) if 0 <= level < i["levels"] else (0, 0)  # (the library refuses it)
+    elif depth is not None:
+        w, h, _ = depth.level_info(level) if 0 <= level < depth.levels() else (0, 0, None)
+    else:
+        w = h = 0
+    args = (None if mask is None else mask._h, None if depth is None else depth._h, None if seeds is None else seeds._h, C.byref(opt),
+            int(level))
+    labels = np.zeros((max(h, 0), max(w, 0)), np.int32)
+    n = C.c_int()
+    records = np.zeros(COMPONENTS_FIRST_CAPACITY, COMPONENT_DTYPE)
+    _check(lib().dvo_amd_mask_components(*args, labels.ctypes.data_as(C.POINTER(C.c_int)), records.ctypes.data_as(C.c_void_p),
+                                         len(records), C.byref(n)), "dvo_amd_mask_components")
+    if n.value > len(records):  # more components than the first call had room for: once more, for the records alone
+        records = np.zeros(n.value, COMPONENT_DTYPE)
+        _check(lib().dvo_amd_mask_components(*args, None, records.ctypes.data_as(C.c_void_p), n.value, C.byref(n)),
+               "dvo_amd_mask_components")
+    records = records[:n.value].copy()
+    return labels, records
 
 
 @dataclasses.dataclass
@@ -1392,6 +1532,16 @@ class RgbdImagePyramid:
         DEPTH_FILTER_DTYPE record); with support=True also the support plane (uint16 [h, w]) -- as a tuple, in this order."""
         got = filter_depth_many([self], options, counts=counts, support=support)
         return tuple(part[0] for part in got) if counts or support else got[0]
+
+    def depth_components(self, seeds=None, counts: bool = False, level=None, options=None, **fields):
+        """The depth-connected surfaces of this pyramid, the mask = None form of the component entries: every pixel with a finite
+        depth is foreground and the depth rule cuts the edges.  level=None: SelectionMask.filter_components' result (the mask of
+        the kept surfaces, with counts=True also the counts); level=l: SelectionMask.components' (labels, records) of that level."""
+        opt = _component_options(options, fields)
+        if level is not None:
+            return _components(None, self, seeds, level, opt)
+        masks, cnt = SelectionMask.filter_components_many([None], [self], [seeds], counts=True, options=opt)
+        return (masks[0], cnt[0]) if counts else masks[0]
 
     def normals(self, level: int = 0, options=None, **fields):
         """The surface normals of a level (dvo_amd_pyramid_normals; the rule is pinned in include/dvo_amd.h under "Surface

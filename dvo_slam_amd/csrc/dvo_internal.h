@@ -24,6 +24,7 @@
 
 #include <atomic>
 #include <cmath>
+#include <cstddef>
 #include <deque>
 #include <memory>
 #include <mutex>
@@ -161,6 +162,15 @@ struct dvo_amd_mask {
   int *counters = nullptr;                        // device, [levels]: where the kernels count the kept pixels
   long long kept[DVO_AMD_MAX_LEVELS] = {};
 };
+
+// tests/test_mask_components.py hands the argument checks of the component entries stand-ins for a mask and a pyramid that hold
+// just the fields those checks read, at these offsets (_MaskHead, _PyramidHead): whoever moves a field moves it there too
+static_assert(sizeof(std::atomic<int>) == 4 && offsetof(dvo_amd_mask, device) == 4 && offsetof(dvo_amd_mask, w) == 8 &&
+                  offsetof(dvo_amd_mask, h) == 12 && offsetof(dvo_amd_mask, levels) == 16,
+              "the head of dvo_amd_mask as tests/test_mask_components.py restates it");
+static_assert(offsetof(dvo_amd_pyramid, device) == 4 && offsetof(dvo_amd_pyramid, n_levels) == 8 && offsetof(dvo_amd_pyramid, timestamp) == 16 &&
+                  offsetof(dvo_amd_pyramid, lv) == 24 && offsetof(LevelData, w) == 0 && offsetof(LevelData, h) == 4,
+              "the head of dvo_amd_pyramid as tests/test_mask_components.py restates it");
 
 // a raw sensor frame (frame ingest on the device)
 struct RawFrame {

@@ -1493,6 +1493,106 @@ int dvo_amd_point_cloud_normals(dvo_amd_context *ctx, dvo_amd_pyramid *image, in
                                 int bgr_stride_bytes, const dvo_amd_normal_options *opt, dvo_amd_point *out, float *normals);
 int dvo_amd_write_pcd_normals(const char *path, const dvo_amd_point *points, const float *normals, long long n, int width, int height);
 
+/*
+ * Mask components: connected-component labelling of a mask, of a depth plane or of both, with per-component statistics -- on the
+ * device.
+ *
+ * Every producer of masks makes speckle (isolated residual outliers, normals that flicker at grazing angles, single-pixel
+ * disagreements of a warp along depth edges), and dvo_amd_mask_morph's erode removes thin true structure with it.  The entries
+ * below tell a 3-pixel speckle from a 3000-pixel object: they drop components by area, keep the k largest, or keep the
+ * components a trusted (eroded) mask still touches -- an erosion's speckle removal without its loss of shape.  With a pyramid's
+ * depth the same kernels segment a frame into depth-connected surfaces (cv::filterSpeckles' case: a floating blob larger than
+ * dvo_amd_pyramid_filter_depth's window).  Inputs are only read; the result is an ordinary dvo_amd_mask -- immutable,
+ * refcounted, with a serial of its own -- that enters wherever a mask enters.
+ *
+ * Processing.  Each level is processed on its own, from the same level of its inputs, as dvo_amd_mask_morph does.
+ * Foreground.  Pixel i of level l is foreground iff (mask is NULL or mask[l][i] != 0) and (depth is NULL or the depth plane of
+ * level l of the pyramid `depth` is finite at i).  At least one of mask and depth must be given.
+ * Edges.  Two foreground pixels are adjacent under connectivity 4 (left/right, up/down) or 8 (plus the diagonals); nothing wraps
+ * at the plane's border.  Without depth every adjacent foreground pair is an edge.  With depth an adjacent pair (a, b) is an
+ * edge iff, in fp32, every operation rounded on its own, no contraction,
+ *     zn  = fminf(za, zb)
+ *     t   = zn - 0.4f
+ *     tol = max_step + depth_sigmas * (0.0012f + 0.0019f * (t * t))
+ *     fabsf(za - zb) <= tol
+ * which is the project's depthStdDevZ (the mask warp's and the depth fusion's) evaluated at the nearer depth, so that the rule
+ * is symmetric.  Components are the connected components of that undirected graph.  The relation is NOT transitive pixel to
+ * pixel: a ramp whose every step passes is one component, however far apart its ends are.  That is intended -- a floor seen at
+ * a grazing angle is one surface.
+ * Canonical names.  The root of a component is its smallest linear pixel index y * w + x; its label is root + 1; background is
+ * 0.  Every output below is therefore a function of the inputs alone, whatever order the device worked in.
+ * Per-component record.  dvo_amd_component {root, area, x0, y0, x1, y1, seeded}: the inclusive bounding box, and seeded = 1 iff
+ * `seeds` is given and keeps at least one pixel of the component on that level.
+ * Filter.  A component is kept iff all three hold:
+ *     min_area[l] <= area, and max_area[l] < 0 or area <= max_area[l];
+ *     seeds is NULL or the component is seeded;
+ *     keep_largest == 0, or the component is among the first keep_largest of those that passed the two tests before, ordered by
+ *     (area descending, root ascending).
+ * keep_largest ranges over 0 .. DVO_AMD_COMPONENTS_MAX_LARGEST.  The output mask keeps exactly the pixels of kept components; it
+ * has the input's level-0 size and level count (with mask NULL: the pyramid's).
+ * Counts (may be NULL).  One record of DVO_AMD_COMPONENTS_COUNTS long long per level, in item order:
+ *     foreground, components, kept_components, kept_pixels, largest_area, edges_cut
+ * largest_area is the area of the level's largest component, kept or not (0 without any).  edges_cut is the number of adjacent
+ * foreground pairs under the chosen connectivity that the depth rule refused, each pair counted once; 0 without depth.
+ *
+ * Defaults (dvo_amd_default_component_options): connectivity 8, max_step 0, depth_sigmas 10, every min_area 0, every max_area
+ * -1, keep_largest 0 -- with these the call returns the foreground unchanged.  depth_sigmas 10 is a default, not a bar: on the
+ * project's synthetic 160x120 and 80x60 sensor frames 6 was the smallest of {3, 6, 10, 20} at which the smooth room stays one
+ * component (at 3 it shatters into 7 to 28), and 10 leaves a margin over that.
+ *
+ *   dvo_amd_mask_filter_components        one item
+ *   dvo_amd_mask_filter_components_many   n items that may differ in size and level count, as dvo_amd_pyramid_filter_depth_many's;
+ *                                         depths and seeds may be NULL or hold NULL entries, masks may too where the item has a
+ *                                         depth.  All items and levels share every kernel launch: a call is FIVE launches (tile
+ *                                         labelling, seams, flatten + records, selection, write) whatever the content, n or the
+ *                                         level count; nothing comes back to the host between them and the call synchronises
+ *                                         once, at its end.  An item's outputs equal its single call's, bit for bit.
+ *   dvo_amd_mask_components               the inspection entry for one level: the label plane (w * h ints of that level, may be
+ *                                         NULL) and the records in ascending root order.  *n_components is always the true
+ *                                         total; at most `capacity` records are written.  It reads opt only for the edge rule
+ *                                         (connectivity, max_step, depth_sigmas); the other fields are still validated (keep_largest, and
+ *                                         min_area on the levels the item has).
+ * All atomics are integer and the canonical root makes every output order-independent: two runs are bit-identical.
+ * Working memory.  A call labels in 41 bytes per pixel of all its items and levels together (an int32 parent, a 32-byte record,
+ * a work-list entry and an edge byte; each plane rounded up to 256 pixels): 16.7 MB for one 640x480 item of four levels, 1.07 GB
+ * for 64 of them in one call.  It is one area per device, grown to the largest call so far and kept for the life of the process,
+ * as the mask warp's table is -- a caller to whom a gigabyte matters splits a large _many call into smaller ones.
+ *
+ * Errors, all reported before any device work, with *out NULL (every out[k] NULL) on every failure:
+ * DVO_AMD_ERR_INVALID_ARGUMENT, with a reason in dvo_amd_last_error(), for NULL where not allowed (including inside the
+ * arrays), mask and depth both NULL, a connectivity other than 4 or 8, a max_step or depth_sigmas that is not finite or is
+ * negative, min_area[l] < 0 on a level the item has, keep_largest outside its range, a depth or seeds that does not fit the mask
+ * as dvo_amd_pyramid_select_masked checks a mask (another level-0 size, or fewer levels), a level outside the item's levels, a
+ * negative capacity; then DVO_AMD_ERR_DEVICE_MISMATCH; then DVO_AMD_ERR_NO_DEVICE.
+ *
+ * Not covered: no hole-filling of components, no labels cached in a mask, no removal of depth from a pyramid (one tracks behind
+ * the mask), no 3-D connectivity over the map's voxels.
+ */
+#define DVO_AMD_COMPONENTS_MAX_LARGEST 8
+#define DVO_AMD_COMPONENTS_COUNTS 6 /* foreground, components, kept_components, kept_pixels, largest_area, edges_cut */
+typedef struct dvo_amd_component_options {
+  int connectivity;                     /* 4 or 8 */
+  float max_step;                       /* metres added to the depth tolerance; >= 0 */
+  float depth_sigmas;                   /* multiples of depthStdDevZ at the nearer depth; >= 0 */
+  int min_area[DVO_AMD_MAX_LEVELS];     /* per level; >= 0 */
+  int max_area[DVO_AMD_MAX_LEVELS];     /* per level; < 0: no upper bound */
+  int keep_largest;                     /* 0: all that pass; else 1 .. DVO_AMD_COMPONENTS_MAX_LARGEST */
+} dvo_amd_component_options;
+typedef struct dvo_amd_component {
+  int root, area, x0, y0, x1, y1, seeded;
+} dvo_amd_component;
+
+void dvo_amd_default_component_options(dvo_amd_component_options *opt);
+int dvo_amd_mask_filter_components(const dvo_amd_mask *mask, const dvo_amd_pyramid *depth, const dvo_amd_mask *seeds,
+                                   const dvo_amd_component_options *opt, dvo_amd_mask **out,
+                                   long long *counts /* [levels][6] or NULL */);
+int dvo_amd_mask_filter_components_many(int n, const dvo_amd_mask *const *masks, const dvo_amd_pyramid *const *depths,
+                                        const dvo_amd_mask *const *seeds, const dvo_amd_component_options *opt,
+                                        dvo_amd_mask **out /* n */, long long *counts /* packed in item order, or NULL */);
+int dvo_amd_mask_components(const dvo_amd_mask *mask, const dvo_amd_pyramid *depth, const dvo_amd_mask *seeds,
+                            const dvo_amd_component_options *opt, int level, int *labels /* w*h of that level, may be NULL */,
+                            dvo_amd_component *components, int capacity, int *n_components);
+
 /* dvo::core::computeResidualsAndValidFlagsSse (dense_tracking_impl.cpp:400-403) for one level and one float transform
  * (column-major 4x4, reference -> current).  residuals: width*height x 2 floats in pixel order, NaN where the pixel is not
  * selected or its warp is invalid.  Used by the parity tests and by dvo_amd_error_image. */

@@ -768,6 +768,69 @@ class SelectionMask {
     if (counts) counts->assign(records, records + out.info().levels);
     return out;
   }
+  // Connected components (dvo_amd.h, "Mask components"): what tells a 3-pixel speckle from a 3000-pixel object.
+  //   filterComponents(options, depth, seeds)   the components of this mask -- cut further by the depth rule where `depth` is
+  //                                             given -- that pass the options' area band, touch `seeds` where given and are
+  //                                             among the keep_largest largest where asked
+  //   reconstruct(seeds)                        the components `seeds` still touches: with seeds = eroded(r), an erosion's speckle
+  //                                             removal without its loss of shape
+  //   components(level, labels, ...)            one level's records in ascending root order, and its label plane (root + 1, 0 =
+  //                                             background) where `labels` is given
+  //   depthComponents(pyramid, options, seeds)  the mask-less form: the depth-connected surfaces of a pyramid
+  // A pyramid holds its levels (RgbdImagePyramid::build; a match has built them).
+  struct ComponentOptions : dvo_amd_component_options {
+    ComponentOptions() { dvo_amd_default_component_options(this); }
+    // an area in pixels of level 0 on every level, max(1, ceil(a0 / 4^l)): level l has a quarter of the pixels of level l - 1
+    static int levelArea(int a0, int level) {
+      const long long q = 1ll << (2 * level), a = ((long long)a0 + q - 1) / q;
+      return a < 1 ? 1 : (int)a;
+    }
+    ComponentOptions &minArea(int a0) {
+      for (int l = 0; l < DVO_AMD_MAX_LEVELS; ++l) min_area[l] = levelArea(a0, l);
+      return *this;
+    }
+    ComponentOptions &maxArea(int a0) {
+      for (int l = 0; l < DVO_AMD_MAX_LEVELS; ++l) max_area[l] = levelArea(a0, l);
+      return *this;
+    }
+  };
+  struct ComponentCounts {  // one level's record
+    long long foreground, components, kept_components, kept_pixels, largest_area, edges_cut;
+  };
+  typedef dvo_amd_component Component;
+  SelectionMask filterComponents(const ComponentOptions &options = ComponentOptions(), const RgbdImagePyramid *depth = nullptr,
+                                 const SelectionMask *seeds = nullptr, std::vector<ComponentCounts> *counts = nullptr) const {
+    return filtered(need(), depth, seeds, options, device_, counts, "SelectionMask::filterComponents");
+  }
+  SelectionMask reconstruct(const SelectionMask &seeds) const {
+    return filtered(need(), nullptr, &seeds, ComponentOptions(), device_, nullptr, "SelectionMask::reconstruct");
+  }
+  static SelectionMask depthComponents(const RgbdImagePyramid &pyramid, const ComponentOptions &options = ComponentOptions(),
+                                       const SelectionMask *seeds = nullptr, std::vector<ComponentCounts> *counts = nullptr) {
+    return filtered(nullptr, &pyramid, seeds, options, pyramid.device(), counts, "SelectionMask::depthComponents");
+  }
+  std::vector<Component> components(int level, std::vector<int> *labels = nullptr, const ComponentOptions &options = ComponentOptions(),
+                                    const RgbdImagePyramid *depth = nullptr, const SelectionMask *seeds = nullptr) const {
+    const char *where = "SelectionMask::components";
+    const Info i = info();
+    if (level < 0 || level >= i.levels) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+    if (labels) labels->assign((size_t)(i.width >> level) * (size_t)(i.height >> level), 0);
+    // one call with room for 4096 records; a second one, for the records alone, only when the level has more components
+    std::vector<Component> records(4096);
+    int n = 0;
+    detail::check(dvo_amd_mask_components(need(), depth ? depth->handle() : nullptr, seeds ? seeds->need() : nullptr, &options, level,
+                                          labels ? labels->data() : nullptr, records.data(), (int)records.size(), &n),
+                  where);
+    if ((size_t)n > records.size()) {
+      records.resize((size_t)n);
+      detail::check(dvo_amd_mask_components(need(), depth ? depth->handle() : nullptr, seeds ? seeds->need() : nullptr, &options, level,
+                                            nullptr, records.data(), n, &n),
+                    where);
+    }
+    records.resize((size_t)n);
+    return records;
+  }
+
   // (R^T, -R^T t) of a rigid transformation, every sum in this order: the inverse the Python binding and the C example form too,
   // so that all three hand the library the same sixteen doubles
   static AffineTransformd rigidInverse(const AffineTransformd &transformation) {
@@ -816,6 +879,19 @@ class SelectionMask {
     dvo_amd_mask *m = nullptr;
     detail::check(dvo_amd_mask_create_budget(pyramid.handle(), &o, &m), where);
     return SelectionMask(m, pyramid.device());
+  }
+  static SelectionMask filtered(const dvo_amd_mask *mask, const RgbdImagePyramid *depth, const SelectionMask *seeds,
+                                const ComponentOptions &options, int device, std::vector<ComponentCounts> *counts, const char *where) {
+    static_assert(sizeof(ComponentCounts) == DVO_AMD_COMPONENTS_COUNTS * sizeof(long long),
+                  "a ComponentCounts is one record of dvo_amd_mask_filter_components' counts");
+    ComponentCounts records[DVO_AMD_MAX_LEVELS];
+    dvo_amd_mask *m = nullptr;
+    detail::check(dvo_amd_mask_filter_components(mask, depth ? depth->handle() : nullptr, seeds ? seeds->need() : nullptr, &options, &m,
+                                                 &records[0].foreground),
+                  where);
+    SelectionMask out(m, device);
+    if (counts) counts->assign(records, records + out.info().levels);
+    return out;
   }
   SelectionMask combine(const SelectionMask *other, int op, const char *where) const {
     dvo_amd_mask *m = nullptr;
