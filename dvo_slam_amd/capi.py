@@ -67,6 +67,7 @@ EXPORTS = [
     "dvo_amd_debug_depth_filter_timing",
     "dvo_amd_default_component_options", "dvo_amd_mask_filter_components", "dvo_amd_mask_filter_components_many",
     "dvo_amd_mask_components", "dvo_amd_debug_components_timing",
+    "dvo_amd_default_pose_score_options", "dvo_amd_score_poses", "dvo_amd_score_poses_many", "dvo_amd_rank_poses", "dvo_amd_pose_grid",
 ]
 
 
@@ -176,6 +177,23 @@ class ResidualMaskOptions(C.Structure):
     """dvo_amd_residual_mask_options, field for field"""
     _fields_ = [("precision", (C.c_float * 4) * MAX_LEVELS), ("max_distance", C.c_float * MAX_LEVELS), ("invalid_keep", C.c_int),
                 ("unevaluated_keep", C.c_int)]
+
+
+class PoseScoreOptions(C.Structure):
+    """dvo_amd_pose_score_options, field for field"""
+    _fields_ = [("level", C.c_int), ("precision", C.c_float * 4), ("max_distance", C.c_float), ("invalid_distance", C.c_float)]
+
+
+class PoseGridOptions(C.Structure):
+    """dvo_amd_pose_grid_options, field for field"""
+    _fields_ = [("count", C.c_int * 6), ("step", C.c_double * 6)]
+
+
+# one dvo_amd_pose_score, field for field
+POSE_SCORE_FIELDS = ("evaluated", "invalid", "inlier", "outlier", "cost", "total")
+POSE_SCORE_DTYPE = np.dtype([(name, np.int64) for name in POSE_SCORE_FIELDS[:4]] + [(name, np.uint64) for name in POSE_SCORE_FIELDS[4:]])
+POSE_SCORE_TILE = 32  # hypotheses a block of k_score_poses takes per visit (kPoseScoreTile, dvo_types.h)
+POSE_GRID_AXES = ("vx", "vy", "vz", "wx", "wy", "wz")
 
 
 class FuseOptions(C.Structure):
@@ -455,6 +473,12 @@ def lib():
                                               C.POINTER(C.POINTER(C.c_float))]
     L.dvo_amd_mask_from_residuals_many.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(ResidualMaskOptions),
                                                    C.POINTER(vp), C.POINTER(C.c_longlong)]
+    L.dvo_amd_default_pose_score_options.argtypes = [C.POINTER(PoseScoreOptions)]
+    L.dvo_amd_default_pose_score_options.restype = None
+    L.dvo_amd_score_poses.argtypes = [vp, vp, vp, C.c_int, dp, C.POINTER(PoseScoreOptions), vp]
+    L.dvo_amd_score_poses_many.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), ip, dp, C.POINTER(PoseScoreOptions), vp]
+    L.dvo_amd_rank_poses.argtypes = [vp, C.c_int, C.c_int, ip, ip]
+    L.dvo_amd_pose_grid.argtypes = [C.POINTER(PoseGridOptions), dp, dp, C.c_int, ip]
     L.dvo_amd_default_fuse_options.argtypes = [C.POINTER(FuseOptions)]
     L.dvo_amd_default_fuse_options.restype = None
     L.dvo_amd_pyramid_fuse_depth.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
@@ -713,6 +737,60 @@ def residual_mask_options(result=None, levels: int = MAX_LEVELS, max_distance=RE
             P = np.asarray(ran[nearest], np.float64)
             opt.precision[l][:] = [P[0, 0], P[1, 0], P[0, 1], P[1, 1]]  # column-major
     return opt
+
+
+def pose_score_options(level: int, precision=None, result=None, max_distance=None, invalid_distance=None) -> PoseScoreOptions:
+    """dvo_amd_default_pose_score_options (max_distance 9.2103, invalid_distance = max_distance) for `level`.  precision: a 2x2
+    matrix, or four floats column-major.  With result= and no precision the level takes its precision from a `Result` as
+    residual_mask_options does: the TDistributionPrecision of the last iteration of the nearest level that ran.  Neither leaves
+    it unset (the library refuses that)."""
+    opt = PoseScoreOptions()
+    lib().dvo_amd_default_pose_score_options(C.byref(opt))
+    opt.level = int(level)
+    if precision is not None:
+        P = np.asarray(precision, np.float64)
+        opt.precision[:] = [P[0, 0], P[1, 0], P[0, 1], P[1, 1]] if P.shape == (2, 2) else [float(v) for v in P.ravel()]
+    elif result is not None:
+        if not 0 <= int(level) < MAX_LEVELS:
+            raise ValueError(f"level must be 0..{MAX_LEVELS - 1}")
+        opt.precision[:] = list(residual_mask_options(result, int(level) + 1).precision[int(level)])
+    if max_distance is not None:
+        opt.max_distance = float(max_distance)
+    if invalid_distance is not None:
+        opt.invalid_distance = float(invalid_distance)
+    return opt
+
+
+def pose_grid(T_centre=None, **axes) -> np.ndarray:
+    """The hypotheses Exp(xi) * T_centre of a grid over xi = (vx, vy, vz, wx, wy, wz) (dvo_amd_pose_grid), as an array [n, 4, 4]
+    of row-major 4x4 matrices.  axes: vx=(count, step), ...: count odd, the values (-(count - 1) / 2 ... (count - 1) / 2) * step; an
+    axis not given has the one value 0.  wz runs fastest, vx slowest; the middle entry is T_centre itself, bit for bit."""
+    opt = PoseGridOptions()
+    for a, name in enumerate(POSE_GRID_AXES):
+        opt.count[a], opt.step[a] = 1, 0.0
+    for name, (count, step) in axes.items():
+        if name not in POSE_GRID_AXES:
+            raise TypeError(f"unknown grid axis {name!r}")
+        a = POSE_GRID_AXES.index(name)
+        opt.count[a], opt.step[a] = int(count), float(step)
+    Tc = _pose_cm(np.eye(4) if T_centre is None else T_centre)
+    dp = C.POINTER(C.c_double)
+    n = C.c_int()
+    _check(lib().dvo_amd_pose_grid(C.byref(opt), Tc.ctypes.data_as(dp), None, 0, C.byref(n)), "dvo_amd_pose_grid")
+    out = np.empty((n.value, 4, 4), np.float64)
+    _check(lib().dvo_amd_pose_grid(C.byref(opt), Tc.ctypes.data_as(dp), out.ctypes.data_as(dp), n.value, C.byref(n)), "dvo_amd_pose_grid")
+    return np.ascontiguousarray(out.transpose(0, 2, 1))
+
+
+def rank_poses(scores, k: int) -> np.ndarray:
+    """The indices of the min(k, len(scores)) records of smallest total, smallest first, ties to the lower index
+    (dvo_amd_rank_poses; host-only)."""
+    scores = np.ascontiguousarray(scores, POSE_SCORE_DTYPE)
+    order = np.zeros(max(1, min(int(k), len(scores))), np.int32)
+    n = C.c_int()
+    _check(lib().dvo_amd_rank_poses(scores.ctypes.data_as(C.c_void_p), len(scores), int(k), order.ctypes.data_as(C.POINTER(C.c_int)),
+                                    C.byref(n)), "dvo_amd_rank_poses")
+    return order[:n.value].copy()
 
 
 def rigid_inverse(T) -> np.ndarray:
@@ -1934,6 +2012,30 @@ class DenseTracker:
             T0 = T0a.ctypes.data_as(C.POINTER(C.c_double))
         _check(lib().dvo_amd_match_sharded(self._h, reference._h, current._h, T0, C.byref(res[0])), "dvo_amd_match_sharded")
         return Result(res[0], its[0])
+
+    def score_poses(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, Ts, options: PoseScoreOptions) -> np.ndarray:
+        """One POSE_SCORE_DTYPE record per hypothesis Ts[j] (4x4, reference -> current, the estimate) of the pair at
+        options.level (dvo_amd_score_poses; the rule is pinned in include/dvo_amd.h under "Pose scoring")."""
+        return self.score_poses_many([reference], [current], [Ts], [options])[0]
+
+    def score_poses_many(self, references, currents, Ts, options) -> list:
+        """n pairs in one call of two kernel launches (dvo_amd_score_poses_many): pair k is (references[k], currents[k]) under
+        the hypotheses Ts[k] ([m_k, 4, 4]) and options[k].  Returns [the POSE_SCORE_DTYPE records of pair k]."""
+        n = len(references)
+        if not (len(currents) == len(Ts) == len(options) == n):
+            raise ValueError("one current, one set of transformations and one option set per reference")
+        vp = C.c_void_p
+        stacks = [np.asarray(t, np.float64).reshape(-1, 4, 4) for t in Ts]
+        m = np.array([len(t) for t in stacks] + [0], np.int32)[:max(1, n)]
+        T = np.ascontiguousarray(np.concatenate(stacks).transpose(0, 2, 1) if n else np.zeros((0, 4, 4)))
+        opts = (PoseScoreOptions * max(1, n))(*options)
+        scores = np.zeros(max(1, len(T)), POSE_SCORE_DTYPE)
+        _check(lib().dvo_amd_score_poses_many(self._h, n, (vp * max(1, n))(*[p._h for p in references]),
+                                              (vp * max(1, n))(*[p._h for p in currents]), m.ctypes.data_as(C.POINTER(C.c_int)),
+                                              T.ctypes.data_as(C.POINTER(C.c_double)), opts, scores.ctypes.data_as(vp)),
+               "dvo_amd_score_poses_many")
+        at = np.concatenate([[0], np.cumsum(m[:n])]).astype(int)
+        return [scores[at[k]:at[k + 1]].copy() for k in range(n)]
 
     def residuals(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, level: int, T, mask: "SelectionMask | None" = None):
         """computeResidualsAndValidFlagsSse: (residuals[h, w, 2] with NaN = invalid, n_valid).  mask (test entry,

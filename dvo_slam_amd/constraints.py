@@ -298,6 +298,28 @@ def proposalsForCandidates(keyframe: Keyframe, candidates: list) -> list:
     return out
 
 
+def seed_proposals(tracker: capi.DenseTracker, keyframes: list, keyframe: Keyframe, candidates: list, grid, options, k: int = 1) -> list:
+    """Proposals whose starts come from pose scoring (include/dvo_amd.h, "Pose scoring") instead of the poses: for every candidate
+    the hypotheses of `grid` ([m, 4, 4], reference -> current, usually capi.pose_grid() around identity) are scored for the pair
+    (keyframe, candidate) in ONE dvo_amd_score_poses_many call, and the k of smallest total become the candidate's proposals, best
+    first, each with its hypothesis as InitialTransformation.  candidates: Keyframe objects, or positions in `keyframes` (what
+    the place index returns).  options: one capi.PoseScoreOptions for all candidates, or one per candidate.  The list feeds
+    ConstraintProposalValidator.validate unchanged, next to proposalsForCandidates; which proposal is a closure is the
+    validator's decision, not this function's."""
+    cands = [c if isinstance(c, Keyframe) else keyframes[int(c)] for c in candidates]
+    if not cands:
+        return []
+    grid = np.asarray(grid, np.float64).reshape(-1, 4, 4)
+    opts = list(options) if isinstance(options, (list, tuple)) else [options] * len(cands)
+    if len(opts) != len(cands):
+        raise ValueError("one option set for all candidates or one per candidate")
+    scores = tracker.score_poses_many([keyframe.image] * len(cands), [c.image for c in cands], [grid] * len(cands), opts)
+    out = []
+    for c, s in zip(cands, scores):
+        out.extend(ConstraintProposal(keyframe, c, grid[j]) for j in capi.rank_poses(s, k))
+    return out
+
+
 # ---- keyframe_constraint_search.h ------------------------------------------------------------------------------------------
 class NearestNeighborConstraintSearch:
     """dvo_slam::NearestNeighborConstraintSearch (keyframe_constraint_search.h:35-58): the keyframes within max_distance of

@@ -2512,6 +2512,128 @@ hipError_t launch_residual_mask(const ResidualMaskRecord *records, int n_records
   return hipGetLastError();
 }
 
+// ---- pose scoring (dvo_amd_score_poses, dvo_pose_score.cpp; the rule is pinned in include/dvo_amd.h under "Pose scoring") ---------
+// k_score_q3: one block per (reference, level) of a call.  What Q3 takes out of a level -- the last evaluated pixel, if their
+// number is odd -- depends on the reference alone, not on the pose: it is found once, ahead of the scoring kernel on the same
+// stream, and k_score_poses reads it as an index.  There is no hand-off between blocks anywhere in this feature.
+__global__ void __launch_bounds__(kResidualMaskBlock) k_score_q3(PoseScoreLevel *__restrict__ levels) {
+  constexpr int kWaves = kResidualMaskBlock / kWave;
+  __shared__ int s_cnt[kWaves], s_last[kWaves];
+  PoseScoreLevel &L = levels[blockIdx.x];
+  const int n = L.n;
+  const float *z = L.z;
+  const float2 *zd = L.zd;
+  int cnt = 0, last = -1;
+  for (int i = threadIdx.x; i < n; i += kResidualMaskBlock) {  // (i grows: the last hit of a lane is its largest)
+    const float zi = z[i];
+    const float2 g = zd[i];
+    const bool evaluated = (zi == zi) && (g.x == g.x) && (g.y == g.y);
+    cnt += evaluated ? 1 : 0;
+    last = evaluated ? i : last;
+  }
+#pragma unroll
+  for (int m = kWave / 2; m >= 1; m >>= 1) {
+    cnt += __shfl_xor(cnt, m, kWave);
+    const int o = __shfl_xor(last, m, kWave);
+    last = o > last ? o : last;
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) s_cnt[threadIdx.x >> 6] = cnt, s_last[threadIdx.x >> 6] = last;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0, l = -1;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) c += s_cnt[w], l = s_last[w] > l ? s_last[w] : l;
+    L.q3 = (c & 1) ? l : -1;
+  }
+}
+
+// k_score_poses: ONE launch over all (pair, hypothesis tile) items of a call.  blockIdx.x is a chunk of the reference level as in
+// k_residual_mask, blockIdx.y strides over the items.  A lane loads its four pixels once and keeps them in registers; per
+// hypothesis only the twelve floats of K T change, read through the constant address space (wave-uniform: scalar registers), and
+// residual_mask_pixels<4> -- k_residual_mask's residual stage and verdict, rounding-mode fencing included -- runs on the same
+// registers again.  Every sum is an integer: counts by ballots, the wave's cost in 32 bits (a lane adds four q <= 2^20, a wave at
+// most 2^28, a block 2^30), per wave into LDS, and one 64-bit atomic per non-zero sum per (block, hypothesis) at the tile's end.
+__global__ void __launch_bounds__(kResidualMaskBlock) k_score_poses(const PoseScoreRecord *__restrict__ records,
+                                                                    const int2 *__restrict__ items, int n_items) {
+  constexpr int kWaves = kResidualMaskBlock / kWave, kLanePixels = kResidualMaskLanePixels;
+  static_assert(kPoseScoreTile * kPsWords <= kResidualMaskBlock, "one lane per (hypothesis, sum) of a tile");
+  __shared__ unsigned s_sum[kWaves][kPoseScoreTile][kPsWords];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x >> 6;
+  for (int it = blockIdx.y; it < n_items; it += gridDim.y) {
+    const int2 item = items[it];  // uniform over the block
+    const PoseScoreRecord R = records[item.x];
+    if (blockIdx.x * kResidualMaskChunk >= R.n) continue;  // (block-uniform)
+    const LevelPairDesc d = residual_mask_desc(R.cur);
+    const int p0 = (blockIdx.x * kResidualMaskBlock + threadIdx.x) * kLanePixels;
+    const bool live = p0 < R.n;  // (n is a multiple of 4: four pixels or none, all in one row)
+    const float qnan = u2f(0x7fc00000u);
+    float z[kLanePixels] = {qnan, qnan, qnan, qnan}, zx[kLanePixels] = {qnan, qnan, qnan, qnan}, zy[kLanePixels] = {qnan, qnan, qnan, qnan};
+    float ri[kLanePixels] = {0.f, 0.f, 0.f, 0.f}, tx[kLanePixels] = {0.f, 0.f, 0.f, 0.f};
+    float ty = 0.f;
+    if (live) {
+      const float4 z4 = *(const float4 *)(R.z + p0), i4 = *(const float4 *)(R.ri + p0);
+      const float4 za = *(const float4 *)(R.zd + p0), zb = *(const float4 *)(R.zd + p0 + 2);
+      z[0] = z4.x, z[1] = z4.y, z[2] = z4.z, z[3] = z4.w;
+      ri[0] = i4.x, ri[1] = i4.y, ri[2] = i4.z, ri[3] = i4.w;
+      zx[0] = za.x, zy[0] = za.y, zx[1] = za.z, zy[1] = za.w, zx[2] = zb.x, zy[2] = zb.y, zx[3] = zb.z, zy[3] = zb.w;
+      const int v = p0 / R.w, u0 = p0 - v * R.w;
+#pragma unroll
+      for (int k = 0; k < kLanePixels; ++k) tx[k] = R.tx[u0 + k];
+      ty = R.ty[v];
+    }
+    const int q3 = R.level->q3;  // (written by k_score_q3, a launch earlier on this stream)
+    const int j0 = item.y, j1 = j0 + kPoseScoreTile < R.m ? j0 + kPoseScoreTile : R.m;
+    for (int j = j0; j < j1; ++j) {
+      const DVO_CONST float *ktc = (const DVO_CONST float *)(R.kt + 12 * (size_t)j);
+      float kt[12];
+#pragma unroll
+      for (int i = 0; i < 12; ++i) kt[i] = ktc[i];
+      int cls[kLanePixels];
+      float dist[kLanePixels];
+      residual_mask_pixels<kLanePixels>(d, kt, R.P, R.max_distance, z, zx, zy, ri, tx, ty, cls, dist);  // (no pixel: z NaN, unevaluated)
+      unsigned n_invalid = 0u, n_inlier = 0u, n_outlier = 0u, cost = 0u;
+#pragma unroll
+      for (int k = 0; k < kLanePixels; ++k) {
+        const int c = (cls[k] >= 0 && p0 + k == q3) ? (int)kRmInvalid : cls[k];  // Q3
+        n_invalid += (unsigned)__popcll(__ballot(c == (int)kRmInvalid));
+        n_inlier += (unsigned)__popcll(__ballot(c == (int)kRmInlier));
+        n_outlier += (unsigned)__popcll(__ballot(c == (int)kRmOutlier));
+        // q(d) = floor(d * 1024): the product is exact (a power of two, d <= max_distance <= 1024); a negative d -- a precision
+        // that is not positive semidefinite -- costs 0
+        const unsigned q = (unsigned)__builtin_floorf(__builtin_fmaxf(dist[k], 0.0f) * 1024.0f);
+        cost += c == (int)kRmInlier ? q : c == (int)kRmOutlier ? R.q_max : 0u;
+      }
+#pragma unroll
+      for (int m = kWave / 2; m >= 1; m >>= 1) cost += (unsigned)__shfl_xor((int)cost, m, kWave);
+      if (lane == 0) {
+        unsigned *s = s_sum[wave][j - j0];
+        s[kPsInvalid] = n_invalid, s[kPsInlier] = n_inlier, s[kPsOutlier] = n_outlier, s[kPsCost] = cost;
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < (j1 - j0) * kPsWords) {
+      const int jj = threadIdx.x / kPsWords, q = threadIdx.x % kPsWords;
+      unsigned sum = 0u;
+#pragma unroll
+      for (int w = 0; w < kWaves; ++w) sum += s_sum[w][jj][q];
+      if (sum) atomicAdd(R.sums + (size_t)(j0 + jj) * kPsWords + q, (unsigned long long)sum);
+    }
+    __syncthreads();  // (s_sum is written again for the block's next item)
+  }
+}
+
+hipError_t launch_score_poses(PoseScoreLevel *levels, int n_levels, const PoseScoreRecord *records, const int2 *items, int n_items,
+                              int max_n, hipStream_t stream) {
+  LaunchGuard guard;
+  hipLaunchKernelGGL(k_score_q3, dim3((unsigned)n_levels), dim3(kResidualMaskBlock), 0, stream, levels);
+  const unsigned gx = (unsigned)((max_n + kResidualMaskChunk - 1) / kResidualMaskChunk);
+  // as launch_residual_mask: fewer than 2^31 threads, at most 65535 rows of blocks; a block takes further items in steps of gridDim.y
+  const long long fit = (1ll << 31) / ((long long)gx * kResidualMaskBlock);
+  const unsigned gy = (unsigned)std::max<long long>(1, std::min<long long>(std::min<long long>((long long)n_items, 65535), fit));
+  hipLaunchKernelGGL(k_score_poses, dim3(gx, gy), dim3(kResidualMaskBlock), 0, stream, records, items, n_items);
+  return hipGetLastError();
+}
+
 // The selected pixels of a level in scan order, compacted (round 5, end): what the residual pass walks.  The reference compacts
 // too -- PointSelection::select fills a dense array of the selected points (point_selection.cpp:119-152) and computeResidualsSse
 // walks that array -- so the pass's cost follows the selection, not the image.  One exclusive prefix over k_select's per-block

@@ -488,6 +488,38 @@ struct ResidualMaskRecord {
 };
 hipError_t launch_residual_mask(const ResidualMaskRecord *records, int n_records, int max_n, hipStream_t stream);
 
+// ---- pose scoring (dvo_amd_score_poses, dvo_pose_score.cpp; the rule is pinned in include/dvo_amd.h under "Pose scoring").
+// k_score_poses walks the hypotheses of a pair over pixels held in registers: the chunk and the lane's four pixels are
+// k_residual_mask's; a block takes kPoseScoreTile consecutive hypotheses of one record per visit (the tests place m across it).
+constexpr int kPoseScoreTile = 32;
+// the sums of one (pair, hypothesis) on the device, 64-bit each, zeroed before the launch (evaluated is their first three added)
+enum { kPsInvalid = 0, kPsInlier, kPsOutlier, kPsCost, kPsWords = 4 };
+// what is pose-independent of a (reference, level) of the call: k_score_q3 counts the evaluated pixels and leaves the index of the
+// one Q3 takes out -- the last evaluated pixel if their number is odd, else -1 -- for every record that scores that level
+struct PoseScoreLevel {
+  const float *z;    // reference: depth plane of the level
+  const float2 *zd;  // ... its {Zx, Zy} plane (c_b)
+  int n;             // pixels of the level
+  int q3;            // written by k_score_q3
+};
+struct PoseScoreRecord {
+  const float *z;                // reference planes, as ResidualMaskRecord
+  const float2 *zd;
+  const float *ri;
+  const float *tx, *ty;
+  const CurLevelDesc *cur;       // current: the level's descriptor
+  const PoseScoreLevel *level;   // whose q3 this record reads
+  const float *kt;               // m x 12: K * T[0:3,0:4] per hypothesis
+  unsigned long long *sums;      // m x kPsWords
+  int w, n, m;
+  float P[4];                    // column-major 2x2 precision
+  float max_distance;
+  unsigned q_max;                // q(max_distance): what an outlier costs
+};
+// items[i] = (record, first hypothesis of the tile): what blockIdx.y strides over
+hipError_t launch_score_poses(PoseScoreLevel *levels, int n_levels, const PoseScoreRecord *records, const int2 *items, int n_items,
+                              int max_n, hipStream_t stream);
+
 // ---- the place index (dvo_amd_place_*, dvo_place.cpp; the rule is pinned in include/dvo_amd.h under "Place index")
 constexpr int kPlaceBlock = 256;
 // k_place_describe: one block per pyramid; planes[i] is the intensity plane (w x h) of pyramid i, row i of `rows` (dim bytes, dim a

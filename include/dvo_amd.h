@@ -703,6 +703,93 @@ int dvo_amd_mask_from_residuals_many(dvo_amd_context *ctx, int n, const dvo_amd_
                                      long long *counts /* packed in pair order, or NULL */);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Pose scoring: many candidate transformations of a pair scored at one coarse level, on the device -- seeds for loop closures.
+ *
+ * The place index answers "which keyframes look like this frame" without a pose; dvo_amd_match is a local method with a basin of
+ * a few degrees and centimetres.  After drift, or for a tracker that is lost, neither start dvo_amd_proposals_for_candidates
+ * offers lies inside that basin.  dvo_amd_score_poses evaluates a set of hypotheses -- dvo_amd_pose_grid builds the usual one --
+ * and dvo_amd_rank_poses hands the best few to dvo_amd_match or dvo_amd_validate_proposals as initial transformations.  It refines
+ * no pose, estimates no precision and decides no closure.
+ *
+ * dvo_amd_score_poses_many(ctx, n, references, currents, m, T, opts, scores) scores pair k = (references[k], currents[k]) under
+ * m[k] transformations; dvo_amd_score_poses is the case n = 1.  T: 16 doubles per transformation, column-major, reference ->
+ * current (the ESTIMATE, as dvo_amd_mask_from_residuals takes it), packed in pair order: pair 0's m[0], then pair 1's m[1], ...
+ * scores receives one dvo_amd_pose_score per transformation in the same order.  Every transformation is cast to float and turned
+ * into K T exactly as dvo_amd_mask_from_residuals does.  opts[k] gives ONE level (scoring two levels is two calls), the column-
+ * major 2 x 2 precision P of that level, max_distance and invalid_distance.
+ *
+ * The rule, for pair k, hypothesis j and every pixel i of the reference's level, with (class, d) exactly what "Residual masks"
+ * above defines at that T, P and max_distance -- unevaluated / invalid / inlier / outlier, Q3 included: where the number of
+ * evaluated pixels of the level is odd, the last of them in scan order is invalid:
+ *     unevaluated, invalid   cost nothing by themselves
+ *     inlier                 costs q(d)
+ *     outlier                (a NaN d included) costs q(max_distance)
+ *     q(x) = (uint32) floor(x * 1024.0f) in fp32, and 0 for x < 0 (a precision that is not positive semidefinite).  The product is
+ *            exact, so q is a pure function of the bits of d; x <= max_distance <= 1024 gives q <= 2^20.
+ * The record of (k, j):
+ *     evaluated, invalid, inlier, outlier    pixel counts, evaluated = invalid + inlier + outlier
+ *     cost                                   the sum of the pixel costs
+ *     total = cost + invalid * q(invalid_distance)      (a negative invalid_distance: q(max_distance))
+ * Everything is an integer sum: the result does not depend on the order of summation, on the launch geometry or on atomics, and
+ * two runs are bit-identical.  evaluated and the Q3 pixel are properties of the reference level alone, the same for all
+ * hypotheses of a pair: ranking by total is ranking by the mean cost with out-of-view pixels charged invalid_distance, and no
+ * division appears anywhere.
+ *
+ * A call makes two kernel launches (the Q3 pixel of each (reference, level), then all pairs and hypotheses) and synchronises once,
+ * whatever n and m are.  The context gives its device and its reciprocal mode, nothing else: no tracker slot is used, no selection
+ * is built, and the context's queue need not be idle.  The pyramids are only read.
+ *
+ * Errors, before any device is looked for: DVO_AMD_ERR_INVALID_ARGUMENT, with a reason in dvo_amd_last_error() that starts with
+ * the entry's name, for a NULL pointer (inside the arrays too); n < 0; m[k] < 1; more than 2^22 hypotheses in a call; a level that
+ * is negative or that either pyramid lacks; a level of another size in the current (dvo_amd_residuals' check); a precision with a
+ * non-finite entry or all zero (there is no default); max_distance not finite, not > 0 or > 1024; invalid_distance not finite or
+ * > max_distance; a non-finite entry of any T; a context in the host-rcpps reciprocal mode (dvo_amd_set_reciprocal_mode), whose
+ * residual stage this entry does not cover.  Then DVO_AMD_ERR_DEVICE_MISMATCH, then DVO_AMD_ERR_NO_DEVICE.  n == 0 is OK and does
+ * nothing.  On every failure scores is left untouched.
+ *
+ * dvo_amd_rank_poses(scores, m, k, order, n_out): host-only, needs no device.  order receives the min(k, m) indices of smallest
+ * total, smallest first, ties going to the lower index; *n_out their number.
+ *
+ * dvo_amd_pose_grid(opt, T_centre, T_out, capacity, n_out): host-only, needs no device.  opt holds six (count, step) pairs for
+ * xi = (vx, vy, vz, wx, wy, wz), the tangent order of Sophus::SE3d (translation first); every count is odd and >= 1, and axis a
+ * takes the values (-(count[a] - 1) / 2 ... (count[a] - 1) / 2) * step[a].  Hypothesis j is Exp(xi_j) * T_centre in double, 16
+ * doubles column-major; j runs with wz FASTEST and vx SLOWEST:
+ *     j = ((((i_vx * count[1] + i_vy) * count[2] + i_vz) * count[3] + i_wx) * count[4] + i_wy) * count[5] + i_wz
+ * The middle index, (count[0] * ... * count[5] - 1) / 2, is T_centre itself, bit for bit: it does not go through Exp.  *n_out is
+ * the number of hypotheses; with T_out NULL nothing else is done; otherwise capacity (in transformations) must hold them all.
+ * DVO_AMD_ERR_INVALID_ARGUMENT for a NULL opt, T_centre or n_out, an even or non-positive count, a non-finite step or centre, more
+ * than 2^22 hypotheses, a capacity that is too small.
+ *
+ * Not covered: refinement of a pose; tracker state of any kind; the host-rcpps reciprocal mode; more than one level per call; an
+ * estimate of the precision (the caller brings one, e.g. tdist_precision of an earlier alignment at that level); the decision
+ * whether a candidate is a closure, which stays with dvo_amd_validate_proposals.
+ */
+typedef struct dvo_amd_pose_score_options {
+  int level;              /* the level scored: it must exist in both pyramids */
+  float precision[4];     /* column-major 2 x 2, finite, not all zero; no default */
+  float max_distance;     /* finite, > 0, <= 1024 */
+  float invalid_distance; /* finite, <= max_distance; negative: = max_distance */
+} dvo_amd_pose_score_options;
+typedef struct dvo_amd_pose_score {
+  long long evaluated, invalid, inlier, outlier;
+  unsigned long long cost, total;
+} dvo_amd_pose_score;
+typedef struct dvo_amd_pose_grid_options {
+  int count[6];   /* (vx, vy, vz, wx, wy, wz): odd, >= 1 */
+  double step[6]; /* metres, radians */
+} dvo_amd_pose_grid_options;
+/* level 0, precision all 0 (not set), max_distance 9.2103f, invalid_distance -1.0f (= max_distance); a NULL opt is a no-op */
+void dvo_amd_default_pose_score_options(dvo_amd_pose_score_options *opt);
+int dvo_amd_score_poses(dvo_amd_context *ctx, const dvo_amd_pyramid *reference, const dvo_amd_pyramid *current, int m,
+                        const double *T /* m x 16 */, const dvo_amd_pose_score_options *opt, dvo_amd_pose_score *scores /* m */);
+int dvo_amd_score_poses_many(dvo_amd_context *ctx, int n, const dvo_amd_pyramid *const *references,
+                             const dvo_amd_pyramid *const *currents, const int *m /* n */, const double *T /* sum(m) x 16 */,
+                             const dvo_amd_pose_score_options *opts /* n */, dvo_amd_pose_score *scores /* sum(m) */);
+int dvo_amd_rank_poses(const dvo_amd_pose_score *scores, int m, int k, int *order /* min(k, m) */, int *n_out);
+int dvo_amd_pose_grid(const dvo_amd_pose_grid_options *opt, const double *T_centre, double *T_out /* capacity x 16, or NULL */,
+                      int capacity, int *n_out);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Depth fusion: the depth of the frames tracked against a keyframe averaged into the keyframe, on the device.
  *
  * A keyframe's depth plane is one raw sensor frame with that frame's noise, and everything that follows is tracked against it.

@@ -460,6 +460,48 @@ typedef std::shared_ptr<ConstraintProposalValidator> ConstraintProposalValidator
 
 }  // namespace constraints
 
+// Proposals whose starts come from pose scoring (dvo_amd.h, "Pose scoring") instead of the keyframes' poses: what a loop that has
+// drifted, or a tracker that is lost, can hand the validator.  For every candidate the hypotheses of `grid` (reference -> current,
+// usually DenseTracker::poseGrid around the identity) are scored for the pair (keyframe, candidate), all candidates in ONE
+// dvo_amd_score_poses_many call, and the k of smallest total become the candidate's proposals, best first, each with its
+// hypothesis as InitialTransformation.  The list feeds ConstraintProposalValidator::validate unchanged, next to the identity /
+// relative proposals; whether a candidate is a closure stays the validator's decision.
+inline constraints::ConstraintProposalVector seedProposals(dvo::DenseTracker &tracker, const KeyframePtr &keyframe,
+                                                           const KeyframeVector &candidates,
+                                                           const std::vector<dvo::core::AffineTransformd> &grid,
+                                                           const dvo::DenseTracker::PoseScoreOptions &options, int k = 1) {
+  constraints::ConstraintProposalVector out;
+  if (candidates.empty() || grid.empty()) return out;
+  const size_t n = candidates.size(), m = grid.size();
+  const size_t levels = (size_t)(options.level >= 0 ? options.level : 0) + 1;
+  keyframe->image()->compute(levels);
+  std::vector<const dvo_amd_pyramid *> references(n, keyframe->image()->handle()), currents(n);
+  for (size_t c = 0; c < n; ++c) {
+    candidates[c]->image()->compute(levels);
+    currents[c] = candidates[c]->image()->handle();
+  }
+  std::vector<double> T(16 * n * m);
+  for (size_t c = 0; c < n; ++c)
+    for (size_t j = 0; j < m; ++j) std::memcpy(&T[16 * (c * m + j)], dvo::core::data(grid[j]), sizeof(double) * 16);
+  const std::vector<int> counts(n, (int)m);
+  const std::vector<dvo_amd_pose_score_options> opts(n, options);
+  std::vector<dvo_amd_pose_score> scores(n * m);
+  dvo::detail::check(dvo_amd_score_poses_many(tracker.handle(), (int)n, references.data(), currents.data(), counts.data(), T.data(),
+                                              opts.data(), scores.data()),
+                     "seedProposals");
+  std::vector<int> order((size_t)(k > 0 ? k : 0) + 1);
+  for (size_t c = 0; c < n; ++c) {
+    int kept = 0;
+    dvo::detail::check(dvo_amd_rank_poses(&scores[c * m], (int)m, k, order.data(), &kept), "seedProposals");
+    for (int r = 0; r < kept; ++r) {
+      constraints::ConstraintProposalPtr p = constraints::ConstraintProposal::createWithIdentity(keyframe, candidates[c]);
+      p->InitialTransformation = grid[(size_t)order[(size_t)r]];
+      out.push_back(p);
+    }
+  }
+  return out;
+}
+
 // The two alignments of LocalTracker::update (local_tracker.cpp:170-186) as one two-pair batch, with the inputs of the
 // accept callbacks of KeyframeTracker (keyframe_tracker.cpp:105-190) in `criteria`.
 inline void trackFrame(dvo::DenseTracker &tracker, dvo::core::RgbdImagePyramid &keyframe, dvo::core::RgbdImagePyramid &last_frame,

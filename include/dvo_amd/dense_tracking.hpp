@@ -1481,6 +1481,65 @@ class DenseTracker {
   }
 #endif
 
+  // Pose scoring (dvo_amd.h, "Pose scoring"): one record per hypothesis of the pair at options.level -- the counts of the four
+  // outcomes, the integer cost and the total a ranking goes by.  transformations: reference -> current, the ESTIMATE (what
+  // computeIntensityErrorImage takes; the inverse of what match() returns).  Both pyramids are built up to the level.  The call
+  // holds no tracker state and refines nothing: the best hypotheses are starts for match() or the proposal validator.
+  struct PoseScoreOptions : dvo_amd_pose_score_options {
+    explicit PoseScoreOptions(int level_ = 0) {
+      dvo_amd_default_pose_score_options(this);
+      level = level_;
+    }
+    // the level's precision as SelectionMask::fromResiduals takes it: the last iteration of the nearest level that ran
+    PoseScoreOptions(int level_, const Result &result) {
+      dvo_amd_default_pose_score_options(this);
+      level = level_;
+      long best = -1, best_distance = 0;
+      for (size_t i = 0; i < result.Statistics.Levels.size(); ++i) {
+        if (result.Statistics.Levels[i].Iterations.empty()) continue;
+        const long id = (long)result.Statistics.Levels[i].Id, distance = id > level_ ? id - level_ : level_ - id;
+        if (best < 0 || distance < best_distance || (distance == best_distance && id < (long)result.Statistics.Levels[(size_t)best].Id))
+          best = (long)i, best_distance = distance;
+      }
+      if (best < 0) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "DenseTracker::PoseScoreOptions");
+      const core::Matrix2d &P = result.Statistics.Levels[(size_t)best].Iterations.back().TDistributionPrecision;
+      for (int i = 0; i < 4; ++i) precision[i] = (float)P(i % 2, i / 2);  // column-major
+    }
+  };
+  typedef dvo_amd_pose_score PoseScore;
+  std::vector<PoseScore> scorePoses(core::RgbdImagePyramid &reference, core::RgbdImagePyramid &current,
+                                    const std::vector<core::AffineTransformd> &transformations, const PoseScoreOptions &options) {
+    if (options.level >= 0 && options.level < DVO_AMD_MAX_LEVELS) {
+      reference.compute((size_t)options.level + 1);
+      current.compute((size_t)options.level + 1);
+    }
+    std::vector<double> T(16 * transformations.size());
+    for (size_t j = 0; j < transformations.size(); ++j) std::memcpy(&T[16 * j], core::data(transformations[j]), sizeof(double) * 16);
+    std::vector<PoseScore> scores(transformations.size());
+    detail::check(dvo_amd_score_poses(ctx_, reference.handle(), current.handle(), (int)transformations.size(), T.data(), &options,
+                                      scores.data()),
+                  "DenseTracker::scorePoses");
+    return scores;
+  }
+  // the min(k, scores.size()) indices of smallest total, smallest first, ties to the lower index (dvo_amd_rank_poses)
+  static std::vector<int> rankPoses(const std::vector<PoseScore> &scores, int k) {
+    std::vector<int> order((size_t)std::max(0, std::min(k, (int)scores.size())) + 1);
+    int n = 0;
+    detail::check(dvo_amd_rank_poses(scores.data(), (int)scores.size(), k, order.data(), &n), "DenseTracker::rankPoses");
+    order.resize((size_t)n);
+    return order;
+  }
+  // Exp(xi) * centre over a grid of xi = (vx, vy, vz, wx, wy, wz), wz fastest; the middle entry is the centre itself (dvo_amd_pose_grid)
+  static std::vector<core::AffineTransformd> poseGrid(const dvo_amd_pose_grid_options &grid, const core::AffineTransformd &centre) {
+    int n = 0;
+    detail::check(dvo_amd_pose_grid(&grid, core::data(centre), nullptr, 0, &n), "DenseTracker::poseGrid");
+    std::vector<double> T(16 * (size_t)n);
+    detail::check(dvo_amd_pose_grid(&grid, core::data(centre), T.data(), n, &n), "DenseTracker::poseGrid");
+    std::vector<core::AffineTransformd> out((size_t)n);
+    for (int j = 0; j < n; ++j) std::memcpy(core::data(out[(size_t)j]), &T[16 * (size_t)j], sizeof(double) * 16);
+    return out;
+  }
+
   dvo_amd_context *handle() const { return ctx_; }
 
  private:
