@@ -12,16 +12,17 @@ CPP := $(SRC)/dvo_kernels.hip $(SRC)/dvo_pyramid.cpp $(SRC)/dvo_tracker.cpp $(SR
        $(SRC)/dvo_graph_batch.cpp $(SRC)/dvo_covisibility.cpp $(SRC)/dvo_rectify.cpp $(SRC)/dvo_register.cpp \
        $(SRC)/dvo_ingest.cpp $(SRC)/dvo_mask.cpp $(SRC)/dvo_budget.cpp $(SRC)/dvo_mask_ops.cpp \
        $(SRC)/dvo_mask_residual.cpp $(SRC)/dvo_fuse.cpp $(SRC)/dvo_place.cpp $(SRC)/dvo_normals.cpp \
-       $(SRC)/dvo_depth_filter.cpp $(SRC)/dvo_components.cpp $(SRC)/dvo_pose_score.cpp
+       $(SRC)/dvo_depth_filter.cpp $(SRC)/dvo_components.cpp $(SRC)/dvo_pose_score.cpp \
+       $(SRC)/dvo_exposure.cpp
 
 $(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_graph_device.h $(SRC)/dvo_graph_host.h \
-        $(SRC)/dvo_components_core.h include/dvo_amd.h include/dvo_amd_debug.h
+        $(SRC)/dvo_components_core.h $(SRC)/dvo_exposure_solve.h include/dvo_amd.h include/dvo_amd_debug.h
 	$(HIPCC) $(FLAGS) '-DDVO_AMD_BUILD_ID="$(BUILD_ID)"' -x hip $(CPP) -lz -o $@
 
 oracle:
 	$(MAKE) -C oracle
 
-# the C examples that need no input files, and budget_selection_example, mask_ops_example, residual_mask_example, depth_fusion_example, place_index_example, the two normals examples, the two depth_filter examples the two mask_components examples and the two pose_scoring examples, which take their frames as float32 files (the tests
+# the C examples that need no input files, and budget_selection_example, mask_ops_example, residual_mask_example, depth_fusion_example, place_index_example, the two normals examples, the two depth_filter examples the two mask_components examples, the two pose_scoring examples and the two exposure examples, which take their frames as float32 files (the tests
 # build every example themselves, tests/test_*_adaptor.py)
 examples: $(LIB)
 	mkdir -p examples/_build
@@ -61,6 +62,10 @@ examples: $(LIB)
 	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 	$(CXX) -std=c++11 -Wall -pthread -Iinclude/dvo_amd_compat -Iinclude examples/pose_scoring_adaptor_example.cpp \
 	    -o examples/_build/pose_scoring_adaptor_example -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CC) -std=c99 -Wall -Iinclude examples/exposure_example.c -o examples/_build/exposure_example \
+	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CXX) -std=c++11 -Wall -pthread -Iinclude/dvo_amd_compat -Iinclude examples/exposure_adaptor_example.cpp \
+	    -o examples/_build/exposure_adaptor_example -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 
 clean:
 	rm -f $(LIB)

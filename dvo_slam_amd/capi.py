@@ -68,6 +68,8 @@ EXPORTS = [
     "dvo_amd_default_component_options", "dvo_amd_mask_filter_components", "dvo_amd_mask_filter_components_many",
     "dvo_amd_mask_components", "dvo_amd_debug_components_timing",
     "dvo_amd_default_pose_score_options", "dvo_amd_score_poses", "dvo_amd_score_poses_many", "dvo_amd_rank_poses", "dvo_amd_pose_grid",
+    "dvo_amd_default_exposure_options", "dvo_amd_estimate_exposure", "dvo_amd_estimate_exposure_many",
+    "dvo_amd_pyramid_adjust_intensity", "dvo_amd_pyramid_adjust_intensity_many", "dvo_amd_debug_exposure_timing",
 ]
 
 
@@ -194,6 +196,32 @@ POSE_SCORE_FIELDS = ("evaluated", "invalid", "inlier", "outlier", "cost", "total
 POSE_SCORE_DTYPE = np.dtype([(name, np.int64) for name in POSE_SCORE_FIELDS[:4]] + [(name, np.uint64) for name in POSE_SCORE_FIELDS[4:]])
 POSE_SCORE_TILE = 32  # hypotheses a block of k_score_poses takes per visit (kPoseScoreTile, dvo_types.h)
 POSE_GRID_AXES = ("vx", "vy", "vz", "wx", "wy", "wz")
+
+
+EXPOSURE_MAX_REFITS = 8
+# the counts of a dvo_amd_exposure_estimate in the record's order, and its six sums
+EXPOSURE_COUNTS = ("valid", "behind", "outside", "no_depth", "consistent", "occluded", "seen_through", "masked", "saturated",
+                   "candidates", "used", "trimmed")
+EXPOSURE_SUMS = ("n", "sx", "sy", "sxx", "sxy", "syy")
+
+
+class ExposureOptions(C.Structure):
+    """dvo_amd_exposure_options, field for field"""
+    _fields_ = [("level", C.c_int), ("near_z", C.c_float), ("depth_sigmas", C.c_float), ("min_intensity", C.c_float),
+                ("max_intensity", C.c_float), ("scale", C.c_float), ("trim", C.c_float), ("refits", C.c_int),
+                ("min_pairs", C.c_longlong), ("min_gain", C.c_double), ("max_gain", C.c_double)]
+
+
+class ExposureEstimate(C.Structure):
+    """dvo_amd_exposure_estimate, field for field"""
+    _fields_ = ([("gain", C.c_double), ("bias", C.c_double), ("r2", C.c_double), ("passes", C.c_int), ("degenerate", C.c_int)] +
+                [(name, C.c_longlong) for name in EXPOSURE_COUNTS + EXPOSURE_SUMS] +
+                [("gain_pass", C.c_double * (EXPOSURE_MAX_REFITS + 1)), ("bias_pass", C.c_double * (EXPOSURE_MAX_REFITS + 1)),
+                 ("used_pass", C.c_longlong * (EXPOSURE_MAX_REFITS + 1))])
+
+    def as_dict(self) -> dict:
+        """every field as a Python value (the per-pass arrays as lists of all nine entries)"""
+        return {name: (list(getattr(self, name)) if name.endswith("_pass") else getattr(self, name)) for name, _ in self._fields_}
 
 
 class FuseOptions(C.Structure):
@@ -479,6 +507,14 @@ def lib():
     L.dvo_amd_score_poses_many.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), ip, dp, C.POINTER(PoseScoreOptions), vp]
     L.dvo_amd_rank_poses.argtypes = [vp, C.c_int, C.c_int, ip, ip]
     L.dvo_amd_pose_grid.argtypes = [C.POINTER(PoseGridOptions), dp, dp, C.c_int, ip]
+    L.dvo_amd_default_exposure_options.argtypes = [C.POINTER(ExposureOptions)]
+    L.dvo_amd_default_exposure_options.restype = None
+    L.dvo_amd_estimate_exposure.argtypes = [vp, vp, vp, dp, vp, C.POINTER(ExposureOptions), C.POINTER(ExposureEstimate)]
+    L.dvo_amd_estimate_exposure_many.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), dp, C.POINTER(vp),
+                                                 C.POINTER(ExposureOptions), C.POINTER(ExposureEstimate)]
+    L.dvo_amd_pyramid_adjust_intensity.argtypes = [vp, C.c_double, C.c_double, C.POINTER(vp)]
+    L.dvo_amd_pyramid_adjust_intensity_many.argtypes = [C.c_int, C.POINTER(vp), dp, dp, C.POINTER(vp)]
+    L.dvo_amd_debug_exposure_timing.argtypes = [C.c_int, C.c_int, dp]
     L.dvo_amd_default_fuse_options.argtypes = [C.POINTER(FuseOptions)]
     L.dvo_amd_default_fuse_options.restype = None
     L.dvo_amd_pyramid_fuse_depth.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
@@ -911,6 +947,77 @@ def filter_depth_many(pyramids, options=None, counts: bool = False, support: boo
     if support:
         result += (planes,)
     return result if len(result) > 1 else made
+
+
+def exposure_options(**options) -> ExposureOptions:
+    """dvo_amd_default_exposure_options (level 0, near_z 0.1, depth_sigmas 20, intensities 4..251, scale 16, trim 12, refits 4,
+    min_pairs 64, gains 0.25..4) with the given fields replaced"""
+    opt = ExposureOptions()
+    lib().dvo_amd_default_exposure_options(C.byref(opt))
+    for k, v in options.items():
+        if k in ("level", "refits", "min_pairs"):
+            setattr(opt, k, int(v))
+        elif k in ("near_z", "depth_sigmas", "min_intensity", "max_intensity", "scale", "trim", "min_gain", "max_gain"):
+            setattr(opt, k, float(v))
+        else:
+            raise TypeError(f"unknown exposure option {k!r}")
+    return opt
+
+
+def _exposure_options(options) -> ExposureOptions:
+    return options if isinstance(options, ExposureOptions) else exposure_options(**(options or {}))
+
+
+def estimate_exposure_many(tracker, references, currents, Ts=None, masks=None, options=None) -> list:
+    """n pairs in one call of refits_max + 1 kernel launches (dvo_amd_estimate_exposure_many): pair k fits I_ref ~ gain * I_cur +
+    bias between references[k] and currents[k] at the level its options name.  Ts: None (the identity for every pair) or one 4x4
+    per pair, reference -> current, the estimate; masks: None, or one SelectionMask or None per pair, on the reference's pixels;
+    options: None, one ExposureOptions / dict for all pairs, or a list of one per pair.  Returns [ExposureEstimate]."""
+    references, currents = list(references), list(currents)
+    n = len(references)
+    per_pair = list(options) if isinstance(options, (list, tuple)) else [options] * n
+    if len(currents) != n or len(per_pair) != n or (Ts is not None and len(Ts) != n) or (masks is not None and len(masks) != n):
+        raise ValueError("one current, one option set and (where given) one transformation and one mask per reference")
+    vp = C.c_void_p
+    opts = (ExposureOptions * max(1, n))(*[_exposure_options(o) for o in per_pair])
+    T = None if Ts is None else np.ascontiguousarray(np.asarray(Ts, np.float64).reshape(-1, 4, 4).transpose(0, 2, 1))
+    out = (ExposureEstimate * max(1, n))()
+    _check(lib().dvo_amd_estimate_exposure_many(tracker._h, n, (vp * max(1, n))(*[p._h for p in references]),
+                                                (vp * max(1, n))(*[p._h for p in currents]),
+                                                None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)),
+                                                None if masks is None else (vp * max(1, n))(*[None if m is None else m._h for m in masks]),
+                                                opts, out), "dvo_amd_estimate_exposure_many")
+    return [ExposureEstimate.from_buffer_copy(out[k]) for k in range(n)]
+
+
+def adjust_intensity_many(pyramids, gains, biases) -> list:
+    """Many pyramids' level-0 intensity mapped to (gains[k] * I) + biases[k] in one call and one kernel launch
+    (dvo_amd_pyramid_adjust_intensity_many); the pyramids may differ in size.  Returns the list of new pyramids."""
+    pyramids = list(pyramids)
+    n = len(pyramids)
+    g, b = np.ascontiguousarray(gains, np.float64).ravel(), np.ascontiguousarray(biases, np.float64).ravel()
+    if len(g) != n or len(b) != n:
+        raise ValueError("one gain and one bias per pyramid")
+    g, b = np.concatenate([g, [1.0]]), np.concatenate([b, [0.0]])  # (never an empty buffer)
+    vp, dp = C.c_void_p, C.POINTER(C.c_double)
+    out = (vp * max(1, n))()
+    _check(lib().dvo_amd_pyramid_adjust_intensity_many(n, (vp * max(1, n))(*[p._h for p in pyramids]), g.ctypes.data_as(dp),
+                                                       b.ctypes.data_as(dp), out), "dvo_amd_pyramid_adjust_intensity_many")
+    made = []
+    for j in range(n):
+        p = RgbdImagePyramid.__new__(RgbdImagePyramid)
+        p._h, p.device, p.registration_stats = vp(out[j]), pyramids[j].device, None
+        made.append(p)
+    return made
+
+
+def exposure_timing(enable: bool = True, device: int = 0) -> float:
+    """(instrumentation) switches the event brackets around the launches of every estimate_exposure / adjust_intensity call of
+    `device` on or off and returns the device time of the most recent bracketed call in ms, its launches added up
+    (dvo_amd_debug_exposure_timing)"""
+    ms = C.c_double()
+    _check(lib().dvo_amd_debug_exposure_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_exposure_timing")
+    return ms.value
 
 
 def depth_filter_timing(enable: bool = True, device: int = 0) -> float:
@@ -1611,6 +1718,21 @@ class RgbdImagePyramid:
         got = filter_depth_many([self], options, counts=counts, support=support)
         return tuple(part[0] for part in got) if counts or support else got[0]
 
+    def estimate_exposure(self, reference: "RgbdImagePyramid", T=None, mask: "SelectionMask | None" = None, options=None,
+                          tracker: "DenseTracker | None" = None) -> ExposureEstimate:
+        """The gain and bias with which THIS frame, the current one, looks like `reference`: I_ref ~ gain * I_cur + bias over the
+        pixels both see (dvo_amd_estimate_exposure; the rule is pinned in include/dvo_amd.h under "Exposure compensation").  T:
+        4x4, reference -> current, the estimate (None: the identity); mask: on the reference's pixels; options: None, an
+        ExposureOptions or a dict of its fields.  The entry runs in a tracker's context, which gives its device and nothing else:
+        `tracker` when one is given, otherwise the shared one point_cloud uses."""
+        return estimate_exposure_many(tracker or _cloud_tracker(self.device), [reference], [self], None if T is None else [T],
+                                      None if mask is None else [mask], [options])[0]
+
+    def adjust_intensity(self, gain: float, bias: float) -> "RgbdImagePyramid":
+        """This pyramid with level 0's intensity mapped to (gain * I) + bias, not clamped (dvo_amd_pyramid_adjust_intensity): a new
+        pyramid with this one's depth, intrinsics, level count and timestamp; this one is only read."""
+        return adjust_intensity_many([self], [gain], [bias])[0]
+
     def depth_components(self, seeds=None, counts: bool = False, level=None, options=None, **fields):
         """The depth-connected surfaces of this pyramid, the mask = None form of the component entries: every pixel with a finite
         depth is foreground and the depth rule cuts the edges.  level=None: SelectionMask.filter_components' result (the mask of
@@ -1869,6 +1991,28 @@ class DenseTracker:
         _check(lib().dvo_amd_match_masked(self._h, reference._h, None if mask is None else mask._h, ti, td, current._h, T0,
                                           C.byref(res[0])), "dvo_amd_match_masked")
         return Result(res[0], its[0])
+
+    def match_compensated(self, reference: RgbdImagePyramid, current: RgbdImagePyramid, T_init=None, options=None, rounds: int = 1,
+                          **match_kw):
+        """match() behind an exposure compensation of the current frame (plain Python over estimate_exposure, adjust_intensity and
+        match; match itself is untouched).  Round 1 estimates gain and bias at T_init (reference -> current, the estimate; None:
+        the identity), adjusts `current` and matches the adjusted pyramid from T_init.  Every further round estimates again at the
+        result (the inverse of its Transformation), adjusts the ORIGINAL frame and matches from the result; like every T_init that
+        start counts only with UseInitialEstimate (and a tracker configured so wants a T_init, as match does).  options: the exposure options (None, an ExposureOptions or a dict); a mask= among
+        match_kw masks the estimate as well.  A degenerate estimate adjusts by (1, 0), which changes no bit.
+        Returns (result, [one ExposureEstimate per round], the adjusted pyramid of the last round)."""
+        if rounds < 1:
+            raise ValueError("rounds must be at least 1")
+        T, estimates, result, adjusted = T_init, [], None, None
+        for _ in range(int(rounds)):
+            estimate = current.estimate_exposure(reference, T=T, mask=match_kw.get("mask"), options=options, tracker=self)
+            adjusted = current.adjust_intensity(estimate.gain, estimate.bias)
+            result = self.match(reference, adjusted, T_init=T, **match_kw)
+            estimates.append(estimate)
+            if result.isNaN():
+                break
+            T = rigid_inverse(result.Transformation)
+        return result, estimates, adjusted
 
     def alloc_results(self, n):
         """(result structs, per-iteration statistics arrays) for n pairs, reusable across match_batch(results=...) calls"""

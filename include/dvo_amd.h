@@ -790,6 +790,115 @@ int dvo_amd_pose_grid(const dvo_amd_pose_grid_options *opt, const double *T_cent
                       int capacity, int *n_out);
 
 /* ------------------------------------------------------------------------------------------------------------------------------
+ * Exposure compensation: the gain and bias between two frames fitted on the device, and a frame's intensity adjusted by them.
+ *
+ * The tracker assumes that a surface keeps its grey value from one frame to the next; a camera with auto-exposure breaks that, and
+ * a loop closure pairs keyframes taken minutes apart.  The t-distribution weights absorb moving objects, not a global gain or bias,
+ * which shifts every intensity residual at once.  dvo_amd_estimate_exposure fits  I_ref ~ gain * I_cur + bias  over the pixels both
+ * frames see; dvo_amd_pyramid_adjust_intensity returns the current frame with that model applied, an ordinary pyramid that enters
+ * wherever a pyramid enters.  Nothing leaves the device but the sums of the fit.
+ *
+ * dvo_amd_estimate_exposure_many(ctx, n, references, currents, T, masks, opts, out); dvo_amd_estimate_exposure is the case n = 1.
+ * Pair k is (references[k], currents[k]) at ONE level L = opts[k].level of both pyramids, whose sizes and intrinsics may differ.
+ * T: n x 16 doubles, column-major, reference -> current: the ESTIMATE, exactly as dvo_amd_mask_from_residuals takes it (for
+ * dvo_amd_match(reference, current) the INVERSE of result.transformation as returned).  T == NULL is the identity for every pair:
+ * what a tracker has before its first match, and enough for the motion between neighbouring frames.  masks may be NULL and so may
+ * any masks[k]; a mask lies on the REFERENCE's pixels and must fit the reference as dvo_amd_pyramid_select_masked checks it.
+ *
+ * The rule for one pair.  Reference pixel i = (u, v) of level L gets an outcome and a landing pixel (pu, pv) in the current's level L
+ * exactly as dvo_amd_mask_warp's rule ("Mask operations") gives them with target = reference and source = current, near_z and
+ * depth_sigmas from the options: rows 0..2 of T cast to float, every fp32 operation rounded on its own.
+ *   1. An outcome other than consistent counts under that outcome (behind, outside, no_depth, occluded, seen_through), and the pixel
+ *      is done; a pixel without a finite depth counts nowhere.  valid = the sum of the six outcomes, as in dvo_amd_covisibility.
+ *   2. With a mask whose byte at i on level L is 0 the pixel counts as masked.
+ *   3. y = I_ref[i], x = I_cur[pv * ws + pu]: the nearest sample, never blended.  Unless min_intensity <= x <= max_intensity and
+ *      min_intensity <= y <= max_intensity the pixel counts as saturated (a NaN compares false and lands here).
+ *   4. Every other pixel is a candidate, quantised as X = (long long) rintf(x * scale), Y = (long long) rintf(y * scale): the
+ *      product rounded in fp32, round to nearest, then to the nearest integer, ties to even.
+ *   5. Pass 0 uses every candidate.  Pass p >= 1 uses the candidates with
+ *          fabsf(((float) gain * x + (float) bias) - y) <= trim
+ *      for the gain and bias of pass p - 1, every operation rounded on its own (no FMA); the others count as trimmed in that pass.
+ *   6. A pass forms n = the pairs used and sx = sum X, sy = sum Y, sxx = sum X X, sxy = sum X Y, syy = sum Y Y as exact 64-bit
+ *      integers (a level of more than 2^22 pixels is refused and |bound| * scale <= 2^20, so sxx <= 2^62).
+ *   7. The host forms three exact integers in 128 bits,
+ *          det = n sxx - sx sx,   ng = n sxy - sx sy,   nb = sy sxx - sx sxy,
+ *      and from them, every conversion of a 128-bit integer to double correctly rounded,
+ *          gain = (double) ng / (double) det
+ *          bias = ((double) nb / (double) det) / (double) scale
+ *          r2   = ((double) ng / (double) det) * ((double) ng / (double) dety),  dety = n syy - sy sy;  0 if dety <= 0
+ *   8. A pass is degenerate with code 1 if n < min_pairs, else 2 if det <= 0, else 3 if the gain is not finite or outside
+ *      [min_gain, max_gain].  The estimate ends there with gain 1, bias 0, r2 0 and the code.
+ * There are refits + 1 passes unless one is degenerate.  The record:
+ *     gain, bias, r2, passes, degenerate     the last pass's fit; passes = the passes that formed sums, the degenerate one included
+ *     valid ... seen_through                 dvo_amd_covisibility's seven counts of the ordered pair (reference, current) at level L
+ *     masked, saturated, candidates          consistent = masked + saturated + candidates
+ *     used, trimmed                          of the last pass: candidates = used + trimmed
+ *     n, sx, sy, sxx, sxy, syy               the last pass's sums; n == used
+ *     gain_pass[p], bias_pass[p], used_pass[p]   per pass p < passes (1 and 0 for a degenerate pass); 0 beyond
+ * Every sum is an integer: no value depends on the launch geometry or on the order atomics land in, and two runs are bit-identical.
+ *
+ * What the fit is and is not.  It is ordinary least squares of y on x, and x carries the sensor's noise: the gain comes out low by
+ * about var(noise) / var(texture), half a percent for 1.5 grey levels of noise on the synthetic sensor frames (regression dilution,
+ * a property of least squares that the refits do not remove).  Pixels the exposure clipped are kept out by the intensity bounds on
+ * both sides; what moved between the frames, and what the estimate T misplaces on strong texture, is kept out by the trim.
+ *
+ * One kernel launch per pass serves all pairs of a call: refits_max + 1 launches and as many synchronisations, whatever n is.  The
+ * context gives its device and nothing else: no tracker slot is used, no selection is built, and the context's queue need not be
+ * idle.  The pyramids and masks are only read.
+ *
+ * Errors, before any device is looked for: DVO_AMD_ERR_INVALID_ARGUMENT, with a reason in dvo_amd_last_error() that starts with the
+ * entry's name, for a NULL pointer (inside the arrays too; T, masks and masks[k] may be NULL); n < 0; a level that is negative or
+ * that either pyramid lacks; a reference level of more than 2^22 pixels; an option outside the range its field states below; a
+ * non-finite entry of T; a mask that does not fit its reference.  Then DVO_AMD_ERR_DEVICE_MISMATCH unless pyramids and masks live on
+ * the context's device, then DVO_AMD_ERR_NO_DEVICE.  n == 0 is OK and does nothing.  On every failure out is left untouched.
+ *
+ * dvo_amd_pyramid_adjust_intensity_many(n, p, gain, bias, out); dvo_amd_pyramid_adjust_intensity is the case n = 1.  Level 0's
+ * intensity becomes ((float) gain[k] * I) + (float) bias[k], product and sum rounded separately, and is NOT clamped.  out[k] is a new
+ * ordinary pyramid with the input's depth bit for bit, its timestamp, intrinsics and level count, and every other plane what the
+ * builder derives: plane for plane the pyramid dvo_amd_pyramid_create makes of those two level-0 planes.  All items of a call, of
+ * any sizes, share ONE launch; the entries take no context and run on the device's internal stream, like the depth filter.  The
+ * inputs are only read.  Errors: INVALID_ARGUMENT for a NULL pointer (inside the array too), n < 0, a gain or bias that is not
+ * finite; then DEVICE_MISMATCH unless all pyramids live on one device; then NO_DEVICE.  Every out[k] is NULL on failure.
+ *
+ * Not covered: affine parameters inside the Gauss-Newton step (the fit runs before the alignment, at an estimate); a per-pixel or
+ * vignetting model; an estimate without depth on both sides; a clamp of the adjusted values; dvo_amd_track_frame and the validator
+ * do not compensate by themselves -- the caller adjusts the pyramid first.
+ */
+#define DVO_AMD_EXPOSURE_MAX_REFITS 8
+typedef struct dvo_amd_exposure_options {
+  int level;                          /* the level fitted: it must exist in both pyramids */
+  float near_z, depth_sigmas;         /* the covisibility rule's: near_z finite, > 0; depth_sigmas finite, >= 0 */
+  float min_intensity, max_intensity; /* both sides; finite, min <= max, |.| * scale <= 2^20 */
+  float scale;                        /* quantisation: finite, > 0 */
+  float trim;                         /* grey levels; > 0, +inf allowed (no trimming) */
+  int refits;                         /* 0..DVO_AMD_EXPOSURE_MAX_REFITS */
+  long long min_pairs;                /* >= 2 */
+  double min_gain, max_gain;          /* finite, 0 < min <= max */
+} dvo_amd_exposure_options;
+typedef struct dvo_amd_exposure_estimate {
+  double gain, bias, r2;
+  int passes, degenerate;
+  long long valid, behind, outside, no_depth, consistent, occluded, seen_through, masked, saturated, candidates;
+  long long used, trimmed;
+  long long n, sx, sy, sxx, sxy, syy;
+  double gain_pass[DVO_AMD_EXPOSURE_MAX_REFITS + 1], bias_pass[DVO_AMD_EXPOSURE_MAX_REFITS + 1];
+  long long used_pass[DVO_AMD_EXPOSURE_MAX_REFITS + 1];
+} dvo_amd_exposure_estimate;
+/* level 0, near_z 0.1, depth_sigmas 20, intensities 4..251, scale 16, trim 12, refits 4, min_pairs 64, gains 0.25..4; a NULL opt is
+ * a no-op */
+void dvo_amd_default_exposure_options(dvo_amd_exposure_options *opt);
+int dvo_amd_estimate_exposure(dvo_amd_context *ctx, const dvo_amd_pyramid *reference, const dvo_amd_pyramid *current,
+                              const double *T /* 16, or NULL */, const dvo_amd_mask *mask /* or NULL */,
+                              const dvo_amd_exposure_options *opt, dvo_amd_exposure_estimate *out);
+int dvo_amd_estimate_exposure_many(dvo_amd_context *ctx, int n, const dvo_amd_pyramid *const *references,
+                                   const dvo_amd_pyramid *const *currents, const double *T /* n x 16, or NULL */,
+                                   const dvo_amd_mask *const *masks /* n, or NULL */, const dvo_amd_exposure_options *opts /* n */,
+                                   dvo_amd_exposure_estimate *out /* n */);
+int dvo_amd_pyramid_adjust_intensity(const dvo_amd_pyramid *p, double gain, double bias, dvo_amd_pyramid **out);
+int dvo_amd_pyramid_adjust_intensity_many(int n, const dvo_amd_pyramid *const *p, const double *gain /* n */,
+                                          const double *bias /* n */, dvo_amd_pyramid **out /* n */);
+
+/* ------------------------------------------------------------------------------------------------------------------------------
  * Depth fusion: the depth of the frames tracked against a keyframe averaged into the keyframe, on the device.
  *
  * A keyframe's depth plane is one raw sensor frame with that frame's noise, and everything that follows is tracked against it.

@@ -300,6 +300,15 @@ class RgbdImage {
   int level_;
 };
 
+class SelectionMask;
+
+// (not in the reference) Exposure compensation (dvo_amd.h, "Exposure compensation"): the options of the gain and bias fit with their
+// defaults, and the record one estimate returns
+struct ExposureOptions : dvo_amd_exposure_options {
+  ExposureOptions() { dvo_amd_default_exposure_options(this); }
+};
+typedef dvo_amd_exposure_estimate ExposureEstimate;
+
 // rgbd_image.h:242-262.  The reference extends a pyramid lazily, level by level; here the base planes are kept on the host
 // until the first build(n), then the device pyramid is (re)built with max(n, levels so far) levels in one go.
 class RgbdImagePyramid {
@@ -478,6 +487,27 @@ class RgbdImagePyramid {
     }
     if (counts) *counts = record;
     return out;
+  }
+
+  // (not in the reference, which assumes constant brightness) The gain and bias with which THIS frame, the current one, looks like
+  // `reference`: I_ref ~ gain * I_cur + bias over the pixels both see, by trimmed least squares on the device (dvo_amd.h, "Exposure
+  // compensation").  estimate: reference -> current, what computeIntensityErrorImage takes and the inverse of what match() returns;
+  // null is the identity.  mask: on the reference's pixels, or null.  Both pyramids are built up to options.level.  context: a
+  // tracker's (DenseTracker::handle()), which gives its device and nothing else; null takes the shared one of the point clouds.
+  ExposureEstimate estimateExposure(RgbdImagePyramid &reference, const AffineTransformd *estimate = nullptr, const SelectionMask *mask = nullptr,
+                                    const ExposureOptions &options = ExposureOptions(), dvo_amd_context *context = nullptr);
+
+  // This frame with level 0's intensity mapped to (gain * I) + bias, not clamped, on the device: a new pyramid of this one's depth,
+  // size, intrinsics, level count and timestamp; this one is only read and must hold its levels (RgbdImagePyramid::build).
+  Ptr adjustIntensity(double gain, double bias) const {
+    dvo_amd_pyramid *made = nullptr;
+    detail::check(dvo_amd_pyramid_adjust_intensity(handle_, gain, bias, &made), "RgbdImagePyramid::adjustIntensity");
+    try {
+      return Ptr(new RgbdImagePyramid(made, width_, height_, K_, device_, timestamp_));
+    } catch (...) {
+      dvo_amd_pyramid_release(made);
+      throw;
+    }
   }
 
   double timestamp() const { return timestamp_; }
@@ -1213,6 +1243,21 @@ class RgbdCameraPyramid {
 };
 typedef std::shared_ptr<RgbdCameraPyramid> RgbdCameraPyramidPtr;
 
+inline ExposureEstimate RgbdImagePyramid::estimateExposure(RgbdImagePyramid &reference, const AffineTransformd *estimate, const SelectionMask *mask,
+                                                           const ExposureOptions &options, dvo_amd_context *context) {
+  if (options.level >= 0 && options.level < DVO_AMD_MAX_LEVELS) {
+    reference.build((size_t)options.level + 1);
+    build((size_t)options.level + 1);
+  }
+  ExposureEstimate out;
+  std::unique_lock<std::mutex> lock;
+  if (!context) context = cloud::context(device_, lock);
+  detail::check(dvo_amd_estimate_exposure(context, reference.handle(), handle_, estimate ? data(*estimate) : nullptr,
+                                          mask ? mask->handle() : nullptr, &options, &out),
+                "RgbdImagePyramid::estimateExposure");
+  return out;
+}
+
 }  // namespace core
 
 // dense_tracking.h:39-213
@@ -1443,6 +1488,37 @@ class DenseTracker {
       result.Statistics.Levels.push_back(ls);
     }
     return true;  // the reference's `success` is constant true (dense_tracking.cpp:135,375)
+  }
+
+  // (not in the reference) match() behind an exposure compensation of the current frame (dvo_amd.h, "Exposure compensation"): the
+  // gain and bias of `current` against `reference` are estimated at the start -- result.Transformation on entry with
+  // UseInitialEstimate, else the identity --, `current` is adjusted by them and the adjusted pyramid is matched.  Every further
+  // round estimates again at the result, adjusts the ORIGINAL frame and matches from the result (with UseInitialEstimate; without,
+  // match() starts from the identity as always).  match() itself is untouched; `current` is only read.  estimates: one record per
+  // round; adjusted: the adjusted pyramid of the last round.
+  bool matchCompensated(core::RgbdImagePyramid &reference, core::RgbdImagePyramid &current, Result &result,
+                        const core::ExposureOptions &options = core::ExposureOptions(), int rounds = 1,
+                        std::vector<core::ExposureEstimate> *estimates = nullptr, core::RgbdImagePyramidPtr *adjusted = nullptr) {
+    if (rounds < 1) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "DenseTracker::matchCompensated");
+    reference.compute(cfg.getNumLevels());
+    current.compute(cfg.getNumLevels());
+    core::AffineTransformd start;  // the identity
+    if (cfg.UseInitialEstimate) start = result.Transformation;
+    if (estimates) estimates->clear();
+    bool success = true;
+    for (int round = 0; round < rounds; ++round) {
+      const core::ExposureEstimate e = current.estimateExposure(reference, &start, nullptr, options, ctx_);
+      core::RgbdImagePyramidPtr made = current.adjustIntensity(e.gain, e.bias);
+      Result r;
+      r.Transformation = start;
+      success = match(reference, *made, r);
+      result = r;
+      if (estimates) estimates->push_back(e);
+      if (adjusted) *adjusted = made;
+      if (r.isNaN()) break;
+      start = core::SelectionMask::rigidInverse(r.Transformation);
+    }
+    return success;
   }
 
   // dense_tracking.cpp:378-444 (caller: keyframe_graph.cpp:354): |intensity residual| per reference pixel of `level`, 0 where

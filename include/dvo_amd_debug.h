@@ -271,6 +271,11 @@ int dvo_amd_debug_normals_timing(int device, int enable, int *launches, int *syn
  * is bracketed by two events on the device's internal stream (the launch alone: not the tables' upload, not the pyramids' build);
  * *last_ms (may be NULL) receives the device time of the most recent bracketed launch */
 int dvo_amd_debug_depth_filter_timing(int device, int enable, double *last_ms);
+/* with enable != 0 every launch of a later dvo_amd_estimate_exposure / _many and dvo_amd_pyramid_adjust_intensity / _many on `device`
+ * is bracketed by two events on the device's internal stream (the launches alone: not the tables' upload, not the host solve between
+ * two passes, not the pyramids' build); *last_ms (may be NULL) receives the device time of the most recent bracketed call, its
+ * launches added up */
+int dvo_amd_debug_exposure_timing(int device, int enable, double *last_ms);
 /* with enable != 0 every later dvo_amd_mask_filter_components, dvo_amd_mask_filter_components_many and dvo_amd_mask_components on
  * `device` is bracketed by two events on the device's internal stream, from before the upload of its plane table to behind its last
  * kernel (five launches for a filter, three for the inspection entry); *last_ms (may be NULL) receives the device time of the most
