@@ -70,6 +70,9 @@ EXPORTS = [
     "dvo_amd_default_pose_score_options", "dvo_amd_score_poses", "dvo_amd_score_poses_many", "dvo_amd_rank_poses", "dvo_amd_pose_grid",
     "dvo_amd_default_exposure_options", "dvo_amd_estimate_exposure", "dvo_amd_estimate_exposure_many",
     "dvo_amd_pyramid_adjust_intensity", "dvo_amd_pyramid_adjust_intensity_many", "dvo_amd_debug_exposure_timing",
+    "dvo_amd_default_warp_options", "dvo_amd_warp_inverse", "dvo_amd_warp_inverse_many", "dvo_amd_pyramid_warp_inverse",
+    "dvo_amd_pyramid_warp_inverse_many", "dvo_amd_warp_forward", "dvo_amd_warp_forward_many", "dvo_amd_pyramid_warp_forward",
+    "dvo_amd_pyramid_warp_forward_many", "dvo_amd_debug_warp_timing",
 ]
 
 
@@ -173,6 +176,12 @@ class BudgetOptions(C.Structure):
 class MaskWarpOptions(C.Structure):
     """dvo_amd_mask_warp_options, field for field"""
     _fields_ = [("near_z", C.c_float), ("depth_sigmas", C.c_float), ("unseen_keep", C.c_int), ("inconsistent_keep", C.c_int)]
+
+
+class WarpOptions(C.Structure):
+    """dvo_amd_warp_options, field for field"""
+    _fields_ = [("near_z", C.c_float), ("occlusion_margin", C.c_float), ("depth", C.c_int), ("splat", C.c_int),
+                ("fill_intensity", C.c_float)]
 
 
 class ResidualMaskOptions(C.Structure):
@@ -299,6 +308,15 @@ RESIDUAL_MASK_MAX_DISTANCE = 9.2103  # -2 ln 0.01: the 99 % point of chi-square 
 # one record of dvo_amd_mask_warp's counts, field for field
 MASK_WARP_COUNTS = ("valid", "behind", "outside", "no_depth", "consistent", "occluded", "seen_through", "dropped_by_source")
 MASK_WARP_DTYPE = np.dtype([(name, np.int64) for name in MASK_WARP_COUNTS])
+
+# frame warps: the depth an inverse warp returns, the pixels a forward warp covers, and one record of each direction's counts
+WARP_DEPTH_TRANSFORMED, WARP_DEPTH_FIXED = 0, 1
+WARP_SPLAT_NEAREST, WARP_SPLAT_FLOOR, WARP_SPLAT_FOOTPRINT = 0, 1, 2
+WARP_MAX_FOOTPRINT = 16
+WARP_INVERSE_COUNTS = ("valid", "behind", "outside", "border", "hidden", "warped", "partial", "no_depth")
+WARP_INVERSE_DTYPE = np.dtype([(name, np.int64) for name in WARP_INVERSE_COUNTS])
+WARP_FORWARD_COUNTS = ("valid", "behind", "outside", "too_large", "drawn", "covered_pixels", "no_depth")
+WARP_FORWARD_DTYPE = np.dtype([(name, np.int64) for name in WARP_FORWARD_COUNTS])
 
 # dvo_amd_covisibility_counts, field for field
 COVISIBILITY_DTYPE = np.dtype([(name, np.uint32) for name in ("valid", "behind", "outside", "no_depth", "consistent", "occluded",
@@ -515,6 +533,18 @@ def lib():
     L.dvo_amd_pyramid_adjust_intensity.argtypes = [vp, C.c_double, C.c_double, C.POINTER(vp)]
     L.dvo_amd_pyramid_adjust_intensity_many.argtypes = [C.c_int, C.POINTER(vp), dp, dp, C.POINTER(vp)]
     L.dvo_amd_debug_exposure_timing.argtypes = [C.c_int, C.c_int, dp]
+    L.dvo_amd_default_warp_options.argtypes = [C.POINTER(WarpOptions)]
+    L.dvo_amd_default_warp_options.restype = None
+    ll, wo, cv = C.POINTER(C.c_longlong), C.POINTER(WarpOptions), C.POINTER(CView)
+    L.dvo_amd_warp_inverse.argtypes = [vp, vp, dp, C.c_int, wo, fp, fp, ll]
+    L.dvo_amd_warp_inverse_many.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), dp, C.c_int, wo, C.POINTER(vp), C.POINTER(vp), ll]
+    L.dvo_amd_pyramid_warp_inverse.argtypes = [vp, vp, dp, wo, C.POINTER(vp), ll]
+    L.dvo_amd_pyramid_warp_inverse_many.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), dp, wo, C.POINTER(vp), ll]
+    L.dvo_amd_warp_forward.argtypes = [vp, dp, cv, C.c_int, wo, fp, fp, ip, ll]
+    L.dvo_amd_warp_forward_many.argtypes = [C.c_int, C.POINTER(vp), dp, cv, C.c_int, wo, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), ll]
+    L.dvo_amd_pyramid_warp_forward.argtypes = [vp, dp, cv, wo, C.POINTER(vp), ll]
+    L.dvo_amd_pyramid_warp_forward_many.argtypes = [C.c_int, C.POINTER(vp), dp, cv, wo, C.POINTER(vp), ll]
+    L.dvo_amd_debug_warp_timing.argtypes = [C.c_int, C.c_int, ip, ip, dp]
     L.dvo_amd_default_fuse_options.argtypes = [C.POINTER(FuseOptions)]
     L.dvo_amd_default_fuse_options.restype = None
     L.dvo_amd_pyramid_fuse_depth.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
@@ -1065,6 +1095,118 @@ def fuse_timing(enable: bool = True, device: int = 0) -> float:
     ms = C.c_double()
     _check(lib().dvo_amd_debug_fuse_timing(device, int(enable), C.byref(ms)), "dvo_amd_debug_fuse_timing")
     return ms.value
+
+
+def warp_options(**options) -> WarpOptions:
+    """dvo_amd_default_warp_options (near_z 0.1, occlusion_margin 0.05, depth WARP_DEPTH_TRANSFORMED, splat WARP_SPLAT_NEAREST,
+    fill_intensity 0) with the given fields replaced"""
+    opt = WarpOptions()
+    lib().dvo_amd_default_warp_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in dict(WarpOptions._fields_):
+            raise TypeError(f"unknown warp option {k!r}")
+        setattr(opt, k, v)
+    return opt
+
+
+def _warp_options(options) -> WarpOptions:
+    return options if isinstance(options, WarpOptions) else warp_options(**(options or {}))
+
+
+def warp_timing(enable: bool = True, device: int = 0) -> dict:
+    """(instrumentation) switches the event bracket around the launches of every warp_inverse / warp_forward of `device` on or
+    off; returns what the most recent such call enqueued of its own (`launches`, `synchronisations`) and the device time of the
+    most recent bracketed call in ms (`ms`) (dvo_amd_debug_warp_timing)"""
+    n, s, ms = C.c_int(), C.c_int(), C.c_double()
+    _check(lib().dvo_amd_debug_warp_timing(device, int(enable), C.byref(n), C.byref(s), C.byref(ms)), "dvo_amd_debug_warp_timing")
+    return dict(launches=n.value, synchronisations=s.value, ms=ms.value)
+
+
+def _warp_poses(Ts, n):
+    if len(Ts) != n:
+        raise ValueError("one transformation per item")
+    return np.ascontiguousarray(np.stack([_pose_cm(t) for t in Ts]) if n else np.zeros((1, 4, 4)), dtype=np.float64)
+
+
+def _wrap_pyramids(handles, like):
+    made = []
+    for h, src in zip(handles, like):
+        p = RgbdImagePyramid.__new__(RgbdImagePyramid)
+        p._h, p.device, p.registration_stats = C.c_void_p(h), src.device, None
+        made.append(p)
+    return made
+
+
+def warp_inverse_many(fixed, moving, Ts, level=None, options=None):
+    """n inverse warps in one call and one kernel launch (dvo_amd_warp_inverse_many / dvo_amd_pyramid_warp_inverse_many; the rule
+    is pinned in include/dvo_amd.h under "Frame warps"): the grey values of moving[k] on the pixels of fixed[k].  Ts[k]: 4x4,
+    maps points of moving[k]'s camera into fixed[k]'s: for tracker.match(fixed[k], moving[k]) the result's Transformation as
+    returned.  options: None, a WarpOptions or a dict of its fields.  With a level: (intensity planes, depth planes, counts) --
+    two lists of float32 [h, w] of the fixed level's size and a WARP_INVERSE_DTYPE array.  With level=None: (pyramids, counts),
+    each pyramid with fixed[k]'s size, intrinsics, level count and timestamp."""
+    n = len(fixed)
+    if len(moving) != n:
+        raise ValueError("one moving pyramid per fixed pyramid")
+    opt, T = _warp_options(options), _warp_poses(Ts, n)
+    vp, ll = C.c_void_p, C.POINTER(C.c_longlong)
+    cnt = np.zeros(max(1, n), WARP_INVERSE_DTYPE)
+    fh, mh = (vp * max(1, n))(*[p._h for p in fixed]), (vp * max(1, n))(*[p._h for p in moving])
+    Tp = T.ctypes.data_as(C.POINTER(C.c_double))
+    if level is None:
+        out = (vp * max(1, n))()
+        _check(lib().dvo_amd_pyramid_warp_inverse_many(n, fh, mh, Tp, C.byref(opt), out, cnt.ctypes.data_as(ll)),
+               "dvo_amd_pyramid_warp_inverse_many")
+        return _wrap_pyramids(out[:n], fixed), cnt[:n].copy()
+    sizes = [p.level_info(level)[:2] if 0 <= level < p.levels() else (0, 0) for p in fixed]  # (the library refuses a bad level)
+    I = [np.empty((h, w), np.float32) for w, h in sizes]
+    Z = [np.empty((h, w), np.float32) for w, h in sizes]
+    _check(lib().dvo_amd_warp_inverse_many(n, fh, mh, Tp, level, C.byref(opt), (vp * max(1, n))(*[a.ctypes.data for a in I]),
+                                           (vp * max(1, n))(*[a.ctypes.data for a in Z]), cnt.ctypes.data_as(ll)),
+           "dvo_amd_warp_inverse_many")
+    return I, Z, cnt[:n].copy()
+
+
+def _warp_view(view, near_z) -> CView:
+    """a view as (K, width, height) or (K, width, height, near_z), or a CView"""
+    if isinstance(view, CView):
+        return view
+    K, width, height = view[:3]
+    fx, fy, ox, oy = [float(k) for k in K]
+    return CView(int(width), int(height), fx, fy, ox, oy, float(view[3]) if len(view) > 3 else float(near_z))
+
+
+def warp_forward_many(moving, Ts, views=None, level=None, options=None):
+    """n forward warps in one call and three kernel launches (dvo_amd_warp_forward_many / dvo_amd_pyramid_warp_forward_many):
+    every pixel of moving[k] drawn into a view with a nearest-depth test.  Ts[k] as for warp_inverse_many.  views: None (the
+    moving level's own camera), or one (K, width, height[, near_z]) or CView per item; near_z defaults to the options'.  With a
+    level: (depth planes, intensity planes, index planes, counts) -- float32, float32 and int32 [h, w] of the view's size and a
+    WARP_FORWARD_DTYPE array.  With level=None: (pyramids, counts), each pyramid with the view's size and intrinsics and
+    moving[k]'s level count and timestamp."""
+    n = len(moving)
+    opt, T = _warp_options(options), _warp_poses(Ts, n)
+    if views is not None and len(views) != n:
+        raise ValueError("one view per item")
+    vp, ll = C.c_void_p, C.POINTER(C.c_longlong)
+    cnt = np.zeros(max(1, n), WARP_FORWARD_DTYPE)
+    mh = (vp * max(1, n))(*[p._h for p in moving])
+    Tp = T.ctypes.data_as(C.POINTER(C.c_double))
+    cviews = None if views is None else (CView * max(1, n))(*[_warp_view(v, opt.near_z) for v in views])
+    if level is None:
+        out = (vp * max(1, n))()
+        _check(lib().dvo_amd_pyramid_warp_forward_many(n, mh, Tp, cviews, C.byref(opt), out, cnt.ctypes.data_as(ll)),
+               "dvo_amd_pyramid_warp_forward_many")
+        return _wrap_pyramids(out[:n], moving), cnt[:n].copy()
+    if cviews is None:
+        sizes = [p.level_info(level)[:2] if 0 <= level < p.levels() else (0, 0) for p in moving]  # (the library refuses a bad level)
+    else:
+        sizes = [(max(0, cviews[k].width), max(0, cviews[k].height)) for k in range(n)]
+    Z = [np.empty((h, w), np.float32) for w, h in sizes]
+    I = [np.empty((h, w), np.float32) for w, h in sizes]
+    X = [np.empty((h, w), np.int32) for w, h in sizes]
+    ptrs = [(vp * max(1, n))(*[a.ctypes.data for a in planes]) for planes in (Z, I, X)]
+    _check(lib().dvo_amd_warp_forward_many(n, mh, Tp, cviews, level, C.byref(opt), ptrs[0], ptrs[1], ptrs[2], cnt.ctypes.data_as(ll)),
+           "dvo_amd_warp_forward_many")
+    return Z, I, X, cnt[:n].copy()
 
 
 def _per_level(value, default, what):
@@ -1709,6 +1851,25 @@ class RgbdImagePyramid:
         if observations:
             result += (planes,)
         return result if len(result) > 1 else made
+
+    # ---- frame warps (the rules are pinned in include/dvo_amd.h under "Frame warps")
+
+    def warp_inverse(self, fixed: "RgbdImagePyramid", T, level=None, options=None):
+        """THIS frame, the moving one, resampled onto the pixels of `fixed` (dvo_amd_warp_inverse / dvo_amd_pyramid_warp_inverse).
+        T: 4x4, maps points of this frame's camera into the fixed camera: for tracker.match(fixed, self) the result's
+        Transformation as returned.  With a level: (intensity float32 [h, w], depth float32 [h, w], counts) on the fixed level's
+        pixels, NaN where empty; with level=None: (pyramid, counts), a pyramid like `fixed` in which only warped pixels have a
+        depth.  counts: one WARP_INVERSE_DTYPE record."""
+        got = warp_inverse_many([fixed], [self], [T], level, options)
+        return tuple(part[0] for part in got)
+
+    def warp_forward(self, T, view=None, level=None, options=None):
+        """This frame's pixels drawn into a view with a nearest-depth test (dvo_amd_warp_forward / dvo_amd_pyramid_warp_forward).
+        T: 4x4, maps points of this frame's camera into the view's.  view: None (this frame's own camera at `level`), or
+        (K, width, height[, near_z]).  With a level: (depth float32, intensity float32, index int32 [h, w], counts), empty pixels
+        NaN, NaN and -1; with level=None: (pyramid, counts).  counts: one WARP_FORWARD_DTYPE record."""
+        got = warp_forward_many([self], [T], None if view is None else [view], level, options)
+        return tuple(part[0] for part in got)
 
     def filter_depth(self, options=None, counts: bool = False, support: bool = False):
         """This pyramid with its level-0 depth filtered (dvo_amd_pyramid_filter_depth; the rule is pinned in include/dvo_amd.h

@@ -1608,6 +1608,121 @@ int dvo_amd_map_render(dvo_amd_map *map, const double *pose, const dvo_amd_view 
 int dvo_amd_map_render_pyramid(dvo_amd_map *map, const double *pose, const dvo_amd_view *view, int levels, double timestamp,
                                dvo_amd_pyramid **out, dvo_amd_render_stats *stats);
 
+/*
+ * Frame warps: a frame's grey values and depth resampled into another camera's pixels, on the device.
+ *
+ * RgbdImage::warpIntensity / warpIntensitySse (the inverse warp: a gather over the target's pixels) and warpIntensityForward /
+ * warpDepthForward / warpDepthForwardAdvanced (the forward warp: a scatter of the source's pixels), rgbd_image.cpp:545-781.  The
+ * operation underneath dvo_amd_mask_warp (masks), dvo_amd_pyramid_fuse_depth (depth) and dvo_amd_map_render (the map): to look at
+ * an alignment, to difference two frames in one pixel grid, to feed a view-normalised frame to the place index or to
+ * dvo_amd_estimate_exposure, to predict the next frame from the last one -- without downloading planes and uploading a result.
+ *
+ * Both directions.  T: 16 doubles, column-major, maps points of the MOVING frame's camera into the FIXED camera: for
+ * dvo_amd_match(reference = fixed, current = moving) the result's transformation as returned (the convention of
+ * dvo_amd_mask_warp and dvo_amd_pyramid_fuse_depth).  The moving frame is the one whose grey values travel; the result lies on
+ * the fixed camera's pixels.  All fp32 arithmetic is uncontracted, every operation rounded on its own, divisions correctly
+ * rounded.  Every count is an integer sum and every collision a 64-bit minimum: no value depends on the launch geometry, on the
+ * order atomics land in or on what else is in the call, and two runs are bit-identical.  The entries take no context, use no
+ * tracker slot and run on the device's internal stream.
+ *
+ * 1. The inverse warp (dvo_amd_warp_inverse / _many): for every pixel of level `level` of fixed[k], the grey value of level
+ *    `level` of moving[k] where that pixel's point lands -- moving.warpIntensity(T^-1, fixed.pointcloud, ...).  The two frames
+ *    may differ in size and intrinsics.  The host forms rows 0..2 of the rigid inverse M of T as depth fusion does: Ri = R^T,
+ *    ti[r] = -((R[0][r]*t0 + R[1][r]*t1) + R[2][r]*t2) in double, each entry cast to float.  Per fixed pixel (u, v), depth z:
+ *     a. z not finite: `no_depth`; both outputs empty;
+ *     b. (x, y, z) = (tx[u]*z, ty[v]*z, z) with the fixed level's rays; q = ((M0*x + M1*y) + M2*z) + M3 per row;
+ *     c. !(qz >= near_z): `behind`; both outputs empty;
+ *     d. px = (qx*fx)/qz + ox, py = (qy*fy)/qz + oy with the moving level's intrinsics;
+ *     e. !(px >= 0 && px < wm && py >= 0 && py < hm), compared in float before any conversion: `outside` (the reference's
+ *        inImage); both outputs empty;
+ *     f. x0 = floorf(px), y0 = floorf(py); x0 + 1 >= wm || y0 + 1 >= hm: `border` (bilinearWithDepthBuffer's first return);
+ *     g. a = px - x0, b = py - y0, wa = 1 - a, wb = 1 - b; the taps (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1) in this order
+ *        with the weights wa*wb, a*wb, wa*b, a*b.  A tap takes part iff its moving depth is finite and > qz - occlusion_margin;
+ *        then val = val + w*I and sum = sum + w (each product and sum rounded, from val = sum = 0).  sum > 0: `warped`, the
+ *        intensity is val / sum; otherwise `hidden`.  `partial` counts the warped pixels of which fewer than four taps took part;
+ *     h. the depth plane holds, for every pixel that passed e (border, hidden and warped pixels alike, as in the reference), qz
+ *        (depth == DVO_AMD_WARP_DEPTH_TRANSFORMED, the reference's rule) or z (DVO_AMD_WARP_DEPTH_FIXED: the geometry of the
+ *        camera the image is now in); the intensity of a border or hidden pixel is empty.
+ *    An empty intensity or depth is NaN (0x7FC00000).  intensity_out / depth_out: host planes of the fixed level's size, either
+ *    may be NULL (in the many form: arrays of n pointers, the array or any entry may be NULL).  counts (may be NULL): per pair
+ *    DVO_AMD_WARP_INVERSE_COUNTS values valid, behind, outside, border, hidden, warped, partial, no_depth; valid = behind + outside
+ *    + border + hidden + warped.
+ *    dvo_amd_pyramid_warp_inverse / _many do the same at level 0 and return an ordinary pyramid with the fixed pyramid's size,
+ *    intrinsics, level count and timestamp.  There every pixel that is not warped is empty in BOTH planes -- intensity
+ *    fill_intensity, depth NaN, dvo_amd_map_render_pyramid's empty pixel -- so that no pixel with a depth but no grey value is
+ *    ever tracked.
+ *    A call is ONE kernel launch for all its pairs and synchronises once; a pyramid form then builds each pyramid as every
+ *    builder does.
+ *
+ * 2. The forward warp (dvo_amd_warp_forward / _many): every pixel of level `level` of moving[k] with a finite depth is
+ *    projected into a view and drawn with a nearest-depth test.  views: n views, or NULL: the fixed camera is the moving
+ *    level's own (its size and intrinsics, near_z = opt->near_z); with a view, the view's near_z applies.  The rule is
+ *    dvo_amd_map_render's steps 2 to 7 with "voxel of rank r" read as "moving pixel of index r = v*w + u": rows 0..2 of T cast
+ *    to float (no inverse); (x, y, z) = (tx[u]*z, ty[v]*z, z); c = ((T0*x + T1*y) + T2*z) + T3; !(cz >= near_z): `behind`;
+ *    pu = (cx*fx)/cz + ox, pv = (cy*fy)/cz + oy with the view's intrinsics.  The pixels covered (opt->splat), columns a0..a1:
+ *     DVO_AMD_WARP_SPLAT_NEAREST    a0 = a1 = floorf(pu + 0.5f);
+ *     DVO_AMD_WARP_SPLAT_FLOOR      a0 = a1 = floorf(pu), the reference's pixel;
+ *     DVO_AMD_WARP_SPLAT_FOOTPRINT  the square the moving pixel spans at its new depth: hx = 0.5f*(((z/fx_m)*fx)/cz) (fx_m: the
+ *                                   moving level's), a0 = ceilf(pu - hx), a1 = floorf(pu + hx), and a0 = a1 = floorf(pu + 0.5f)
+ *                                   where a1 < a0;
+ *    rows b0..b1 the same way with pv, fy and fy_m.  a1 - a0 > 15 || b1 - b0 > 15 (more than DVO_AMD_WARP_MAX_FOOTPRINT columns
+ *    or rows before clamping): not drawn, `too_large`.  Otherwise drawn only if a1 >= 0 && a0 <= (float)(width-1) && b1 >= 0 &&
+ *    b0 <= (float)(height-1), compared in float before any conversion to int (false for NaN), else `outside`; the footprint is
+ *    clamped to the view as in dvo_amd_map_render's step 5.  Every covered pixel keeps the minimum of (bits(cz) << 32) | r: the
+ *    nearest depth wins, ties go to the lower index.  Per pixel of the view: depth = cz, intensity = the moving pixel's grey
+ *    value bit for bit, index = r; empty: depth NaN, intensity NaN, index -1.
+ *    (The reference's 5 cm hysteresis and "the last writer in scan order wins" depend on the order of the scan; the
+ *    nearest-depth rule of the map render and of the depth registration replaces them.)
+ *    depth_out / intensity_out / index_out: host planes of the view's size, any may be NULL (many form: arrays of n pointers).
+ *    counts (may be NULL): per item DVO_AMD_WARP_FORWARD_COUNTS values valid, behind, outside, too_large, drawn, covered_pixels,
+ *    no_depth; valid = behind + outside + too_large + drawn; covered_pixels = the pixels of the view that are not empty.
+ *    dvo_amd_pyramid_warp_forward / _many work at level 0 and return a pyramid of the view with the moving pyramid's level count
+ *    and timestamp (dvo_amd_pyramid_create_from_device's rules for width, height and levels); an empty pixel's intensity is
+ *    fill_intensity there.
+ *    A call is THREE kernel launches for all its items (clear, splat, resolve) and synchronises once.
+ *
+ * Errors, in this order: DVO_AMD_ERR_INVALID_ARGUMENT with a reason that starts with the entry's name, before a device is looked
+ * for (a NULL pointer, also inside an array; n < 0; a level beyond either pyramid; a non-finite entry of T; near_z not finite and
+ * positive; occlusion_margin not >= 0 (+inf switches the depth-buffer test off); an unknown depth or splat; a non-finite
+ * fill_intensity; a view dvo_amd_map_render would refuse); DVO_AMD_ERR_DEVICE_MISMATCH; DVO_AMD_ERR_NO_DEVICE.  n == 0 is OK and
+ * does nothing.  On failure the outputs are untouched and every out[k] is NULL.
+ */
+#define DVO_AMD_WARP_DEPTH_TRANSFORMED 0
+#define DVO_AMD_WARP_DEPTH_FIXED 1
+#define DVO_AMD_WARP_SPLAT_NEAREST 0
+#define DVO_AMD_WARP_SPLAT_FLOOR 1
+#define DVO_AMD_WARP_SPLAT_FOOTPRINT 2
+#define DVO_AMD_WARP_MAX_FOOTPRINT 16
+#define DVO_AMD_WARP_INVERSE_COUNTS 8
+#define DVO_AMD_WARP_FORWARD_COUNTS 7
+
+typedef struct {
+  float near_z;            /* 0.1; > 0 */
+  float occlusion_margin;  /* 0.05, the reference's constant; >= 0, +inf: no depth-buffer test (inverse) */
+  int depth;               /* DVO_AMD_WARP_DEPTH_TRANSFORMED (inverse) */
+  int splat;               /* DVO_AMD_WARP_SPLAT_NEAREST (forward) */
+  float fill_intensity;    /* 0: an empty pixel's intensity in the pyramid forms */
+} dvo_amd_warp_options;
+
+void dvo_amd_default_warp_options(dvo_amd_warp_options *opt);
+int dvo_amd_warp_inverse(const dvo_amd_pyramid *fixed, const dvo_amd_pyramid *moving, const double *T, int level,
+                         const dvo_amd_warp_options *opt, float *intensity_out, float *depth_out, long long *counts);
+int dvo_amd_warp_inverse_many(int n, const dvo_amd_pyramid *const *fixed, const dvo_amd_pyramid *const *moving, const double *T, int level,
+                              const dvo_amd_warp_options *opt, float *const *intensity_out, float *const *depth_out, long long *counts);
+int dvo_amd_pyramid_warp_inverse(const dvo_amd_pyramid *fixed, const dvo_amd_pyramid *moving, const double *T,
+                                 const dvo_amd_warp_options *opt, dvo_amd_pyramid **out, long long *counts);
+int dvo_amd_pyramid_warp_inverse_many(int n, const dvo_amd_pyramid *const *fixed, const dvo_amd_pyramid *const *moving, const double *T,
+                                      const dvo_amd_warp_options *opt, dvo_amd_pyramid **out, long long *counts);
+int dvo_amd_warp_forward(const dvo_amd_pyramid *moving, const double *T, const dvo_amd_view *view, int level, const dvo_amd_warp_options *opt,
+                         float *depth_out, float *intensity_out, int *index_out, long long *counts);
+int dvo_amd_warp_forward_many(int n, const dvo_amd_pyramid *const *moving, const double *T, const dvo_amd_view *views, int level,
+                              const dvo_amd_warp_options *opt, float *const *depth_out, float *const *intensity_out, int *const *index_out,
+                              long long *counts);
+int dvo_amd_pyramid_warp_forward(const dvo_amd_pyramid *moving, const double *T, const dvo_amd_view *view, const dvo_amd_warp_options *opt,
+                                 dvo_amd_pyramid **out, long long *counts);
+int dvo_amd_pyramid_warp_forward_many(int n, const dvo_amd_pyramid *const *moving, const double *T, const dvo_amd_view *views,
+                                      const dvo_amd_warp_options *opt, dvo_amd_pyramid **out, long long *counts);
+
 /* Binary PCD v0.7 as pcl::io::savePCDFileBinary writes a PointXYZRGB cloud: FIELDS x y z rgb, SIZE 4 4 4 4, TYPE F F F F
  * (rgb holds the packed bits), COUNT 1 1 1 1, WIDTH / HEIGHT as given (organized, or n x 1), VIEWPOINT 0 0 0 1 0 0 0,
  * POINTS width*height (= n), then the records.  Host code only. */

@@ -510,6 +510,97 @@ class RgbdImagePyramid {
     }
   }
 
+  // RgbdImage::warpIntensity / warpIntensitySse and warpIntensityForward / warpDepthForward / warpDepthForwardAdvanced
+  // (rgbd_image.cpp:545-781) on the device, operation by operation as dvo_amd.h pins them ("Frame warps").  THIS frame is the
+  // moving one, whose grey values travel.  transformation: moving camera -> fixed camera; for tracker.match(fixed, *this, result)
+  // that is result.Transformation as returned.  All pyramids must hold their levels (RgbdImagePyramid::build; a match has built
+  // them).
+  struct WarpOptions : dvo_amd_warp_options {
+    WarpOptions() { dvo_amd_default_warp_options(this); }
+  };
+  struct WarpInverseCounts {
+    long long valid, behind, outside, border, hidden, warped, partial, no_depth;
+  };
+  struct WarpForwardCounts {
+    long long valid, behind, outside, too_large, drawn, covered_pixels, no_depth;
+  };
+  // one level's planes, row-major; index only from warpForward (-1: empty; empty intensity and depth are NaN)
+  struct WarpedPlanes {
+    int width, height;
+    std::vector<float> intensity, depth;
+    std::vector<int> index;
+  };
+  // the inverse warp (a gather): this frame's grey values on the pixels of level `level` of `fixed`
+  WarpedPlanes warpInverse(const RgbdImagePyramid &fixed, const AffineTransformd &transformation, int level,
+                           const WarpOptions &options = WarpOptions(), WarpInverseCounts *counts = nullptr) const {
+    static_assert(sizeof(WarpInverseCounts) == DVO_AMD_WARP_INVERSE_COUNTS * sizeof(long long), "the count record is dvo_amd_warp_inverse's");
+    const char *where = "RgbdImagePyramid::warpInverse";
+    WarpedPlanes out;
+    float k[4];
+    detail::check(dvo_amd_pyramid_level_info(fixed.handle_, level, &out.width, &out.height, k), where);
+    out.intensity.resize((size_t)out.width * out.height), out.depth.resize((size_t)out.width * out.height);
+    WarpInverseCounts record;
+    detail::check(dvo_amd_warp_inverse(fixed.handle_, handle_, data(transformation), level, &options, out.intensity.data(), out.depth.data(),
+                                       &record.valid),
+                  where);
+    if (counts) *counts = record;
+    return out;
+  }
+  // ... as a pyramid like `fixed` (its size, intrinsics, level count and timestamp) in which only warped pixels have a depth
+  Ptr warpInverse(const RgbdImagePyramid &fixed, const AffineTransformd &transformation, const WarpOptions &options = WarpOptions(),
+                  WarpInverseCounts *counts = nullptr) const {
+    WarpInverseCounts record;
+    dvo_amd_pyramid *made = nullptr;
+    detail::check(dvo_amd_pyramid_warp_inverse(fixed.handle_, handle_, data(transformation), &options, &made, &record.valid),
+                  "RgbdImagePyramid::warpInverse");
+    if (counts) *counts = record;
+    try {
+      return Ptr(new RgbdImagePyramid(made, fixed.width_, fixed.height_, fixed.K_, device_, fixed.timestamp_));
+    } catch (...) {
+      dvo_amd_pyramid_release(made);
+      throw;
+    }
+  }
+  // the forward warp (a scatter with a nearest-depth test): this frame's level `level` drawn into `view` (null: this frame's own
+  // camera at that level)
+  WarpedPlanes warpForward(const AffineTransformd &transformation, const dvo_amd_view *view, int level,
+                           const WarpOptions &options = WarpOptions(), WarpForwardCounts *counts = nullptr) const {
+    static_assert(sizeof(WarpForwardCounts) == DVO_AMD_WARP_FORWARD_COUNTS * sizeof(long long), "the count record is dvo_amd_warp_forward's");
+    const char *where = "RgbdImagePyramid::warpForward";
+    WarpedPlanes out;
+    if (view) {
+      out.width = view->width > 0 ? view->width : 0, out.height = view->height > 0 ? view->height : 0;  // (the library refuses the rest)
+    } else {
+      float k[4];
+      detail::check(dvo_amd_pyramid_level_info(handle_, level, &out.width, &out.height, k), where);
+    }
+    const size_t n = (size_t)out.width * out.height;
+    out.intensity.resize(n), out.depth.resize(n), out.index.resize(n);
+    WarpForwardCounts record;
+    detail::check(dvo_amd_warp_forward(handle_, data(transformation), view, level, &options, out.depth.data(), out.intensity.data(),
+                                       out.index.data(), &record.valid),
+                  where);
+    if (counts) *counts = record;
+    return out;
+  }
+  // ... as a pyramid of the view with this frame's level count and timestamp
+  Ptr warpForward(const AffineTransformd &transformation, const dvo_amd_view *view = nullptr, const WarpOptions &options = WarpOptions(),
+                  WarpForwardCounts *counts = nullptr) const {
+    WarpForwardCounts record;
+    dvo_amd_pyramid *made = nullptr;
+    detail::check(dvo_amd_pyramid_warp_forward(handle_, data(transformation), view, &options, &made, &record.valid),
+                  "RgbdImagePyramid::warpForward");
+    if (counts) *counts = record;
+    try {
+      return view ? Ptr(new RgbdImagePyramid(made, view->width, view->height, IntrinsicMatrix::create(view->fx, view->fy, view->ox, view->oy),
+                                             device_, timestamp_))
+                  : Ptr(new RgbdImagePyramid(made, width_, height_, K_, device_, timestamp_));
+    } catch (...) {
+      dvo_amd_pyramid_release(made);
+      throw;
+    }
+  }
+
   double timestamp() const { return timestamp_; }
   int device() const { return device_; }
   int width() const { return width_; }

@@ -281,6 +281,13 @@ int dvo_amd_debug_exposure_timing(int device, int enable, double *last_ms);
  * kernel (five launches for a filter, three for the inspection entry); *last_ms (may be NULL) receives the device time of the most
  * recent bracketed call */
 int dvo_amd_debug_components_timing(int device, int enable, double *last_ms);
+/* what the most recent successful dvo_amd_warp_inverse / _forward entry (plane or pyramid form, single or many) on `device`
+ * enqueued of its own: kernel launches (1 for an inverse warp, 3 for a forward warp counting the clear, whatever n is) and host
+ * synchronisations (one; a pyramid form's builder comes on top); with enable != 0 the launches of every later such call are
+ * bracketed by two events on the device's internal stream (the launches alone: not the table's upload, not the copies back, not
+ * the pyramids' build) and *last_ms receives the device time of the most recent bracketed call.  Any output may be NULL; all
+ * zero before the first such call */
+int dvo_amd_debug_warp_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms);
 
 #ifdef __cplusplus
 }
