@@ -13,10 +13,10 @@ CPP := $(SRC)/dvo_kernels.hip $(SRC)/dvo_pyramid.cpp $(SRC)/dvo_tracker.cpp $(SR
        $(SRC)/dvo_ingest.cpp $(SRC)/dvo_mask.cpp $(SRC)/dvo_budget.cpp $(SRC)/dvo_mask_ops.cpp \
        $(SRC)/dvo_mask_residual.cpp $(SRC)/dvo_fuse.cpp $(SRC)/dvo_place.cpp $(SRC)/dvo_normals.cpp \
        $(SRC)/dvo_depth_filter.cpp $(SRC)/dvo_components.cpp $(SRC)/dvo_pose_score.cpp \
-       $(SRC)/dvo_exposure.cpp $(SRC)/dvo_warp.cpp
+       $(SRC)/dvo_exposure.cpp $(SRC)/dvo_warp.cpp $(SRC)/dvo_volume.cpp
 
 $(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_graph_device.h $(SRC)/dvo_graph_host.h \
-        $(SRC)/dvo_components_core.h $(SRC)/dvo_exposure_solve.h include/dvo_amd.h include/dvo_amd_debug.h
+        $(SRC)/dvo_components_core.h $(SRC)/dvo_exposure_solve.h $(SRC)/dvo_volume_box.h include/dvo_amd.h include/dvo_amd_debug.h
 	$(HIPCC) $(FLAGS) '-DDVO_AMD_BUILD_ID="$(BUILD_ID)"' -x hip $(CPP) -lz -o $@
 
 oracle:
@@ -70,6 +70,10 @@ examples: $(LIB)
 	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 	$(CXX) -std=c++11 -Wall -pthread -Iinclude/dvo_amd_compat -Iinclude examples/frame_warp_adaptor_example.cpp \
 	    -o examples/_build/frame_warp_adaptor_example -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CC) -std=c99 -Wall -Iinclude examples/volume_example.c -o examples/_build/volume_example \
+	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CXX) -std=c++11 -Wall -pthread -Iinclude/dvo_amd_compat -Iinclude examples/volume_adaptor_example.cpp \
+	    -o examples/_build/volume_adaptor_example -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 
 clean:
 	rm -f $(LIB)

@@ -21,8 +21,9 @@ SOURCES = ["dvo_kernels.hip", "dvo_pyramid.cpp", "dvo_tracker.cpp", "dvo_sharded
            "dvo_rectify.cpp", "dvo_register.cpp", "dvo_ingest.cpp", "dvo_mask.cpp", "dvo_budget.cpp",
            "dvo_mask_ops.cpp", "dvo_mask_residual.cpp", "dvo_fuse.cpp", "dvo_place.cpp", "dvo_normals.cpp",
            "dvo_depth_filter.cpp", "dvo_components.cpp", "dvo_pose_score.cpp", "dvo_exposure.cpp",
-           "dvo_warp.cpp"]
+           "dvo_warp.cpp", "dvo_volume.cpp"]
 HEADERS = ["dvo_types.h", "dvo_internal.h", "se3.h", "dvo_graph_device.h", "dvo_graph_host.h", "dvo_components_core.h", "dvo_exposure_solve.h",
+           "dvo_volume_box.h",
            os.path.join("..", "..", "include", "dvo_amd.h"),
            os.path.join("..", "..", "include", "dvo_amd_debug.h")]
 FLAGS = [

@@ -73,6 +73,10 @@ EXPORTS = [
     "dvo_amd_default_warp_options", "dvo_amd_warp_inverse", "dvo_amd_warp_inverse_many", "dvo_amd_pyramid_warp_inverse",
     "dvo_amd_pyramid_warp_inverse_many", "dvo_amd_warp_forward", "dvo_amd_warp_forward_many", "dvo_amd_pyramid_warp_forward",
     "dvo_amd_pyramid_warp_forward_many", "dvo_amd_debug_warp_timing",
+    "dvo_amd_default_volume_options", "dvo_amd_default_volume_raycast_options", "dvo_amd_volume_create", "dvo_amd_volume_destroy",
+    "dvo_amd_volume_clear", "dvo_amd_volume_options_get", "dvo_amd_volume_integrate", "dvo_amd_volume_insert",
+    "dvo_amd_volume_set_poses", "dvo_amd_volume_remove", "dvo_amd_volume_stats", "dvo_amd_volume_download", "dvo_amd_volume_raycast",
+    "dvo_amd_volume_raycast_pyramid", "dvo_amd_volume_extract", "dvo_amd_debug_volume_timing",
 ]
 
 
@@ -182,6 +186,25 @@ class WarpOptions(C.Structure):
     """dvo_amd_warp_options, field for field"""
     _fields_ = [("near_z", C.c_float), ("occlusion_margin", C.c_float), ("depth", C.c_int), ("splat", C.c_int),
                 ("fill_intensity", C.c_float)]
+
+
+class VolumeOptions(C.Structure):
+    """dvo_amd_volume_options, field for field"""
+    _fields_ = [("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int), ("voxel", C.c_float), ("origin", C.c_float * 3), ("trunc", C.c_float),
+                ("near_z", C.c_float), ("far_z", C.c_float), ("weight", C.c_int)]
+
+
+class VolumeRaycastOptions(C.Structure):
+    """dvo_amd_volume_raycast_options, field for field"""
+    _fields_ = [("step_fraction", C.c_float), ("min_weight", C.c_int), ("fill_intensity", C.c_float)]
+
+
+class CVolumeRaycastStats(C.Structure):
+    _fields_ = [(n, C.c_longlong) for n in ("pixels", "hit", "backface", "missed", "uncoloured")]
+
+
+class CVolumeExtractCounts(C.Structure):
+    _fields_ = [(n, C.c_longlong) for n in ("points", "uncoloured")]
 
 
 class ResidualMaskOptions(C.Structure):
@@ -317,6 +340,13 @@ WARP_INVERSE_COUNTS = ("valid", "behind", "outside", "border", "hidden", "warped
 WARP_INVERSE_DTYPE = np.dtype([(name, np.int64) for name in WARP_INVERSE_COUNTS])
 WARP_FORWARD_COUNTS = ("valid", "behind", "outside", "too_large", "drawn", "covered_pixels", "no_depth")
 WARP_FORWARD_DTYPE = np.dtype([(name, np.int64) for name in WARP_FORWARD_COUNTS])
+
+# the signed-distance volume: its weights, one public voxel record and one record of an integration's counts, field for field
+VOLUME_WEIGHT_CONSTANT, VOLUME_WEIGHT_SENSOR = 0, 1
+VOLUME_MAX_STEPS = 8192
+VOLUME_VOXEL_DTYPE = np.dtype([(name, np.int32) for name in ("w_sum", "sd_sum", "iw_sum", "i_sum")])
+VOLUME_COUNTS = ("updated", "near", "free")
+VOLUME_COUNTS_DTYPE = np.dtype([(name, np.int64) for name in VOLUME_COUNTS])
 
 # dvo_amd_covisibility_counts, field for field
 COVISIBILITY_DTYPE = np.dtype([(name, np.uint32) for name in ("valid", "behind", "outside", "no_depth", "consistent", "occluded",
@@ -545,6 +575,26 @@ def lib():
     L.dvo_amd_pyramid_warp_forward.argtypes = [vp, dp, cv, wo, C.POINTER(vp), ll]
     L.dvo_amd_pyramid_warp_forward_many.argtypes = [C.c_int, C.POINTER(vp), dp, cv, wo, C.POINTER(vp), ll]
     L.dvo_amd_debug_warp_timing.argtypes = [C.c_int, C.c_int, ip, ip, dp]
+    vo, ro = C.POINTER(VolumeOptions), C.POINTER(VolumeRaycastOptions)
+    L.dvo_amd_default_volume_options.argtypes = [vo]
+    L.dvo_amd_default_volume_options.restype = None
+    L.dvo_amd_default_volume_raycast_options.argtypes = [ro]
+    L.dvo_amd_default_volume_raycast_options.restype = None
+    L.dvo_amd_volume_create.argtypes = [C.c_int, vo, C.POINTER(vp)]
+    L.dvo_amd_volume_destroy.argtypes = [vp]
+    L.dvo_amd_volume_destroy.restype = None
+    L.dvo_amd_volume_clear.argtypes = [vp]
+    L.dvo_amd_volume_options_get.argtypes = [vp, vo]
+    L.dvo_amd_volume_integrate.argtypes = [vp, C.c_int, C.POINTER(vp), C.c_int, dp, C.c_int, ll]
+    L.dvo_amd_volume_insert.argtypes = [vp, C.c_int, ip, C.POINTER(vp), C.c_int, dp, ll]
+    L.dvo_amd_volume_set_poses.argtypes = [vp, C.c_int, ip, dp]
+    L.dvo_amd_volume_remove.argtypes = [vp, C.c_int, ip]
+    L.dvo_amd_volume_stats.argtypes = [vp, ip, ll]
+    L.dvo_amd_volume_download.argtypes = [vp, ip, vp, C.c_longlong, ll]
+    L.dvo_amd_volume_raycast.argtypes = [vp, dp, cv, ro, fp, fp, ip, C.POINTER(CVolumeRaycastStats)]
+    L.dvo_amd_volume_raycast_pyramid.argtypes = [vp, dp, cv, ro, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(CVolumeRaycastStats)]
+    L.dvo_amd_volume_extract.argtypes = [vp, C.c_int, vp, C.c_longlong, ll, C.POINTER(CVolumeExtractCounts)]
+    L.dvo_amd_debug_volume_timing.argtypes = [C.c_int, C.c_int, ip, ip, dp]
     L.dvo_amd_default_fuse_options.argtypes = [C.POINTER(FuseOptions)]
     L.dvo_amd_default_fuse_options.restype = None
     L.dvo_amd_pyramid_fuse_depth.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
@@ -2588,6 +2638,178 @@ class KeyframeMap:
         _check(lib().dvo_amd_debug_keyframe_map_timing(self._h, C.byref(d), C.byref(c), C.byref(p), C.byref(v), C.byref(t)),
                "dvo_amd_debug_keyframe_map_timing")
         return d.value, c.value, p.value, v.value, t.value
+
+
+def volume_options(**options) -> VolumeOptions:
+    """dvo_amd_default_volume_options (64^3 voxels of 0.05 m, origin (-1.6, -1.6, 0.4), trunc 0.15, near_z 0.4, far_z 5,
+    VOLUME_WEIGHT_SENSOR) with the given fields replaced; origin: three floats"""
+    opt = VolumeOptions()
+    lib().dvo_amd_default_volume_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in dict(VolumeOptions._fields_):
+            raise TypeError(f"unknown volume option {k!r}")
+        setattr(opt, k, (C.c_float * 3)(*[float(x) for x in v]) if k == "origin" else v)
+    return opt
+
+
+def volume_raycast_options(**options) -> VolumeRaycastOptions:
+    """dvo_amd_default_volume_raycast_options (step_fraction 0.5, min_weight 1, fill_intensity 0) with the given fields replaced"""
+    opt = VolumeRaycastOptions()
+    lib().dvo_amd_default_volume_raycast_options(C.byref(opt))
+    for k, v in options.items():
+        if k not in dict(VolumeRaycastOptions._fields_):
+            raise TypeError(f"unknown volume raycast option {k!r}")
+        setattr(opt, k, v)
+    return opt
+
+
+def volume_timing(enable: bool = True, device: int = 0) -> dict:
+    """(instrumentation) switches the event bracket around the launches of every SurfaceVolume call of `device` on or off; returns
+    what the most recent such call enqueued of its own (`launches`, `synchronisations`) and the device time of the most recent
+    bracketed call in ms (`ms`) (dvo_amd_debug_volume_timing)"""
+    n, s, ms = C.c_int(), C.c_int(), C.c_double()
+    _check(lib().dvo_amd_debug_volume_timing(device, int(enable), C.byref(n), C.byref(s), C.byref(ms)), "dvo_amd_debug_volume_timing")
+    return dict(launches=n.value, synchronisations=s.value, ms=ms.value)
+
+
+class SurfaceVolume:
+    """A truncated signed-distance volume kept on one device (dvo_amd_volume_*; the rules are pinned in include/dvo_amd.h):
+    keyframes are fused into a dense grid of integer sums -- inserted, moved and removed exactly, like KeyframeMap's -- which
+    raycast() turns into a hole-free model view and extract() into surface points.  options: None, a VolumeOptions or a dict of
+    its fields.  Context-free: no tracker is needed; calls on one volume are serialised by the caller."""
+
+    def __init__(self, options=None, device: int = 0):
+        self._h = C.c_void_p()
+        self.options = options if isinstance(options, VolumeOptions) else volume_options(**(options or {}))
+        self.device = device
+        _check(lib().dvo_amd_volume_create(device, C.byref(self.options), C.byref(self._h)), "dvo_amd_volume_create")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().dvo_amd_volume_destroy(h)
+            self._h = None
+
+    @property
+    def shape(self):
+        """(nz, ny, nx): the shape download() returns"""
+        return self.options.nz, self.options.ny, self.options.nx
+
+    @staticmethod
+    def _frames(pyramids, poses):
+        n = len(pyramids)
+        if poses is not None and len(poses) != n:
+            raise ValueError("one pose per pyramid")
+        T = None
+        if poses is not None:
+            T = np.ascontiguousarray(np.stack([_pose_cm(np.eye(4) if P is None else P) for P in poses]) if n else np.zeros((1, 4, 4)))
+        return n, (C.c_void_p * max(1, n))(*[p._h for p in pyramids]), T, None if T is None else T.ctypes.data_as(C.POINTER(C.c_double))
+
+    def clear(self):
+        """all records to zero; the keyframes of the tracked form are dropped"""
+        _check(lib().dvo_amd_volume_clear(self._h), "dvo_amd_volume_clear")
+
+    def integrate(self, pyramids, poses=None, level: int = 0, sign: int = 1):
+        """the anonymous form: level `level` of every pyramid at its pose (4x4 camera -> world, None = identity) added (sign +1)
+        or subtracted (-1) in one launch; returns a VOLUME_COUNTS_DTYPE array, one record per frame"""
+        n, ph, T, Tp = self._frames(pyramids, poses)
+        cnt = np.zeros(max(1, n), VOLUME_COUNTS_DTYPE)
+        _check(lib().dvo_amd_volume_integrate(self._h, n, ph, level, Tp, sign, cnt.ctypes.data_as(C.POINTER(C.c_longlong))),
+               "dvo_amd_volume_integrate")
+        return cnt[:n].copy()
+
+    def insert(self, ids, pyramids, poses=None, level: int = 0):
+        """the tracked form: keyframes `ids` in one launch; the volume retains the pyramids.  Returns the counts as integrate()"""
+        ids = [int(i) for i in ids]
+        if len(ids) != len(pyramids):
+            raise ValueError("one id per pyramid")
+        n, ph, T, Tp = self._frames(pyramids, poses)
+        cnt = np.zeros(max(1, n), VOLUME_COUNTS_DTYPE)
+        _check(lib().dvo_amd_volume_insert(self._h, n, (C.c_int * max(1, n))(*ids), ph, level, Tp, cnt.ctypes.data_as(C.POINTER(C.c_longlong))),
+               "dvo_amd_volume_insert")
+        return cnt[:n].copy()
+
+    def set_poses(self, ids, poses):
+        """new poses (4x4 each) of the keyframes `ids`: subtracted at the old pose and added at the new one in one launch"""
+        ids = [int(i) for i in ids]
+        if len(poses) != len(ids):
+            raise ValueError("one pose per id")
+        n = len(ids)
+        T = np.ascontiguousarray(np.stack([_pose_cm(P) for P in poses])) if n else np.zeros((1, 4, 4))
+        _check(lib().dvo_amd_volume_set_poses(self._h, n, (C.c_int * max(1, n))(*ids), T.ctypes.data_as(C.POINTER(C.c_double))),
+               "dvo_amd_volume_set_poses")
+
+    def remove(self, ids):
+        ids = [int(i) for i in ids]
+        _check(lib().dvo_amd_volume_remove(self._h, len(ids), (C.c_int * max(1, len(ids)))(*ids)), "dvo_amd_volume_remove")
+
+    def stats(self) -> dict:
+        """{"keyframes", "updated_total"}: the keyframes of the tracked form and the sum of their `updated` counts"""
+        n, total = C.c_int(), C.c_longlong()
+        _check(lib().dvo_amd_volume_stats(self._h, C.byref(n), C.byref(total)), "dvo_amd_volume_stats")
+        return {"keyframes": n.value, "updated_total": total.value}
+
+    def download(self, box=None) -> np.ndarray:
+        """the records as a VOLUME_VOXEL_DTYPE array [nz, ny, nx], or those of the inclusive index box (x0, y0, z0, x1, y1, z1)"""
+        bx = None if box is None else (C.c_int * 6)(*[int(b) for b in box])
+        shape = self.shape if box is None else tuple(max(0, int(box[3 + a]) - int(box[a]) + 1) for a in (2, 1, 0))
+        out = np.zeros(shape, VOLUME_VOXEL_DTYPE)
+        n = C.c_longlong()
+        _check(lib().dvo_amd_volume_download(self._h, bx, out.ctypes.data, out.size, C.byref(n)), "dvo_amd_volume_download")
+        return out
+
+    def raycast(self, pose, K, width: int, height: int, near=None, options=None, planes=("depth", "intensity", "weight")):
+        """The volume seen from `pose` (4x4 camera -> world, None = identity) through K = (fx, fy, ox, oy) (dvo_amd_volume_raycast):
+        a dict of the requested planes, [height, width] each -- depth and intensity float32 (NaN where empty), weight int32 --
+        plus "stats".  near=None: the volume's near_z.  options: None, a VolumeRaycastOptions or a dict of its fields."""
+        kinds = {"depth": np.float32, "intensity": np.float32, "weight": np.int32}
+        unknown = [p for p in planes if p not in kinds]
+        if unknown:
+            raise ValueError(f"unknown planes {unknown}")
+        view = _warp_view((K, width, height), self.options.near_z if near is None else near)
+        opt = options if isinstance(options, VolumeRaycastOptions) else volume_raycast_options(**(options or {}))
+        ok = view.width >= 1 and view.height >= 1 and view.width * view.height <= 1 << 26  # (the entry rejects the rest)
+        out = {p: np.empty((view.height, view.width) if ok else (1, 1), kinds[p]) for p in kinds if p in planes}
+        T = None if pose is None else _pose_cm(pose)
+        st = CVolumeRaycastStats()
+        ptr = [out[p].ctypes.data_as(C.POINTER(C.c_float if p != "weight" else C.c_int)) if p in out else None
+               for p in ("depth", "intensity", "weight")]
+        _check(lib().dvo_amd_volume_raycast(self._h, None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(view),
+                                            C.byref(opt), ptr[0], ptr[1], ptr[2], C.byref(st)), "dvo_amd_volume_raycast")
+        out["stats"] = {n: getattr(st, n) for n, _ in CVolumeRaycastStats._fields_}
+        return out
+
+    def raycast_pyramid(self, pose, K, width: int, height: int, levels: int, near=None, options=None, timestamp: float = 0.0):
+        """The same view as an RgbdImagePyramid built on the device from the raycast planes (dvo_amd_volume_raycast_pyramid): every
+        pixel that is not hit and coloured is empty (depth NaN, intensity fill_intensity).  The stats are left in `raycast_stats`."""
+        view = _warp_view((K, width, height), self.options.near_z if near is None else near)
+        opt = options if isinstance(options, VolumeRaycastOptions) else volume_raycast_options(**(options or {}))
+        T = None if pose is None else _pose_cm(pose)
+        st = CVolumeRaycastStats()
+        pyr = RgbdImagePyramid.__new__(RgbdImagePyramid)
+        pyr._h = C.c_void_p()
+        _check(lib().dvo_amd_volume_raycast_pyramid(self._h, None if T is None else T.ctypes.data_as(C.POINTER(C.c_double)), C.byref(view),
+                                                    C.byref(opt), levels, timestamp, C.byref(pyr._h), C.byref(st)),
+               "dvo_amd_volume_raycast_pyramid")
+        pyr.device, pyr.registration_stats = self.device, None
+        pyr.raycast_stats = {n: getattr(st, n) for n, _ in CVolumeRaycastStats._fields_}
+        return pyr
+
+    def extract(self, min_weight: int = 1, capacity: int | None = None):
+        """the surface crossings as (xyz float32 [n, 3], rgb uint32 [n], counts dict) in ascending 3*L + a (dvo_amd_volume_extract).
+        capacity=None: asked of the library first; a given capacity that is too small raises DvoAmdError (status 7)"""
+        n, cnt = C.c_longlong(), CVolumeExtractCounts()
+        cap = 0 if capacity is None else int(capacity)
+        out = np.empty((max(1, cap), 4), np.float32)
+        rc = lib().dvo_amd_volume_extract(self._h, min_weight, out.ctypes.data, cap, C.byref(n), C.byref(cnt))
+        if rc == 7 and capacity is None:  # DVO_AMD_ERR_CAPACITY: n is the size needed
+            cap = int(n.value)
+            out = np.empty((max(1, cap), 4), np.float32)
+            rc = lib().dvo_amd_volume_extract(self._h, min_weight, out.ctypes.data, cap, C.byref(n), C.byref(cnt))
+        self.last_extract_size = int(n.value)
+        _check(rc, "dvo_amd_volume_extract")
+        xyz, rgb = _split_points(out[:n.value])
+        return xyz, rgb, {"points": cnt.points, "uncoloured": cnt.uncoloured}
 
 
 def pack_keyframes(keyframes):

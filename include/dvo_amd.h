@@ -1723,6 +1723,153 @@ int dvo_amd_pyramid_warp_forward(const dvo_amd_pyramid *moving, const double *T,
 int dvo_amd_pyramid_warp_forward_many(int n, const dvo_amd_pyramid *const *moving, const double *T, const dvo_amd_view *views,
                                       const dvo_amd_warp_options *opt, dvo_amd_pyramid **out, long long *counts);
 
+/*
+ * A truncated signed-distance volume on the device (dvo_amd_volume): keyframes fused into a dense voxel grid that is raycast
+ * into a hole-free, denoised model view and from which surface points are pulled.  Context-free like the place index and the
+ * warps: the device's prep stream, scratch from the slab pool, no tracker slot; calls on one volume are serialised by the caller.
+ *
+ * The store.  nx*ny*nz voxels, index L = (iz*ny + iy)*nx + ix (x fastest); origin is the world position of voxel (0,0,0)'s centre.
+ * Per voxel four int32 sums {w_sum, sd_sum, iw_sum, i_sum} (dvo_amd_volume_voxel), all taken modulo 2^32, so subtracting what was
+ * added is exact even after a wrap.  With |q| <= 2047 and a weight <= 256 per observation no sum has wrapped while a voxel holds
+ * at most 4096 full-weight observations (4096 * 256 * 2047 < 2^31; i_sum: at most 2056 of them at the brightest grey value 4080).
+ *
+ * The integration rule, per voxel (ix,iy,iz) and frame (level `level` of a pyramid: intrinsics fx,fy,ox,oy, size w x h, planes Z
+ * and I); all arithmetic fp32, every operation rounded on its own (no contraction), divisions correctly rounded.  pose: camera ->
+ * world, column-major 4x4 doubles, NULL = identity; the host forms the rigid inverse M in double exactly as dvo_amd_map_render's
+ * step 2 does and casts every entry to float.
+ *  1. x = origin[0] + (float)ix*voxel, y and z alike; c_r = ((M_r0*x + M_r1*y) + M_r2*z) + M_r3 for r = x, y, z.  Position and
+ *     transformation are formed from the indices for every voxel (a running sum along an axis would round differently);
+ *  2. !(cz >= near_z): skip;
+ *  3. px = (cx*fx)/cz + ox, py = (cy*fy)/cz + oy; pu = floorf(px + 0.5f), pv = floorf(py + 0.5f);
+ *  4. !(0 <= pu && pu <= (float)(w-1) && 0 <= pv && pv <= (float)(h-1)), compared in float before any conversion: skip;
+ *  5. Zs = Z[pv,pu], Is = I[pv,pu]; !(isfinite(Zs) && isfinite(Is) && Zs <= far_z): skip;
+ *  6. d = Zs - cz; d < -trunc: skip (hidden);
+ *  7. near = d <= trunc; dc = fminf(d, trunc); q = (int)rintf((dc/trunc)*2047.0f);
+ *  8. weight: DVO_AMD_VOLUME_WEIGHT_CONSTANT: wgt = 1.  DVO_AMD_VOLUME_WEIGHT_SENSOR: s = 0.0012f + 0.0019f*((Zs-0.4f)*(Zs-0.4f))
+ *     (depthStdDevZ), wgt = (int)fminf(fmaxf(rintf(256.0f*((0.0012f*0.0012f)/(s*s))), 1.0f), 256.0f);
+ *  9. g = (int)fminf(fmaxf(rintf(Is*16.0f), 0.0f), 4080.0f);
+ * 10. with sign = +1 or -1: w_sum += sign*wgt, sd_sum += sign*wgt*q; where near: iw_sum += sign*wgt, i_sum += sign*wgt*g.
+ * Per frame three integer counts come back (dvo_amd_volume_counts): updated = near + free, the voxels that reached step 10.
+ * A voxel with cz > far_z + trunc can never be updated, so the host bounds every frame by a conservative index box of (its
+ * frustum between near_z and far_z + trunc) intersected with the volume, computed in double with a margin of a voxel; the launch
+ * covers the union of the call's boxes and a voxel outside a frame's box skips that frame.  Culling drops only what the rule
+ * skips: records and counts do not depend on it.
+ *
+ * Entries.  dvo_amd_volume_integrate is the anonymous form (no bookkeeping; sign -1 undoes sign +1 exactly).  The tracked form
+ * mirrors the map: insert retains the pyramids until remove or destroy, set_poses subtracts a keyframe at its stored float inverse
+ * pose and adds it at the new one in the same launch (a new pose whose inverse casts to the same floats does nothing), remove
+ * subtracts.  One call is one kernel launch and one synchronisation whatever n is: a lane accumulates all frames of the call for
+ * its voxel in registers and reads and writes each plane once.
+ * The contract: after any sequence of successful calls the records equal those of a fresh volume into which the keyframes now
+ * present were integrated at their current poses in one call -- bit for bit, independent of order, batching and launch geometry.
+ * Errors: a failed call leaves the volume as it was.  DVO_AMD_ERR_INVALID_ARGUMENT with a reason in dvo_amd_last_error() that starts
+ * with the entry's name: a NULL pointer (also inside an array); n < 0; a level beyond a pyramid (or negative); a non-finite pose
+ * entry; sign other than +1 / -1; insert of an id already present, an unknown id in set_poses or remove, the same id twice in one
+ * call; in create: a dimension outside 2..2048, nx*ny*nz > 2^30, voxel, trunc, near_z or far_z not finite and positive,
+ * trunc < voxel, far_z <= near_z, a non-finite origin, an unknown weight.  Then DVO_AMD_ERR_DEVICE_MISMATCH, then
+ * DVO_AMD_ERR_NO_DEVICE.  n == 0 is OK and does nothing.
+ * dvo_amd_volume_download returns the records of an index box {x0,y0,z0,x1,y1,z1} (inclusive, NULL: the whole volume) in the
+ * order of L; a capacity too small: DVO_AMD_ERR_CAPACITY with *n_out the size needed and records untouched.
+ *
+ * The raycast.  view: a dvo_amd_view, its near_z is where the march starts; step = step_fraction*trunc (fp32);
+ * step_fraction in (0, 1], min_weight >= 1, fill_intensity finite and (far_z - near_z)/step <= 8192 or
+ * DVO_AMD_ERR_INVALID_ARGUMENT; the view is checked as dvo_amd_warp_forward checks one.  Per pixel (u,v), with rows P of `pose`
+ * cast to float:
+ *  1. rx = ((float)u - ox)/fx, ry = ((float)v - oy)/fy;
+ *  2. sample k is at t_k = near_z + (float)k*step (this product, never an accumulation); the march goes on while t_k <= far_z;
+ *  3. x = rx*t, y = ry*t; p_r = ((P_r0*x + P_r1*y) + P_r2*t) + P_r3; g_a = (p_a - origin[a])/voxel;
+ *  4. the sample is known iff 0 <= g_a && g_a < (float)(n_a - 1) on all axes (false for NaN) and all eight corners have
+ *     w_sum >= min_weight;
+ *  5. a corner's value is Fv = (float)sd_sum/(float)w_sum; trilinear blend with i0 = floorf(g), fr = g - i0: along x first,
+ *     c00 = F000 + fr_x*(F100 - F000) and likewise c10 (y+1), c01 (z+1), c11 (y+1, z+1); then y, c0 = c00 + fr_y*(c10 - c00)
+ *     and c1 = c01 + fr_y*(c11 - c01); then z, f = c0 + fr_z*(c1 - c0);
+ *  6. with the previous sample known: f_prev > 0 && f <= 0 is a hit at t* = t_prev + step*(f_prev/(f_prev - f));
+ *     f_prev < 0 && f > 0 ends the ray empty (backface); an unknown sample forgets f_prev; a ray that ends otherwise is missed;
+ *  7. depth = t* (the ray's z component is 1: the camera's z depth);
+ *  8. intensity: steps 3 to 5 at t = t* with Gv = (float)i_sum/(float)iw_sum in Fv's place, times 0.0625f; valid iff that sample
+ *     satisfies step 4's inequalities and all eight corners have iw_sum > 0, otherwise the pixel counts as uncoloured and its
+ *     intensity is empty;
+ *  9. weight (may be NULL): w_sum of the corner nearest to the sample at t*, i0 + (fr >= 0.5f ? 1 : 0) per axis; 0 where the pixel
+ *     is not hit or that sample fails step 4's inequalities;
+ * 10. empty values are NaN (0x7FC00000) in the plane form; in the pyramid form every pixel that is not hit and coloured is empty
+ *     in both planes (depth NaN, intensity fill_intensity), as dvo_amd_pyramid_warp_inverse does;
+ * 11. stats: pixels = hit + backface + missed; uncoloured counts hit pixels.
+ * One launch and one synchronisation per call; the pyramid form hands the device planes to the ordinary builder
+ * (dvo_amd_pyramid_create_from_device's rules for width, height and levels).  There is no empty-space skipping.
+ *
+ * The surface.  dvo_amd_volume_extract writes one dvo_amd_point per crossing: candidates are voxel L and axis a in {x,y,z} where
+ * the neighbour at +1 along a exists and both voxels have w_sum >= min_weight (>= 1); with Fa, Fb the two values (step 5's Fv)
+ * there is a crossing iff (Fa > 0 && Fb <= 0) || (Fa <= 0 && Fb > 0); s = Fa/(Fa - Fb); the coordinate along a is
+ * origin[a] + ((float)i_a + s)*voxel, the other two are the voxel centre's (step 1 of the integration rule).  Colour: with
+ * iw_sum > 0 on both voxels grey = (int)fminf(fmaxf(rintf((Ga + s*(Gb - Ga))*0.0625f), 0.0f), 255.0f), packed B = G = R; otherwise
+ * rgb = 0 and the point counts as uncoloured.  Points come in ascending 3*L + a.  Capacity as in dvo_amd_map_extract:
+ * DVO_AMD_ERR_CAPACITY with *n_out the size needed and out untouched.  The result goes straight into dvo_amd_write_pcd.
+ */
+#define DVO_AMD_VOLUME_WEIGHT_CONSTANT 0
+#define DVO_AMD_VOLUME_WEIGHT_SENSOR 1
+#define DVO_AMD_VOLUME_MAX_STEPS 8192
+
+typedef struct {
+  int nx, ny, nz;      /* 2..2048 each, nx*ny*nz <= 2^30 */
+  float voxel;         /* edge of a voxel in metres */
+  float origin[3];     /* world position of the centre of voxel (0,0,0) */
+  float trunc;         /* truncation distance, >= voxel */
+  float near_z, far_z; /* sensor depths used: cz >= near_z, Zs <= far_z */
+  int weight;          /* DVO_AMD_VOLUME_WEIGHT_CONSTANT or _SENSOR */
+} dvo_amd_volume_options;
+
+typedef struct {
+  int w_sum, sd_sum, iw_sum, i_sum;
+} dvo_amd_volume_voxel;
+
+typedef struct {
+  long long updated, near, free;
+} dvo_amd_volume_counts;
+
+typedef struct {
+  float step_fraction;  /* 0.5; in (0, 1] */
+  int min_weight;       /* 1; >= 1 */
+  float fill_intensity; /* 0: an empty pixel's intensity in the pyramid form */
+} dvo_amd_volume_raycast_options;
+
+typedef struct {
+  long long pixels, hit, backface, missed, uncoloured;
+} dvo_amd_volume_raycast_stats;
+
+typedef struct {
+  long long points, uncoloured;
+} dvo_amd_volume_extract_counts;
+
+typedef struct dvo_amd_volume dvo_amd_volume;
+/* 64 x 64 x 64 voxels of 0.05 m, origin (-1.6, -1.6, 0.4), trunc 0.15, near_z 0.4, far_z 5, sensor weights */
+void dvo_amd_default_volume_options(dvo_amd_volume_options *opt);
+/* step_fraction 0.5, min_weight 1, fill_intensity 0 */
+void dvo_amd_default_volume_raycast_options(dvo_amd_volume_raycast_options *opt);
+int dvo_amd_volume_create(int device, const dvo_amd_volume_options *opt, dvo_amd_volume **out);
+void dvo_amd_volume_destroy(dvo_amd_volume *vol);
+/* all records to zero; the keyframes of the tracked form are released */
+int dvo_amd_volume_clear(dvo_amd_volume *vol);
+int dvo_amd_volume_options_get(const dvo_amd_volume *vol, dvo_amd_volume_options *opt);
+/* poses: NULL (all identity) or n x 16 doubles, column-major each; counts: NULL or n records */
+int dvo_amd_volume_integrate(dvo_amd_volume *vol, int n, const dvo_amd_pyramid *const *pyramids, int level, const double *poses, int sign,
+                             dvo_amd_volume_counts *counts);
+int dvo_amd_volume_insert(dvo_amd_volume *vol, int n, const int *ids, dvo_amd_pyramid *const *pyramids, int level, const double *poses,
+                          dvo_amd_volume_counts *counts);
+int dvo_amd_volume_set_poses(dvo_amd_volume *vol, int n, const int *ids, const double *poses);
+int dvo_amd_volume_remove(dvo_amd_volume *vol, int n, const int *ids);
+/* n_keyframes: the keyframes of the tracked form; updated_total: the sum of their `updated` counts at their current poses */
+int dvo_amd_volume_stats(const dvo_amd_volume *vol, int *n_keyframes, long long *updated_total);
+/* box: NULL or {x0,y0,z0,x1,y1,z1}, inclusive voxel indices with 0 <= x0 <= x1 < nx and alike */
+int dvo_amd_volume_download(dvo_amd_volume *vol, const int *box, dvo_amd_volume_voxel *records, long long capacity, long long *n_out);
+/* any of depth / intensity / weight / stats may be NULL; each plane is width*height, row-major, host memory */
+int dvo_amd_volume_raycast(dvo_amd_volume *vol, const double *pose, const dvo_amd_view *view, const dvo_amd_volume_raycast_options *opt,
+                           float *depth, float *intensity, int *weight, dvo_amd_volume_raycast_stats *stats);
+int dvo_amd_volume_raycast_pyramid(dvo_amd_volume *vol, const double *pose, const dvo_amd_view *view,
+                                   const dvo_amd_volume_raycast_options *opt, int levels, double timestamp, dvo_amd_pyramid **out,
+                                   dvo_amd_volume_raycast_stats *stats);
+int dvo_amd_volume_extract(dvo_amd_volume *vol, int min_weight, dvo_amd_point *out, long long capacity, long long *n_out,
+                           dvo_amd_volume_extract_counts *counts);
+
 /* Binary PCD v0.7 as pcl::io::savePCDFileBinary writes a PointXYZRGB cloud: FIELDS x y z rgb, SIZE 4 4 4 4, TYPE F F F F
  * (rgb holds the packed bits), COUNT 1 1 1 1, WIDTH / HEIGHT as given (organized, or n x 1), VIEWPOINT 0 0 0 1 0 0 0,
  * POINTS width*height (= n), then the records.  Host code only. */

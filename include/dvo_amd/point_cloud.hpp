@@ -414,6 +414,168 @@ class KeyframeMap {
   float leaf_;
 };
 
+// The signed-distance volume kept on the device (dvo_amd.h: dvo_amd_volume_*), next to KeyframeMap: keyframes are fused into a
+// dense grid of integer sums -- inserted, moved and removed exactly --, raycast() gives a hole-free model view, raycastPyramid()
+// the same view as a reference any tracker entry accepts, extract() the surface crossings as a cloud.  Context-free: it needs no
+// tracker; calls on one volume are serialised by the caller.
+class SurfaceVolume {
+ public:
+  typedef AsyncPointCloudBuilder::PointCloud PointCloud;
+
+  // a raycast view: width * height values per plane, row-major; empty pixels hold NaN (weight 0)
+  struct View {
+    int width, height;
+    std::vector<float> depth, intensity;
+    std::vector<int> weight;
+    dvo_amd_volume_raycast_stats stats;
+  };
+
+  static dvo_amd_volume_options defaultOptions() {
+    dvo_amd_volume_options o;
+    dvo_amd_default_volume_options(&o);
+    return o;
+  }
+  static dvo_amd_volume_raycast_options defaultRaycastOptions() {
+    dvo_amd_volume_raycast_options o;
+    dvo_amd_default_volume_raycast_options(&o);
+    return o;
+  }
+
+  explicit SurfaceVolume(const dvo_amd_volume_options &options = defaultOptions(), int device = 0)
+      : device_(device), volume_(nullptr), options_(options) {
+    ::dvo::detail::check(dvo_amd_volume_create(device, &options, &volume_), "SurfaceVolume");
+  }
+  ~SurfaceVolume() { dvo_amd_volume_destroy(volume_); }
+  SurfaceVolume(const SurfaceVolume &) = delete;
+  SurfaceVolume &operator=(const SurfaceVolume &) = delete;
+
+  const dvo_amd_volume_options &options() const { return options_; }
+
+  // the anonymous form: `level` of every frame at its pose (camera -> world), added (sign +1) or subtracted (-1) in one launch
+  std::vector<dvo_amd_volume_counts> integrate(const std::vector<core::RgbdImagePyramid *> &frames,
+                                               const std::vector<core::AffineTransformd> &poses, int level = 0, int sign = 1) {
+    std::vector<dvo_amd_pyramid *> handles;
+    std::vector<double> flat;
+    pack("SurfaceVolume::integrate", frames, poses, level, handles, flat);
+    std::vector<dvo_amd_volume_counts> counts(frames.size());
+    ::dvo::detail::check(dvo_amd_volume_integrate(volume_, (int)frames.size(), handles.data(), level, flat.data(), sign, counts.data()),
+                         "SurfaceVolume::integrate");
+    return counts;
+  }
+  // the tracked form: the volume retains the pyramids until remove()
+  std::vector<dvo_amd_volume_counts> insert(const std::vector<int> &ids, const std::vector<core::RgbdImagePyramid *> &frames,
+                                            const std::vector<core::AffineTransformd> &poses, int level = 0) {
+    if (ids.size() != frames.size()) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "SurfaceVolume::insert: one id per frame");
+    std::vector<dvo_amd_pyramid *> handles;
+    std::vector<double> flat;
+    pack("SurfaceVolume::insert", frames, poses, level, handles, flat);
+    std::vector<dvo_amd_volume_counts> counts(frames.size());
+    ::dvo::detail::check(dvo_amd_volume_insert(volume_, (int)frames.size(), ids.data(), handles.data(), level, flat.data(), counts.data()),
+                         "SurfaceVolume::insert");
+    return counts;
+  }
+  void set_poses(const std::vector<int> &ids, const std::vector<core::AffineTransformd> &poses) {
+    if (ids.size() != poses.size()) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, "SurfaceVolume::set_poses: one pose per id");
+    std::vector<double> flat;
+    for (size_t i = 0; i < poses.size(); ++i) flat.insert(flat.end(), core::data(poses[i]), core::data(poses[i]) + 16);
+    ::dvo::detail::check(dvo_amd_volume_set_poses(volume_, (int)ids.size(), ids.data(), flat.data()), "SurfaceVolume::set_poses");
+  }
+  void remove(const std::vector<int> &ids) {
+    ::dvo::detail::check(dvo_amd_volume_remove(volume_, (int)ids.size(), ids.data()), "SurfaceVolume::remove");
+  }
+  void clear() { ::dvo::detail::check(dvo_amd_volume_clear(volume_), "SurfaceVolume::clear"); }
+  long long stats(int *n_keyframes = nullptr) const {
+    long long updated = 0;
+    ::dvo::detail::check(dvo_amd_volume_stats(volume_, n_keyframes, &updated), "SurfaceVolume::stats");
+    return updated;
+  }
+
+  // the records of the inclusive index box {x0,y0,z0,x1,y1,z1} (null: the whole volume), x fastest
+  void download(std::vector<dvo_amd_volume_voxel> &out, const int *box = nullptr) {
+    long long n = 0;
+    int rc = dvo_amd_volume_download(volume_, box, nullptr, 0, &n);
+    if (rc == DVO_AMD_ERR_CAPACITY) {
+      out.resize((size_t)n);
+      rc = dvo_amd_volume_download(volume_, box, out.data(), (long long)out.size(), &n);
+    }
+    ::dvo::detail::check(rc, "SurfaceVolume::download");
+    out.resize((size_t)n);
+  }
+
+  // near_z <= 0: the volume's near_z
+  dvo_amd_view view(const core::IntrinsicMatrix &K, int width, int height, float near_z = 0.0f) const {
+    dvo_amd_view v;
+    v.width = width, v.height = height, v.fx = K.fx(), v.fy = K.fy(), v.ox = K.ox(), v.oy = K.oy();
+    v.near_z = near_z > 0.0f ? near_z : options_.near_z;
+    return v;
+  }
+  void raycast(const core::AffineTransformd &pose, const core::IntrinsicMatrix &K, int width, int height, View &out, float near_z = 0.0f,
+               const dvo_amd_volume_raycast_options &options = defaultRaycastOptions()) {
+    const dvo_amd_view v = view(K, width, height, near_z);
+    const size_t n = width > 0 && height > 0 ? (size_t)width * (size_t)height : 0;
+    out.width = width, out.height = height;
+    out.depth.resize(n), out.intensity.resize(n), out.weight.resize(n);
+    ::dvo::detail::check(dvo_amd_volume_raycast(volume_, core::data(pose), &v, &options, out.depth.data(), out.intensity.data(),
+                                                out.weight.data(), &out.stats),
+                         "SurfaceVolume::raycast");
+  }
+  core::RgbdImagePyramidPtr raycastPyramid(const core::AffineTransformd &pose, const core::IntrinsicMatrix &K, int width, int height,
+                                           int levels, float near_z = 0.0f,
+                                           const dvo_amd_volume_raycast_options &options = defaultRaycastOptions(), double timestamp = 0.0,
+                                           dvo_amd_volume_raycast_stats *stats = nullptr) {
+    const dvo_amd_view v = view(K, width, height, near_z);
+    dvo_amd_pyramid *pyr = nullptr;
+    ::dvo::detail::check(dvo_amd_volume_raycast_pyramid(volume_, core::data(pose), &v, &options, levels, timestamp, &pyr, stats),
+                         "SurfaceVolume::raycastPyramid");
+    try {
+      return core::RgbdImagePyramidPtr(new core::RgbdImagePyramid(pyr, width, height, K, device_, timestamp));
+    } catch (...) {  // (the adopting object was never made: the handle is still ours)
+      dvo_amd_pyramid_release(pyr);
+      throw;
+    }
+  }
+
+  // the surface crossings in ascending 3*L + a
+  void records(std::vector<dvo_amd_point> &out, int min_weight = 1, dvo_amd_volume_extract_counts *counts = nullptr) {
+    long long n = 0;
+    int rc = dvo_amd_volume_extract(volume_, min_weight, nullptr, 0, &n, counts);
+    if (rc == DVO_AMD_ERR_CAPACITY) {
+      out.resize((size_t)n);
+      rc = dvo_amd_volume_extract(volume_, min_weight, out.data(), (long long)out.size(), &n, counts);
+    }
+    ::dvo::detail::check(rc, "SurfaceVolume::extract");
+    out.resize((size_t)n);
+  }
+  PointCloud::Ptr extract(int min_weight = 1) {
+    std::vector<dvo_amd_point> points;
+    records(points, min_weight);
+    PointCloud::Ptr out(new PointCloud);
+    out->reserve(points.size());
+    for (size_t i = 0; i < points.size(); ++i) out->points.push_back(detail::from_record(points[i]));
+    out->width = (std::uint32_t)points.size(), out->height = 1;
+    return out;
+  }
+
+  dvo_amd_volume *handle() const { return volume_; }
+
+ private:
+  static void pack(const char *where, const std::vector<core::RgbdImagePyramid *> &frames, const std::vector<core::AffineTransformd> &poses,
+                   int level, std::vector<dvo_amd_pyramid *> &handles, std::vector<double> &flat) {
+    if (frames.size() != poses.size()) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+    for (size_t i = 0; i < frames.size(); ++i) {
+      if (!frames[i]) throw DvoAmdError(DVO_AMD_ERR_INVALID_ARGUMENT, where);
+      frames[i]->build((size_t)(level < 0 ? 0 : level) + 1);
+      handles.push_back(frames[i]->handle());
+      flat.insert(flat.end(), core::data(poses[i]), core::data(poses[i]) + 16);
+    }
+    if (flat.empty()) flat.resize(16);  // (n == 0: the entries still want arrays)
+  }
+
+  int device_;
+  dvo_amd_volume *volume_;
+  dvo_amd_volume_options options_;
+};
+
 }  // namespace visualization
 }  // namespace dvo
 

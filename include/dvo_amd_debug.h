@@ -288,6 +288,13 @@ int dvo_amd_debug_components_timing(int device, int enable, double *last_ms);
  * the pyramids' build) and *last_ms receives the device time of the most recent bracketed call.  Any output may be NULL; all
  * zero before the first such call */
 int dvo_amd_debug_warp_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms);
+/* what the most recent successful dvo_amd_volume_integrate / _insert / _set_poses / _remove / _raycast / _raycast_pyramid / _extract
+ * on `device` enqueued of its own: kernel launches (1 for an integration of any n and for a raycast, 3 for an extract: count, scan,
+ * write; 2 when it ends at the capacity check) and host synchronisations (1; an extract: 2, the total comes back before the write);
+ * a raycast pyramid's builder comes on top.  With enable != 0 the launches of every later such call are bracketed by two events on
+ * the device's internal stream (the launches alone) and *last_ms receives the device time of the most recent bracketed call.  Any
+ * output may be NULL; all zero before the first such call */
+int dvo_amd_debug_volume_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms);
 
 #ifdef __cplusplus
 }
