@@ -16,7 +16,8 @@ CPP := $(SRC)/dvo_kernels.hip $(SRC)/dvo_pyramid.cpp $(SRC)/dvo_tracker.cpp $(SR
        $(SRC)/dvo_exposure.cpp $(SRC)/dvo_warp.cpp $(SRC)/dvo_volume.cpp
 
 $(LIB): $(CPP) $(SRC)/dvo_types.h $(SRC)/dvo_internal.h $(SRC)/se3.h $(SRC)/dvo_graph_device.h $(SRC)/dvo_graph_host.h \
-        $(SRC)/dvo_components_core.h $(SRC)/dvo_exposure_solve.h $(SRC)/dvo_volume_box.h include/dvo_amd.h include/dvo_amd_debug.h
+        $(SRC)/dvo_components_core.h $(SRC)/dvo_exposure_solve.h $(SRC)/dvo_volume_box.h $(SRC)/dvo_launch_rules.h \
+        $(SRC)/dvo_call.h $(SRC)/dvo_device_rules.h include/dvo_amd.h include/dvo_amd_debug.h
 	$(HIPCC) $(FLAGS) '-DDVO_AMD_BUILD_ID="$(BUILD_ID)"' -x hip $(CPP) -lz -o $@
 
 oracle:

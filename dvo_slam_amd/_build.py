@@ -23,7 +23,7 @@ SOURCES = ["dvo_kernels.hip", "dvo_pyramid.cpp", "dvo_tracker.cpp", "dvo_sharded
            "dvo_depth_filter.cpp", "dvo_components.cpp", "dvo_pose_score.cpp", "dvo_exposure.cpp",
            "dvo_warp.cpp", "dvo_volume.cpp"]
 HEADERS = ["dvo_types.h", "dvo_internal.h", "se3.h", "dvo_graph_device.h", "dvo_graph_host.h", "dvo_components_core.h", "dvo_exposure_solve.h",
-           "dvo_volume_box.h",
+           "dvo_volume_box.h", "dvo_launch_rules.h", "dvo_call.h", "dvo_device_rules.h",
            os.path.join("..", "..", "include", "dvo_amd.h"),
            os.path.join("..", "..", "include", "dvo_amd_debug.h")]
 FLAGS = [

@@ -22,6 +22,7 @@
 // of the inputs alone and two runs are bit-identical.  Nothing here waits for another thread: the only loops that depend on other
 // threads' writes are cc_union's retry and the 16-bit compare-and-swap, and both are bounded (see the core header).
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 #include <algorithm>
 #include <climits>
@@ -86,13 +87,7 @@ __device__ __forceinline__ float cc_pixel(const Plane &R, int x, int y) {
   if (R.mask && R.mask[at] == 0) return __builtin_nanf("");
   if (!R.z) return 0.0f;
   const float z = R.z[at];
-  return fabsf(z) <= 3.402823466e38f ? z : __builtin_nanf("");
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-  return v;
+  return rules::finite_f(z) ? z : __builtin_nanf("");
 }
 
 __global__ void __launch_bounds__(kBlock) k_cc_local(const Plane *__restrict__ planes, int n_planes, int connectivity, float max_step,
@@ -140,7 +135,7 @@ __global__ void __launch_bounds__(kBlock) k_cc_local(const Plane *__restrict__ p
       lab[(r0 + k) * kTile + col] = (unsigned short)((r0 + k) * kTile + col);
       pw = zw, pc = zc, pe = ze;
     }
-    n_fg = wave_sum(n_fg), n_cut = wave_sum(n_cut);
+    n_fg = rules::wave_sum(n_fg), n_cut = rules::wave_sum(n_cut);
     if ((threadIdx.x & 63) == 0) {
       if (n_fg) atomicAdd(R.counts + 0, (unsigned long long)n_fg);
       if (n_cut) atomicAdd(R.counts + 5, (unsigned long long)n_cut);
@@ -350,39 +345,11 @@ namespace {
 // dvo_amd_debug_components_timing: two events around the launches of a call on the prep stream (off unless asked for).  One pair
 // of events per device, recorded without the device's mutex: a diagnostic for one thread at a time.  Two threads that call on one
 // device with timing on may interleave their records, and last_ms then spans parts of both calls.
-struct Timing {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double last_ms = 0.0;
-};
-Timing g_timing[kMaxDevices];
-
-struct Bracket {
-  Timing &t;
-  bool timed;
-  explicit Bracket(int device) : t(g_timing[device]), timed(false) {
-    std::lock_guard<std::mutex> lk(t.mu);
-    timed = t.on && t.ev[0] && t.ev[1];
-  }
-  hipError_t begin(hipStream_t st) { return timed ? hipEventRecord(t.ev[0], st) : hipSuccess; }
-  hipError_t end(hipStream_t st) { return timed ? hipEventRecord(t.ev[1], st) : hipSuccess; }
-  void read() {
-    if (!timed) return;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(t.mu);
-    t.last_ms = ms;
-  }
-};
+DeviceTiming g_timing[kMaxDevices];
 
 // the plane table, the counts and the working planes of the call in flight: grown to the largest call and kept, used with the
 // device's mutex held from the table's upload to the last thing enqueued that touches it (as dvo_mask_ops.cpp's warp area)
-struct Area {
-  void *mem = nullptr;
-  size_t bytes = 0;
-};
-Area g_area[kMaxDevices];
+DeviceBuf g_area[kMaxDevices];
 
 void drop(dvo_amd_mask *m) {
   (void)hipFree(m->mem);
@@ -457,18 +424,7 @@ Layout layout(size_t n_planes, size_t pixels) {
   return L;
 }
 
-int grow_area(Area &area, size_t bytes) {
-  if (area.bytes >= bytes) return DVO_AMD_OK;
-  if (area.mem) (void)hipFree(area.mem), area.mem = nullptr, area.bytes = 0;  // (hipFree waits for whatever still reads it)
-  const size_t grown = align_up(bytes, 1 << 20);
-  const hipError_t e = hipMalloc(&area.mem, grown);
-  if (e != hipSuccess) {
-    area.mem = nullptr;
-    return e == hipErrorOutOfMemory ? (int)DVO_AMD_ERR_OUT_OF_MEMORY : fail_hip("hipMalloc (components area)", e);
-  }
-  area.bytes = grown;
-  return DVO_AMD_OK;
-}
+int grow_area(DeviceBuf &area, size_t bytes) { return grow(area, bytes, 1 << 20, "components area"); }
 
 // the table of a call's planes in the area at `base`; out[k] may be null (dvo_amd_mask_components)
 void fill_table(std::vector<Plane> &table, const std::vector<Item> &items, const std::vector<int> &first_level, const std::vector<int> &n_levels,
@@ -501,23 +457,18 @@ void fill_table(std::vector<Plane> &table, const std::vector<Item> &items, const
   }
 }
 
-// a launch holds fewer than 2^31 threads and at most 65535 rows of blocks: a block takes further planes in steps of gridDim.y
-unsigned rows_of_blocks(size_t n_planes, unsigned gx, int block) {
-  return (unsigned)std::max<long long>(1, std::min<long long>(std::min<long long>((long long)n_planes, 65535), (1ll << 31) / ((long long)gx * block)));
-}
-
 // k_cc_local, k_cc_border, k_cc_flatten: the labelling, shared by the filter and the inspection entry
 hipError_t launch_labelling(const Plane *d_table, size_t n_planes, int max_n, int max_tiles, const dvo_amd_component_options *opt,
                             hipStream_t st) {
   const unsigned gt = (unsigned)max_tiles, g4 = (unsigned)((max_n + kChunk - 1) / kChunk), g1 = (unsigned)((max_n + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_cc_local, dim3(gt, rows_of_blocks(n_planes, gt, kBlock)), dim3(kBlock), 0, st, d_table, (int)n_planes,
+  hipLaunchKernelGGL(k_cc_local, dim3(gt, grid_rows((long long)n_planes, gt, kBlock)), dim3(kBlock), 0, st, d_table, (int)n_planes,
                      opt->connectivity, opt->max_step, opt->depth_sigmas);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_cc_border, dim3(g4, rows_of_blocks(n_planes, g4, kBlock)), dim3(kBlock), 0, st, d_table, (int)n_planes);
+  hipLaunchKernelGGL(k_cc_border, dim3(g4, grid_rows((long long)n_planes, g4, kBlock)), dim3(kBlock), 0, st, d_table, (int)n_planes);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_cc_flatten, dim3(g1, rows_of_blocks(n_planes, g1, kBlock)), dim3(kBlock), 0, st, d_table, (int)n_planes);
+  hipLaunchKernelGGL(k_cc_flatten, dim3(g1, grid_rows((long long)n_planes, g1, kBlock)), dim3(kBlock), 0, st, d_table, (int)n_planes);
   return hipGetLastError();
 }
 
@@ -560,20 +511,20 @@ int filter_many(const char *entry, bool single, int n, const dvo_amd_mask *const
       if (m) drop(m);
     return status;
   };
-  Bracket bracket(device);
+  Bracket bracket(g_timing[device]);
   for (int k = 0; k < n; ++k) {
     rc = mask_alloc(entry, device, items[(size_t)k].w, items[(size_t)k].h, items[(size_t)k].levels, &made[(size_t)k], &st);
     if (rc) return unwind(rc);
   }
   const Layout L = layout(n_planes, pixels);
   std::unique_lock<std::mutex> area_lock(device_mutex(device));
-  Area &area = g_area[device];
+  DeviceBuf &area = g_area[device];
   rc = grow_area(area, L.total);
   if (rc) {
     area_lock.unlock();
     return unwind(rc);
   }
-  char *base = (char *)area.mem;
+  char *base = (char *)area.p;
   std::vector<Plane> table(n_planes);
   std::vector<int> first((size_t)n, 0), levels((size_t)n);
   for (int k = 0; k < n; ++k) levels[(size_t)k] = items[(size_t)k].levels;
@@ -593,7 +544,7 @@ int filter_many(const char *entry, bool single, int n, const dvo_amd_mask *const
   }
   if (e == hipSuccess) {
     const unsigned g4 = (unsigned)((max_n + kChunk - 1) / kChunk);
-    hipLaunchKernelGGL(k_cc_write, dim3(g4, rows_of_blocks(n_planes, g4, kBlock)), dim3(kBlock), 0, st, d_table, (int)n_planes);
+    hipLaunchKernelGGL(k_cc_write, dim3(g4, grid_rows((long long)n_planes, g4, kBlock)), dim3(kBlock), 0, st, d_table, (int)n_planes);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = bracket.end(st);
@@ -680,16 +631,16 @@ int dvo_amd_mask_components(const dvo_amd_mask *mask, const dvo_amd_pyramid *dep
   if (rc) return rc;
   const size_t n = (size_t)(it.w >> level) * (size_t)(it.h >> level);
   const Layout L = layout(1, align_up(n, 256));
-  Bracket bracket(device);
+  Bracket bracket(g_timing[device]);
   std::vector<int> h_parent(n), h_roots, h_rec;
   unsigned long long h_counts[kPlaneCounts] = {};
   size_t n_written = 0;
   {
     std::unique_lock<std::mutex> area_lock(device_mutex(device));
-    Area &area = g_area[device];
+    DeviceBuf &area = g_area[device];
     rc = grow_area(area, L.total);
     if (rc) return rc;
-    char *base = (char *)area.mem;
+    char *base = (char *)area.p;
     std::vector<Plane> table(1);
     int max_n = 1, max_tiles = 1;
     fill_table(table, items, std::vector<int>(1, level), std::vector<int>(1, 1), std::vector<dvo_amd_mask *>(1, nullptr), opt, base, L, &max_n,
@@ -737,20 +688,7 @@ int dvo_amd_mask_components(const dvo_amd_mask *mask, const dvo_amd_pyramid *dep
 /* instrumentation: with enable != 0 every later dvo_amd_mask_filter_components / _many and dvo_amd_mask_components on `device` is
  * bracketed by two events on the prep stream; *last_ms (may be NULL) receives the device time of the most recent bracketed call */
 int dvo_amd_debug_components_timing(int device, int enable, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  Timing &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, nullptr, nullptr, last_ms);
 }
 
 }  // extern "C"

@@ -81,7 +81,7 @@ DVO_CC_HD bool cc_depth_edge(float za, float zb, float max_step, float depth_sig
   const float zn = za < zb ? za : zb;  // fminf of two finite numbers
   const float t = zn - 0.4f;
   const float tt = t * t;
-  const float s = 0.0019f * tt;
+  const float s = 0.0019f * tt;  // (the sensor sigma step by step, not rules::depth_sigma: this header is compiled for the host alone too)
   const float m = 0.0012f + s;
   const float tol = max_step + depth_sigmas * m;
   const float d = za - zb;

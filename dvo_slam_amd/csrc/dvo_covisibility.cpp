@@ -6,6 +6,7 @@
 //             projected and classified against b's depth plane; the seven counts are reduced per wave (ballots), per block (LDS)
 //             and added to the pair's record with one integer atomic per non-zero count
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -40,8 +41,6 @@ __global__ void __launch_bounds__(kBlock) k_covis(const Pair *__restrict__ pairs
     const int na = P.na;
     const int base = blockIdx.x * kChunk + wave * (kSteps * 64);
     if (blockIdx.x * kChunk >= na) continue;  // (block-uniform: no barrier is skipped by part of a block)
-    const float *T = P.T;
-    const float wmax = (float)(P.wb - 1), hmax = (float)(P.hb - 1);
     unsigned cnt[kCounts] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
 #pragma unroll
     for (int k = 0; k < kSteps; ++k) {
@@ -49,31 +48,10 @@ __global__ void __launch_bounds__(kBlock) k_covis(const Pair *__restrict__ pairs
       int cls = -1;  // -1: no pixel or no depth; else the index of the outcome's count
       if (p < na) {
         const float z = P.za[p];
-        if (fabsf(z) <= 3.402823466e38f) {  // finite (false for NaN)
+        if (rules::finite_f(z)) {
           const int v = p / P.wa, u = p - v * P.wa;
-          const float x = P.txa[u] * z, y = P.tya[v] * z;
-          const float qx = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-          const float qy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-          const float qz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-          if (!(qz >= near_z)) {
-            cls = 1;
-          } else {
-            const float pu = floorf(((qx * P.fx) / qz + P.ox) + 0.5f);
-            const float pv = floorf(((qy * P.fy) / qz + P.oy) + 0.5f);
-            if (!(pu >= 0.0f && pu <= wmax && pv >= 0.0f && pv <= hmax)) {
-              cls = 2;
-            } else {
-              const float zb = P.zb[(size_t)(int)pv * P.wb + (int)pu];  // 0 <= pu <= wb-1, 0 <= pv <= hb-1: tested in float above
-              if (!(zb == zb)) {
-                cls = 3;
-              } else {
-                const float s = qz - 0.4f;
-                const float tol = sigmas * (0.0012f + 0.0019f * (s * s));
-                const float d = zb - qz;
-                cls = d < -tol ? 5 : (d > tol ? 6 : 4);
-              }
-            }
-          }
+          size_t at;
+          cls = rules::classify_covisible(z, P.txa[u], P.tya[v], P.T, near_z, sigmas, P.zb, P.wb, P.hb, P.fx, P.fy, P.ox, P.oy, at);
         }
       }
       cnt[0] += (unsigned)__popcll(__ballot(cls >= 0));
@@ -100,23 +78,16 @@ __global__ void __launch_bounds__(kBlock) k_covis(const Pair *__restrict__ pairs
 namespace host {
 
 struct CovisWorkspace {
-  void *pairs = nullptr, *out = nullptr;
-  size_t pairs_bytes = 0, out_bytes = 0;
+  DeviceBuf pairs, out;
   hipEvent_t ev[2] = {nullptr, nullptr};
   double device_ms = 0.0;
 };
 
 namespace {
 
-int grow_covis(void **p, size_t *have, size_t bytes) {
-  if (bytes <= *have) return DVO_AMD_OK;
-  if (*p) (void)hipFree(*p), *p = nullptr, *have = 0;
-  bytes = align_up(std::max(bytes, 2 * *have), 1 << 16);
-  const hipError_t e = hipMalloc(p, bytes);
-  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
-  if (e != hipSuccess) return fail_hip("hipMalloc (covisibility workspace)", e);
-  *have = bytes;
-  return DVO_AMD_OK;
+// (a buffer that has to grow at least doubles)
+int grow_covis(DeviceBuf &b, size_t bytes) {
+  return grow(b, bytes <= b.bytes ? bytes : std::max(bytes, 2 * b.bytes), 1 << 16, "covisibility workspace");
 }
 
 int check_options(const char *entry, const dvo_amd_covisibility_options *opt) {
@@ -140,17 +111,6 @@ int check_pairs(const char *entry, int n_keyframes, const dvo_amd_keyframe *keyf
     }
   }
   return n_pairs > 0 || opt ? check_options(entry, opt) : DVO_AMD_OK;
-}
-
-// rows 0..2 of pose_b^-1 * pose_a in double, the inverse taken as rigid, every product and sum rounded on its own in index
-// order, then cast to float (dvo_amd.h, rule 1).  Column-major poses: R[i][j] = P[j * 4 + i], t[i] = P[12 + i].
-void relative_transform(const double *A, const double *B, float T[12]) {
-  for (int r = 0; r < 3; ++r) {
-    const double i0 = B[r * 4 + 0], i1 = B[r * 4 + 1], i2 = B[r * 4 + 2];  // row r of Rb^T
-    const double ti = -((i0 * B[12] + i1 * B[13]) + i2 * B[14]);
-    for (int c = 0; c < 3; ++c) T[r * 4 + c] = (float)((i0 * A[c * 4 + 0] + i1 * A[c * 4 + 1]) + i2 * A[c * 4 + 2]);
-    T[r * 4 + 3] = (float)(((i0 * A[12] + i1 * A[13]) + i2 * A[14]) + ti);
-  }
 }
 
 int covisibility(dvo_amd_context *ctx, int n_keyframes, const dvo_amd_keyframe *keyframes, const dvo_amd_covisibility_options *opt,
@@ -184,25 +144,24 @@ int covisibility(dvo_amd_context *ctx, int n_keyframes, const dvo_amd_keyframe *
     P.za = A.z_plane, P.txa = A.tx, P.tya = A.ty, P.zb = B.z_plane;
     P.wa = A.w, P.na = A.w * A.h, P.wb = B.w, P.hb = B.h;
     P.fx = B.fx, P.fy = B.fy, P.ox = B.ox, P.oy = B.oy;
-    relative_transform(ka.pose, kb.pose, P.T);
+    relative_rows(ka.pose, kb.pose, P.T);
     max_na = std::max(max_na, P.na);
   }
   const size_t out_bytes = sizeof(dvo_amd_covisibility_counts) * (size_t)n_pairs;
-  rc = grow_covis(&W.pairs, &W.pairs_bytes, sizeof(covis::Pair) * (size_t)n_pairs);
-  if (!rc) rc = grow_covis(&W.out, &W.out_bytes, out_bytes);
+  rc = grow_covis(W.pairs, sizeof(covis::Pair) * (size_t)n_pairs);
+  if (!rc) rc = grow_covis(W.out, out_bytes);
   if (rc) return rc;
   const hipStream_t st = ctx->stream;
-  HIP_TRY(hipMemcpyAsync(W.pairs, table.data(), sizeof(covis::Pair) * (size_t)n_pairs, hipMemcpyHostToDevice, st));
-  HIP_TRY(hipMemsetAsync(W.out, 0, out_bytes, st));
+  HIP_TRY(hipMemcpyAsync(W.pairs.p, table.data(), sizeof(covis::Pair) * (size_t)n_pairs, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(W.out.p, 0, out_bytes, st));
   const unsigned gx = (unsigned)((max_na + covis::kChunk - 1) / covis::kChunk);
-  // a launch holds fewer than 2^31 threads and at most 65535 rows of blocks: a block takes further pairs in steps of gridDim.y
-  const unsigned gy = (unsigned)std::max<long long>(1, std::min<long long>(std::min(n_pairs, 65535), (1ll << 31) / ((long long)gx * covis::kBlock)));
+  const unsigned gy = grid_rows(n_pairs, gx, covis::kBlock);  // a block takes further pairs in steps of gridDim.y
   HIP_TRY(hipEventRecord(W.ev[0], st));
-  hipLaunchKernelGGL(covis::k_covis, dim3(gx, gy), dim3(covis::kBlock), 0, st, (const covis::Pair *)W.pairs, n_pairs, opt->near_z,
-                     opt->depth_sigmas, (unsigned *)W.out);
+  hipLaunchKernelGGL(covis::k_covis, dim3(gx, gy), dim3(covis::kBlock), 0, st, (const covis::Pair *)W.pairs.p, n_pairs, opt->near_z,
+                     opt->depth_sigmas, (unsigned *)W.out.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(W.ev[1], st));
-  HIP_TRY(hipMemcpyAsync(out, W.out, out_bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(out, W.out.p, out_bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
@@ -217,8 +176,8 @@ double overlap_of(const dvo_amd_covisibility_counts &c) { return c.valid ? (doub
 void covis_workspace_release(dvo_amd_context *ctx) {
   CovisWorkspace *w = ctx->covis_ws;
   if (!w) return;
-  if (w->pairs) (void)hipFree(w->pairs);
-  if (w->out) (void)hipFree(w->out);
+  if (w->pairs.p) (void)hipFree(w->pairs.p);
+  if (w->out.p) (void)hipFree(w->out.p);
   for (hipEvent_t e : w->ev)
     if (e) (void)hipEventDestroy(e);
   delete w;

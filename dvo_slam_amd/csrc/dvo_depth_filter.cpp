@@ -15,6 +15,7 @@
 // Counts (with_depth, kept, dropped, holes, filled) are ballots and popcounts per wave, integer adds into LDS per block and one
 // integer atomicAdd per non-zero count and block: integers only, no float atomic anywhere.
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -35,7 +36,6 @@ constexpr int kTable = kSide * kSide;  // the spatial weights of one window, at 
 static_assert(kBlock == 256 && kBlock % 64 == 0, "four waves per block");
 static_assert(DVO_AMD_DEPTH_FILTER_MAX_RADIUS == 8 && DVO_AMD_DEPTH_FILTER_COUNTS == 5, "the header's bounds");
 
-#define DEPTH_FILTER_GLOBAL __attribute__((address_space(1)))
 
 // one pyramid of one call as the kernel reads it (block-uniform: scalar registers)
 struct Record {
@@ -54,8 +54,6 @@ struct Params {
   float range_sigmas;
 };
 
-__device__ __forceinline__ bool finite(float v) { return fabsf(v) <= 3.402823466e38f; }  // (false for NaN)
-__device__ __forceinline__ float sigma(float z) { return 0.0012f + 0.0019f * ((z - 0.4f) * (z - 0.4f)); }  // depthStdDevZ
 
 // ws: (2 radius + 1)^2 weights of the filter window, then (2 fill_radius + 1)^2 of the fill window, rows dy, columns dx
 __global__ void __launch_bounds__(kBlock) k_depth_filter(const Record *__restrict__ records, int n_records, const float *__restrict__ ws,
@@ -80,8 +78,8 @@ __global__ void __launch_bounds__(kBlock) k_depth_filter(const Record *__restric
   const bool live = u < w && v < h;
   const int r = P.radius, fr = P.fill_radius;
   const int halo = max(r, fr);
-  const DEPTH_FILTER_GLOBAL float *Z = (const DEPTH_FILTER_GLOBAL float *)L.z;
-  const DEPTH_FILTER_GLOBAL float *WS = (const DEPTH_FILTER_GLOBAL float *)ws;
+  const DVO_DEVICE_GLOBAL float *Z = (const DVO_DEVICE_GLOBAL float *)L.z;
+  const DVO_DEVICE_GLOBAL float *WS = (const DVO_DEVICE_GLOBAL float *)ws;
   const float nan = __builtin_nanf("");
 
   if (threadIdx.x < kCounts) s_cnt[threadIdx.x] = 0u;
@@ -102,13 +100,13 @@ __global__ void __launch_bounds__(kBlock) k_depth_filter(const Record *__restric
   __syncthreads();  // (s_cnt is cleared; the tile is staged)
   if (halo != 0) zc = s_z[(ly + halo) * zw + lx + halo];  // (NaN for a thread outside the plane)
 
-  const bool has = live && finite(zc);
+  const bool has = live && rules::finite_f(zc);
   float out = nan;
   int n = 0;
   bool kept = false, filled = false;
   if (has) {
     // steps 1 and 2: the members of the window are the positions within s of the centre; a position outside the plane holds NaN
-    const float s = P.range_sigmas * sigma(zc);
+    const float s = P.range_sigmas * rules::depth_sigma(zc);
     const float ss = s * s;
     float sw = 0.0f, swd = 0.0f;
     if (halo == 0) {
@@ -139,23 +137,23 @@ __global__ void __launch_bounds__(kBlock) k_depth_filter(const Record *__restric
   } else if (live && fr > 0) {
     // step 3: a hole takes the weighted mean of the farthest surface in its window
     const int off = halo - fr, side = 2 * fr + 1;
-    const DEPTH_FILTER_GLOBAL float *WF = WS + (2 * r + 1) * (2 * r + 1);
+    const DVO_DEVICE_GLOBAL float *WF = WS + (2 * r + 1) * (2 * r + 1);
     float zfar = nan;
     for (int dy = 0; dy < side; ++dy) {
       const int row = (ly + off + dy) * zw + lx + off;
       for (int dx = 0; dx < side; ++dx) {
         const float zm = s_z[row + dx];
-        if (finite(zm) && !(zfar >= zm)) zfar = zm;  // (the first finite one, then every larger one)
+        if (rules::finite_f(zm) && !(zfar >= zm)) zfar = zm;  // (the first finite one, then every larger one)
       }
     }
-    if (finite(zfar)) {
-      const float s = P.range_sigmas * sigma(zfar);
+    if (rules::finite_f(zfar)) {
+      const float s = P.range_sigmas * rules::depth_sigma(zfar);
       float sw = 0.0f, swd = 0.0f;
       for (int dy = 0; dy < side; ++dy) {
         const int row = (ly + off + dy) * zw + lx + off;
         for (int dx = 0; dx < side; ++dx) {
           const float zm = s_z[row + dx];
-          const bool member = finite(zm) && zfar - zm <= s;
+          const bool member = rules::finite_f(zm) && zfar - zm <= s;
           const float wt = WF[dy * side + dx];
           sw = member ? sw + wt : sw;
           swd = member ? swd + wt * (zm - zfar) : swd;
@@ -169,8 +167,8 @@ __global__ void __launch_bounds__(kBlock) k_depth_filter(const Record *__restric
 
   if (live) {
     const size_t at = (size_t)v * (size_t)w + (size_t)u;
-    ((DEPTH_FILTER_GLOBAL float *)L.out)[at] = out;
-    if (L.support) ((DEPTH_FILTER_GLOBAL unsigned short *)L.support)[at] = (unsigned short)(has ? n : 0);
+    ((DVO_DEVICE_GLOBAL float *)L.out)[at] = out;
+    if (L.support) ((DVO_DEVICE_GLOBAL unsigned short *)L.support)[at] = (unsigned short)(has ? n : 0);
   }
   const unsigned n_has = (unsigned)__popcll(__ballot(has));
   const unsigned n_kept = (unsigned)__popcll(__ballot(has && kept));
@@ -186,7 +184,7 @@ __global__ void __launch_bounds__(kBlock) k_depth_filter(const Record *__restric
   __syncthreads();
   if (threadIdx.x < kCounts) {
     const unsigned c = s_cnt[threadIdx.x];
-    if (c) (void)__hip_atomic_fetch_add((DEPTH_FILTER_GLOBAL unsigned *)L.counts + threadIdx.x, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (c) (void)__hip_atomic_fetch_add((DVO_DEVICE_GLOBAL unsigned *)L.counts + threadIdx.x, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -200,13 +198,7 @@ using namespace dvo_amd::depth_filter;
 namespace {
 
 // dvo_amd_debug_depth_filter_timing: two events around the filter launch on the prep stream, when asked for
-struct FilterTiming {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double last_ms = 0.0;
-};
-FilterTiming g_timing[kMaxDevices];
+DeviceTiming g_timing[kMaxDevices];
 
 int check_options(const char *entry, const dvo_amd_depth_filter_options *opt) {
   const std::string top = std::to_string(DVO_AMD_DEPTH_FILTER_MAX_RADIUS);
@@ -284,10 +276,10 @@ int filter_many(const char *entry, int n, const dvo_amd_pyramid *const *p, const
   hipStream_t st = nullptr;
   rc = device_prep_stream(device, &st);
   if (rc) return rc;
-  void *scratch = nullptr;
-  rc = slab_alloc(device, scratch_bytes, &scratch);
+  Scratch scratch;  // (every return below stands behind a synchronisation of the stream: the filter's own, then pyramid_build's)
+  rc = scratch.take(device, scratch_bytes);
   if (rc) return rc;
-  char *base = (char *)scratch;
+  char *base = scratch.base();
   Record *d_records = (Record *)base;
   float *d_ws = (float *)(base + record_bytes);
   unsigned *d_counts = (unsigned *)(base + record_bytes + table_bytes);
@@ -305,21 +297,16 @@ int filter_many(const char *entry, int n, const dvo_amd_pyramid *const *p, const
   std::vector<unsigned> h_counts((size_t)kCounts * (size_t)n);
   const Params P{opt->radius, opt->fill_radius, opt->min_support, opt->min_fill_support, opt->range_sigmas};
 
-  FilterTiming &timing = g_timing[device];
-  bool timed;
-  {
-    std::lock_guard<std::mutex> lk(timing.mu);
-    timed = timing.on && timing.ev[0] && timing.ev[1];
-  }
+  Bracket bracket(g_timing[device]);
   hipError_t e = hipMemcpyAsync(d_records, table.data(), sizeof(Record) * (size_t)n, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_ws, h_ws, sizeof(float) * (size_t)(window + fill_window), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, count_bytes, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_depth_filter, dim3((unsigned)n_blocks), dim3(kBlock), 0, st, (const Record *)d_records, n, (const float *)d_ws, P);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   if (e == hipSuccess && counts) e = hipMemcpyAsync(h_counts.data(), d_counts, sizeof(unsigned) * h_counts.size(), hipMemcpyDeviceToHost, st);
   for (int k = 0; k < n && e == hipSuccess; ++k)
     if (support && support[k])
@@ -327,17 +314,8 @@ int filter_many(const char *entry, int n, const dvo_amd_pyramid *const *p, const
   // the filter's one synchronisation (whatever failed, the stream is drained before the scratch goes back to the pool)
   const hipError_t es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    slab_free(device, scratch_bytes, scratch);
-    return fail_hip("depth filtering", e);
-  }
-  if (timed) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, timing.ev[0], timing.ev[1]) == hipSuccess) {
-      std::lock_guard<std::mutex> lk(timing.mu);
-      timing.last_ms = ms;
-    }
-  }
+  if (e != hipSuccess) return fail_hip("depth filtering", e);
+  bracket.read();
   // every pyramid from its own intensity plane and its filtered plane, by the builder every pyramid comes from
   for (int k = 0; k < n; ++k) {
     const LevelData &L = p[k]->lv[0];
@@ -347,11 +325,10 @@ int filter_many(const char *entry, int n, const dvo_amd_pyramid *const *p, const
     if (rc) {
       for (int j = 0; j < k; ++j) dvo_amd_pyramid_release(out[j]), out[j] = nullptr;
       out[k] = nullptr;
-      slab_free(device, scratch_bytes, scratch);
       return rc;
     }
   }
-  slab_free(device, scratch_bytes, scratch);  // (pyramid_build drained the stream: nothing reads the scratch any more)
+  // (pyramid_build drained the stream: nothing reads the scratch any more when it goes out of scope)
   if (counts)
     for (size_t i = 0; i < h_counts.size(); ++i) counts[i] = (long long)h_counts[i];
   return DVO_AMD_OK;
@@ -382,20 +359,7 @@ int dvo_amd_pyramid_filter_depth(const dvo_amd_pyramid *p, const dvo_amd_depth_f
 /* instrumentation: with enable != 0 the filter launch of every later dvo_amd_pyramid_filter_depth / _many on `device` is bracketed
  * by two events on the prep stream; *last_ms (may be NULL) receives the device time of the most recent bracketed launch */
 int dvo_amd_debug_depth_filter_timing(int device, int enable, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  FilterTiming &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, nullptr, nullptr, last_ms);
 }
 
 }  // extern "C"

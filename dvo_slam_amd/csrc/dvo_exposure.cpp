@@ -17,6 +17,7 @@
 // The host solves each pass from the six sums in 128-bit integers (dvo_exposure_solve.h) and hands gain and bias, as floats, to the
 // next pass: a call is refits_max + 1 launches and as many synchronisations, whatever number of pairs it holds.
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 #include "dvo_exposure_solve.h"
 
 #include <algorithm>
@@ -40,7 +41,6 @@ constexpr int kAdjustPixels = 4;
 static_assert(kBlock % 64 == 0, "whole waves");
 static_assert(DVO_AMD_EXPOSURE_MAX_REFITS == 8, "the header's bound: gain_pass[9]");
 
-#define EXPOSURE_GLOBAL __attribute__((address_space(1)))
 
 // one pair as the kernel reads it (uniform over the block: scalar registers)
 struct Pair {
@@ -69,8 +69,6 @@ __global__ void __launch_bounds__(kBlock) k_exposure(const Pair *__restrict__ pa
     if (!S.active) continue;  // (block-uniform: no barrier is skipped by part of a block)
     const Pair P = pairs[pair];
     if (blockIdx.x * kChunk >= P.nr) continue;
-    const float *T = P.T;
-    const float wmax = (float)(P.wc - 1), hmax = (float)(P.hc - 1);
     const int base = blockIdx.x * kChunk + wave * (kSteps * 64);
     unsigned cnt[kCounts] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
     long long sx = 0, sy = 0, sxx = 0, sxy = 0, syy = 0;
@@ -81,47 +79,25 @@ __global__ void __launch_bounds__(kBlock) k_exposure(const Pair *__restrict__ pa
       bool trimmed = false, used = false;
       if (p < P.nr) {
         const float z = P.zr[p];
-        if (fabsf(z) <= 3.402823466e38f) {  // finite (false for NaN)
+        size_t at;
+        if (rules::finite_f(z)) {
           const int v = p / P.wr, u = p - v * P.wr;
-          const float x = P.txr[u] * z, y = P.tyr[v] * z;
-          const float qx = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-          const float qy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-          const float qz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-          if (!(qz >= P.near_z)) {
-            cls = 1;
+          cls = rules::classify_covisible(z, P.txr[u], P.tyr[v], P.T, P.near_z, P.sigmas, P.zc, P.wc, P.hc, P.fx, P.fy, P.ox, P.oy, at);
+        }
+        if (cls == 4) {
+          if (P.mask && P.mask[p] == 0) {
+            cls = 7;
           } else {
-            const float pu = floorf(((qx * P.fx) / qz + P.ox) + 0.5f);
-            const float pv = floorf(((qy * P.fy) / qz + P.oy) + 0.5f);
-            if (!(pu >= 0.0f && pu <= wmax && pv >= 0.0f && pv <= hmax)) {
-              cls = 2;
+            const float iy = P.ir[p], ix = P.ic[at];
+            if (!(ix >= P.lo && ix <= P.hi && iy >= P.lo && iy <= P.hi)) {  // (false for a NaN)
+              cls = 8;
             } else {
-              const size_t at = (size_t)(int)pv * (size_t)P.wc + (size_t)(int)pu;  // 0 <= pu <= wc-1, 0 <= pv <= hc-1: tested in float above
-              const float zc = P.zc[at];
-              if (!(zc == zc)) {
-                cls = 3;
-              } else {
-                const float s = qz - 0.4f;
-                const float tol = P.sigmas * (0.0012f + 0.0019f * (s * s));
-                const float d = zc - qz;
-                cls = d < -tol ? 5 : (d > tol ? 6 : 4);
-                if (cls == 4) {
-                  if (P.mask && P.mask[p] == 0) {
-                    cls = 7;
-                  } else {
-                    const float iy = P.ir[p], ix = P.ic[at];
-                    if (!(ix >= P.lo && ix <= P.hi && iy >= P.lo && iy <= P.hi)) {  // (false for a NaN)
-                      cls = 8;
-                    } else {
-                      cls = 9;
-                      used = !S.trimming || fabsf((S.gain * ix + S.bias) - iy) <= P.trim;
-                      trimmed = !used;
-                      if (used) {
-                        const long long X = (long long)rintf(ix * P.scale), Y = (long long)rintf(iy * P.scale);
-                        sx += X, sy += Y, sxx += X * X, sxy += X * Y, syy += Y * Y;
-                      }
-                    }
-                  }
-                }
+              cls = 9;
+              used = !S.trimming || fabsf((S.gain * ix + S.bias) - iy) <= P.trim;
+              trimmed = !used;
+              if (used) {
+                const long long X = (long long)rintf(ix * P.scale), Y = (long long)rintf(iy * P.scale);
+                sx += X, sy += Y, sxx += X * X, sxy += X * Y, syy += Y * Y;
               }
             }
           }
@@ -157,7 +133,7 @@ __global__ void __launch_bounds__(kBlock) k_exposure(const Pair *__restrict__ pa
 #pragma unroll
       for (int w = 0; w < kWaves; ++w) sum += s_v[w][threadIdx.x];
       if (sum)
-        (void)__hip_atomic_fetch_add((EXPOSURE_GLOBAL unsigned long long *)out + (size_t)pair * kWordsPad + threadIdx.x, sum, __ATOMIC_RELAXED,
+        (void)__hip_atomic_fetch_add((DVO_DEVICE_GLOBAL unsigned long long *)out + (size_t)pair * kWordsPad + threadIdx.x, sum, __ATOMIC_RELAXED,
                                      __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();  // s_v is written again for the block's next pair
@@ -208,30 +184,7 @@ constexpr double kMaxQuantised = 1048576.0;      // |intensity bound| * scale <=
 
 // dvo_amd_debug_exposure_timing: two events around every launch of a call on the prep stream, when asked for; a call's launches
 // are added up
-struct ExposureTiming {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double last_ms = 0.0;
-};
-ExposureTiming g_timing[kMaxDevices];
-
-bool timing_wanted(int device) {
-  ExposureTiming &t = g_timing[device];
-  std::lock_guard<std::mutex> lk(t.mu);
-  return t.on && t.ev[0] && t.ev[1];
-}
-
-// after the synchronisation behind a bracketed launch: its device time (0 where the events cannot be read)
-double bracket_ms(int device) {
-  float ms = 0.f;
-  return hipEventElapsedTime(&ms, g_timing[device].ev[0], g_timing[device].ev[1]) == hipSuccess ? (double)ms : 0.0;
-}
-
-void timing_store(int device, double ms) {
-  std::lock_guard<std::mutex> lk(g_timing[device].mu);
-  g_timing[device].last_ms = ms;
-}
+DeviceTiming g_timing[kMaxDevices];
 
 int check_options(const char *entry, const std::string &pair, const dvo_amd_exposure_options &o) {
   if (!std::isfinite(o.near_z) || !(o.near_z > 0.0f)) return invalid(entry, pair + ": near_z must be finite and positive");
@@ -303,24 +256,21 @@ int estimate_many(const char *entry, dvo_amd_context *ctx, int n, const dvo_amd_
     P.mask = masks && masks[k] ? masks[k]->plane[o.level] : nullptr;
     P.wr = A.w, P.nr = A.w * A.h, P.wc = B.w, P.hc = B.h;
     P.fx = B.fx, P.fy = B.fy, P.ox = B.ox, P.oy = B.oy;
-    for (int row = 0; row < 3; ++row)
-      for (int col = 0; col < 4; ++col)  // column-major in, rows 0..2 out; no T: the identity
-        P.T[row * 4 + col] = T ? (float)T[16 * (size_t)k + col * 4 + row] : (row == col ? 1.0f : 0.0f);
+    rows_from_column_major(T ? T + 16 * (size_t)k : nullptr, P.T);  // (no T: the identity)
     P.near_z = o.near_z, P.sigmas = o.depth_sigmas, P.lo = o.min_intensity, P.hi = o.max_intensity, P.scale = o.scale, P.trim = o.trim;
     max_nr = std::max(max_nr, P.nr);
   }
-  void *scratch = nullptr;
-  rc = slab_alloc(device, scratch_bytes, &scratch);
+  Scratch scratch;  // (every return below stands behind a synchronisation of the stream)
+  rc = scratch.take(device, scratch_bytes);
   if (rc) return rc;
-  char *base = (char *)scratch;
+  char *base = scratch.base();
   const Pair *d_pairs = (const Pair *)base;
   PassState *d_states = (PassState *)(base + pairs_bytes);
   unsigned long long *d_sums = (unsigned long long *)(base + pairs_bytes + states_bytes);
 
   const unsigned gx = (unsigned)((max_nr + kChunk - 1) / kChunk);
-  // a launch holds fewer than 2^31 threads and at most 65535 rows of blocks: a block takes further pairs in steps of gridDim.y
-  const unsigned gy = (unsigned)std::max<long long>(1, std::min<long long>(std::min(n, 65535), (1ll << 31) / ((long long)gx * kBlock)));
-  const bool timed = timing_wanted(device);
+  const unsigned gy = grid_rows(n, gx, kBlock);  // a block takes further pairs in steps of gridDim.y
+  Bracket bracket(g_timing[device]);
   double device_ms = 0.0;
 
   std::vector<dvo_amd_exposure_estimate> made((size_t)n);  // (the outputs stay untouched until nothing can fail any more)
@@ -345,17 +295,18 @@ int estimate_many(const char *entry, dvo_amd_context *ctx, int n, const dvo_amd_
     if (!any) break;
     unsigned long long *d_pass = d_sums + pass_words * (size_t)pass;
     e = hipMemcpyAsync(d_states, states.data(), sizeof(PassState) * (size_t)n, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && timed) e = hipEventRecord(g_timing[device].ev[0], st);
+    if (e == hipSuccess) e = bracket.begin(st);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(k_exposure, dim3(gx, gy), dim3(kBlock), 0, st, d_pairs, (const PassState *)d_states, n, d_pass);
       e = hipGetLastError();
     }
-    if (e == hipSuccess && timed) e = hipEventRecord(g_timing[device].ev[1], st);
+    if (e == hipSuccess) e = bracket.end(st);
     if (e == hipSuccess) e = hipMemcpyAsync(words.data(), d_pass, sizeof(unsigned long long) * pass_words, hipMemcpyDeviceToHost, st);
     if (e != hipSuccess) break;
     e = hipStreamSynchronize(st);  // the pass's one synchronisation
     if (e != hipSuccess) break;
-    if (timed) device_ms += bracket_ms(device);
+    double pass_ms = 0.0;
+    if (bracket.elapsed(&pass_ms)) device_ms += pass_ms;
     for (int k = 0; k < n; ++k) {
       if (!states[(size_t)k].active) continue;
       const unsigned long long *w = words.data() + (size_t)kWordsPad * (size_t)k;
@@ -376,10 +327,11 @@ int estimate_many(const char *entry, dvo_amd_context *ctx, int n, const dvo_amd_
       states[(size_t)k].gain = (float)f.gain, states[(size_t)k].bias = (float)f.bias;
     }
   }
-  if (e != hipSuccess) (void)hipStreamSynchronize(st);  // (whatever failed, the stream is drained before the scratch goes back to the pool)
-  slab_free(device, scratch_bytes, scratch);
-  if (e != hipSuccess) return fail_hip("exposure estimate", e);
-  if (timed) timing_store(device, device_ms);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(st);  // (whatever failed, the stream is drained before the scratch goes back to the pool)
+    return fail_hip("exposure estimate", e);
+  }
+  if (bracket.timed) bracket.store(device_ms);
   for (int k = 0; k < n; ++k) out[k] = made[(size_t)k];
   return DVO_AMD_OK;
 }
@@ -423,30 +375,27 @@ int adjust_many(const char *entry, int n, const dvo_amd_pyramid *const *p, const
   hipStream_t st = nullptr;
   rc = device_prep_stream(device, &st);
   if (rc) return rc;
-  void *scratch = nullptr;
-  rc = slab_alloc(device, scratch_bytes, &scratch);
+  Scratch scratch;  // (every return below stands behind a synchronisation of the stream: the adjust's own, then pyramid_build's)
+  rc = scratch.take(device, scratch_bytes);
   if (rc) return rc;
-  char *base = (char *)scratch;
+  char *base = scratch.base();
   for (int k = 0; k < n; ++k) {
     table[(size_t)k].in = p[k]->lv[0].i_plane;
     table[(size_t)k].out = (float *)(base + plane_at[(size_t)k]);
   }
-  const bool timed = timing_wanted(device);
+  Bracket bracket(g_timing[device]);
   hipError_t e = hipMemcpyAsync(base, table.data(), sizeof(AdjustRecord) * (size_t)n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(g_timing[device].ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_adjust, dim3((unsigned)n_blocks), dim3(kBlock), 0, st, (const AdjustRecord *)base, n);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(g_timing[device].ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   // the adjust's one synchronisation (whatever failed, the stream is drained before the scratch goes back to the pool)
   const hipError_t es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    slab_free(device, scratch_bytes, scratch);
-    return fail_hip("intensity adjustment", e);
-  }
-  if (timed) timing_store(device, bracket_ms(device));
+  if (e != hipSuccess) return fail_hip("intensity adjustment", e);
+  bracket.read();
   // every pyramid from its adjusted intensity plane and its own depth plane, by the builder every pyramid comes from
   for (int k = 0; k < n; ++k) {
     const LevelData &L = p[k]->lv[0];
@@ -456,12 +405,10 @@ int adjust_many(const char *entry, int n, const dvo_amd_pyramid *const *p, const
     if (rc) {
       for (int j = 0; j < k; ++j) dvo_amd_pyramid_release(out[j]), out[j] = nullptr;
       out[k] = nullptr;
-      slab_free(device, scratch_bytes, scratch);
       return rc;
     }
   }
-  slab_free(device, scratch_bytes, scratch);  // (pyramid_build drained the stream: nothing reads the scratch any more)
-  return DVO_AMD_OK;
+  return DVO_AMD_OK;  // (pyramid_build drained the stream: nothing reads the scratch any more)
 }
 
 }  // namespace
@@ -509,20 +456,7 @@ int dvo_amd_pyramid_adjust_intensity(const dvo_amd_pyramid *p, double gain, doub
  * _many on `device` is bracketed by two events on the prep stream; *last_ms (may be NULL) receives the device time of the most recent
  * bracketed call, its launches added up */
 int dvo_amd_debug_exposure_timing(int device, int enable, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  ExposureTiming &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, nullptr, nullptr, last_ms);
 }
 
 }  // extern "C"

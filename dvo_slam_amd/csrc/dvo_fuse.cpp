@@ -19,6 +19,7 @@
 // anywhere, so nothing depends on the launch geometry or on the order atomics land in.  One synchronisation for the fusion on
 // the device's prep stream, then pyramid_build's own per keyframe.
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -38,9 +39,8 @@ constexpr int kFrameBatch = kBlock / kFrameCounts;  // frames whose counts a blo
 static_assert(kFrameBatch * kFrameCounts == kBlock, "a thread per (frame of the batch, count) clears and flushes the LDS counts");
 static_assert(DVO_AMD_FUSE_MAX_FRAMES <= 255, "a pixel's observations fit a byte");
 
-// Pointers read from a record in memory are generic ("flat") to the compiler, and a flat load counts as an LDS access too: the
-// scalar load of the next frame's record would wait for every gather in flight.  The planes live in device global memory: say so.
-#define FUSE_GLOBAL __attribute__((address_space(1)))
+// (The planes are read through DVO_DEVICE_GLOBAL: with flat loads, the scalar load of the next frame's record would wait for every
+// gather in flight.)
 typedef float vpf __attribute__((ext_vector_type(kLanePixels)));  // a lane's pixels (a plain vector type: loadable from any address space)
 typedef std::conditional<kLanePixels == 4, unsigned, unsigned short>::type obs_word;  // ... and their observation bytes
 static_assert(kLanePixels == 2 || kLanePixels == 4, "a lane's pixels are one load, and they divide every width (a multiple of 4)");
@@ -75,32 +75,26 @@ struct Sample {
 // one integer add to a count in global memory (a flat atomic would count as an LDS access too and, while one is in flight, make
 // every wait for a gather a wait for all of them)
 __device__ __forceinline__ void add_global(unsigned *p, unsigned v) {
-  (void)__hip_atomic_fetch_add((FUSE_GLOBAL unsigned *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ float sigma_z(float z) {
-  const float s = z - 0.4f;
-  return 0.0012f + 0.0019f * (s * s);
+  (void)__hip_atomic_fetch_add((DVO_DEVICE_GLOBAL unsigned *)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // steps 3a..3e for one pixel and one frame: the point, the projection, the gathers (issued, not waited for)
 template <bool kNearest>
 __device__ __forceinline__ void issue(const FrameRecord &F, float near_z, bool has, float x, float y, float z0, Sample<kNearest> &S) {
-  const float *M = F.M;
-  const float qx = ((M[0] * x + M[1] * y) + M[2] * z0) + M[3];
-  const float qy = ((M[4] * x + M[5] * y) + M[6] * z0) + M[7];
-  const float qz = ((M[8] * x + M[9] * y) + M[10] * z0) + M[11];
+  float qx, qy, qz;
+  rules::transform_rows(F.M, x, y, z0, qx, qy, qz);
   S.qz = qz, S.a = 0.f, S.b = 0.f;
   int cls = has ? 0 : -1;
   if (has && !(qz >= near_z)) cls = 1;
   const float px = (qx * F.fx) / qz + F.ox, py = (qy * F.fy) / qz + F.oy;
-  const FUSE_GLOBAL float *Z = (const FUSE_GLOBAL float *)F.z;
+  const DVO_DEVICE_GLOBAL float *Z = (const DVO_DEVICE_GLOBAL float *)F.z;
   size_t at = 0;  // (the plane's first pixel where nothing is sampled: every load below is unconditional and in bounds)
   if constexpr (kNearest) {
     const float pu = floorf(px + 0.5f), pv = floorf(py + 0.5f);
+    // (rules::pixel_inside's test, kept as a value of its own: the select below is part of the branchless form)
     const bool inside = pu >= 0.0f && pu <= (float)(F.w - 1) && pv >= 0.0f && pv <= (float)(F.h - 1);
     if (cls == 0 && !inside) cls = 2;
-    if (cls == 0) at = (size_t)(int)pv * (size_t)F.w + (size_t)(int)pu;  // 0 <= pu <= w-1, 0 <= pv <= h-1: tested in float above
+    if (cls == 0) at = rules::pixel_offset(pu, pv, F.w);
     S.z[0] = Z[at];
   } else {
     const float x0 = floorf(px), y0 = floorf(py);
@@ -120,7 +114,7 @@ __device__ __forceinline__ int consume(const FrameRecord &F, const Sample<kNeare
                                        float z0, float &sw, float &swz, int &n_obs, bool &fused) {
   // Without a branch: every lane forms every value and the outcome selects.  A branch around the first use of the gathered depths
   // would leave a path on which they are never waited for, and the wait before the next frame's gathers would then be for all of
-  // them (vmcnt(0)) instead of for this frame's alone.
+  // them (vmcnt(0)) instead of for this frame's alone.  (So not rules::classify_covisible, which branches: its parts only.)
   float Zs;
   bool nan;
   if constexpr (kNearest) {
@@ -134,10 +128,10 @@ __device__ __forceinline__ int consume(const FrameRecord &F, const Sample<kNeare
     Zs = top + S.b * (bot - top);
   }
   const float d = Zs - S.qz;
-  const float tol = sigmas * sigma_z(S.qz);
+  const float tol = sigmas * rules::depth_sigma(S.qz);
   const float c = (F.M[8] * tx + F.M[9] * ty) + F.M[10];
   const float z_obs = z0 + d / c;
-  const float sg = sigma_z(Zs);
+  const float sg = rules::depth_sigma(Zs);
   const float w = 1.0f / (sg * sg);
   const bool sampled = S.cls == 0 && !nan;
   const int cls = S.cls != 0 ? S.cls : nan ? 3 : d < -tol ? 5 : d > tol ? 6 : 4;
@@ -168,19 +162,19 @@ __global__ void __launch_bounds__(kBlock) k_fuse_depth(const KeyRecord *__restri
     {
       vpf z = 0.f, t = 0.f;
       if (live) {
-        z = *(const FUSE_GLOBAL vpf *)(K.z + p0);
+        z = *(const DVO_DEVICE_GLOBAL vpf *)(K.z + p0);
         const int v = p0 / K.w, u0 = p0 - v * K.w;
-        t = *(const FUSE_GLOBAL vpf *)(K.tx + u0);  // (u0 is a multiple of kLanePixels and the ray plane is 256-byte aligned)
-        ty = ((const FUSE_GLOBAL float *)K.ty)[v];
+        t = *(const DVO_DEVICE_GLOBAL vpf *)(K.tx + u0);  // (u0 is a multiple of kLanePixels and the ray plane is 256-byte aligned)
+        ty = ((const DVO_DEVICE_GLOBAL float *)K.ty)[v];
       }
 #pragma unroll
       for (int i = 0; i < kLanePixels; ++i) z0[i] = z[i], tx[i] = t[i];
     }
 #pragma unroll
     for (int i = 0; i < kLanePixels; ++i) {
-      has[i] = live && fabsf(z0[i]) <= 3.402823466e38f;  // finite (false for NaN)
+      has[i] = live && rules::finite_f(z0[i]);
       x[i] = tx[i] * z0[i], y[i] = ty * z0[i];
-      const float sg = sigma_z(z0[i]);
+      const float sg = rules::depth_sigma(z0[i]);
       const float w = 1.0f / (sg * sg);
       sw[i] = w, swz[i] = w * z0[i], n_obs[i] = 0;
     }
@@ -253,8 +247,8 @@ __global__ void __launch_bounds__(kBlock) k_fuse_depth(const KeyRecord *__restri
       vpf fused;
 #pragma unroll
       for (int i = 0; i < kLanePixels; ++i) fused[i] = o[i];
-      *(FUSE_GLOBAL vpf *)(K.out + p0) = fused;
-      if (K.obs) *(FUSE_GLOBAL obs_word *)(K.obs + p0) = (obs_word)word;
+      *(DVO_DEVICE_GLOBAL vpf *)(K.out + p0) = fused;
+      if (K.obs) *(DVO_DEVICE_GLOBAL obs_word *)(K.obs + p0) = (obs_word)word;
     }
     if (lane == 0) {
 #pragma unroll
@@ -286,21 +280,11 @@ using namespace dvo_amd::fuse;
 namespace {
 
 // dvo_amd_debug_fuse_timing: two events around the fusion launch of a call on the prep stream (off unless asked for)
-struct FuseTiming {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double last_ms = 0.0;
-};
-FuseTiming g_timing[kMaxDevices];
+DeviceTiming g_timing[kMaxDevices];
 
 // the record tables and the counts of the call in flight (grown to the largest call and kept; used with the device's mutex held
 // from the tables' upload to the last thing enqueued that touches the area)
-struct FuseArea {
-  void *mem = nullptr;
-  size_t bytes = 0;
-};
-FuseArea g_area[kMaxDevices];
+DeviceBuf g_area[kMaxDevices];
 
 int check_options(const char *entry, const dvo_amd_fuse_options *opt) {
   if (!std::isfinite(opt->near_z) || !(opt->near_z > 0.0f)) return invalid(entry, "near_z must be finite and positive");
@@ -311,16 +295,6 @@ int check_options(const char *entry, const dvo_amd_fuse_options *opt) {
   if (opt->min_observations < 0 || opt->min_observations > DVO_AMD_FUSE_MAX_FRAMES)
     return invalid(entry, "min_observations is outside 0.." + std::to_string(DVO_AMD_FUSE_MAX_FRAMES));
   return DVO_AMD_OK;
-}
-
-// rows 0..2 of the rigid inverse of a column-major transformation, cast to float (dvo_amd_covisibility's step 1)
-void inverse_rows(const double *T, float *M) {
-  const double t0 = T[12], t1 = T[13], t2 = T[14];
-  for (int r = 0; r < 3; ++r) {
-    // R[i][r] = T[r * 4 + i]: row r of R^T is column r of R
-    for (int c = 0; c < 3; ++c) M[r * 4 + c] = (float)T[r * 4 + c];
-    M[r * 4 + 3] = (float)(-((T[r * 4 + 0] * t0 + T[r * 4 + 1] * t1) + T[r * 4 + 2] * t2));
-  }
 }
 
 int fuse_many(const char *entry, int nk, const dvo_amd_pyramid *const *keyframes, const int *offsets,
@@ -377,9 +351,11 @@ int fuse_many(const char *entry, int nk, const dvo_amd_pyramid *const *keyframes
       obs_at[(size_t)k] = scratch_bytes;
       scratch_bytes += align_up((size_t)keyframes[k]->lv[0].n, 256);
     }
-  void *scratch = nullptr;
-  rc = slab_alloc(device, scratch_bytes, &scratch);
+  // (given back when the call ends: every return below stands before anything is enqueued or behind a synchronisation of the stream)
+  Scratch S;
+  rc = S.take(device, scratch_bytes);
   if (rc) return rc;
+  void *const scratch = S.mem;
 
   const size_t key_bytes = align_up(sizeof(KeyRecord) * (size_t)nk, 256);
   const size_t frame_bytes = align_up(sizeof(FrameRecord) * (size_t)std::max(total, 1), 256);
@@ -389,32 +365,16 @@ int fuse_many(const char *entry, int nk, const dvo_amd_pyramid *const *keyframes
   std::vector<FrameRecord> frame_table((size_t)total);
   std::vector<unsigned> h_counts(n_counts);
 
-  FuseTiming &timing = g_timing[device];
-  bool timed;
-  {
-    std::lock_guard<std::mutex> lk(timing.mu);
-    timed = timing.on && timing.ev[0] && timing.ev[1];
-  }
+  Bracket bracket(g_timing[device]);
   // The tables and the counts live in the device's one fuse area, which the next call overwrites: the device's mutex is held from
   // the upload to the last thing enqueued that reads or writes the area (dvo_amd_mask_warp_many does the same for its table).
   std::unique_lock<std::mutex> area_lock(device_mutex(device));
-  FuseArea &area = g_area[device];
-  const size_t area_bytes = key_bytes + frame_bytes + count_bytes;
-  if (area.bytes < area_bytes) {
-    if (area.mem) (void)hipFree(area.mem), area.mem = nullptr, area.bytes = 0;  // (hipFree waits for whatever still reads it)
-    const size_t grown = align_up(area_bytes, 1 << 16);
-    const hipError_t ea = hipMalloc(&area.mem, grown);
-    if (ea != hipSuccess) {
-      area.mem = nullptr;
-      area_lock.unlock();
-      slab_free(device, scratch_bytes, scratch);
-      return ea == hipErrorOutOfMemory ? (int)DVO_AMD_ERR_OUT_OF_MEMORY : fail_hip("hipMalloc (fuse tables)", ea);
-    }
-    area.bytes = grown;
-  }
-  KeyRecord *d_keys = (KeyRecord *)area.mem;
-  FrameRecord *d_frames = (FrameRecord *)((char *)area.mem + key_bytes);
-  unsigned *d_counts = (unsigned *)((char *)area.mem + key_bytes + frame_bytes);
+  DeviceBuf &area = g_area[device];
+  rc = grow(area, key_bytes + frame_bytes + count_bytes, 1 << 16, "fuse tables");
+  if (rc) return rc;  // (nothing has been enqueued)
+  KeyRecord *d_keys = (KeyRecord *)area.p;
+  FrameRecord *d_frames = (FrameRecord *)((char *)area.p + key_bytes);
+  unsigned *d_counts = (unsigned *)((char *)area.p + key_bytes + frame_bytes);
   unsigned *d_key_counts = d_counts + (size_t)kFrameCounts * (size_t)total;
   for (int k = 0; k < nk; ++k) {
     const LevelData &L = keyframes[k]->lv[0];
@@ -436,12 +396,10 @@ int fuse_many(const char *entry, int nk, const dvo_amd_pyramid *const *keyframes
   if (e == hipSuccess && total > 0)
     e = hipMemcpyAsync(d_frames, frame_table.data(), sizeof(FrameRecord) * (size_t)total, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, count_bytes, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   if (e == hipSuccess) {
     const unsigned gx = (unsigned)((max_n + kChunk - 1) / kChunk);
-    // a launch holds fewer than 2^31 threads and at most 65535 rows of blocks: a block takes further keyframes in steps of gridDim.y
-    const unsigned gy = (unsigned)std::max<long long>(
-        1, std::min<long long>(std::min<long long>((long long)nk, 65535), (1ll << 31) / ((long long)gx * kBlock)));
+    const unsigned gy = grid_rows(nk, gx, kBlock);  // a block takes further keyframes in steps of gridDim.y
     if (opt->sample == DVO_AMD_FUSE_NEAREST)
       hipLaunchKernelGGL(k_fuse_depth<true>, dim3(gx, gy), dim3(kBlock), 0, st, (const KeyRecord *)d_keys, nk, (const FrameRecord *)d_frames,
                          opt->near_z, opt->depth_sigmas, opt->min_cos, opt->min_observations, opt->drop_unconfirmed);
@@ -450,7 +408,7 @@ int fuse_many(const char *entry, int nk, const dvo_amd_pyramid *const *keyframes
                          opt->near_z, opt->depth_sigmas, opt->min_cos, opt->min_observations, opt->drop_unconfirmed);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   if (e == hipSuccess && (frame_counts || keyframe_counts)) e = hipMemcpyAsync(h_counts.data(), d_counts, count_bytes, hipMemcpyDeviceToHost, st);
   for (int k = 0; k < nk && e == hipSuccess; ++k)
     if (observations && observations[k])
@@ -459,17 +417,8 @@ int fuse_many(const char *entry, int nk, const dvo_amd_pyramid *const *keyframes
   // the fusion's one synchronisation (whatever failed, the stream is drained before the scratch goes back to the pool)
   const hipError_t es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
-  if (e != hipSuccess) {
-    slab_free(device, scratch_bytes, scratch);
-    return fail_hip("depth fusion", e);
-  }
-  if (timed) {
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, timing.ev[0], timing.ev[1]) == hipSuccess) {
-      std::lock_guard<std::mutex> lk(timing.mu);
-      timing.last_ms = ms;
-    }
-  }
+  if (e != hipSuccess) return fail_hip("depth fusion", e);
+  bracket.read();
   // every keyframe's pyramid from its own intensity plane and its fused plane, by the builder every pyramid comes from
   for (int k = 0; k < nk; ++k) {
     const dvo_amd_pyramid *kf = keyframes[k];
@@ -480,11 +429,10 @@ int fuse_many(const char *entry, int nk, const dvo_amd_pyramid *const *keyframes
     if (rc) {
       for (int j = 0; j < k; ++j) dvo_amd_pyramid_release(out[j]), out[j] = nullptr;
       out[k] = nullptr;
-      slab_free(device, scratch_bytes, scratch);
       return rc;
     }
   }
-  slab_free(device, scratch_bytes, scratch);  // (pyramid_build drained the stream: nothing reads the scratch any more)
+  // (pyramid_build drained the stream: nothing reads the scratch any more when S goes out of scope)
   if (frame_counts)
     for (size_t i = 0; i < (size_t)kFrameCounts * (size_t)total; ++i) frame_counts[i] = (long long)h_counts[i];
   if (keyframe_counts)
@@ -523,20 +471,7 @@ int dvo_amd_pyramid_fuse_depth(const dvo_amd_pyramid *keyframe, int n, const dvo
 /* instrumentation: with enable != 0 the fusion launch of every later dvo_amd_pyramid_fuse_depth / _many on `device` is bracketed by
  * two events on the prep stream; *last_ms (may be NULL) receives the device time of the most recent bracketed launch */
 int dvo_amd_debug_fuse_timing(int device, int enable, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  FuseTiming &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, nullptr, nullptr, last_ms);
 }
 
 }  // extern "C"

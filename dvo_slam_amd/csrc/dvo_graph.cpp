@@ -833,7 +833,7 @@ struct GraphWorkspace {
 
 namespace {
 
-int grow(DeviceBuf &b, size_t bytes) { return grow(b, bytes, "graph workspace"); }
+int grow(DeviceBuf &b, size_t bytes) { return grow(b, bytes, kGraphBufStep, "graph workspace"); }
 
 int workspace(dvo_amd_context *ctx, GraphWorkspace **out) {
   if (!ctx->graph_ws) {

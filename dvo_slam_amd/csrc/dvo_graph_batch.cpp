@@ -582,7 +582,7 @@ namespace {
 
 const char *const kEntry = "dvo_amd_optimize_graphs_batch";
 
-int grow(DeviceBuf &b, size_t bytes) { return grow(b, bytes, "graph batch workspace"); }
+int grow(DeviceBuf &b, size_t bytes) { return grow(b, bytes, kGraphBufStep, "graph batch workspace"); }
 
 int optimize_batch(dvo_amd_context *ctx, int n_graphs, dvo_amd_graph_batch_item *items, const dvo_amd_graph_options &opt) {
   // per graph: the unknowns and the contributor lists (CSR by lower block / by vertex slot, contributors in edge order)

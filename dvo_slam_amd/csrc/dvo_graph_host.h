@@ -14,27 +14,13 @@ namespace host {
     if (rc_) return rc_;      \
   } while (0)
 
-// a device buffer of a graph workspace: grown to the largest call (in 4 KiB steps), never shrunk; `what` names the workspace
-// in dvo_amd_last_error().  (The map workspace keeps its own: it grows in 64 KiB steps.)
-struct DeviceBuf {
-  void *p = nullptr;
-  size_t bytes = 0;
-};
-
-inline int grow(DeviceBuf &b, size_t bytes, const char *what) {
-  if (bytes <= b.bytes) return DVO_AMD_OK;
-  if (b.p) (void)hipFree(b.p), b.p = nullptr, b.bytes = 0;
-  bytes = align_up(bytes < 256 ? 256 : bytes, 1 << 12);
-  const hipError_t e = hipMalloc(&b.p, bytes);
-  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
-  if (e != hipSuccess) return fail_hip(("hipMalloc (" + std::string(what) + ")").c_str(), e);
-  b.bytes = bytes;
-  return DVO_AMD_OK;
-}
+// a device buffer of a graph workspace (DeviceBuf, dvo_call.h) grows in 4 KiB steps; `what` names the workspace in
+// dvo_amd_last_error()
+constexpr size_t kGraphBufStep = 1 << 12;
 
 // grow to at least one byte, then the asynchronous upload (none for bytes == 0); `copy_what` names the upload
 inline int grow_upload(DeviceBuf &b, const void *src, size_t bytes, hipStream_t st, const char *what, const char *copy_what) {
-  const int rc = grow(b, bytes ? bytes : 1, what);
+  const int rc = grow(b, bytes ? bytes : 1, kGraphBufStep, what);
   if (rc || !bytes) return rc;
   const hipError_t e = hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
   return e == hipSuccess ? DVO_AMD_OK : fail_hip(("hipMemcpyAsync (" + std::string(copy_what) + ")").c_str(), e);

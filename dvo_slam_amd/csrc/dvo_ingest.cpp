@@ -15,25 +15,12 @@ namespace {
 
 // The per-device staging area of host raw frames and of the grey plane of BGR sources that go through a remap: grown to the
 // largest seen and kept; used with the device's mutex held.
-struct Area {
-  void *p = nullptr;
-  size_t bytes = 0;
-};
 struct Staging {
-  Area img, z, grey;
+  DeviceBuf img, z, grey;
 };
 Staging g_stage[kMaxDevices];
 
-int staging_grow(Area &a, size_t bytes) {
-  if (bytes <= a.bytes) return DVO_AMD_OK;
-  if (a.p) (void)hipFree(a.p), a.p = nullptr, a.bytes = 0;  // (hipFree waits for whatever still reads the old area)
-  bytes = align_up(bytes, 1 << 16);
-  const hipError_t e = hipMalloc(&a.p, bytes);
-  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
-  if (e != hipSuccess) return fail_hip("hipMalloc (ingest staging)", e);
-  a.bytes = bytes;
-  return DVO_AMD_OK;
-}
+int staging_grow(DeviceBuf &a, size_t bytes) { return grow(a, bytes, 1 << 16, "ingest staging"); }
 
 // `rows` rows of `row_bytes` from host memory, `src_stride_bytes` apart, packed into `dst`
 hipError_t upload_rows(void *dst, const void *src, size_t row_bytes, size_t src_stride_bytes, int rows, hipStream_t st) {

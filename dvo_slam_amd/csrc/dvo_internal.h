@@ -17,6 +17,19 @@
 //   dvo_fuse.cpp      depth fusion: the frames tracked against a keyframe averaged into its depth plane, a new pyramid from it
 //   dvo_place.cpp     the place index: int8 appearance descriptors of keyframes, their dot products, the best k per query
 //   dvo_register.cpp  depth-to-colour registration: the kernels that splat another camera's raw depth into level 0's depth plane
+//   dvo_covisibility.cpp  loop-closure candidates by geometry: the radius search, the view overlap of keyframe pairs
+//   dvo_normals.cpp   surface normals of a pyramid's levels: normal planes, facing masks, clouds with normals
+//   dvo_depth_filter.cpp  a frame's level-0 depth denoised: filter, reject, fill; a new pyramid from it
+//   dvo_components.cpp  connected components of masks and of depth: filter by size, label
+//   dvo_pose_score.cpp  many candidate transformations of a pair scored at one coarse level: seeds for loop closures
+//   dvo_exposure.cpp  gain and bias between two frames fitted over the pixels both see, a frame's intensity adjusted by them
+//   dvo_warp.cpp      a frame resampled into another camera's pixels: inverse (gather) and forward (splat)
+//   dvo_volume.cpp    the signed-distance volume: keyframes integrated into a voxel grid, raycast, surface extraction
+//   dvo_validator.cpp, dvo_frontend.cpp, dvo_tum.cpp  on top of the C ABI: loop-closure validation, the dual-match step, TUM files
+// (dvo_kernels.hip holds the alignment kernels and their launchers.)  What the feature units share is stated once:
+//   dvo_launch_rules.h  host, no HIP: the rows of a grid, the float rows of a double transformation
+//   dvo_call.h          host: the timing bracket of a debug entry, the grow-and-keep device buffer, the call's scratch
+//   dvo_device_rules.h  device: the covisibility rule and its parts, wave sums, depth-buffer minimum, footprints, the block scan
 // Until round 4 all of it was one 3 000-line translation unit.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -33,6 +46,7 @@
 
 #include "../../include/dvo_amd.h"
 #include "../../include/dvo_amd_debug.h"
+#include "dvo_launch_rules.h"
 #include "dvo_types.h"
 #include "se3.h"
 
@@ -81,7 +95,7 @@ constexpr int kMaxBands = 16;
 }  // namespace host
 }  // namespace dvo_amd
 
-using namespace dvo_amd;  // (an internal header of four translation units that all say the same)
+using namespace dvo_amd;  // (an internal header of the units listed above, which all say the same)
 
 // ------------------------------------------------------------------------------------------------------------------
 // pyramid
@@ -563,3 +577,5 @@ int match_one_banded(dvo_amd_context *ctx, dvo_amd_pyramid *reference, dvo_amd_p
 
 }  // namespace host
 }  // namespace dvo_amd
+
+#include "dvo_call.h"

@@ -25,6 +25,7 @@
 #include <mutex>
 #include <vector>
 
+#include "dvo_launch_rules.h"
 #include "dvo_types.h"
 
 namespace dvo_amd {
@@ -2505,9 +2506,7 @@ __global__ void __launch_bounds__(kResidualMaskBlock) k_residual_mask(const Resi
 hipError_t launch_residual_mask(const ResidualMaskRecord *records, int n_records, int max_n, hipStream_t stream) {
   LaunchGuard guard;
   const unsigned gx = (unsigned)((max_n + kResidualMaskChunk - 1) / kResidualMaskChunk);
-  // a launch holds fewer than 2^31 threads and at most 65535 rows of blocks: a block takes further records in steps of gridDim.y
-  const long long fit = (1ll << 31) / ((long long)gx * kResidualMaskBlock);
-  const unsigned gy = (unsigned)std::max<long long>(1, std::min<long long>(std::min<long long>((long long)n_records, 65535), fit));
+  const unsigned gy = host::grid_rows(n_records, gx, kResidualMaskBlock);  // a block takes further records in steps of gridDim.y
   hipLaunchKernelGGL(k_residual_mask, dim3(gx, gy), dim3(kResidualMaskBlock), 0, stream, records, n_records);
   return hipGetLastError();
 }
@@ -2627,9 +2626,7 @@ hipError_t launch_score_poses(PoseScoreLevel *levels, int n_levels, const PoseSc
   LaunchGuard guard;
   hipLaunchKernelGGL(k_score_q3, dim3((unsigned)n_levels), dim3(kResidualMaskBlock), 0, stream, levels);
   const unsigned gx = (unsigned)((max_n + kResidualMaskChunk - 1) / kResidualMaskChunk);
-  // as launch_residual_mask: fewer than 2^31 threads, at most 65535 rows of blocks; a block takes further items in steps of gridDim.y
-  const long long fit = (1ll << 31) / ((long long)gx * kResidualMaskBlock);
-  const unsigned gy = (unsigned)std::max<long long>(1, std::min<long long>(std::min<long long>((long long)n_items, 65535), fit));
+  const unsigned gy = host::grid_rows(n_items, gx, kResidualMaskBlock);  // a block takes further items in steps of gridDim.y
   hipLaunchKernelGGL(k_score_poses, dim3(gx, gy), dim3(kResidualMaskBlock), 0, stream, records, items, n_items);
   return hipGetLastError();
 }

@@ -23,6 +23,7 @@
 #include <cstring>
 
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 namespace dvo_amd {
 namespace map {
@@ -131,14 +132,9 @@ __device__ __forceinline__ void key_and_count(const float4 pt, float inv, bool a
     for (int a = 0; a < 3; ++a) cnt.mn[a] = min(cnt.mn[a], idx[a]), cnt.mx[a] = max(cnt.mx[a], idx[a]);
 }
 
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // every lane of the wave must call it
 __device__ __forceinline__ void flush_counts(Counts &cnt, MapCtrl *ctrl) {
-  const unsigned long long fin = wave_sum(cnt.finite), oor = wave_sum(cnt.out_of_range);
+  const unsigned long long fin = rules::wave_sum(cnt.finite), oor = rules::wave_sum(cnt.out_of_range);
   int mn[3], mx[3];
   for (int a = 0; a < 3; ++a) mn[a] = wave_min(cnt.mn[a]), mx[a] = wave_max(cnt.mx[a]);
   if ((threadIdx.x & 63) == 0) {
@@ -181,7 +177,7 @@ __global__ void __launch_bounds__(kBlock) k_map_keys(const MapImage *images, int
     if (keep) pts[slot] = pt, keys[slot] = key, vals[slot] = (unsigned)slot | im.neg;
   }
   if (per_image) {  // (finite, out of range) of every image on its own: the totals a persistent map keeps per keyframe
-    const unsigned long long fin = wave_sum(cnt.finite), oor = wave_sum(cnt.out_of_range);
+    const unsigned long long fin = rules::wave_sum(cnt.finite), oor = rules::wave_sum(cnt.out_of_range);
     if ((threadIdx.x & 63) == 0) {
       if (fin) atomicAdd(&per_image[2 * (size_t)(image0 + blockIdx.y)], fin);
       if (oor) atomicAdd(&per_image[2 * (size_t)(image0 + blockIdx.y) + 1], oor);
@@ -274,27 +270,6 @@ __global__ void __launch_bounds__(kBlock) k_radix_scatter(const unsigned long lo
   }
 }
 
-// exclusive scan of one value per thread over the block (256 threads); *total = the block's sum
-__device__ unsigned block_exclusive_scan(unsigned v, unsigned *total) {
-  __shared__ unsigned wsum[kBlock / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned incl = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned t = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += t;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  unsigned before = 0, all = 0;
-  for (int w = 0; w < kBlock / 64; ++w) {
-    before += w < wave ? wsum[w] : 0u;
-    all += wsum[w];
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - v;
-}
-
 __global__ void __launch_bounds__(kBlock) k_scan_reduce(const unsigned *a, unsigned n, unsigned *bsum) {
   const unsigned t0 = blockIdx.x * kScanTile;
   unsigned s = 0;
@@ -303,7 +278,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_reduce(const unsigned *a, unsig
     if (p < n) s += a[p];
   }
   unsigned total;
-  (void)block_exclusive_scan(s, &total);
+  (void)rules::block_exclusive_scan<kBlock / 64>(s, &total);
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
@@ -314,7 +289,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_blocks(unsigned *bsum, unsigned
     const unsigned p = c0 + threadIdx.x;
     const unsigned v = p < nb ? bsum[p] : 0u;
     unsigned total;
-    const unsigned ex = block_exclusive_scan(v, &total);
+    const unsigned ex = rules::block_exclusive_scan<kBlock / 64>(v, &total);
     if (p < nb) bsum[p] = carry + ex;
     carry += total;
   }
@@ -328,7 +303,7 @@ __global__ void __launch_bounds__(kBlock) k_scan_apply(unsigned *a, unsigned n, 
     const unsigned p = t0 + c * kBlock + threadIdx.x;
     const unsigned v = p < n ? a[p] : 0u;
     unsigned total;
-    const unsigned ex = block_exclusive_scan(v, &total);
+    const unsigned ex = rules::block_exclusive_scan<kBlock / 64>(v, &total);
     if (p < n) a[p] = carry + ex;
     carry += total;
   }
@@ -551,22 +526,6 @@ __global__ void __launch_bounds__(kBlock) k_render_clear(ulonglong2 *z, unsigned
     z[p] = make_ulonglong2(kEmptyWord, kEmptyWord);
 }
 
-// one axis of the footprint (dvo_amd.h, rule 5), compared in float; false: no pixel of the axis is covered
-__device__ __forceinline__ bool footprint_axis(float c, float half, int size, int &lo, int &hi) {
-  float a = ceilf(c - half), b = floorf(c + half);
-  if (b < a) a = b = floorf(c + 0.5f);
-  const float last = (float)(size - 1);
-  if (!(b >= 0.0f && a <= last)) return false;
-  lo = a > 0.0f ? (int)a : 0;
-  hi = b < last ? (int)b : size - 1;
-  return true;
-}
-
-// the stale value a plain load may return is never smaller than the word in memory: skipping the atomic on it is exact
-__device__ __forceinline__ void depth_min(unsigned long long *z, unsigned long long word) {
-  if (*z > word) atomicMin(z, word);
-}
-
 __global__ void __launch_bounds__(kBlock) k_render_splat(const VoxelAcc *acc, unsigned n_vox, RenderView V, unsigned long long *zbuf,
                                                          RenderCtrl *ctrl) {
   const int lane = threadIdx.x & 63;
@@ -591,7 +550,8 @@ __global__ void __launch_bounds__(kBlock) k_render_splat(const VoxelAcc *acc, un
       } else {
         const float u = (cx * V.fx) / cz + V.ox, v = (cy * V.fy) / cz + V.oy;
         const float hx = 0.5f * ((V.leaf * V.fx) / cz), hy = 0.5f * ((V.leaf * V.fy) / cz);
-        const bool in_x = footprint_axis(u, hx, V.w, x0, x1), in_y = footprint_axis(v, hy, V.h, y0, y1);
+        const bool in_x = rules::footprint_axis(u, hx, rules::kFootprintFill, V.w, x0, x1),
+                   in_y = rules::footprint_axis(v, hy, rules::kFootprintFill, V.h, y0, y1);
         draw = in_x && in_y;
         if (draw) ++drawn, word = ((unsigned long long)__float_as_uint(cz) << 32) | r;
         else ++outside;
@@ -602,7 +562,7 @@ __global__ void __launch_bounds__(kBlock) k_render_splat(const VoxelAcc *acc, un
     const bool small = some && (long long)fw * fh <= kSmallFootprint;
     if (small)
       for (int yy = y0; yy <= y1; ++yy)
-        for (int xx = x0; xx <= x1; ++xx) depth_min(zbuf + (size_t)yy * V.w + xx, word);
+        for (int xx = x0; xx <= x1; ++xx) rules::depth_min(zbuf + (size_t)yy * V.w + xx, word);
     // the larger footprints of the wave, one after the other: a lane per pixel along the rows, so one atomic instruction
     // touches runs of adjacent words
     unsigned long long todo = __ballot(some && !small);
@@ -615,11 +575,11 @@ __global__ void __launch_bounds__(kBlock) k_render_splat(const VoxelAcc *acc, un
       const int npx = sfw * sfh;  // (at most the view: 2^26)
       for (int p = lane; p < npx; p += 64) {
         const int row = p / sfw, col = p - row * sfw;
-        depth_min(zbuf + (size_t)(sy0 + row) * V.w + (sx0 + col), sword);
+        rules::depth_min(zbuf + (size_t)(sy0 + row) * V.w + (sx0 + col), sword);
       }
     }
   }
-  const unsigned long long b = wave_sum(behind), o = wave_sum(outside), d = wave_sum(drawn);
+  const unsigned long long b = rules::wave_sum(behind), o = rules::wave_sum(outside), d = rules::wave_sum(drawn);
   if (lane == 0) {
     if (b) atomicAdd(&ctrl->behind_near, b);
     if (o) atomicAdd(&ctrl->outside, o);
@@ -656,7 +616,7 @@ __global__ void __launch_bounds__(kBlock) k_render_resolve(const unsigned long l
     if (intensity) intensity[p] = g;
     if (index) index[p] = at;
   }
-  covered = wave_sum(covered);
+  covered = rules::wave_sum(covered);
   if ((threadIdx.x & 63) == 0 && covered) atomicAdd(&ctrl->covered, covered);
 }
 
@@ -675,10 +635,7 @@ namespace host {
 
 // device buffers of the map entries: grown to the largest call, kept by the context (nothing is allocated once warm)
 struct MapWorkspace {
-  struct Buf {
-    void *p = nullptr;
-    size_t bytes = 0;
-  };
+  typedef DeviceBuf Buf;  // (grown in 64 KiB steps: grow_ws)
   Buf pts, keys[2], vals[2], flags, counts, bsum, acc, out, bgr, images, ctrl;
   Buf zbuf, planes;  // a render: the 64-bit z-buffer, then depth | rgb | intensity | index of the view
   hipEvent_t ev[8] = {};  // input stage, sort, reduction, output copy: begin / end each
@@ -688,16 +645,7 @@ struct MapWorkspace {
 
 namespace {
 
-int grow(MapWorkspace::Buf &b, size_t bytes) {
-  if (bytes <= b.bytes) return DVO_AMD_OK;
-  if (b.p) (void)hipFree(b.p), b.p = nullptr, b.bytes = 0;
-  bytes = align_up(std::max<size_t>(bytes, 256), 1 << 16);
-  const hipError_t e = hipMalloc(&b.p, bytes);
-  if (e == hipErrorOutOfMemory) return DVO_AMD_ERR_OUT_OF_MEMORY;
-  if (e != hipSuccess) return fail_hip("hipMalloc (map workspace)", e);
-  b.bytes = bytes;
-  return DVO_AMD_OK;
-}
+int grow_ws(DeviceBuf &b, size_t bytes) { return grow(b, bytes, 1 << 16, "map workspace"); }
 
 int workspace(dvo_amd_context *ctx, MapWorkspace **out) {
   if (!ctx->map_ws) {
@@ -731,7 +679,7 @@ int bits_for(int span) {
 // exclusive scan of a[0..n) in place on the stream; grand (device, may be null) = the total
 int scan(MapWorkspace &W, unsigned *a, unsigned n, unsigned *grand, hipStream_t st) {
   const unsigned nb = std::max(1u, (n + map::kScanTile - 1) / map::kScanTile);
-  int rc = grow(W.bsum, sizeof(unsigned) * nb);
+  int rc = grow_ws(W.bsum, sizeof(unsigned) * nb);
   if (rc) return rc;
   unsigned *bsum = (unsigned *)W.bsum.p;
   hipLaunchKernelGGL(map::k_scan_reduce, dim3(nb), dim3(map::kBlock), 0, st, a, n, bsum);
@@ -751,9 +699,9 @@ int sort_voxels(MapWorkspace &W, const map::MapCtrl &c, hipStream_t st, int *cur
   map::Rekey r = {{c.mn[0], c.mn[1], c.mn[2]}, bj + bk, bk};
   const int passes = (bi + bj + bk + map::kRadixBits - 1) / map::kRadixBits;
   const unsigned nb = (m + map::kSortTile - 1) / map::kSortTile;
-  int rc = grow(W.counts, sizeof(unsigned) * map::kRadix * (size_t)nb);
+  int rc = grow_ws(W.counts, sizeof(unsigned) * map::kRadix * (size_t)nb);
   // the scan scratch for the larger of the two scans (the digit table, the head flags), before anything is enqueued
-  if (!rc) rc = grow(W.bsum, sizeof(unsigned) * (std::max<size_t>((size_t)map::kRadix * nb, m) / map::kScanTile + 1));
+  if (!rc) rc = grow_ws(W.bsum, sizeof(unsigned) * (std::max<size_t>((size_t)map::kRadix * nb, m) / map::kScanTile + 1));
   if (rc) return rc;
   unsigned long long *keys[2] = {(unsigned long long *)W.keys[0].p, (unsigned long long *)W.keys[1].p};
   unsigned *vals[2] = {(unsigned *)W.vals[0].p, (unsigned *)W.vals[1].p};
@@ -798,8 +746,8 @@ int reduce_voxels(MapWorkspace &W, const map::MapCtrl &c, const float4 *pts, dvo
     const unsigned *const vals[2] = {(unsigned *)W.vals[0].p, (unsigned *)W.vals[1].p};
     const unsigned *flags = (unsigned *)W.flags.p;
     if ((long long)n_vox <= capacity && out) {
-      rc = grow(W.acc, sizeof(map::VoxelAcc) * (size_t)n_vox);
-      if (!rc) rc = grow(W.out, sizeof(float4) * (size_t)n_vox);
+      rc = grow_ws(W.acc, sizeof(map::VoxelAcc) * (size_t)n_vox);
+      if (!rc) rc = grow_ws(W.out, sizeof(float4) * (size_t)n_vox);
       if (rc) return rc;
       map::VoxelAcc *acc = (map::VoxelAcc *)W.acc.p;
       HIP_TRY(hipEventRecord(W.ev[4], st));
@@ -835,7 +783,7 @@ int reduce_voxels(MapWorkspace &W, const map::MapCtrl &c, const float4 *pts, dvo
 
 // the control block before an input stage, and its read-back into the stats
 int start_ctrl(MapWorkspace &W, hipStream_t st) {
-  int rc = grow(W.ctrl, sizeof(map::MapCtrl));
+  int rc = grow_ws(W.ctrl, sizeof(map::MapCtrl));
   if (rc) return rc;
   map::MapCtrl c;
   std::memset(&c, 0, sizeof(c));
@@ -864,9 +812,9 @@ int read_ctrl(MapWorkspace &W, map::MapCtrl *c, long long points_in, dvo_amd_clo
 // the per-point buffers of the sort for n points
 int grow_points(MapWorkspace &W, size_t n, bool pts) {
   int rc = DVO_AMD_OK;
-  for (int b = 0; b < 2 && !rc; ++b) rc = grow(W.keys[b], 8 * n), rc = rc ? rc : grow(W.vals[b], 4 * n);
-  if (!rc) rc = grow(W.flags, 4 * n);
-  if (!rc && pts) rc = grow(W.pts, 16 * n);
+  for (int b = 0; b < 2 && !rc; ++b) rc = grow_ws(W.keys[b], 8 * n), rc = rc ? rc : grow_ws(W.vals[b], 4 * n);
+  if (!rc) rc = grow_ws(W.flags, 4 * n);
+  if (!rc && pts) rc = grow_ws(W.pts, 16 * n);
   return rc;
 }
 
@@ -882,8 +830,8 @@ int upload_images(MapWorkspace &W, int n, dvo_amd_pyramid *const *images, int le
     float_pose(poses ? poses + (size_t)pose_stride * k : nullptr, im.T);
     if (bgrs && bgrs[k]) bgr_bytes += (size_t)L.w * L.h * 3;
   }
-  int rc = grow(W.images, sizeof(map::MapImage) * std::max(1, n));
-  if (!rc && bgr_bytes) rc = grow(W.bgr, bgr_bytes);
+  int rc = grow_ws(W.images, sizeof(map::MapImage) * std::max(1, n));
+  if (!rc && bgr_bytes) rc = grow_ws(W.bgr, bgr_bytes);
   if (rc) return rc;
   size_t at = 0;
   for (int k = 0; k < n; ++k) {
@@ -964,7 +912,7 @@ struct DeltaItem {
 };
 
 // the store buffers grow geometrically: a session that gains a keyframe at a time reallocates O(log) times
-int grow_store(MapWorkspace::Buf &b, size_t bytes) { return bytes <= b.bytes ? DVO_AMD_OK : grow(b, std::max(bytes, 2 * b.bytes)); }
+int grow_store(MapWorkspace::Buf &b, size_t bytes) { return bytes <= b.bytes ? DVO_AMD_OK : grow_ws(b, std::max(bytes, 2 * b.bytes)); }
 
 int find_keyframe(const dvo_amd_map *M, int id) {
   for (size_t k = 0; k < M->kfs.size(); ++k)
@@ -1026,8 +974,8 @@ int apply_delta(dvo_amd_map *M, const std::vector<DeltaItem> &items, bool from_s
   const int n_items = (int)items.size();
   if (n_items > 0) {
     rc = grow_points(W, std::max<size_t>(1, total), true);
-    if (!rc) rc = grow(M->images, sizeof(map::MapImage) * (size_t)n_items);
-    if (!rc) rc = grow(M->counts, 2 * sizeof(unsigned long long) * (size_t)n_items);
+    if (!rc) rc = grow_ws(M->images, sizeof(map::MapImage) * (size_t)n_items);
+    if (!rc) rc = grow_ws(M->counts, 2 * sizeof(unsigned long long) * (size_t)n_items);
     if (rc) return rc;
     std::vector<map::MapImage> im((size_t)n_items);
     for (int k = 0; k < n_items; ++k) {
@@ -1066,8 +1014,8 @@ int apply_delta(dvo_amd_map *M, const std::vector<DeltaItem> &items, bool from_s
       int cur = 0;
       map::Rekey r;
       rc = sort_voxels(W, c, st, &cur, &n_delta, &r);
-      if (!rc) rc = grow(W.acc, sizeof(map::VoxelAcc) * (size_t)n_delta);
-      if (!rc) rc = grow(M->dkeys, sizeof(unsigned long long) * (size_t)n_delta);
+      if (!rc) rc = grow_ws(W.acc, sizeof(map::VoxelAcc) * (size_t)n_delta);
+      if (!rc) rc = grow_ws(M->dkeys, sizeof(unsigned long long) * (size_t)n_delta);
       if (rc) return rc;
       float ms = 0.f;
       HIP_TRY(hipEventElapsedTime(&ms, W.ev[2], W.ev[3]));
@@ -1100,7 +1048,7 @@ int apply_delta(dvo_amd_map *M, const std::vector<DeltaItem> &items, bool from_s
     if (!rc) rc = grow_store(M->tkeys, 8 * (size_t)merged);
     if (!rc) rc = grow_store(M->tacc, sizeof(map::VoxelAcc) * (size_t)merged);
     if (!rc) rc = grow_store(M->flags, 4 * (size_t)merged);
-    if (!rc) rc = grow(W.bsum, sizeof(unsigned) * ((size_t)merged / map::kScanTile + 1));
+    if (!rc) rc = grow_ws(W.bsum, sizeof(unsigned) * ((size_t)merged / map::kScanTile + 1));
     if (rc) return rc;
     map::MapCtrl *dctrl = (map::MapCtrl *)W.ctrl.p;
     HIP_TRY(hipEventRecord(M->ev[2], st));
@@ -1169,9 +1117,9 @@ int render_launches(dvo_amd_map *M, const double *pose, const dvo_amd_view *view
   if (rc) return rc;
   MapWorkspace &W = *Wp;
   const size_t n_px = (size_t)view->width * view->height;
-  rc = grow(W.zbuf, 8 * (n_px + 1));  // (cleared 16 bytes at a time)
-  if (!rc) rc = grow(W.planes, 16 * n_px);
-  if (!rc) rc = grow(W.ctrl, std::max(sizeof(map::MapCtrl), sizeof(map::RenderCtrl)));
+  rc = grow_ws(W.zbuf, 8 * (n_px + 1));  // (cleared 16 bytes at a time)
+  if (!rc) rc = grow_ws(W.planes, 16 * n_px);
+  if (!rc) rc = grow_ws(W.ctrl, std::max(sizeof(map::MapCtrl), sizeof(map::RenderCtrl)));
   if (rc) return rc;
   map::RenderView V;
   V.w = view->width, V.h = view->height, V.fx = view->fx, V.fy = view->fy, V.ox = view->ox, V.oy = view->oy;
@@ -1417,11 +1365,11 @@ int dvo_amd_map_extract(dvo_amd_map *M, const float *box, dvo_amd_point *out, lo
   }
   host::MapWorkspace *W = nullptr;
   rc = host::workspace(M->ctx, &W);
-  if (!rc) rc = host::grow(W->out, sizeof(float4) * (size_t)n);
-  if (!rc && box) rc = host::grow(W->pts, sizeof(float4) * (size_t)n);
+  if (!rc) rc = host::grow_ws(W->out, sizeof(float4) * (size_t)n);
+  if (!rc && box) rc = host::grow_ws(W->pts, sizeof(float4) * (size_t)n);
   if (!rc && box) rc = host::grow_store(M->flags, 4 * (size_t)n);
-  if (!rc && box) rc = host::grow(W->ctrl, sizeof(map::MapCtrl));
-  if (!rc && box) rc = host::grow(W->bsum, sizeof(unsigned) * ((size_t)n / map::kScanTile + 1));
+  if (!rc && box) rc = host::grow_ws(W->ctrl, sizeof(map::MapCtrl));
+  if (!rc && box) rc = host::grow_ws(W->bsum, sizeof(unsigned) * ((size_t)n / map::kScanTile + 1));
   if (rc) return rc;
   const hipStream_t st = M->ctx->stream;
   const float4 *src = (const float4 *)W->out.p;
@@ -1577,17 +1525,17 @@ int dvo_amd_debug_map_merge(dvo_amd_context *ctx, long long na, const unsigned l
   rc = host::workspace(ctx, &W);
   MergeProbeBuffers B;
   const size_t acc_bytes = sizeof(map::VoxelAcc);
-  if (!rc) rc = host::grow(B.ka, 8 * (size_t)n_store);
-  if (!rc) rc = host::grow(B.va, acc_bytes * n_store);
-  if (!rc) rc = host::grow(B.kb, 8 * (size_t)n_delta);
-  if (!rc) rc = host::grow(B.vb, acc_bytes * n_delta);
-  if (!rc) rc = host::grow(B.kt, 8 * (size_t)merged);
-  if (!rc) rc = host::grow(B.vt, acc_bytes * merged);
-  if (!rc) rc = host::grow(B.flags, 4 * (size_t)merged);
-  if (!rc) rc = host::grow(B.ko, 8 * (size_t)merged);
-  if (!rc) rc = host::grow(B.vo, acc_bytes * merged);
-  if (!rc) rc = host::grow(W->ctrl, sizeof(map::MapCtrl));
-  if (!rc) rc = host::grow(W->bsum, sizeof(unsigned) * ((size_t)merged / map::kScanTile + 1));
+  if (!rc) rc = host::grow_ws(B.ka, 8 * (size_t)n_store);
+  if (!rc) rc = host::grow_ws(B.va, acc_bytes * n_store);
+  if (!rc) rc = host::grow_ws(B.kb, 8 * (size_t)n_delta);
+  if (!rc) rc = host::grow_ws(B.vb, acc_bytes * n_delta);
+  if (!rc) rc = host::grow_ws(B.kt, 8 * (size_t)merged);
+  if (!rc) rc = host::grow_ws(B.vt, acc_bytes * merged);
+  if (!rc) rc = host::grow_ws(B.flags, 4 * (size_t)merged);
+  if (!rc) rc = host::grow_ws(B.ko, 8 * (size_t)merged);
+  if (!rc) rc = host::grow_ws(B.vo, acc_bytes * merged);
+  if (!rc) rc = host::grow_ws(W->ctrl, sizeof(map::MapCtrl));
+  if (!rc) rc = host::grow_ws(W->bsum, sizeof(unsigned) * ((size_t)merged / map::kScanTile + 1));
   if (rc) return rc;
   const hipStream_t st = ctx->stream;
   if (n_store > 0) {
@@ -1641,7 +1589,7 @@ int dvo_amd_point_cloud(dvo_amd_context *ctx, dvo_amd_pyramid *image, int level,
   rc = host::upload_images(*W, 1, &image, level, pose, 16, bgr ? bgrs : nullptr, strides, im, st);
   if (rc) return rc;
   const size_t n = (size_t)im[0].w * im[0].h;
-  rc = host::grow(W->out, 16 * n);
+  rc = host::grow_ws(W->out, 16 * n);
   if (rc) return rc;
   hipLaunchKernelGGL(map::k_cloud, dim3(map::grid_for(n, map::kBlock)), dim3(map::kBlock), 0, st, im[0], (float4 *)W->out.p);
   HIP_TRY(hipGetLastError());

@@ -22,6 +22,7 @@
 // integers only, so nothing depends on the launch geometry or on the order atomics land in.  One synchronisation per call
 // (mask_finish's), on the device's prep stream.
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -164,8 +165,6 @@ __global__ void __launch_bounds__(kBlock) k_mask_warp(const WarpRecord *__restri
   for (int rec = blockIdx.y; rec < n_records; rec += gridDim.y) {
     const WarpRecord R = records[rec];  // uniform over the block
     if (blockIdx.x * kChunk >= R.nt) continue;  // (block-uniform: no barrier is skipped by part of a block)
-    const float *T = R.T;
-    const float wmax = (float)(R.ws - 1), hmax = (float)(R.hs - 1);
     const int p0 = (blockIdx.x * kBlock + threadIdx.x) * kLanePixels;
     const bool live = p0 < R.nt;  // (nt is a multiple of 4: four pixels or none, all in one row)
     float z4[kLanePixels] = {0.f, 0.f, 0.f, 0.f};
@@ -185,38 +184,15 @@ __global__ void __launch_bounds__(kBlock) k_mask_warp(const WarpRecord *__restri
       bool keep = false, dropped = false;
       if (live) {
         const float z = z4[k];
-        keep = unseen_keep != 0;
-        if (fabsf(z) <= 3.402823466e38f) {  // finite (false for NaN)
-          const float x = R.txt[u0 + k] * z, y = ty * z;
-          const float qx = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-          const float qy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-          const float qz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
-          if (!(qz >= near_z)) {
-            cls = 1;
-          } else {
-            const float pu = floorf(((qx * R.fx) / qz + R.ox) + 0.5f);
-            const float pv = floorf(((qy * R.fy) / qz + R.oy) + 0.5f);
-            if (!(pu >= 0.0f && pu <= wmax && pv >= 0.0f && pv <= hmax)) {
-              cls = 2;
-            } else {
-              const size_t at = (size_t)(int)pv * (size_t)R.ws + (size_t)(int)pu;  // 0 <= pu <= ws-1, 0 <= pv <= hs-1: tested in float above
-              const float zs = R.zs[at];
-              if (!(zs == zs)) {
-                cls = 3;
-              } else {
-                const float s = qz - 0.4f;
-                const float tol = sigmas * (0.0012f + 0.0019f * (s * s));
-                const float d = zs - qz;
-                cls = d < -tol ? 5 : (d > tol ? 6 : 4);
-                if (cls == 4) {
-                  keep = R.ms[at] != 0;
-                  dropped = !keep;
-                } else {
-                  keep = inconsistent_keep != 0;
-                }
-              }
-            }
-          }
+        keep = unseen_keep != 0;  // (what is not seen: no depth here, behind, outside, no depth there)
+        size_t at;
+        if (rules::finite_f(z))
+          cls = rules::classify_covisible(z, R.txt[u0 + k], ty, R.T, near_z, sigmas, R.zs, R.ws, R.hs, R.fx, R.fy, R.ox, R.oy, at);
+        if (cls == 4) {
+          keep = R.ms[at] != 0;
+          dropped = !keep;
+        } else if (cls >= 5) {
+          keep = inconsistent_keep != 0;
         }
       }
       word |= keep ? (1u << (8 * k)) : 0u;
@@ -255,40 +231,11 @@ using namespace dvo_amd::mask_ops;
 namespace {
 
 // dvo_amd_debug_mask_ops_timing: two events around the launches of a call on the prep stream (off unless asked for)
-struct OpsTiming {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double last_ms = 0.0;
-};
-OpsTiming g_timing[kMaxDevices];
-
-// the bracket of one call: begin() before the first thing enqueued, end() behind the last launch, read() after the synchronisation
-struct Bracket {
-  OpsTiming &t;
-  bool timed;
-  explicit Bracket(int device) : t(g_timing[device]), timed(false) {
-    std::lock_guard<std::mutex> lk(t.mu);
-    timed = t.on && t.ev[0] && t.ev[1];
-  }
-  hipError_t begin(hipStream_t st) { return timed ? hipEventRecord(t.ev[0], st) : hipSuccess; }
-  hipError_t end(hipStream_t st) { return timed ? hipEventRecord(t.ev[1], st) : hipSuccess; }
-  void read() {
-    if (!timed) return;
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(t.mu);
-    t.last_ms = ms;
-  }
-};
+DeviceTiming g_timing[kMaxDevices];
 
 // dvo_amd_mask_warp_many: the record table and the counts of the call in flight (grown to the largest call and kept; used with
 // the device's mutex held from the table's upload to the last thing enqueued that touches it)
-struct WarpArea {
-  void *mem = nullptr;
-  size_t bytes = 0;
-};
-WarpArea g_warp_area[kMaxDevices];
+DeviceBuf g_warp_area[kMaxDevices];
 
 void drop(dvo_amd_mask *m) {
   (void)hipFree(m->mem);
@@ -342,7 +289,7 @@ int warp_many(const char *entry, int n, const dvo_amd_mask *const *masks, const 
       if (m) drop(m);
     return status;
   };
-  Bracket bracket(device);
+  Bracket bracket(g_timing[device]);
   for (int k = 0; k < n; ++k) {
     const dvo_amd_pyramid *t = targets[k];
     rc = mask_alloc(entry, device, t->lv[0].w, t->lv[0].h, t->n_levels, &made[(size_t)k], &st);
@@ -353,19 +300,13 @@ int warp_many(const char *entry, int n, const dvo_amd_mask *const *masks, const 
   // after the other (pyramid_build_batch does the same for its frame table).  mask_alloc above took and released it on its own.
   const size_t table_bytes = align_up(sizeof(WarpRecord) * n_records, 256), count_bytes = sizeof(unsigned) * kWarpCounts * n_records;
   std::unique_lock<std::mutex> area_lock(device_mutex(device));
-  WarpArea &area = g_warp_area[device];
-  if (area.bytes < table_bytes + count_bytes) {
-    if (area.mem) (void)hipFree(area.mem), area.mem = nullptr, area.bytes = 0;  // (hipFree waits for whatever still reads it)
-    const size_t grown = align_up(table_bytes + count_bytes, 1 << 16);
-    const hipError_t ea = hipMalloc(&area.mem, grown);
-    if (ea != hipSuccess) {
-      area.mem = nullptr;
-      area_lock.unlock();
-      return unwind(ea == hipErrorOutOfMemory ? (int)DVO_AMD_ERR_OUT_OF_MEMORY : fail_hip("hipMalloc (warp table)", ea));
-    }
-    area.bytes = grown;
+  DeviceBuf &area = g_warp_area[device];
+  rc = grow(area, table_bytes + count_bytes, 1 << 16, "warp table");
+  if (rc) {
+    area_lock.unlock();
+    return unwind(rc);
   }
-  void *scratch = area.mem;
+  void *scratch = area.p;
   unsigned *d_counts = (unsigned *)((char *)scratch + table_bytes);
   hipError_t e = hipSuccess;
   std::vector<WarpRecord> table(n_records);
@@ -381,8 +322,7 @@ int warp_many(const char *entry, int n, const dvo_amd_mask *const *masks, const 
       R.counts = d_counts + kWarpCounts * r;
       R.wt = A.w, R.nt = A.w * A.h, R.ws = B.w, R.hs = B.h;
       R.fx = B.fx, R.fy = B.fy, R.ox = B.ox, R.oy = B.oy;
-      for (int row = 0; row < 3; ++row)
-        for (int col = 0; col < 4; ++col) R.T[row * 4 + col] = (float)Tk[col * 4 + row];  // column-major in, rows 0..2 out
+      rows_from_column_major(Tk, R.T);
       max_nt = std::max(max_nt, R.nt);
     }
   }
@@ -393,9 +333,7 @@ int warp_many(const char *entry, int n, const dvo_amd_mask *const *masks, const 
   if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, count_bytes, st);
   if (e == hipSuccess) {
     const unsigned gx = (unsigned)((max_nt + kChunk - 1) / kChunk);
-    // a launch holds fewer than 2^31 threads and at most 65535 rows of blocks: a block takes further records in steps of gridDim.y
-    const unsigned gy = (unsigned)std::max<long long>(
-        1, std::min<long long>(std::min<long long>((long long)n_records, 65535), (1ll << 31) / ((long long)gx * kBlock)));
+    const unsigned gy = grid_rows((long long)n_records, gx, kBlock);  // a block takes further records in steps of gridDim.y
     hipLaunchKernelGGL(k_mask_warp, dim3(gx, gy), dim3(kBlock), 0, st, (const WarpRecord *)scratch, (int)n_records, opt->near_z,
                        opt->depth_sigmas, opt->unseen_keep, opt->inconsistent_keep);
     e = hipGetLastError();
@@ -446,7 +384,7 @@ int dvo_amd_mask_combine(const dvo_amd_mask *a, const dvo_amd_mask *b, int op, d
   hipStream_t st;
   const int rc = mask_alloc(entry, a->device, a->w, a->h, a->levels, &m, &st);
   if (rc) return rc;
-  Bracket bracket(a->device);
+  Bracket bracket(g_timing[a->device]);
   CombineLevels L = {};
   for (int l = 0; l < a->levels; ++l) {
     L.a[l] = a->plane[l], L.b[l] = b ? b->plane[l] : nullptr, L.out[l] = m->plane[l];
@@ -477,7 +415,7 @@ int dvo_amd_mask_morph(const dvo_amd_mask *mask, int op, const int *radius, dvo_
   hipStream_t st;
   const int rc = mask_alloc(entry, mask->device, mask->w, mask->h, mask->levels, &m, &st);
   if (rc) return rc;
-  Bracket bracket(mask->device);
+  Bracket bracket(g_timing[mask->device]);
   MorphLevels L = {};
   for (int l = 0; l < mask->levels; ++l) {
     L.src[l] = mask->plane[l], L.dst[l] = m->plane[l];
@@ -521,20 +459,7 @@ int dvo_amd_mask_warp(const dvo_amd_mask *mask, const dvo_amd_pyramid *source, c
 /* instrumentation: with enable != 0 every later dvo_amd_mask_combine / _morph / _warp / _warp_many on `device` is bracketed by two
  * events on the prep stream; *last_ms (may be NULL) receives the device time of the most recent bracketed call */
 int dvo_amd_debug_mask_ops_timing(int device, int enable, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  OpsTiming &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, nullptr, nullptr, last_ms);
 }
 
 }  // extern "C"

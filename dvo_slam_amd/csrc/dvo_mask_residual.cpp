@@ -24,11 +24,7 @@ namespace {
 
 // the record table and the counter blocks of the call in flight (grown to the largest call and kept; used with the device's mutex
 // held from the table's upload to the last thing enqueued that touches it, as dvo_amd_mask_warp_many's area)
-struct Area {
-  void *mem = nullptr;
-  size_t bytes = 0;
-};
-Area g_area[kMaxDevices];
+DeviceBuf g_area[kMaxDevices];
 
 void drop(dvo_amd_mask *m) {
   (void)hipFree(m->mem);
@@ -113,20 +109,14 @@ int from_residuals_many(const char *entry, dvo_amd_context *ctx, int n, const dv
   // the counter blocks lead the area (zeroed as one block that starts at the allocation's start), the table follows
   const size_t count_bytes = align_up(sizeof(unsigned) * kRmWords * n_records, 256), table_bytes = sizeof(ResidualMaskRecord) * n_records;
   std::unique_lock<std::mutex> area_lock(device_mutex(device));
-  Area &area = g_area[device];
-  if (area.bytes < count_bytes + table_bytes) {
-    if (area.mem) (void)hipFree(area.mem), area.mem = nullptr, area.bytes = 0;  // (hipFree waits for whatever still reads it)
-    const size_t grown = align_up(count_bytes + table_bytes, 1 << 16);
-    const hipError_t ea = hipMalloc(&area.mem, grown);
-    if (ea != hipSuccess) {
-      area.mem = nullptr;
-      area_lock.unlock();
-      return unwind(ea == hipErrorOutOfMemory ? (int)DVO_AMD_ERR_OUT_OF_MEMORY : fail_hip("hipMalloc (residual mask table)", ea));
-    }
-    area.bytes = grown;
+  DeviceBuf &area = g_area[device];
+  rc = grow(area, count_bytes + table_bytes, 1 << 16, "residual mask table");
+  if (rc) {
+    area_lock.unlock();
+    return unwind(rc);
   }
-  unsigned *d_counts = (unsigned *)area.mem;
-  ResidualMaskRecord *d_table = (ResidualMaskRecord *)((char *)area.mem + count_bytes);
+  unsigned *d_counts = (unsigned *)area.p;
+  ResidualMaskRecord *d_table = (ResidualMaskRecord *)((char *)area.p + count_bytes);
   std::vector<ResidualMaskRecord> table(n_records);
   int max_n = 1;
   size_t r = 0;

@@ -18,6 +18,7 @@
 // Counts (defined, undefined, kept) are ballots and popcounts per wave, integer adds into LDS per block and one integer
 // atomicAdd per non-zero count and block: integers only, no float atomic anywhere.
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -36,7 +37,6 @@ constexpr int kZW = kCW + 2, kZH = kCH + 2;                        // the depths
 static_assert(kBlock == 256 && kBlock % 64 == 0, "four waves per block");
 static_assert(DVO_AMD_NORMAL_MAX_RADIUS == 8, "the header's bound");
 
-#define NORMALS_GLOBAL __attribute__((address_space(1)))
 typedef float v4f __attribute__((ext_vector_type(4)));  // a normal (a plain vector type: storable to any address space)
 
 // one level of one call as the kernel reads it (block-uniform: scalar registers)
@@ -54,7 +54,6 @@ struct Record {
   float R[9];                // (rotate) row-major rotation applied to a defined normal
 };
 
-__device__ __forceinline__ bool finite(float v) { return fabsf(v) <= 3.402823466e38f; }  // (false for NaN)
 
 // steps 4..7 for a pixel whose window sum is (mx, my, mz) over `have` members, and its outputs
 struct Pixel {
@@ -99,9 +98,9 @@ __global__ void __launch_bounds__(kBlock) k_normals(const Record *__restrict__ r
   const int u = x0 + lx, v = y0 + ly;
   const bool live = u < L.w && v < L.h;
   const int w = L.w, h = L.h, r = L.r;
-  const NORMALS_GLOBAL float *Z = (const NORMALS_GLOBAL float *)L.z;
-  const NORMALS_GLOBAL float *TX = (const NORMALS_GLOBAL float *)L.tx;
-  const NORMALS_GLOBAL float *TY = (const NORMALS_GLOBAL float *)L.ty;
+  const DVO_DEVICE_GLOBAL float *Z = (const DVO_DEVICE_GLOBAL float *)L.z;
+  const DVO_DEVICE_GLOBAL float *TX = (const DVO_DEVICE_GLOBAL float *)L.tx;
+  const DVO_DEVICE_GLOBAL float *TY = (const DVO_DEVICE_GLOBAL float *)L.ty;
   const float nan = __builtin_nanf("");
 
   if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0u;
@@ -121,9 +120,9 @@ __global__ void __launch_bounds__(kBlock) k_normals(const Record *__restrict__ r
       const float bx = txu * zq - txu * zn, by = tyq * zq - tyn * zn, bz = zq - zn;
       const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
       px = txu * z, py = tyv * z;
-      const bool usable = finite(cx) && finite(cy) && finite(cz);
+      const bool usable = rules::finite_f(cx) && rules::finite_f(cy) && rules::finite_f(cz);
       const bool near = !(L.ratio > 0.0f) || fabsf(z - z) <= L.ratio * z;
-      have = finite(z) && usable && near;
+      have = rules::finite_f(z) && usable && near;
       mx = cx, my = cy, mz = cz;
     }
     __syncthreads();  // (s_cnt is cleared)
@@ -158,7 +157,7 @@ __global__ void __launch_bounds__(kBlock) k_normals(const Record *__restrict__ r
         const float ax = txp * zp - txm * zm, ay = tyv * zp - tyv * zm, az = zp - zm;
         const float bx = txu * zq - txu * zn, by = tyq * zq - tyn * zn, bz = zq - zn;
         cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
-        if (!(finite(cx) && finite(cy) && finite(cz))) cx = nan;  // not usable: never a member
+        if (!(rules::finite_f(cx) && rules::finite_f(cy) && rules::finite_f(cz))) cx = nan;  // not usable: never a member
       }
       s_cx[k] = cx, s_cy[k] = cy, s_cz[k] = cz;
     }
@@ -168,7 +167,7 @@ __global__ void __launch_bounds__(kBlock) k_normals(const Record *__restrict__ r
     px = s_tx[lx + r + 1] * z, py = s_ty[ly + r + 1] * z;
     const float tol = L.ratio * z;
     const bool test = L.ratio > 0.0f;
-    if (live && finite(z)) {
+    if (live && rules::finite_f(z)) {
       for (int dv = 0; dv <= 2 * r; ++dv) {
         const int crow = (ly + dv) * cw + lx, zrow = (ly + dv + 1) * zw + lx + 1;
         for (int du = 0; du <= 2 * r; ++du) {
@@ -197,10 +196,10 @@ __global__ void __launch_bounds__(kBlock) k_normals(const Record *__restrict__ r
     if (L.normals) {
       v4f n4;
       n4[0] = o.nx, n4[1] = o.ny, n4[2] = o.nz, n4[3] = o.nw;
-      ((NORMALS_GLOBAL v4f *)L.normals)[at] = n4;  // (one 16-byte store)
+      ((DVO_DEVICE_GLOBAL v4f *)L.normals)[at] = n4;  // (one 16-byte store)
     }
-    if (L.facing) ((NORMALS_GLOBAL float *)L.facing)[at] = o.facing;
-    if (L.mask) ((NORMALS_GLOBAL unsigned char *)L.mask)[at] = keep ? 1 : 0;
+    if (L.facing) ((DVO_DEVICE_GLOBAL float *)L.facing)[at] = o.facing;
+    if (L.mask) ((DVO_DEVICE_GLOBAL unsigned char *)L.mask)[at] = keep ? 1 : 0;
   }
   const unsigned n_def = (unsigned)__popcll(__ballot(live && o.defined));
   const unsigned n_und = (unsigned)__popcll(__ballot(live && !o.defined));
@@ -213,10 +212,10 @@ __global__ void __launch_bounds__(kBlock) k_normals(const Record *__restrict__ r
   __syncthreads();
   if (threadIdx.x < 2) {
     const unsigned c = s_cnt[threadIdx.x];
-    if (c) (void)__hip_atomic_fetch_add((NORMALS_GLOBAL unsigned *)L.counts + threadIdx.x, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (c) (void)__hip_atomic_fetch_add((DVO_DEVICE_GLOBAL unsigned *)L.counts + threadIdx.x, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   } else if (threadIdx.x == 2 && L.mask) {
     const unsigned c = s_cnt[2];
-    if (c) (void)__hip_atomic_fetch_add((NORMALS_GLOBAL int *)L.kept, (int)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (c) (void)__hip_atomic_fetch_add((DVO_DEVICE_GLOBAL int *)L.kept, (int)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -231,14 +230,7 @@ namespace {
 
 // dvo_amd_debug_normals_timing: what the last call on the device launched and waited for, and (when asked for) two events
 // around its launch on the prep stream
-struct NormalsTiming {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int launches = 0, synchronisations = 0;
-  double last_ms = 0.0;
-};
-NormalsTiming g_timing[kMaxDevices];
+DeviceTiming g_timing[kMaxDevices];
 
 int check_options(const char *entry, const dvo_amd_pyramid *p, const dvo_amd_normal_options *opt) {
   for (int l = 0; l < p->n_levels && l < DVO_AMD_MAX_LEVELS; ++l)
@@ -265,58 +257,35 @@ void fill_record(Record &R, const LevelData &L, int level, const dvo_amd_normal_
 }
 
 // the call's own scratch on the device: the records and the counts in front, then whatever planes the call wants
-struct Scratch {
-  int device = 0;
-  void *mem = nullptr;
-  size_t bytes = 0;
+struct CallScratch : Scratch {
   Record *records = nullptr;
   unsigned *counts = nullptr;  // [DVO_AMD_MAX_LEVELS][2]
   char *planes = nullptr;
-  ~Scratch() {
-    if (mem) slab_free(device, bytes, mem);
-  }
 };
 constexpr size_t kRecordBytes = (sizeof(Record) * DVO_AMD_MAX_LEVELS + 255) / 256 * 256;
 constexpr size_t kCountBytes = 256;
 static_assert(sizeof(unsigned) * 2 * DVO_AMD_MAX_LEVELS <= kCountBytes, "two counts per level");
 
-int scratch_alloc(Scratch &S, int device, size_t plane_bytes) {
-  S.device = device, S.bytes = kRecordBytes + kCountBytes + plane_bytes;
-  const int rc = slab_alloc(device, S.bytes, &S.mem);
-  if (rc) {
-    S.mem = nullptr;
-    return rc;
-  }
+int scratch_alloc(CallScratch &S, int device, size_t plane_bytes) {
+  const int rc = S.take(device, kRecordBytes + kCountBytes + plane_bytes);
+  if (rc) return rc;
   S.records = (Record *)S.mem;
-  S.counts = (unsigned *)((char *)S.mem + kRecordBytes);
-  S.planes = (char *)S.mem + kRecordBytes + kCountBytes;
+  S.counts = (unsigned *)(S.base() + kRecordBytes);
+  S.planes = S.base() + kRecordBytes + kCountBytes;
   return DVO_AMD_OK;
 }
 
 // the records up, the counts cleared, the one launch (bracketed by the device's two events when timing is on)
-hipError_t launch(const Scratch &S, const Record *table, int n_records, int n_blocks, NormalsTiming &timing, bool timed, hipStream_t st) {
+hipError_t launch(const CallScratch &S, const Record *table, int n_records, int n_blocks, Bracket &bracket, hipStream_t st) {
   hipError_t e = hipMemcpyAsync(S.records, table, sizeof(Record) * (size_t)n_records, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(S.counts, 0, kCountBytes, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_normals, dim3((unsigned)n_blocks), dim3(kBlock), 0, st, (const Record *)S.records, n_records);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   return e;
-}
-
-bool timing_begin(NormalsTiming &t) {
-  std::lock_guard<std::mutex> lk(t.mu);
-  return t.on && t.ev[0] && t.ev[1];
-}
-
-void timing_end(NormalsTiming &t, bool timed, int launches, int synchronisations) {
-  float ms = 0.f;
-  const bool have_ms = timed && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess;
-  std::lock_guard<std::mutex> lk(t.mu);
-  t.launches = launches, t.synchronisations = synchronisations;
-  if (have_ms) t.last_ms = ms;
 }
 
 // one level's planes into host memory; rotation: null, or nine floats applied to every defined normal
@@ -331,7 +300,7 @@ int level_to_host(const char *entry, const dvo_amd_pyramid *p, int level, const 
   if ((long long)L.w * L.h > (1ll << 30)) return invalid(entry, "the level is larger than 2^30 pixels");
   const size_t n = (size_t)L.n;
   const size_t normal_bytes = normals ? align_up(16 * n, 256) : 0, facing_bytes = facing ? align_up(4 * n, 256) : 0;
-  Scratch S;
+  CallScratch S;
   rc = scratch_alloc(S, device, normal_bytes + facing_bytes);
   if (rc) return rc;
   Record R;
@@ -344,17 +313,16 @@ int level_to_host(const char *entry, const dvo_amd_pyramid *p, int level, const 
     R.rotate = 1;
     for (int i = 0; i < 9; ++i) R.R[i] = rotation[i];
   }
-  NormalsTiming &timing = g_timing[device];
-  const bool timed = timing_begin(timing);
+  Bracket bracket(g_timing[device]);
   unsigned h_counts[2] = {0u, 0u};
-  hipError_t e = launch(S, &R, 1, n_blocks, timing, timed, st);
+  hipError_t e = launch(S, &R, 1, n_blocks, bracket, st);
   if (e == hipSuccess && normals) e = hipMemcpyAsync(normals, R.normals, 16 * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && facing) e = hipMemcpyAsync(facing, R.facing, 4 * n, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && counts) e = hipMemcpyAsync(h_counts, S.counts, sizeof(h_counts), hipMemcpyDeviceToHost, st);
   const hipError_t es = hipStreamSynchronize(st);  // the call's one synchronisation (before the scratch goes back, whatever failed)
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail_hip("surface normals", e);
-  timing_end(timing, timed, 1, 1);
+  bracket.read(1, 1);
   if (counts) counts[0] = h_counts[0], counts[1] = h_counts[1];
   return DVO_AMD_OK;
 }
@@ -400,7 +368,7 @@ int dvo_amd_mask_from_normals(const dvo_amd_pyramid *p, const dvo_amd_normal_opt
   hipStream_t st = nullptr;
   rc = mask_alloc(entry, device, p->lv[0].w, p->lv[0].h, levels, &m, &st);
   if (rc) return rc;
-  Scratch S;
+  CallScratch S;
   rc = scratch_alloc(S, device, 0);
   if (rc) {
     (void)hipStreamSynchronize(st);
@@ -416,17 +384,16 @@ int dvo_amd_mask_from_normals(const dvo_amd_pyramid *p, const dvo_amd_normal_opt
     R.mask = m->plane[l], R.kept = m->counters + l, R.counts = S.counts + 2 * l;
     R.min_facing = min_facing[l], R.undefined_keep = undefined_keep;
   }
-  NormalsTiming &timing = g_timing[device];
-  const bool timed = timing_begin(timing);
+  Bracket bracket(g_timing[device]);
   unsigned h_counts[2 * DVO_AMD_MAX_LEVELS] = {};
-  hipError_t e = launch(S, table, levels, n_blocks, timing, timed, st);
+  hipError_t e = launch(S, table, levels, n_blocks, bracket, st);
   if (e == hipSuccess && counts) e = hipMemcpyAsync(h_counts, S.counts, sizeof(unsigned) * 2 * (size_t)levels, hipMemcpyDeviceToHost, st);
   rc = mask_finish(m, e, st, out);  // the call's one synchronisation; on failure the mask is gone (and the stream drained)
   if (rc) {
     *out = nullptr;
     return rc;
   }
-  timing_end(timing, timed, 1, 1);
+  bracket.read(1, 1);
   if (counts)
     for (int l = 0; l < levels; ++l) counts[3 * l] = h_counts[2 * l], counts[3 * l + 1] = h_counts[2 * l + 1], counts[3 * l + 2] = (*out)->kept[l];
   return DVO_AMD_OK;
@@ -491,22 +458,7 @@ int dvo_amd_write_pcd_normals(const char *path, const dvo_amd_point *points, con
  * the launch of every later call is bracketed by two events on the prep stream and *last_ms (may be NULL) receives the device
  * time of the most recent bracketed launch */
 int dvo_amd_debug_normals_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  NormalsTiming &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (launches) *launches = t.launches;
-  if (synchronisations) *synchronisations = t.synchronisations;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, launches, synchronisations, last_ms);
 }
 
 }  // extern "C"

@@ -21,10 +21,7 @@
 
 namespace {
 
-struct Buf {  // device memory grown to the largest call and kept
-  void *mem = nullptr;
-  size_t bytes = 0;
-};
+typedef DeviceBuf Buf;  // device memory grown to the largest call (in 64 KiB steps) and kept
 
 }  // namespace
 
@@ -54,13 +51,7 @@ constexpr size_t kDotsCapBytes = (size_t)DVO_AMD_PLACE_DOTS_CAP_MB << 20;  // th
 constexpr int kMaxPanelRows = 1 << 16;
 
 // dvo_amd_debug_place_timing: two events around the launches of the most recent scores / query call (off unless asked for)
-struct PlaceTiming {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  double last_ms = 0.0;
-};
-PlaceTiming g_timing[kMaxDevices];
+DeviceTiming g_timing[kMaxDevices];
 
 int dots_tile() {  // DVO_AMD_PLACE_TILE=1|2|4: the workgroup tile of k_place_dots (tuning; 0 = chosen by the number of queries)
   static const int t = [] {
@@ -70,22 +61,11 @@ int dots_tile() {  // DVO_AMD_PLACE_TILE=1|2|4: the workgroup tile of k_place_do
   return t;
 }
 
-int grow(Buf &b, size_t bytes, const char *what) {
-  if (b.bytes >= bytes) return DVO_AMD_OK;
-  if (b.mem) (void)hipFree(b.mem), b.mem = nullptr, b.bytes = 0;
-  const size_t grown = align_up(bytes, 1 << 16);
-  const hipError_t e = hipMalloc(&b.mem, grown);
-  if (e != hipSuccess) {
-    b.mem = nullptr;
-    return e == hipErrorOutOfMemory ? (int)DVO_AMD_ERR_OUT_OF_MEMORY : fail_hip(what, e);
-  }
-  b.bytes = grown;
-  return DVO_AMD_OK;
-}
+int grow(Buf &b, size_t bytes, const char *what) { return grow(b, bytes, 1 << 16, what); }
 
 void release(Buf &b) {
-  if (b.mem) (void)hipFree(b.mem);
-  b.mem = nullptr, b.bytes = 0;
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr, b.bytes = 0;
 }
 
 inline double inv_norm(int nn) { return nn > 0 ? 1.0 / std::sqrt((double)nn) : 0.0; }
@@ -122,22 +102,9 @@ hipError_t describe(dvo_amd_place_index &ix, int n, const dvo_amd_pyramid *const
                     std::vector<const float *> &table, hipStream_t st) {
   table.resize((size_t)n);
   for (int i = 0; i < n; ++i) table[(size_t)i] = p[i]->lv[ix.level].r_i;  // the level's intensity plane, row-major w x h
-  hipError_t e = hipMemcpyAsync(ix.ptrs.mem, table.data(), sizeof(const float *) * (size_t)n, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_place_describe((const float *const *)ix.ptrs.mem, n, w, h, dim, ix.gain, rows, nn, st);
+  hipError_t e = hipMemcpyAsync(ix.ptrs.p, table.data(), sizeof(const float *) * (size_t)n, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = launch_place_describe((const float *const *)ix.ptrs.p, n, w, h, dim, ix.gain, rows, nn, st);
   return e;
-}
-
-bool timing_on(PlaceTiming &t) {
-  std::lock_guard<std::mutex> lk(t.mu);
-  return t.on && t.ev[0] && t.ev[1];
-}
-
-void timing_take(PlaceTiming &t) {
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess) {
-    std::lock_guard<std::mutex> lk(t.mu);
-    t.last_ms = ms;
-  }
 }
 
 int panel_rows(int n_queries, int n) {
@@ -154,15 +121,14 @@ int run_query(dvo_amd_place_index &ix, const char *what, int nq, const std::vect
   const size_t nk = (size_t)nq * (size_t)k;
   // io: [r_query nq][scores nq k] doubles, then [query ids nq][candidates nq k][counts nq] ints
   const size_t io_bytes = sizeof(double) * ((size_t)nq + nk) + sizeof(int) * (2 * (size_t)nq + nk);
-  int rc = grow(ix.io, io_bytes, "hipMalloc (place query)");
+  int rc = grow(ix.io, io_bytes, "place query");
   if (rc) return rc;
   const int panel = panel_rows(nq, n);
-  rc = grow(ix.dots, sizeof(int) * (size_t)panel * (size_t)n, "hipMalloc (place dots)");
+  rc = grow(ix.dots, sizeof(int) * (size_t)panel * (size_t)n, "place dots");
   if (rc) return rc;
-  double *d_rq = (double *)ix.io.mem, *d_scores = d_rq + nq;
+  double *d_rq = (double *)ix.io.p, *d_scores = d_rq + nq;
   int *d_qid = (int *)(d_scores + nk), *d_cand = d_qid + nq, *d_counts = d_cand + nk;
-  PlaceTiming &timing = g_timing[ix.device];
-  const bool timed = timing_on(timing);
+  Bracket bracket(g_timing[ix.device]);
   hipError_t e = hipSuccess;
   if (ix.r_uploaded < n) {
     e = hipMemcpyAsync(ix.r + ix.r_uploaded, ix.h_r.data() + ix.r_uploaded, sizeof(double) * (size_t)(n - ix.r_uploaded), hipMemcpyHostToDevice, st);
@@ -170,23 +136,23 @@ int run_query(dvo_amd_place_index &ix, const char *what, int nq, const std::vect
   }
   if (e == hipSuccess) e = hipMemcpyAsync(d_rq, h_rq.data(), sizeof(double) * (size_t)nq, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemcpyAsync(d_qid, h_qid.data(), sizeof(int) * (size_t)nq, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   for (int q0 = 0; q0 < nq && e == hipSuccess; q0 += panel) {
     const int cnt = std::min(panel, nq - q0);
     e = launch_place_dots(ix.rows, frame_rows ? nullptr : d_qid + q0, frame_rows ? frame_rows + (size_t)q0 * (size_t)ix.dim : nullptr, cnt, ix.rows, n,
-                          ix.dim, (int *)ix.dots.mem, dots_tile(), st);
+                          ix.dim, (int *)ix.dots.p, dots_tile(), st);
     if (e == hipSuccess)
-      e = launch_place_topk((const int *)ix.dots.mem, cnt, n, d_qid + q0, d_rq + q0, ix.r, k, opt->min_score, opt->exclude_recent,
+      e = launch_place_topk((const int *)ix.dots.p, cnt, n, d_qid + q0, d_rq + q0, ix.r, k, opt->min_score, opt->exclude_recent,
                             d_cand + (size_t)q0 * k, d_scores + (size_t)q0 * k, d_counts + q0, st);
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   if (e == hipSuccess) e = hipMemcpyAsync(candidates, d_cand, sizeof(int) * nk, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(scores, d_scores, sizeof(double) * nk, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(counts, d_counts, sizeof(int) * (size_t)nq, hipMemcpyDeviceToHost, st);
   const hipError_t es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail_hip(what, e);
-  if (timed) timing_take(timing);
+  bracket.read();
   return DVO_AMD_OK;
 }
 
@@ -260,7 +226,7 @@ int dvo_amd_place_index_add(dvo_amd_place_index *ix, int n, const dvo_amd_pyrami
   hipStream_t st = nullptr;
   rc = device_prep_stream(ix->device, &st);
   if (rc) return rc;
-  rc = grow(ix->ptrs, sizeof(const float *) * (size_t)n, "hipMalloc (place table)");
+  rc = grow(ix->ptrs, sizeof(const float *) * (size_t)n, "place table");
   if (rc) return rc;
 
   // growth: a new allocation of twice the rows (at least DVO_AMD_PLACE_INITIAL_CAPACITY, at least what the call needs), the old rows copied
@@ -355,26 +321,25 @@ int dvo_amd_place_scores(const dvo_amd_place_index *index, int n_queries, const 
   hipStream_t st = nullptr;
   rc = device_prep_stream(ix.device, &st);
   if (rc) return rc;
-  rc = grow(ix.io, sizeof(int) * (size_t)n_queries, "hipMalloc (place scores)");
+  rc = grow(ix.io, sizeof(int) * (size_t)n_queries, "place scores");
   if (rc) return rc;
   const int panel = panel_rows(n_queries, n);
-  rc = grow(ix.dots, sizeof(int) * (size_t)panel * (size_t)n, "hipMalloc (place dots)");
+  rc = grow(ix.dots, sizeof(int) * (size_t)panel * (size_t)n, "place dots");
   if (rc) return rc;
-  int *d_qid = (int *)ix.io.mem;
-  PlaceTiming &timing = g_timing[ix.device];
-  const bool timed = timing_on(timing);
+  int *d_qid = (int *)ix.io.p;
+  Bracket bracket(g_timing[ix.device]);
   hipError_t e = hipMemcpyAsync(d_qid, query_ids, sizeof(int) * (size_t)n_queries, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   for (int q0 = 0; q0 < n_queries && e == hipSuccess; q0 += panel) {
     const int cnt = std::min(panel, n_queries - q0);
-    e = launch_place_dots(ix.rows, d_qid + q0, nullptr, cnt, ix.rows + (size_t)first * (size_t)ix.dim, n, ix.dim, (int *)ix.dots.mem, dots_tile(), st);
-    if (e == hipSuccess && timed && q0 + cnt == n_queries) e = hipEventRecord(timing.ev[1], st);
-    if (e == hipSuccess) e = hipMemcpyAsync(dots + (size_t)q0 * (size_t)n, ix.dots.mem, sizeof(int) * (size_t)cnt * (size_t)n, hipMemcpyDeviceToHost, st);
+    e = launch_place_dots(ix.rows, d_qid + q0, nullptr, cnt, ix.rows + (size_t)first * (size_t)ix.dim, n, ix.dim, (int *)ix.dots.p, dots_tile(), st);
+    if (e == hipSuccess && q0 + cnt == n_queries) e = bracket.end(st);
+    if (e == hipSuccess) e = hipMemcpyAsync(dots + (size_t)q0 * (size_t)n, ix.dots.p, sizeof(int) * (size_t)cnt * (size_t)n, hipMemcpyDeviceToHost, st);
   }
   const hipError_t es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail_hip("place scores", e);
-  if (timed) timing_take(timing);
+  bracket.read();
   return DVO_AMD_OK;
 }
 
@@ -429,13 +394,13 @@ int dvo_amd_place_query_frames(const dvo_amd_place_index *index, int n_queries, 
   hipStream_t st = nullptr;
   rc = device_prep_stream(ix.device, &st);
   if (rc) return rc;
-  rc = grow(ix.ptrs, sizeof(const float *) * (size_t)n_queries, "hipMalloc (place table)");
+  rc = grow(ix.ptrs, sizeof(const float *) * (size_t)n_queries, "place table");
   if (rc) return rc;
   const size_t row_bytes = align_up((size_t)n_queries * (size_t)ix.dim, 256);
-  rc = grow(ix.qrows, row_bytes + sizeof(int) * (size_t)n_queries, "hipMalloc (place frames)");
+  rc = grow(ix.qrows, row_bytes + sizeof(int) * (size_t)n_queries, "place frames");
   if (rc) return rc;
-  signed char *d_rows = (signed char *)ix.qrows.mem;
-  int *d_nn = (int *)((char *)ix.qrows.mem + row_bytes);
+  signed char *d_rows = (signed char *)ix.qrows.p;
+  int *d_nn = (int *)((char *)ix.qrows.p + row_bytes);
   std::vector<const float *> table;
   std::vector<int> norms((size_t)n_queries);
   hipError_t e = describe(ix, n_queries, frames, ix.w, ix.h, ix.dim, d_rows, d_nn, table, st);
@@ -452,20 +417,7 @@ int dvo_amd_place_query_frames(const dvo_amd_place_index *index, int n_queries, 
 /* instrumentation: with enable != 0 the kernel launches of every later dvo_amd_place_scores / _query / _query_frames on `device` are
  * bracketed by two events on the prep stream; *last_ms (may be NULL) receives the device time of the most recent bracketed call */
 int dvo_amd_debug_place_timing(int device, int enable, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  PlaceTiming &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, nullptr, nullptr, last_ms);
 }
 
 }  // extern "C"

@@ -29,11 +29,7 @@ namespace {
 constexpr float kMaxMaxDistance = 1024.0f;  // q(max_distance) <= 2^20: a lane's four costs and a wave's sum stay inside 32 bits
 constexpr size_t kMaxHypotheses = (size_t)1 << 22;  // of a call: 80 bytes each in the kept area
 
-struct Area {
-  void *mem = nullptr;
-  size_t bytes = 0;
-};
-Area g_area[kMaxDevices];
+DeviceBuf g_area[kMaxDevices];
 
 // q(x) = (uint32) floor(x * 1024.0f) in fp32 for 0 <= x <= 1024: the product is exact
 unsigned q_of(float x) { return (unsigned)std::floor(x * 1024.0f); }
@@ -107,19 +103,11 @@ int score_many(const char *entry, dvo_amd_context *ctx, int n, const dvo_amd_pyr
   float *h_kt = (float *)(staged.data() + kt_at);
 
   std::unique_lock<std::mutex> area_lock(device_mutex(device));
-  Area &area = g_area[device];
-  if (area.bytes < sums_bytes + upload_bytes) {
-    if (area.mem) (void)hipFree(area.mem), area.mem = nullptr, area.bytes = 0;  // (hipFree waits for whatever still reads it)
-    const size_t grown = align_up(sums_bytes + upload_bytes, 1 << 16);
-    const hipError_t ea = hipMalloc(&area.mem, grown);
-    if (ea != hipSuccess) {
-      area.mem = nullptr;
-      return ea == hipErrorOutOfMemory ? (int)DVO_AMD_ERR_OUT_OF_MEMORY : fail_hip("hipMalloc (pose score area)", ea);
-    }
-    area.bytes = grown;
-  }
-  unsigned long long *d_sums = (unsigned long long *)area.mem;
-  char *d_upload = (char *)area.mem + sums_bytes;
+  DeviceBuf &area = g_area[device];
+  rc = grow(area, sums_bytes + upload_bytes, 1 << 16, "pose score area");
+  if (rc) return rc;
+  unsigned long long *d_sums = (unsigned long long *)area.p;
+  char *d_upload = (char *)area.p + sums_bytes;
   PoseScoreLevel *d_levels = (PoseScoreLevel *)(d_upload + levels_at);
   const float *d_kt = (const float *)(d_upload + kt_at);
 

@@ -10,6 +10,7 @@
 // The minimum does not depend on the order the atomics land in and the words only decrease: the plane and the counters are a
 // function of the frame and the registration alone.
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -31,28 +32,6 @@ struct View {
 struct Ctrl {
   unsigned long long behind, outside, drawn, covered;
 };
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// one axis of the footprint (dvo_amd.h: rule 5 of the registration, which is rule 5 of dvo_amd_map_render), compared in float
-// before any conversion to int; false: no pixel of the axis is covered
-__device__ __forceinline__ bool footprint_axis(float c, float half, bool fill, int size, int &lo, int &hi) {
-  float a = ceilf(c - half), b = floorf(c + half);
-  if (!fill || b < a) a = b = floorf(c + 0.5f);
-  const float last = (float)(size - 1);
-  if (!(b >= 0.0f && a <= last)) return false;
-  lo = a > 0.0f ? (int)a : 0;
-  hi = b < last ? (int)b : size - 1;
-  return true;
-}
-
-// the stale value a plain load may return is never smaller than the word in memory: skipping the atomic on it is exact
-__device__ __forceinline__ void depth_min(unsigned *z, unsigned word) {
-  if (*z > word) atomicMin(z, word);
-}
 
 __global__ void __launch_bounds__(kBlock) k_register_splat(const unsigned short *__restrict__ raw_z, int z_stride, float z_scale,
                                                            Registration R, View V, unsigned *zbuf, Ctrl *ctrl) {
@@ -81,7 +60,8 @@ __global__ void __launch_bounds__(kBlock) k_register_splat(const unsigned short 
           const float uc = (cx * V.fx) / cz + V.ox, vc = (cy * V.fy) / cz + V.oy;
           const float s = z / cz;
           const float hx = fminf(0.5f * (R.mx * s), 4.0f), hy = fminf(0.5f * (R.my * s), 4.0f);
-          const bool in_x = footprint_axis(uc, hx, R.fill != 0, V.w, x0, x1), in_y = footprint_axis(vc, hy, R.fill != 0, V.h, y0, y1);
+          const int mode = R.fill != 0 ? rules::kFootprintFill : rules::kFootprintNearest;
+          const bool in_x = rules::footprint_axis(uc, hx, mode, V.w, x0, x1), in_y = rules::footprint_axis(vc, hy, mode, V.h, y0, y1);
           draw = in_x && in_y;
           if (draw) ++drawn, word = __float_as_uint(cz);
           else ++outside;
@@ -92,7 +72,7 @@ __global__ void __launch_bounds__(kBlock) k_register_splat(const unsigned short 
       const bool small = some && fw * fh <= kSmallFootprint;
       if (small)
         for (int yy = y0; yy <= y1; ++yy)
-          for (int xx = x0; xx <= x1; ++xx) depth_min(zbuf + (size_t)yy * V.w + xx, word);
+          for (int xx = x0; xx <= x1; ++xx) rules::depth_min(zbuf + (size_t)yy * V.w + xx, word);
       // the larger footprints of the wave, one after the other: a lane per pixel along the rows
       unsigned long long todo = __ballot(some && !small);
       while (todo) {
@@ -103,12 +83,13 @@ __global__ void __launch_bounds__(kBlock) k_register_splat(const unsigned short 
         const int npx = sfw * sfh;  // (at most 81)
         for (int p = lane; p < npx; p += 64) {
           const int row = p / sfw, col = p - row * sfw;
-          depth_min(zbuf + (size_t)(sy0 + row) * V.w + (sx0 + col), sword);
+          rules::depth_min(zbuf + (size_t)(sy0 + row) * V.w + (sx0 + col), sword);
         }
       }
     }
   }
-  const unsigned long long b = wave_sum(behind), o = wave_sum(outside), dr = wave_sum(drawn);
+  const unsigned long long b = rules::wave_sum((unsigned long long)behind), o = rules::wave_sum((unsigned long long)outside),
+                           dr = rules::wave_sum((unsigned long long)drawn);
   if (lane == 0) {
     if (b) atomicAdd(&ctrl->behind, b);
     if (o) atomicAdd(&ctrl->outside, o);
@@ -123,7 +104,7 @@ __global__ void __launch_bounds__(kBlock) k_register_count(const uint4 *__restri
     const uint4 q = zbuf[p];
     covered += (q.x != kEmptyWord) + (q.y != kEmptyWord) + (q.z != kEmptyWord) + (q.w != kEmptyWord);
   }
-  const unsigned long long c = wave_sum(covered);
+  const unsigned long long c = rules::wave_sum((unsigned long long)covered);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(&ctrl->covered, c);
 }
 

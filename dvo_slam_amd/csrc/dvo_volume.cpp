@@ -17,6 +17,7 @@
 //                       ascending 3*L + a.  No per-voxel count array exists: a tile is counted twice instead.
 //   k_volume_gather     the public records of an index box, packed for the copy to the host
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 #include "dvo_volume_box.h"
 
 #include <algorithm>
@@ -35,7 +36,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kVoxelsPerLane = 8;                  // surface kernels: consecutive voxels a lane walks
 constexpr int kTile = kBlock * kVoxelsPerLane;     // ... and a block
 constexpr unsigned kNaN = 0x7FC00000u;
-constexpr float kFltMax = 3.402823466e38f;
 
 struct Geom {
   int nx, ny, nz;
@@ -54,7 +54,7 @@ struct FrameRecord {
   int slot;              // where its two counts go (near, free), -1: nowhere
 };
 
-__device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= kFltMax; }  // false for NaN
+using rules::finite_f;
 
 __global__ void __launch_bounds__(kBlock) k_volume_integrate(uint2 *__restrict__ pa, uint2 *__restrict__ pb, Geom G,
                                                              const FrameRecord *__restrict__ records, int n_records, int3 lo, int3 ext,
@@ -79,15 +79,11 @@ __global__ void __launch_bounds__(kBlock) k_volume_integrate(uint2 *__restrict__
     const FrameRecord &R = records[rec];  // uniform over the block
     bool is_near = false, is_free = false;
     if (live && ix >= R.lo[0] && ix <= R.hi[0] && iy >= R.lo[1] && iy <= R.hi[1] && iz >= R.lo[2] && iz <= R.hi[2]) {
-      const float *M = R.M;
-      const float cx = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
-      const float cy = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
-      const float cz = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
-      if (cz >= G.near_z) {
-        const float px = (cx * R.fx) / cz + R.ox, py = (cy * R.fy) / cz + R.oy;
-        const float pu = floorf(px + 0.5f), pv = floorf(py + 0.5f);
-        if (pu >= 0.0f && pu <= (float)(R.w - 1) && pv >= 0.0f && pv <= (float)(R.h - 1)) {
-          const size_t at = (size_t)(int)pv * (size_t)R.w + (size_t)(int)pu;  // 0 <= pu <= w-1, 0 <= pv <= h-1: tested in float
+      float cx, cy, cz;
+      rules::transform_rows(R.M, x, y, z, cx, cy, cz);
+      {
+        size_t at;
+        if (rules::project_nearest(cx, cy, cz, G.near_z, R.fx, R.fy, R.ox, R.oy, R.w, R.h, at) == 0) {
           const float Zs = R.z[at], Is = R.i[at];
           if (finite_f(Zs) && finite_f(Is) && Zs <= G.far_z) {
             const float d = Zs - cz;
@@ -98,8 +94,7 @@ __global__ void __launch_bounds__(kBlock) k_volume_integrate(uint2 *__restrict__
               const int q = (int)rintf((dc / G.trunc) * 2047.0f);
               int wgt = 1;
               if (G.weight == DVO_AMD_VOLUME_WEIGHT_SENSOR) {
-                const float dz = Zs - 0.4f;
-                const float s = 0.0012f + 0.0019f * (dz * dz);
+                const float s = rules::depth_sigma(Zs);
                 wgt = (int)fminf(fmaxf(rintf(256.0f * ((0.0012f * 0.0012f) / (s * s))), 1.0f), 256.0f);
               }
               const int g = (int)fminf(fmaxf(rintf(Is * 16.0f), 0.0f), 4080.0f);
@@ -154,11 +149,8 @@ struct Sample {
 
 __device__ __forceinline__ Sample sample_at(const Geom &G, const RayParams &V, float rx, float ry, float t) {
   Sample S;
-  const float x = rx * t, y = ry * t;
-  const float *P = V.P;
-  const float p0 = ((P[0] * x + P[1] * y) + P[2] * t) + P[3];
-  const float p1 = ((P[4] * x + P[5] * y) + P[6] * t) + P[7];
-  const float p2 = ((P[8] * x + P[9] * y) + P[10] * t) + P[11];
+  float p0, p1, p2;
+  rules::transform_rows(V.P, rx * t, ry * t, t, p0, p1, p2);
   const float g0 = (p0 - G.o[0]) / G.voxel, g1 = (p1 - G.o[1]) / G.voxel, g2 = (p2 - G.o[2]) / G.voxel;
   S.inside = g0 >= 0.0f && g0 < (float)(G.nx - 1) && g1 >= 0.0f && g1 < (float)(G.ny - 1) && g2 >= 0.0f && g2 < (float)(G.nz - 1);
   S.base = 0;
@@ -269,30 +261,6 @@ __global__ void __launch_bounds__(kBlock) k_volume_raycast(const uint2 *__restri
 
 // ---- the surface
 
-// exclusive scan of one value per thread over the block (256 threads); *total = the block's sum
-__device__ unsigned block_scan(unsigned v, unsigned *total) {
-  __shared__ unsigned s_wave[kWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned inc = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned up = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += up;
-  }
-  __syncthreads();  // (s_wave of an earlier call has been read)
-  if (lane == 63) s_wave[wave] = inc;
-  __syncthreads();
-  unsigned before = 0u, all = 0u;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const unsigned s = s_wave[w];
-    if (w < wave) before += s;
-    all += s;
-  }
-  *total = all;
-  return before + inc - v;
-}
-
 // the crossings of voxel L = (ix,iy,iz) along the three axes: bit a of the result; `emit` receives (a, point, coloured)
 template <typename Emit>
 __device__ __forceinline__ int crossings(const uint2 *__restrict__ pa, const uint2 *__restrict__ pb, const Geom &G, int min_weight, size_t L,
@@ -336,7 +304,7 @@ __global__ void __launch_bounds__(kBlock) k_volume_count(const uint2 *__restrict
     mine += (unsigned)__popc(crossings(pa, pb, G, min_weight, L, ix, iy, iz, [](int, float, float, size_t) {}));
   }
   unsigned total = 0u;
-  (void)block_scan(mine, &total);
+  (void)rules::block_exclusive_scan<kWaves>(mine, &total);
   if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
 }
 
@@ -348,7 +316,7 @@ __global__ void __launch_bounds__(kBlock) k_volume_scan(unsigned long long *__re
     const unsigned i = base + threadIdx.x;
     const unsigned v = i < n_tiles ? (unsigned)tile_sums[i] : 0u;  // (a tile holds at most 3 * kTile crossings)
     unsigned total = 0u;
-    const unsigned ex = block_scan(v, &total);  // (a chunk's sum is at most 256 * 3 * kTile < 2^32)
+    const unsigned ex = rules::block_exclusive_scan<kWaves>(v, &total);  // (a chunk's sum is at most 256 * 3 * kTile < 2^32)
     if (i < n_tiles) tile_sums[i] = carry + ex;
     carry += total;
   }
@@ -370,7 +338,7 @@ __global__ void __launch_bounds__(kBlock) k_volume_write(const uint2 *__restrict
     mine += (unsigned)__popc(crossings(pa, pb, G, min_weight, L, ix, iy, iz, [](int, float, float, size_t) {}));
   }
   unsigned total = 0u;
-  unsigned long long at = tile_offsets[blockIdx.x] + block_scan(mine, &total);
+  unsigned long long at = tile_offsets[blockIdx.x] + rules::block_exclusive_scan<kWaves>(mine, &total);
   unsigned unc = 0u;
   for (int j = 0; j < kVoxelsPerLane; ++j) {
     const size_t L = first + j;
@@ -456,80 +424,7 @@ namespace {
 
 // dvo_amd_debug_volume_timing: what the last call on the device launched and waited for, and (when asked for) two events around
 // its launches on the prep stream
-struct VolumeTiming {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int launches = 0, synchronisations = 0;
-  double last_ms = 0.0;
-};
-VolumeTiming g_timing[kMaxDevices];
-
-bool timing_begin(VolumeTiming &t) {
-  std::lock_guard<std::mutex> lk(t.mu);
-  return t.on && t.ev[0] && t.ev[1];
-}
-
-void timing_end(VolumeTiming &t, bool timed, int launches, int synchronisations) {
-  float ms = 0.f;
-  const bool have_ms = timed && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess;
-  std::lock_guard<std::mutex> lk(t.mu);
-  t.launches = launches, t.synchronisations = synchronisations;
-  if (have_ms) t.last_ms = ms;
-}
-
-// a size the pool can hand out again: the next power of two from 64 KiB
-size_t pool_size(size_t bytes) {
-  size_t s = (size_t)64 << 10;
-  while (s < bytes) s <<= 1;
-  return s;
-}
-
-// The call's own scratch, given back when the call ends.  Up to kPooledBytes it comes from the slab pool, rounded up so that the
-// pool can hand it out again; the pool keeps what it is given for the life of the process, so anything larger (the points of a
-// big extract, the planes of a very large view) is allocated for the call and freed behind it: nothing of that size stays parked
-// on the device.  The owner has drained the stream before a Scratch goes out of scope.
-constexpr size_t kPooledBytes = (size_t)32 << 20;
-struct Scratch {
-  int device = 0;
-  void *mem = nullptr;
-  size_t bytes = 0;
-  bool pooled = true;
-  ~Scratch() {
-    if (!mem) return;
-    if (pooled)
-      slab_free(device, bytes, mem);
-    else
-      (void)hipFree(mem);
-  }
-  int take(int dev, size_t n) {
-    device = dev, pooled = n <= kPooledBytes, bytes = pooled ? pool_size(n) : n;
-    if (pooled) {
-      const int rc = slab_alloc(dev, bytes, &mem);
-      if (rc) mem = nullptr;
-      return rc;
-    }
-    if (hipMalloc(&mem, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      mem = nullptr;
-      return DVO_AMD_ERR_OUT_OF_MEMORY;
-    }
-    return DVO_AMD_OK;
-  }
-};
-
-// rows 0..2 of the rigid inverse of a column-major transformation, cast to float (dvo_amd_map_render's step 2); NULL: identity
-void inverse_rows(const double *T, float *M) {
-  if (!T) {
-    for (int i = 0; i < 12; ++i) M[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    return;
-  }
-  const double t0 = T[12], t1 = T[13], t2 = T[14];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) M[r * 4 + c] = (float)T[r * 4 + c];
-    M[r * 4 + 3] = (float)(-((T[r * 4 + 0] * t0 + T[r * 4 + 1] * t1) + T[r * 4 + 2] * t2));
-  }
-}
+DeviceTiming g_timing[kMaxDevices];
 
 // one frame of an integration call on the host
 struct Item {
@@ -544,7 +439,7 @@ struct Item {
 int run_integration(dvo_amd_volume *vol, const std::vector<Item> &items, int n_slots, std::vector<unsigned> &near_free) {
   near_free.assign((size_t)2 * (size_t)std::max(n_slots, 0), 0u);
   if (items.empty()) {  // nothing moves: nothing is launched
-    timing_end(g_timing[vol->device], false, 0, 0);
+    g_timing[vol->device].count(0, 0);
     return DVO_AMD_OK;
   }
   const int device = vol->device;
@@ -580,15 +475,14 @@ int run_integration(dvo_amd_volume *vol, const std::vector<Item> &items, int n_s
   const size_t table_bytes = align_up(sizeof(FrameRecord) * table.size(), 256);
   const size_t count_bytes = align_up(sizeof(unsigned) * std::max<size_t>(near_free.size(), 1), 256);
   Scratch S;
-  rc = S.take(device, table_bytes + count_bytes);
+  rc = S.take(device, table_bytes + count_bytes, true);
   if (rc) return rc;
   char *base = (char *)S.mem;
   unsigned *d_counts = (unsigned *)(base + table_bytes);
-  VolumeTiming &timing = g_timing[device];
-  const bool timed = timing_begin(timing);
+  Bracket bracket(g_timing[device]);
   hipError_t e = hipMemcpyAsync(base, table.data(), sizeof(FrameRecord) * table.size(), hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, count_bytes, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   int launches = 0;
   if (e == hipSuccess && total > 0u) {
     const unsigned blocks = (total + kBlock - 1) / kBlock;
@@ -597,14 +491,14 @@ int run_integration(dvo_amd_volume *vol, const std::vector<Item> &items, int n_s
     e = hipGetLastError();
     launches = 1;
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   if (e == hipSuccess && !near_free.empty())
     e = hipMemcpyAsync(near_free.data(), d_counts, sizeof(unsigned) * near_free.size(), hipMemcpyDeviceToHost, st);
   // the call's one synchronisation (whatever failed, the stream is drained before the scratch goes back to the pool)
   const hipError_t es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail_hip("volume integration", e);
-  timing_end(timing, timed, launches, 1);
+  bracket.read(launches, 1);
   return DVO_AMD_OK;
 }
 
@@ -700,7 +594,7 @@ int raycast(const char *entry, dvo_amd_volume *vol, const double *pose, const dv
   if (want_i) need += plane;
   const size_t w_at = need;
   if (want_w) need += plane;
-  rc = S.take(device, need);
+  rc = S.take(device, need, true);
   if (rc) return rc;
   char *base = (char *)S.mem;
   unsigned *d_stats = (unsigned *)base;
@@ -708,17 +602,16 @@ int raycast(const char *entry, dvo_amd_volume *vol, const double *pose, const dv
   float *d_i = want_i ? (float *)(base + i_at) : nullptr;
   int *d_w = want_w ? (int *)(base + w_at) : nullptr;
   unsigned h_stats[4] = {0u, 0u, 0u, 0u};
-  VolumeTiming &timing = g_timing[device];
-  const bool timed = timing_begin(timing);
+  Bracket bracket(g_timing[device]);
   hipError_t e = hipMemsetAsync(d_stats, 0, 256, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   if (e == hipSuccess) {
     const unsigned tiles = (unsigned)(((view->width + 7) / 8) * (size_t)((view->height + 7) / 8));
     hipLaunchKernelGGL(k_volume_raycast, dim3((tiles + kWaves - 1) / kWaves), dim3(kBlock), 0, st, (const uint2 *)vol->a, (const uint2 *)vol->b,
                        vol->geom, V, d_z, d_i, d_w, d_stats);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   if (e == hipSuccess) e = hipMemcpyAsync(h_stats, d_stats, sizeof(h_stats), hipMemcpyDeviceToHost, st);
   if (!as_pyramid) {
     if (e == hipSuccess && depth) e = hipMemcpyAsync(depth, d_z, sizeof(float) * n_px, hipMemcpyDeviceToHost, st);
@@ -728,7 +621,7 @@ int raycast(const char *entry, dvo_amd_volume *vol, const double *pose, const dv
   const hipError_t es = hipStreamSynchronize(st);  // the raycast's one synchronisation
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail_hip("volume raycast", e);
-  timing_end(timing, timed, 1, 1);
+  bracket.read(1, 1);
   if (as_pyramid) {
     const PyramidSpec spec{view->width, view->height, view->fx, view->fy, view->ox, view->oy, levels, timestamp};
     const Level0Source src{d_i, d_z, view->width, nullptr, true};
@@ -997,7 +890,7 @@ int dvo_amd_volume_download(dvo_amd_volume *vol, const int *box, dvo_amd_volume_
   if (rc) return rc;
   const unsigned long long chunk = std::min<unsigned long long>(need, 1ull << 21);  // 32 MiB of records at a time
   Scratch S;
-  rc = S.take(vol->device, sizeof(uint4) * (size_t)chunk);
+  rc = S.take(vol->device, sizeof(uint4) * (size_t)chunk, true);
   if (rc) return rc;
   for (unsigned long long first = 0; first < need; first += chunk) {
     const unsigned count = (unsigned)std::min<unsigned long long>(chunk, need - first);
@@ -1044,16 +937,15 @@ int dvo_amd_volume_extract(dvo_amd_volume *vol, int min_weight, dvo_amd_point *o
   const unsigned n_tiles = (unsigned)((vol->n_vox + kTile - 1) / kTile);
   const size_t sums_bytes = align_up(sizeof(unsigned long long) * (size_t)n_tiles, 256);
   Scratch S;
-  rc = S.take(device, sums_bytes + 256);
+  rc = S.take(device, sums_bytes + 256, true);
   if (rc) return rc;
   unsigned long long *d_sums = (unsigned long long *)S.mem;
   unsigned long long *d_grand = (unsigned long long *)((char *)S.mem + sums_bytes);
   unsigned *d_unc = (unsigned *)(d_grand + 1);
-  VolumeTiming &timing = g_timing[device];
-  const bool timed = timing_begin(timing);
+  Bracket bracket(g_timing[device]);
   unsigned long long grand = 0ull;
   hipError_t e = hipMemsetAsync(d_grand, 0, 256, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(k_volume_count, dim3(n_tiles), dim3(kBlock), 0, st, (const uint2 *)vol->a, (const uint2 *)vol->b, vol->geom, min_weight,
                        vol->n_vox, d_sums);
@@ -1069,47 +961,32 @@ int dvo_amd_volume_extract(dvo_amd_volume *vol, int min_weight, dvo_amd_point *o
   if (e != hipSuccess) return fail_hip("volume extract (count)", e);
   *n_out = (long long)grand;
   if ((unsigned long long)capacity < grand) {
-    if (timed) (void)hipEventRecord(timing.ev[1], st), (void)hipStreamSynchronize(st);
-    timing_end(timing, timed, 2, 1);
+    if (bracket.timed) (void)bracket.end(st), (void)hipStreamSynchronize(st);
+    bracket.read(2, 1);
     return DVO_AMD_ERR_CAPACITY;
   }
   Scratch P;
   unsigned h_unc = 0u;
   if (grand > 0ull) {
-    rc = P.take(device, sizeof(dvo_amd_point) * (size_t)grand);
+    rc = P.take(device, sizeof(dvo_amd_point) * (size_t)grand, true);
     if (rc) return rc;
     hipLaunchKernelGGL(k_volume_write, dim3(n_tiles), dim3(kBlock), 0, st, (const uint2 *)vol->a, (const uint2 *)vol->b, vol->geom, min_weight,
                        vol->n_vox, (const unsigned long long *)d_sums, (dvo_amd_point *)P.mem, grand, d_unc);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   if (e == hipSuccess && grand > 0ull) e = hipMemcpyAsync(out, P.mem, sizeof(dvo_amd_point) * (size_t)grand, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipMemcpyAsync(&h_unc, d_unc, sizeof(h_unc), hipMemcpyDeviceToHost, st);
   es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail_hip("volume extract (write)", e);
-  timing_end(timing, timed, grand > 0ull ? 3 : 2, 2);
+  bracket.read(grand > 0ull ? 3 : 2, 2);
   if (counts) counts->points = (long long)grand, counts->uncoloured = (long long)h_unc;
   return DVO_AMD_OK;
 }
 
 int dvo_amd_debug_volume_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  VolumeTiming &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (launches) *launches = t.launches;
-  if (synchronisations) *synchronisations = t.synchronisations;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, launches, synchronisations, last_ms);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@
 // only, so nothing depends on the launch geometry or on the order atomics land in.  Everything runs on the device's prep stream
 // with scratch from the slab pool and one synchronisation per call; the pyramid forms then run pyramid_build per item.
 #include "dvo_internal.h"
+#include "dvo_device_rules.h"
 
 #include <algorithm>
 #include <cmath>
@@ -61,7 +62,6 @@ __global__ void __launch_bounds__(kBlock) k_warp_inverse(const InverseRecord *__
   for (int rec = blockIdx.y; rec < n_records; rec += gridDim.y) {
     const InverseRecord R = records[rec];        // uniform over the block
     if (blockIdx.x * kChunk >= R.nf) continue;   // (block-uniform: no barrier is skipped by part of a block)
-    const float *M = R.M;
     const float wm = (float)R.wm, hm = (float)R.hm;
     const int p0 = (blockIdx.x * kBlock + threadIdx.x) * kLanePixels;
     const bool live = p0 < R.nf;  // (nf is a multiple of 4: four pixels or none, all in one row)
@@ -85,11 +85,9 @@ __global__ void __launch_bounds__(kBlock) k_warp_inverse(const InverseRecord *__
       if (live) {
         const float z = z4[k];
         cls = 7;
-        if (fabsf(z) <= 3.402823466e38f) {  // finite (false for NaN)
-          const float x = R.txf[u0 + k] * z, y = ty * z;
-          const float qx = ((M[0] * x + M[1] * y) + M[2] * z) + M[3];
-          const float qy = ((M[4] * x + M[5] * y) + M[6] * z) + M[7];
-          const float qz = ((M[8] * x + M[9] * y) + M[10] * z) + M[11];
+        if (rules::finite_f(z)) {
+          float qx, qy, qz;
+          rules::transform_rows(R.M, R.txf[u0 + k] * z, ty * z, z, qx, qy, qz);
           if (!(qz >= near_z)) {
             cls = 1;
           } else {
@@ -111,7 +109,7 @@ __global__ void __launch_bounds__(kBlock) k_warp_inverse(const InverseRecord *__
                 float val = 0.0f, sum = 0.0f;
                 int taps = 0;
                 auto tap = [&](const float2 t, float w) {
-                  if (fabsf(t.y) <= 3.402823466e38f && t.y > thr) {
+                  if (rules::finite_f(t.y) && t.y > thr) {
                     val = val + w * t.x;
                     sum = sum + w;
                     ++taps;
@@ -180,22 +178,9 @@ __global__ void __launch_bounds__(kBlock) k_warp_clear(ulonglong2 *z, unsigned l
     z[p] = make_ulonglong2(kEmptyWord, kEmptyWord);
 }
 
-// one axis of what a moving pixel covers (dvo_amd.h: the splat rule), in float; lo..hi before clamping
-__device__ __forceinline__ void splat_axis(float c, float half, int splat, float &lo, float &hi) {
-  if (splat == DVO_AMD_WARP_SPLAT_FLOOR) {
-    lo = hi = floorf(c);
-  } else if (splat == DVO_AMD_WARP_SPLAT_NEAREST) {
-    lo = hi = floorf(c + 0.5f);
-  } else {
-    lo = ceilf(c - half), hi = floorf(c + half);
-    if (hi < lo) lo = hi = floorf(c + 0.5f);
-  }
-}
-
-// the stale value a plain load may return is never smaller than the word in memory: skipping the atomic on it is exact
-__device__ __forceinline__ void depth_min(unsigned long long *z, unsigned long long word) {
-  if (*z > word) atomicMin(z, word);
-}
+static_assert(DVO_AMD_WARP_SPLAT_NEAREST == rules::kFootprintNearest && DVO_AMD_WARP_SPLAT_FLOOR == rules::kFootprintFloor &&
+                  DVO_AMD_WARP_SPLAT_FOOTPRINT == rules::kFootprintFill,
+              "the splat modes of include/dvo_amd.h are the footprint modes of dvo_device_rules.h");
 
 __global__ void __launch_bounds__(kBlock) k_warp_splat(const ForwardRecord *__restrict__ records, int n_records, int splat) {
   __shared__ unsigned s_cnt[kWaves][kFwdCounts];
@@ -203,7 +188,6 @@ __global__ void __launch_bounds__(kBlock) k_warp_splat(const ForwardRecord *__re
   for (int rec = blockIdx.y; rec < n_records; rec += gridDim.y) {
     const ForwardRecord R = records[rec];        // uniform over the block
     if (blockIdx.x * kBlock >= R.n) continue;    // (block-uniform)
-    const float *T = R.T;
     const int r = blockIdx.x * kBlock + threadIdx.x;
     int cls = -1;  // -1: no pixel; 6 no depth; 1 behind, 2 outside, 3 too large, 4 drawn
     int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
@@ -211,20 +195,19 @@ __global__ void __launch_bounds__(kBlock) k_warp_splat(const ForwardRecord *__re
     if (r < R.n) {
       const float z = R.z[r];
       cls = 6;
-      if (fabsf(z) <= 3.402823466e38f) {  // finite (false for NaN)
+      if (rules::finite_f(z)) {
         const int v = r / R.w, u = r - v * R.w;
-        const float x = R.tx[u] * z, y = R.ty[v] * z;
-        const float cx = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
-        const float cy = ((T[4] * x + T[5] * y) + T[6] * z) + T[7];
-        const float cz = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
+        float cx, cy, cz;
+        rules::transform_rows(R.T, R.tx[u] * z, R.ty[v] * z, z, cx, cy, cz);
         if (!(cz >= R.near_z)) {
           cls = 1;
         } else {
           const float pu = (cx * R.fx) / cz + R.ox, pv = (cy * R.fy) / cz + R.oy;
           const float hx = 0.5f * (((z / R.fxm) * R.fx) / cz), hy = 0.5f * (((z / R.fym) * R.fy) / cz);
           float a0, a1, b0, b1;
-          splat_axis(pu, hx, splat, a0, a1);
-          splat_axis(pv, hy, splat, b0, b1);
+          // (the span of either axis first: a footprint that is too large is counted before one that is outside)
+          rules::footprint_span(pu, hx, splat, a0, a1);
+          rules::footprint_span(pv, hy, splat, b0, b1);
           const float wlast = (float)(R.vw - 1), hlast = (float)(R.vh - 1);
           if (a1 - a0 > (float)(DVO_AMD_WARP_MAX_FOOTPRINT - 1) || b1 - b0 > (float)(DVO_AMD_WARP_MAX_FOOTPRINT - 1)) {
             cls = 3;
@@ -245,7 +228,7 @@ __global__ void __launch_bounds__(kBlock) k_warp_splat(const ForwardRecord *__re
     const bool small = some && fw * fh <= kSmallFootprint;
     if (small)
       for (int yy = y0; yy <= y1; ++yy)
-        for (int xx = x0; xx <= x1; ++xx) depth_min(R.zbuf + (size_t)yy * R.vw + xx, word);
+        for (int xx = x0; xx <= x1; ++xx) rules::depth_min(R.zbuf + (size_t)yy * R.vw + xx, word);
     // the larger footprints of the wave, one after the other: a lane per pixel along the rows
     unsigned long long todo = __ballot(some && !small);
     while (todo) {
@@ -257,7 +240,7 @@ __global__ void __launch_bounds__(kBlock) k_warp_splat(const ForwardRecord *__re
       const int npx = sfw * sfh;  // (at most 256)
       for (int p = lane; p < npx; p += 64) {
         const int row = p / sfw, col = p - row * sfw;
-        depth_min(R.zbuf + (size_t)(sy0 + row) * R.vw + (sx0 + col), sword);
+        rules::depth_min(R.zbuf + (size_t)(sy0 + row) * R.vw + (sx0 + col), sword);
       }
     }
     unsigned cnt[kFwdCounts];
@@ -328,37 +311,7 @@ namespace {
 
 // dvo_amd_debug_warp_timing: what the last call on the device launched and waited for (the warp's own kernels and its own
 // synchronisation, not pyramid_build's), and (when asked for) two events around its launches on the prep stream
-struct WarpTiming {
-  std::mutex mu;
-  bool on = false;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int launches = 0, synchronisations = 0;
-  double last_ms = 0.0;
-};
-WarpTiming g_timing[kMaxDevices];
-
-bool timing_begin(WarpTiming &t) {
-  std::lock_guard<std::mutex> lk(t.mu);
-  return t.on && t.ev[0] && t.ev[1];
-}
-
-void timing_end(WarpTiming &t, bool timed, int launches, int synchronisations) {
-  float ms = 0.f;
-  const bool have_ms = timed && hipEventElapsedTime(&ms, t.ev[0], t.ev[1]) == hipSuccess;
-  std::lock_guard<std::mutex> lk(t.mu);
-  t.launches = launches, t.synchronisations = synchronisations;
-  if (have_ms) t.last_ms = ms;
-}
-
-// the call's own scratch from the slab pool, given back when the call ends
-struct Scratch {
-  int device = 0;
-  void *mem = nullptr;
-  size_t bytes = 0;
-  ~Scratch() {
-    if (mem) slab_free(device, bytes, mem);
-  }
-};
+DeviceTiming g_timing[kMaxDevices];
 
 int check_options(const char *entry, const dvo_amd_warp_options *opt) {
   if (!std::isfinite(opt->near_z) || !(opt->near_z > 0.0f)) return invalid(entry, "near_z must be finite and positive");
@@ -380,20 +333,6 @@ int check_view(const char *entry, const std::string &item, const dvo_amd_view *v
   if (!std::isfinite(v->ox) || !std::isfinite(v->oy)) return invalid(entry, item + ": the view's ox and oy must be finite");
   if (!std::isfinite(v->near_z) || !(v->near_z > 0.0f)) return invalid(entry, item + ": the view's near_z must be finite and positive");
   return DVO_AMD_OK;
-}
-
-// rows 0..2 of the rigid inverse of a column-major transformation, cast to float (depth fusion's step 1)
-void inverse_rows(const double *T, float *M) {
-  const double t0 = T[12], t1 = T[13], t2 = T[14];
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) M[r * 4 + c] = (float)T[r * 4 + c];
-    M[r * 4 + 3] = (float)(-((T[r * 4 + 0] * t0 + T[r * 4 + 1] * t1) + T[r * 4 + 2] * t2));
-  }
-}
-
-// a launch holds fewer than 2^31 threads and at most 65535 rows of blocks: a block takes further records in steps of gridDim.y
-unsigned grid_rows(int n_records, unsigned gx) {
-  return (unsigned)std::max<long long>(1, std::min<long long>(std::min<long long>((long long)n_records, 65535), (1ll << 31) / ((long long)gx * kBlock)));
 }
 
 void release_all(dvo_amd_pyramid **out, int n) {
@@ -438,23 +377,20 @@ int inverse_many(const char *entry, int n, const dvo_amd_pyramid *const *fixed, 
   const size_t count_bytes = align_up(sizeof(unsigned) * kInvCounts * (size_t)n, 256);
   std::vector<size_t> i_at((size_t)n, 0), z_at((size_t)n, 0);
   std::vector<char> want_i((size_t)n, 0), want_z((size_t)n, 0);
-  Scratch S;
-  S.device = device, S.bytes = table_bytes + count_bytes;
+  size_t scratch_bytes = table_bytes + count_bytes;
   int max_n = 1;
   for (int k = 0; k < n; ++k) {
     const size_t plane = align_up(sizeof(float) * (size_t)fixed[k]->lv[lv].n, 256);
     want_i[(size_t)k] = as_pyramid || (intensity_out && intensity_out[k]);
     want_z[(size_t)k] = as_pyramid || (depth_out && depth_out[k]);
-    if (want_i[(size_t)k]) i_at[(size_t)k] = S.bytes, S.bytes += plane;
-    if (want_z[(size_t)k]) z_at[(size_t)k] = S.bytes, S.bytes += plane;
+    if (want_i[(size_t)k]) i_at[(size_t)k] = scratch_bytes, scratch_bytes += plane;
+    if (want_z[(size_t)k]) z_at[(size_t)k] = scratch_bytes, scratch_bytes += plane;
     max_n = std::max(max_n, fixed[k]->lv[lv].n);
   }
-  rc = slab_alloc(device, S.bytes, &S.mem);
-  if (rc) {
-    S.mem = nullptr;
-    return rc;
-  }
-  char *base = (char *)S.mem;
+  Scratch S;  // (every return below stands behind a synchronisation of the stream)
+  rc = S.take(device, scratch_bytes);
+  if (rc) return rc;
+  char *base = S.base();
   unsigned *d_counts = (unsigned *)(base + table_bytes);
   std::vector<InverseRecord> table((size_t)n);
   for (int k = 0; k < n; ++k) {
@@ -469,18 +405,17 @@ int inverse_many(const char *entry, int n, const dvo_amd_pyramid *const *fixed, 
     inverse_rows(T + 16 * (size_t)k, R.M);
   }
   std::vector<unsigned> h_counts((size_t)kInvCounts * (size_t)n);
-  WarpTiming &timing = g_timing[device];
-  const bool timed = timing_begin(timing);
+  Bracket bracket(g_timing[device]);
   hipError_t e = hipMemcpyAsync(base, table.data(), sizeof(InverseRecord) * (size_t)n, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, count_bytes, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   if (e == hipSuccess) {
     const unsigned gx = (unsigned)((max_n + kChunk - 1) / kChunk);
-    hipLaunchKernelGGL(k_warp_inverse, dim3(gx, grid_rows(n, gx)), dim3(kBlock), 0, st, (const InverseRecord *)base, n, opt->near_z,
+    hipLaunchKernelGGL(k_warp_inverse, dim3(gx, grid_rows(n, gx, kBlock)), dim3(kBlock), 0, st, (const InverseRecord *)base, n, opt->near_z,
                        opt->occlusion_margin, opt->depth == DVO_AMD_WARP_DEPTH_FIXED ? 1 : 0, as_pyramid ? 1 : 0, opt->fill_intensity);
     e = hipGetLastError();
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   if (e == hipSuccess && counts) e = hipMemcpyAsync(h_counts.data(), d_counts, sizeof(unsigned) * h_counts.size(), hipMemcpyDeviceToHost, st);
   if (!as_pyramid)
     for (int k = 0; k < n && e == hipSuccess; ++k) {
@@ -492,7 +427,7 @@ int inverse_many(const char *entry, int n, const dvo_amd_pyramid *const *fixed, 
   const hipError_t es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail_hip("inverse warp", e);
-  timing_end(timing, timed, 1, 1);
+  bracket.read(1, 1);
   if (as_pyramid)
     for (int k = 0; k < n; ++k) {
       const dvo_amd_pyramid *f = fixed[k];
@@ -560,31 +495,28 @@ int forward_many(const char *entry, int n, const dvo_amd_pyramid *const *moving,
   const size_t count_bytes = align_up(sizeof(unsigned) * kFwdCounts * (size_t)n, 256);
   std::vector<size_t> buf_at((size_t)n), z_at((size_t)n, 0), i_at((size_t)n, 0), x_at((size_t)n, 0);
   std::vector<char> want_z((size_t)n, 0), want_i((size_t)n, 0), want_x((size_t)n, 0);
-  Scratch S;
-  S.device = device, S.bytes = table_bytes + count_bytes;
-  const size_t zbuf_first = S.bytes;
+  size_t scratch_bytes = table_bytes + count_bytes;
+  const size_t zbuf_first = scratch_bytes;
   int max_n = 1, max_vn = 1;
   for (int k = 0; k < n; ++k) {
     const size_t vn = (size_t)V[(size_t)k].width * (size_t)V[(size_t)k].height;
-    buf_at[(size_t)k] = S.bytes, S.bytes += align_up(sizeof(unsigned long long) * vn, 256);
+    buf_at[(size_t)k] = scratch_bytes, scratch_bytes += align_up(sizeof(unsigned long long) * vn, 256);
     max_n = std::max(max_n, moving[k]->lv[lv].n), max_vn = std::max(max_vn, (int)vn);
   }
-  const size_t zbuf_bytes = S.bytes - zbuf_first;  // (a multiple of 256: cleared 16 bytes at a time)
+  const size_t zbuf_bytes = scratch_bytes - zbuf_first;  // (a multiple of 256: cleared 16 bytes at a time)
   for (int k = 0; k < n; ++k) {
     const size_t plane = align_up(sizeof(float) * (size_t)V[(size_t)k].width * (size_t)V[(size_t)k].height, 256);
     want_z[(size_t)k] = as_pyramid || (depth_out && depth_out[k]);
     want_i[(size_t)k] = as_pyramid || (intensity_out && intensity_out[k]);
     want_x[(size_t)k] = !as_pyramid && index_out && index_out[k];
-    if (want_z[(size_t)k]) z_at[(size_t)k] = S.bytes, S.bytes += plane;
-    if (want_i[(size_t)k]) i_at[(size_t)k] = S.bytes, S.bytes += plane;
-    if (want_x[(size_t)k]) x_at[(size_t)k] = S.bytes, S.bytes += plane;
+    if (want_z[(size_t)k]) z_at[(size_t)k] = scratch_bytes, scratch_bytes += plane;
+    if (want_i[(size_t)k]) i_at[(size_t)k] = scratch_bytes, scratch_bytes += plane;
+    if (want_x[(size_t)k]) x_at[(size_t)k] = scratch_bytes, scratch_bytes += plane;
   }
-  rc = slab_alloc(device, S.bytes, &S.mem);
-  if (rc) {
-    S.mem = nullptr;
-    return rc;
-  }
-  char *base = (char *)S.mem;
+  Scratch S;  // (every return below stands behind a synchronisation of the stream)
+  rc = S.take(device, scratch_bytes);
+  if (rc) return rc;
+  char *base = S.base();
   unsigned *d_counts = (unsigned *)(base + table_bytes);
   std::vector<ForwardRecord> table((size_t)n);
   for (int k = 0; k < n; ++k) {
@@ -602,15 +534,13 @@ int forward_many(const char *entry, int n, const dvo_amd_pyramid *const *moving,
     R.vw = v.width, R.vh = v.height, R.vn = v.width * v.height;
     R.fx = v.fx, R.fy = v.fy, R.ox = v.ox, R.oy = v.oy, R.near_z = v.near_z;
     R.fxm = L.fx, R.fym = L.fy;
-    for (int row = 0; row < 3; ++row)
-      for (int col = 0; col < 4; ++col) R.T[row * 4 + col] = (float)Tk[col * 4 + row];  // column-major in, rows 0..2 out
+    rows_from_column_major(Tk, R.T);
   }
   std::vector<unsigned> h_counts((size_t)kFwdCounts * (size_t)n);
-  WarpTiming &timing = g_timing[device];
-  const bool timed = timing_begin(timing);
+  Bracket bracket(g_timing[device]);
   hipError_t e = hipMemcpyAsync(base, table.data(), sizeof(ForwardRecord) * (size_t)n, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, count_bytes, st);
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[0], st);
+  if (e == hipSuccess) e = bracket.begin(st);
   if (e == hipSuccess) {
     const unsigned long long n2 = zbuf_bytes / sizeof(ulonglong2);
     const unsigned gc = (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((n2 + kBlock - 1) / kBlock, 4096));
@@ -619,16 +549,16 @@ int forward_many(const char *entry, int n, const dvo_amd_pyramid *const *moving,
   }
   if (e == hipSuccess) {
     const unsigned gx = (unsigned)((max_n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_warp_splat, dim3(gx, grid_rows(n, gx)), dim3(kBlock), 0, st, (const ForwardRecord *)base, n, opt->splat);
+    hipLaunchKernelGGL(k_warp_splat, dim3(gx, grid_rows(n, gx, kBlock)), dim3(kBlock), 0, st, (const ForwardRecord *)base, n, opt->splat);
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
     const unsigned gx = (unsigned)((max_vn + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_warp_resolve, dim3(gx, grid_rows(n, gx)), dim3(kBlock), 0, st, (const ForwardRecord *)base, n,
+    hipLaunchKernelGGL(k_warp_resolve, dim3(gx, grid_rows(n, gx, kBlock)), dim3(kBlock), 0, st, (const ForwardRecord *)base, n,
                        as_pyramid ? opt->fill_intensity : __builtin_nanf(""));
     e = hipGetLastError();
   }
-  if (e == hipSuccess && timed) e = hipEventRecord(timing.ev[1], st);
+  if (e == hipSuccess) e = bracket.end(st);
   if (e == hipSuccess && counts) e = hipMemcpyAsync(h_counts.data(), d_counts, sizeof(unsigned) * h_counts.size(), hipMemcpyDeviceToHost, st);
   if (!as_pyramid)
     for (int k = 0; k < n && e == hipSuccess; ++k) {
@@ -641,7 +571,7 @@ int forward_many(const char *entry, int n, const dvo_amd_pyramid *const *moving,
   const hipError_t es = hipStreamSynchronize(st);
   if (e == hipSuccess) e = es;
   if (e != hipSuccess) return fail_hip("forward warp", e);
-  timing_end(timing, timed, 3, 1);
+  bracket.read(3, 1);
   if (as_pyramid)
     for (int k = 0; k < n; ++k) {
       const dvo_amd_view &v = V[(size_t)k];
@@ -736,22 +666,7 @@ int dvo_amd_pyramid_warp_forward(const dvo_amd_pyramid *moving, const double *T,
  * with enable != 0 the launches of every later call are bracketed by two events on the prep stream and *last_ms (may be NULL)
  * receives the device time of the most recent bracketed call */
 int dvo_amd_debug_warp_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms) {
-  if (device < 0 || device >= kMaxDevices) return DVO_AMD_ERR_INVALID_ARGUMENT;
-  WarpTiming &t = g_timing[device];
-  if (enable) {
-    const int rc = have_device();
-    if (rc) return rc;
-  }
-  std::lock_guard<std::mutex> lk(t.mu);
-  if (enable && !t.ev[0]) {
-    HIP_TRY(hipSetDevice(device));
-    for (hipEvent_t &e : t.ev) HIP_TRY(hipEventCreate(&e));
-  }
-  t.on = enable != 0;
-  if (launches) *launches = t.launches;
-  if (synchronisations) *synchronisations = t.synchronisations;
-  if (last_ms) *last_ms = t.last_ms;
-  return DVO_AMD_OK;
+  return timing_entry(g_timing, device, enable, launches, synchronisations, last_ms);
 }
 
 }  // extern "C"
