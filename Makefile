@@ -75,6 +75,10 @@ examples: $(LIB)
 	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 	$(CXX) -std=c++11 -Wall -pthread -Iinclude/dvo_amd_compat -Iinclude examples/volume_adaptor_example.cpp \
 	    -o examples/_build/volume_adaptor_example -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CC) -std=c99 -Wall -Iinclude examples/volume_mesh_example.c -o examples/_build/volume_mesh_example \
+	    -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
+	$(CXX) -std=c++11 -Wall -pthread -Iinclude/dvo_amd_compat -Iinclude examples/volume_mesh_adaptor_example.cpp \
+	    -o examples/_build/volume_mesh_adaptor_example -Ldvo_slam_amd -ldvo_amd -Wl,-rpath,$(CURDIR)/dvo_slam_amd -Wl,--allow-shlib-undefined
 
 clean:
 	rm -f $(LIB)

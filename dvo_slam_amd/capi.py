@@ -77,6 +77,7 @@ EXPORTS = [
     "dvo_amd_volume_clear", "dvo_amd_volume_options_get", "dvo_amd_volume_integrate", "dvo_amd_volume_insert",
     "dvo_amd_volume_set_poses", "dvo_amd_volume_remove", "dvo_amd_volume_stats", "dvo_amd_volume_download", "dvo_amd_volume_raycast",
     "dvo_amd_volume_raycast_pyramid", "dvo_amd_volume_extract", "dvo_amd_debug_volume_timing",
+    "dvo_amd_volume_mesh", "dvo_amd_volume_upload", "dvo_amd_write_ply",
 ]
 
 
@@ -205,6 +206,10 @@ class CVolumeRaycastStats(C.Structure):
 
 class CVolumeExtractCounts(C.Structure):
     _fields_ = [(n, C.c_longlong) for n in ("points", "uncoloured")]
+
+
+class CVolumeMeshCounts(C.Structure):
+    _fields_ = [(n, C.c_longlong) for n in ("vertices", "triangles", "open_edges", "uncoloured", "flat")]
 
 
 class ResidualMaskOptions(C.Structure):
@@ -595,6 +600,9 @@ def lib():
     L.dvo_amd_volume_raycast_pyramid.argtypes = [vp, dp, cv, ro, C.c_int, C.c_double, C.POINTER(vp), C.POINTER(CVolumeRaycastStats)]
     L.dvo_amd_volume_extract.argtypes = [vp, C.c_int, vp, C.c_longlong, ll, C.POINTER(CVolumeExtractCounts)]
     L.dvo_amd_debug_volume_timing.argtypes = [C.c_int, C.c_int, ip, ip, dp]
+    L.dvo_amd_volume_mesh.argtypes = [vp, C.c_int, vp, fp, C.c_longlong, ip, C.c_longlong, C.POINTER(CVolumeMeshCounts)]
+    L.dvo_amd_volume_upload.argtypes = [vp, ip, vp, C.c_longlong]
+    L.dvo_amd_write_ply.argtypes = [C.c_char_p, vp, fp, C.c_longlong, ip, C.c_longlong]
     L.dvo_amd_default_fuse_options.argtypes = [C.POINTER(FuseOptions)]
     L.dvo_amd_default_fuse_options.restype = None
     L.dvo_amd_pyramid_fuse_depth.argtypes = [vp, C.c_int, C.POINTER(vp), dp, C.POINTER(FuseOptions), C.POINTER(vp),
@@ -2810,6 +2818,45 @@ class SurfaceVolume:
         _check(rc, "dvo_amd_volume_extract")
         xyz, rgb = _split_points(out[:n.value])
         return xyz, rgb, {"points": cnt.points, "uncoloured": cnt.uncoloured}
+
+    def mesh(self, min_weight: int = 1, normals: bool = True, capacity=None):
+        """the surface as an indexed triangle mesh by surface nets (dvo_amd_volume_mesh): (xyz float32 [V, 3], rgb uint32 [V],
+        normals float32 [V, 3] or None, triangles int32 [T, 3], counts dict); one vertex per active cell in ascending cell
+        index, two triangles per crossing edge whose four cells are known.  capacity=None: asked of the library first; a given
+        (vertices, triangles) that is too small raises DvoAmdError (status 7) with the sizes needed in `last_mesh_size`"""
+        cnt = CVolumeMeshCounts()
+        cap = (0, 0) if capacity is None else (int(capacity[0]), int(capacity[1]))
+
+        def call():
+            pts = np.empty((max(1, cap[0]), 4), np.float32)
+            nrm = np.empty((max(1, cap[0]), 3), np.float32) if normals else None
+            tri = np.empty((max(1, cap[1]), 3), np.int32)
+            rc = lib().dvo_amd_volume_mesh(self._h, min_weight, pts.ctypes.data, None if nrm is None else _fp(nrm), cap[0],
+                                           tri.ctypes.data_as(C.POINTER(C.c_int)), cap[1], C.byref(cnt))
+            return rc, pts, nrm, tri
+
+        rc, pts, nrm, tri = call()
+        if rc == 7 and capacity is None:  # DVO_AMD_ERR_CAPACITY: the counts hold the sizes needed
+            cap = (int(cnt.vertices), int(cnt.triangles))
+            rc, pts, nrm, tri = call()
+        self.last_mesh_size = (int(cnt.vertices), int(cnt.triangles))
+        _check(rc, "dvo_amd_volume_mesh")
+        xyz, rgb = _split_points(pts[:cnt.vertices])
+        return (xyz, rgb, None if nrm is None else nrm[:cnt.vertices].copy(), tri[:cnt.triangles].copy(),
+                {n: getattr(cnt, n) for n, _ in CVolumeMeshCounts._fields_})
+
+    def upload(self, records, box=None):
+        """the inverse of download(): overwrites the records of the volume, or of the inclusive index box (x0, y0, z0, x1, y1, z1),
+        with a VOLUME_VOXEL_DTYPE array (or an integer array [..., 4]) in the order of L (dvo_amd_volume_upload).  Refused while
+        the tracked form holds keyframes."""
+        rec = np.asarray(records)
+        if rec.dtype != VOLUME_VOXEL_DTYPE:
+            if rec.ndim < 1 or rec.shape[-1] != 4 or rec.dtype.kind not in "iu" or rec.dtype.itemsize != 4:
+                raise ValueError("records: a VOLUME_VOXEL_DTYPE array, or 32-bit integers [..., 4]")
+            rec = np.ascontiguousarray(rec).view(VOLUME_VOXEL_DTYPE).reshape(rec.shape[:-1])
+        rec = np.ascontiguousarray(rec)
+        bx = None if box is None else (C.c_int * 6)(*[int(b) for b in box])
+        _check(lib().dvo_amd_volume_upload(self._h, bx, rec.ctypes.data, rec.size), "dvo_amd_volume_upload")
 
 
 def pack_keyframes(keyframes):

@@ -15,7 +15,8 @@
 //   k_volume_count / k_volume_scan / k_volume_write   the surface: crossings per tile of voxels, an exclusive scan of the tile
 //                       totals by one block, then every tile recounts, scans inside the block and writes its points in
 //                       ascending 3*L + a.  No per-voxel count array exists: a tile is counted twice instead.
-//   k_volume_gather     the public records of an index box, packed for the copy to the host
+//   k_volume_gather / k_volume_scatter   the public records of an index box, packed for the copy to the host and back
+//   k_mesh_*            the surface as an indexed triangle mesh (surface nets): see "the mesh" below
 #include "dvo_internal.h"
 #include "dvo_device_rules.h"
 #include "dvo_volume_box.h"
@@ -23,6 +24,7 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -309,8 +311,8 @@ __global__ void __launch_bounds__(kBlock) k_volume_count(const uint2 *__restrict
 }
 
 // one block: the exclusive scan of the tile totals in place; *grand = the sum of all
-__global__ void __launch_bounds__(kBlock) k_volume_scan(unsigned long long *__restrict__ tile_sums, unsigned n_tiles,
-                                                        unsigned long long *__restrict__ grand) {
+__device__ __forceinline__ void scan_tile_sums(unsigned long long *__restrict__ tile_sums, unsigned n_tiles,
+                                               unsigned long long *__restrict__ grand) {
   unsigned long long carry = 0ull;
   for (unsigned base = 0; base < n_tiles; base += kBlock) {
     const unsigned i = base + threadIdx.x;
@@ -321,6 +323,11 @@ __global__ void __launch_bounds__(kBlock) k_volume_scan(unsigned long long *__re
     carry += total;
   }
   if (threadIdx.x == 0) *grand = carry;
+}
+
+__global__ void __launch_bounds__(kBlock) k_volume_scan(unsigned long long *__restrict__ tile_sums, unsigned n_tiles,
+                                                        unsigned long long *__restrict__ grand) {
+  scan_tile_sums(tile_sums, n_tiles, grand);
 }
 
 __global__ void __launch_bounds__(kBlock) k_volume_write(const uint2 *__restrict__ pa, const uint2 *__restrict__ pb, Geom G, int min_weight,
@@ -396,6 +403,301 @@ __global__ void __launch_bounds__(kBlock) k_volume_gather(const uint2 *__restric
   const size_t L = ((size_t)iz * (size_t)G.ny + (size_t)iy) * (size_t)G.nx + (size_t)ix;  // (inside the volume: the host checks the box)
   const uint2 a = pa[L], b = pb[L];
   out[i] = make_uint4(a.x, a.y, b.x, b.y);
+}
+
+// ... and the way back: the packed records of the same stretch of a box into the two planes
+__global__ void __launch_bounds__(kBlock) k_volume_scatter(uint2 *__restrict__ pa, uint2 *__restrict__ pb, Geom G, int3 lo, int3 ext,
+                                                           unsigned long long first, unsigned count, const uint4 *__restrict__ in) {
+  const unsigned i = blockIdx.x * (unsigned)kBlock + threadIdx.x;
+  if (i >= count) return;
+  const unsigned long long idx = first + i;
+  const unsigned long long row = idx / (unsigned)ext.x;
+  const int ix = lo.x + (int)(idx - row * (unsigned)ext.x);
+  const unsigned long long slab = row / (unsigned)ext.y;
+  const int iy = lo.y + (int)(row - slab * (unsigned)ext.y), iz = lo.z + (int)slab;
+  const size_t L = ((size_t)iz * (size_t)G.ny + (size_t)iy) * (size_t)G.nx + (size_t)ix;  // (inside the volume: the host checks the box)
+  const uint4 r = in[i];
+  pa[L] = make_uint2(r.x, r.y), pb[L] = make_uint2(r.z, r.w);
+}
+
+// ---- the mesh (include/dvo_amd.h, "The mesh"): naive surface nets, one vertex per active cell, one quad per crossing edge
+//
+// Cells are indexed Lc = (cz*(ny-1) + cy)*(nx-1) + cx.  What a cell's rank among the active ones is, is never stored per cell:
+//   k_mesh_cells     a lane walks kCellsPerLane consecutive cells and keeps the four taps of the face it shares with the next one
+//                    (they are consecutive along x until a row ends: 4 loads per cell instead of 8); eight lanes' bytes make one
+//                    64-bit activity word, the block scans its 32 words and leaves word, offset of the word inside the tile, tile total
+//   k_mesh_edges     the faces per tile of voxels: crossings() whose four cells exist and are active (a cell around a crossing
+//                    edge is active iff it is known); the open ones are counted, one integer atomic per block
+//   k_mesh_scan      one block: both lists of tile totals
+//   k_mesh_vertices  a lane takes its byte of the activity word and computes the vertices of its active cells at their rank
+//   k_mesh_faces     every tile of voxels recounts, scans inside the block and writes two triangles per face from the four ranks
+// rank(Lc) = tile_offset[Lc / kCellTile] + word_offset[Lc / 64] + popcll(word[Lc / 64] & below(Lc % 64)).
+constexpr int kCellsPerLane = 8;
+constexpr int kCellTile = kBlock * kCellsPerLane;
+constexpr int kWordsPerTile = kCellTile / 64;
+static_assert(kCellsPerLane == 8 && kWordsPerTile * 64 == kCellTile, "eight lanes' bytes make one 64-bit word");
+
+struct Cells {
+  int nx, ny, nz;  // cells along each axis: the volume's dimensions minus one
+  size_t n;
+  const unsigned long long *word;     // [tiles * kWordsPerTile] activity bits
+  const unsigned *word_offset;        // the active cells of the tile before the word
+  const unsigned long long *tile_offset;
+};
+
+__device__ __forceinline__ bool cell_active(const Cells &C, int cx, int cy, int cz) {
+  const size_t Lc = ((size_t)cz * (size_t)C.ny + (size_t)cy) * (size_t)C.nx + (size_t)cx;
+  return (C.word[Lc >> 6] >> (Lc & 63)) & 1ull;
+}
+
+__device__ __forceinline__ int cell_rank(const Cells &C, size_t Lc) {
+  const size_t w = Lc >> 6;
+  const unsigned long long below = C.word[w] & ((1ull << (Lc & 63)) - 1ull);
+  return (int)(C.tile_offset[Lc / kCellTile] + C.word_offset[w] + (unsigned)__popcll(below));  // (< 2^30 cells)
+}
+
+// the four cells q0..q3 around the crossing edge of voxel (ix,iy,iz) along a, counter-clockwise seen from +a; false: one of them
+// does not exist or is not active
+__device__ __forceinline__ bool quad_cells(const Cells &C, int a, int ix, int iy, int iz, size_t q[4]) {
+  // (b,c) = (y,z), (z,x), (x,y) for a = x, y, z; selects, not indexed arrays: a is not a constant everywhere this is inlined
+  const int ib = a == 0 ? iy : a == 1 ? iz : ix, ic = a == 0 ? iz : a == 1 ? ix : iy;
+  const int nb = a == 0 ? C.ny : a == 1 ? C.nz : C.nx, nc = a == 0 ? C.nz : a == 1 ? C.nx : C.ny;
+  if (ib < 1 || ib > nb - 1 || ic < 1 || ic > nc - 1) return false;  // (cells i-1 and i: 1 <= i <= cells - 1)
+  bool all = true;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int cb = ib - (k == 0 || k == 3 ? 1 : 0), cc = ic - (k < 2 ? 1 : 0);
+    const int cx = a == 0 ? ix : a == 1 ? cc : cb, cy = a == 0 ? cb : a == 1 ? iy : cc, cz = a == 0 ? cc : a == 1 ? cb : iz;
+    q[k] = ((size_t)cz * (size_t)C.ny + (size_t)cy) * (size_t)C.nx + (size_t)cx;
+    all = all && cell_active(C, cx, cy, cz);
+  }
+  return all;
+}
+
+__global__ void __launch_bounds__(kBlock) k_mesh_cells(const uint2 *__restrict__ pa, Geom G, int min_weight, size_t n_cells,
+                                                       unsigned long long *__restrict__ word, unsigned *__restrict__ word_offset,
+                                                       unsigned long long *__restrict__ tile_sums) {
+  const int ncx = G.nx - 1, ncy = G.ny - 1;
+  const size_t first = (size_t)blockIdx.x * kCellTile + (size_t)threadIdx.x * kCellsPerLane;
+  const size_t sy = (size_t)G.nx, sz = (size_t)G.nx * (size_t)G.ny;
+  // the four taps of a cell's face at x: bit dy + 2*dz of `known` and of `inside`
+  auto face = [&](size_t L, unsigned &known, unsigned &inside) {
+    known = inside = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const uint2 t = pa[L + (k & 1 ? sy : 0) + (k & 2 ? sz : 0)];
+      const bool ok = (int)t.x >= min_weight;
+      known |= (ok ? 1u : 0u) << k;
+      inside |= (ok && (float)(int)t.y / (float)(int)t.x <= 0.0f ? 1u : 0u) << k;
+    }
+  };
+  unsigned byte = 0u, k_lo = 0u, i_lo = 0u;
+  bool have = false;
+  int cx = 0, cy = 0, cz = 0;
+  for (int j = 0; j < kCellsPerLane; ++j) {
+    const size_t Lc = first + j;
+    if (Lc >= n_cells) break;
+    if (j == 0) {
+      const size_t row = Lc / (size_t)ncx;
+      cx = (int)(Lc - row * (size_t)ncx);
+      cz = (int)(row / (size_t)ncy);
+      cy = (int)(row - (size_t)cz * (size_t)ncy);
+    } else if (++cx == ncx) {  // the row ends: the next cell shares no face with this one
+      cx = 0, have = false;
+      if (++cy == ncy) cy = 0, ++cz;
+    }
+    const size_t L = ((size_t)cz * (size_t)G.ny + (size_t)cy) * (size_t)G.nx + (size_t)cx;  // corner 0; cx + 1 <= nx - 1 and alike
+    if (!have) face(L, k_lo, i_lo);
+    unsigned k_hi, i_hi;
+    face(L + 1, k_hi, i_hi);
+    const unsigned in = i_lo | (i_hi << 4);
+    const bool active = k_lo == 15u && k_hi == 15u && in != 0u && in != 255u;
+    byte |= (active ? 1u : 0u) << j;
+    k_lo = k_hi, i_lo = i_hi, have = true;
+  }
+  // eight lanes' bytes are one word
+  unsigned long long m = (unsigned long long)byte << (8 * (threadIdx.x & 7));
+#pragma unroll
+  for (int o = 1; o < 8; o <<= 1) m |= __shfl_xor(m, o, 64);
+  const bool writer = (threadIdx.x & 7) == 0;
+  unsigned total = 0u;
+  const unsigned ex = rules::block_exclusive_scan<kWaves>(writer ? (unsigned)__popcll(m) : 0u, &total);
+  if (writer) {
+    const size_t w = (size_t)blockIdx.x * kWordsPerTile + (threadIdx.x >> 3);
+    word[w] = m, word_offset[w] = ex;
+  }
+  if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+// the faces of a lane's voxels; *open: the crossings that yield none
+__device__ __forceinline__ unsigned lane_faces(const uint2 *__restrict__ pa, const uint2 *__restrict__ pb, const Geom &G, const Cells &C,
+                                               int min_weight, size_t first, size_t n_vox, unsigned *open) {
+  unsigned faces = 0u, none = 0u;
+  for (int j = 0; j < kVoxelsPerLane; ++j) {
+    const size_t L = first + j;
+    if (L >= n_vox) break;
+    int ix, iy, iz;
+    voxel_of(G, L, ix, iy, iz);
+    const int found = crossings(pa, pb, G, min_weight, L, ix, iy, iz, [](int, float, float, size_t) {});
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (!((found >> a) & 1)) continue;
+      size_t q[4];
+      if (quad_cells(C, a, ix, iy, iz, q))
+        ++faces;
+      else
+        ++none;
+    }
+  }
+  *open = none;
+  return faces;
+}
+
+__global__ void __launch_bounds__(kBlock) k_mesh_edges(const uint2 *__restrict__ pa, const uint2 *__restrict__ pb, Geom G, Cells C,
+                                                       int min_weight, size_t n_vox, unsigned long long *__restrict__ tile_sums,
+                                                       unsigned *__restrict__ open_edges) {
+  const size_t first = (size_t)blockIdx.x * kTile + (size_t)threadIdx.x * kVoxelsPerLane;
+  unsigned open = 0u;
+  const unsigned faces = lane_faces(pa, pb, G, C, min_weight, first, n_vox, &open);
+  unsigned total = 0u, total_open = 0u;
+  (void)rules::block_exclusive_scan<kWaves>(faces, &total);
+  (void)rules::block_exclusive_scan<kWaves>(open, &total_open);
+  if (threadIdx.x == 0) {
+    tile_sums[blockIdx.x] = total;
+    if (total_open) atomicAdd(open_edges, total_open);
+  }
+}
+
+// one block: grand[0] = the vertices, grand[1] = the faces (quads)
+__global__ void __launch_bounds__(kBlock) k_mesh_scan(unsigned long long *__restrict__ cell_sums, unsigned n_cell_tiles,
+                                                      unsigned long long *__restrict__ face_sums, unsigned n_voxel_tiles,
+                                                      unsigned long long *__restrict__ grand) {
+  scan_tile_sums(cell_sums, n_cell_tiles, grand);
+  scan_tile_sums(face_sums, n_voxel_tiles, grand + 1);
+}
+
+// counts[0]: uncoloured, counts[1]: flat
+__global__ void __launch_bounds__(kBlock) k_mesh_vertices(const uint2 *__restrict__ pa, const uint2 *__restrict__ pb, Geom G, Cells C,
+                                                          dvo_amd_point *__restrict__ out, float *__restrict__ normals,
+                                                          unsigned long long capacity, unsigned *__restrict__ counts) {
+  __shared__ unsigned s_cnt[kWaves][2];
+  const size_t w = (size_t)blockIdx.x * kWordsPerTile + (threadIdx.x >> 3);
+  const unsigned long long m = C.word[w];
+  const int shift = 8 * (threadIdx.x & 7);
+  unsigned byte = (unsigned)(m >> shift) & 255u;
+  unsigned long long at = C.tile_offset[blockIdx.x] + C.word_offset[w] + (unsigned)__popcll(m & ((1ull << shift) - 1ull));
+  const size_t first = (size_t)blockIdx.x * kCellTile + (size_t)threadIdx.x * kCellsPerLane;
+  const size_t stride[3] = {1, (size_t)G.nx, (size_t)G.nx * (size_t)G.ny};
+  unsigned unc = 0u, flat = 0u;
+  while (byte) {
+    const int j = __ffs(byte) - 1;
+    byte &= byte - 1u;
+    const size_t Lc = first + j;  // (< cells: a bit beyond them is never set)
+    const size_t row = Lc / (size_t)C.nx;
+    int cc[3];
+    cc[0] = (int)(Lc - row * (size_t)C.nx);
+    cc[2] = (int)(row / (size_t)C.ny);
+    cc[1] = (int)(row - (size_t)cc[2] * (size_t)C.ny);
+    const size_t L = ((size_t)cc[2] * (size_t)G.ny + (size_t)cc[1]) * (size_t)G.nx + (size_t)cc[0];
+    float Fk[8], Gk[8];
+    bool col[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const size_t Lk = L + (k & 1 ? stride[0] : 0) + (k & 2 ? stride[1] : 0) + (k & 4 ? stride[2] : 0);
+      const uint2 ta = pa[Lk], tb = pb[Lk];
+      Fk[k] = (float)(int)ta.y / (float)(int)ta.x;  // (an active cell: every corner has w_sum >= min_weight >= 1)
+      col[k] = (int)tb.x > 0;
+      Gk[k] = (float)(int)tb.y / (float)(int)tb.x;  // (used where col[k])
+    }
+    float S[3] = {0.0f, 0.0f, 0.0f}, grad[3] = {0.0f, 0.0f, 0.0f}, grey_sum = 0.0f;
+    int n_cross = 0, n_grey = 0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const int b = (a + 1) % 3, c = (a + 2) % 3;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int db = e & 1, dc = e >> 1;
+        const int lo = (db << b) | (dc << c), hi = lo | (1 << a);
+        const float Fa = Fk[lo], Fb = Fk[hi];
+        grad[a] = grad[a] + (Fb - Fa);
+        if (!((Fa > 0.0f && Fb <= 0.0f) || (Fa <= 0.0f && Fb > 0.0f))) continue;
+        const float s = Fa / (Fa - Fb);
+        float pt[3];
+        pt[a] = s, pt[b] = (float)db, pt[c] = (float)dc;
+        S[0] = S[0] + pt[0], S[1] = S[1] + pt[1], S[2] = S[2] + pt[2];
+        ++n_cross;
+        if (col[lo] && col[hi]) {
+          grey_sum = grey_sum + (Gk[lo] + s * (Gk[hi] - Gk[lo]));
+          ++n_grey;
+        }
+      }
+    }
+    dvo_amd_point p;
+    const float mf = (float)n_cross;
+    p.x = G.o[0] + ((float)cc[0] + S[0] / mf) * G.voxel;
+    p.y = G.o[1] + ((float)cc[1] + S[1] / mf) * G.voxel;
+    p.z = G.o[2] + ((float)cc[2] + S[2] / mf) * G.voxel;
+    p.rgb = 0u;
+    if (n_grey > 0) {
+      const unsigned grey = (unsigned)(int)fminf(fmaxf(rintf((grey_sum / (float)n_grey) * 0.0625f), 0.0f), 255.0f);
+      p.rgb = (grey << 16) | (grey << 8) | grey;
+    } else {
+      ++unc;
+    }
+    const float len = sqrtf((grad[0] * grad[0] + grad[1] * grad[1]) + grad[2] * grad[2]);
+    float nrm[3] = {0.0f, 0.0f, 0.0f};
+    if (len == 0.0f)
+      ++flat;
+    else
+      nrm[0] = grad[0] / len, nrm[1] = grad[1] / len, nrm[2] = grad[2] / len;
+    if (at < capacity) {  // (the host launches this kernel only with room for every vertex)
+      out[at] = p;
+      if (normals) normals[3 * at] = nrm[0], normals[3 * at + 1] = nrm[1], normals[3 * at + 2] = nrm[2];
+    }
+    ++at;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) unc += __shfl_down(unc, o, 64), flat += __shfl_down(flat, o, 64);
+  if (lane == 0) s_cnt[wave][0] = unc, s_cnt[wave][1] = flat;
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    unsigned sum = 0u;
+#pragma unroll
+    for (int v = 0; v < kWaves; ++v) sum += s_cnt[v][threadIdx.x];
+    if (sum) atomicAdd(counts + threadIdx.x, sum);
+  }
+}
+
+__global__ void __launch_bounds__(kBlock) k_mesh_faces(const uint2 *__restrict__ pa, const uint2 *__restrict__ pb, Geom G, Cells C,
+                                                       int min_weight, size_t n_vox, const unsigned long long *__restrict__ tile_offsets,
+                                                       int *__restrict__ out, unsigned long long capacity) {
+  const size_t first = (size_t)blockIdx.x * kTile + (size_t)threadIdx.x * kVoxelsPerLane;
+  unsigned open = 0u, total = 0u;
+  const unsigned mine = lane_faces(pa, pb, G, C, min_weight, first, n_vox, &open);
+  unsigned long long at = tile_offsets[blockIdx.x] + rules::block_exclusive_scan<kWaves>(mine, &total);  // in faces
+  if (!mine) return;  // (behind the block's last barrier)
+  for (int j = 0; j < kVoxelsPerLane; ++j) {
+    const size_t L = first + j;
+    if (L >= n_vox) break;
+    int ix, iy, iz;
+    voxel_of(G, L, ix, iy, iz);
+    int faces_up = 0;  // bit a: Fb > 0, the surface faces +a
+    const int found = crossings(pa, pb, G, min_weight, L, ix, iy, iz, [&](int a, float, float Fb, size_t) { faces_up |= (Fb > 0.0f ? 1 : 0) << a; });
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      size_t q[4];
+      if (!((found >> a) & 1) || !quad_cells(C, a, ix, iy, iz, q)) continue;
+      const int v0 = cell_rank(C, q[0]), v1 = cell_rank(C, q[1]), v2 = cell_rank(C, q[2]), v3 = cell_rank(C, q[3]);
+      const bool up = (faces_up >> a) & 1;
+      if (2ull * at + 2ull <= capacity) {  // (the host launches this kernel only with room for every triangle)
+        int *t = out + 6ull * at;
+        t[0] = v0, t[1] = up ? v1 : v2, t[2] = up ? v2 : v1;
+        t[3] = v0, t[4] = up ? v2 : v3, t[5] = up ? v3 : v2;
+      }
+      ++at;
+    }
+  }
 }
 
 }  // namespace volume
@@ -983,6 +1285,198 @@ int dvo_amd_volume_extract(dvo_amd_volume *vol, int min_weight, dvo_amd_point *o
   bracket.read(grand > 0ull ? 3 : 2, 2);
   if (counts) counts->points = (long long)grand, counts->uncoloured = (long long)h_unc;
   return DVO_AMD_OK;
+}
+
+int dvo_amd_volume_upload(dvo_amd_volume *vol, const int *box, const dvo_amd_volume_voxel *records, long long n) {
+  static const char *entry = "dvo_amd_volume_upload";
+  if (n < 0) return invalid(entry, "a negative count");
+  if (!vol || !records) return invalid(entry, "a NULL pointer");
+  const int dims[3] = {vol->opt.nx, vol->opt.ny, vol->opt.nz};
+  int b[6] = {0, 0, 0, dims[0] - 1, dims[1] - 1, dims[2] - 1};
+  if (box)
+    for (int a = 0; a < 3; ++a) {
+      if (!(0 <= box[a] && box[a] <= box[3 + a] && box[3 + a] < dims[a])) return invalid(entry, "the box must satisfy 0 <= lo <= hi < n on every axis");
+      b[a] = box[a], b[3 + a] = box[3 + a];
+    }
+  const int3 lo = make_int3(b[0], b[1], b[2]), ext = make_int3(b[3] - b[0] + 1, b[4] - b[1] + 1, b[5] - b[2] + 1);
+  const unsigned long long need = (unsigned long long)ext.x * (unsigned long long)ext.y * (unsigned long long)ext.z;
+  if (n < 0 || (unsigned long long)n != need) return invalid(entry, "n is " + std::to_string(n) + ", the box holds " + std::to_string(need) + " records");
+  if (!vol->keyframes.empty())
+    return invalid(entry, "the volume holds " + std::to_string(vol->keyframes.size()) + " keyframes of the tracked form: remove them or clear first");
+  int rc = have_device();
+  if (rc) return rc;
+  HIP_TRY(hipSetDevice(vol->device));
+  hipStream_t st = nullptr;
+  rc = device_prep_stream(vol->device, &st);
+  if (rc) return rc;
+  const unsigned long long chunk = std::min<unsigned long long>(need, 1ull << 21);  // 32 MiB of records at a time
+  Scratch S;
+  rc = S.take(vol->device, sizeof(uint4) * (size_t)chunk, true);
+  if (rc) return rc;
+  for (unsigned long long first = 0; first < need; first += chunk) {
+    const unsigned count = (unsigned)std::min<unsigned long long>(chunk, need - first);
+    hipError_t e = hipMemcpyAsync(S.mem, records + first, sizeof(uint4) * (size_t)count, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(k_volume_scatter, dim3((count + kBlock - 1) / kBlock), dim3(kBlock), 0, st, vol->a, vol->b, vol->geom, lo, ext, first,
+                         count, (const uint4 *)S.mem);
+      e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(st);  // (the scratch is filled again for the next stretch)
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail_hip("volume upload", e);
+  }
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_volume_mesh(dvo_amd_volume *vol, int min_weight, dvo_amd_point *vertices, float *normals, long long vertex_capacity, int *triangles,
+                        long long triangle_capacity, dvo_amd_volume_mesh_counts *counts) {
+  static const char *entry = "dvo_amd_volume_mesh";
+  if (counts) *counts = dvo_amd_volume_mesh_counts{0, 0, 0, 0, 0};
+  if (min_weight < 1) return invalid(entry, "min_weight must be >= 1");
+  if (vertex_capacity < 0 || (vertex_capacity > 0 && !vertices)) return invalid(entry, "a negative vertex capacity, or a capacity without vertices");
+  if (triangle_capacity < 0 || (triangle_capacity > 0 && !triangles))
+    return invalid(entry, "a negative triangle capacity, or a capacity without triangles");
+  if (!vol || !counts) return invalid(entry, "a NULL pointer");
+  int rc = have_device();
+  if (rc) return rc;
+  const int device = vol->device;
+  HIP_TRY(hipSetDevice(device));
+  hipStream_t st = nullptr;
+  rc = device_prep_stream(device, &st);
+  if (rc) return rc;
+  const Geom &G = vol->geom;
+  Cells C;
+  C.nx = G.nx - 1, C.ny = G.ny - 1, C.nz = G.nz - 1;
+  C.n = (size_t)C.nx * (size_t)C.ny * (size_t)C.nz;
+  const unsigned cell_tiles = (unsigned)((C.n + kCellTile - 1) / kCellTile), voxel_tiles = (unsigned)((vol->n_vox + kTile - 1) / kTile);
+  const size_t n_words = (size_t)cell_tiles * kWordsPerTile;
+  // the scratch: words, their offsets, the two lists of tile totals, then {vertices, faces} and {open, uncoloured, flat}
+  const size_t word_bytes = align_up(sizeof(unsigned long long) * n_words, 256), offset_bytes = align_up(sizeof(unsigned) * n_words, 256);
+  const size_t cell_bytes = align_up(sizeof(unsigned long long) * (size_t)cell_tiles, 256);
+  const size_t face_bytes = align_up(sizeof(unsigned long long) * (size_t)voxel_tiles, 256);
+  Scratch S;
+  rc = S.take(device, word_bytes + offset_bytes + cell_bytes + face_bytes + 256, true);
+  if (rc) return rc;
+  char *base = (char *)S.mem;
+  unsigned long long *d_word = (unsigned long long *)base;
+  unsigned *d_offset = (unsigned *)(base + word_bytes);
+  unsigned long long *d_cell_sums = (unsigned long long *)(base + word_bytes + offset_bytes);
+  unsigned long long *d_face_sums = (unsigned long long *)(base + word_bytes + offset_bytes + cell_bytes);
+  unsigned long long *d_grand = (unsigned long long *)(base + word_bytes + offset_bytes + cell_bytes + face_bytes);
+  unsigned *d_cnt = (unsigned *)(d_grand + 2);  // open, uncoloured, flat
+  C.word = d_word, C.word_offset = d_offset, C.tile_offset = d_cell_sums;
+  const uint2 *pa = vol->a, *pb = vol->b;
+  Bracket bracket(g_timing[device]);
+  unsigned long long grand[2] = {0ull, 0ull};
+  unsigned h_cnt[3] = {0u, 0u, 0u};
+  hipError_t e = hipMemsetAsync(d_grand, 0, 256, st);
+  if (e == hipSuccess) e = bracket.begin(st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mesh_cells, dim3(cell_tiles), dim3(kBlock), 0, st, pa, G, min_weight, C.n, d_word, d_offset, d_cell_sums);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mesh_edges, dim3(voxel_tiles), dim3(kBlock), 0, st, pa, pb, G, C, min_weight, vol->n_vox, d_face_sums, d_cnt);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_mesh_scan, dim3(1), dim3(kBlock), 0, st, d_cell_sums, cell_tiles, d_face_sums, voxel_tiles, d_grand);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(grand, d_grand, sizeof(grand), hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, sizeof(unsigned), hipMemcpyDeviceToHost, st);
+  hipError_t es = hipStreamSynchronize(st);  // the totals decide whether anything is written
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail_hip("volume mesh (count)", e);
+  const unsigned long long n_vertices = grand[0], n_triangles = 2ull * grand[1];
+  counts->vertices = (long long)n_vertices, counts->triangles = (long long)n_triangles, counts->open_edges = (long long)h_cnt[0];
+  if ((unsigned long long)vertex_capacity < n_vertices || (unsigned long long)triangle_capacity < n_triangles) {
+    if (bracket.timed) (void)bracket.end(st), (void)hipStreamSynchronize(st);
+    bracket.read(3, 1);
+    return DVO_AMD_ERR_CAPACITY;
+  }
+  Scratch P;
+  int launches = 3;
+  const size_t vertex_bytes = align_up(sizeof(dvo_amd_point) * (size_t)n_vertices, 256);
+  const size_t normal_bytes = normals ? align_up(3 * sizeof(float) * (size_t)n_vertices, 256) : 0;
+  const size_t triangle_bytes = align_up(3 * sizeof(int) * (size_t)n_triangles, 256);
+  dvo_amd_point *d_vertices = nullptr;
+  float *d_normals = nullptr;
+  int *d_triangles = nullptr;
+  if (n_vertices > 0ull) {  // (no vertex: no face either)
+    rc = P.take(device, vertex_bytes + normal_bytes + triangle_bytes, true);
+    if (rc) return rc;
+    d_vertices = (dvo_amd_point *)P.mem;
+    if (normals) d_normals = (float *)((char *)P.mem + vertex_bytes);
+    d_triangles = (int *)((char *)P.mem + vertex_bytes + normal_bytes);
+    hipLaunchKernelGGL(k_mesh_vertices, dim3(cell_tiles), dim3(kBlock), 0, st, pa, pb, G, C, d_vertices, d_normals, n_vertices, d_cnt + 1);
+    e = hipGetLastError();
+    launches = 4;
+    if (e == hipSuccess && n_triangles > 0ull) {
+      hipLaunchKernelGGL(k_mesh_faces, dim3(voxel_tiles), dim3(kBlock), 0, st, pa, pb, G, C, min_weight, vol->n_vox,
+                         (const unsigned long long *)d_face_sums, d_triangles, n_triangles);
+      e = hipGetLastError();
+      launches = 5;
+    }
+  }
+  if (e == hipSuccess) e = bracket.end(st);
+  if (e == hipSuccess && n_vertices > 0ull) e = hipMemcpyAsync(vertices, d_vertices, sizeof(dvo_amd_point) * (size_t)n_vertices, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && n_vertices > 0ull && normals)
+    e = hipMemcpyAsync(normals, d_normals, 3 * sizeof(float) * (size_t)n_vertices, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && n_triangles > 0ull) e = hipMemcpyAsync(triangles, d_triangles, 3 * sizeof(int) * (size_t)n_triangles, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(h_cnt, d_cnt, sizeof(h_cnt), hipMemcpyDeviceToHost, st);
+  es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail_hip("volume mesh (write)", e);
+  bracket.read(launches, 2);
+  counts->uncoloured = (long long)h_cnt[1], counts->flat = (long long)h_cnt[2];
+  return DVO_AMD_OK;
+}
+
+int dvo_amd_write_ply(const char *path, const dvo_amd_point *vertices, const float *normals, long long n_vertices, const int *triangles,
+                      long long n_triangles) {
+  static const char *entry = "dvo_amd_write_ply";
+  if (!path || (n_vertices > 0 && !vertices) || (n_triangles > 0 && !triangles)) return invalid(entry, "a NULL pointer");
+  if (n_vertices < 0 || n_triangles < 0) return invalid(entry, "a negative count");
+  for (long long i = 0; i < 3 * n_triangles; ++i)
+    if (triangles[i] < 0 || triangles[i] >= n_vertices)
+      return invalid(entry, "triangle " + std::to_string(i / 3) + " names vertex " + std::to_string(triangles[i]) + " of " + std::to_string(n_vertices));
+  std::FILE *f = std::fopen(path, "wb");
+  if (!f) return DVO_AMD_ERR_IO;
+  bool ok = std::fprintf(f,
+                         "ply\nformat binary_little_endian 1.0\ncomment dvo_amd_volume_mesh\nelement vertex %lld\n"
+                         "property float x\nproperty float y\nproperty float z\n%s"
+                         "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+                         "element face %lld\nproperty list uchar int vertex_indices\nend_header\n",
+                         n_vertices, normals ? "property float nx\nproperty float ny\nproperty float nz\n" : "", n_triangles) > 0;
+  // records are packed by hand: 15 or 27 bytes a vertex, 13 a face (the values are little-endian as the host is)
+  std::vector<unsigned char> rows;
+  const size_t vertex_size = normals ? 27 : 15;
+  const long long batch = 1 << 14;
+  for (long long at = 0; ok && at < n_vertices; at += batch) {
+    const size_t k = (size_t)std::min<long long>(batch, n_vertices - at);
+    rows.resize(k * vertex_size);
+    unsigned char *w = rows.data();
+    for (size_t i = 0; i < k; ++i) {
+      const dvo_amd_point &p = vertices[at + (long long)i];
+      std::memcpy(w, &p.x, 12), w += 12;
+      if (normals) std::memcpy(w, normals + 3 * (at + (long long)i), 12), w += 12;
+      *w++ = (unsigned char)(p.rgb >> 16), *w++ = (unsigned char)(p.rgb >> 8), *w++ = (unsigned char)p.rgb;
+    }
+    ok = std::fwrite(rows.data(), vertex_size, k, f) == k;
+  }
+  for (long long at = 0; ok && at < n_triangles; at += batch) {
+    const size_t k = (size_t)std::min<long long>(batch, n_triangles - at);
+    rows.resize(k * 13);
+    unsigned char *w = rows.data();
+    for (size_t i = 0; i < k; ++i) {
+      *w++ = 3;
+      std::memcpy(w, triangles + 3 * (at + (long long)i), 12), w += 12;
+    }
+    ok = std::fwrite(rows.data(), 13, k, f) == k;
+  }
+  ok = (std::fclose(f) == 0) && ok;
+  return ok ? DVO_AMD_OK : DVO_AMD_ERR_IO;
 }
 
 int dvo_amd_debug_volume_timing(int device, int enable, int *launches, int *synchronisations, double *last_ms) {

@@ -205,3 +205,17 @@ def write_pcd(path: str, xyz, rgb, normals=None):
                     "dvo_amd_write_pcd_normals")
         return
     capi._check(_lib().dvo_amd_write_pcd(os.fsencode(path), pts.ctypes.data, len(pts), width, height), "dvo_amd_write_pcd")
+
+
+def write_ply(path: str, xyz, rgb, triangles, normals=None):
+    """Binary little-endian PLY of an indexed triangle mesh (dvo_amd_write_ply): vertices xyz [V, 3] with packed rgb [V] and,
+    when given, normals [V, 3]; triangles int32 [T, 3] -- what SurfaceVolume.mesh() returns."""
+    pts = capi._pack_points(xyz, rgb)
+    tri = np.ascontiguousarray(np.asarray(triangles, dtype=np.int32).reshape(-1, 3))
+    nrm = None
+    if normals is not None:
+        nrm = np.ascontiguousarray(np.asarray(normals, dtype=np.float32).reshape(-1, 3))
+        if len(nrm) != len(pts):
+            raise ValueError("xyz and normals must hold the same number of vertices")
+    capi._check(_lib().dvo_amd_write_ply(os.fsencode(path), pts.ctypes.data, None if nrm is None else capi._fp(nrm), len(pts),
+                                         tri.ctypes.data_as(C.POINTER(C.c_int)), len(tri)), "dvo_amd_write_ply")

@@ -1804,6 +1804,50 @@ int dvo_amd_pyramid_warp_forward_many(int n, const dvo_amd_pyramid *const *movin
  * iw_sum > 0 on both voxels grey = (int)fminf(fmaxf(rintf((Ga + s*(Gb - Ga))*0.0625f), 0.0f), 255.0f), packed B = G = R; otherwise
  * rgb = 0 and the point counts as uncoloured.  Points come in ascending 3*L + a.  Capacity as in dvo_amd_map_extract:
  * DVO_AMD_ERR_CAPACITY with *n_out the size needed and out untouched.  The result goes straight into dvo_amd_write_pcd.
+ *
+ * The mesh.  dvo_amd_volume_mesh writes the same surface as an indexed triangle mesh by naive surface nets: one vertex per cell
+ * the surface runs through, one quad (two triangles) per crossing edge, i.e. per point of dvo_amd_volume_extract.  All arithmetic
+ * fp32, every operation rounded on its own (no contraction), divisions and the square root correctly rounded.
+ *  Cells.  Cell C = (cx,cy,cz), 0 <= c_a <= n_a - 2, index Lc = (cz*(ny-1) + cy)*(nx-1) + cx; its corner k = dx + 2*dy + 4*dz is
+ *   voxel (cx+dx, cy+dy, cz+dz).  A cell is KNOWN iff all eight corners have w_sum >= min_weight (>= 1).  F_k = (float)sd_sum /
+ *   (float)w_sum (the raycast's step 5); corner k is INSIDE iff F_k <= 0, so the two corners of an edge differ in this exactly
+ *   when dvo_amd_volume_extract sees a crossing there.  A cell is ACTIVE iff it is known and its corners are neither all inside
+ *   nor all outside.  Vertices: one per active cell in ascending Lc; a vertex's index is its rank in that order.
+ *  Edges.  The twelve edges of a cell are walked in the order e = 4*a + j: axis a = 0,1,2, the other two axes (b,c) = (1,2), (2,0),
+ *   (0,1) (cyclic), j = db + 2*dc; the edge runs from corner lo (offset 0 along a, db along b, dc along c) to corner hi (offset 1
+ *   along a, the same along b and c); Fa = F_lo, Fb = F_hi; it crosses iff (Fa > 0 && Fb <= 0) || (Fa <= 0 && Fb > 0).
+ *  Position.  Over the crossing edges in order e: s = Fa/(Fa - Fb); the crossing's local point is s along a, (float)db along b,
+ *   (float)dc along c; three sums S_x, S_y, S_z start at 0 and add the local points one after the other; m = the number of
+ *   crossings (>= 3 in an active cell); p_a = S_a/(float)m; the coordinate is origin[a] + ((float)c_a + p_a)*voxel.
+ *  Colour.  Over the crossing edges whose two voxels both have iw_sum > 0, in order e: g = Ga + s*(Gb - Ga) with
+ *   Gv = (float)i_sum/(float)iw_sum, added one after the other to a sum that starts at 0; mc of them.  mc > 0:
+ *   grey = (int)fminf(fmaxf(rintf((sum/(float)mc)*0.0625f), 0.0f), 255.0f), packed B = G = R; otherwise rgb = 0 and the vertex
+ *   counts as uncoloured.
+ *  Normal (normals may be NULL; 3 floats per vertex): the gradient of F over the cell.  G_a starts at 0 and adds (Fb - Fa) of the
+ *   axis's four edges in order j, crossing or not; len = sqrtf((G_x*G_x + G_y*G_y) + G_z*G_z); n = (G_x/len, G_y/len, G_z/len);
+ *   len == 0 (a 3-D checkerboard of signs): n = (0,0,0) and the vertex counts as flat.  F is positive in front of the surface,
+ *   so the normal points out of the solid, towards where the cameras were.
+ *  Faces.  Over dvo_amd_volume_extract's candidates (L, a) that cross, in ascending 3*L + a, voxel (ix,iy,iz), (b,c) as above: the
+ *   four cells around the edge have i_a along a and (i_b-1, i_c-1), (i_b, i_c-1), (i_b, i_c), (i_b-1, i_c) along (b,c): q0..q3,
+ *   counter-clockwise seen from +a.  If one of them does not exist or is not known the edge yields no face and counts as open;
+ *   otherwise two triangles on the diagonal q0-q2: (q0,q1,q2), (q0,q2,q3) when Fb > 0 (the surface faces +a), else (q0,q2,q1),
+ *   (q0,q3,q2).  Triangles are int vertex indices, three each, in that order.  (A known cell around a crossing edge is active.)
+ *  So triangles/2 + open_edges == the points of dvo_amd_volume_extract for the same min_weight, and a closed surface inside the
+ *  known region comes out closed, consistently oriented (counter-clockwise seen from outside) with normals on the faces' side.
+ *  What the rule does not promise: where two solids touch along an edge or at a corner the mesh is not manifold there (surface
+ *  nets' known ambiguity: one vertex serves both sheets); an active cell at the rim of the known region has a vertex that no face
+ *  may use; a quad is split on a fixed diagonal, whatever its shape.
+ * counts (never NULL) receives {vertices, triangles, open_edges, uncoloured, flat}.  Capacities are in vertices and in triangles:
+ * if either is too small the call returns DVO_AMD_ERR_CAPACITY with counts->vertices, ->triangles and ->open_edges set (the other
+ * two 0) and no array touched.  Three launches and one synchronisation find the sizes, two launches and a second synchronisation
+ * write (one launch when there is no face, none when there is no vertex), whatever the volume holds.  Nothing is kept per cell but
+ * one bit; there is no floating-point atomic.  Argument errors as above: a NULL volume or counts, min_weight < 1, a negative
+ * capacity, a capacity without its array.
+ *
+ * dvo_amd_volume_upload is the inverse of dvo_amd_volume_download: it overwrites the records of the box (NULL: the whole volume)
+ * with n records in the order of L; n must be the number of voxels of the box.  It saves and restores a volume, and places crafted
+ * records.  While the tracked form holds keyframes it returns DVO_AMD_ERR_INVALID_ARGUMENT, because their contract (above)
+ * would no longer hold: remove them or clear first.
  */
 #define DVO_AMD_VOLUME_WEIGHT_CONSTANT 0
 #define DVO_AMD_VOLUME_WEIGHT_SENSOR 1
@@ -1840,6 +1884,10 @@ typedef struct {
   long long points, uncoloured;
 } dvo_amd_volume_extract_counts;
 
+typedef struct {
+  long long vertices, triangles, open_edges, uncoloured, flat;
+} dvo_amd_volume_mesh_counts;
+
 typedef struct dvo_amd_volume dvo_amd_volume;
 /* 64 x 64 x 64 voxels of 0.05 m, origin (-1.6, -1.6, 0.4), trunc 0.15, near_z 0.4, far_z 5, sensor weights */
 void dvo_amd_default_volume_options(dvo_amd_volume_options *opt);
@@ -1869,6 +1917,18 @@ int dvo_amd_volume_raycast_pyramid(dvo_amd_volume *vol, const double *pose, cons
                                    dvo_amd_volume_raycast_stats *stats);
 int dvo_amd_volume_extract(dvo_amd_volume *vol, int min_weight, dvo_amd_point *out, long long capacity, long long *n_out,
                            dvo_amd_volume_extract_counts *counts);
+/* vertices: vertex_capacity records; normals: NULL or 3 floats per vertex; triangles: 3 ints per triangle; host memory */
+int dvo_amd_volume_mesh(dvo_amd_volume *vol, int min_weight, dvo_amd_point *vertices, float *normals, long long vertex_capacity, int *triangles,
+                        long long triangle_capacity, dvo_amd_volume_mesh_counts *counts);
+/* box: as in dvo_amd_volume_download; n: the number of voxels of the box */
+int dvo_amd_volume_upload(dvo_amd_volume *vol, const int *box, const dvo_amd_volume_voxel *records, long long n);
+
+/* PLY, format binary_little_endian 1.0: element vertex with float x y z, with normals float nx ny nz (3 floats per vertex, as
+ * dvo_amd_volume_mesh writes them), uchar red green blue (from the packed rgb); element face with `list uchar int vertex_indices`,
+ * three indices each.  DVO_AMD_ERR_INVALID_ARGUMENT: a NULL path or array, a negative count, an index outside 0..n_vertices-1.
+ * Host code only. */
+int dvo_amd_write_ply(const char *path, const dvo_amd_point *vertices, const float *normals, long long n_vertices, const int *triangles,
+                      long long n_triangles);
 
 /* Binary PCD v0.7 as pcl::io::savePCDFileBinary writes a PointXYZRGB cloud: FIELDS x y z rgb, SIZE 4 4 4 4, TYPE F F F F
  * (rgb holds the packed bits), COUNT 1 1 1 1, WIDTH / HEIGHT as given (organized, or n x 1), VIEWPOINT 0 0 0 1 0 0 0,

@@ -556,6 +556,37 @@ class SurfaceVolume {
     return out;
   }
 
+  // the surface as an indexed triangle mesh (dvo_amd_volume_mesh: surface nets, one vertex per active cell, two triangles per
+  // crossing edge whose four cells are known); normals: 3 floats per vertex, triangles: 3 vertex indices each
+  struct Mesh {
+    std::vector<dvo_amd_point> vertices;
+    std::vector<float> normals;
+    std::vector<int> triangles;
+    dvo_amd_volume_mesh_counts counts;
+  };
+  void extractMesh(Mesh &out, int min_weight = 1, bool with_normals = true) {
+    int rc = dvo_amd_volume_mesh(volume_, min_weight, nullptr, nullptr, 0, nullptr, 0, &out.counts);
+    if (rc == DVO_AMD_ERR_CAPACITY) {
+      out.vertices.resize((size_t)out.counts.vertices), out.triangles.resize(3 * (size_t)out.counts.triangles);
+      out.normals.resize(with_normals ? 3 * (size_t)out.counts.vertices : 0);
+      rc = dvo_amd_volume_mesh(volume_, min_weight, out.vertices.data(), with_normals ? out.normals.data() : nullptr,
+                               (long long)out.vertices.size(), out.triangles.data(), (long long)(out.triangles.size() / 3), &out.counts);
+    }
+    ::dvo::detail::check(rc, "SurfaceVolume::extractMesh");
+    out.vertices.resize((size_t)out.counts.vertices), out.triangles.resize(3 * (size_t)out.counts.triangles);
+    out.normals.resize(with_normals ? 3 * (size_t)out.counts.vertices : 0);
+  }
+  // a mesh as a binary little-endian PLY file (dvo_amd_write_ply), with normals when the mesh holds them
+  static void writePly(const std::string &path, const Mesh &mesh) {
+    ::dvo::detail::check(dvo_amd_write_ply(path.c_str(), mesh.vertices.data(), mesh.normals.empty() ? nullptr : mesh.normals.data(),
+                                           (long long)mesh.vertices.size(), mesh.triangles.data(), (long long)(mesh.triangles.size() / 3)),
+                         "SurfaceVolume::writePly");
+  }
+  // the inverse of download(): the records of the box (null: the whole volume) are overwritten; refused while keyframes are held
+  void upload(const std::vector<dvo_amd_volume_voxel> &records, const int *box = nullptr) {
+    ::dvo::detail::check(dvo_amd_volume_upload(volume_, box, records.data(), (long long)records.size()), "SurfaceVolume::upload");
+  }
+
   dvo_amd_volume *handle() const { return volume_; }
 
  private:
